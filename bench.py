@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- bundle-adjustment throughput on MI355X (metric of BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Both forms run N ranks, one device each: started plain with N > 1 the script starts torch.distributed.run on itself (ensure_ranks), it refuses when
 fewer than N devices are visible or when --gpus contradicts the launcher's WORLD_SIZE, and the line's `n_gpus` is the rank count RCCL itself reports for the
-library's own communicator (rccl_rank_count).  Every number of the line -- headline, extra_workloads, cfg4, sharded.* -- carries `parity_ok` against the
-oracle's stored result for its problem (tests/golden/oracle_final_costs.json).
+library's own communicator (rccl_rank_count).
+
+A plain run sets up, warms up, times the K steps, writes what the last timed step computed when --dump-outputs is given (dump_outputs) and
+prints the headline line.  Everything else moves behind --full: the event-bracketed per-kernel profile and the roofline (with the live
+rocprofv3 traffic passes), the CPU baseline, the library default (AUTO) and inexact-Newton variants, the other BASELINE configurations, at
+N > 1 cfg4 and the sharded extras -- and `parity_ok` against the oracle's stored result for its problem (tests/golden/oracle_final_costs.json)
+beside every number of the line.
 
 A "step" is one full pass of the hot path over one batch of synthetic input: one complete
 adjustBundle()-equivalent solve (ceres::Solve semantics, reference options BA.cpp:171-177 except the
@@ -19,11 +24,11 @@ is quoted on: synthetic 200 cams / 100k pts / 1M obs, fp32 Jacobian blocks + fp6
 seeded generator of sfm-toy-library_amd/synthetic.py.  With N > 1 every rank solves an independent
 problem of that size (different seed): the reference has no exchange step between independent
 reconstructions, so there is no data-path collective and scaling is "weak".
-The same invocation then ALSO runs the path that does have an exchange step -- ONE problem (cfg 3, then the
+With --full the same invocation ALSO runs the path that does have an exchange step -- ONE problem (cfg 3, then the
 1000-camera cfg 5) with its points sharded over the N ranks and the reduced camera system all-reduced over
 RCCL / xGMI once per LM iteration (sfmba_problem_solve_sharded, strong scaling) -- and reports it in the
 "sharded" object of the same JSON line (--sharded-extras 0 turns that off; at N = 1 it is off unless asked for).
-BASELINE config 4 as written (the 200-camera problem as 8 independent sub-problems of 25 cams / 12.5k pts / 125k obs) is timed too: at N > 1 as
+With --full BASELINE config 4 as written (the 200-camera problem as 8 independent sub-problems of 25 cams / 12.5k pts / 125k obs) is timed too: at N > 1 as
 `cfg4_replicas` (rank g solves sub-problem g), at N = 1 as `extra_workloads.cfg4_8_concurrent` (the eight on eight streams of the one GPU).
 
 value = LM iterations (successful + unsuccessful) of all ranks / max-over-ranks wall time.
@@ -62,23 +67,31 @@ def parse():
                     help="N > 1: 'independent' = one whole problem per GPU (weak scaling, no data-path collective; the default the "
                          "driver runs); 'sharded' = ONE problem with its points sharded over the ranks and the reduced camera "
                          "system all-reduced over RCCL every LM iteration (strong scaling; BASELINE config 5 is quoted this way)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline also run everything else the benchmark measures or checks: per-kernel profile and roofline "
+                         "(live rocprofv3 traffic passes), CPU baseline, AUTO and inexact-Newton variants, the other BASELINE configurations, "
+                         "cfg4 and the sharded extras at N > 1, parity against the oracle's stored results.  Off by default: a plain run "
+                         "only sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (solved cameras, points, focal length, summary, "
+                         "per-iteration trace) as DIR/<name>.npy in float64 (dump_outputs)")
     ap.add_argument("--sharded-extras", type=int, default=-1,
                     help="after the headline run also time ONE problem sharded over all ranks (cfg3 and cfg5) with the RCCL all-reduce "
-                         "of the reduced camera system: 1 = yes, 0 = no, -1 (default) = only when N > 1")
+                         "of the reduced camera system: 1 = yes, 0 = no, -1 (default) = only with --full and N > 1")
     ap.add_argument("--distributed-cg", action="store_true", help="--mode sharded: the CG without the redundant solve (reduce-scatter + one small all-reduce per CG iteration)")
     ap.add_argument("--implicit-cg", action="store_true", help="--mode sharded: the CG with the product formed implicitly from every rank's own points (no exchange of the reduced matrix at all)")
     ap.add_argument("--row-sharded", action="store_true", help="--mode sharded: block ROWS of the reduced matrix per rank (every rank holds the whole problem; per-point table all-gathered; "
                                                               "multi-workgroup distributed CG on the owned rows)")
     ap.add_argument("--extra-workloads", type=int, default=-1,
                     help="after the timed region also run the other BASELINE configurations (cfg 2 in fp64 with the reference's solver, cfg 3 in all-fp64, cfg3_banded, cfg 5) and hold "
-                         "each to the oracle's stored final cost: 1 = yes, 0 = no, -1 (default) = at N = 1 in the driver's plain invocation (default workload and solver, "
-                         "CPU baseline not switched off: the tool runs under rocprofv3 stay lean)")
+                         "each to the oracle's stored final cost: 1 = yes, 0 = no, -1 (default) = at N = 1 in a --full run of the default workload and solver "
+                         "with the CPU baseline not switched off (the tool runs under rocprofv3 stay lean)")
     ap.add_argument("--extras-timeout", type=int, default=420, help="seconds after which the sharded extras are abandoned (the headline line is printed regardless)")
     ap.add_argument("--opt", action="append", default=[], metavar="FIELD=VALUE",
                     help="set a field of sfmba_options for the headline solve (A/B runs: --opt pcg_symmetric=-1); may be repeated")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not spawn the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic live; the committed "
+                    help="--full: do not spawn the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic live; the committed "
                          "profiles/*_pmc_traffic.txt summary is used instead")
     ap.add_argument("--cpu-iters", type=int, default=0, help="LM iterations of the CPU sample (0 = auto)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="OpenMP threads of the CPU sample (0 = swept upwards from 16 while it still gets faster; "
@@ -91,6 +104,32 @@ def emit(obj):
     pipe separately -- two ranks' lines then come out glued together now and then."""
     sys.stdout.write(json.dumps(obj) + "\n")
     sys.stdout.flush()
+
+
+SUMMARY_FIELDS = ("termination", "iterations", "successful_steps", "unsuccessful_steps", "residual_evals", "jacobian_evals", "linear_iters",
+                  "initial_cost", "final_cost", "cholesky_fallbacks")
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, cam6, pt3, focal, summ, trace=None):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as out_dir/<name>.npy in float64 --
+    cameras [n_cam, 6] (angle-axis, translation), points [n_pt, 3], focal [1], summary [SUMMARY_FIELDS] and, where the path returns
+    one, trace [LM iterations, the fields of sfmba_iteration].  Wall times are left out: the same inputs give the same files up to
+    the summation-order noise of the atomics.  Points beyond the 64 MB budget are thinned to a fixed seeded sample of rows
+    (point_rows holds their indices)."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"cameras": cam6, "focal": [focal], "summary": [float(summ.get(k, np.nan)) for k in SUMMARY_FIELDS]}
+    pt3 = np.asarray(pt3, dtype=np.float64)
+    room = DUMP_BUDGET_BYTES - (1 << 20)                  # (cameras, summary and trace stay far below 1 MB)
+    if pt3.nbytes > room:
+        keep = np.sort(np.random.default_rng(0).choice(pt3.shape[0], room // 40, replace=False))   # 24 bytes of point + 8 of index, and room to spare
+        out["point_rows"] = keep
+        pt3 = pt3[keep]
+    out["points"] = pt3
+    if trace:
+        out["trace"] = [list(row.values()) for row in trace]
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def ensure_ranks(args):
@@ -325,33 +364,37 @@ def main():
     barrier()
     t0 = time.perf_counter()
     iters = res_evals = jac_evals = lin_iters = 0
-    summ = None
+    summ = trace = None
     for _ in range(args.steps):
         P.reset()
-        summ, _ = P.solve(opt)
+        summ, trace = P.solve(opt)
         iters += summ["iterations"]
         res_evals += summ["residual_evals"]
         jac_evals += summ["jacobian_evals"]
         lin_iters += summ["linear_iters"]
     barrier()
     dt = time.perf_counter() - t0
-    # ---- the same K steps again with every launch bracketed by HIP events on the solver's stream:
-    # per-kernel average launch durations for the roofline object (not part of `value`) ----
-    P.set_profiling(True)
-    t1 = time.perf_counter()
-    lin_iters_prof = 0
-    for _ in range(args.steps):
-        P.reset()
-        sp, _ = P.solve(opt)
-        lin_iters_prof += sp["linear_iters"]
-    barrier()
-    dt_prof = time.perf_counter() - t1
-    profile = P.get_profile()
-    P.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *P.get_params(), summ, trace)
+    par = None
+    if args.full:
+        # ---- the same K steps again with every launch bracketed by HIP events on the solver's stream:
+        # per-kernel average launch durations for the roofline object (not part of `value`) ----
+        P.set_profiling(True)
+        t1 = time.perf_counter()
+        lin_iters_prof = 0
+        for _ in range(args.steps):
+            P.reset()
+            sp, _ = P.solve(opt)
+            lin_iters_prof += sp["linear_iters"]
+        barrier()
+        dt_prof = time.perf_counter() - t1
+        profile = P.get_profile()
+        P.set_profiling(False)
+        # every rank's own result against the oracle's stored one for ITS problem (rank g of N > 1 solves make_problem(workload, sub=g))
+        par = parity_vs_oracle(summ, prob.n_obs, args.workload if sub is None else "%s.%d" % (args.workload, sub))
 
-    # every rank's own result against the oracle's stored one for ITS problem (rank g of N > 1 solves make_problem(workload, sub=g))
-    par = parity_vs_oracle(summ, prob.n_obs, args.workload if sub is None else "%s.%d" % (args.workload, sub))
-    tot = torch.tensor([float(iters), float(res_evals + jac_evals), dt, 0.0 if par["parity_ok"] is False else 1.0], dtype=torch.float64, device="cuda")
+    tot = torch.tensor([float(iters), float(res_evals + jac_evals), dt, 0.0 if par and par["parity_ok"] is False else 1.0], dtype=torch.float64, device="cuda")
     if dist is not None:
         tmax, tmin = tot[2:3].clone(), tot[3:4].clone()
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -392,9 +435,11 @@ def main():
             "final_rms_px": rms,
             "final_cost": summ["final_cost"],
             "termination": summ["termination_name"],
-            # every rank's result against the oracle's stored one for its own problem (None: nothing stored for this workload)
-            "parity_ok": None if par["parity_ok"] is None else bool(g_par == 1.0), "parity_rank0": par,
         }
+    if rank == 0 and args.full:
+        # every rank's result against the oracle's stored one for its own problem (None: nothing stored for this workload)
+        line["parity_ok"] = None if par["parity_ok"] is None else bool(g_par == 1.0)
+        line["parity_rank0"] = par
         # fraction of the HBM roofline of the whole LM iteration (algorithmic bytes of SURVEY 8d)
         n_lin = 1 if linear == 0 else max(1.0, lin_iters / max(iters, 1))
         b_iter = algorithmic_bytes_per_iteration(n_obs, n_pt, n_cam, s_o, n_lin)
@@ -428,7 +473,7 @@ def main():
                                         for k, v in profile.items()}
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.workload, sub, args, rms)
-    if rank == 0 and linear == 1 and world == 1:
+    if rank == 0 and args.full and linear == 1 and world == 1:
         # the library / shim default (AUTO) on the same resident problem, untimed extra: what a drop-in caller gets without opting in
         o2 = capi.default_options(max_seconds=0.0, precision=precision)
         for _ in range(2):
@@ -446,12 +491,12 @@ def main():
                                        "cg_iterations_per_step": li2 / args.steps, "cholesky_fallbacks": fb2,
                                        "final_cost": s2["final_cost"], "note": "same problem, sfmba_options_default (SFMBA_LINEAR_AUTO)"}
     if rank == 0 and world == 1 and not os.environ.get("SFMBA_BENCH_PMC_CHILD") and \
-            (args.extra_workloads == 1 or (args.extra_workloads == -1 and args.workload == "cfg3" and linear == 1 and precision == 1 and not args.no_cpu_baseline)):
+            (args.extra_workloads == 1 or (args.extra_workloads == -1 and args.full and args.workload == "cfg3" and linear == 1 and precision == 1 and not args.no_cpu_baseline)):
         try:
             line["extra_workloads"] = extra_workloads(args, torch, sfm, capi)
         except Exception as e:                                  # never lose the headline line to the extras
             line["extra_workloads"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if rank == 0 and linear == 1 and world == 1 and args.pcg_tol < 1e-3:
+    if rank == 0 and args.full and linear == 1 and world == 1 and args.pcg_tol < 1e-3:
         # Inexact Newton: the same solver with the CG stopped at 1e-3 relative (Ceres' own default for its iterative Schur solvers is
         # eta = 1e-1, the reference sets eta = 1e-2, BA.cpp:173) -- NOT the headline: the headline keeps the 1e-8 of rounds 1 / 2, which
         # reproduces the exact solve's PARAMETERS to 1e-8.  Reported because it is the time-to-solution optimum at the north_star's bar:
@@ -479,7 +524,7 @@ def main():
     # (the N > 1 RCCL path has only ever run on one rank here) a watchdog prints the headline line as it stands and ends the process ...
     import signal
     import threading
-    want_sharded = args.sharded_extras == 1 or (args.sharded_extras == -1 and world > 1)
+    want_sharded = args.sharded_extras == 1 or (args.sharded_extras == -1 and args.full and world > 1)
     sh = {} if want_sharded else None
     stage = ["the RCCL rank count"]
     watchdog, old_term = None, None
@@ -507,7 +552,7 @@ def main():
             line["n_gpus"] = n_gpus
             line["rccl_check"] = rccl_check
     stage[0] = "cfg4_replicas"
-    if world > 1 and args.workload == "cfg3":
+    if world > 1 and args.full and args.workload == "cfg3":
         # BASELINE config 4 as written: one 25-camera sub-problem per GPU (all ranks take part; rank 0 reports)
         try:
             c4 = cfg4_replicas(args, rank, local_rank, world, torch, dist, sfm, capi)
@@ -716,9 +761,10 @@ def extra_workloads(args, torch, sfm, capi):
     return out
 
 
-def sharded_run(workload, args, rank, local_rank, world, torch, dist, sfm, capi, precision, linear, steps, distributed=False, prob=None):
+def sharded_run(workload, args, rank, local_rank, world, torch, dist, sfm, capi, precision, linear, steps, distributed=False, prob=None, dump_dir=None):
     """ONE problem, points sharded over the ranks; the LM loop runs inside the C library (sfmba_problem_solve_sharded) with
-    ncclAllReduce on the solver's stream (sharded.RcclComm); every rank times the same K solves.  Returns the result dict."""
+    ncclAllReduce on the solver's stream (sharded.RcclComm); every rank times the same K solves.  Returns the result dict.
+    dump_dir: rank 0 writes what its last timed solve computed there (dump_outputs; the points of its own range)."""
     from sfm_toy_library_amd import sharded
     import ctypes as C
     if prob is None:
@@ -747,6 +793,8 @@ def sharded_run(workload, args, rank, local_rank, world, torch, dist, sfm, capi,
             iters += summ["iterations"]
         barrier()
         dt = time.perf_counter() - t0
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, *be.get_params(), summ)
         # one rank: the same loop WITHOUT a communicator (the C loop then issues no collective call; pack / unpack kernels and the rest of
         # the sharded machinery stay) -- separates the loop's own overhead from what RCCL's one-rank all-reduce launches (two fills and a
         # copy per call in the r04_f kernel statistics)
@@ -854,7 +902,7 @@ def sharded_run(workload, args, rank, local_rank, world, torch, dist, sfm, capi,
 def main_sharded(args, rank, local_rank, world, torch, dist, sfm, capi, precision, linear, n_gpus):
     """--mode sharded: the sharded run IS the headline line (strong scaling)."""
     r = sharded_run(args.workload, args, rank, local_rank, world, torch, dist, sfm, capi, precision, linear, steps=args.steps,
-                    distributed=3 if args.row_sharded else 2 if args.implicit_cg else 1 if args.distributed_cg else 0)
+                    distributed=3 if args.row_sharded else 2 if args.implicit_cg else 1 if args.distributed_cg else 0, dump_dir=args.dump_outputs)
     if rank == 0:
         _flush_c_stdio()
         emit({
@@ -901,7 +949,7 @@ def live_pmc_passes(args):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter)
             cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", d, "--",
-                   sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-live-traffic",
+                   sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-live-traffic",
                    "--workload", args.workload, "--linear", args.linear, "--precision", args.precision, "--pcg-tol", repr(args.pcg_tol)]
             proc = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:

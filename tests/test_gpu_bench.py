@@ -1,4 +1,4 @@
-"""bench.py contract (-m gpu): one JSON line with the keys the driver and the judge read, on a small workload."""
+"""bench.py contract (-m gpu): one JSON line with the keys the driver and the judge read, on a small workload -- the plain run and --full."""
 import json
 import os
 import subprocess
@@ -20,7 +20,7 @@ def _run(*extra):
 
 
 def test_bench_line_has_the_contract_keys():
-    d = _run("--cpu-threads", "2")
+    d = _run("--full", "--cpu-threads", "2")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -44,8 +44,30 @@ def test_bench_line_has_the_contract_keys():
 
 
 def test_bench_cholesky_and_f64_modes_run():
-    d = _run("--linear", "cholesky", "--precision", "f64", "--no-cpu-baseline", "--no-live-traffic")
+    d = _run("--full", "--linear", "cholesky", "--precision", "f64", "--no-cpu-baseline", "--no-live-traffic")
     assert d["termination"] == "CONVERGENCE" and "cpu_baseline" not in d
+
+
+def test_plain_run_is_lean_and_dumps_what_the_timed_path_computed(tmp_path):
+    """A plain run: the headline line without the --full objects, and --dump-outputs writes the last timed solve's result."""
+    d = _run("--steps", "3", "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["unit"] == "LM iterations/s"
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["termination"] == "CONVERGENCE"
+    for k in ("roofline", "roofline_all_kernels", "kernel_profile_us", "cpu_baseline", "parity_ok", "default_solver_auto",
+              "extra_workloads", "inexact_newton_pcg_tol_1e-3", "sharded"):
+        assert k not in d, k
+    import numpy as np
+    a = {n: np.load(tmp_path / (n + ".npy")) for n in ("cameras", "points", "focal", "summary", "trace")}
+    assert all(v.dtype == np.float64 and np.all(np.isfinite(v)) for v in a.values())
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 << 20
+    assert a["cameras"].shape == (20, 6) and a["points"].shape == (5000, 3) and a["focal"].shape == (1,)
+    summ = dict(zip(_bench_module().SUMMARY_FIELDS, a["summary"]))
+    assert summ["final_cost"] == d["final_cost"] and summ["iterations"] == a["trace"].shape[0] - 1 and a["trace"].shape[1] == 10
+    # what was dumped is the solved problem: the oracle's stored final cost for cfg2
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "oracle_final_costs.json")))["cfg2"]
+    assert abs(summ["final_cost"] - want["final_cost"]) <= 1e-6 * want["final_cost"] and summ["iterations"] == want["iterations"]
 
 
 def _bench_module():
@@ -57,7 +79,7 @@ def _bench_module():
 
 
 def test_headline_and_modes_carry_parity_against_the_stored_oracle_result():
-    d = _run("--no-cpu-baseline", "--no-live-traffic")
+    d = _run("--full", "--no-cpu-baseline", "--no-live-traffic")
     assert d["parity_ok"] is True and d["parity_rank0"]["oracle_key"] == "cfg2" and d["parity_rank0"]["rel_cost_diff_vs_oracle"] < 1e-6
     s = _run("--no-cpu-baseline", "--no-live-traffic", "--mode", "sharded", "--row-sharded")
     assert s["n_gpus"] == 1 and s["parity_ok"] is True and s["sharded"]["parity_ok"] is True and s["sharded"]["oracle_key"] == "cfg2"

@@ -7,7 +7,7 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/evidence5
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --workload cfg5 --no-cpu-baseline --no-live-traffic $*"
+BENCH="python $REPO/bench.py --full --workload cfg5 --no-cpu-baseline --no-live-traffic $*"
 # 1. the bench line (unsharded, one resident problem) and the sharded loop on this box's one rank, both CG forms
 $BENCH --steps 5 --warmup 2 > $OUT/${TAG}_cfg5_pcg_bench.json 2> $OUT/bench5.err
 # 2. rocprofv3 kernel statistics of the same command

@@ -7,7 +7,7 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/evidence
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py"
+BENCH="python $REPO/bench.py --full"
 # 1. the bench line itself (with cpu_baseline), PCG (default) and the exact Cholesky path
 $BENCH > $OUT/${TAG}_cfg3_pcg_bench.json 2> $OUT/bench_pcg.err
 # (the same default run carries `extra_workloads`: cfg 2 in fp64, cfg 3 in fp64, cfg3_banded, cfg 5 -- each held to the oracle's stored result)

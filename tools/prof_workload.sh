@@ -7,7 +7,7 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $OUT
 OUT=$(cd $OUT && pwd)
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --no-cpu-baseline --no-live-traffic --extra-workloads 0 $*"
+BENCH="python $REPO/bench.py --full --no-cpu-baseline --no-live-traffic --extra-workloads 0 $*"
 $BENCH --steps 10 --warmup 3 2> $OUT/${NAME}.err | grep '^{' > $OUT/${TAG}_${NAME}_bench.json
 rm -rf $OUT/st_$NAME
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/st_$NAME -- $BENCH --steps 6 --warmup 2 > /dev/null 2>> $OUT/${NAME}.err
