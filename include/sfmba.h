@@ -493,6 +493,37 @@ SFMBA_API int sfmba_find_2d3d_matches(int device, int n_views, const unsigned ch
 SFMBA_API int sfmba_merge_candidates(int device, int n_exist, const float* exist_xyz, int n_new, const float* new_xyz, float max_dist,
                 int64_t* cand_ptr, int32_t* cand_idx, int64_t cap, int64_t* total);
 
+/*
+ * The feature match matrix (SfM::createFeatureMatchMatrix, SfMToyLib/SfM.cpp:157-212): SfM2DFeatureUtilities::matchFeatures
+ * (SfM2DFeatureUtilities.cpp:53-71) -- a brute-force Hamming 2-NN and the ratio test -- for a list of image pairs in one call.
+ *
+ *   descriptors   image i owns rows img_ptr[i] .. img_ptr[i+1]-1 of desc; a row is desc_bytes bytes (1..64; ORB: 32), rows
+ *                 packed back to back.  An image may hold at most 2^22 - 1 rows.
+ *   pair p        query rows = the rows of image pair_left[p], train rows = those of image pair_right[p]; l == r is allowed.
+ *   distance      d(q, j) = popcount(desc_l[q] XOR desc_r[j]) over the row's bytes (an integer <= 8 desc_bytes).
+ *   2-NN          best(q), second(q) = the two smallest (d, j) in lexicographic order: a tie on distance goes to the lower
+ *                 train index (OpenCV's BFMatcher::knnMatch, K = 2, inserts with a strict <).
+ *   ratio test    q is kept iff the train image has >= 2 rows and (double)d_best < ratio * (double)d_second, in double as the
+ *                 reference compares a float DMatch distance with NN_MATCH_RATIO.  The reference's value is ratio =
+ *                 (double)0.8f = 0.800000011920929, with which d = 4 against 5 IS kept (an exact 0.8 would drop it).
+ *                 The one deliberate departure: with fewer than 2 train rows the reference reads initialMatching[i][1] out of
+ *                 bounds (undefined behaviour); here that pair has no matches.
+ *   output        a kept query yields (query_idx = q, train_idx = j_best, distance = (float)d_best) -- the DMatch the reference
+ *                 keeps (imgIdx = 0).  Entries are in ascending q within a pair (prunedMatching order), pairs in the order of
+ *                 the pair list: pair_ptr [n_pairs + 1] is the CSR of the flattened match-matrix encoding that
+ *                 sfmba_find_2d3d_matches reads.  An empty query or train image gives an empty list.  distance may be NULL.
+ *
+ * Host pointers in and out, synchronous.  *total receives the number of entries; SFMBA_ERR_CAPACITY (pair_ptr and *total valid,
+ * nothing else written) if cap < *total.  SFMBA_ERR_INVALID_ARG for desc_bytes outside 1..64, an image with >= 2^22 rows, a pair
+ * index out of range, a ratio that is not finite or <= 0, and more than 2^31 - 1 query rows (summed over the pairs) in one call.
+ * Deterministic: the result does not depend on how the work is cut up.  The work is cut into batches of query tiles (512 query
+ * rows of one pair) in pair-list order, at most 512 tiles per batch (a fixed 64 MiB bound on the per-slice scratch); a batch of
+ * n tiles splits every train image into min(ceil(4096 / n), ceil(max train rows of the batch / 256), 32) slices (at least 1).
+ */
+SFMBA_API int sfmba_match_features(int device, int n_images, const int64_t* img_ptr, const unsigned char* desc, int desc_bytes,
+                int n_pairs, const int32_t* pair_left, const int32_t* pair_right, double ratio,
+                int64_t* pair_ptr, int32_t* query_idx, int32_t* train_idx, float* distance, int64_t cap, int64_t* total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ SYMBOLS = [
     "sfmba_comm_allreduce_f32", "sfmba_problem_set_allreduce_f32", "sfmba_shard_last_exchange",
     "sfmba_problem_create_ex", "sfmba_comm_abort", "sfmba_comm_reduce_scatter", "sfmba_problem_set_reduce_scatter",
     "sfmba_comm_allgather", "sfmba_problem_set_allgather", "sfmba_comm_size", "sfmba_device_warmup",
+    "sfmba_match_features",
 ]
 
 
@@ -124,6 +125,42 @@ def merge_candidates(exist_xyz, new_xyz, max_dist=0.01, cap=None, device=0):
         cap = int(total.value)
     _check(rc)
     return ptr, idx[:total.value].copy()
+
+
+def match_features(descs, pairs=None, ratio=float(np.float32(0.8)), cap=None, device=0):
+    """sfmba_match_features: brute-force Hamming 2-NN + ratio test for every pair (see include/sfmba.h).
+
+    descs: list of uint8 arrays [n_i, B] (one per image, the same B for all).  pairs: list of (left, right) image indices, None = all
+    i < j in row-major order (SfM::createFeatureMatchMatrix).  ratio defaults to the reference's (double)0.8f.
+    Returns (pair_left, pair_right, pair_ptr [n_pairs+1], query_idx, train_idx, distance float32)."""
+    descs = [np.asarray(d, dtype=np.uint8) for d in descs]
+    nb = {d.shape[1] for d in descs if d.ndim == 2}
+    if any(d.ndim != 2 for d in descs) or len(nb) > 1:
+        raise ValueError("descs must be 2-D uint8 arrays with one row length")
+    B = nb.pop() if nb else 32
+    if pairs is None:
+        pairs = [(i, j) for i in range(len(descs)) for j in range(i + 1, len(descs))]
+    pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    pl, pr = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+    img_ptr = np.zeros(len(descs) + 1, dtype=np.int64)
+    img_ptr[1:] = np.cumsum([d.shape[0] for d in descs])
+    flat = np.ascontiguousarray(np.concatenate(descs, axis=0) if descs else np.zeros((0, B), np.uint8))
+    if cap is None:                      # at most one entry per query row of a pair with >= 2 train rows: one call, no retry
+        cap = int(sum(descs[l].shape[0] for l, r in zip(pl, pr) if 0 <= r < len(descs) and descs[r].shape[0] >= 2 and 0 <= l < len(descs)))
+    lp, fp = C.POINTER(C.c_int64), C.POINTER(C.c_float)
+    ptr = np.zeros(len(pl) + 1, dtype=np.int64)
+    total = C.c_int64(0)
+    for _ in range(2):
+        q, t, d = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float32)
+        rc = lib().sfmba_match_features(C.c_int(device), C.c_int(len(descs)), _p(img_ptr, lp), flat.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                        C.c_int(B), C.c_int(len(pl)), _p(pl, _ip), _p(pr, _ip), C.c_double(ratio), _p(ptr, lp), _p(q, _ip),
+                                        _p(t, _ip), _p(d, fp), C.c_int64(cap), C.byref(total))
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        cap = int(total.value)
+    _check(rc)
+    n = total.value
+    return pl, pr, ptr, q[:n].copy(), t[:n].copy(), d[:n].copy()
 
 
 def release_cache():

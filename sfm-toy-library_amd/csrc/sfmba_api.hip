@@ -11,6 +11,7 @@
 // SFMBA_ERR_NO_DEVICE.
 #include "../../include/sfmba.h"
 #include "association.h"
+#include "feature_match.h"
 #include "ba_kernels.h"
 #include "dense_solver.h"
 #include "dist_cg.h"
@@ -23,6 +24,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2416,6 +2418,48 @@ int sfmba_merge_candidates(int device, int n_exist, const float* exist_xyz, int 
     struct KitGuard { HostKit k; ~KitGuard() { if (k.stream) (void)hipStreamSynchronize(k.stream); hostkit_release(k); } } kg{ kit };
     return assoc_result(assoc_radius_candidates(kit.stream, device, n_exist, exist_xyz, n_new, new_xyz, max_dist, cand_ptr, cand_idx, cap, total),
                         "merge_candidates");
+}
+
+// ---- feature match matrix (SfM::createFeatureMatchMatrix) ---------------------------------------------------------
+int sfmba_match_features(int device, int n_images, const int64_t* img_ptr, const unsigned char* desc, int desc_bytes, int n_pairs,
+                         const int32_t* pair_left, const int32_t* pair_right, double ratio, int64_t* pair_ptr, int32_t* query_idx,
+                         int32_t* train_idx, float* distance, int64_t cap, int64_t* total) {
+    if (n_images < 0 || n_pairs < 0 || cap < 0 || !img_ptr || !pair_ptr || !total || (n_pairs > 0 && (!pair_left || !pair_right)) ||
+        (cap > 0 && (!query_idx || !train_idx)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (desc_bytes < 1 || desc_bytes > 64) return fail(SFMBA_ERR_INVALID_ARG, "desc_bytes must be in 1..64");
+    if (!std::isfinite(ratio) || !(ratio > 0.0)) return fail(SFMBA_ERR_INVALID_ARG, "ratio must be finite and > 0");
+    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        const int64_t n = img_ptr[i + 1] - img_ptr[i];
+        if (n < 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
+        if (n >= ((int64_t)1 << 22)) return fail(SFMBA_ERR_INVALID_ARG, "an image has 2^22 or more descriptor rows (the train index is packed in 22 bits)");
+    }
+    if (img_ptr[n_images] > 0 && !desc) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    int64_t rows = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        const int l = pair_left[p], r = pair_right[p];
+        if (l < 0 || l >= n_images || r < 0 || r >= n_images) return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
+        if (img_ptr[r + 1] - img_ptr[r] >= 2) rows += img_ptr[l + 1] - img_ptr[l];
+    }
+    if (rows >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "match_features: too many query rows in one call (2^31)");
+    int rc = check_device(device);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    HostKit kit;
+    if (!hostkit_acquire(device, &kit)) return fail(SFMBA_ERR_HIP, "stream creation failed");
+    struct KitGuard { HostKit k; ~KitGuard() { if (k.stream) (void)hipStreamSynchronize(k.stream); hostkit_release(k); } } kg{ kit };
+    // SFMBA_MATCH_TIMING: one stderr line per call with the HIP-event times of its phases (tools/match_bench.py)
+    double tm[5];
+    const bool timing = std::getenv("SFMBA_MATCH_TIMING") != nullptr;
+    rc = match_features(kit.stream, device, n_images, img_ptr, desc, desc_bytes, n_pairs, pair_left, pair_right, ratio, pair_ptr, query_idx,
+                        train_idx, distance, cap, total, timing ? tm : nullptr);
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba match] upload_ms %.6f top2_ms %.6f compact_ms %.6f download_ms %.6f batches %d\n", tm[0], tm[1], tm[2], tm[3], (int)tm[4]);
+    if (rc == MATCH_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "match_features: output capacity too small");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "match_features: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("match_features: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,106 @@
+// SfM2DFeatureUtilities.cpp -- host side of the feature matcher: flattens the descriptor matrices, calls the C ABI
+// (include/sfmba.h, sfmba_match_features) and rebuilds the reference's Matching lists.  See SfM2DFeatureUtilities.h.
+#include "SfM2DFeatureUtilities.h"
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "../../include/sfmba.h"
+
+namespace sfmtoylib {
+
+namespace {
+
+const double NN_MATCH_RATIO = 0.8f;     // SfM2DFeatureUtilities.cpp:35 -- a float literal widened to double
+
+struct FlatDescriptors {
+    std::vector<int64_t> ptr;
+    std::vector<unsigned char> bytes;
+    int rowBytes = 32;
+};
+
+// The descriptors of images[0..n-1] back to back; false (with a stderr line) if one is not CV_8U or the row lengths differ.
+bool flatten(const std::vector<const Features*>& images, FlatDescriptors& f) {
+    f.ptr.assign(images.size() + 1, 0);
+    int cols = -1;
+    for (size_t i = 0; i < images.size(); ++i) {
+        const cv::Mat& d = images[i]->descriptors;
+        const int rows = d.empty() ? 0 : d.rows;
+        if (rows > 0) {
+            if (d.type() != CV_8U) { std::fprintf(stderr, "matchFeatures: descriptors must be CV_8U\n"); return false; }
+            if (cols >= 0 && d.cols != cols) { std::fprintf(stderr, "matchFeatures: descriptor lengths differ\n"); return false; }
+            cols = d.cols;
+        }
+        f.ptr[i + 1] = f.ptr[i] + rows;
+    }
+    if (cols >= 0) f.rowBytes = cols;
+    f.bytes.resize((size_t)f.ptr.back() * (size_t)f.rowBytes);
+    for (size_t i = 0; i < images.size(); ++i) {
+        const cv::Mat& d = images[i]->descriptors;
+        for (int64_t r = 0; r < f.ptr[i + 1] - f.ptr[i]; ++r)           // row by row: an OpenCV matrix need not be continuous
+            std::memcpy(&f.bytes[(size_t)(f.ptr[i] + r) * (size_t)f.rowBytes], d.ptr<unsigned char>((int)r), (size_t)f.rowBytes);
+    }
+    return true;
+}
+
+// One device call for the pair list; out[p] receives the Matching of pair p.
+bool matchPairs(const std::vector<const Features*>& images, const std::vector<int32_t>& left, const std::vector<int32_t>& right,
+                std::vector<Matching>& out) {
+    out.assign(left.size(), Matching());
+    FlatDescriptors f;
+    if (!flatten(images, f)) return false;
+    const int n_pairs = (int)left.size();
+    std::vector<int64_t> ptr((size_t)n_pairs + 1, 0);
+    std::vector<int32_t> query, train;
+    std::vector<float> dist;
+    int64_t cap = 0, total = 0;
+    for (int p = 0; p < n_pairs; ++p)                     // at most one match per query row of a pair with >= 2 train rows
+        if (f.ptr[right[p] + 1] - f.ptr[right[p]] >= 2) cap += f.ptr[left[p] + 1] - f.ptr[left[p]];
+    int rc = SFMBA_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        query.resize((size_t)cap + 1); train.resize((size_t)cap + 1); dist.resize((size_t)cap + 1);
+        rc = sfmba_match_features(0, (int)images.size(), f.ptr.data(), f.bytes.data(), f.rowBytes, n_pairs, left.data(), right.data(),
+                                  NN_MATCH_RATIO, ptr.data(), query.data(), train.data(), dist.data(), cap, &total);
+        if (rc == SFMBA_ERR_CAPACITY && attempt == 0) { cap = total; continue; }
+        break;
+    }
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "matchFeatures failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return false;
+    }
+    for (int p = 0; p < n_pairs; ++p) {
+        Matching& m = out[(size_t)p];
+        m.reserve((size_t)(ptr[p + 1] - ptr[p]));
+        for (int64_t e = ptr[p]; e < ptr[p + 1]; ++e) {
+            cv::DMatch d(query[(size_t)e], train[(size_t)e], dist[(size_t)e]);
+            d.imgIdx = 0;                                                  // what OpenCV sets for a single train set
+            m.push_back(d);
+        }
+    }
+    return true;
+}
+
+}  // namespace
+
+Matching SfM2DFeatureUtilities::matchFeatures(const Features& featuresLeft, const Features& featuresRight) {
+    std::vector<Matching> out;
+    if (!matchPairs({ &featuresLeft, &featuresRight }, { 0 }, { 1 }, out)) return Matching();
+    return out[0];
+}
+
+bool SfMFeatureMatching::createFeatureMatchMatrix(const std::vector<Features>& imageFeatures, MatchMatrix& featureMatchMatrix) {
+    const size_t numImages = imageFeatures.size();
+    featureMatchMatrix.resize(numImages, std::vector<Matching>(numImages));     // SfM.cpp:163
+    std::vector<const Features*> images;
+    for (const Features& f : imageFeatures) images.push_back(&f);
+    std::vector<int32_t> left, right;
+    for (size_t i = 0; i < numImages; i++)
+        for (size_t j = i + 1; j < numImages; j++) { left.push_back((int32_t)i); right.push_back((int32_t)j); }
+    std::vector<Matching> out;
+    if (!matchPairs(images, left, right, out)) return false;
+    for (size_t p = 0; p < left.size(); ++p) featureMatchMatrix[(size_t)left[p]][(size_t)right[p]].swap(out[p]);
+    return true;
+}
+
+}  // namespace sfmtoylib

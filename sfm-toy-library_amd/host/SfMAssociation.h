@@ -20,7 +20,6 @@
 
 namespace sfmtoylib {
 
-typedef std::vector<std::vector<Matching> > MatchMatrix;          // SfM.h:50
 struct Image2D3DMatch {                                           // SfMCommon.h:71-74
     Points2f points2D;
     Points3f points3D;

@@ -33,6 +33,7 @@ struct Point3DInMap {
 
 typedef std::vector<Point3DInMap> PointCloud;
 typedef std::vector<cv::DMatch>   Matching;      // SfMCommon.h:95
+typedef std::vector<std::vector<Matching> > MatchMatrix;          // SfM.h:50
 
 struct ImagePair {                                // SfMCommon.h:61-63
     size_t left, right;

@@ -3,7 +3,7 @@
 // The reference's data model (SfMToyLib/SfMCommon.h:55-99) is built on cv::Matx34f, cv::Point3f,
 // cv::Point2f and a CV_32F 3x3 cv::Mat.  OpenCV is not installable in this environment, so this header
 // provides layout- and API-compatible stand-ins for exactly the members adjustBundle() touches
-// (BA.cpp:111-221).  Building with -DSFMBA_HAVE_OPENCV uses the real headers instead; the shim source
+// (BA.cpp:111-221), plus CV_8U descriptor matrices for matchFeatures().  Building with -DSFMBA_HAVE_OPENCV uses the real headers instead; the shim source
 // is identical in both cases.
 #pragma once
 #ifdef SFMBA_HAVE_OPENCV
@@ -12,6 +12,8 @@
 #else
 #include <cstring>
 #include <vector>
+
+enum { CV_8U = 0, CV_32F = 5 };     // OpenCV's depth codes (single channel); global, as OpenCV's macros are
 
 namespace cv {
 
@@ -44,17 +46,26 @@ typedef Point3_<float> Point3f;
 struct KeyPoint { Point2f pt; float size = 0, angle = -1, response = 0; int octave = 0, class_id = -1; };
 struct DMatch { int queryIdx = -1, trainIdx = -1, imgIdx = -1; float distance = 0; DMatch() {} DMatch(int q, int t, float d) : queryIdx(q), trainIdx(t), distance(d) {} };
 
-// Dense row-major float matrix: only what Intrinsics::K needs (K.at<float>(r, c), BA.cpp:138,151-153,188-189).
+// Dense row-major matrix, continuous, zero-initialised: a CV_32F one is what Intrinsics::K needs (K.at<float>(r, c),
+// BA.cpp:138,151-153,188-189), a CV_8U one holds binary descriptors (Features::descriptors, one row per key point).
 class Mat {
 public:
-    Mat() : rows(0), cols(0) {}
-    Mat(int r, int c) : rows(r), cols(c), data_((size_t)r * c, 0.0f) {}
-    template <typename T> T& at(int r, int c) { return reinterpret_cast<T&>(data_[(size_t)r * cols + c]); }
-    template <typename T> const T& at(int r, int c) const { return reinterpret_cast<const T&>(data_[(size_t)r * cols + c]); }
+    Mat() : rows(0), cols(0), type_(CV_32F) {}
+    Mat(int r, int c) : Mat(r, c, CV_32F) {}
+    Mat(int r, int c, int type) : rows(r), cols(c), type_(type), data_(((size_t)r * c * elem(type) + 3) / 4, 0.0f) {}
+    template <typename T> T& at(int r, int c) { return ptr<T>(r)[c]; }
+    template <typename T> const T& at(int r, int c) const { return ptr<T>(r)[c]; }
+    template <typename T> T* ptr(int r) { return reinterpret_cast<T*>(bytes() + (size_t)r * cols * elem(type_)); }
+    template <typename T> const T* ptr(int r) const { return reinterpret_cast<const T*>(bytes() + (size_t)r * cols * elem(type_)); }
+    int type() const { return type_; }
     bool empty() const { return data_.empty(); }
     int rows, cols;
 private:
-    std::vector<float> data_;
+    static size_t elem(int type) { return type == CV_8U ? 1 : 4; }
+    unsigned char* bytes() { return reinterpret_cast<unsigned char*>(data_.data()); }
+    const unsigned char* bytes() const { return reinterpret_cast<const unsigned char*>(data_.data()); }
+    int type_;
+    std::vector<float> data_;      // float words whatever the type: 4-byte aligned storage
 };
 
 }  // namespace cv

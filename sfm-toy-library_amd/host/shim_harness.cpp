@@ -1,4 +1,4 @@
-// shim_harness.cpp -- flat-array entry point used by tests/test_gpu_shim.py to drive the C++ shim:
+// shim_harness.cpp -- flat-array entry points used by the tests to drive the C++ shim, e.g. for tests/test_gpu_shim.py:
 // builds the reference's containers (PointCloud / vector<Matx34f> / Intrinsics / vector<Features>),
 // calls sfmtoylib::SfMBundleAdjustmentUtils::adjustBundle() and copies the containers back.
 #include <chrono>
@@ -9,6 +9,7 @@
 #include "SfMStereoUtilities.h"
 #include "SfMAssociation.h"
 #include "SfMExport.h"
+#include "SfM2DFeatureUtilities.h"
 
 extern "C" __attribute__((visibility("default")))
 void sfmba_shim_adjust_bundle(int n_views, float* poses /*[n_views][12]*/, float* K /*[9]*/, int n_pts, float* points /*[n_pts][3]*/,
@@ -179,4 +180,57 @@ int sfmba_shim_save_ply(const char* prefix, int n_views, const float* poses /*[n
 #endif
     }
     return SfMExport::saveCloudAndCamerasToPLY(prefix, cloud, cams, feats, imgs) ? 0 : -1;
+}
+
+namespace {
+std::vector<Features> buildDescriptors(int n_images, const int64_t* img_ptr, const unsigned char* desc, int desc_bytes) {
+    std::vector<Features> feats((size_t)n_images);
+    for (int i = 0; i < n_images; ++i) {
+        const int rows = (int)(img_ptr[i + 1] - img_ptr[i]);
+        if (rows == 0) continue;                                  // an image without key points: an empty matrix
+        feats[i].descriptors = cv::Mat(rows, desc_bytes, CV_8U);
+        for (int r = 0; r < rows; ++r)
+            for (int b = 0; b < desc_bytes; ++b) feats[i].descriptors.at<unsigned char>(r, b) = desc[(size_t)(img_ptr[i] + r) * desc_bytes + b];
+    }
+    return feats;
+}
+int64_t flattenMatching(const Matching& m, int64_t at, int64_t cap, int32_t* query, int32_t* train, int32_t* img, float* dist) {
+    for (const cv::DMatch& d : m) {
+        if (at < cap) { query[at] = d.queryIdx; train[at] = d.trainIdx; img[at] = d.imgIdx; dist[at] = d.distance; }
+        ++at;
+    }
+    return at;
+}
+}  // namespace
+
+// Flat-array driver of sfmtoylib::SfM2DFeatureUtilities::matchFeatures (tests/test_gpu_feature_match.py): image 0 of the
+// descriptor CSR is the left one, image 1 the right one.  Returns the number of matches (entries beyond cap are not written).
+extern "C" __attribute__((visibility("default")))
+int64_t sfmba_shim_match_features(const int64_t* img_ptr /*[3]*/, const unsigned char* desc, int desc_bytes, int64_t cap, int32_t* query,
+                                  int32_t* train, int32_t* img_idx, float* dist) {
+    using namespace sfmtoylib;
+    const std::vector<Features> feats = buildDescriptors(2, img_ptr, desc, desc_bytes);
+    return flattenMatching(SfM2DFeatureUtilities::matchFeatures(feats[0], feats[1]), 0, cap, query, train, img_idx, dist);
+}
+
+// Flat-array driver of sfmtoylib::SfMFeatureMatching::createFeatureMatchMatrix.  sizes [n_images * n_images] receives the length
+// of every entry [l][r] (row-major), the entries are flattened in that order.  Returns the number of matches, -1 if the call
+// reported failure, -2 if the matrix is not n_images x n_images.
+extern "C" __attribute__((visibility("default")))
+int64_t sfmba_shim_feature_match_matrix(int n_images, const int64_t* img_ptr, const unsigned char* desc, int desc_bytes, int64_t* sizes,
+                                        int64_t cap, int32_t* query, int32_t* train, int32_t* img_idx, float* dist) {
+    using namespace sfmtoylib;
+    const std::vector<Features> feats = buildDescriptors(n_images, img_ptr, desc, desc_bytes);
+    MatchMatrix mm;
+    if (!SfMFeatureMatching::createFeatureMatchMatrix(feats, mm)) return -1;
+    if (mm.size() != (size_t)n_images) return -2;
+    int64_t n = 0;
+    for (int l = 0; l < n_images; ++l) {
+        if (mm[l].size() != (size_t)n_images) return -2;
+        for (int r = 0; r < n_images; ++r) {
+            sizes[(size_t)l * n_images + r] = (int64_t)mm[l][r].size();
+            n = flattenMatching(mm[l][r], n, cap, query, train, img_idx, dist);
+        }
+    }
+    return n;
 }

@@ -230,3 +230,38 @@ def make_problem(name="cfg2", sub=None, n_cam=None, n_pt=None, views=None, seed=
                      np.ascontiguousarray(obs_xy), cam_true, pt_true, F_TRUE,
                      dict(name=name, sub=sub, seed=seed, noise_px=noise_px,
                           image_size=IMAGE_SIZE, principal_point=PRINCIPAL_POINT))
+
+
+def make_descriptors(n_images=7, n_rows=5000, desc_bytes=32, n_tracks=None, flip_bits=8, seed=0, extras=True):
+    """Binary descriptors for the feature matcher (sfmba_match_features): a list of uint8 arrays [n_i, desc_bytes].
+
+    True correspondences are planted: a track is one shared random descriptor, seen in a random subset of the images with
+    `flip_bits` random bits flipped per image; the remaining rows are random distractors.  Rows are shuffled per image.
+    With `extras`, every image also gets duplicated rows (exact distance ties, where the lower train index must win) and a
+    block of all-equal rows, and two images are appended: one with 0 rows and one with 1 row (the reference's undefined case)."""
+    rng = np.random.default_rng(seed)
+    n_bits = 8 * desc_bytes
+    n_tracks = int(0.6 * n_rows) if n_tracks is None else int(n_tracks)
+    tracks = rng.integers(0, 256, (n_tracks, desc_bytes), dtype=np.uint8)
+    out = []
+    for _ in range(n_images):
+        seen = rng.random(n_tracks) < 0.7
+        rows = tracks[seen][: n_rows].copy()
+        if len(rows):
+            flip = rng.integers(0, n_bits, (len(rows), max(flip_bits, 0)))
+            bits = np.unpackbits(rows, axis=1)
+            for k in range(flip.shape[1]):
+                bits[np.arange(len(rows)), flip[:, k]] ^= 1
+            rows = np.packbits(bits, axis=1)
+        n_rand = n_rows - len(rows)
+        rows = np.concatenate([rows, rng.integers(0, 256, (n_rand, desc_bytes), dtype=np.uint8)], axis=0)
+        rows = rows[rng.permutation(n_rows)]
+        if extras and n_rows >= 8:
+            dup = rng.choice(n_rows, size=max(1, n_rows // 50), replace=False)
+            rows[rng.choice(n_rows, size=len(dup), replace=False)] = rows[dup]      # duplicated rows: ties on distance
+            rows[:3] = rows[3]                                                       # a block of all-equal rows
+        out.append(np.ascontiguousarray(rows))
+    if extras:
+        out.append(np.zeros((0, desc_bytes), np.uint8))
+        out.append(rng.integers(0, 256, (1, desc_bytes), dtype=np.uint8))
+    return out
