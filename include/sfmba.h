@@ -330,6 +330,29 @@ SFMBA_API int sfmba_problem_set_profiling(sfmba_problem* p, int enable);
 SFMBA_API int sfmba_problem_get_profile(sfmba_problem* p, sfmba_kernel_time* out, int cap, int* n);
 
 /*
+ * Step probe (a test hook, like sfmba_problem_build_reduced): what the LAST back-substitution that ran
+ * on the handle consumed -- in any loop (sfmba_problem_solve, the matrix-free / sharded loop of
+ * sfmba_problem_solve_sharded, sfmba_shard_solve_update).
+ *   z   [dim]        the reduced step in build_reduced's unknowns (Jacobi-scaled, cameras in ascending
+ *                    active order, focal last), after the block-Jacobi back-transform: the trial
+ *                    cameras are x0 - scale * z.  NULL: not copied.
+ *   dpt [3 * n_pt]   the point step k_point_update subtracted (unscaled, caller order; 0 for points
+ *                    without observations): the trial points are x0 - dpt.  NULL: not copied.
+ *   info             the reduced-system solver family that produced z, whether its CG read the matrix
+ *                    in fp32, its coarse vectors (0, 8, 57 or 7 G + 1), the CG iterations of that LM
+ *                    iteration, and whether AUTO fell back to the Cholesky on that linearisation.
+ * Enabling it (re)arms the probe for the next solve: its buffers are allocated only while it is on, and
+ * a solve with the probe off is the same solve.  get_step_probe waits for the problem's stream; family 0
+ * means that no back-substitution has run since the probe was enabled.
+ */
+typedef struct sfmba_step_probe { int family; int f32_matrix; int coarse_vectors; int cg_iters; int cholesky_fallback; } sfmba_step_probe;
+enum { SFMBA_FAMILY_CHOL_SMALL = 1, SFMBA_FAMILY_CHOL_FUSED, SFMBA_FAMILY_CHOL_PANEL, SFMBA_FAMILY_PCG_FAST, SFMBA_FAMILY_PCG_SEGMENTS,
+       SFMBA_FAMILY_PCG_SYMMETRIC, SFMBA_FAMILY_PCG_STREAMING, SFMBA_FAMILY_PCG_SEGMENTS_STREAMING, SFMBA_FAMILY_PCG_SEGMENTS_STREAMING_SPARSE,
+       SFMBA_FAMILY_DIST_BLOCKS, SFMBA_FAMILY_DIST_ROWS, SFMBA_FAMILY_IMPLICIT };
+SFMBA_API int sfmba_problem_set_step_probe(sfmba_problem* p, int enable);
+SFMBA_API int sfmba_problem_get_step_probe(sfmba_problem* p, double* z /*[dim]*/, double* dpt /*[3*n_pt] or NULL*/, sfmba_step_probe* info);
+
+/*
  * Kernel-level entry points (parity tests call these through the C ABI).
  *   residuals_out : [2*n_obs] in the caller's observation order
  *   cost_out      : 1/2 sum r^2

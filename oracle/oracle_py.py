@@ -147,6 +147,27 @@ def build_reduced(prob, radius, opt=None, cam6=None, pt3=None, focal=None):
     return S.reshape(d, d), rhs, scale, int(info)
 
 
+def lm_step(prob, radius, opt=None, z=None, cam6=None, pt3=None, focal=None):
+    """One exact LM step of the DENSE_SCHUR solver (sfmba_oracle_lm_step): dict with build_reduced's S, rhs, scale, the reduced
+    step z (exact, or the given `z` taken as is), the unscaled point step dpt [n_pt][3] in caller order (trial points = pt3 - dpt),
+    cond(V_i) [n_pt] of every damped 3x3 point block, dmag [n_pt] the size of the terms that cancel into each point step, and the
+    factorisation status info."""
+    keep, args = _prob_args(prob, cam6, pt3)
+    n_active = len(np.unique(prob.obs_cam))
+    d = 6 * n_active + 1
+    S, rhs, scale, zo = np.zeros(d * d), np.zeros(d), np.zeros(d), np.zeros(d)
+    dpt, vcond, dmag = np.zeros(3 * max(prob.n_pt, 1)), np.zeros(max(prob.n_pt, 1)), np.zeros(max(prob.n_pt, 1))
+    zin = None if z is None else _d(z)
+    if zin is not None and zin.shape != (d,):
+        raise ValueError("z must have %d entries" % d)
+    opt = opt or SfmbaOptions.defaults()
+    info = lib().sfmba_oracle_lm_step(*args, C.c_double(prob.focal if focal is None else focal), C.byref(opt), C.c_double(radius),
+                                      _p(S, _dp), _p(rhs, _dp), _p(scale, _dp), None if zin is None else _p(zin, _dp),
+                                      _p(zo, _dp), _p(dpt, _dp), _p(vcond, _dp), _p(dmag, _dp))
+    return dict(S=S.reshape(d, d), rhs=rhs, scale=scale, z=zo, dpt=dpt[:3 * prob.n_pt].reshape(prob.n_pt, 3),
+                vcond=vcond[:prob.n_pt], dmag=dmag[:prob.n_pt], info=int(info))
+
+
 def dense_spd_solve(A, b):
     A, b = _d(A), _d(b)
     n = b.shape[0]

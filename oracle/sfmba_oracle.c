@@ -472,12 +472,16 @@ typedef struct {
  * diagonal D^2 (per parameter: dcam[6*n_acam], dfocal, dpt[3*n_apt]).
  * Solves (J^T J + D^2) y = J^T r and returns y (NOT negated) in ycam/yfocal/ypt.
  * If S_out/rhs_out are given (dim*dim / dim), the reduced system is copied there.
+ * z_in (dim, or NULL): the reduced step to back-substitute instead of solving for it (sfmba_oracle_lm_step).
+ * vcond (n_apt, or NULL): 2-norm condition number of every damped 3x3 point block V_i; ymag (n_apt, or NULL): |(|V_i^-1| (|b_p| + sum |E^T u|))|,
+ * the size of the terms that cancel into the point step y_i (its rounding error is relative to THAT, not to |y_i|).
  * Returns 0 OK, >0 linear solver failure.
  */
+static double cond3_spd(const double V[9]);
 static int schur_solve(const ba_structure* s, const ba_lin* lin,
                        const double* dcam2, double dfocal2, const double* dpt2,
                        double* ycam, double* yfocal, double* ypt,
-                       double* S_out, double* rhs_out, int solve) {
+                       double* S_out, double* rhs_out, int solve, const double* z_in, double* vcond, double* ymag) {
     const int d = s->dim;
     const int fo = d - 1; /* focal index in the reduced system */
     int nthreads = 1;
@@ -549,6 +553,7 @@ static int schur_solve(const ba_structure* s, const ba_lin* lin,
                 rhs[fo] += G[0] * r[0] + G[1] * r[1];
             }
             double Vi[9];
+            if (vcond) vcond[i] = cond3_spd(V);
             if (inv3_spd(V, Vi)) {
 #pragma omp atomic write
                 fail = 1;
@@ -601,15 +606,17 @@ static int schur_solve(const ba_structure* s, const ba_lin* lin,
 
     int info = fail;
     if (!fail && solve) {
-        info = dense_cholesky_lower(d, S);
+        if (z_in) { info = 0; memcpy(rhs, z_in, sizeof(double) * (size_t)d); }
+        else info = dense_cholesky_lower(d, S);
         if (info == 0) {
-            dense_cholesky_solve_lower(d, S, rhs);
+            if (!z_in) dense_cholesky_solve_lower(d, S, rhs);
             for (int e = 0; e < 6 * s->n_acam; ++e) ycam[e] = rhs[e];
             *yfocal = rhs[fo];
             /* back substitution: y_e = V^-1 (E^T b - E^T F z) */
 #pragma omp parallel for schedule(static)
             for (int i = 0; i < s->n_apt; ++i) {
                 double t[3] = { bp[3 * i], bp[3 * i + 1], bp[3 * i + 2] };
+                double ta[3] = { fabs(t[0]), fabs(t[1]), fabs(t[2]) };
                 for (int64_t q = s->pt_ptr[i]; q < s->pt_ptr[i + 1]; ++q) {
                     const int64_t o = s->pt_obs[q];
                     const double* A = lin->jc + 12 * o;
@@ -618,9 +625,14 @@ static int schur_solve(const ba_structure* s, const ba_lin* lin,
                     const int j = s->cam_slot[s->obs_cam[o]];
                     double u0 = G[0] * rhs[fo], u1 = G[1] * rhs[fo];
                     for (int a = 0; a < 6; ++a) { u0 += A[a] * rhs[6 * j + a]; u1 += A[6 + a] * rhs[6 * j + a]; }
-                    for (int a = 0; a < 3; ++a) t[a] -= B[a] * u0 + B[3 + a] * u1;
+                    for (int a = 0; a < 3; ++a) { t[a] -= B[a] * u0 + B[3 + a] * u1; ta[a] += fabs(B[a] * u0) + fabs(B[3 + a] * u1); }
                 }
                 const double* Vi = vinv + 9 * i;
+                if (ymag) {
+                    double m2 = 0.0;
+                    for (int a = 0; a < 3; ++a) { const double v = fabs(Vi[3 * a]) * ta[0] + fabs(Vi[3 * a + 1]) * ta[1] + fabs(Vi[3 * a + 2]) * ta[2]; m2 += v * v; }
+                    ymag[i] = sqrt(m2);
+                }
                 for (int a = 0; a < 3; ++a) ypt[3 * i + a] = Vi[3 * a] * t[0] + Vi[3 * a + 1] * t[1] + Vi[3 * a + 2] * t[2];
             }
         }
@@ -738,10 +750,29 @@ static double max_abs(const double* v, int n) {
  * Reduced system only (parity check of the HIP Schur kernels).  S [dim*dim], rhs [dim],
  * scale [dim] in (active cameras..., focal) order.
  * ---------------------------------------------------------------------------------------- */
-ORACLE_API int sfmba_oracle_build_reduced(int n_cam, const double* cam6, int n_pt, const double* pt3,
-                                          int64_t n_obs, const int32_t* obs_cam, const int32_t* obs_pt,
-                                          const double* obs_xy, double focal, const sfmba_options* opt_in,
-                                          double radius, double* S, double* rhs, double* scale) {
+/* 2-norm condition number of a symmetric positive definite 3x3 matrix: its eigenvalues in closed form (the trigonometric
+ * solution of the characteristic cubic); infinity if it is not positive definite */
+static double cond3_spd(const double V[9]) {
+    const double p1 = V[1] * V[1] + V[2] * V[2] + V[5] * V[5];
+    const double q = (V[0] + V[4] + V[8]) / 3.0;
+    const double p2 = (V[0] - q) * (V[0] - q) + (V[4] - q) * (V[4] - q) + (V[8] - q) * (V[8] - q) + 2.0 * p1;
+    const double p = sqrt(p2 / 6.0);
+    if (!(p > 0.0)) return q > 0.0 ? 1.0 : INFINITY;
+    double B[9];
+    for (int e = 0; e < 9; ++e) B[e] = (V[e] - ((e % 4) == 0 ? q : 0.0)) / p;
+    const double detB = B[0] * (B[4] * B[8] - B[5] * B[7]) - B[1] * (B[3] * B[8] - B[5] * B[6]) + B[2] * (B[3] * B[7] - B[4] * B[6]);
+    const double r = fmin(1.0, fmax(-1.0, detB / 2.0));
+    const double phi = acos(r) / 3.0;
+    const double e1 = q + 2.0 * p * cos(phi), e3 = q + 2.0 * p * cos(phi + 2.0 * M_PI / 3.0);
+    return e3 > 0.0 ? e1 / e3 : INFINITY;
+}
+
+/* build_reduced and lm_step: the damped, scaled reduced system at the given parameters; solve = 1 also the step */
+static int reduced_step(int n_cam, const double* cam6, int n_pt, const double* pt3,
+                        int64_t n_obs, const int32_t* obs_cam, const int32_t* obs_pt,
+                        const double* obs_xy, double focal, const sfmba_options* opt_in,
+                        double radius, double* S, double* rhs, double* scale,
+                        int solve, const double* z_in, double* z_out, double* dpt_out, double* vcond_out, double* dmag_out) {
     sfmba_options opt;
     if (opt_in) opt = *opt_in; else sfmba_oracle_options_default(&opt);
     ba_structure s;
@@ -775,12 +806,55 @@ ORACLE_API int sfmba_oracle_build_reduced(int n_cam, const double* cam6, int n_p
     for (int e = 0; e < nc; ++e) dcam[e] = CLAMPD(dcam[e]);
     for (int e = 0; e < np; ++e) dpt[e] = CLAMPD(dpt[e]);
     dfocal = CLAMPD(dfocal);
-    const int info = schur_solve(&s, &lin, dcam, dfocal, dpt, NULL, NULL, NULL, S, rhs, 0);
+#undef CLAMPD
+    double* ycam = solve ? (double*)malloc(sizeof(double) * (size_t)(nc + 1)) : NULL;
+    double* ypt = solve ? (double*)malloc(sizeof(double) * (size_t)(np + 1)) : NULL;
+    double* vcond_a = vcond_out ? (double*)malloc(sizeof(double) * (size_t)(s.n_apt + 1)) : NULL;
+    double* ymag_a = dmag_out ? (double*)calloc((size_t)s.n_apt + 1, sizeof(double)) : NULL;
+    double yfocal = 0.0;
+    const int info = schur_solve(&s, &lin, dcam, dfocal, dpt, ycam, &yfocal, ypt, S, rhs, solve, z_in, vcond_a, ymag_a);
     if (scale) { memcpy(scale, scam, sizeof(double) * (size_t)nc); scale[nc] = sfocal; }
+    if (solve && info == 0) {
+        /* z in the reduced unknowns (scaled); the point step unscaled, in caller order, as k_point_update subtracts it */
+        if (z_out) { memcpy(z_out, ycam, sizeof(double) * (size_t)nc); z_out[nc] = yfocal; }
+        if (dpt_out) {
+            memset(dpt_out, 0, sizeof(double) * 3 * (size_t)n_pt);
+            for (int i = 0; i < s.n_apt; ++i)
+                for (int c = 0; c < 3; ++c) dpt_out[3 * (size_t)s.apt_id[i] + c] = ypt[3 * i + c] * spt[3 * i + c];
+        }
+    }
+    if (vcond_out) {
+        memset(vcond_out, 0, sizeof(double) * (size_t)n_pt);
+        for (int i = 0; i < s.n_apt; ++i) vcond_out[s.apt_id[i]] = vcond_a[i];
+    }
+    if (dmag_out) {      /* (unscaled like dpt) */
+        memset(dmag_out, 0, sizeof(double) * (size_t)n_pt);
+        for (int i = 0; i < s.n_apt; ++i) dmag_out[s.apt_id[i]] = ymag_a[i] * fmax(spt[3 * i], fmax(spt[3 * i + 1], spt[3 * i + 2]));
+    }
     free(x.cam); free(x.pt); free(lin.r); free(lin.jc); free(lin.jp); free(lin.jf);
-    free(scam); free(spt); free(dcam); free(dpt);
+    free(scam); free(spt); free(dcam); free(dpt); free(ycam); free(ypt); free(vcond_a); free(ymag_a);
     ba_structure_free(&s);
     return info;
+}
+
+ORACLE_API int sfmba_oracle_build_reduced(int n_cam, const double* cam6, int n_pt, const double* pt3,
+                                          int64_t n_obs, const int32_t* obs_cam, const int32_t* obs_pt,
+                                          const double* obs_xy, double focal, const sfmba_options* opt_in,
+                                          double radius, double* S, double* rhs, double* scale) {
+    return reduced_step(n_cam, cam6, n_pt, pt3, n_obs, obs_cam, obs_pt, obs_xy, focal, opt_in, radius, S, rhs, scale, 0, NULL, NULL, NULL, NULL, NULL);
+}
+
+/* One LM step of the DENSE_SCHUR solver at the given parameters and radius (tests/linear_step_check.py): build_reduced's S, rhs
+ * and scale, the exact reduced step z (Cholesky of S) -- or, with z_in, that z taken as given and only back-substituted --, the
+ * unscaled point step dpt [3 * n_pt] in caller order (x0 - dpt are the trial points), cond(V_i) [n_pt] of every damped 3x3
+ * point block and dmag [n_pt], the size of the terms that cancel into each point's step (0 for points without observations).  Any
+ * output may be NULL.  Returns 0, or > 0 if a factorisation failed. */
+ORACLE_API int sfmba_oracle_lm_step(int n_cam, const double* cam6, int n_pt, const double* pt3,
+                                    int64_t n_obs, const int32_t* obs_cam, const int32_t* obs_pt,
+                                    const double* obs_xy, double focal, const sfmba_options* opt_in,
+                                    double radius, double* S, double* rhs, double* scale,
+                                    const double* z_in, double* z, double* dpt, double* vcond, double* dmag) {
+    return reduced_step(n_cam, cam6, n_pt, pt3, n_obs, obs_cam, obs_pt, obs_xy, focal, opt_in, radius, S, rhs, scale, 1, z_in, z, dpt, vcond, dmag);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -1047,7 +1121,7 @@ static int bam_solve(void* c, double radius) {
     for (int e = 0; e < nc; ++e) b->dcam[e] = b->diagc[e] / radius;
     for (int e = 0; e < np; ++e) b->dpt[e] = b->diagp[e] / radius;
     const double dfocal = b->diagf / radius;
-    int lin_fail = schur_solve(b->s, &b->lin, b->dcam, dfocal, b->dpt, b->ycam, &b->yfocal, b->ypt, NULL, NULL, 1);
+    int lin_fail = schur_solve(b->s, &b->lin, b->dcam, dfocal, b->dpt, b->ycam, &b->yfocal, b->ypt, NULL, NULL, 1, NULL, NULL, NULL);
     if (!lin_fail) {
         int ok = isfinite(b->yfocal);
         for (int e = 0; e < nc && ok; ++e) ok = isfinite(b->ycam[e]);

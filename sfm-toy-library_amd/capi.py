@@ -34,8 +34,25 @@ SYMBOLS = [
     "sfmba_comm_allreduce_f32", "sfmba_problem_set_allreduce_f32", "sfmba_shard_last_exchange",
     "sfmba_problem_create_ex", "sfmba_comm_abort", "sfmba_comm_reduce_scatter", "sfmba_problem_set_reduce_scatter",
     "sfmba_comm_allgather", "sfmba_problem_set_allgather", "sfmba_comm_size", "sfmba_device_warmup",
-    "sfmba_match_features",
+    "sfmba_match_features", "sfmba_problem_set_step_probe", "sfmba_problem_get_step_probe",
 ]
+
+# reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
+FAMILIES = ("NONE", "CHOL_SMALL", "CHOL_FUSED", "CHOL_PANEL", "PCG_FAST", "PCG_SEGMENTS", "PCG_SYMMETRIC", "PCG_STREAMING",
+            "PCG_SEGMENTS_STREAMING", "PCG_SEGMENTS_STREAMING_SPARSE", "DIST_BLOCKS", "DIST_ROWS", "IMPLICIT")
+
+
+class _StepProbe(C.Structure):
+    _fields_ = [("family", C.c_int), ("f32_matrix", C.c_int), ("coarse_vectors", C.c_int), ("cg_iters", C.c_int), ("cholesky_fallback", C.c_int)]
+
+
+def get_step_probe(handle, dim, n_pt):
+    """What the last back-substitution on `handle` consumed (include/sfmba.h, sfmba_problem_get_step_probe): (z [dim], dpt [n_pt][3], info dict)."""
+    z, dpt, info = np.zeros(max(dim, 1)), np.zeros(3 * max(n_pt, 1)), _StepProbe()
+    _check(lib().sfmba_problem_get_step_probe(handle, _p(z, _dp), _p(dpt, _dp), C.byref(info)))
+    out = {k: int(getattr(info, k)) for k, _ in _StepProbe._fields_}
+    out["family_name"] = FAMILIES[out["family"]] if 0 <= out["family"] < len(FAMILIES) else str(out["family"])
+    return z[:dim], dpt[:3 * n_pt].reshape(n_pt, 3), out
 
 
 def triangulate(K, P_left, P_right, left_xy, right_xy, max_reproj_px=10.0, device=0):
@@ -378,6 +395,14 @@ class Problem:
             k = buf[i]
             out[k.name.decode()] = dict(total_us=k.total_us, launches=int(k.launches), avg_us=k.total_us / max(1, k.launches))
         return out
+
+    def set_step_probe(self, enable):
+        """Record the step of every back-substitution (a test hook; off = nothing allocated, nothing stored)."""
+        _check(lib().sfmba_problem_set_step_probe(self._h, C.c_int(1 if enable else 0)))
+
+    def step_probe(self):
+        """(z, dpt, info) of the last back-substitution: z in build_reduced's unknowns, dpt the point step in caller order."""
+        return get_step_probe(self._h, self.reduced_dim, self.n_pt)
 
     def eval_residuals(self):
         res = np.zeros(2 * self.n_obs)

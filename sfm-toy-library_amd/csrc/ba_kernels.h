@@ -164,6 +164,8 @@ struct DeviceBuffers {
     double* pcg_W;            // [8][ld] gauge vectors in the transformed unknowns (coarse space of the two-level CG preconditioner,
                               //         dense_solver.hip), written by k_finalize (PCG mode); null = not wanted
     int* lm_mailbox;          // host-mapped {seq, termination, message, iter}: polled by the host instead of a D2H copy + sync
+    double* probe_z;          // step probe (sfmba_problem_set_step_probe), else null: [d] the reduced step z k_cam_update consumed (slot order, focal last)
+    double* probe_dpt;        //   ... and [npt][3] the point step dX k_point_update subtracted (point slots)
     double shared_weight;     // 1 normally; 0 on ranks > 0 of a sharded solve (replicated cameras/focal counted once)
     float* shard_blocks32;    // ... the same in fp32 (exchange (B) in single precision: the streaming CG path stores S~ in fp32 anyway)
     double* shard_blocks;     // sharded CG path: the pair pass (MODE 1) stores the off-diagonal blocks of S~ here (all-reduce layout) instead of pcg_F

@@ -1546,6 +1546,10 @@ __global__ __launch_bounds__(BLK) void k_cam_update(DeviceStructure ds, DeviceBu
 #pragma unroll
             for (int c = 0; c < 6; ++c) z[c] = db.rhs[6 * j + c];
         }
+        if (db.probe_z) {
+#pragma unroll
+            for (int e = 0; e < 6; ++e) db.probe_z[6 * j + e] = z[e];
+        }
 #pragma unroll
         for (int e = 0; e < 6; ++e) {
             dlt[e] = cs[e] * z[e];
@@ -1583,6 +1587,7 @@ __global__ __launch_bounds__(BLK) void k_cam_update(DeviceStructure ds, DeviceBu
         const double f0 = st->focal[cur];
         double zf = db.rhs[ds.d - 1];
         if (db.pcg_vec) zf = db.pcg_linv[(size_t)ds.ncam * 36] * db.pcg_vec[(size_t)db.pcg_flags[2] * ds.ld + ds.d - 1];
+        if (db.probe_z) db.probe_z[ds.d - 1] = zf;
         const double fn = f0 - st->fscale * zf;
         st->focal[nxt] = fn;
         const double df = f0 - fn;
@@ -1839,6 +1844,7 @@ __global__ __launch_bounds__(PBK, 4) void k_point_update(DeviceStructure ds, Dev
             step2 += df * df;
             xn2 += Xn[c] * Xn[c];
             db.pts[nxt][3 * i + c] = Xn[c];
+            if (db.probe_dpt) db.probe_dpt[3 * i + c] = dX[c];
         }
         const double zGz = Gd[0] * z0 * z0 + Gd[3] * z1 * z1 + Gd[5] * z2 * z2 + 2.0 * (Gd[1] * z0 * z1 + Gd[2] * z0 * z2 + Gd[4] * z1 * z2);
         model += ur + (z0 * tp[0] + z1 * tp[1] + z2 * tp[2]) - 0.5 * uu - (z0 * zacc[0] + z1 * zacc[1] + z2 * zacc[2]) - 0.5 * zGz;

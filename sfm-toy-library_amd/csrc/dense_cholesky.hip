@@ -10,7 +10,7 @@
 // L(d, 0:d) = (L^-1 rhs)^T, i.e. the forward substitution comes for free with the panel updates.
 //
 // Three forms, chosen by size only (dense_cholesky_solve):
-//   d <= 256 unknowns                 k_chol_small: factorisation and both substitutions in ONE launch
+//   one block column (d <= 63)        k_chol_small: factorisation and both substitutions in ONE launch (ld / 64 == 1: <= 10 cameras)
 //   <= 40 block columns of 64         k_chol_step: one launch per block column (panel + trailing update fused, the 64x64
 //                                     diagonal factor with its inverse in LDS: chol_tile.h), k_chol_backsolve: one launch
 //   beyond                            k_chol_panel + k_chol_update per block column, k_chol_backstep per block column
@@ -18,6 +18,7 @@
 #include "sfmba_device.h"
 #include "chol_tile.h"
 #include "coarse_inverse.h"
+#include "../../include/sfmba.h"
 #include <math.h>
 #include <algorithm>
 
@@ -564,6 +565,8 @@ __global__ __launch_bounds__(256, 1) void k_chol_small(double* __restrict__ A, i
 
 void dense_cholesky_solve(hipStream_t s, DenseSolver* ws, double* S, double* rhs, int* info_dev, Profiler* prof) {
     const int ld = ws->ld, d = ws->d, nblk = ld / NB;
+    ws->family = nblk == 1 ? SFMBA_FAMILY_CHOL_SMALL : nblk <= CHOL_FUSED_MAX_BLOCKS ? SFMBA_FAMILY_CHOL_FUSED : SFMBA_FAMILY_CHOL_PANEL;
+    ws->coarse_vectors = 0;
     if (nblk == 1) {
         static bool small_attr_set = false;
         if (!small_attr_set) { (void)hipFuncSetAttribute((const void*)k_chol_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * CS_LDS_DOUBLES)); small_attr_set = true; }

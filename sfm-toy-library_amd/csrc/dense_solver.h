@@ -49,6 +49,8 @@ struct DenseSolver {
     const unsigned* blk_mask = nullptr;   // [ncam][(ncam + 31) / 32] per camera: cameras with a non-empty block in common (set by the caller; null: dense product)
     double blk_fill = 1.0;    // non-empty off-diagonal blocks / all (set by the caller)
     int last_iters = 0;       // CG iterations of the previous solve
+    int family = 0;           // SFMBA_FAMILY_* of the last dense_pcg_solve / dense_cholesky_solve (the step probe, include/sfmba.h)
+    int coarse_vectors = 0;   // ... and the coarse vectors of that CG: 0, 8, 57 (segments) or 7 G + 1 (segments, streaming path)
     std::vector<int> hist;    // CG iterations of the previous call per caller key (LM iteration index): sizes the first launch batch
     double* binv = nullptr;   // [ld*6] inverses of the 6x6 diagonal blocks (+1x1 focal)
     double* scal = nullptr;   // [8] rz, pq, bnorm2, rnorm2, ...

@@ -10,6 +10,7 @@
 #include "sfmba_device.h"
 #include "chol_tile.h"
 #include "coarse_inverse.h"
+#include "../../include/sfmba.h"
 #include <math.h>
 #include <stdio.h>
 #include <algorithm>
@@ -2549,6 +2550,13 @@ int dense_pcg_solve(hipStream_t s, DenseSolver* ws, double* S, double* rhs, doub
     if (mb) { mb[0] = -1; mb[1] = 0; }
     ws->run.nwg = nwg; ws->run.rows_per_wg = rows_per_wg; ws->run.lds = lds; ws->run.fast = fast; ws->run.f32 = f32; ws->run.coarse = coarse; ws->run.ml = ml; ws->run.sg = sg;
     ws->run.sym = sym;
+    {
+        const bool sparse_q = sg && ws->blk_mask != nullptr && ws->blk_fill < 0.25 && (d - 1) / 6 + 1 <= PCG_PART;     // (launch_cg_iteration's choice)
+        ws->family = fast ? (ml ? SFMBA_FAMILY_PCG_SEGMENTS : SFMBA_FAMILY_PCG_FAST)
+                   : sg ? (sparse_q ? SFMBA_FAMILY_PCG_SEGMENTS_STREAMING_SPARSE : SFMBA_FAMILY_PCG_SEGMENTS_STREAMING)
+                   : sym ? SFMBA_FAMILY_PCG_SYMMETRIC : SFMBA_FAMILY_PCG_STREAMING;
+        ws->coarse_vectors = ml ? ML_NC : sg ? 7 * sg_hats((d - 1) / 6) + 1 : coarse ? 8 : 0;
+    }
 
     ws->run.tol2 = tol * tol; ws->run.in = 1; ws->run.launched = 0; ws->run.max_iters = max_iters; ws->run.info = info_dev;
     { ProfScope ps(prof, KID_PCG_ITER, s);

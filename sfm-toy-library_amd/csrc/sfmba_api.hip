@@ -308,6 +308,10 @@ struct sfmba_problem {
     int dcg_last_f32 = -1;
     sfmba_summary shard_sum;
     Profiler prof;
+    // step probe (sfmba_problem_set_step_probe): off = no buffer, null pointers in db, nothing stored
+    bool probe_on = false;
+    double* d_probe = nullptr; size_t probe_cap = 0;   // [ld] z | [3 * point slots] dX (hipMalloc: it outlives the arena of an append)
+    sfmba_step_probe probe = {};
 };
 
 namespace {
@@ -338,6 +342,33 @@ DeviceStructure ds_cams(const sfmba_problem* p) {
 }
 DeviceBuffers db_cams(const sfmba_problem* p) {
     return p->db;      // (deterministic mode: a chunk's slot in cd_part is its index in the chunk LIST, whatever the launch order; the slots of the others' chunks stay zero)
+}
+
+// Step probe: arms db.probe_z / db.probe_dpt for the next solve (or leaves them null), sized to the current structure.
+int probe_arm(sfmba_problem* p) {
+    p->db.probe_z = nullptr; p->db.probe_dpt = nullptr;
+    p->probe = sfmba_step_probe{};
+    if (!p->probe_on) return SFMBA_OK;
+    const size_t npt_slots = (size_t)std::max(p->ds.npt, p->own_pt_stride * p->shard_world);
+    const size_t need = (size_t)p->ds.ld + 3 * npt_slots;
+    if (need > p->probe_cap) {
+        if (p->d_probe) (void)hipFree(p->d_probe);
+        p->d_probe = nullptr; p->probe_cap = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->d_probe), sizeof(double) * need));
+        p->probe_cap = need;
+    }
+    HIP_TRY(hipMemsetAsync(p->d_probe, 0, sizeof(double) * need, p->stream));
+    p->db.probe_z = p->d_probe; p->db.probe_dpt = p->d_probe + p->ds.ld;
+    return SFMBA_OK;
+}
+// ... and what the host decided for the back-substitution it has just enqueued (the probe describes the last one that ran)
+void probe_note(sfmba_problem* p, int family, int f32_matrix, int coarse_vectors, int cholesky_fallback) {
+    if (!p->probe_on) return;
+    p->probe.family = family; p->probe.f32_matrix = f32_matrix; p->probe.coarse_vectors = coarse_vectors;
+    p->probe.cholesky_fallback = cholesky_fallback;
+}
+void probe_note_solver(sfmba_problem* p, bool pcg, int cholesky_fallback) {
+    probe_note(p, p->solver.family, pcg && p->solver.run.f32 ? 1 : 0, pcg ? p->solver.coarse_vectors : 0, cholesky_fallback);
 }
 
 void init_state(sfmba_problem* p, LMState& st, const sfmba_options& o) {
@@ -431,6 +462,7 @@ int run_solve(sfmba_problem* p, const sfmba_options& o, sfmba_summary* summary, 
     const int want_rows = std::min(std::max(o.max_iters, 0) + 2, 1 << 16);
     int rc = ensure_trace(p, want_rows);
     if (rc) return rc;
+    if ((rc = probe_arm(p))) return rc;
     // no stream synchronisation here: whatever the caller enqueued before (reset, set_params) is ordered by the stream
     const double t0 = now_seconds();
 
@@ -555,6 +587,7 @@ int run_solve(sfmba_problem* p, const sfmba_options& o, sfmba_summary* summary, 
         DeviceBuffers dbu = p->db;
         if (sizeof(T) == 4) dbu.pu32 = p->d_pu32;       // F32J: the back-substitution's first sweep gathers fp32 camera records (ba_kernels.hip, k_cam_update / k_point_update)
         bool pcg_gated = false;
+        bool fell_back = false;
         RoctxRange rx_solve(p->roctx, pcg ? "solve: two-level CG on the reduced system" : "solve: Cholesky of the reduced system");
         if (pcg) {
             const int anchor = anchored_cg ? (first_linear_solve ? 1 : 2) : 0;
@@ -581,6 +614,7 @@ int run_solve(sfmba_problem* p, const sfmba_options& o, sfmba_summary* summary, 
         bool lm_done = false;
         while (!lm_done) {
             launch_back_substitution<T>(p->stream, p->ds, p->ds, dbu, prof);
+            probe_note_solver(p, pcg && !fell_back, fell_back ? 1 : 0);
             { ProfScope ps(prof, KID_CONTROL, p->stream); launch_control(p->stream, p->ds, dbu); }
             { ProfScope ps(prof, KID_EMPTY, p->stream); }   // two back-to-back event records: the bracketing overhead itself
             ++launched_controls;
@@ -615,6 +649,7 @@ int run_solve(sfmba_problem* p, const sfmba_options& o, sfmba_summary* summary, 
                         dense_cholesky_solve(p->stream, &p->solver, p->db.S, p->db.rhs, p->d_info, prof);
                         dbu.pcg_vec = nullptr; dbu.pcg_linv = nullptr; dbu.pcg_flags = nullptr; dbu.cg_gate = nullptr;
                         pcg_gated = false;
+                        fell_back = true;
                         ++cholesky_fallbacks;
                     } else {
                         dbu.cg_force = 1;
@@ -631,6 +666,7 @@ int run_solve(sfmba_problem* p, const sfmba_options& o, sfmba_summary* summary, 
                 const int it = (pcg_gated || dbu.pcg_vec) ? mb[4] : p->solver.run.launched;      // after a fallback: the launches that were spent
                 if (exact_pcg && it > cg_break_even) auto_prefers_cholesky = true;                 // the next linearisations of THIS solve are factorised
                 dense_pcg_note(&p->solver, (int)lin_hist.size(), it);
+                if (p->probe_on) p->probe.cg_iters = it;
                 sum.linear_iters += it;
                 lin_hist.push_back(it);
             }
@@ -755,6 +791,7 @@ void sfmba_problem_destroy(sfmba_problem* p) {
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     dense_solver_destroy(&p->solver);
+    if (p->d_probe) (void)hipFree(p->d_probe);
     if (p->db.trace && !p->trace_mapped) (void)hipFree(p->db.trace);
     p->arena.release();
     p->prof.destroy();
@@ -1593,6 +1630,37 @@ int sfmba_problem_get_profile(sfmba_problem* p, sfmba_kernel_time* out, int cap,
     return SFMBA_OK;
 }
 
+int sfmba_problem_set_step_probe(sfmba_problem* p, int enable) {
+    if (!p) return fail(SFMBA_ERR_INVALID_ARG, "NULL problem");
+    if (p->poisoned) return fail(SFMBA_ERR_INVALID_ARG, "poisoned problem (a failed sfmba_problem_append): destroy it");
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->stream) HIP_TRY(hipStreamSynchronize(p->stream));
+    p->probe_on = enable != 0;
+    p->probe = sfmba_step_probe{};
+    p->db.probe_z = nullptr; p->db.probe_dpt = nullptr;      // (armed by the next solve)
+    if (!p->probe_on && p->d_probe) { (void)hipFree(p->d_probe); p->d_probe = nullptr; p->probe_cap = 0; }
+    return SFMBA_OK;
+}
+
+int sfmba_problem_get_step_probe(sfmba_problem* p, double* z, double* dpt, sfmba_step_probe* info) {
+    if (!p) return fail(SFMBA_ERR_INVALID_ARG, "NULL problem");
+    if (!p->probe_on) return fail(SFMBA_ERR_INVALID_ARG, "the step probe is off (sfmba_problem_set_step_probe)");
+    if (info) *info = p->probe;
+    if (p->probe.family == 0 || !p->d_probe) return SFMBA_OK;      // no back-substitution has run since the probe was enabled
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (z) HIP_TRY(hipMemcpy(z, p->d_probe, sizeof(double) * (size_t)p->ds.d, hipMemcpyDeviceToHost));
+    if (dpt) {
+        const int npt = (int)p->apt_id.size();
+        std::vector<double> h((size_t)3 * std::max(npt, 1));
+        if (npt > 0) HIP_TRY(hipMemcpy(h.data(), p->d_probe + p->ds.ld, sizeof(double) * 3 * (size_t)npt, hipMemcpyDeviceToHost));
+        std::memset(dpt, 0, sizeof(double) * 3 * (size_t)p->n_pt_full);
+        for (int i = 0; i < npt; ++i)
+            for (int c = 0; c < 3; ++c) dpt[3 * (size_t)p->apt_id[i] + c] = h[3 * (size_t)i + c];
+    }
+    return SFMBA_OK;
+}
+
 // ---- kernel-level entry points ----------------------------------------------------------------
 int sfmba_problem_eval_residuals(sfmba_problem* p, double* residuals_out, double* cost_out) {
     if (p && !p->poisoned) { const int frc = flush_reset(p); if (frc) return frc; }
@@ -1747,6 +1815,7 @@ static int shard_begin_impl(sfmba_problem* p, const sfmba_options* opt, bool fus
     p->shard_host_iter = 0;
     std::memset(&p->shard_sum, 0, sizeof(p->shard_sum));
     p->db.shared_weight = p->shard_rank == 0 ? 1.0 : 0.0;
+    if ((rc = probe_arm(p))) return rc;
     LMState st;
     init_state(p, st, p->shard_opt);
     const int f32 = p->precision == SFMBA_PRECISION_F32J;
@@ -1831,8 +1900,11 @@ int sfmba_shard_solve_update(sfmba_problem* p) {
         if (it < 0) return fail(SFMBA_ERR_ALLOC, "PCG workspace allocation failed");
         p->shard_sum.linear_iters += it;
         dbu.pcg_vec = p->solver.vec; dbu.pcg_linv = p->solver.binv; dbu.pcg_flags = p->solver.flags;
+        probe_note_solver(p, true, 0);
+        if (p->probe_on) p->probe.cg_iters = it;
     } else {
         dense_cholesky_solve(p->stream, &p->solver, p->db.S, p->db.rhs, p->d_info, nullptr);
+        probe_note_solver(p, false, 0);
     }
     if (p->precision == SFMBA_PRECISION_F32J) launch_back_substitution<float>(p->stream, p->ds, p->ds, dbu, nullptr);      // (one DeviceBuffers for both: sum u . r is formed in ONE of the two)
     else launch_back_substitution<double>(p->stream, p->ds, p->ds, dbu, nullptr);
@@ -2103,6 +2175,8 @@ static int solve_sharded_impl(sfmba_problem* p, const sfmba_options* opt, sfmba_
             volatile int* mb = p->h_lm_mail;
             for (;;) {
                 if (f32) launch_back_substitution<float>(p->stream, p->ds, dsp, dbu, nullptr); else launch_back_substitution<double>(p->stream, p->ds, dsp, dbu, nullptr);
+                if (!dist_cg) probe_note_solver(p, true, 0);
+                else probe_note(p, implicit_cg ? SFMBA_FAMILY_IMPLICIT : row_cg ? SFMBA_FAMILY_DIST_ROWS : SFMBA_FAMILY_DIST_BLOCKS, implicit_cg ? 0 : x32 ? 1 : 0, coarse_cg ? 8 : 0, 0);
                 launch_shard_pack(p->stream, p->db, p->d_scal, 2, p->shard_rank);
                 if ((rc = reduce(sfmba_shard_scalars_buf(p), SFMBA_SHARD_SCALARS))) return rc;
                 dbu.shard_scal = p->d_scal;        // k_lm_control reads the sums from the all-reduced block
@@ -2135,6 +2209,7 @@ static int solve_sharded_impl(sfmba_problem* p, const sfmba_options* opt, sfmba_
                 } else if (dense_pcg_more(p->stream, &p->solver, 8, nullptr) == 0) dbu.cg_force = 1;
             }
             dense_pcg_note(&p->solver, p->shard_host_iter, mb[4]);
+            if (p->probe_on) p->probe.cg_iters = mb[4];
             p->shard_sum.linear_iters += mb[4];
             if (o.verbose) std::fprintf(stderr, "[sfmba shard %d/%d] LM iteration %d: %d CG iterations (%d launched), termination %d\n", p->shard_rank, p->shard_world, mb[3], mb[4], dist_cg ? dcg_launched : 0, mb[1]);
             p->shard_host_iter = mb[3];

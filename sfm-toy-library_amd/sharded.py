@@ -62,6 +62,14 @@ class HipShardBackend:
         self.setup_t = torch.as_tensor(_DevicePtr(L.sfmba_shard_setup_buf(self._h), L.sfmba_shard_setup_len(self._h)), device=dev)
         self.scalars_t = torch.as_tensor(_DevicePtr(L.sfmba_shard_scalars_buf(self._h), 80), device=dev)
 
+    # -- step probe (include/sfmba.h, sfmba_problem_set_step_probe) --
+    def set_step_probe(self, enable):
+        capi._check(self.L.sfmba_problem_set_step_probe(self._h, C.c_int(1 if enable else 0)))
+
+    def step_probe(self):
+        """(z, dpt, info) of this rank's last back-substitution; dpt in this handle's point order."""
+        return capi.get_step_probe(self._h, int(self.L.sfmba_problem_reduced_dim(self._h)), len(self._template[1]))
+
     # -- protocol --
     def begin(self, opt):
         self._opt = opt

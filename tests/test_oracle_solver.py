@@ -245,3 +245,54 @@ def test_final_rms_is_insensitive_to_the_upstream_minimizer_ordering(oracle, sfm
         assert out[1][1]["successful_steps"] in (s0["successful_steps"], s0["successful_steps"] + 1)
     # variant 2 differs from 0 only on a measure-zero tie (the oracle's OpenMP reductions are not bitwise repeatable: 1e-12)
     assert abs(out[2][1]["final_cost"] - s0["final_cost"]) <= 1e-12 * s0["final_cost"] and np.allclose(out[2][2], out[0][2], rtol=0, atol=1e-10)
+
+
+# ---- sfmba_oracle_lm_step: the exact LM step the step checks of the solver families are held to (tests/linear_step_check.py) ----
+@pytest.fixture(scope="module")
+def step_fixture(oracle, sfm):
+    prob = sfm.make_problem("small")
+    return prob, oracle.lm_step(prob, 1e4)
+
+
+def test_lm_step_solves_the_reduced_system(oracle, sfm, step_fixture):
+    prob, st = step_fixture
+    S, rhs, scale, info = oracle.build_reduced(prob, 1e4)
+    assert st["info"] == 0 and info == 0
+    np.testing.assert_array_equal(st["scale"], scale)
+    np.testing.assert_allclose(st["S"], S, rtol=0, atol=1e-13 * np.abs(S).max())
+    q = np.longdouble
+    r = rhs.astype(q) - S.astype(q) @ st["z"].astype(q)
+    assert float(np.sqrt(np.sum(r * r)) / np.linalg.norm(rhs)) <= 1e-13
+    assert np.all(st["vcond"] >= 1.0) and np.all(np.isfinite(st["vcond"]))
+
+
+def test_lm_step_is_the_first_step_of_solve(oracle, sfm, step_fixture):
+    prob, _ = step_fixture
+    # one thread: the reduced system is then summed in the same order by both calls (with several, the order of the thread-private
+    # copies' contributions varies and the steps differ by kappa(S) u, not by rounding of the update)
+    n = oracle.num_threads()
+    oracle.set_num_threads(1)
+    try:
+        st = oracle.lm_step(prob, 1e4)
+        cam, pt, f, summ, trace = oracle.solve(prob, sfm.SfmbaOptions.defaults(max_seconds=0.0, max_iters=1))
+    finally:
+        oracle.set_num_threads(n)
+    assert summ["successful_steps"] == 1           # the fixture's first step is accepted
+    act = np.unique(prob.obs_cam)
+    nc = 6 * len(act)
+    cam_step = prob.cam6[act].ravel() - st["scale"][:nc] * st["z"][:nc]
+    ulp = 8 * np.spacing(np.maximum(np.abs(prob.cam6[act].ravel()), np.abs(cam_step)))
+    assert np.all(np.abs(cam[act].ravel() - cam_step) <= ulp), np.abs(cam[act].ravel() - cam_step).max()
+    pt_step = prob.pt3 - st["dpt"]
+    assert np.all(np.abs(pt - pt_step) <= 8 * np.spacing(np.maximum(np.abs(prob.pt3), np.abs(pt_step))))
+    f_step = prob.focal - st["scale"][-1] * st["z"][-1]
+    assert abs(f - f_step) <= 8 * np.spacing(max(abs(prob.focal), abs(f_step)))
+
+
+def test_lm_step_back_substitutes_a_given_z(oracle, sfm, step_fixture):
+    prob, st = step_fixture
+    again = oracle.lm_step(prob, 1e4, z=st["z"])
+    np.testing.assert_array_equal(again["z"], st["z"])
+    np.testing.assert_array_equal(again["dpt"], st["dpt"])
+    unref = np.setdiff1d(np.arange(prob.n_pt), prob.obs_pt)
+    assert np.all(st["dpt"][unref] == 0.0)
