@@ -81,6 +81,8 @@ enum { SFMBA_PRECISION_F64  = 0,    /* everything fp64 (parity mode) */
                                        fp64, and so are the residuals, the cost, the reduced system and its solve (ABI v4 summed a block's
                                        up-to-512 pair products in fp32 before widening).  The back-substitution evaluates the Jacobian-type terms of an observation (J x step,
                                        C = B~ L^-T) from an fp32 copy of the camera's R, t and step; the TRIAL residuals, which decide accept / reject, from the fp64 pose.
+                                       The pair pass (the off-diagonal blocks of the reduced matrix), which forms no residual, evaluates the PROJECTION of
+                                       its observations in fp32 as well, in both of its geometries (one wave or sixteen lanes per block).
                                        What to expect (tests/test_gpu_baseline_parity.py): final cost within 1e-6
                                        relative (measured 3e-13) and final RMS within 1e-4 px of the fp64 solve (measured < 1e-9 px),
                                        parameters within ~2e-5 -- EXCEPT points on weakly constrained tracks: a point seen by two

@@ -629,8 +629,10 @@ __device__ __forceinline__ void pair_epilogue(const DeviceStructure& ds, const D
 // One wave per CHUNK of a block: at most SFMBA_PAIR_CHUNK pairs (eight rounds of 64), so lane-local sums in T never pile up more than eight
 // terms and no wave runs longer than eight rounds whatever the co-visibility (structure_build.hip, build_pair_chunks).  The per-camera
 // factor diag(R K', I) of the camera blocks is applied once per block in the epilogue (pair_G), the pair loop works on [ -[R X]x | I ], the
-// projection Jacobian and C: 295 wave instructions per 64 pairs, 128 registers (four waves per SIMD) in fp32 mode.  A block of several
-// chunks leaves its partial sums in pair_partial; k_schur_combine (the next launch) adds them and runs the epilogue.
+// projection Jacobian and C.  In fp32 mode both observations of a pair are evaluated at once as packed fp32 halves and the 6x6 update is
+// summed in its rank-2 form (sfmba_device.h: obs_factored_ab, pair_product_ab): 139 wave instructions per 64 pairs, 96 registers (five
+// waves per SIMD; tools/pair_isa_count.py counts them from the compiler's output).  A block of several chunks leaves its partial sums in
+// pair_partial; k_schur_combine (the next launch) adds them and runs the epilogue.
 template <typename T, int MODE>
 __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 4 : 2)) void k_schur_pairs(DeviceStructure ds, DeviceBuffers db) {
     __shared__ double tile[36];
@@ -679,22 +681,68 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 4 : 2)) void k_schur_pairs(De
         const LMState* st = db.st;
         const int cur = st->cur;
         const double focal = st->focal[cur];
-        CamG<T> ca, cb;
-        load_cam_g<T>(db.camtab[cur], __builtin_amdgcn_readfirstlane(cj.x), ds.ncam, ca);
-        load_cam_g<T>(db.camtab[cur], __builtin_amdgcn_readfirstlane(cj.y), ds.ncam, cb);
         const PtRecA<T>* PA = reinterpret_cast<const PtRecA<T>*>(db.PA);
-        // lane (s, g) owns pair p0 + 16 s + g of a round; the point slot of the NEXT round's pair is fetched one round ahead (one
-        // dependent memory level per round: the point-table entry)
+        // lane (s, g) owns pair p0 + 16 s + g of a round.  A round issues the loads of its own point-table entry and of the NEXT round's point
+        // slot together, and the next entry's address is formed from that slot at the round's end: one dependent memory level per round (the
+        // entry), the slot's latency behind the round's arithmetic.  (Carried as a bare slot the load is moved by the compiler to the top of
+        // the round that uses it -- a phi of loads becomes a load of a phi -- and the round waits for two dependent loads; the address is
+        // arithmetic on the loaded value and stays in the round that loaded it.)  Rounds past the end re-read the chunk's last pair.
         const int mine = 16 * s + g;
-        int pt_next = ds.pair_pt[pbeg < p1 ? (pbeg + mine < p1 ? pbeg + mine : p1 - 1) : 0];
-        for (int p0 = pbeg; p0 < p1; p0 += 64) {
-            const PtRecA<T> pa = load_ptrec(PA + pt_next);
-            { const int p = p0 + 64 + mine; pt_next = ds.pair_pt[p < p1 ? p : p1 - 1]; }
-            T ga[GREC], gb[GREC];
-            obs_factored<T>(ca, focal, pa.X, pa.L, ga);
-            obs_factored<T>(cb, focal, pa.X, pa.L, gb);
-            if (p0 + mine >= p1) ga[3] = (T)0;      // this lane's pair lies beyond the chunk: contribute nothing (N carries f_a / p_z)
-            pair_product_factored<T, PairAcc<T>>(ga, gb, acc);
+        const int plast = pbeg < p1 ? p1 - 1 : 0;
+        const PtRecA<T>* ent_next = PA + ds.pair_pt[pbeg + mine < p1 ? pbeg + mine : plast];
+        auto rounds = [&](auto&& body) {
+            for (int p0 = pbeg; p0 < p1; p0 += 64) {
+                const PtRecA<T> pa = load_ptrec(ent_next);
+                const int p = p0 + 64 + mine;
+                const int pt = ds.pair_pt[p < p1 ? p : plast];
+                body(pa, p0 + mine < p1);               // (pair inside the chunk?)
+                ent_next = PA + pt;
+            }
+        };
+        if constexpr (sizeof(T) == 4) {
+            // fp32-Jacobian mode: both observations of a pair as the halves of packed fp32 values (obs_factored_ab).  Lane k < 12 fetches
+            // value k (R, t) of camera a, lane 12 + k that of camera b: one load and one conversion, then 24 lane reads into uniform pairs.
+            const double* tab = db.camtab[cur];
+            const int ja = __builtin_amdgcn_readfirstlane(cj.x), jb = __builtin_amdgcn_readfirstlane(cj.y);
+            const int kk = lane < 12 ? lane : (lane < 24 ? lane - 12 : 0);
+            const int rv = __float_as_int((float)tab[cam_tab_index(kk, lane < 12 ? ja : jb, ds.ncam)]);
+            v2f R[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k)
+                R[k] = v2f{__int_as_float(__builtin_amdgcn_readlane(rv, k)), __int_as_float(__builtin_amdgcn_readlane(rv, 12 + k))};
+            const bool fo_a = tab[cam_tab_index(CT_SMALL, ja, ds.ncam)] != 0.0, fo_b = tab[cam_tab_index(CT_SMALL, jb, ds.ncam)] != 0.0;   // wave-uniform
+            const float focal_t = (float)focal;
+            if constexpr (SFMBA_PAIR_ACC == 1) {
+                PairAccAB accp;
+                accp.clear();
+                rounds([&](const PtRecA<T>& pa, bool live) {
+                    v2f gab[GREC];
+                    obs_factored_ab(R, fo_a, fo_b, focal_t, (float)pa.X[0], (float)pa.X[1], (float)pa.X[2], pa.L, gab);
+                    pair_product_ab(gab, live, accp);
+                });
+                accp.unpack(acc);
+            } else {
+                rounds([&](const PtRecA<T>& pa, bool live) {
+                    v2f gab[GREC];
+                    obs_factored_ab(R, fo_a, fo_b, focal_t, (float)pa.X[0], (float)pa.X[1], (float)pa.X[2], pa.L, gab);
+                    T ga[GREC], gb[GREC];
+#pragma unroll
+                    for (int k = 0; k < GREC; ++k) { ga[k] = gab[k].x; gb[k] = gab[k].y; }
+                    if (!live) ga[3] = (T)0;            // this lane's pair lies beyond the chunk: contribute nothing (N carries f_a / p_z)
+                    pair_product_factored<T, PairAcc<T>>(ga, gb, acc);
+                });
+            }
+        } else {
+            CamG<T> ca, cb;
+            load_cam_g<T>(db.camtab[cur], __builtin_amdgcn_readfirstlane(cj.x), ds.ncam, ca);
+            load_cam_g<T>(db.camtab[cur], __builtin_amdgcn_readfirstlane(cj.y), ds.ncam, cb);
+            rounds([&](const PtRecA<T>& pa, bool live) {
+                T ga[GREC], gb[GREC];
+                obs_factored<T>(ca, focal, pa.X, pa.L, ga);
+                obs_factored<T>(cb, focal, pa.X, pa.L, gb);
+                if (!live) ga[3] = (T)0;                // this lane's pair lies beyond the chunk: contribute nothing (N carries f_a / p_z)
+                pair_product_factored<T, PairAcc<T>>(ga, gb, acc);
+            });
         }
     }
     // Sum of the 36 entries over the 64 lanes by a halving butterfly: afterwards lane `base` -- 36 of the 64 lanes -- owns ONE

@@ -44,7 +44,8 @@ constexpr int YREC = 16;
 // ---- per-point table (round 3): what the reduced-system passes need about a POINT to RE-EVALUATE the blocks of one of its
 // observations instead of gathering a 64-byte record per observation (the records of BASELINE config 3 are 64 MB gathered ~10 times
 // at random; this table is 4.8 MB and stays in every XCD's L2).  Written by k_point_build once per linearisation.
-//   PtRecA: X (3 doubles: the projection is evaluated in fp64, exactly as the point pass does) | L = L^-1 diag(s_p) (6 values T:
+//   PtRecA: X (3 doubles: the projection is evaluated in fp64, exactly as the point pass does; the pair pass, which forms no residual,
+//           rounds X to T in fp32 mode) | L = L^-1 diag(s_p) (6 values T:
 //           l00 l10 l11 l20 l21 l22 -- C = B L^T row by row)                    64 B (48 + pad: one sector, so that the four lanes of
 //           a quad can fetch it with ONE request) in fp32 mode, 80 B (72 + pad) in fp64 mode
 //   PtRecB: t = L^-1 b_p (3 T) | y_f = L^-1 E_f (3 T)                           (camera-diagonal pass only)
@@ -347,10 +348,10 @@ __device__ __forceinline__ void obs_factored(const CamG<T>& cam, double focal, c
         g[6 + 3 * r + 2] = b0 * l20 + b1 * l21 + b2 * l22;
     }
 }
-// The same with the PROJECTION in the precision of the Jacobian blocks as well (small-block pair pass in fp32-Jacobian mode: every value
-// the pair product uses is rounded to T anyway, the pass needs no residual, and a camera row held per lane is 12 registers instead of 24;
-// measured at BASELINE config 5: 468 -> 431 us per launch.  The wave-per-chunk pass keeps the fp64 projection: with its two rows in
-// scalar registers the fp32 form is SLOWER, 62 -> 72 us).  Rt: R (9, row-major) and t (3) in T.
+// The same with the PROJECTION in the precision of the Jacobian blocks as well (fp32-Jacobian mode: every value the pair product uses is
+// rounded to T anyway and the pass needs no residual).  This scalar form serves the sixteen-lane pair pass, whose column camera is held
+// per lane (12 registers instead of 24; measured at BASELINE config 5: 468 -> 431 us per launch); the wave-per-chunk pass evaluates both
+// observations of a pair at once (obs_factored_ab below).  Rt: R (9, row-major) and t (3) in T.
 template <typename T>
 __device__ __forceinline__ void obs_factored_t(const T (&Rt)[12], bool first_order, T focal, T X0, T X1, T X2, const T L[6], T g[GREC]) {
     const T rx = Rt[0] * X0 + Rt[1] * X1 + Rt[2] * X2;
@@ -373,6 +374,40 @@ __device__ __forceinline__ void obs_factored_t(const T (&Rt)[12], bool first_ord
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const T b0 = B[3 * r], b1 = B[3 * r + 1], b2 = B[3 * r + 2];
+        g[6 + 3 * r + 0] = b0 * L[0];
+        g[6 + 3 * r + 1] = b0 * L[1] + b1 * L[2];
+        g[6 + 3 * r + 2] = b0 * L[3] + b1 * L[4] + b2 * L[5];
+    }
+}
+// BOTH observations of a pair at once, fp32 only: a pair is the SAME formula on the SAME point under two cameras, so with (camera a,
+// camera b) as the (lo, hi) halves of every value the whole evaluation is packed fp32 arithmetic (v_pk_*) on operands that already sit side
+// by side -- the two camera rows are twelve wave-uniform pairs {Ra[k], Rb[k]}, the point's X and L are broadcast, nothing is moved.  The
+// expressions are those of obs_factored_t.  R[0..8]: rotation (row-major), R[9..11]: translation; g[k] = {ga[k], gb[k]}.
+// (Two calls of the scalar obs_factored_t on rows in scalar registers, left to the compiler's own packing, were SLOWER than the fp64
+// projection, 62 -> 72 us; this form together with pair_product_ab: 279 -> 139 instructions per round of 64 pairs, 62.0 -> 49.0 us per launch
+// at BASELINE config 3, profiles/pair_packed_ab.txt.)
+typedef float v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void obs_factored_ab(const v2f (&R)[12], bool fo_a, bool fo_b, float focal, float X0, float X1, float X2, const float L[6], v2f g[GREC]) {
+    const v2f rx = R[0] * X0 + R[1] * X1 + R[2] * X2;
+    const v2f ry = R[3] * X0 + R[4] * X1 + R[5] * X2;
+    const v2f rz = R[6] * X0 + R[7] * X1 + R[8] * X2;
+    const v2f pz = rz + R[11];
+    v2f iz = {__builtin_amdgcn_rcpf(pz.x), __builtin_amdgcn_rcpf(pz.y)};
+    iz = iz * (2.0f - pz * iz);                               // estimate + one Newton step
+    const v2f xp = (rx + R[9]) * iz, yp = (ry + R[10]) * iz, fz = focal * iz;
+    g[0] = v2f{fo_a ? X0 : rx.x, fo_b ? X0 : rx.y};           // first-order branch: wave-uniform per half
+    g[1] = v2f{fo_a ? X1 : ry.x, fo_b ? X1 : ry.y};
+    g[2] = v2f{fo_a ? X2 : rz.x, fo_b ? X2 : rz.y};
+    g[3] = fz; g[4] = xp; g[5] = yp;
+    v2f B[6];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        B[c] = fz * (R[c] - xp * R[6 + c]);
+        B[3 + c] = fz * (R[3 + c] - yp * R[6 + c]);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const v2f b0 = B[3 * r], b1 = B[3 * r + 1], b2 = B[3 * r + 2];
         g[6 + 3 * r + 0] = b0 * L[0];
         g[6 + 3 * r + 1] = b0 * L[1] + b1 * L[2];
         g[6 + 3 * r + 2] = b0 * L[3] + b1 * L[4] + b2 * L[5];
@@ -414,6 +449,51 @@ __device__ __forceinline__ void pair_product_factored(const T ga[GREC], const T 
         acc[6 * (3 + r) + 1] += (A)(b2 * n0 - b0 * n2);
         acc[6 * (3 + r) + 2] += (A)(b0 * n1 - b1 * n0);
         acc[6 * (3 + r) + 3] += (A)n0; acc[6 * (3 + r) + 4] += (A)n1; acc[6 * (3 + r) + 5] += (A)n2;
+    }
+}
+
+// The same update from the packed evaluation (obs_factored_ab: g[k] = {ga[k], gb[k]}), fp32 lane sums only, written so that every packed
+// operand is formed side by side.  With U = M P_b (2 x 3; M = f_a f_b C_a C_b^T, row r: u_r) every row of W = [T; N] is a combination
+// alpha_i u_0 + beta_i u_1 whose coefficients depend on camera a alone,
+//   N: (1, 0), (0, 1), (-x_a, -y_a)      T = [X_a]x N: (-a1 x_a, -a1 y_a - a2), (a2 + a0 x_a, a0 y_a), (-a1, a0)
+// and row i of the update is [X_b x w_i | w_i], so the 6 x 6 update is the RANK-2 form alpha V_0^T + beta V_1^T with the 6-vectors
+// V_r = [X_b x u_r | u_r].  Halves: V[k] = {V_0[k], V_1[k]} (the two rows of M side by side: the only values that have to be brought
+// together are C_a's two rows and a few coefficients); the 36 sums are kept as 18 pairs of ROWS -- (0, 1), (2, 5), (3, 4) -- whose
+// coefficient pairs multiply V[k]'s halves as broadcasts.  Rows 3 and 4 have coefficients (1, 0) and (0, 1): their pair is V[k] itself.
+struct PairAccAB {
+    v2f A[6], B[6], C[6];     // rows (0, 1), (2, 5), (3, 4); k = column
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { A[k] = v2f{0.0f, 0.0f}; B[k] = v2f{0.0f, 0.0f}; C[k] = v2f{0.0f, 0.0f}; }
+    }
+    __device__ __forceinline__ void unpack(float acc[36]) const {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            acc[k] = A[k].x; acc[6 + k] = A[k].y; acc[12 + k] = B[k].x; acc[30 + k] = B[k].y; acc[18 + k] = C[k].x; acc[24 + k] = C[k].y;
+        }
+    }
+};
+// live: false for a lane whose pair lies beyond the chunk (it contributes nothing: M carries f_a / p_z)
+__device__ __forceinline__ void pair_product_ab(const v2f g[GREC], bool live, PairAccAB& acc) {
+    const float ff = (live ? g[3].x : 0.0f) * g[3].y;
+    const v2f ca0 = {g[6].x, g[9].x}, ca1 = {g[7].x, g[10].x}, ca2 = {g[8].x, g[11].x};      // C_a, its two rows as halves
+    const float xa = g[4].x, ya = g[5].x, xb = g[4].y, yb = g[5].y;
+    const float a0 = g[0].x, a1 = g[1].x, a2 = g[2].x, b0 = g[0].y, b1 = g[1].y, b2 = g[2].y;
+    v2f V[6];
+    V[3] = ff * (ca0 * g[6].y + ca1 * g[7].y + ca2 * g[8].y);
+    V[4] = ff * (ca0 * g[9].y + ca1 * g[10].y + ca2 * g[11].y);
+    V[5] = -(V[3] * xb + V[4] * yb);
+    V[0] = b1 * V[5] - b2 * V[4];
+    V[1] = b2 * V[3] - b0 * V[5];
+    V[2] = b0 * V[4] - b1 * V[3];
+    const v2f q = {-a1, a0};
+    const v2f al01 = q * xa + v2f{0.0f, a2}, be01 = q * ya - v2f{a2, 0.0f};
+    const v2f al25 = {-a1, -xa}, be25 = {a0, -ya};
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        acc.A[k] += al01 * V[k].x; acc.A[k] += be01 * V[k].y;       // (two fused multiply-adds each)
+        acc.B[k] += al25 * V[k].x; acc.B[k] += be25 * V[k].y;
+        acc.C[k] += V[k];
     }
 }
 
