@@ -71,7 +71,7 @@ struct TraceRow {   // same layout as sfmba_iteration
     double cost, cost_change, gradient_max_norm, step_norm, relative_decrease, trust_region_radius;
 };
 
-// Static structure of a problem, all device pointers (built once on the host, see sfmba_api.cpp).
+// Static structure of a problem, all device pointers (built once on the host, see problem_build.hip).
 struct DeviceStructure {
     int ncam, npt, nobs;      // active cameras / points, observations
     int pt_base;              // first point slot of the passes that walk the points in slot order without pt_order (k_xnorm): 0, or the first own slot of a

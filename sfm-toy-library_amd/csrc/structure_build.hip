@@ -61,7 +61,7 @@ __global__ void k_block_ptr(int nblock, int npair, const unsigned* __restrict__ 
 // d_pair_off[i] = number of pairs of the points before i (npt + 1 entries, device; build_point_major), npair their total (the caller
 // knows it from its per-point observation counts).  On success *d_pair_pt (npair point slots) and *d_blk_ptr (nblock + 1 ints) live in
 // `arena`; the sort's temporaries come from `scratch`, which the caller keeps until the stream has drained: nothing here waits
-// for the device (the whole structure build is ONE enqueue, sfmba_api.hip build_structure).  Returns 0, or a hipError_t value.
+// for the device (the whole structure build is ONE enqueue, problem_build.hip build_structure).  Returns 0, or a hipError_t value.
 int build_pair_lists(hipStream_t s, DeviceArena* arena, DeviceArena* scratch_arena, int npt, int nobs, int ncam, int nblock, const int* d_pt_ptr, const int* d_obs_pt,
                      const int* d_obs_cam, const long long* d_pair_off, long long npair, int** d_blk_ptr, int** d_pair_pt) {
     *d_blk_ptr = nullptr; *d_pair_pt = nullptr;

@@ -89,7 +89,7 @@ def test_concurrent_resident_problems_are_independent(capi, sfm):
 
 def test_concurrent_structure_builds(capi, sfm):
     """Problems CREATED from concurrent host threads: one build at a time gets the process's helper thread for its host half, the
-    others run both halves themselves (sfmba_api.hip build_structure) -- every one must come out like a build made alone."""
+    others run both halves themselves (problem_build.hip build_structure) -- every one must come out like a build made alone."""
     import threading
     probs = [sfm.make_problem("cfg4", n_pt=3000, sub=g) for g in range(8)]
     opt = capi.default_options(max_seconds=0.0, precision=1, linear_solver=1)
