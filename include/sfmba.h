@@ -145,7 +145,7 @@ typedef struct sfmba_options {
     int    verbose;                   /* 0 silent (BA.cpp:177), 1 per-iteration lines on stderr */
     int    pcg_anchored;              /* 1: inside an LM solve the CG tolerance is anchored to the FIRST iteration's right-hand side,
                                          |r| <= tol * max(|b_k|, |b_first|), never looser than 1e-4 |b_k| -- every LM step is then solved
-                                         to the same ABSOLUTE accuracy (dense_solver.hip).  0: plain relative residual. */
+                                         to the same ABSOLUTE accuracy (pcg_common.h pcg_threshold_base).  0: plain relative residual. */
     /* ---- ABI v4: behaviour switches that were environment variables only (a C caller could not set them per problem or
        thread-safely).  0 = library default, 1 = on, -1 = off.  ABI v4 let the environment variable named beside each switch
        override the field; since ABI v5 NOTHING below sfmba_problem_create* reads the environment: the fields are the only way
@@ -160,7 +160,7 @@ typedef struct sfmba_options {
                                          The sharded solve keeps the eight global vectors (the choice would have to be agreed between the ranks). */
     int    pcg_symmetric;             /* ABI v6 (the slot ABI v4 called pcg_persistent; reserved in v5)  default on : the streaming CG (d > 1280, no
                                          segmented coarse space, not a deterministic handle) reads ONE triangle of S~ per iteration and uses every entry
-                                         twice (k_pcg_iter_sym); the pair pass then writes that triangle only.  -1 = both triangles, the round-5 kernels */
+                                         twice (k_sy_prod, pcg_symmetric.hip); the pair pass then writes that triangle only.  -1 = both triangles, the round-5 kernels */
     int    pcg_f32_matrix;            /* SFMBA_PCG_F32_MATRIX     default on : F32J + streaming CG (d > 1280) store S~ in fp32 */
     int    early_linearise;           /* SFMBA_EARLY_LINEARISE    default on : next linearisation enqueued before the host reads the verdict */
     int    shard_two_phase;           /* SFMBA_SHARD_TWO_PHASE    default on : sharded CG path exchanges (A) diagonal data, (B) preconditioned blocks */

@@ -143,7 +143,7 @@ struct DeviceBuffers {
     int trace_cap;
     int* lin_info;            // dense-solver status word (device), consumed and cleared by k_lm_control
     int* fin_counter;         // arrival counter of k_finalize (last block runs the post-linearisation logic)
-    // block-Jacobi PCG: the solution is x~ with z = Lb^-T x~ (dense_solver.hip); k_cam_update applies Lb^-T itself
+    // block-Jacobi PCG: the solution is x~ with z = Lb^-T x~ (pcg_common.h); k_cam_update applies Lb^-T itself
     const double* pcg_vec;    // x~ buffers (two, selected by pcg_flags[2]); nullptr when the Cholesky path wrote z to rhs
     const double* pcg_linv;
     const int* pcg_flags;
@@ -153,7 +153,7 @@ struct DeviceBuffers {
     int cg_force;             //           (the host enqueues them behind a CG batch of guessed length without waiting for it)
     double* pcg_F;            // [d][ld] preconditioned reduced matrix S~ written directly by k_schur_pairs (PCG mode)
     float* pcg_F32;           // the same in fp32 instead (streaming CG path, d > 1280: the matvec is HBM-bound); else null
-    int pcg_upper_only;       // 1: the CG reads ONE triangle of S~ (dense_solver.hip, symmetric streaming path): store_block_entry writes the upper block only
+    int pcg_upper_only;       // 1: the CG reads ONE triangle of S~ (pcg_symmetric.hip, symmetric streaming path): store_block_entry writes the upper block only
     double* pcg_zero;         // ... and its coarse set-up ADDS S~ W~ into this buffer (atomics): k_finalize(pcg = 1) zeroes pcg_zero_n doubles of it; else null
     int pcg_zero_n;
     double* pcg_bt;           // [ld]    Lb^-1 rhs
@@ -162,7 +162,7 @@ struct DeviceBuffers {
     double* pair_G;           // [ncam*36] per-camera factor the factored pair pass applies from both sides of a block (row-major 6 x 6):
                               // Linv D E^T (PCG: k_finalize) or D E^T (exact solver: k_pair_factors), E = diag(R K', I) -- sfmba_device.h
     double* pcg_W;            // [8][ld] gauge vectors in the transformed unknowns (coarse space of the two-level CG preconditioner,
-                              //         dense_solver.hip), written by k_finalize (PCG mode); null = not wanted
+                              //         pcg_common.h "Coarse space"), written by k_finalize (PCG mode); null = not wanted
     int* lm_mailbox;          // host-mapped {seq, termination, message, iter}: polled by the host instead of a D2H copy + sync
     double* probe_z;          // step probe (sfmba_problem_set_step_probe), else null: [d] the reduced step z k_cam_update consumed (slot order, focal last)
     double* probe_dpt;        //   ... and [npt][3] the point step dX k_point_update subtracted (point slots)

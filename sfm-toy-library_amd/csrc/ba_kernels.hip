@@ -1173,7 +1173,7 @@ template void launch_cam_diag<double>(hipStream_t, const DeviceStructure&, const
 // finalize: damping of the reduced diagonal, camera/focal part of the gradient max-norm, padding
 // ------------------------------------------------------------------------------------------
 // Rows of camera j in the 8 gauge vectors of the problem, in the unknowns of the block-Jacobi transformed reduced system
-// (coarse space of the two-level CG preconditioner, dense_solver.hip).  adjustBundle() holds no block constant
+// (coarse space of the two-level CG preconditioner, pcg_common.h "Coarse space").  adjustBundle() holds no block constant
 // (BA.cpp:160-164), so the undamped problem does not change under a similarity transform of the scene; in camera
 // parameters (p = R X + t), to first order:
 //   world translation a   (X -> X + a):        dt = -R a,  dw = 0
@@ -1408,7 +1408,7 @@ __global__ __launch_bounds__(256) void k_finalize(DeviceStructure ds, DeviceBuff
         }
         if (bad && writer) atomicAdd(slot_ptr(db, ACC_BAD_LIN), 1.0);
         if (pcg) {
-            // Linv of the damped block (row-major lower, zeros above), see dense_solver.hip
+            // Linv of the damped block (row-major lower, zeros above), see dense_solver.hip k_pcg_blockchol
             double L[6][6], Li[6][6];
 #pragma unroll
             for (int r = 0; r < 6; ++r)

@@ -1,5 +1,5 @@
 // chol_tile.h -- one workgroup factors one 64x64 SPD tile held in LDS and forms the inverse of the factor on the way
-// (device functions shared by dense_solver.hip and tools/micro/chol_tile_bench.hip).
+// (device functions shared by dense_cholesky.hip and tools/micro/chol_tile_bench.hip).
 //
 // The diagonal tile of a blocked Cholesky is the serial part of the factorisation: 64 pivots, each one a dependent chain
 //   pivot -> 1/sqrt -> scaled column -> update of the next pivot

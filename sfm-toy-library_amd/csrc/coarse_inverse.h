@@ -1,5 +1,5 @@
 // coarse_inverse.h -- the 8 x 8 inverse of the coarse matrix E = W~^T S~ W~ of the two-level CG preconditioner, shared by the one-GPU CG
-// kernels (dense_solver.hip) and the distributed CG of the sharded solve (dist_cg.hip).
+// kernels (pcg_fast.hip) and the distributed CG of the sharded solve (dist_cg.hip).
 #pragma once
 #include "sfmba_device.h"
 

@@ -9,6 +9,17 @@ namespace sfmba {
 
 constexpr int CHOL_NB = 64;
 
+// The path one CG solve takes through the families of pcg_common.h: chosen once per solve (dense_solver.hip, dense_pcg_path), read by everything else.
+struct CgPath {
+    int family = 0;           // SFMBA_FAMILY_PCG_* (include/sfmba.h)
+    bool f32 = false;         // S~ is read from Sfull32 (streaming families only)
+    bool coarse = false;      // a coarse space is in use; coarse_vectors: 0, 8, 57 (segments) or 7 G + 1 (segments, streaming path)
+    int coarse_vectors = 0;
+    int rows_per_wg = 0, nwg = 0;     // row geometry of the product and of the 8-vector set-up
+    size_t lds = 0;           // dynamic LDS of the iteration kernel
+    bool first_launch_is_iteration = false;   // the first launch of the solve is also CG iteration 1 (fast family with the coarse space)
+};
+
 // Workspace of the reduced-system solver (allocated once per problem).
 struct DenseSolver {
     int ld = 0;               // padded dimension (multiple of CHOL_NB, > d)
@@ -19,7 +30,7 @@ struct DenseSolver {
     double* Sfull = nullptr;  // [ld*ld] full symmetric copy (PCG only, allocated lazily)
     float* Sfull32 = nullptr; // fp32 copy for the streaming path (allocated by dense_pcg_want_f32)
     // launch parameters of the running CG solve (dense_pcg_solve ... dense_pcg_more)
-    struct CgRun { int nwg = 0, rows_per_wg = 0; size_t lds = 0; bool fast = false, f32 = false, coarse = false, ml = false, sg = false, sym = false; double tol2 = 0.0; int in = 1, launched = 0, max_iters = 0; int* info = nullptr; } run;
+    struct CgRun { CgPath path; double tol2 = 0.0; int in = 1, launched = 0, max_iters = 0; int* info = nullptr; } run;
     bool use_f32 = false;     // set by the caller per solve: the preconditioned matrix of THIS solve lives in Sfull32
     bool symmetric = false;   // set by the caller per solve: take the symmetric streaming path (k_sy_vec + k_sy_prod: the UPPER triangle of S~ read once per
                               // iteration) where it applies -- d > 1280, no segmented coarse space
@@ -31,12 +42,12 @@ struct DenseSolver {
     double* sym_zero = nullptr; size_t sym_zero_n = 0;   // (= AWt) what the caller's linearisation has to zero
     double* vec = nullptr;    // [9*ld] x[2] r[2] p[2] q[2] btilde
     double* part = nullptr;   // [2][9][1024] per-workgroup partial sums of one iteration (p_r.q, W~^T q), by iteration parity
-    // coarse space of the two-level preconditioner (dense_solver.hip): 8 gauge vectors in the transformed unknowns
+    // coarse space of the two-level preconditioner (pcg_common.h "Coarse space"): 8 gauge vectors in the transformed unknowns
     double* W = nullptr;      // [8][ld] W~, written by the linearisation (k_finalize); fp32-representable values
     double* AW = nullptr;     // [d][8]  S~ W~
     double* epart = nullptr;  // [72][1024] per-workgroup partials of E = W~^T S~ W~ and c_0 = W~^T b~
     double* coarse = nullptr; // [72] E^-1 (64) and c_0 (8)
-    // segmented coarse space (dense_solver.hip, "Segmented coarse space"): 57 hat-restricted gauge vectors, workgroup = camera
+    // segmented coarse space (pcg_segments.hip, "Segmented coarse space"): 57 hat-restricted gauge vectors, workgroup = camera
     double* mlAW = nullptr;   // [d][64] S~ W~
     double* mlV = nullptr;    // [nc + 1][8][64] per-camera pieces of E
     double* mlU = nullptr;    // [nc + 1][8] per-camera pieces of c_0
@@ -49,16 +60,17 @@ struct DenseSolver {
     const unsigned* blk_mask = nullptr;   // [ncam][(ncam + 31) / 32] per camera: cameras with a non-empty block in common (set by the caller; null: dense product)
     double blk_fill = 1.0;    // non-empty off-diagonal blocks / all (set by the caller)
     int last_iters = 0;       // CG iterations of the previous solve
-    int family = 0;           // SFMBA_FAMILY_* of the last dense_pcg_solve / dense_cholesky_solve (the step probe, include/sfmba.h)
-    int coarse_vectors = 0;   // ... and the coarse vectors of that CG: 0, 8, 57 (segments) or 7 G + 1 (segments, streaming path)
+    int family = 0;           // SFMBA_FAMILY_* of the last dense_pcg_solve (a copy of run.path.family) / dense_cholesky_solve (the step probe, include/sfmba.h)
+    int coarse_vectors = 0;   // ... and the coarse vectors of that CG (a copy of run.path.coarse_vectors)
     std::vector<int> hist;    // CG iterations of the previous call per caller key (LM iteration index): sizes the first launch batch
     double* binv = nullptr;   // [ld*6] inverses of the 6x6 diagonal blocks (+1x1 focal)
-    double* scal = nullptr;   // [8] rz, pq, bnorm2, rnorm2, ...
-    int* flags = nullptr;     // [4] done, iters
+    double* scal = nullptr;   // [PS_STATE + 2 PS_STATE_LEN] threshold base, |b~_first|^2, then the solver state by iteration parity (pcg_common.h: PS_*)
+    int* flags = nullptr;     // [4] PF_DONE, PF_ITERS, PF_XBUF (pcg_common.h)
     int* h_flags = nullptr;   // pinned host mirror
     volatile int* h_mailbox = nullptr;   // host-mapped {iterations, done}: polled instead of copy + synchronise
     int* d_mailbox = nullptr;
     DeviceArena* arena = nullptr;   // when set, the device arrays above live in (and are released with) this arena
+    std::vector<void*> owned;       // else: what was hipMalloc'ed for them, freed by dense_solver_destroy (AWt aliases sym_zero: one entry)
     bool pinned_external = false;   // h_flags / h_mailbox are slices of the caller's pinned block
 };
 
@@ -75,14 +87,18 @@ inline int dense_padded_dim(int d) { return ((d + 1 + CHOL_NB - 1) / CHOL_NB) * 
 void dense_cholesky_solve(hipStream_t s, DenseSolver* ws, double* S, double* rhs, int* info_dev, Profiler* prof = nullptr);
 
 // Block-Jacobi PCG on the same storage.  Returns the number of iterations (host sync inside).
-// pretransformed = true: ws->Sfull, the right-hand side at ws->vec + 8*ld and ws->binv were already written by the
-// linearisation kernels (k_finalize / k_schur_pairs mode 1), so the block-Cholesky + transform launches are skipped.
-// finish = false leaves the solution in transformed form (x~, see dense_solver.hip) for k_cam_update;
-// hist_key >= 0 selects the history slot used to size the first batch of launches.
+struct PcgSolveOptions {
+    bool finish = true;           // false leaves the solution in transformed form (x~, see pcg_common.h) for k_cam_update
+    int hist_key = -1;            // >= 0 selects the history slot used to size the first batch of launches
+    bool pretransformed = false;  // ws->Sfull, the right-hand side at ws->vec + 8*ld and ws->binv were already written by the linearisation kernels
+                                  // (k_finalize / k_schur_pairs mode 1), so the block-Cholesky + transform launches are skipped
+    int anchor = 0;               // the stopping rule, see below
+    bool no_wait = false;         // enqueue the first batch and return, see below
+    bool coarse = false;          // ws->W holds the 8 gauge vectors of this linearisation, see below
+    bool segments = false;        // (with coarse) the segmented coarse space where it applies (dense_pcg_segments_applicable: d = 6 nc + 1 <= 1280, nc >= 32)
+};
 int dense_pcg_solve(hipStream_t s, DenseSolver* ws, double* S, double* rhs, double tol, int max_iters, int* info_dev,
-                    Profiler* prof = nullptr, bool finish = true, int hist_key = -1, bool pretransformed = false, int anchor = 0,
-                    bool no_wait = false, bool coarse = false, bool segments = false);
-// segments = true (with coarse): the segmented coarse space where it applies (dense_pcg_segments_applicable: d = 6 nc + 1 <= 1280, nc >= 32)
+                    Profiler* prof = nullptr, const PcgSolveOptions& o = PcgSolveOptions());
 bool dense_pcg_segments_applicable(const DenseSolver* ws);
 // ... or its streaming-path form (1280 < d <= 8192): classical PCG in three launches per iteration, up to 20 hats (at most 1007 cameras)
 bool dense_pcg_segments_streaming_applicable(const DenseSolver* ws);
@@ -91,8 +107,8 @@ bool dense_pcg_segments_streaming_applicable(const DenseSolver* ws);
 int dense_pcg_transform(hipStream_t s, DenseSolver* ws, double* S, double* rhs, int* info_dev, Profiler* prof = nullptr);
 // coarse = true: ws->W holds the 8 gauge vectors of this linearisation (written by k_finalize): two-level preconditioner
 // anchor: 0 = relative residual |r| <= tol |b~|; 1 = first solve of an LM run (remembers |b~|); 2 = later solve of the
-// same run: |r| <= tol * max(|b~|, |b~_first|), but never looser than max(tol, 1e-4) relative (see dense_solver.hip)
-// no_wait variant: dense_pcg_solve(..., no_wait = true) enqueues the first batch of iterations and returns at once (the
+// same run: |r| <= tol * max(|b~|, |b~_first|), but never looser than max(tol, 1e-4) relative (see pcg_common.h, pcg_threshold_base)
+// no_wait = true: dense_pcg_solve enqueues the first batch of iterations and returns at once (the
 // iteration count is then unknown to the host: consumers gate on ws->flags[0] on the device); dense_pcg_more enqueues up to
 // n further iterations of the same solve (returns how many; 0 = max_iters reached); dense_pcg_note records the final count.
 int dense_pcg_more(hipStream_t s, DenseSolver* ws, int n, Profiler* prof = nullptr);

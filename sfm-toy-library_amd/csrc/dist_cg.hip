@@ -3,13 +3,13 @@
 #include "dist_cg.h"
 #include "sfmba_device.h"
 #include "coarse_inverse.h"
+#include "pcg_common.h"     // PF_*: the layout of DenseSolver::flags
 #include <algorithm>
 
 namespace sfmba {
 
 namespace {
 
-enum { PF_DONE = 0, PF_ITERS = 1, PF_XBUF = 2 };                       // DenseSolver::flags (dense_solver.hip)
 enum { DS_RZ = 0, DS_RR0 = 1, DS_RRF = 2, DS_EINV = 8, DS_NV = 80 };  // scal: rz, threshold base, |b~|^2 of the first solve of an anchored run, E^-1 (64), live vectors
 constexpr int NW = 8;
 constexpr int STEP_T = 1024;

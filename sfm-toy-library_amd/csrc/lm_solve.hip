@@ -157,7 +157,7 @@ void probe_note(sfmba_problem* p, int family, int f32_matrix, int coarse_vectors
     p->probe.cholesky_fallback = cholesky_fallback;
 }
 void probe_note_solver(sfmba_problem* p, bool pcg, int cholesky_fallback) {
-    probe_note(p, p->solver.family, pcg && p->solver.run.f32 ? 1 : 0, pcg ? p->solver.coarse_vectors : 0, cholesky_fallback);
+    probe_note(p, p->solver.family, pcg && p->solver.run.path.f32 ? 1 : 0, pcg ? p->solver.coarse_vectors : 0, cholesky_fallback);
 }
 
 void init_state(sfmba_problem* p, LMState& st, const sfmba_options& o) {
@@ -250,10 +250,10 @@ int run_solve(sfmba_problem* p, const sfmba_options& o, sfmba_summary* summary, 
     bool first_linearisation = true;
     bool first_linear_solve = true;
     const bool f32_matrix = option_switch(o.pcg_f32_matrix, true);
-    // two-level preconditioner (8 gauge vectors as a coarse space, dense_solver.hip)
+    // two-level preconditioner (8 gauge vectors as a coarse space, pcg_common.h)
     const bool coarse_cg = option_switch(o.pcg_coarse_space, true);
     // ... and for a sparsely filled reduced matrix (a camera graph of large diameter) the same vectors restricted to eight segments of the
-    // camera order (dense_solver.hip "Segmented coarse space"); SFMBA_PCG_SEGMENTS=0|1 forces it off / on wherever it applies
+    // camera order (pcg_segments.hip "Segmented coarse space"); SFMBA_PCG_SEGMENTS=0|1 forces it off / on wherever it applies
     // -- where the structure says the camera order IS that path: a sparsely filled matrix whose blocks sit near the (cyclic) diagonal
     // (options.pcg_coarse_space: 0 = by structure, 1 = the eight global vectors only, 2 = the segments wherever they apply)
     const bool segments_cg = coarse_cg && (dense_pcg_segments_applicable(&p->solver) || dense_pcg_segments_streaming_applicable(&p->solver)) &&
@@ -319,7 +319,7 @@ int run_solve(sfmba_problem* p, const sfmba_options& o, sfmba_summary* summary, 
             // fp32 Jacobian mode + streaming CG path: the preconditioned matrix is stored in fp32 (halves the HBM-bound matvec)
             p->db.pcg_F32 = (p->precision == SFMBA_PRECISION_F32J && f32_matrix) ? dense_pcg_want_f32(&p->solver) : nullptr;
             p->solver.use_f32 = p->db.pcg_F32 != nullptr;
-            // the streaming CG on ONE triangle of S~ (dense_solver.hip "Symmetric streaming path"); its sums arrive through atomics: not for deterministic handles
+            // the streaming CG on ONE triangle of S~ (pcg_symmetric.hip "Symmetric streaming path"); its sums arrive through atomics: not for deterministic handles
             p->solver.symmetric = symmetric_cg && dense_pcg_symmetric_applicable(&p->solver);
             p->db.pcg_upper_only = p->solver.symmetric ? 1 : 0;      // ... and the pair pass then writes that triangle only
             p->db.pcg_zero = p->solver.symmetric ? p->solver.sym_zero : nullptr;        // S~ W~, the CG's products and partial sums: added into with atomics
@@ -359,7 +359,8 @@ int run_solve(sfmba_problem* p, const sfmba_options& o, sfmba_summary* summary, 
             // not wait for the linear solve.  If the batch was too short k_lm_control says so and more is enqueued.
             pcg_gated = true;
             const int it = dense_pcg_solve(p->stream, &p->solver, p->db.S, p->db.rhs, plan.tol, plan.max_iters, p->d_info, prof,
-                                           /*finish=*/false, /*hist_key=*/host_iter, /*pretransformed=*/true, plan.anchor(first_linear_solve), /*no_wait=*/true, /*coarse=*/coarse_cg, /*segments=*/segments_cg);
+                                           { .finish = false, .hist_key = host_iter, .pretransformed = true, .anchor = plan.anchor(first_linear_solve), .no_wait = true,
+                                             .coarse = coarse_cg, .segments = segments_cg });
             first_linear_solve = false;
             if (it < 0) return fail(SFMBA_ERR_ALLOC, "PCG workspace allocation failed");
             dbu.pcg_vec = p->solver.vec; dbu.pcg_linv = p->solver.binv; dbu.pcg_flags = p->solver.flags;

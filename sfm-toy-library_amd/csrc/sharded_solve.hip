@@ -101,7 +101,7 @@ int sfmba_shard_solve_update(sfmba_problem* p) {
         const bool coarse_cg = option_switch(o.pcg_coarse_space, true);
         if (coarse_cg) { p->db.pcg_W = p->solver.W; launch_gauge(p->stream, p->ds, p->db); }
         const int it = dense_pcg_solve(p->stream, &p->solver, p->db.S, p->db.rhs, plan.tol, plan.max_iters, p->d_info, nullptr,
-                                       false, p->shard_host_iter, /*pretransformed=*/true, plan.anchor(p->shard_host_iter == 0), /*no_wait=*/false, /*coarse=*/coarse_cg);
+                                       { .finish = false, .hist_key = p->shard_host_iter, .pretransformed = true, .anchor = plan.anchor(p->shard_host_iter == 0), .coarse = coarse_cg });
         if (it < 0) return fail(SFMBA_ERR_ALLOC, "PCG workspace allocation failed");
         p->shard_sum.linear_iters += it;
         dbu.pcg_vec = p->solver.vec; dbu.pcg_linv = p->solver.binv; dbu.pcg_flags = p->solver.flags;
@@ -320,7 +320,8 @@ static int solve_sharded_impl(sfmba_problem* p, const sfmba_options* opt, sfmba_
                 if (F32) launch_narrow_matrix(p->stream, p->solver.Sfull, F32, (long long)p->ds.d * p->ds.ld);
             }
             const int it0 = dense_pcg_solve(p->stream, &p->solver, p->db.S, p->db.rhs, cg_tol, plan.max_iters, p->d_info, nullptr,
-                                            /*finish=*/false, /*hist_key=*/p->shard_host_iter, /*pretransformed=*/true, plan.anchor(first_linear_solve), /*no_wait=*/true, coarse_cg);
+                                            { .finish = false, .hist_key = p->shard_host_iter, .pretransformed = true, .anchor = plan.anchor(first_linear_solve), .no_wait = true,
+                                              .coarse = coarse_cg });
             first_linear_solve = false;
             if (it0 < 0) return fail(SFMBA_ERR_ALLOC, "PCG workspace allocation failed");
             }

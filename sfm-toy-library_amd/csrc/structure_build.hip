@@ -417,7 +417,7 @@ int build_pair_chunks(hipStream_t s, DeviceArena* scratch, int nwg, int chunk, c
     return (int)hipGetLastError();
 }
 // Per camera j the set of cameras c whose block (min, max) of the reduced matrix holds a pair -- and j itself --, as a bit mask of `words` 32-bit words:
-// what a block-sparse product of the CG needs (dense_solver.hip, k_sg_q_sparse).  One thread per (camera, word).
+// what a block-sparse product of the CG needs (pcg_segments_streaming.hip, k_sg_q_sparse).  One thread per (camera, word).
 __global__ __launch_bounds__(256) void k_block_mask(int ncam, int words, const int* __restrict__ blk_ptr, unsigned* __restrict__ mask) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ncam * words) return;

@@ -1,11 +1,11 @@
 """Reference check of ONE linear solve of an LM step (numpy only): is the reduced step z that a back-substitution consumed a solution
 of the damped reduced camera system S z = rhs as accurate as its solver family promises, and is the point step the one that z implies?
 
-The CG families iterate in the block-Jacobi transformed unknowns (dense_solver.hip, "block-Jacobi PCG"): B is the Cholesky factor of
+The CG families iterate in the block-Jacobi transformed unknowns (pcg_common.h, "Block-Jacobi preconditioned conjugate gradients"): B is the Cholesky factor of
 every 6x6 diagonal camera block of S plus the square root of the focal diagonal entry, S~ = B^-1 S B^-T, b~ = B^-1 rhs, x~ = B^T z, and
 k_cam_update forms z = B^-T x~.  Their stopping test is on the 2-norm of the recursively updated residual of THAT system, relative to
-|b~| (dense_solver.hip: `rrn <= tol2 * rr0` in k_pcg_iter / k_pcg_iter_fast / k_pcg_iter_ml / k_sg_p / the symmetric vector kernel,
-lines ~518, ~803, ~1270, ~1830, ~2281; rr0 = |b~|^2 from pcg_threshold_base, anchored -- max(|b~|, |b~_first|) capped -- only from the
+|b~| (`rrn <= tol2 * rr0` in k_pcg_iter of pcg_streaming.hip, k_sy_vec of pcg_symmetric.hip, k_pcg_iter_fast of pcg_fast.hip, k_pcg_iter_ml of
+pcg_segments.hip, `rr <= tol2 * scal[PS_RR0]` in k_sg_p of pcg_segments_streaming.hip; rr0 = |b~|^2 from pcg_threshold_base, anchored -- max(|b~|, |b~_first|) capped -- only from the
 second solve of an LM run, which a one-iteration solve never reaches).  So the residual checked here is
 
     rho = |b~ - S~ x~| / |b~| = |B^-1 (rhs - S z)| / |B^-1 rhs|,      evaluated in np.longdouble,

@@ -173,7 +173,7 @@ def test_streaming_cg_path_with_fp32_matrix(capi, sfm, monkeypatch):
 
 
 def test_gauge_coarse_space_cuts_cg_iterations_and_gauge_drift(capi, sfm, cfg3, monkeypatch):
-    """Two-level preconditioner (8 analytic gauge vectors as a coarse space, dense_solver.hip): same LM trajectory, at most
+    """Two-level preconditioner (8 analytic gauge vectors as a coarse space, pcg_common.h): same LM trajectory, at most
     10 CG iterations per LM iteration at cfg 3 (was 17-20), and the truncation error no longer sits in the gauge directions:
     parameters within 5e-8 of the exact Cholesky solve (plain block-Jacobi at the same tolerance: 2e-7)."""
     ref = capi.solve(cfg3, capi.default_options(max_seconds=0.0, precision=1, linear_solver=0))

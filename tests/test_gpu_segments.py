@@ -1,4 +1,4 @@
-"""The segmented coarse space of the reduced-system CG (dense_solver.hip "Segmented coarse space"): the seven similarity vectors restricted to
+"""The segmented coarse space of the reduced-system CG (pcg_segments.hip "Segmented coarse space"): the seven similarity vectors restricted to
 eight overlapping segments of the camera order + the global focal/depth vector.  A preconditioner only -- the solve must land where the
 oracle's does whatever the coarse space; what it buys is CG iterations on camera graphs laid out along a path."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The streaming CG on ONE triangle of the preconditioned reduced matrix (-m gpu; round 6, ABI v6: sfmba_options.pcg_symmetric; csrc/dense_solver.hip
+"""The streaming CG on ONE triangle of the preconditioned reduced matrix (-m gpu; round 6, ABI v6: sfmba_options.pcg_symmetric; csrc/pcg_symmetric.hip
 "Symmetric streaming path": k_sy_vec + k_sy_prod + k_sy_coarse).  The matrix in question is the dense S of the reference's DENSE_SCHUR (BA.cpp:172) after
 the block-Jacobi transform; what is held here: the symmetric form reaches the ORACLE's result in both precisions, with and without the coarse space and
 under AUTO (1e-12, no Cholesky fallback), takes the iterations the both-triangles kernels of round 5 take (pcg_symmetric = -1), and a deterministic

@@ -1,5 +1,5 @@
 """CPU (numpy) restatements of two pieces of host-visible arithmetic behind the segmented coarse space, so that their properties are pinned where no GPU is
-needed: (1) the hats along the camera order (dense_solver.hip: ml_first_cam / ml_frac / sg_first_cam / sg_frac) are a partition of unity with exactly two
+needed: (1) the hats along the camera order (pcg_segments.hip: ml_first_cam / ml_frac; pcg_segments_streaming.hip: sg_first_cam / sg_frac) are a partition of unity with exactly two
 hats per camera, so the coarse space contains the eight global gauge vectors; (2) the sampled estimate of "pairs in the block of an average pair" the
 structure build uses to choose the pair-pass geometry (problem_build.hip, host_half)."""
 import numpy as np

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(64 * WPB) void k_symv_units(int d, int ld, const fl
     if (curc >= 0) flush(curc, colacc);
 }
 
-// the product as the streaming CG does it today: both triangles read, a wave per two rows, 16-byte loads four deep (k_pcg_iter, dense_solver.hip)
+// the product as the streaming CG does it today: both triangles read, a wave per two rows, 16-byte loads four deep (k_pcg_iter, pcg_streaming.hip)
 __global__ __launch_bounds__(256) void k_full(int d, int ld, const float* __restrict__ F, const double* __restrict__ p, double* __restrict__ q, int rows_per_wg) {
     extern __shared__ double pl[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;

@@ -2,7 +2,7 @@
 // Team = the workgroups with blockIdx % STRIDE == 0 of a 256-workgroup launch (dispatch order: workgroup i -> XCD i % 8), the others
 // return at once.  Every team member publishes its slice of a d-vector as 8-byte {tag, half} granules (agent-scope relaxed stores) and
 // gathers the whole vector (agent-scope relaxed loads) until every tag carries the iteration -- the exchange of k_pcg_persistent
-// (dense_solver.hip).  Also: load time of the team's rows of a d x d fp64 matrix into registers (once per solve).
+// (removed from dense_solver.hip in round 5).  Also: load time of the team's rows of a d x d fp64 matrix into registers (once per solve).
 //   hipcc --offload-arch=gfx950 -O3 -o xcd_exchange xcd_exchange.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -1,4 +1,4 @@
-"""A/B of the segmented coarse space (dense_solver.hip) on banded problems: CG iterations, result, time per solve with SFMBA_PCG_SEGMENTS=0 / 1.
+"""A/B of the segmented coarse space (pcg_segments.hip, pcg_segments_streaming.hip) on banded problems: CG iterations, result, time per solve with SFMBA_PCG_SEGMENTS=0 / 1.
     python tools/segments_check.py [workload ...]      (runs on the GPU box)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
