@@ -549,6 +549,53 @@ SFMBA_API int sfmba_match_features(int device, int n_images, const int64_t* img_
                 int n_pairs, const int32_t* pair_left, const int32_t* pair_right, double ratio,
                 int64_t* pair_ptr, int32_t* query_idx, int32_t* train_idx, float* distance, int64_t cap, int64_t* total);
 
+/*
+ * Pose a not-yet-registered view from its 2D-3D matches (SfMStereoUtilities::findCameraPoseFrom2D3DMatch,
+ * SfMToyLib/SfMStereoUtilities.cpp:208-243: cv::solvePnPRansac + the inlier-ratio gate) for a batch of views in one call.
+ * The reference's result depends on OpenCV's global RNG; THIS CONTRACT IS OUR OWN, deterministic one -- it is not, and does not
+ * claim to be, the sample stream of cv::solvePnPRansac.
+ *
+ *   problems      problem p owns entries prob_ptr[p] .. prob_ptr[p+1]-1 of xyz [total][3] (world points) and uv [total][2]
+ *                 (pixels); n = its number of entries.  With out_point / out_feature gathered this is the output of
+ *                 sfmba_find_2d3d_matches (one problem per view).  K [9] row-major; only fx = K[0], fy = K[4], cx = K[2],
+ *                 cy = K[5] are read.  There is no distortion (the reference's is all zeros, SfM.cpp:74).
+ *   sample        mix(z) is splitmix64's output function: z += 0x9E3779B97F4A7C15; z = (z ^ z>>30) * 0xBF58476D1CE4E5B9;
+ *                 z = (z ^ z>>27) * 0x94D049BB133111EB; return z ^ z>>31 (all mod 2^64).  key = mix(seed + p); draw
+ *                 k = 0, 1, .., 63 of hypothesis h is index mix(key ^ ((h << 8) | k)) mod n; the sample is the first four DISTINCT
+ *                 indices in draw order; a hypothesis that has not found four by draw 63 is invalid.  Integer work: exact.
+ *   hypothesis    unit bearings from ((u-cx)/fx, (v-cy)/fy, 1) in fp64; P3P on the first three correspondences (Grunert's
+ *                 quartic solved in closed form, every real root polished by Newton, then the three distances polished by
+ *                 Newton on the distance equations); of the solutions with positive depth at all four sample points the one
+ *                 whose pixel error at the fourth point is smallest.  Invalid if there is none, or if two of the three 3D
+ *                 points coincide.  An invalid hypothesis has hyp_count = -1 and a zero hyp_pose.
+ *   score         a point is an inlier of a pose iff its depth is > 0 and its squared pixel reprojection error is
+ *                 <= threshold_px^2.  One device function takes this decision for the count and for the mask (fp32 products
+ *                 of the pose pre-multiplied by diag(fx, fy, 1) against the observation minus the principal point, division
+ *                 free: decisions can differ from fp64 only within ~1e-3 px of the threshold), so
+ *                 sum(inlier of p) == n_inliers == hyp_count[best_hypothesis] exactly.
+ *   winner        the valid hypothesis with the largest count; ties go to the lowest h.  inlier [total] is the WINNER's mask
+ *                 (as OpenCV returns the mask of the RANSAC model, not of the refined pose).  All n_hyp hypotheses are
+ *                 evaluated: there is no confidence-based early stop.
+ *   refine        Gauss-Newton in fp64 on the winner's inliers; residual = pixel reprojection; update R <- exp([dw]x) R,
+ *                 t <- t + dt; stops when |(dw, dt)| < 1e-12 or after max_refine_iters steps (the shim passes 20; 0 = off).
+ *                 Skipped when n_inliers < 4.  refine_iters = steps taken; refine_cost = 1/2 sum |r|^2 over the inliers at the
+ *                 returned pose.
+ *   status        0 ok | 1 fewer than 4 points: pose = [I|0], mask zero, best_hypothesis = -1 | 2 no valid hypothesis: same
+ *                 outputs as 1 | 3 refinement met a non-finite value or a singular normal matrix: the unrefined winner is
+ *                 returned (refine_iters = 0).
+ *
+ * Outputs: pose [n_prob][12] row-major [R|t] (fp64), inlier [total], result [n_prob]; optional (NULL or not) hyp_pose
+ * [n_prob][n_hyp][12] and hyp_count [n_prob][n_hyp], every hypothesis' unrefined pose and inlier count.  Host pointers in and out,
+ * synchronous.  A degenerate problem never makes the call fail: the others of the batch are still answered.
+ * SFMBA_ERR_INVALID_ARG for n_hyp outside 1..65536, a non-finite or non-positive threshold_px, fx or fy, a negative or decreasing
+ * prob_ptr, max_refine_iters < 0, a problem of 2^31 or more points.  Deterministic: the same arguments give the same bytes in
+ * every output (counts are integer atomics; the normal equations are reduced in a fixed order).
+ */
+typedef struct sfmba_pnp_result { int status; int best_hypothesis; int n_inliers; int refine_iters; double refine_cost; } sfmba_pnp_result;
+SFMBA_API int sfmba_pnp_ransac(int device, int n_prob, const int64_t* prob_ptr, const float* xyz, const float* uv, const float* K,
+                int n_hyp, float threshold_px, uint64_t seed, int max_refine_iters,
+                double* pose, unsigned char* inlier, sfmba_pnp_result* result, double* hyp_pose, int32_t* hyp_count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,7 @@ SYMBOLS = [
     "sfmba_comm_allreduce_f32", "sfmba_problem_set_allreduce_f32", "sfmba_shard_last_exchange",
     "sfmba_problem_create_ex", "sfmba_comm_abort", "sfmba_comm_reduce_scatter", "sfmba_problem_set_reduce_scatter",
     "sfmba_comm_allgather", "sfmba_problem_set_allgather", "sfmba_comm_size", "sfmba_device_warmup",
-    "sfmba_match_features", "sfmba_problem_set_step_probe", "sfmba_problem_get_step_probe",
+    "sfmba_match_features", "sfmba_problem_set_step_probe", "sfmba_problem_get_step_probe", "sfmba_pnp_ransac",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -178,6 +178,50 @@ def match_features(descs, pairs=None, ratio=float(np.float32(0.8)), cap=None, de
     _check(rc)
     n = total.value
     return pl, pr, ptr, q[:n].copy(), t[:n].copy(), d[:n].copy()
+
+
+class _PnpResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("best_hypothesis", C.c_int), ("n_inliers", C.c_int), ("refine_iters", C.c_int), ("refine_cost", C.c_double)]
+
+
+def pnp_ransac(problems, K, n_hyp=100, threshold_px=10.0, seed=0, max_refine_iters=20, debug=False, device=0):
+    """sfmba_pnp_ransac: pose every problem of a batch from its 2D-3D matches (the contract is in include/sfmba.h).
+
+    problems: list of (xyz [n_i, 3], uv [n_i, 2]) -- one per view to register.  K [3, 3].  Returns one dict per problem: status,
+    best_hypothesis, n_inliers, refine_iters, refine_cost, pose [3, 4] float64, inlier [n_i] bool; with debug=True also
+    hyp_pose [n_hyp, 3, 4] and hyp_count [n_hyp] (every hypothesis' unrefined pose and count, -1 = invalid)."""
+    xs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3) for x, _ in problems]
+    us = [np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2) for _, u in problems]
+    if any(len(x) != len(u) for x, u in zip(xs, us)):
+        raise ValueError("xyz and uv of a problem must have the same number of rows")
+    n_prob = len(xs)
+    ptr = np.zeros(n_prob + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum([len(x) for x in xs])
+    total = int(ptr[-1])
+    xyz = np.ascontiguousarray(np.concatenate(xs, axis=0) if xs else np.zeros((0, 3), np.float32))
+    uv = np.ascontiguousarray(np.concatenate(us, axis=0) if us else np.zeros((0, 2), np.float32))
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    pose = np.zeros((max(n_prob, 1), 12))
+    inl = np.zeros(max(total, 1), dtype=np.uint8)
+    res = (_PnpResult * max(n_prob, 1))()
+    n_dbg = max(n_prob, 1) * max(int(n_hyp), 1) if debug else 0
+    hp = np.zeros((n_dbg, 12)) if debug else None
+    hc = np.zeros(n_dbg, dtype=np.int32) if debug else None
+    lp, fp = C.POINTER(C.c_int64), C.POINTER(C.c_float)
+    _check(lib().sfmba_pnp_ransac(C.c_int(device), C.c_int(n_prob), _p(ptr, lp), _p(xyz, fp), _p(uv, fp), _p(K, fp), C.c_int(n_hyp),
+                                  C.c_float(threshold_px), C.c_uint64(seed), C.c_int(max_refine_iters), _p(pose, _dp),
+                                  inl.ctypes.data_as(C.POINTER(C.c_ubyte)), res, _p(hp, _dp) if debug else None,
+                                  _p(hc, _ip) if debug else None))
+    out = []
+    for p in range(n_prob):
+        d = {k: getattr(res[p], k) for k, _ in _PnpResult._fields_}
+        d["pose"] = pose[p].reshape(3, 4).copy()
+        d["inlier"] = inl[ptr[p]:ptr[p + 1]].astype(bool)
+        if debug:
+            d["hyp_pose"] = hp[p * n_hyp:(p + 1) * n_hyp].reshape(n_hyp, 3, 4).copy()
+            d["hyp_count"] = hc[p * n_hyp:(p + 1) * n_hyp].copy()
+        out.append(d)
+    return out
 
 
 def release_cache():

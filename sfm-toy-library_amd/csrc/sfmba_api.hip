@@ -5,6 +5,7 @@
 #include "association.h"
 #include "feature_match.h"
 #include "lm_loop.h"
+#include "pnp_ransac.h"
 #include <climits>
 #include <cmath>
 
@@ -481,6 +482,36 @@ int sfmba_match_features(int device, int n_images, const int64_t* img_ptr, const
     if (rc == MATCH_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "match_features: output capacity too small");
     if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "match_features: device allocation failed");
     if (rc) return fail(SFMBA_ERR_HIP, std::string("match_features: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+// ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------
+int sfmba_pnp_ransac(int device, int n_prob, const int64_t* prob_ptr, const float* xyz, const float* uv, const float* K, int n_hyp,
+                     float threshold_px, uint64_t seed, int max_refine_iters, double* pose, unsigned char* inlier,
+                     sfmba_pnp_result* result, double* hyp_pose, int32_t* hyp_count) {
+    if (n_prob < 0 || !prob_ptr || !K || (n_prob > 0 && (!pose || !result))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (n_hyp < 1 || n_hyp > 65536) return fail(SFMBA_ERR_INVALID_ARG, "n_hyp must be in 1..65536");
+    if (!std::isfinite(threshold_px) || !(threshold_px > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "threshold_px must be finite and > 0");
+    if (!std::isfinite(K[0]) || !(K[0] > 0.0f) || !std::isfinite(K[4]) || !(K[4] > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "fx and fy must be finite and > 0");
+    if (max_refine_iters < 0) return fail(SFMBA_ERR_INVALID_ARG, "max_refine_iters must be >= 0");
+    if (prob_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "prob_ptr must not be negative");
+    for (int p = 0; p < n_prob; ++p) {
+        if (prob_ptr[p + 1] < prob_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "prob_ptr not monotone");
+        if (prob_ptr[p + 1] - prob_ptr[p] >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "pnp_ransac: a problem has 2^31 or more points");
+    }
+    if (prob_ptr[n_prob] > 0 && (!xyz || !uv || !inlier)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (n_prob == 0) return check_device(device);
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    // SFMBA_PNP_TIMING: one stderr line per call with the HIP-event times of its phases (tools/pnp_bench.py)
+    double tm[3];
+    const bool timing = std::getenv("SFMBA_PNP_TIMING") != nullptr;
+    rc = pnp_ransac(ck.kit.stream, device, n_prob, prob_ptr, xyz, uv, K, n_hyp, threshold_px, seed, max_refine_iters, pose, inlier, result,
+                    hyp_pose, hyp_count, timing ? tm : nullptr);
+    if (rc == 0 && timing) std::fprintf(stderr, "[sfmba pnp] upload_ms %.6f kernels_ms %.6f download_ms %.6f\n", tm[0], tm[1], tm[2]);
+    if (rc == PNP_ERR_TOO_LARGE) return fail(SFMBA_ERR_INVALID_ARG, "pnp_ransac: too many problems x hypotheses for one call");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "pnp_ransac: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("pnp_ransac: ") + hipGetErrorString((hipError_t)rc));
     return SFMBA_OK;
 }
 }  // extern "C"

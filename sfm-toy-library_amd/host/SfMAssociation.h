@@ -20,10 +20,6 @@
 
 namespace sfmtoylib {
 
-struct Image2D3DMatch {                                           // SfMCommon.h:71-74
-    Points2f points2D;
-    Points3f points3D;
-};
 typedef std::map<int, Image2D3DMatch> Images2D3DMatches;          // SfM.h:52
 
 class SfMAssociation {

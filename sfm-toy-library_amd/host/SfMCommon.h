@@ -18,6 +18,11 @@ typedef std::vector<cv::KeyPoint> Keypoints;
 typedef std::vector<cv::Point2f>  Points2f;
 typedef std::vector<cv::Point3f>  Points3f;
 
+struct Image2D3DMatch {                           // SfMCommon.h:71-74
+    Points2f points2D;
+    Points3f points3D;
+};
+
 struct Features {
     Keypoints keyPoints;
     Points2f  points;
@@ -39,5 +44,7 @@ struct ImagePair {                                // SfMCommon.h:61-63
     size_t left, right;
 };
 typedef cv::Matx34f Pose;
+
+const float POSE_INLIERS_MINIMAL_RATIO = 0.5;     // SfMCommon.h:53
 
 }  // namespace sfmtoylib

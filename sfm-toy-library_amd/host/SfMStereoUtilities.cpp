@@ -4,6 +4,12 @@
 // feature indices (GetAlignedPointsFromMatch, SfMCommon.cpp:63-87; the 2D points are the key points' pt, :85-86), the
 // triangulation + 10 px reprojection filter runs on the GPU (sfmba_triangulate), and every surviving point is appended to
 // pointCloud with originatingViews[left] / [right] = those back references (:192-203).  Points are appended in match order.
+//
+// findCameraPoseFrom2D3DMatch (SfMToyLib/SfMStereoUtilities.cpp:208-243): the reference calls cv::solvePnPRansac with
+// iterationsCount = 100, reprojectionError = RANSAC_THRESHOLD = 10 and confidence 0.99, then rejects the pose when fewer than
+// POSE_INLIERS_MINIMAL_RATIO of the matches are inliers.  Here sfmba_pnp_ransac evaluates all 100 hypotheses at once -- the
+// confidence-based early stop has no meaning in a parallel evaluation, so 0.99 has no counterpart -- with threshold 10, seed 0
+// and 20 refinement steps; the gate and its message are the reference's.
 #include "SfMStereoUtilities.h"
 
 #include <iostream>
@@ -54,6 +60,46 @@ bool SfMStereoUtilities::triangulateViews(
         p.originatingViews[(int)imagePair.right] = rightBackReference[i];
         pointCloud.push_back(p);
     }
+    return true;
+}
+
+bool SfMStereoUtilities::findCameraPoseFrom2D3DMatch(
+        const Intrinsics&     intrinsics,
+        const Image2D3DMatch& match,
+        cv::Matx34f&          cameraPose) {
+    const size_t n = match.points2D.size();
+    if (match.points3D.size() != n) {
+        std::cerr << "findCameraPoseFrom2D3DMatch failed. (" << n << " 2D points, " << match.points3D.size() << " 3D points)" << std::endl;
+        return false;
+    }
+    std::vector<float> xyz(3 * n), uv(2 * n);
+    for (size_t i = 0; i < n; i++) {
+        xyz[3 * i] = match.points3D[i].x; xyz[3 * i + 1] = match.points3D[i].y; xyz[3 * i + 2] = match.points3D[i].z;
+        uv[2 * i] = match.points2D[i].x;  uv[2 * i + 1] = match.points2D[i].y;
+    }
+    float K[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) K[3 * r + c] = intrinsics.K.at<float>(r, c);
+
+    const int    ITERATIONS_COUNT = 100;            // SfMStereoUtilities.cpp:224 (all are evaluated)
+    const float  RANSAC_THRESHOLD = 10.0f;          // SfMStereoUtilities.cpp:41
+    const int    REFINE_STEPS     = 20;
+    const int64_t prob_ptr[2] = { 0, (int64_t)n };
+    double pose[12];
+    std::vector<unsigned char> inliers(n ? n : 1);
+    sfmba_pnp_result res;
+    const int rc = sfmba_pnp_ransac(0, 1, prob_ptr, xyz.data(), uv.data(), K, ITERATIONS_COUNT, RANSAC_THRESHOLD, 0, REFINE_STEPS,
+                                    pose, inliers.data(), &res, nullptr, nullptr);
+    if (rc != SFMBA_OK) {
+        std::cerr << "findCameraPoseFrom2D3DMatch failed. (sfmba rc=" << rc << ": " << sfmba_last_error() << ")" << std::endl;
+        return false;
+    }
+    //check inliers ratio and reject if too small
+    if (res.status != 0 || n == 0 || ((float)res.n_inliers / (float)n) < POSE_INLIERS_MINIMAL_RATIO) {
+        std::cerr << "Inliers ratio is too small: " << res.n_inliers << " / " << n << std::endl;
+        return false;
+    }
+    for (int e = 0; e < 12; e++) cameraPose.val[e] = (float)pose[e];
     return true;
 }
 

@@ -1,7 +1,7 @@
-// SfMStereoUtilities.h -- the triangulation entry point of the reference with its own signature
-// (SfMToyLib/SfMStereoUtilities.h:72-91), backed by the MI355X kernel (include/sfmba.h: sfmba_triangulate).
-// Only triangulateViews is provided: the other members of the reference class (homography inliers, essential-matrix pose,
-// PnP) stay on the reference's OpenCV path (out of scope).
+// SfMStereoUtilities.h -- the triangulation and the 2D-3D pose entry points of the reference with their own signatures
+// (SfMToyLib/SfMStereoUtilities.h:72-105), backed by the MI355X kernels (include/sfmba.h: sfmba_triangulate, sfmba_pnp_ransac).
+// The other members of the reference class (homography inliers, essential-matrix pose) stay on the reference's OpenCV path
+// (out of scope).
 #pragma once
 #include "SfMCommon.h"
 
@@ -22,6 +22,18 @@ public:
             const cv::Matx34f& Pleft,
             const cv::Matx34f& Pright,
             PointCloud&        pointCloud);
+
+    /**
+     * Find the camera pose of a new view from its 2D-3D matches (P3P RANSAC + refinement on the GPU).
+     * The reference runs cv::solvePnPRansac on OpenCV's global RNG; this runs the project's own deterministic contract
+     * (include/sfmba.h, sfmba_pnp_ransac): the same call always gives the same pose.
+     * @return true on success; false (cameraPose untouched) when the inlier ratio is below POSE_INLIERS_MINIMAL_RATIO, the
+     *         problem is degenerate, or there is no HIP device / a device error.
+     */
+    static bool findCameraPoseFrom2D3DMatch(
+            const Intrinsics&     intrinsics,
+            const Image2D3DMatch& match,
+            cv::Matx34f&          cameraPose);
 };
 
 }  // namespace sfmtoylib

@@ -72,6 +72,26 @@ int sfmba_shim_triangulate_views(const float* K /*[9]*/, int left_view, int righ
     return n;
 }
 
+// Flat-array driver of sfmtoylib::SfMStereoUtilities::findCameraPoseFrom2D3DMatch (tests/test_gpu_pnp_ransac.py).  pose [12] goes
+// in and comes back (untouched when the call reports failure).  Returns 1 / 0 = the call's true / false.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_find_camera_pose(const float* K /*[9]*/, int n, const float* xyz /*[n][3]*/, const float* uv /*[n][2]*/, float* pose /*[12]*/) {
+    using namespace sfmtoylib;
+    Intrinsics intr;
+    intr.K = cv::Mat(3, 3);
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) intr.K.at<float>(r, c) = K[3 * r + c];
+    Image2D3DMatch match;
+    for (int i = 0; i < n; ++i) {
+        match.points2D.push_back(cv::Point2f(uv[2 * i], uv[2 * i + 1]));
+        match.points3D.push_back(cv::Point3f(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]));
+    }
+    cv::Matx34f P;
+    for (int e = 0; e < 12; ++e) P.val[e] = pose[e];
+    const bool ok = SfMStereoUtilities::findCameraPoseFrom2D3DMatch(intr, match, P);
+    for (int e = 0; e < 12; ++e) pose[e] = P.val[e];
+    return ok ? 1 : 0;
+}
+
 namespace {
 using namespace sfmtoylib;
 PointCloud buildCloud(int n, const float* xyz, const int64_t* view_ptr, const int32_t* view_idx, const int32_t* feat_idx) {

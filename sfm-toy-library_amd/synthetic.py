@@ -265,3 +265,25 @@ def make_descriptors(n_images=7, n_rows=5000, desc_bytes=32, n_tracks=None, flip
         out.append(np.zeros((0, desc_bytes), np.uint8))
         out.append(rng.integers(0, 256, (1, desc_bytes), dtype=np.uint8))
     return out
+
+
+def make_pnp_scene(n, outlier_frac, seed):
+    """One 2D-3D posing problem for sfmba_pnp_ransac: a dict with X [n,3] float32, uv [n,2] float32 (pixels), K [3,3],
+    the planted pose R [3,3] / t [3] and bad [n] bool (the rows of uv that were replaced by uniform clutter).
+
+    Points are uniform in [-1, 1]^3 in front of a camera at depth 5 (fx = fy = 2500, c = (512, 384), a 1024 x 768 image);
+    observations carry 0.5 px Gaussian noise; X and uv are rounded through float32, as cv::Point3f / Point2f hold them."""
+    rng = np.random.default_rng(seed)
+    R = rotvec_to_matrix(rng.normal(0, 0.2, 3))
+    X = rng.uniform(-1, 1, (n, 3))
+    t = np.array([0.1, -0.2, 5.0])
+    K = np.array([[2500.0, 0.0, 512.0], [0.0, 2500.0, 384.0], [0.0, 0.0, 1.0]])
+    pc = X @ R.T + t
+    uv = pc[:, :2] / pc[:, 2:3] * np.array([K[0, 0], K[1, 1]]) + np.array([K[0, 2], K[1, 2]]) + rng.normal(0, 0.5, (n, 2))
+    X = X.astype(np.float32)
+    uv = uv.astype(np.float32)
+    bad = rng.random(n) < outlier_frac
+    k = int(bad.sum())
+    uv[bad, 0] = rng.uniform(0, 1024, k)
+    uv[bad, 1] = rng.uniform(0, 768, k)
+    return dict(X=X, uv=uv, K=K, R=R, t=t, bad=bad)
