@@ -1,6 +1,7 @@
-// ba_common.h -- device helpers shared by the kernel files of the bundle-adjustment path (ba_kernels.hip, implicit_schur.hip,
-// shard_exchange.hip): block / slot reductions, launch geometry of the point and camera passes, the stores into the CG's matrix, the
-// post-linearisation bookkeeping, and the evaluation of one observation in the factored form of sfmba_device.h.
+// ba_common.h -- device helpers shared by the kernel files of the bundle-adjustment path (the ba_*.hip units listed in ba_kernels.h,
+// implicit_schur.hip, shard_exchange.hip): the camera table, block / slot / halving reductions, launch geometry of the point and camera
+// passes, the stores into the CG's matrix and the glue of the block-Jacobi transform, the post-linearisation bookkeeping, and the
+// evaluation of one observation in the factored form of sfmba_device.h.
 #pragma once
 #include "ba_kernels.h"
 #include "sfmba_device.h"
@@ -9,6 +10,85 @@
 namespace sfmba {
 
 #define BLK 256
+
+// ------------------------------------------------------------------------------------------
+// camera tables
+// ------------------------------------------------------------------------------------------
+__device__ inline void make_cam_table(const double cam[6], const double* scale6, double* ct) {
+    const double w0 = cam[0], w1 = cam[1], w2 = cam[2];
+    const double theta2 = w0 * w0 + w1 * w1 + w2 * w2;
+    double R[9], K[9];
+    double small = 0.0;
+    double cq = 1.0 / 12.0;
+    if (theta2 > DBL_EPSILON) {
+        const double theta = sqrt(theta2);
+        double s, c;
+        sincos(theta, &s, &c);
+        if (theta2 > 1e-8) { const double den = 2.0 * theta * s; cq = fabs(den) > 1e-12 ? 1.0 / theta2 - (1.0 + c) / den : 0.0; }
+        const double ti = 1.0 / theta;
+        const double k0 = w0 * ti, k1 = w1 * ti, k2 = w2 * ti;
+        const double oc = 1.0 - c;
+        R[0] = c + k0 * k0 * oc;       R[1] = k0 * k1 * oc - k2 * s;  R[2] = k0 * k2 * oc + k1 * s;
+        R[3] = k0 * k1 * oc + k2 * s;  R[4] = c + k1 * k1 * oc;       R[5] = k1 * k2 * oc - k0 * s;
+        R[6] = k0 * k2 * oc - k1 * s;  R[7] = k1 * k2 * oc + k0 * s;  R[8] = c + k2 * k2 * oc;
+        // K' = (w w^T + (R^T - I) [w]x) / theta^2,  [w]x = [[0,-w2,w1],[w2,0,-w0],[-w1,w0,0]]
+        const double Wx[9] = { 0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0 };
+        const double w[3] = { w0, w1, w2 };
+        const double it2 = 1.0 / theta2;
+        for (int r = 0; r < 3; ++r)
+            for (int cc = 0; cc < 3; ++cc) {
+                double acc = w[r] * w[cc];
+                for (int m = 0; m < 3; ++m) {
+                    const double rtmi = R[m * 3 + r] - (m == r ? 1.0 : 0.0);   // (R^T - I)[r][m]
+                    acc += rtmi * Wx[m * 3 + cc];
+                }
+                K[r * 3 + cc] = acc * it2;
+            }
+    } else {
+        R[0] = 1.0;  R[1] = -w2;  R[2] = w1;
+        R[3] = w2;   R[4] = 1.0;  R[5] = -w0;
+        R[6] = -w1;  R[7] = w0;   R[8] = 1.0;
+        for (int e = 0; e < 9; ++e) K[e] = (e % 4 == 0) ? 1.0 : 0.0;
+        small = 1.0;
+    }
+    for (int e = 0; e < 9; ++e) { ct[CT_R + e] = R[e]; ct[CT_K + e] = K[e]; }
+    ct[CT_T + 0] = cam[3]; ct[CT_T + 1] = cam[4]; ct[CT_T + 2] = cam[5];
+    ct[CT_SMALL] = small;
+    for (int e = 0; e < 6; ++e) ct[CT_SCALE + e] = scale6 ? scale6[e] : 1.0;
+    for (int c = 0; c < 3; ++c)
+        for (int a = 0; a < 3; ++a) {
+            double q = (a == c) ? 1.0 : 0.0;
+            if (small == 0.0) q = R[3 * c + 0] * K[0 + a] + R[3 * c + 1] * K[3 + a] + R[3 * c + 2] * K[6 + a];
+            ct[CT_QD + 3 * c + a] = q;
+        }
+    for (int e = CT_QD + 9; e < CT_STRIDE; ++e) ct[e] = 0.0;
+    // coefficient of [w]x^2 in Jr(w)^-1 = I + [w]x / 2 + cq [w]x^2 (gauge vectors, k_finalize): 1 / theta^2 - (1 + cos) / (2 theta sin), 1 / 12
+    // in the limit; formed here, where sin and cos of theta are at hand anyway (theta near pi: the term is dropped, any vector will do)
+    ct[CT_CQ] = cq;
+}
+
+// [R | t] of a camera from its six parameters: the rotation part of make_cam_table (same expressions, same branches), for a pass that would
+// rather rebuild R per observation than gather nine more doubles of it (k_point_update's trial sweep: the pass is bound by its gather instructions)
+__device__ __forceinline__ void pose_from_params(const double (&cam)[6], double (&RT)[12]) {
+    const double w0 = cam[0], w1 = cam[1], w2 = cam[2];
+    const double theta2 = w0 * w0 + w1 * w1 + w2 * w2;
+    if (theta2 > DBL_EPSILON) {
+        const double theta = sqrt(theta2);
+        double s, c;
+        sincos(theta, &s, &c);
+        const double ti = 1.0 / theta;
+        const double k0 = w0 * ti, k1 = w1 * ti, k2 = w2 * ti;
+        const double oc = 1.0 - c;
+        RT[0] = c + k0 * k0 * oc;       RT[1] = k0 * k1 * oc - k2 * s;  RT[2] = k0 * k2 * oc + k1 * s;
+        RT[3] = k0 * k1 * oc + k2 * s;  RT[4] = c + k1 * k1 * oc;       RT[5] = k1 * k2 * oc - k0 * s;
+        RT[6] = k0 * k2 * oc - k1 * s;  RT[7] = k1 * k2 * oc + k0 * s;  RT[8] = c + k2 * k2 * oc;
+    } else {
+        RT[0] = 1.0;  RT[1] = -w2;  RT[2] = w1;
+        RT[3] = w2;   RT[4] = 1.0;  RT[5] = -w0;
+        RT[6] = -w1;  RT[7] = w0;   RT[8] = 1.0;
+    }
+    RT[9] = cam[3]; RT[10] = cam[4]; RT[11] = cam[5];
+}
 
 __device__ __forceinline__ double wave_max(double v) {
     v = fmax(v, xlane_get<32>(v)); v = fmax(v, xlane_get<16>(v)); v = fmax(v, xlane_get<8>(v));
@@ -107,27 +187,55 @@ __device__ __forceinline__ void slots_take_n(const DeviceBuffers& db, const int 
     for (int k = 0; k < N; ++k) out[k] = v[k];
 }
 
+// Sum of N per-lane values over the lanes that differ in the bits OFF, OFF/2, ..., 1: at every level a lane keeps one half of
+// the values and sends the other half to its partner, so the whole reduction moves N/2 + N/4 + ... values instead of N per level.
+// On return v[0 .. len) of this lane are the sums of values base .. base + len - 1 (len may be <= 0).
+// VALU64: fp64 values exchanged in the VALU as well (two 32-bit halves per value: DPP / permlane swaps) -- the pair pass's block sums
+template <typename V, int N, int OFF, bool VALU64 = false>
+struct HalvingReduceT {
+    static __device__ __forceinline__ void run(V* v, int lane, int& base, int& len) {
+        constexpr int H = (N + 1) / 2;
+        const bool up = (lane & OFF) != 0;
+#pragma unroll
+        for (int k = 0; k < H; ++k) {
+            const V lo = v[k];
+            const V hi = (H + k < N) ? v[H + k] : (V)0;
+            if constexpr (sizeof(V) == 8 && !VALU64) {
+                // fp64 (camera pass: 24 doubles): through the LDS pipe as before.  The permlane / DPP forms cost that pass its occupancy
+                // (62 -> 144 registers: two registers in and two out per swapped word), and it is bound by loads in flight, not by issue.
+                const V send = up ? lo : hi;
+                const V keep = up ? hi : lo;
+                v[k] = keep + __shfl_xor(send, OFF, 64);
+            } else if constexpr (OFF >= 16) {
+                v[k] = xlane_pairsum<OFF>(lo, hi);                           // the swap does the selects (sfmba_device.h)
+            } else {
+                const V send = up ? lo : hi;
+                const V keep = up ? hi : lo;
+                v[k] = keep + xlane_get<OFF>(send);                          // partner: lane ^ OFF (lane ^ 7 at OFF = 4)
+            }
+        }
+        base += up ? H : 0;
+        len = up ? len - H : (len < H ? len : H);
+        HalvingReduceT<V, H, OFF / 2, VALU64>::run(v, lane, base, len);
+    }
+};
+template <typename V, int N, bool VALU64>
+struct HalvingReduceT<V, N, 0, VALU64> {
+    static __device__ __forceinline__ void run(V*, int, int&, int&) {}
+};
+template <int N, int OFF> using HalvingReduce = HalvingReduceT<double, N, OFF>;
+
 template <typename T>
 __device__ __forceinline__ void load_obs(const void* base, int q, double& ox, double& oy) {
     const typename ObsXY<T>::type v = reinterpret_cast<const typename ObsXY<T>::type*>(base)[q];
     ox = (double)v.x; oy = (double)v.y;
 }
 
-
 // workgroup of the two point passes: PBK / 64 waves that share nothing but the final block reduction
 #ifndef PBK
 #define PBK 128
 #endif
 #define WPB (PBK / 64)
-// minimum waves per SIMD the point passes are compiled for (register budget 512 / this); 0 = let the compiler decide
-#ifndef SFMBA_PB_WAVES
-#define SFMBA_PB_WAVES 0
-#endif
-#if SFMBA_PB_WAVES > 0
-#define PB_BOUNDS __launch_bounds__(PBK, SFMBA_PB_WAVES)
-#else
-#define PB_BOUNDS __launch_bounds__(PBK)
-#endif
 
 __device__ __forceinline__ void wave_lds_fence() {
     // LDS traffic of one wave is processed in order; this only stops the compiler from moving the
@@ -143,8 +251,6 @@ __device__ __forceinline__ void wave_lds_fence() {
 #define CD_OBS (SFMBA_CAM_CHUNK / CD_BLK)
 static_assert(SFMBA_CAM_CHUNK % CD_BLK == 0, "camera chunk length");
 
-
-
 // one entry of the preconditioned reduced matrix (fp64, or fp32 when the streaming CG path asked for it)
 __device__ __forceinline__ void store_F(const DeviceBuffers& db, size_t idx, double v) {
     if (db.pcg_F32) db.pcg_F32[idx] = (float)v; else db.pcg_F[idx] = v;
@@ -159,9 +265,32 @@ __device__ __forceinline__ void store_block_entry(const DeviceStructure& ds, con
         return;
     }
     store_F(db, (size_t)(6 * cj.x + r) * ds.ld + 6 * cj.y + c, v);
-#ifndef SFMBA_WHATIF_UPPER_ONLY       // (timing what-if: the lower triangle never written -- wrong results where a kernel reads it)
     if (!db.pcg_upper_only) store_F(db, (size_t)(6 * cj.y + c) * ds.ld + 6 * cj.x + r, v);
-#endif
+}
+
+// Glue of the block-Jacobi transform for camera j: S~_jf = Linv_j S_jf / sqrt(S_ff), b~_j = Linv_j rhs_j -- row l of it (both places of
+// the focal entry in the CG's matrix, pcg_bt); linv_f = pcg_glue_linv_f().  Done on the way by the pair pass (k_schur_pairs MODE 1, which
+// also writes S~_jj = I) or on its own by k_pcg_glue (implicit_schur.hip).
+__device__ __forceinline__ double pcg_glue_linv_f(const DeviceStructure& ds, const DeviceBuffers& db) {
+    const int fo = ds.d - 1;
+    return 1.0 / sqrt(db.S[(size_t)fo * ds.ld + fo]);
+}
+__device__ __forceinline__ void pcg_glue_row(const DeviceStructure& ds, const DeviceBuffers& db, int j, int l, double linv_f) {
+    const int fo = ds.d - 1, row0 = 6 * j;
+    const double* Li = db.pcg_binv + (size_t)j * 36;
+    double vf = 0.0, vb = 0.0;
+    for (int a = 0; a <= l; ++a) { vf += Li[l * 6 + a] * db.S[(size_t)(row0 + a) * ds.ld + fo]; vb += Li[l * 6 + a] * db.rhs[row0 + a]; }
+    vf *= linv_f;
+    store_F(db, (size_t)(row0 + l) * ds.ld + fo, vf);
+    store_F(db, (size_t)fo * ds.ld + row0 + l, vf);
+    db.pcg_bt[row0 + l] = vb;
+}
+// the focal unknown's own three values (ONE lane, camera 0's): S~_ff = 1, b~_f, and 1 / sqrt(S_ff) behind the last Linv
+__device__ __forceinline__ void pcg_glue_focal(const DeviceStructure& ds, const DeviceBuffers& db, double linv_f) {
+    const int fo = ds.d - 1;
+    store_F(db, (size_t)fo * ds.ld + fo, 1.0);
+    db.pcg_bt[fo] = db.rhs[fo] * linv_f;
+    db.pcg_binv[(size_t)ds.ncam * 36] = linv_f;
 }
 
 // after a linearisation: initial cost (iteration 0), gradient tolerance, evaluation failure.  One wave.
@@ -227,6 +356,5 @@ __device__ __forceinline__ void imp_eval(const CamPtr& ct, const DirPtr& dr, dou
         C[3 * r + 2] = b0 * pa.L[3] + b1 * pa.L[4] + b2 * pa.L[5];
     }
 }
-
 
 }  // namespace sfmba

@@ -1,4 +1,15 @@
-// ba_kernels.h -- host-visible declarations of the bundle-adjustment kernels (ba_kernels.hip).
+// ba_kernels.h -- host-visible declarations of the bundle-adjustment kernel family: the structures every pass takes (LMState,
+// DeviceStructure, DeviceBuffers) and the launchers, grouped below by the unit that defines them.  One unit per pass of an LM iteration:
+//   ba_setup.hip      once per solve: camera tables, the clearing first launch, ||x||, Jacobi column scaling
+//   ba_points.hip     linearisation 1: point pass (per-point table, t, M)
+//   ba_cams.hip       linearisation 2: camera-diagonal pass
+//   ba_finalize.hip   linearisation 3: damping, block factors, pair factor, gauge vectors (+ k_cd_fold, k_gauge for the sharded solve)
+//   ba_pairs.hip      linearisation 4: off-diagonal blocks over camera pairs, glue of the block-Jacobi transform
+//   ba_step.hip       behind the linear solve: back-substitution, trial point, LM control
+//   ba_eval.hip       outside the iteration: residual / Jacobian / reduced-system read-outs of the parity tests
+// and, declared here as well: implicit_schur.hip (matrix-free CG product, the glue on its own), shard_exchange.hip (packing for the
+// all-reduces of a sharded solve), structure_build.hip (problem structure on the device), triangulate.hip.
+// Device helpers the units share: ba_common.h, sfmba_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -173,31 +184,50 @@ struct DeviceBuffers {
     const int* shard_row_shift; // distributed CG: blocks to ADD to a block's list position, per block row (reduce-scatter layout: dist_cg.h); null = none
 };
 
+// ---- ba_setup.hip
 template <typename T> void launch_cam_setup(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int which);
+void launch_begin(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, const LMState& st, const double* cam_src = nullptr,
+                  const double* pts_src = nullptr);
 void launch_xnorm(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);
 template <typename T> void launch_colnorm(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int jacobi_scaling, bool clear_udiag = true,
                                          bool points = true, bool finish_xnorm = false, bool with_xnorm = false);
-void launch_begin(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, const LMState& st, const double* cam_src = nullptr,
-                  const double* pts_src = nullptr);
+void launch_colnorm_points_only(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int jacobi, int precision_f32);
+void launch_colnorm_cams_only(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int jacobi, int precision_f32, bool clear_udiag = true);
+void launch_colnorm_finish(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int jacobi);
+void launch_iter0(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);
+
+// ---- ba_points.hip
 template <typename T> void launch_point_build(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db,
                                              int ps_mode = 0 /* 0: point scales from db.pscale; 1 / 2: form them here (Jacobi / unit) */);
+
+// ---- ba_cams.hip
+template <typename T> void launch_cam_diag(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);
+
+// ---- ba_finalize.hip
+void launch_finalize(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int pcg);
+void launch_cd_fold(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);   // deterministic + sharded: chunk sums into the partial system (before the exchange)
+void launch_gauge(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);   // gauge vectors from db.pcg_binv (see k_gauge)
+
+// ---- ba_pairs.hip
 // mode 0: off-diagonal blocks of S (upper triangle);  mode 1: the same blocks written straight into S~ = Lb^-1 S Lb^-T
 // (both triangles) + the per-camera glue of the block-Jacobi transform;  mode 2: diagonal blocks with duplicate pairs.
 // Both reduced-system passes re-evaluate every observation from the camera row and the per-point table (nothing is stored per observation).
 template <typename T> void launch_schur_pairs(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int mode);
-template <typename T> void launch_cam_diag(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);
-void launch_finalize(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int pcg);
-void launch_cd_fold(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);   // deterministic + sharded: chunk sums into the partial system (before the exchange)
-void launch_gauge(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);   // gauge vectors from db.pcg_binv (see k_gauge)
+
+// ---- ba_step.hip
 void launch_cam_update(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);
 template <typename T> void launch_point_update(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);
 void launch_control(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);
-void launch_iter0(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);
+
+// ---- ba_eval.hip
 template <typename T> void launch_eval_residuals(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db,
                                                  const int* perm, double* res_out, double* cost_out);
 template <typename T> void launch_eval_jacobian(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db,
                                                 const int* obs_pt, const int* perm, double* jc, double* jp, double* jf);
-// Implicit Schur product of the sharded solve (implicit_schur.hip): out = this rank's part of S~ p~ from its own
+void launch_mirror_scale(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, double* S_full, double* scale_out);
+
+// ---- implicit_schur.hip
+// Implicit Schur product of the sharded solve: out = this rank's part of S~ p~ from its own
 // points (+ on rank 0 what every rank knows: identity diagonal blocks, focal row / column); summed over the ranks it is S~ p~.
 struct ImplicitProduct {
     DeviceStructure ds;
@@ -212,11 +242,13 @@ struct ImplicitProduct {
 };
 void launch_implicit_product(hipStream_t s, const ImplicitProduct& ip, const double* p_tilde, double* out, const int* flags);
 void launch_pcg_glue(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db);
+
+// ---- shard_exchange.hip
 // sharded mode: move slotted accumulators to / from the all-reduce scalar block
 void launch_shard_pack(hipStream_t s, const DeviceBuffers& db, double* scal, int phase, int rank);
 void launch_shard_tri(hipStream_t s, double* sys, double* packed, int ld, long long tail, bool unpack);
 void launch_shard_unpack(hipStream_t s, const DeviceBuffers& db, const double* scal, int phase, int world);
-// two-phase all-reduce of the sharded CG path (ba_kernels.hip): (A) diagonal blocks + vectors + scalars, (B) off-diagonal blocks of S~
+// two-phase all-reduce of the sharded CG path: (A) diagonal blocks + vectors + scalars, (B) off-diagonal blocks of S~
 long long shard_diag_len(const DeviceStructure& ds);
 void launch_shard_diag(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, double* buf, bool unpack, int rank, int world);
 long long shard_offdiag_len(const DeviceStructure& ds);
@@ -225,13 +257,8 @@ void launch_narrow_matrix(hipStream_t s, const double* src, float* dst, long lon
 void launch_shard_offdiag_f32(hipStream_t s, const DeviceStructure& ds, float* F32, const float* buf);      // unpack of the fp32 exchange
 void launch_clear_slots(hipStream_t s, const DeviceBuffers& db);
 void launch_shard_xnorm_finish(hipStream_t s, const DeviceBuffers& db);
-void launch_colnorm_points_only(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int jacobi, int precision_f32);
-void launch_colnorm_cams_only(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int jacobi, int precision_f32, bool clear_udiag = true);
-void launch_colnorm_finish(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, int jacobi);
-void launch_mirror_scale(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db, double* S_full, double* scale_out);
 
-
-// structure_build.hip: the problem structure is built on the device
+// ---- structure_build.hip: the problem structure is built on the device
 class DeviceArena;
 struct PointMajor {            // point-major observation list (build_point_major)
     int* obs_pt = nullptr;     // [2 n] point slot per sorted position, then the caller index of that observation
@@ -268,7 +295,7 @@ void launch_block_fill(hipStream_t s, int nblock, int ncam, const int2* blk_cams
 void launch_block_mask(hipStream_t s, int ncam, const int* blk_ptr, unsigned* mask);       // per camera: the cameras it shares a non-empty block with (bit mask)
 void launch_dup_blocks(hipStream_t s, int ncam, const int* blk_ptr, const long long* pair_total, int2* dup, int* report);
 
-// triangulate.hip: two-view DLT triangulation + reprojection filter (SfMStereoUtilities::triangulateViews), device pointers
+// ---- triangulate.hip: two-view DLT triangulation + reprojection filter (SfMStereoUtilities::triangulateViews), device pointers
 void launch_triangulate(hipStream_t s, long long n, const float* d_left, const float* d_right, const float K[9], const float Pl[12],
                         const float Pr[12], float max_err, float* d_points3d, unsigned char* d_keep, float* d_err);
 

@@ -3,7 +3,7 @@
 // Replaces what DENSE_SCHUR hands to Eigen's LLT in the reference configuration
 // (SfMToyLib/SfMBundleAdjustmentUtils.cpp:172, DenseSchurComplementSolver [Ceres-upstream]).
 //
-// Storage: the kernels in ba_kernels.hip accumulate the UPPER triangle of the row-major matrix,
+// Storage: the linearisation passes (ba_cams.hip, ba_pairs.hip, ba_finalize.hip) accumulate the UPPER triangle of the row-major matrix,
 // which is byte-for-byte the LOWER triangle of a column-major matrix A(i,j) = S[j*ld + i], i >= j.
 // The matrix is padded to a multiple of CHOL_NB with an identity diagonal, and the right-hand
 // side is stored as one extra ROW of A (row index d): the blocked factorisation then produces

@@ -4,7 +4,7 @@
 // Replaces what DENSE_SCHUR hands to Eigen's LLT in the reference configuration
 // (SfMToyLib/SfMBundleAdjustmentUtils.cpp:172, DenseSchurComplementSolver [Ceres-upstream]); the factorisation itself
 // (SFMBA_LINEAR_CHOLESKY, AUTO's fallback) is dense_cholesky.hip.  Both share the workspace of dense_solver.h and the storage:
-// the kernels in ba_kernels.hip accumulate the UPPER triangle of the row-major matrix, padded to a multiple of CHOL_NB.
+// the linearisation passes (ba_cams.hip, ba_pairs.hip, ba_finalize.hip) accumulate the UPPER triangle of the row-major matrix, padded to a multiple of CHOL_NB.
 //
 // Six CG families (DESIGN.md section 4 "CG families"), one unit each behind the entry points of pcg_common.h: fast (d <= 1280, rows in registers),
 // segmented fast, streaming, symmetric streaming, streaming segmented with the dense and with the block-sparse product.  dense_pcg_path picks one.
@@ -21,6 +21,7 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 constexpr int NB = CHOL_NB;   // padding unit of the matrix (dense_cholesky.hip)
 
 // Linv of each diagonal block: row-major lower 6x6 (zeros above), focal: 1/sqrt(S_ff) at [nb6*36]
+// (Sibling: the factor and inverse inside k_finalize, ba_finalize.hip -- fast_rsq and reciprocal pivots there, sqrt and divisions here: they stay two.)
 __global__ void k_pcg_blockchol(const double* __restrict__ S, int ld, int d, double* __restrict__ linv, int* info) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     const int nb6 = (d - 1) / 6;

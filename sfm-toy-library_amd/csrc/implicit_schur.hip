@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void k_imp_dir(DeviceStructure ds, DeviceBuffe
 }
 
 template <typename T>
-__global__ PB_BOUNDS void k_imp_points(DeviceStructure ds, DeviceBuffers db, const double* __restrict__ dtab, double* __restrict__ spt, const int* __restrict__ flags) {
+__global__ __launch_bounds__(PBK) void k_imp_points(DeviceStructure ds, DeviceBuffers db, const double* __restrict__ dtab, double* __restrict__ spt, const int* __restrict__ flags) {
     if (flags && flags[0]) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int gw = blockIdx.x * WPB + w;
@@ -219,22 +219,9 @@ __global__ __launch_bounds__(256) void k_pcg_glue(DeviceStructure ds, DeviceBuff
     if (blockIdx.x == 0 && threadIdx.x < 64) post_linearisation(ds, db);
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= ds.ncam) return;
-    const int fo = ds.d - 1, row0 = 6 * j;
-    const double* Li = db.pcg_binv + (size_t)j * 36;
-    const double linv_f = 1.0 / sqrt(db.S[(size_t)fo * ds.ld + fo]);
-    for (int l = 0; l < 6; ++l) {
-        double vf = 0.0, vb = 0.0;
-        for (int a = 0; a <= l; ++a) { vf += Li[l * 6 + a] * db.S[(size_t)(row0 + a) * ds.ld + fo]; vb += Li[l * 6 + a] * db.rhs[row0 + a]; }
-        vf *= linv_f;
-        store_F(db, (size_t)(row0 + l) * ds.ld + fo, vf);
-        store_F(db, (size_t)fo * ds.ld + row0 + l, vf);
-        db.pcg_bt[row0 + l] = vb;
-    }
-    if (j == 0) {
-        store_F(db, (size_t)fo * ds.ld + fo, 1.0);
-        db.pcg_bt[fo] = db.rhs[fo] * linv_f;
-        db.pcg_binv[(size_t)ds.ncam * 36] = linv_f;
-    }
+    const double linv_f = pcg_glue_linv_f(ds, db);
+    for (int l = 0; l < 6; ++l) pcg_glue_row(ds, db, j, l, linv_f);      // (the identity diagonal blocks are not this kernel's: nothing here reads them)
+    if (j == 0) pcg_glue_focal(ds, db, linv_f);
 }
 void launch_pcg_glue(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db) {
     hipLaunchKernelGGL(k_pcg_glue, dim3((ds.ncam + 255) / 256), dim3(256), 0, s, ds, db);

@@ -502,7 +502,7 @@ static int build_structure(sfmba_problem* p, const ObsSource& src, const double*
         p->imp_dtab = p->imp_spt = p->imp_acc = p->imp_part = nullptr;
     }
     if (sharded) {
-        // the all-reduce buffer: packed triangle of S + tail (exact solver), or the two blocks of the CG path (ba_kernels.hip, k_shard_diag)
+        // the all-reduce buffer: packed triangle of S + tail (exact solver), or the two blocks of the CG path (shard_exchange.hip, k_shard_diag)
         const size_t tri = (size_t)ds.ld * (ds.ld + 1) / 2 + 3 * (size_t)ds.ld + SFMBA_SHARD_SCALARS;
         // distributed CG: the blocks go behind the region of exchange (A), in `world` equal chunks (the padding stays zero)
         std::vector<int> rows; long long chunk = 0;

@@ -277,7 +277,7 @@ __device__ __forceinline__ void camera_block(CamPtr cam, const Proj& pr, double 
     A[9] = (T)0; A[10] = fz;  A[11] = -fz * yp;
 }
 
-// The packed record of one observation (layout: ba_kernels.hip, "Packed per-observation record") from the camera's table row, the
+// The packed record of one observation (layout: below, with rec_camera_block) from the camera's table row, the
 // point and the point's L -- the SAME expressions, in the same order, as the record sweep of k_point_build, so that a pass which
 // re-evaluates an observation sees bit for bit what a pass reading the stored record sees.  rec[15] (camera slot) is not set.
 template <typename T, typename CamPtr>
@@ -297,6 +297,22 @@ __device__ __forceinline__ void obs_record(CamPtr cam, double focal, const doubl
         rec[9 + 3 * r + 2] = b0 * l20 + b1 * l21 + b2 * l22;
     }
     rec[15] = (T)0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The blocks of one observation in registers (obs_record): 16 values
+//                 [0..5] A_w = Aproj G (2x3, unscaled)  [6] fz = f/pz  [7] xp  [8] yp
+//                 [9..14] C = B~ L^-T (2x3)             [15] unused
+// The whitened Schur block of two observations a, b of one point is
+//   Y_a Y_b^T = S_a A_a^T (C_a C_b^T) A_b S_b,   A = [A_w | Aproj],  S = Jacobi scale of the camera.
+// ------------------------------------------------------------------------------------------
+// unscaled camera block A (2x6, row-major) from a record (camera pass, duplicate-pair pass)
+template <typename T>
+__device__ __forceinline__ void rec_camera_block(const T rec[YREC], T A[12]) {
+    A[0] = rec[0]; A[1] = rec[1]; A[2] = rec[2];
+    A[3] = rec[6]; A[4] = (T)0; A[5] = -rec[6] * rec[7];
+    A[6] = rec[3]; A[7] = rec[4]; A[8] = rec[5];
+    A[9] = (T)0; A[10] = rec[6]; A[11] = -rec[6] * rec[8];
 }
 
 // ---- factored form of an observation for the pair pass -------------------------------------------------------------------------
@@ -415,9 +431,8 @@ __device__ __forceinline__ void obs_factored_ab(const v2f (&R)[12], bool fo_a, b
 }
 // acc += G_a^T N G_b  (6 x 6 row-major; rows: camera a, columns: camera b; the first three of each are the rotation part)
 //   = [[ -[X_a]x N [X_b]x ,  [X_a]x N ],  [ -N [X_b]x ,  N ]]   with  v [X]x = v x X  and  [X]x v = X x v
-// (A: the type the lane's sums are kept in -- T, or double with the products widened one by one)
-template <typename T, typename A = T>
-__device__ __forceinline__ void pair_product_factored(const T ga[GREC], const T gb[GREC], A acc[36]) {
+template <typename T>
+__device__ __forceinline__ void pair_product_factored(const T ga[GREC], const T gb[GREC], T acc[36]) {
     const T ff = ga[3] * gb[3];
     const T m00 = ff * (ga[6] * gb[6] + ga[7] * gb[7] + ga[8] * gb[8]);
     const T m01 = ff * (ga[6] * gb[9] + ga[7] * gb[10] + ga[8] * gb[11]);
@@ -440,15 +455,15 @@ __device__ __forceinline__ void pair_product_factored(const T ga[GREC], const T 
     for (int r = 0; r < 3; ++r) {
         const T t0 = Tm[3 * r], t1 = Tm[3 * r + 1], t2 = Tm[3 * r + 2];
         // -(T[r, :] [X_b]x) = X_b x T[r, :]
-        acc[6 * r + 0] += (A)(b1 * t2 - b2 * t1);
-        acc[6 * r + 1] += (A)(b2 * t0 - b0 * t2);
-        acc[6 * r + 2] += (A)(b0 * t1 - b1 * t0);
-        acc[6 * r + 3] += (A)t0; acc[6 * r + 4] += (A)t1; acc[6 * r + 5] += (A)t2;
+        acc[6 * r + 0] += (b1 * t2 - b2 * t1);
+        acc[6 * r + 1] += (b2 * t0 - b0 * t2);
+        acc[6 * r + 2] += (b0 * t1 - b1 * t0);
+        acc[6 * r + 3] += t0; acc[6 * r + 4] += t1; acc[6 * r + 5] += t2;
         const T n0 = N[3 * r], n1 = N[3 * r + 1], n2 = N[3 * r + 2];
-        acc[6 * (3 + r) + 0] += (A)(b1 * n2 - b2 * n1);
-        acc[6 * (3 + r) + 1] += (A)(b2 * n0 - b0 * n2);
-        acc[6 * (3 + r) + 2] += (A)(b0 * n1 - b1 * n0);
-        acc[6 * (3 + r) + 3] += (A)n0; acc[6 * (3 + r) + 4] += (A)n1; acc[6 * (3 + r) + 5] += (A)n2;
+        acc[6 * (3 + r) + 0] += (b1 * n2 - b2 * n1);
+        acc[6 * (3 + r) + 1] += (b2 * n0 - b0 * n2);
+        acc[6 * (3 + r) + 2] += (b0 * n1 - b1 * n0);
+        acc[6 * (3 + r) + 3] += n0; acc[6 * (3 + r) + 4] += n1; acc[6 * (3 + r) + 5] += n2;
     }
 }
 

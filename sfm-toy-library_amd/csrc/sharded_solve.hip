@@ -179,7 +179,7 @@ static int solve_sharded_impl(sfmba_problem* p, const sfmba_options* opt, sfmba_
     int controls = 0;
     if (two_phase) {
         // CG solver: two all-reduces per linearisation (diagonal blocks + vectors, then the off-diagonal blocks of the preconditioned
-        // matrix, ba_kernels.hip k_shard_diag / k_shard_offdiag) and the same fused kernels as the one-GPU loop in run_solve:
+        // matrix, shard_exchange.hip k_shard_diag / k_shard_offdiag) and the same fused kernels as the one-GPU loop in run_solve:
         // block factors and gauge vectors in k_finalize, transform in the pair pass, gated CG batches (no host wait on the solve).
         const bool coarse_cg = option_switch(o.pcg_coarse_space, true);
         const bool f32 = p->precision == SFMBA_PRECISION_F32J;

@@ -16,7 +16,7 @@ def skew(v):
 
 
 def camera(w):
-    """R, K', first-order flag -- the camera table row (ba_kernels.hip: make_cam_table)."""
+    """R, K', first-order flag -- the camera table row (ba_common.h: make_cam_table)."""
     th2 = float(w @ w)
     if th2 > np.finfo(float).eps:
         th = np.sqrt(th2)

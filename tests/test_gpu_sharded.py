@@ -34,7 +34,7 @@ CASES = {
     "dist_auto": (dict(name="cfg3", n_cam=60, n_pt=8003, seed=5), 0, 2, dict(shard_distributed_cg=1)),
     "dist_plain": (dict(name="cfg3", n_cam=60, n_pt=8003, seed=5), 1, 1, dict(shard_distributed_cg=1, pcg_coarse_space=-1)),
     # ... and WITHOUT any exchange of the reduced matrix: the CG product formed implicitly from every rank's own points
-    # (ba_kernels.hip "Implicit Schur product"), one all-reduce of ld doubles per CG iteration and nothing else -- fp64, fp32 Jacobian
+    # (implicit_schur.hip "Implicit Schur product"), one all-reduce of ld doubles per CG iteration and nothing else -- fp64, fp32 Jacobian
     # blocks at d = 1381, the library default (AUTO), plain block-Jacobi
     "dist_imp_cfg2": (dict(name="cfg2", n_pt=5003), 0, 1, dict(pcg_tolerance=1e-12, pcg_anchored=0, shard_distributed_cg=2)),
     "dist_imp_wide": (dict(name="cfg3", n_cam=230, n_pt=6001, seed=78), 1, 1, dict(shard_distributed_cg=2)),

@@ -6,7 +6,8 @@ Each .hip is compiled with the Makefile's flags plus --cuda-device-only -S (a .s
 moving a function inside or between units changes -- and printed as one line: sha256 prefix, instruction count, demangled name; sorted by name, the unit
 not shown, so that two listings compare with diff.  A kernel defined by two of the units is an error.
 --check LISTING: exit status 1 unless the kernels and fingerprints equal the stored listing's (lines starting with # are ignored).
-   profiles/cg_split_kernel_isa_before.txt / _after.txt: dense_solver.hip + dist_cg.hip before the split into one unit per CG family, and the units after it."""
+   profiles/cg_split_kernel_isa_before.txt / _after.txt: dense_solver.hip + dist_cg.hip before the split into one unit per CG family, and the units after it.
+   profiles/ba_split_kernel_isa_before.txt / _after.txt: ba_kernels.hip + implicit_schur.hip before the split into one unit per pass, and the units after it."""
 import hashlib
 import os
 import re

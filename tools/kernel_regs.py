@@ -1,5 +1,5 @@
 """Register budget of every kernel of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage), one line per kernel.
-   python tools/kernel_regs.py sfm-toy-library_amd/csrc/ba_kernels.hip [filter]"""
+   python tools/kernel_regs.py sfm-toy-library_amd/csrc/ba_pairs.hip [filter]"""
 import re, subprocess, sys
 src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""

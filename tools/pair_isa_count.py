@@ -1,6 +1,6 @@
 """Instruction count of the pair-pass kernels, from the compiler's gfx950 assembly (no GPU needed): the pair pass is bound by VALU issue
 (DESIGN_HISTORY "What bounds what": one wave instruction = one quad-cycle), so the count of its loop body prices a change before it runs.
-   python tools/pair_isa_count.py [--src sfm-toy-library_amd/csrc/ba_kernels.hip] [--check] [extra compiler flags ...]
+   python tools/pair_isa_count.py [--src sfm-toy-library_amd/csrc/ba_pairs.hip] [--check] [extra compiler flags ...]
 Per kernel whose name contains k_schur_pairs: wave instructions before / inside / after the pair loop (the innermost loop that loads
 16-byte point-table words), the loop body by class, registers, scratch, and whether a full vector-memory wait (vmcnt(0)) stands between
 the loop's first load and its point-table loads (the look-ahead of the point slot is real only if there is none).
@@ -98,7 +98,7 @@ def main():
     args = sys.argv[1:]
     check = "--check" in args
     args = [a for a in args if a != "--check"]
-    src = os.path.join(ROOT, "sfm-toy-library_amd", "csrc", "ba_kernels.hip")
+    src = os.path.join(ROOT, "sfm-toy-library_amd", "csrc", "ba_pairs.hip")
     if "--src" in args:
         k = args.index("--src")
         src = args[k + 1]
