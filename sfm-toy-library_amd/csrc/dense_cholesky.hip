@@ -495,30 +495,6 @@ __global__ __launch_bounds__(256) void k_chol_backsolve(const double* __restrict
     }
 }
 
-// The fused factorisation followed by the step-by-step back substitution (SFMBA_CHOL_BACKSOLVE=0, or more than 64 block columns):
-// that one expects L_ik in place, so the panel tiles are multiplied by M_k once, after the last step (one workgroup per tile).
-__global__ __launch_bounds__(256) void k_chol_apply_minv(double* __restrict__ A, int ld, int nblk, const double* __restrict__ minv) {
-    __shared__ double Ti[NB][NB + 1];
-    __shared__ double Mk[NB][NB + 1];
-    // tile (i, k), i > k, from the linear index
-    const int t = blockIdx.x;
-    int i = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((i + 1) * (i + 2) / 2 <= t) ++i;
-    while (i * (i + 1) / 2 > t) --i;
-    const int k = t - i * (i + 1) / 2;
-    ++i;                                            // (i - 1, k) enumerates the lower triangle incl. its diagonal: shift to i > k
-    if (i >= nblk) return;
-    const double* M = minv + (size_t)k * NB * NB;
-    for (int idx = threadIdx.x; idx < NB * NB; idx += 256) { const int r = idx % NB, c = idx / NB; Ti[r][c] = AT(i * NB + r, k * NB + c); Mk[r][c] = M[r + c * NB]; }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < NB * NB; idx += 256) {
-        const int r = idx % NB, c = idx / NB;
-        double sum = 0.0;
-        for (int q = 0; q <= c; ++q) sum = fma(Ti[r][q], Mk[q][c], sum);       // M_k is upper triangular
-        AT(i * NB + r, k * NB + c) = sum;
-    }
-}
-
 // d < 64 (up to ten cameras: the reference's own data sets start there): the whole solve in ONE launch of one workgroup -- the tile
 // is read together with the right-hand side as its row d, factored with the inverse riding along, and x = L^-T y follows from the
 // rows already in LDS.  Replaces k_augment + k_chol_step + k_chol_backsolve (three launches of a launch-bound LM iteration).
@@ -575,7 +551,7 @@ void dense_cholesky_solve(hipStream_t s, DenseSolver* ws, double* S, double* rhs
         return;
     }
     // (the two-kernel factorisation and the step-by-step back substitution take over beyond CHOL_FUSED_MAX_BLOCKS block columns: chosen by size only)
-    const bool one_launch_back = nblk <= CHOL_FUSED_MAX_BLOCKS && nblk <= 64;
+    const bool one_launch_back = nblk <= CHOL_FUSED_MAX_BLOCKS;
     { ProfScope ps(prof, KID_CHOL_AUGMENT, s);
       const int pending = one_launch_back ? nblk * NB : 0;
       hipLaunchKernelGGL(k_augment, dim3((ld + 255) / 256), dim3(256), 0, s, S, ld, d, rhs, pending); }
@@ -603,8 +579,6 @@ void dense_cholesky_solve(hipStream_t s, DenseSolver* ws, double* S, double* rhs
         hipLaunchKernelGGL(k_chol_backsolve, dim3(nblk), dim3(256), 0, s, S, ld, d, ws->minv, rhs, nblk);
         return;
     }
-    if (nblk <= CHOL_FUSED_MAX_BLOCKS && nblk > 1)
-        hipLaunchKernelGGL(k_chol_apply_minv, dim3(nblk * (nblk - 1) / 2), dim3(256), 0, s, S, ld, nblk, ws->minv);
     { ProfScope ps(prof, KID_CHOL_EXTRACT, s);
       hipLaunchKernelGGL(k_extract_y, dim3((ld + 255) / 256), dim3(256), 0, s, S, ld, d, ws->y); }
     for (int k = nblk - 1; k >= 0; --k) {

@@ -130,9 +130,9 @@ def test_reduced_system_without_jacobi_scaling(capi, sfm, oracle):
 # ---------------------------------------------------------------------------------------------
 # dense reduced-system solver in isolation
 # ---------------------------------------------------------------------------------------------
-# 1215 / 1216: the augmented row fills the last tile / needs a tile of its own; 2559 / 2561: last size of the one-launch-per-block-column
-# factorisation (40 block columns) / first size of the two-kernel form
-@pytest.mark.parametrize("n", [1, 7, 63, 64, 121, 200, 1201, 1215, 1216, 2559, 2561])
+# 1215 / 1216: the augmented row fills the last tile / needs a tile of its own; 2559 / 2560: last size of the one-launch-per-block-column
+# factorisation (40 block columns) / first size of the two-kernel form (ld = 2624: 41 block columns, the augmented row in a tile of its own)
+@pytest.mark.parametrize("n", [1, 7, 63, 64, 121, 200, 1201, 1215, 1216, 2559, 2560, 2561])
 def test_dense_cholesky(capi, n):
     rng = np.random.default_rng(n)
     M = rng.normal(size=(n, n))
