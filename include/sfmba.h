@@ -596,6 +596,57 @@ SFMBA_API int sfmba_pnp_ransac(int device, int n_prob, const int64_t* prob_ptr, 
                 int n_hyp, float threshold_px, uint64_t seed, int max_refine_iters,
                 double* pose, unsigned char* inlier, sfmba_pnp_result* result, double* hyp_pose, int32_t* hyp_count);
 
+/*
+ * Rank the image pairs for the baseline (SfM::sortViewsForBaseline, SfMToyLib/SfM.cpp:333-364, through
+ * SfMStereoUtilities::findHomographyInliers, SfMStereoUtilities.cpp:51-72: cv::findHomography(RANSAC, 10 px) + countNonZero(mask))
+ * for a batch of image pairs in one call.  The reference's result depends on OpenCV's global RNG and on its confidence-based early
+ * stop; THIS CONTRACT IS OUR OWN, deterministic one -- it is not, and does not claim to be, the sample stream of cv::findHomography.
+ *
+ *   problems      pair p owns entries pair_ptr[p] .. pair_ptr[p+1]-1 of query_idx / train_idx; n = its number of entries.  Entry i
+ *                 is the correspondence x = pts[img_ptr[pair_left[p]] + query_idx[i]] -> x' = pts[img_ptr[pair_right[p]] +
+ *                 train_idx[i]]; pts [img_ptr[n_images]][2] holds the key points of all images (pixels), image i owning rows
+ *                 img_ptr[i] .. img_ptr[i+1]-1.  These are the arrays sfmba_match_features returns plus the key point
+ *                 coordinates: the reference's GetAlignedPointsFromMatch is folded into the call and done on the device.
+ *                 left == right and repeated indices inside a pair are allowed.
+ *   sample        the stream of sfmba_pnp_ransac: key = mix(seed + p); draw k = 0, 1, .., 63 of hypothesis h is entry
+ *                 mix(key ^ ((h << 8) | k)) mod n; the sample is the first four DISTINCT entries in draw order; a hypothesis
+ *                 that has not found four by draw 63 is invalid.  Integer work: exact.
+ *   hypothesis    fp64.  Each side's four points are normalised: their mean c is subtracted and the result divided by s, the
+ *                 mean of |coordinate - c| over the eight numbers; s == 0 makes the hypothesis invalid.  With homogeneous
+ *                 a_i = (x^_i, 1) and b_i = (x^'_i, 1) the four triple determinants dl_k = det[a_i a_j a_k] (triple k omits
+ *                 point k and keeps ascending order) and dr_k likewise decide validity: invalid if any |dl_k| <= 1e-3 or any
+ *                 |dr_k| <= 1e-3 (three of the four nearly collinear), and invalid if the four products dl_k dr_k do not all have
+ *                 the same sign (the quad is not mapped with one orientation: some sample point would cross the line at
+ *                 infinity).  Otherwise H is THE homography through the four correspondences (closed form: [b_0 b_1 b_2]
+ *                 diag(mu_i / lambda_i) adj([a_0 a_1 a_2]) with lambda, mu the Cramer ratios of those determinants), de-normalised
+ *                 and scaled so that its third row applied to (c_left, 1) is 1; w > 0 then holds at all four sample points.  An
+ *                 invalid hypothesis has hyp_count = -1 and a zero hyp_H.
+ *   score         a correspondence is an inlier of H iff w = h31 x + h32 y + h33 > 0 and |H x / w - x'|^2 <= threshold_px^2: the
+ *                 forward transfer error only, which is what OpenCV's homography RANSAC scores.  One device function takes this
+ *                 decision for the count and for the mask (fp32, division-free: (X, Y, W) = H (x, y, 1), W > 0 and
+ *                 (X - x' W)^2 + (Y - y' W)^2 <= thr^2 W^2; decisions can differ from fp64 only within ~1e-3 px of the
+ *                 threshold), so sum(inlier of p) == n_inliers == hyp_count[best_hypothesis] exactly.
+ *   winner        the valid hypothesis with the largest count; ties go to the lowest h.  H [p] is the winner's hypothesis as it
+ *                 stands: there is no least-squares refit (the reference's only consumer reads the mask count).  inlier is the
+ *                 winner's mask.  All n_hyp hypotheses are evaluated: there is no confidence-based early stop.
+ *   status        0 ok | 1 fewer than 4 matches: H = I, mask zero, best_hypothesis = -1, n_inliers = 0 | 2 no valid hypothesis:
+ *                 same outputs as 1.  n_matches echoes the pair's number of entries.
+ *
+ * Outputs: H [n_pairs][9] row-major (fp64), inlier [pair_ptr[n_pairs]] (entries in front of pair_ptr[0] are written as 0), result
+ * [n_pairs]; optional (NULL or not) hyp_H [n_pairs][n_hyp][9] and hyp_count [n_pairs][n_hyp], every hypothesis' H and inlier count.
+ * Host pointers in and out, synchronous.  A degenerate pair never makes the call fail: the others of the batch are still answered.
+ * SFMBA_ERR_INVALID_ARG for n_hyp outside 1..65536, a non-finite or non-positive threshold_px, a negative or decreasing img_ptr or
+ * pair_ptr, a pair index out of range, a query_idx or train_idx outside its image (checked on the host before anything is launched),
+ * a pair of 2^31 or more matches.  Deterministic: the same arguments give the same bytes in every output (counts are integer atomics).
+ */
+typedef struct sfmba_homography_result { int status; int best_hypothesis; int n_inliers; int n_matches; } sfmba_homography_result;
+SFMBA_API int sfmba_homography_ransac(int device, int n_images, const int64_t* img_ptr, const float* pts /*[img_ptr[n_images]][2]*/,
+                int n_pairs, const int32_t* pair_left, const int32_t* pair_right,
+                const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx,
+                int n_hyp, float threshold_px, uint64_t seed,
+                double* H /*[n_pairs][9]*/, unsigned char* inlier /*[pair_ptr[n_pairs]]*/, sfmba_homography_result* result,
+                double* hyp_H /*[n_pairs][n_hyp][9] or NULL*/, int32_t* hyp_count /*[n_pairs][n_hyp] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,17 +115,6 @@ __global__ __launch_bounds__(PNP_SCORE_THREADS) void k_pnp_score(int n_hyp, int 
     }
 }
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)(v & 0xffffffffull), off);
-        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), off);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // lane 0 only: solve H d = -g by Cholesky.  H = the 21 entries of the upper triangle, row by row.  Every loop has constant bounds
 // and is unrolled, so the factor lives in registers (an indexed 6 x 6 array would sit in scratch or cost an LDS round trip per
 // entry on the one lane everybody waits for).  false = not positive definite / a non-finite value.

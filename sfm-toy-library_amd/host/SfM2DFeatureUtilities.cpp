@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "../../include/sfmba.h"
+#include "SfMStereoUtilities.h"
 
 namespace sfmtoylib {
 
@@ -101,6 +102,34 @@ bool SfMFeatureMatching::createFeatureMatchMatrix(const std::vector<Features>& i
     if (!matchPairs(images, left, right, out)) return false;
     for (size_t p = 0; p < left.size(); ++p) featureMatchMatrix[(size_t)left[p]][(size_t)right[p]].swap(out[p]);
     return true;
+}
+
+std::map<float, ImagePair> SfMFeatureMatching::sortViewsForBaseline(const std::vector<Features>& imageFeatures, const MatchMatrix& featureMatchMatrix) {
+    const size_t MIN_POINT_COUNT_FOR_HOMOGRAPHY = 100;                          // SfM.cpp:47
+    const size_t numImages = imageFeatures.size();
+    std::vector<const Features*> images;
+    for (const Features& f : imageFeatures) images.push_back(&f);
+    std::vector<int> left, right, inliers;
+    std::vector<const Matching*> matches;
+    for (size_t i = 0; i + 1 < numImages; i++)
+        for (size_t j = i + 1; j < numImages; j++)
+            if (featureMatchMatrix[i][j].size() >= MIN_POINT_COUNT_FOR_HOMOGRAPHY) {
+                left.push_back((int)i); right.push_back((int)j); matches.push_back(&featureMatchMatrix[i][j]);
+            }
+    SfMStereoUtilities::findHomographyInliersBatch(images, left, right, matches, inliers);
+    // the reference's loop and its insertion order (SfM.cpp:341-361): the map keeps the LAST pair of every key
+    std::map<float, ImagePair> matchesSizes;
+    size_t q = 0;
+    for (size_t i = 0; i + 1 < numImages; i++)
+        for (size_t j = i + 1; j < numImages; j++) {
+            if (featureMatchMatrix[i][j].size() < MIN_POINT_COUNT_FOR_HOMOGRAPHY) {
+                matchesSizes[1.0] = { i, j };
+                continue;
+            }
+            const float inliersRatio = (float)inliers[q++] / (float)(featureMatchMatrix[i][j].size());
+            matchesSizes[inliersRatio] = { i, j };
+        }
+    return matchesSizes;
 }
 
 }  // namespace sfmtoylib

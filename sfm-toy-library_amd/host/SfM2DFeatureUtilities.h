@@ -11,7 +11,14 @@
 //
 // Results are identical to the reference's: the same DMatch entries in the same order (queryIdx, trainIdx, imgIdx = 0,
 // distance), for descriptors of type CV_8U.
+//
+// The consumer of the whole matrix, SfM::sortViewsForBaseline (SfMToyLib/SfM.cpp:333-364), is restated the same way:
+//
+//   map<float, ImagePair> SfM::sortViewsForBaseline() {
+//       return SfMFeatureMatching::sortViewsForBaseline(mImageFeatures, mFeatureMatchMatrix);
+//   }
 #pragma once
+#include <map>
 #include <vector>
 
 #include "SfMCommon.h"
@@ -40,6 +47,17 @@ public:
     static bool createFeatureMatchMatrix(
             const std::vector<Features>& imageFeatures,
             MatchMatrix&                 featureMatchMatrix);
+
+    /**
+     * SfM::sortViewsForBaseline: every pair i < j keyed by its homography-inlier ratio (float)inliers / (float)matches, pairs with
+     * fewer than MIN_POINT_COUNT_FOR_HOMOGRAPHY = 100 matches under key 1.0; a later pair with an equal key overwrites the earlier
+     * one, as in the reference's std::map.  All qualifying pairs go to the device in ONE call
+     * (SfMStereoUtilities::findHomographyInliersBatch) instead of one cv::findHomography each.  On a device error the qualifying
+     * pairs count 0 inliers (a line is written to stderr).
+     */
+    static std::map<float, ImagePair> sortViewsForBaseline(
+            const std::vector<Features>& imageFeatures,
+            const MatchMatrix&           featureMatchMatrix);
 };
 
 }  // namespace sfmtoylib

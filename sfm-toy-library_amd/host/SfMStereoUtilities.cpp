@@ -10,6 +10,11 @@
 // POSE_INLIERS_MINIMAL_RATIO of the matches are inliers.  Here sfmba_pnp_ransac evaluates all 100 hypotheses at once -- the
 // confidence-based early stop has no meaning in a parallel evaluation, so 0.99 has no counterpart -- with threshold 10, seed 0
 // and 20 refinement steps; the gate and its message are the reference's.
+//
+// findHomographyInliers (SfMToyLib/SfMStereoUtilities.cpp:51-72): the reference aligns the matched key points
+// (GetAlignedPointsFromMatch, SfMCommon.cpp:63-87), calls cv::findHomography(RANSAC, RANSAC_THRESHOLD = 10) and counts the mask.
+// Here the key points of the images and the match lists go to sfmba_homography_ransac as they are -- the alignment happens on the
+// device -- with threshold 10, seed 0 and 2000 hypotheses (OpenCV's default maxIters: where its loop stops at the latest).
 #include "SfMStereoUtilities.h"
 
 #include <iostream>
@@ -18,6 +23,58 @@
 #include "../../include/sfmba.h"
 
 namespace sfmtoylib {
+
+bool SfMStereoUtilities::findHomographyInliersBatch(
+        const std::vector<const Features*>& images,
+        const std::vector<int>&             left,
+        const std::vector<int>&             right,
+        const std::vector<const Matching*>& matches,
+        std::vector<int>&                   inliers) {
+    const int    HOMOGRAPHY_HYPOTHESES = 2000;      // cv::findHomography's default maxIters (all are evaluated)
+    const float  RANSAC_THRESHOLD      = 10.0f;     // SfMStereoUtilities.cpp:41
+    const size_t n_pairs = left.size();
+    inliers.assign(n_pairs, 0);
+    if (n_pairs == 0) return true;
+    std::vector<int64_t> img_ptr(images.size() + 1, 0);
+    for (size_t i = 0; i < images.size(); i++) img_ptr[i + 1] = img_ptr[i] + (int64_t)images[i]->keyPoints.size();
+    std::vector<float> pts(2 * (size_t)img_ptr.back() + 2);
+    for (size_t i = 0; i < images.size(); i++)
+        for (size_t k = 0; k < images[i]->keyPoints.size(); k++) {
+            pts[2 * ((size_t)img_ptr[i] + k)]     = images[i]->keyPoints[k].pt.x;
+            pts[2 * ((size_t)img_ptr[i] + k) + 1] = images[i]->keyPoints[k].pt.y;
+        }
+    std::vector<int64_t> pair_ptr(n_pairs + 1, 0);
+    for (size_t p = 0; p < n_pairs; p++) pair_ptr[p + 1] = pair_ptr[p] + (int64_t)matches[p]->size();
+    std::vector<int32_t> pl(left.begin(), left.end()), pr(right.begin(), right.end());
+    std::vector<int32_t> query((size_t)pair_ptr.back() + 1), train((size_t)pair_ptr.back() + 1);
+    for (size_t p = 0; p < n_pairs; p++)
+        for (size_t e = 0; e < matches[p]->size(); e++) {
+            query[(size_t)pair_ptr[p] + e] = (*matches[p])[e].queryIdx;
+            train[(size_t)pair_ptr[p] + e] = (*matches[p])[e].trainIdx;
+        }
+    std::vector<double> H(9 * n_pairs);
+    std::vector<unsigned char> mask((size_t)pair_ptr.back() + 1);
+    std::vector<sfmba_homography_result> res(n_pairs);
+    const int rc = sfmba_homography_ransac(0, (int)images.size(), img_ptr.data(), pts.data(), (int)n_pairs, pl.data(), pr.data(), pair_ptr.data(),
+                                           query.data(), train.data(), HOMOGRAPHY_HYPOTHESES, RANSAC_THRESHOLD, 0, H.data(), mask.data(),
+                                           res.data(), nullptr, nullptr);
+    if (rc != SFMBA_OK) {
+        std::cerr << "findHomographyInliers failed. (sfmba rc=" << rc << ": " << sfmba_last_error() << ")" << std::endl;
+        return false;
+    }
+    for (size_t p = 0; p < n_pairs; p++) inliers[p] = res[p].status == 0 ? res[p].n_inliers : 0;
+    return true;
+}
+
+int SfMStereoUtilities::findHomographyInliers(
+        const Features& left,
+        const Features& right,
+        const Matching& matches) {
+    if (matches.size() < 4) return 0;               // SfMStereoUtilities.cpp:67
+    std::vector<int> inliers;
+    findHomographyInliersBatch({ &left, &right }, { 0 }, { 1 }, { &matches }, inliers);
+    return inliers[0];
+}
 
 bool SfMStereoUtilities::triangulateViews(
         const Intrinsics&  intrinsics,

@@ -1,14 +1,41 @@
-// SfMStereoUtilities.h -- the triangulation and the 2D-3D pose entry points of the reference with their own signatures
-// (SfMToyLib/SfMStereoUtilities.h:72-105), backed by the MI355X kernels (include/sfmba.h: sfmba_triangulate, sfmba_pnp_ransac).
-// The other members of the reference class (homography inliers, essential-matrix pose) stay on the reference's OpenCV path
-// (out of scope).
+// SfMStereoUtilities.h -- the homography-inlier count, the triangulation and the 2D-3D pose entry points of the reference with
+// their own signatures (SfMToyLib/SfMStereoUtilities.h:53-105), backed by the MI355X kernels (include/sfmba.h:
+// sfmba_homography_ransac, sfmba_triangulate, sfmba_pnp_ransac).  The one member of the reference class that stays on the
+// reference's OpenCV path is findCameraMatricesFromMatch (essential matrix + recoverPose of the ONE chosen baseline pair).
 #pragma once
+#include <vector>
+
 #include "SfMCommon.h"
 
 namespace sfmtoylib {
 
 class SfMStereoUtilities {
 public:
+    /**
+     * Number of matches that agree with one homography (four-point RANSAC on the GPU, threshold RANSAC_THRESHOLD = 10 px).
+     * The reference runs cv::findHomography on OpenCV's global RNG with a confidence-based early stop; this runs the project's
+     * own deterministic contract (include/sfmba.h, sfmba_homography_ransac) with all 2000 hypotheses -- OpenCV's default
+     * maxIters, where its loop stops at the latest -- and seed 0: the same call always gives the same count.
+     * @return the inlier count; 0 for fewer than 4 matches, no valid hypothesis, no HIP device or a device error.
+     */
+    static int findHomographyInliers(
+            const Features& left,
+            const Features& right,
+            const Matching& matches);
+
+    /**
+     * The same for a list of pairs in ONE device call: pair p = images[left[p]] -> images[right[p]] with matches[p];
+     * inliers[p] receives its count.  Pair p draws the sample stream of seed 0 + p (include/sfmba.h), so only pair 0 of a batch
+     * counts exactly what findHomographyInliers counts for it.
+     * @return false (every count 0; a line is written to stderr) when there is no HIP device or on a device error.
+     */
+    static bool findHomographyInliersBatch(
+            const std::vector<const Features*>& images,
+            const std::vector<int>&             left,
+            const std::vector<int>&             right,
+            const std::vector<const Matching*>& matches,
+            std::vector<int>&                   inliers);
+
     /**
      * Triangulate (recover 3D locations) from point matching.
      * @return true on success (false: no HIP device / device error; pointCloud untouched).

@@ -93,6 +93,29 @@ int sfmba_shim_find_camera_pose(const float* K /*[9]*/, int n, const float* xyz 
 }
 
 namespace {
+std::vector<sfmtoylib::Features> buildKeyPoints(int n_images, const int64_t* img_ptr, const float* xy) {
+    std::vector<sfmtoylib::Features> feats((size_t)n_images);
+    for (int v = 0; v < n_images; ++v)
+        for (int64_t f = img_ptr[v]; f < img_ptr[v + 1]; ++f) {
+            cv::KeyPoint kp; kp.pt = cv::Point2f(xy[2 * f], xy[2 * f + 1]);
+            feats[v].keyPoints.push_back(kp); feats[v].points.push_back(kp.pt);
+        }
+    return feats;
+}
+}  // namespace
+
+// Flat-array driver of sfmtoylib::SfMStereoUtilities::findHomographyInliers (tests/test_gpu_homography_ransac.py): img_ptr [3] / xy
+// hold the key points of the left (image 0) and the right image.  Returns the call's count.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_find_homography_inliers(const int64_t* img_ptr /*[3]*/, const float* xy, int n_match, const int32_t* query_idx, const int32_t* train_idx) {
+    using namespace sfmtoylib;
+    const std::vector<Features> feats = buildKeyPoints(2, img_ptr, xy);
+    Matching matches;
+    for (int i = 0; i < n_match; ++i) matches.push_back(cv::DMatch(query_idx[i], train_idx[i], 0.0f));
+    return SfMStereoUtilities::findHomographyInliers(feats[0], feats[1], matches);
+}
+
+namespace {
 using namespace sfmtoylib;
 PointCloud buildCloud(int n, const float* xyz, const int64_t* view_ptr, const int32_t* view_idx, const int32_t* feat_idx) {
     PointCloud cloud((size_t)n);
@@ -251,6 +274,23 @@ int64_t sfmba_shim_feature_match_matrix(int n_images, const int64_t* img_ptr, co
             sizes[(size_t)l * n_images + r] = (int64_t)mm[l][r].size();
             n = flattenMatching(mm[l][r], n, cap, query, train, img_idx, dist);
         }
+    }
+    return n;
+}
+
+// Flat-array driver of sfmtoylib::SfMFeatureMatching::sortViewsForBaseline: the map comes back in key order as keys [cap] and
+// pairs [cap][2] (left, right).  Returns the number of map entries (entries beyond cap are not written).
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_sort_views_for_baseline(int n_images, const int64_t* img_ptr, const float* xy, int n_pairs, const int32_t* left, const int32_t* right,
+                                       const int64_t* pair_ptr, const int32_t* query, const int32_t* train, int cap, float* keys, int32_t* pairs) {
+    using namespace sfmtoylib;
+    const std::vector<Features> feats = buildKeyPoints(n_images, img_ptr, xy);
+    const MatchMatrix mm = buildMatchMatrix(n_images, n_pairs, left, right, pair_ptr, query, train, nullptr);
+    const std::map<float, ImagePair> sorted = SfMFeatureMatching::sortViewsForBaseline(feats, mm);
+    int n = 0;
+    for (const auto& kv : sorted) {
+        if (n < cap) { keys[n] = kv.first; pairs[2 * n] = (int32_t)kv.second.left; pairs[2 * n + 1] = (int32_t)kv.second.right; }
+        ++n;
     }
     return n;
 }

@@ -287,3 +287,28 @@ def make_pnp_scene(n, outlier_frac, seed):
     uv[bad, 0] = rng.uniform(0, 1024, k)
     uv[bad, 1] = rng.uniform(0, 768, k)
     return dict(X=X, uv=uv, K=K, R=R, t=t, bad=bad)
+
+
+def make_homography_scene(n, outlier_frac, seed, size=(1024, 768)):
+    """One image pair for sfmba_homography_ransac: a dict with left [n,2] float32, right [n,2] float32 (pixels), the planted
+    H [3,3] (H[2,2] = 1) and bad [n] bool (the rows of right that were replaced by uniform clutter).
+
+    Left points are uniform in the size[0] x size[1] image; right points are the left points under H = a similarity (rotation
+    N(0, 0.05 rad), scale 1 + N(0, 0.05), translation N(0, 30 px)) with a perspective row N(0, 2e-5), plus 0.5 px Gaussian
+    noise; both sides are rounded through float32, as cv::Point2f holds them."""
+    rng = np.random.default_rng(seed)
+    w, h = float(size[0]), float(size[1])
+    th, sc = rng.normal(0, 0.05), 1.0 + rng.normal(0, 0.05)
+    tr = rng.normal(0, 30.0, 2)
+    pv = rng.normal(0, 2e-5, 2)
+    H = np.array([[sc * np.cos(th), -sc * np.sin(th), tr[0]], [sc * np.sin(th), sc * np.cos(th), tr[1]], [pv[0], pv[1], 1.0]])
+    left = rng.uniform(0, 1, (n, 2)) * np.array([w, h])
+    q = np.concatenate([left, np.ones((n, 1))], axis=1) @ H.T
+    right = q[:, :2] / q[:, 2:3] + rng.normal(0, 0.5, (n, 2))
+    left = left.astype(np.float32)
+    right = right.astype(np.float32)
+    bad = rng.random(n) < outlier_frac
+    k = int(bad.sum())
+    right[bad, 0] = rng.uniform(0, w, k)
+    right[bad, 1] = rng.uniform(0, h, k)
+    return dict(left=left, right=right, H=H, bad=bad)

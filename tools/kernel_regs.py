@@ -10,7 +10,7 @@ rows = {}
 for line in out.splitlines():
     m = re.search(r"remark: Function Name: (\S+)", line)
     if m:
-        cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
+        cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "").split("(")[0]
         rows[cur] = {}
         continue
     m = re.search(r"remark:\s+(VGPRs|AGPRs|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]|TotalSGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
