@@ -474,8 +474,9 @@ SFMBA_API int  sfmba_shard_last_exchange(const sfmba_problem* p, int64_t out[4])
 /*
  * The step in front of bundle adjustment: SfMStereoUtilities::triangulateViews
  * (SfMToyLib/SfMStereoUtilities.cpp:120-206) for n ALIGNED matches -- normalise with K (no distortion), DLT
- * triangulation (cv::triangulatePoints), de-homogenise, re-project into both views, keep[i] = both reprojection errors
- * <= max_reproj_px (the reference's MIN_REPROJECTION_ERROR = 10, :42).  left_xy / right_xy [n][2] pixels, K [9]
+ * triangulation (cv::triangulatePoints), de-homogenise, re-project into both views; a match is kept unless an error >
+ * max_reproj_px (the reference's MIN_REPROJECTION_ERROR = 10, :42; its test is norm(...) > 10, :186, so a NaN error is
+ * kept), keep[i] = 1 then.  left_xy / right_xy [n][2] pixels, K [9]
  * row-major, P_left / P_right [12] row-major [R|t]; outputs points3d [n][3], keep [n] and (optional) reproj_err [n][2].
  * Host pointers; the computation runs on `device`.
  */

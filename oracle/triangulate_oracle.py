@@ -31,6 +31,7 @@ def triangulate_views(K, P_left, P_right, left_xy, right_xy, max_err=MIN_REPROJE
 
     def normalise(p):
         q = np.stack([(p[:, 0].astype(np.float64) - cx) / fx, (p[:, 1].astype(np.float64) - cy) / fy], axis=1)
+        q[~np.isfinite(q).all(axis=1)] = np.nan      # undistortPoints' homogeneous product with R = I: 0 * inf, both coordinates NaN
         return q.astype(np.float32).astype(np.float64)
 
     nl, nr = normalise(l), normalise(r)

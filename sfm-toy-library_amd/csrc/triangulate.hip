@@ -3,13 +3,14 @@
 // Device counterpart of SfMStereoUtilities::triangulateViews for ALIGNED matches
 // (SfMToyLib/SfMStereoUtilities.cpp:120-206): per match
 //   :145-149  undistortPoints with no distortion         x_n = (u - cx)/fx, y_n = (v - cy)/fy            (-> float)
+//                                                        (NaN, NaN) for a pixel that is not finite, see normalise_px
 //   :151-152  cv::triangulatePoints [OpenCV-upstream]    A = [x P3 - P1; y P3 - P2] of both views, 4x4, fp64;
 //                                                        X_h = right singular vector of the smallest singular value (-> float)
 //   :154-155  convertPointsFromHomogeneous               X = X_h.xyz / X_h.w                               (float)
 //   :157-169  projectPoints (Rodrigues(R) == R)          u = fx (R X + t)_x / (R X + t)_z + cx, fp64      (-> float)
-//   :183-190  keep iff both reprojection errors <= 10 px (MIN_REPROJECTION_ERROR, :42)
+//   :183-190  kept unless a reprojection error > 10 px (MIN_REPROJECTION_ERROR, :42): a NaN error is kept
 // One lane per match, everything in registers: the 4x4 SVD is a one-sided (Hestenes) Jacobi iteration on the columns of A
-// with V accumulated -- 6 sweeps of the 6 column pairs, no LDS, no divergence beyond the rotation skip.  The pass is
+// with V accumulated -- 8 sweeps of the 6 column pairs, no LDS, no divergence beyond the rotation skip.  The pass is
 // HBM-trivial (16 B in, 13 B out per match); it exists so that the step in front of bundle adjustment need not leave the GPU.
 #include "ba_kernels.h"
 
@@ -40,6 +41,18 @@ __device__ __forceinline__ void jacobi_pair(double A[4][4], double V[4][4], int 
     }
 }
 
+// undistortPoints without distortion still takes the normalised point through its homogeneous product with R = I
+// [OpenCV-upstream: xx = 1 x + 0 y + 0, yy = 0 x + 1 y + 0, ww = 1 / (0 x + 0 y + 1), (xx ww, yy ww)]: a finite pixel passes
+// unchanged, a pixel with a NaN or an infinite coordinate comes out as (NaN, NaN) through 0 * inf -- and then has a NaN point
+// and NaN errors, which the filter keeps.  Without this an infinite pixel met the rotation skip of jacobi_pair as inf <= inf,
+// left V the identity and gave the finite point (1, 0, 0), dropped on its infinite error.
+__device__ __forceinline__ float2 normalise_px(float2 p, double fx, double fy, double cx, double cy) {
+    const double x = ((double)p.x - cx) / fx, y = ((double)p.y - cy) / fy;
+    const bool finite = isfinite(x) && isfinite(y);
+    const double nan = __builtin_nan("");
+    return make_float2((float)(finite ? x : nan), (float)(finite ? y : nan));
+}
+
 __device__ __forceinline__ float2 project_px(const float* P, const float* K, const float X[3]) {
     const double x = (double)P[0] * X[0] + (double)P[1] * X[1] + (double)P[2] * X[2] + (double)P[3];
     const double y = (double)P[4] * X[0] + (double)P[5] * X[1] + (double)P[6] * X[2] + (double)P[7];
@@ -54,8 +67,8 @@ __global__ __launch_bounds__(256) void k_triangulate(long long n, const float2* 
     if (i >= n) return;
     const float2 l = left[i], r = right[i];
     const double fx = cams.K[0], fy = cams.K[4], cx = cams.K[2], cy = cams.K[5];
-    const double xl = (double)(float)(((double)l.x - cx) / fx), yl = (double)(float)(((double)l.y - cy) / fy);
-    const double xr = (double)(float)(((double)r.x - cx) / fx), yr = (double)(float)(((double)r.y - cy) / fy);
+    const float2 nl = normalise_px(l, fx, fy, cx, cy), nr = normalise_px(r, fx, fy, cx, cy);
+    const double xl = (double)nl.x, yl = (double)nl.y, xr = (double)nr.x, yr = (double)nr.y;
     double A[4][4], V[4][4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {

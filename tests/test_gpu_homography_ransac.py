@@ -12,7 +12,8 @@ figures they rest on without a GPU):
             of 0); the oracle alone finds none
 Scene sizes: the minimum (4, 5), one wave +- 1 (64, 65), several waves (300), two chunks (2000) and the score kernel's LDS chunk
 - 1, + 0, + 1; the 2000-point scene once more on a 4096 x 3072 image, where fp32 has the fewest bits left for the decision.  Every
-scene reaches the device through shuffled key point lists and index arrays, as a match list does."""
+scene reaches the device through shuffled key point lists and index arrays, as a match list does.  Section 8: one list past the
+score kernel's grid cap (HOM_MAX_CHUNK_BLOCKS * HOM_CHUNK + HOM_CHUNK + 1 correspondences), alone and inside a batch of short ones."""
 import ctypes as C
 import os
 import re
@@ -335,3 +336,73 @@ def test_shim_sort_views_for_baseline(capi):
                                                keys.ctypes.data_as(fp), out.ctypes.data_as(ip))
     assert n == len(want)
     assert [(k, tuple(v)) for k, v in zip(keys[:n], out[:n])] == [(k, want[k]) for k in sorted(want)]
+
+
+# ---- 8. a list past the score kernel's grid cap -------------------------------------------------------------------------
+# k_hom_score caps grid.y at HOM_MAX_CHUNK_BLOCKS; past HOM_MAX_CHUNK_BLOCKS * HOM_CHUNK correspondences a block walks several
+# chunks and reuses its LDS tile.  LONG_N: two blocks make a second trip, and the last chunk, reached on that trip, holds ONE
+# correspondence.  65 hypotheses: the second tile has one live lane.
+MAX_CHUNK_BLOCKS = int(re.search(r"HOM_MAX_CHUNK_BLOCKS\s*=\s*(\d+)", open(os.path.join(ROOT, "sfm-toy-library_amd", "csrc", "homography_ransac.h")).read()).group(1))
+FIRST_TRIP = MAX_CHUNK_BLOCKS * CHUNK
+LONG_N = FIRST_TRIP + CHUNK + 1
+LONG_SEED = 21
+LONG_HYP = 65
+
+
+@pytest.fixture(scope="module")
+def long_scene():
+    """(scene, its arrays as the C ABI takes them, the oracle's answer for seed 0): computed once, never modified.  The tail must
+    matter: the oracle's winner has more inliers past the first trip than border points, so a count without them cannot pass."""
+    import sfm_toy_library_amd as sfm
+    sc = sfm.make_homography_scene(LONG_N, 0.3, LONG_SEED)
+    want = ho.homography_ransac(sc["left"], sc["right"], n_hyp=LONG_HYP, threshold_px=THR, seed=0)
+    assert want["status"] == 0
+    tail, border = int(want["inlier"][FIRST_TRIP:].sum()), ho.border_points(want["H"], sc["left"], sc["right"], THR)
+    print("front_end_edges homography long list: n %d, oracle winner %d with %d inliers, %d of them past the first trip, %d border points"
+          % (LONG_N, want["best_hypothesis"], want["n_inliers"], tail, border))
+    assert len(sc["left"]) == LONG_N == FIRST_TRIP + CHUNK + 1 and tail > border and tail > 0.5 * (LONG_N - FIRST_TRIP)
+    assert want["inlier"][-1] or want["inlier"][FIRST_TRIP:FIRST_TRIP + CHUNK].sum() > border      # either later chunk alone would show
+    return sc, ho.scene_arrays(sc, LONG_SEED), want
+
+
+@pytest.fixture(scope="module")
+def long_run(capi, long_scene):
+    return call(capi, long_scene[1], n_hyp=LONG_HYP, debug=True)
+
+
+def test_long_list_counts_against_fp64_recount(long_scene, long_run):
+    sc, _, want = long_scene
+    r = long_run
+    L, R = sc["left"], sc["right"]
+    counts = r["hyp_count"]
+    assert r["status"] == 0 and r["n_matches"] == LONG_N and len(counts) == LONG_HYP
+    worst = 0.0
+    for h in np.flatnonzero(counts >= 0):
+        recount = int(ho.inlier_mask(r["hyp_H"][h], L, R, THR).sum())
+        border = ho.border_points(r["hyp_H"][h], L, R, THR)
+        worst = max(worst, abs(int(counts[h]) - recount) / max(border, 1))
+        assert abs(int(counts[h]) - recount) <= border, (h, counts[h], recount, border)
+    print("front_end_edges homography long list: worst |count - fp64 recount| / border count over %d valid hypotheses: %.3f" % ((counts >= 0).sum(), worst))
+    sure = np.array([not ho.ill_conditioned(info) for _, _, info in want["hyp"]])
+    assert np.array_equal((counts >= 0)[sure], (want["hyp_count"] >= 0)[sure]) and sure.sum() >= LONG_HYP - 1
+    assert counts[LONG_HYP - 1] >= 0 and want["hyp_count"][LONG_HYP - 1] >= 0           # the one live lane of the second tile is a valid one
+    assert r["best_hypothesis"] == int(np.argmax(counts))                                # the first maximum
+    assert int(r["inlier"].sum()) == r["n_inliers"] == int(counts[r["best_hypothesis"]])
+    assert r["H"].tobytes() == r["hyp_H"][r["best_hypothesis"]].tobytes()
+    assert r["n_inliers"] >= want["n_inliers"] - ho.border_points(want["H"], L, R, THR)
+    assert int(r["inlier"][FIRST_TRIP:].sum()) > 0.5 * (LONG_N - FIRST_TRIP)
+
+
+def test_long_list_in_a_mixed_batch(capi, scenes, long_scene):
+    """grid.y is at its cap while three of the four pairs have one chunk: 5, LONG_N, 300 and HOM_CHUNK correspondences."""
+    arrays = [scenes[(5, 0.0, 2)][1], long_scene[1], scenes[(300, 0.45, 5)][1], scenes[(CHUNK, 0.3, 8)][1]]
+    assert [len(a[2]) for a in arrays] == [5, LONG_N, 300, CHUNK]
+    seed = 41
+    batch = capi.homography_ransac(*as_batch(arrays), n_hyp=LONG_HYP, seed=seed, debug=True)
+    for p, arr in enumerate(arrays):
+        same_bytes(batch[p], call(capi, arr, n_hyp=LONG_HYP, seed=seed + p, debug=True))
+        assert batch[p]["status"] == 0
+
+
+def test_long_list_two_calls_are_byte_equal(capi, long_scene, long_run):
+    same_bytes(long_run, call(capi, long_scene[1], n_hyp=LONG_HYP, debug=True))

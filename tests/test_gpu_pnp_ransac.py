@@ -11,7 +11,8 @@ Bounds (all set by the contract's issue, none taken from the device's output):
   1e-8    per pose entry between the device's Gauss-Newton and the oracle's from the same start on the same inliers
           (the oracle against scipy: 2.7e-11), 1e-9 relative on the cost
 Scene sizes: the minimum (4, 5), one wave +- 1 (64, 65), several waves (300), two chunks (2000) and the score kernel's LDS chunk
-- 1, + 0, + 1."""
+- 1, + 0, + 1.  Section 9: one list past the score kernel's grid cap (PNP_MAX_CHUNK_BLOCKS * PNP_CHUNK + PNP_CHUNK + 1 points),
+alone and inside a batch of short ones."""
 import ctypes as C
 import json
 import os
@@ -271,3 +272,86 @@ def test_shim_gate(capfd):
     ok, pose = shim_pose(sc["K"], sc["X"], sc["uv"], before)
     assert ok
     assert np.abs(pose[:, :3] - sc["R"]).max() < 0.01 and np.abs(pose[:, 3] - sc["t"]).max() < 0.1
+
+
+# ---- 9. a list past the score kernel's grid cap -------------------------------------------------------------------------
+# k_pnp_score caps grid.y at PNP_MAX_CHUNK_BLOCKS; past PNP_MAX_CHUNK_BLOCKS * PNP_CHUNK points a block walks several chunks and
+# reuses its LDS tile.  LONG_N: two blocks make a second trip, and the last chunk, reached on that trip, holds ONE point.
+# 65 hypotheses: the second tile has one live lane.  The refinement's fixed-order sums then run over about 46 000 inliers.
+MAX_CHUNK_BLOCKS = int(re.search(r"PNP_MAX_CHUNK_BLOCKS\s*=\s*(\d+)", open(os.path.join(ROOT, "sfm-toy-library_amd", "csrc", "pnp_ransac.h")).read()).group(1))
+FIRST_TRIP = MAX_CHUNK_BLOCKS * CHUNK
+LONG_N = FIRST_TRIP + CHUNK + 1
+LONG_SEED = 21
+LONG_HYP = 65
+
+
+@pytest.fixture(scope="module")
+def long_scene():
+    """(scene, the oracle's answer for seed 0): computed once, never modified.  The tail must matter: the oracle's winner has more
+    inliers past the first trip than border points, so a count without them cannot pass."""
+    import sfm_toy_library_amd as sfm
+    sc = sfm.make_pnp_scene(LONG_N, 0.3, LONG_SEED)
+    want = po.pnp_ransac(sc["X"], sc["uv"], sc["K"], n_hyp=LONG_HYP, threshold_px=THR, seed=0, max_refine_iters=0)
+    assert want["status"] == 0
+    tail, border = int(want["inlier"][FIRST_TRIP:].sum()), po.border_points(want["pose"], sc["X"], sc["uv"], sc["K"], THR)
+    print("front_end_edges pnp long list: n %d, oracle winner %d with %d inliers, %d of them past the first trip, %d border points"
+          % (LONG_N, want["best_hypothesis"], want["n_inliers"], tail, border))
+    assert len(sc["X"]) == LONG_N == FIRST_TRIP + CHUNK + 1 and tail > border and tail > 0.5 * (LONG_N - FIRST_TRIP)
+    return sc, want
+
+
+@pytest.fixture(scope="module")
+def long_run(capi, long_scene):
+    sc, _ = long_scene
+    return capi.pnp_ransac([(sc["X"], sc["uv"])], sc["K"], n_hyp=LONG_HYP, debug=True)[0]
+
+
+def test_long_list_counts_against_fp64_recount(long_scene, long_run):
+    sc, want = long_scene
+    r = long_run
+    X, uv, K = sc["X"], sc["uv"], sc["K"]
+    counts = r["hyp_count"]
+    assert r["status"] == 0 and len(counts) == LONG_HYP and len(r["inlier"]) == LONG_N
+    worst = 0.0
+    for h in np.flatnonzero(counts >= 0):
+        recount = int(po.inlier_mask(r["hyp_pose"][h], X, uv, K, THR).sum())
+        border = po.border_points(r["hyp_pose"][h], X, uv, K, THR)
+        worst = max(worst, abs(int(counts[h]) - recount) / max(border, 1))
+        assert abs(int(counts[h]) - recount) <= border, (h, counts[h], recount, border)
+    print("front_end_edges pnp long list: worst |count - fp64 recount| / border count over %d valid hypotheses: %.3f" % ((counts >= 0).sum(), worst))
+    assert (counts >= 0).sum() > LONG_HYP // 2
+    assert r["best_hypothesis"] == int(np.argmax(counts))                                # the first maximum
+    assert int(r["inlier"].sum()) == r["n_inliers"] == int(counts[r["best_hypothesis"]])
+    assert r["n_inliers"] >= want["n_inliers"] - po.border_points(want["pose"], X, uv, K, THR)
+    assert int(r["inlier"][FIRST_TRIP:].sum()) > 0.5 * (LONG_N - FIRST_TRIP)
+
+
+def test_long_list_refinement_against_oracle(capi, long_scene, long_run):
+    sc, _ = long_scene
+    r = long_run
+    X, uv, K = sc["X"].astype(np.float64), sc["uv"].astype(np.float64), sc["K"]
+    start, mask = r["hyp_pose"][r["best_hypothesis"]], r["inlier"]
+    pose, cost, iters, status = po.refine(start, X[mask], uv[mask], K, 20)
+    print("front_end_edges pnp long list: refinement over %d inliers: |pose - oracle| %.2e, cost relative %.2e, iterations %d (oracle %d)"
+          % (mask.sum(), np.abs(r["pose"] - pose).max(), abs(r["refine_cost"] - cost) / cost, r["refine_iters"], iters))
+    assert status == 0 and r["status"] == 0 and mask.sum() > 40000
+    assert 1 <= r["refine_iters"] <= 20 and r["refine_iters"] == iters
+    assert np.abs(r["pose"] - pose).max() < 1e-8
+    assert abs(r["refine_cost"] - cost) <= 1e-9 * cost
+
+
+def test_long_list_in_a_mixed_batch(capi, scenes, long_scene):
+    """grid.y is at its cap while three of the four problems have one chunk: 5, LONG_N, 300 and PNP_CHUNK points."""
+    scs = [scenes[(5, 0.0, 2)][0], long_scene[0], scenes[(300, 0.45, 5)][0], scenes[(CHUNK, 0.3, 8)][0]]
+    probs = [(s["X"], s["uv"]) for s in scs]
+    assert [len(x) for x, _ in probs] == [5, LONG_N, 300, CHUNK]
+    K, seed = scs[0]["K"], 41
+    batch = capi.pnp_ransac(probs, K, n_hyp=LONG_HYP, seed=seed, debug=True)
+    for p, prob in enumerate(probs):
+        same_bytes(batch[p], capi.pnp_ransac([prob], K, n_hyp=LONG_HYP, seed=seed + p, debug=True)[0])
+        assert batch[p]["status"] == 0
+
+
+def test_long_list_two_calls_are_byte_equal(capi, long_scene, long_run):
+    sc, _ = long_scene
+    same_bytes(long_run, capi.pnp_ransac([(sc["X"], sc["uv"])], sc["K"], n_hyp=LONG_HYP, debug=True)[0])
