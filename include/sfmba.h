@@ -648,6 +648,73 @@ SFMBA_API int sfmba_homography_ransac(int device, int n_images, const int64_t* i
                 double* H /*[n_pairs][9]*/, unsigned char* inlier /*[pair_ptr[n_pairs]]*/, sfmba_homography_result* result,
                 double* hyp_H /*[n_pairs][n_hyp][9] or NULL*/, int32_t* hyp_count /*[n_pairs][n_hyp] or NULL*/);
 
+/*
+ * Recover the relative pose of an image pair from its matches (SfMStereoUtilities::findCameraMatricesFromMatch,
+ * SfMToyLib/SfMStereoUtilities.cpp:74-118: cv::findEssentialMat(RANSAC, 0.999, 1 px) + cv::recoverPose, Pleft = I, Pright = [R|t],
+ * the matches pruned by the final mask) for a batch of image pairs in one call: the baseline loop (SfM.cpp:236-320) and the pairs
+ * (good view, new view) of every added view (SfM.cpp:413-431).  The reference's result depends on OpenCV's global RNG and on its
+ * confidence-based early stop; THIS CONTRACT IS OUR OWN, deterministic one -- it is not, and does not claim to be, the sample stream
+ * of cv::findEssentialMat.  It is tested against a CPU restatement of itself (tests/essential_oracle.py).
+ *
+ *   problems      the arrays of sfmba_homography_ransac (n_images, img_ptr, pts, n_pairs, pair_left, pair_right, pair_ptr, query_idx,
+ *                 train_idx: entry i of pair p is x = pts[img_ptr[pair_left[p]] + query_idx[i]] -> x' = pts[img_ptr[pair_right[p]] +
+ *                 train_idx[i]], gathered on the device) plus K [9] row-major, of which only fx = K[0], fy = K[4], cx = K[2],
+ *                 cy = K[5] are read, as in sfmba_pnp_ransac.  left == right and repeated indices inside a pair are allowed.
+ *   sample        the stream of sfmba_pnp_ransac: key = mix(seed + p); draw k = 0, 1, .., 63 of hypothesis h is entry
+ *                 mix(key ^ ((h << 8) | k)) mod n; the sample is the first SIX DISTINCT entries in draw order; a hypothesis that
+ *                 has not found six by draw 63 is invalid.  Entries 0..4 go to the solver, entry 5 selects among its solutions.
+ *                 Integer work: exact.
+ *   hypothesis    fp64, on the normalised points x = ((u - cx) / fx, (v - cy) / fy, 1).  The four-dimensional null space of the
+ *                 5 x 9 epipolar system x'^T E x = 0 (invalid if the system is rank-deficient: a pivot of the completely pivoted
+ *                 elimination at or below 1e-12 of its largest entry -- five collinear or coinciding points); the ten cubic
+ *                 constraints det E = 0 and 2 E E^T E - tr(E E^T) E = 0 on the 20 monomials of (x, y, z) up to degree 3;
+ *                 elimination of the 10 x 20 system (invalid if the eliminated 10 x 10 block is singular: a pivot at or below 1e-13
+ *                 of the largest entry); the real solutions -- at most 10 -- from the real roots of the degree-10 polynomial in z
+ *                 (Sturm's sequence and bisection, two Newton steps), x and y back-substituted, each solution then polished by three
+ *                 Gauss-Newton steps on the ten constraints themselves.  Every solution is scaled to Frobenius norm sqrt 2; of them
+ *                 the one with the smallest squared Sampson distance at the sixth correspondence (normalised points; the first in
+ *                 ascending z on a tie) is kept and its sign fixed so that its entry of largest magnitude (the first on ties, row-
+ *                 major) is positive.  Invalid if there is no real solution or on any non-finite value.  An invalid hypothesis has
+ *                 hyp_count = -1 and a zero hyp_E.  hyp_nsol = the number of real solutions found.
+ *   score         the squared Sampson distance in pixels, cv::findEssentialMat's error: with centred pixels p = (u - cx, v - cy, 1),
+ *                 F = diag(1/fx, 1/fy, 1) E diag(1/fx, 1/fy, 1), l' = F p, l = F^T p' and e = p' . l', a correspondence is an inlier
+ *                 iff e^2 <= threshold_px^2 (l'_1^2 + l'_2^2 + l_1^2 + l_2^2) and that sum is > 0.  One device function takes this
+ *                 decision for the count and for the mask (division-free on centred pixels, F scaled by fx fy; the residual e in
+ *                 fp64, because its terms cancel from ~fx fy down to a pixel and the fp32 bound of that leaves the 5e-3 px band; the
+ *                 gradient sum in fp32: decisions can differ from fp64 only within ~1e-6 px of the threshold), so
+ *                 n_inliers == hyp_count[best_hypothesis] == the size of the winner's mask exactly.
+ *   winner        the valid hypothesis with the largest count; ties go to the lowest h.  E [p] is the winner's hypothesis as it
+ *                 stands: there is no refit.  All n_hyp hypotheses are evaluated: there is no confidence-based early stop.
+ *   pose          recoverPose in fp64 on the winner's inliers only.  The four candidates in closed form (Horn 1990): t t^T =
+ *                 1/2 tr(E E^T) I - E E^T, t = its column with the largest diagonal entry (the first on ties) over the root of that
+ *                 entry, so |t| = 1; R(+-t) = cof(E) - [+-t]x E with cof the cofactor matrix (not its transpose).  Candidate order:
+ *                 (R(+t), +t), (R(-t), -t), (R(-t), +t), (R(+t), -t).  An inlier is IN FRONT for a candidate iff the least-squares
+ *                 depths lambda, lambda' of lambda' x' = lambda R x + t satisfy 0 < lambda < 50 and 0 < lambda' < 50 and the
+ *                 determinant of their 2 x 2 normal equations, |R x  x  x'|^2, is > 0 (50 is OpenCV's distanceThresh at |t| = 1).
+ *                 The pose is the candidate with the most points in front, ties to the lowest index (integer counts).  inlier is
+ *                 the winner's mask AND in-front-for-the-chosen-pose, as recoverPose updates its mask and the reference prunes.
+ *   status        0 ok | 1 fewer than 6 matches: E = 0, pose = [I|0], mask zero, best_hypothesis = -1, n_inliers = 0 | 2 no valid
+ *                 hypothesis: same outputs as 1 | 3 a winner, but no point in front for any candidate (or E has no translation):
+ *                 E, best_hypothesis and n_inliers are valid, pose = [I|0], mask zero.  n_pose_inliers = the size of the final mask;
+ *                 pose_candidate = 0..3, -1 unless status is 0; n_matches echoes the pair's number of entries.
+ *
+ * Outputs: E [n_pairs][9] row-major (fp64), pose [n_pairs][12] row-major [R|t] (fp64), inlier [pair_ptr[n_pairs]] (entries in front
+ * of pair_ptr[0] are written as 0), result [n_pairs]; optional (NULL or not) hyp_E [n_pairs][n_hyp][9], hyp_count [n_pairs][n_hyp]
+ * and hyp_nsol [n_pairs][n_hyp].  Host pointers in and out, synchronous.  A degenerate pair never makes the call fail: the others of
+ * the batch are still answered.  SFMBA_ERR_INVALID_ARG for n_hyp outside 1..65536, a non-finite or non-positive threshold_px, fx or
+ * fy, a negative or decreasing img_ptr or pair_ptr, a pair index out of range, a query_idx or train_idx outside its image (checked on
+ * the host before anything is launched), a pair of 2^31 or more matches.  Deterministic: the same arguments give the same bytes in
+ * every output (counts are integer atomics).
+ */
+typedef struct sfmba_essential_result { int status; int best_hypothesis; int n_inliers; int n_pose_inliers; int pose_candidate; int n_matches; } sfmba_essential_result;
+SFMBA_API int sfmba_essential_ransac(int device, int n_images, const int64_t* img_ptr, const float* pts /*[img_ptr[n_images]][2]*/,
+                int n_pairs, const int32_t* pair_left, const int32_t* pair_right,
+                const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx, const float* K /*[9]*/,
+                int n_hyp, float threshold_px, uint64_t seed,
+                double* E /*[n_pairs][9]*/, double* pose /*[n_pairs][12]*/, unsigned char* inlier /*[pair_ptr[n_pairs]]*/,
+                sfmba_essential_result* result, double* hyp_E /*[n_pairs][n_hyp][9] or NULL*/,
+                int32_t* hyp_count /*[n_pairs][n_hyp] or NULL*/, int32_t* hyp_nsol /*[n_pairs][n_hyp] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

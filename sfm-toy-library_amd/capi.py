@@ -35,7 +35,7 @@ SYMBOLS = [
     "sfmba_problem_create_ex", "sfmba_comm_abort", "sfmba_comm_reduce_scatter", "sfmba_problem_set_reduce_scatter",
     "sfmba_comm_allgather", "sfmba_problem_set_allgather", "sfmba_comm_size", "sfmba_device_warmup",
     "sfmba_match_features", "sfmba_problem_set_step_probe", "sfmba_problem_get_step_probe", "sfmba_pnp_ransac",
-    "sfmba_homography_ransac",
+    "sfmba_homography_ransac", "sfmba_essential_ransac",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -276,6 +276,65 @@ def homography_ransac(pts_per_image, pairs, matches, n_hyp=2000, threshold_px=10
         if debug:
             d["hyp_H"] = hh[p * n_hyp:(p + 1) * n_hyp].reshape(n_hyp, 3, 3).copy()
             d["hyp_count"] = hc[p * n_hyp:(p + 1) * n_hyp].copy()
+        out.append(d)
+    return out
+
+
+class _EssentialResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("best_hypothesis", C.c_int), ("n_inliers", C.c_int), ("n_pose_inliers", C.c_int),
+                ("pose_candidate", C.c_int), ("n_matches", C.c_int)]
+
+
+def essential_ransac(pts_per_image, pairs, matches, K, n_hyp=1000, threshold_px=1.0, seed=0, debug=False, device=0):
+    """sfmba_essential_ransac: five-point essential-matrix RANSAC + recoverPose for every image pair of a batch (the contract is in
+    include/sfmba.h).
+
+    pts_per_image, pairs, matches: as homography_ransac takes them.  K [3, 3].  Returns one dict per pair: status, best_hypothesis,
+    n_inliers, n_pose_inliers, pose_candidate, n_matches, E [3, 3] float64, pose [3, 4] float64 ([R|t]), inlier [n_p] bool (the
+    winner's mask AND in front for the pose); with debug=True also hyp_E [n_hyp, 3, 3], hyp_count [n_hyp] (-1 = invalid) and
+    hyp_nsol [n_hyp] (every hypothesis' E, count and number of real solutions)."""
+    ps = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 2) for x in pts_per_image]
+    if len(matches) == 6:
+        pl, pr, ptr, q, t = matches[:5]
+    else:
+        if pairs is None:
+            pairs = [(i, j) for i in range(len(ps)) for j in range(i + 1, len(ps))]
+        pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        pl, pr = pairs[:, 0], pairs[:, 1]
+        ptr, q, t = matches
+    pl, pr, q, t = _i(pl), _i(pr), _i(q), _i(t)
+    ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+    n_pairs = len(pl)
+    if len(pr) != n_pairs or len(ptr) != n_pairs + 1 or len(q) != len(t) or (n_pairs and len(q) < ptr[-1]):
+        raise ValueError("pair_left / pair_right / pair_ptr / query_idx / train_idx do not fit together")
+    img_ptr = np.zeros(len(ps) + 1, dtype=np.int64)
+    img_ptr[1:] = np.cumsum([len(x) for x in ps])
+    pts = np.ascontiguousarray(np.concatenate(ps, axis=0) if ps else np.zeros((0, 2), np.float32))
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    total = int(ptr[-1]) if n_pairs else 0
+    E = np.zeros((max(n_pairs, 1), 9))
+    pose = np.zeros((max(n_pairs, 1), 12))
+    inl = np.zeros(max(total, 1), dtype=np.uint8)
+    res = (_EssentialResult * max(n_pairs, 1))()
+    n_dbg = max(n_pairs, 1) * max(int(n_hyp), 1) if debug else 0
+    he = np.zeros((n_dbg, 9)) if debug else None
+    hc = np.zeros(n_dbg, dtype=np.int32) if debug else None
+    hn = np.zeros(n_dbg, dtype=np.int32) if debug else None
+    lp, fp = C.POINTER(C.c_int64), C.POINTER(C.c_float)
+    _check(lib().sfmba_essential_ransac(C.c_int(device), C.c_int(len(ps)), _p(img_ptr, lp), _p(pts, fp), C.c_int(n_pairs), _p(pl, _ip),
+                                        _p(pr, _ip), _p(ptr, lp), _p(q, _ip), _p(t, _ip), _p(K, fp), C.c_int(n_hyp), C.c_float(threshold_px),
+                                        C.c_uint64(seed), _p(E, _dp), _p(pose, _dp), inl.ctypes.data_as(C.POINTER(C.c_ubyte)), res,
+                                        _p(he, _dp) if debug else None, _p(hc, _ip) if debug else None, _p(hn, _ip) if debug else None))
+    out = []
+    for p in range(n_pairs):
+        d = {k: getattr(res[p], k) for k, _ in _EssentialResult._fields_}
+        d["E"] = E[p].reshape(3, 3).copy()
+        d["pose"] = pose[p].reshape(3, 4).copy()
+        d["inlier"] = inl[ptr[p]:ptr[p + 1]].astype(bool)
+        if debug:
+            d["hyp_E"] = he[p * n_hyp:(p + 1) * n_hyp].reshape(n_hyp, 3, 3).copy()
+            d["hyp_count"] = hc[p * n_hyp:(p + 1) * n_hyp].copy()
+            d["hyp_nsol"] = hn[p * n_hyp:(p + 1) * n_hyp].copy()
         out.append(d)
     return out
 

@@ -1,4 +1,4 @@
-// ransac_common.h -- what the batched RANSAC units share (pnp_ransac.hip, homography_ransac.hip): the seeded sampler of their
+// ransac_common.h -- what the batched RANSAC units share (pnp_ransac.hip, homography_ransac.hip, essential_ransac.hip): the seeded sampler of their
 // contracts (include/sfmba.h) and the wave-wide maximum their select kernels take the winner with.  Plain C++ apart from the
 // qualifiers, so a host build can exercise the sampler.
 #pragma once
@@ -37,6 +37,27 @@ PNP_HD bool pnp_sample(uint64_t key, int h, long long n, long long& i0, long lon
     i2 = pnp_next_draw(key, h, (uint64_t)n, k, i0, i1, -1);
     i3 = pnp_next_draw(key, h, (uint64_t)n, k, i0, i1, i2);
     return i3 >= 0;
+}
+
+// The first six distinct indices of the same draws (sfmba_essential_ransac); false when there are fewer.  No run-time index into
+// id: every store is a select, so the array stays in registers.
+PNP_HD bool pnp_sample6(uint64_t key, int h, long long n, long long (&id)[6]) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) id[j] = -1;
+    if (n < 6) return false;
+    int got = 0;
+    for (int k = 0; k < 64 && got < 6; ++k) {
+        const long long i = (long long)(pnp_mix(key ^ (((uint64_t)(unsigned)h << 8) | (uint64_t)k)) % (uint64_t)n);
+        bool dup = false;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) dup = dup || id[j] == i;
+        if (dup) continue;
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+            if (j == got) id[j] = i;
+        ++got;
+    }
+    return got == 6;
 }
 
 // the largest value of the wave, in every lane

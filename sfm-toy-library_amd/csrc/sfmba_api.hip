@@ -7,6 +7,7 @@
 #include "lm_loop.h"
 #include "pnp_ransac.h"
 #include "homography_ransac.h"
+#include "essential_ransac.h"
 #include <climits>
 #include <cmath>
 
@@ -555,6 +556,49 @@ int sfmba_homography_ransac(int device, int n_images, const int64_t* img_ptr, co
     if (rc == HOM_ERR_TOO_LARGE) return fail(SFMBA_ERR_INVALID_ARG, "homography_ransac: too many pairs x hypotheses for one call");
     if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "homography_ransac: device allocation failed");
     if (rc) return fail(SFMBA_ERR_HIP, std::string("homography_ransac: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+// ---- pose of an image pair (SfMStereoUtilities::findCameraMatricesFromMatch) -------------------------------------------
+int sfmba_essential_ransac(int device, int n_images, const int64_t* img_ptr, const float* pts, int n_pairs, const int32_t* pair_left,
+                           const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx, const float* K,
+                           int n_hyp, float threshold_px, uint64_t seed, double* E, double* pose, unsigned char* inlier,
+                           sfmba_essential_result* result, double* hyp_E, int32_t* hyp_count, int32_t* hyp_nsol) {
+    if (n_images < 0 || n_pairs < 0 || !img_ptr || !pair_ptr || !K || (n_pairs > 0 && (!pair_left || !pair_right || !E || !pose || !result)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (n_hyp < 1 || n_hyp > 65536) return fail(SFMBA_ERR_INVALID_ARG, "n_hyp must be in 1..65536");
+    if (!std::isfinite(threshold_px) || !(threshold_px > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "threshold_px must be finite and > 0");
+    if (!std::isfinite(K[0]) || !(K[0] > 0.0f) || !std::isfinite(K[4]) || !(K[4] > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "fx and fy must be finite and > 0");
+    if (img_ptr[0] < 0 || pair_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr and pair_ptr must not be negative");
+    for (int i = 0; i < n_images; ++i)
+        if (img_ptr[i + 1] < img_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
+    for (int p = 0; p < n_pairs; ++p) {
+        if (pair_ptr[p + 1] < pair_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "pair_ptr not monotone");
+        if (pair_ptr[p + 1] - pair_ptr[p] > (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "essential_ransac: a pair has 2^31 or more matches");
+        if (pair_left[p] < 0 || pair_left[p] >= n_images || pair_right[p] < 0 || pair_right[p] >= n_images)
+            return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
+    }
+    if (pair_ptr[n_pairs] > pair_ptr[0] && (!query_idx || !train_idx || !inlier || !pts)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    for (int p = 0; p < n_pairs; ++p) {
+        const int64_t nl = img_ptr[pair_left[p] + 1] - img_ptr[pair_left[p]], nr = img_ptr[pair_right[p] + 1] - img_ptr[pair_right[p]];
+        for (int64_t e = pair_ptr[p]; e < pair_ptr[p + 1]; ++e)
+            if (query_idx[e] < 0 || query_idx[e] >= nl || train_idx[e] < 0 || train_idx[e] >= nr)
+                return fail(SFMBA_ERR_INVALID_ARG, "essential_ransac: a query_idx / train_idx lies outside its image");
+    }
+    if (n_pairs == 0) return check_device(device);
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    // SFMBA_ESSENTIAL_TIMING: one stderr line per call with the HIP-event times of its phases (tools/essential_bench.py)
+    double tm[5];
+    const bool timing = std::getenv("SFMBA_ESSENTIAL_TIMING") != nullptr;
+    rc = essential_ransac(ck.kit.stream, device, n_images, img_ptr, pts, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx, K, n_hyp,
+                          threshold_px, seed, E, pose, inlier, result, hyp_E, hyp_count, hyp_nsol, timing ? tm : nullptr);
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba essential] upload_ms %.6f hypotheses_ms %.6f score_ms %.6f select_ms %.6f download_ms %.6f\n", tm[0], tm[1], tm[2],
+                     tm[3], tm[4]);
+    if (rc == ESS_ERR_TOO_LARGE) return fail(SFMBA_ERR_INVALID_ARG, "essential_ransac: too many pairs x hypotheses for one call");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "essential_ransac: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("essential_ransac: ") + hipGetErrorString((hipError_t)rc));
     return SFMBA_OK;
 }
 }  // extern "C"

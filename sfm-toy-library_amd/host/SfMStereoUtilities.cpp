@@ -15,6 +15,12 @@
 // (GetAlignedPointsFromMatch, SfMCommon.cpp:63-87), calls cv::findHomography(RANSAC, RANSAC_THRESHOLD = 10) and counts the mask.
 // Here the key points of the images and the match lists go to sfmba_homography_ransac as they are -- the alignment happens on the
 // device -- with threshold 10, seed 0 and 2000 hypotheses (OpenCV's default maxIters: where its loop stops at the latest).
+//
+// findCameraMatricesFromMatch (SfMToyLib/SfMStereoUtilities.cpp:74-118): the reference aligns the matched key points, calls
+// cv::findEssentialMat(RANSAC, 0.999, 1.0) and cv::recoverPose, sets Pleft = I and Pright = [R|t] and keeps the matches of the final
+// mask.  Here the key points and the match lists go to sfmba_essential_ransac as they are, with threshold 1, seed 0 and 1000
+// hypotheses (cv::findEssentialMat's maxIters: where its loop stops at the latest); fx and fy are both read from K (the reference
+// assumes fx = fy).
 #include "SfMStereoUtilities.h"
 
 #include <iostream>
@@ -74,6 +80,87 @@ int SfMStereoUtilities::findHomographyInliers(
     std::vector<int> inliers;
     findHomographyInliersBatch({ &left, &right }, { 0 }, { 1 }, { &matches }, inliers);
     return inliers[0];
+}
+
+bool SfMStereoUtilities::findCameraMatricesFromMatchBatch(
+        const Intrinsics&                   intrinsics,
+        const std::vector<const Features*>& images,
+        const std::vector<int>&             left,
+        const std::vector<int>&             right,
+        const std::vector<const Matching*>& matches,
+        std::vector<unsigned char>&         ok,
+        std::vector<Matching>&              prunedMatches,
+        std::vector<cv::Matx34f>&           Pleft,
+        std::vector<cv::Matx34f>&           Pright) {
+    const int    ESSENTIAL_HYPOTHESES = 1000;       // cv::findEssentialMat's maxIters (all are evaluated)
+    const float  ESSENTIAL_THRESHOLD  = 1.0f;       // SfMStereoUtilities.cpp:97
+    const size_t n_pairs = left.size();
+    ok.assign(n_pairs, 0);
+    prunedMatches.assign(n_pairs, Matching());
+    Pleft.assign(n_pairs, cv::Matx34f::eye());
+    Pright.assign(n_pairs, cv::Matx34f::eye());
+    if (intrinsics.K.empty()) {
+        std::cerr << "Intrinsics matrix (K) must be initialized." << std::endl;
+        return false;
+    }
+    if (n_pairs == 0) return true;
+    float K[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) K[3 * r + c] = intrinsics.K.at<float>(r, c);
+    std::vector<int64_t> img_ptr(images.size() + 1, 0);
+    for (size_t i = 0; i < images.size(); i++) img_ptr[i + 1] = img_ptr[i] + (int64_t)images[i]->keyPoints.size();
+    std::vector<float> pts(2 * (size_t)img_ptr.back() + 2);
+    for (size_t i = 0; i < images.size(); i++)
+        for (size_t k = 0; k < images[i]->keyPoints.size(); k++) {
+            pts[2 * ((size_t)img_ptr[i] + k)]     = images[i]->keyPoints[k].pt.x;
+            pts[2 * ((size_t)img_ptr[i] + k) + 1] = images[i]->keyPoints[k].pt.y;
+        }
+    std::vector<int64_t> pair_ptr(n_pairs + 1, 0);
+    for (size_t p = 0; p < n_pairs; p++) pair_ptr[p + 1] = pair_ptr[p] + (int64_t)matches[p]->size();
+    std::vector<int32_t> pl(left.begin(), left.end()), pr(right.begin(), right.end());
+    std::vector<int32_t> query((size_t)pair_ptr.back() + 1), train((size_t)pair_ptr.back() + 1);
+    for (size_t p = 0; p < n_pairs; p++)
+        for (size_t e = 0; e < matches[p]->size(); e++) {
+            query[(size_t)pair_ptr[p] + e] = (*matches[p])[e].queryIdx;
+            train[(size_t)pair_ptr[p] + e] = (*matches[p])[e].trainIdx;
+        }
+    std::vector<double> E(9 * n_pairs), pose(12 * n_pairs);
+    std::vector<unsigned char> mask((size_t)pair_ptr.back() + 1);
+    std::vector<sfmba_essential_result> res(n_pairs);
+    const int rc = sfmba_essential_ransac(0, (int)images.size(), img_ptr.data(), pts.data(), (int)n_pairs, pl.data(), pr.data(), pair_ptr.data(),
+                                          query.data(), train.data(), K, ESSENTIAL_HYPOTHESES, ESSENTIAL_THRESHOLD, 0, E.data(), pose.data(),
+                                          mask.data(), res.data(), nullptr, nullptr, nullptr);
+    if (rc != SFMBA_OK) {
+        std::cerr << "findCameraMatricesFromMatch failed. (sfmba rc=" << rc << ": " << sfmba_last_error() << ")" << std::endl;
+        return false;
+    }
+    for (size_t p = 0; p < n_pairs; p++) {
+        if (res[p].status != 0) continue;
+        ok[p] = 1;
+        for (int e = 0; e < 12; e++) Pright[p].val[e] = (float)pose[12 * p + e];
+        for (size_t e = 0; e < matches[p]->size(); e++)
+            if (mask[(size_t)pair_ptr[p] + e]) prunedMatches[p].push_back((*matches[p])[e]);
+    }
+    return true;
+}
+
+bool SfMStereoUtilities::findCameraMatricesFromMatch(
+        const Intrinsics& intrinsics,
+        const Matching&   matches,
+        const Features&   featuresLeft,
+        const Features&   featuresRight,
+        Matching&         prunedMatches,
+        cv::Matx34f&      Pleft,
+        cv::Matx34f&      Pright) {
+    std::vector<unsigned char> ok;
+    std::vector<Matching> pruned;
+    std::vector<cv::Matx34f> Pl, Pr;
+    if (!findCameraMatricesFromMatchBatch(intrinsics, { &featuresLeft, &featuresRight }, { 0 }, { 1 }, { &matches }, ok, pruned, Pl, Pr) || !ok[0])
+        return false;
+    Pleft = Pl[0];
+    Pright = Pr[0];
+    prunedMatches = pruned[0];
+    return true;
 }
 
 bool SfMStereoUtilities::triangulateViews(

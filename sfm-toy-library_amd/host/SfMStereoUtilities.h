@@ -1,7 +1,7 @@
-// SfMStereoUtilities.h -- the homography-inlier count, the triangulation and the 2D-3D pose entry points of the reference with
-// their own signatures (SfMToyLib/SfMStereoUtilities.h:53-105), backed by the MI355X kernels (include/sfmba.h:
-// sfmba_homography_ransac, sfmba_triangulate, sfmba_pnp_ransac).  The one member of the reference class that stays on the
-// reference's OpenCV path is findCameraMatricesFromMatch (essential matrix + recoverPose of the ONE chosen baseline pair).
+// SfMStereoUtilities.h -- the homography-inlier count, the relative pose of a pair, the triangulation and the 2D-3D pose entry
+// points of the reference with their own signatures (SfMToyLib/SfMStereoUtilities.h:53-105), backed by the MI355X kernels
+// (include/sfmba.h: sfmba_homography_ransac, sfmba_essential_ransac, sfmba_triangulate, sfmba_pnp_ransac).  Every member of the
+// reference class has its counterpart here.
 #pragma once
 #include <vector>
 
@@ -35,6 +35,43 @@ public:
             const std::vector<int>&             right,
             const std::vector<const Matching*>& matches,
             std::vector<int>&                   inliers);
+
+    /**
+     * Find the camera matrices of a pair from its matches: Pleft = I, Pright = [R|t] with |t| = 1, prunedMatches = the matches
+     * that agree with the essential matrix AND lie in front of both cameras, in their order (five-point RANSAC + recoverPose on
+     * the GPU, threshold 1 px).  The reference runs cv::findEssentialMat on OpenCV's global RNG with a confidence-based early stop;
+     * this runs the project's own deterministic contract (include/sfmba.h, sfmba_essential_ransac) with all 1000 hypotheses --
+     * cv::findEssentialMat's maxIters, where its loop stops at the latest -- and seed 0: the same call always gives the same pose.
+     * @return true on success; false (prunedMatches, Pleft and Pright untouched) when K is empty, the pair is degenerate (fewer
+     *         than 6 matches, no valid hypothesis, no point in front), or there is no HIP device / a device error.
+     */
+    static bool findCameraMatricesFromMatch(
+            const Intrinsics& intrinsics,
+            const Matching&   featureMatching,
+            const Features&   featuresLeft,
+            const Features&   featuresRight,
+            Matching&         prunedMatches,
+            cv::Matx34f&      Pleft,
+            cv::Matx34f&      Pright);
+
+    /**
+     * The same for a list of pairs in ONE device call -- the pairs (good view, new view) of one added view (SfM.cpp:413-431):
+     * pair p = images[left[p]] -> images[right[p]] with matches[p]; ok[p], prunedMatches[p], Pleft[p], Pright[p] receive what
+     * findCameraMatricesFromMatch returns for it (Pleft / Pright / prunedMatches of a pair with ok[p] == 0 are [I|0] / [I|0] /
+     * empty).  Pair p draws the sample stream of seed 0 + p (include/sfmba.h), so only pair 0 of a batch gets exactly what
+     * findCameraMatricesFromMatch gives it.
+     * @return false (every ok 0; a line is written to stderr) when K is empty, there is no HIP device or on a device error.
+     */
+    static bool findCameraMatricesFromMatchBatch(
+            const Intrinsics&                   intrinsics,
+            const std::vector<const Features*>& images,
+            const std::vector<int>&             left,
+            const std::vector<int>&             right,
+            const std::vector<const Matching*>& matches,
+            std::vector<unsigned char>&         ok,
+            std::vector<Matching>&              prunedMatches,
+            std::vector<cv::Matx34f>&           Pleft,
+            std::vector<cv::Matx34f>&           Pright);
 
     /**
      * Triangulate (recover 3D locations) from point matching.

@@ -21,6 +21,7 @@ template <typename T, int M, int N>
 struct Matx {
     T val[M * N];
     Matx() { for (int i = 0; i < M * N; ++i) val[i] = T(0); }
+    static Matx eye() { Matx m; for (int i = 0; i < (M < N ? M : N); ++i) m(i, i) = T(1); return m; }
     T& operator()(int r, int c) { return val[r * N + c]; }
     const T& operator()(int r, int c) const { return val[r * N + c]; }
     template <int M1, int N1>

@@ -116,6 +116,72 @@ int sfmba_shim_find_homography_inliers(const int64_t* img_ptr /*[3]*/, const flo
 }
 
 namespace {
+sfmtoylib::Intrinsics buildIntrinsics(const float* K) {
+    sfmtoylib::Intrinsics intr;
+    if (K) {
+        intr.K = cv::Mat(3, 3);
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) intr.K.at<float>(r, c) = K[3 * r + c];
+    }
+    return intr;
+}
+}  // namespace
+
+// Flat-array driver of sfmtoylib::SfMStereoUtilities::findCameraMatricesFromMatch (tests/test_gpu_essential_ransac.py): img_ptr [3] /
+// xy hold the key points of the left (image 0) and the right image; K == NULL leaves the intrinsics empty.  P_left / P_right [12] and
+// pruned [n_match][2] (query, train) go in and come back (untouched when the call reports failure); *n_pruned likewise.  Returns
+// 1 / 0 = the call's true / false.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_find_camera_matrices(const float* K /*[9] or NULL*/, const int64_t* img_ptr /*[3]*/, const float* xy, int n_match,
+                                    const int32_t* query_idx, const int32_t* train_idx, float* P_left, float* P_right, int32_t* pruned,
+                                    int* n_pruned) {
+    using namespace sfmtoylib;
+    const std::vector<Features> feats = buildKeyPoints(2, img_ptr, xy);
+    Matching matches, kept;
+    for (int i = 0; i < n_match; ++i) matches.push_back(cv::DMatch(query_idx[i], train_idx[i], 0.0f));
+    for (int i = 0; i < *n_pruned; ++i) kept.push_back(cv::DMatch(pruned[2 * i], pruned[2 * i + 1], 0.0f));
+    cv::Matx34f Pl, Pr;
+    for (int e = 0; e < 12; ++e) { Pl.val[e] = P_left[e]; Pr.val[e] = P_right[e]; }
+    const bool ok = SfMStereoUtilities::findCameraMatricesFromMatch(buildIntrinsics(K), matches, feats[0], feats[1], kept, Pl, Pr);
+    for (int e = 0; e < 12; ++e) { P_left[e] = Pl.val[e]; P_right[e] = Pr.val[e]; }
+    *n_pruned = (int)kept.size();
+    for (size_t i = 0; i < kept.size(); ++i) { pruned[2 * i] = kept[i].queryIdx; pruned[2 * i + 1] = kept[i].trainIdx; }
+    return ok ? 1 : 0;
+}
+
+// Flat-array driver of sfmtoylib::SfMStereoUtilities::findCameraMatricesFromMatchBatch: ok [n_pairs], P_left / P_right [n_pairs][12],
+// pruned_ptr [n_pairs + 1] and pruned [pair_ptr[n_pairs]][2] (query, train) come back.  Returns 1 / 0 = the call's true / false.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_find_camera_matrices_batch(const float* K /*[9] or NULL*/, int n_images, const int64_t* img_ptr, const float* xy, int n_pairs,
+                                          const int32_t* left, const int32_t* right, const int64_t* pair_ptr, const int32_t* query,
+                                          const int32_t* train, unsigned char* ok, float* P_left, float* P_right, int64_t* pruned_ptr,
+                                          int32_t* pruned) {
+    using namespace sfmtoylib;
+    const std::vector<Features> feats = buildKeyPoints(n_images, img_ptr, xy);
+    std::vector<const Features*> images;
+    for (const Features& f : feats) images.push_back(&f);
+    std::vector<Matching> lists((size_t)n_pairs);
+    std::vector<const Matching*> matches;
+    for (int p = 0; p < n_pairs; ++p) {
+        for (int64_t e = pair_ptr[p]; e < pair_ptr[p + 1]; ++e) lists[p].push_back(cv::DMatch(query[e], train[e], 0.0f));
+        matches.push_back(&lists[p]);
+    }
+    std::vector<unsigned char> good;
+    std::vector<Matching> kept;
+    std::vector<cv::Matx34f> Pl, Pr;
+    const bool all = SfMStereoUtilities::findCameraMatricesFromMatchBatch(buildIntrinsics(K), images, std::vector<int>(left, left + n_pairs),
+                                                                          std::vector<int>(right, right + n_pairs), matches, good, kept, Pl, Pr);
+    int64_t n = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        ok[p] = good[p];
+        for (int e = 0; e < 12; ++e) { P_left[12 * p + e] = Pl[p].val[e]; P_right[12 * p + e] = Pr[p].val[e]; }
+        pruned_ptr[p] = n;
+        for (const cv::DMatch& d : kept[p]) { pruned[2 * n] = d.queryIdx; pruned[2 * n + 1] = d.trainIdx; ++n; }
+    }
+    pruned_ptr[n_pairs] = n;
+    return all ? 1 : 0;
+}
+
+namespace {
 using namespace sfmtoylib;
 PointCloud buildCloud(int n, const float* xyz, const int64_t* view_ptr, const int32_t* view_idx, const int32_t* feat_idx) {
     PointCloud cloud((size_t)n);

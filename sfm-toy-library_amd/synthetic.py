@@ -312,3 +312,34 @@ def make_homography_scene(n, outlier_frac, seed, size=(1024, 768)):
     right[bad, 0] = rng.uniform(0, w, k)
     right[bad, 1] = rng.uniform(0, h, k)
     return dict(left=left, right=right, H=H, bad=bad)
+
+
+def make_essential_scene(n, outlier_frac, seed, noise=0.2, planar=False, size=(1024, 768)):
+    """One image pair for sfmba_essential_ransac: a dict with left [n,2] float32, right [n,2] float32 (pixels), K [3,3], the
+    planted relative pose R [3,3] / t [3] (|t| = 1; x' ~ R X + t for X in the left camera's frame) and bad [n] bool (the rows of
+    right that were replaced by uniform clutter).
+
+    Camera: fx = fy = 2500, c = (512, 384) on the 1024 x 768 image (another size scales all three by size[0] / 1024 and puts c at
+    the image centre).  Points are uniform in [-1, 1] x [-0.7, 0.7] x [-1, 1] around depth 5 in the left camera's frame; planar=True
+    puts them on the plane Z = 5 + 0.1 X.  The second camera: R = exp of a rotation vector N(0, 0.1), t = (1, 0.1, 0.05)
+    normalised.  Both images carry `noise` px of Gaussian noise per axis and are rounded through float32, as cv::Point2f holds
+    them.  Draw order: rotation vector, points, left noise, right noise, bad, clutter u, clutter v."""
+    rng = np.random.default_rng(seed)
+    w, h = float(size[0]), float(size[1])
+    f = 2500.0 * w / 1024.0
+    K = np.array([[f, 0.0, 0.5 * w], [0.0, f, 0.5 * h], [0.0, 0.0, 1.0]])
+    R = rotvec_to_matrix(rng.normal(0, 0.1, 3))
+    t = np.array([1.0, 0.1, 0.05])
+    t /= np.linalg.norm(t)
+    X = rng.uniform(-1, 1, (n, 3)) * np.array([1.0, 0.7, 1.0])
+    X[:, 2] = 5.0 + 0.1 * X[:, 0] if planar else X[:, 2] + 5.0
+    Y = X @ R.T + t
+    left = X[:, :2] / X[:, 2:3] * f + K[:2, 2] + rng.normal(0, noise, (n, 2))
+    right = Y[:, :2] / Y[:, 2:3] * f + K[:2, 2] + rng.normal(0, noise, (n, 2))
+    left = left.astype(np.float32)
+    right = right.astype(np.float32)
+    bad = rng.random(n) < outlier_frac
+    k = int(bad.sum())
+    right[bad, 0] = rng.uniform(0, w, k)
+    right[bad, 1] = rng.uniform(0, h, k)
+    return dict(left=left, right=right, K=K, R=R, t=t, bad=bad)
