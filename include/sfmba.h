@@ -715,6 +715,76 @@ SFMBA_API int sfmba_essential_ransac(int device, int n_images, const int64_t* im
                 sfmba_essential_result* result, double* hyp_E /*[n_pairs][n_hyp][9] or NULL*/,
                 int32_t* hyp_count /*[n_pairs][n_hyp] or NULL*/, int32_t* hyp_nsol /*[n_pairs][n_hyp] or NULL*/);
 
+/*
+ * Extract the features of a batch of images (SfM::extractFeatures, SfMToyLib/SfM.cpp:141-154: SfM2DFeatureUtilities::extractFeatures,
+ * SfM2DFeatureUtilities.cpp:46-51, i.e. ORB::create(5000)->detectAndCompute per image) in one call: an ORB-style detector and a
+ * steered-BRIEF descriptor of 32 bytes.  OpenCV's learned 256-pair table is not reproduced; THIS CONTRACT IS OUR OWN, deterministic
+ * one -- it is not, and does not claim to be, cv::ORB.  It is integer arithmetic end to end (the three places that use double say
+ * so), so the device is held BIT FOR BIT to a CPU restatement of itself (tests/orb_oracle.py).  Departures from cv::ORB: our own
+ * pattern (steered BRIEF, not the learned rBRIEF table); 30 orientation bins; Harris ranks ALL non-maximum-suppressed FAST corners
+ * (no pre-cut by FAST score); fixed-point resampling and smoothing; no mask.
+ *
+ *   images        image i owns bytes img_ptr[i] .. img_ptr[i+1]-1 of pixels: height[i] rows of width[i] * channels bytes, rows tight.
+ *   gray          channels == 3 (B, G, R): g = (1868 B + 9617 G + 4899 R + 8192) >> 14.  channels == 1: the byte as it is.
+ *   pyramid       in double: s_0 = 1, s_l = s_{l-1} * (double)scale_factor.  Level l is w_l = floor(w / s_l + 0.5) wide, h_l likewise,
+ *                 and is resampled from level l - 1 (not from level 0).  Per axis, for destination index d, source length n and
+ *                 destination length m: num = (2 d + 1) n - m, den = 2 m, i0 = num / den, f = ((num - i0 den) 2048 + den / 2) / den,
+ *                 i1 = min(i0 + 1, n - 1).  The value is ((I00 (2048 - fx) + I01 fx) (2048 - fy) + (I10 (2048 - fx) + I11 fx) fy + 2^21)
+ *                 >> 22.  A level with w_l <= 62 or h_l <= 62 has no key points; a level of size 0 ends the pyramid.
+ *   FAST score    the 16-pixel circle of radius 3, clockwise from (0,-3): (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3)
+ *                 (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3).  d_k = c_k - p (circle pixel k, centre p);
+ *                 S = max over the 16 starts s of max(min_{k<9} d_{s+k}, min_{k<9} -d_{s+k}), indices mod 16; S <= fast_threshold
+ *                 counts as 0.  S is defined for pixels at least 3 from every edge.
+ *   candidates    a pixel is a candidate iff S > 0, S is strictly greater than S at each of its 8 neighbours, and it lies at least
+ *                 31 from every edge of its level.  Equal neighbours drop each other, as OpenCV's non-maximum suppression does.
+ *   response      exact int64.  3 x 3 Sobel: Ix = (I[y-1][x+1] + 2 I[y][x+1] + I[y+1][x+1]) - (I[y-1][x-1] + 2 I[y][x-1] + I[y+1][x-1]),
+ *                 Iy likewise with rows and columns exchanged; a = sum Ix^2, b = sum Iy^2, c = sum Ix Iy over the 7 x 7 block centred
+ *                 on the candidate; R = 25 (a b - c^2) - (a + b)^2 (Harris with k = 0.04, scaled by 25).  a, b <= 5.1e7, so 25 a b
+ *                 stays below 2^63.
+ *   quota         in double: f = 1 / (double)scale_factor, f^n_levels by repeated multiplication, want_0 = n_features (1 - f) /
+ *                 (1 - f^n_levels); q_l = rint(want_l) (round-half-even), want_{l+1} = want_l f; the last level gets
+ *                 max(n_features - sum, 0).  (5000, 1.2, 8) gives 1086 905 754 628 524 436 364 303.  A level with fewer candidates
+ *                 than its quota keeps them all; nothing is redistributed.
+ *   selection     a level keeps its first q_l candidates in the total order (R descending, then y ascending, then x ascending); that
+ *                 is also the output order within a level; levels are ascending within an image.
+ *   orientation   m10 = sum u I(x+u, y+v), m01 = sum v I(x+u, y+v) over the unblurred level and the disc u^2 + v^2 <= 225.  The bin
+ *                 is the lowest k in 0..29 that maximises m10 C_k + m01 S_k in int64, with C_k = floor(16384 cos(2 pi k / 30) + 0.5):
+ *                   16384 16026 14968 13255 10963 8192 5063 1713 -1713 -5063 -8192 -10963 -13255 -14968 -16026
+ *                   -16384 -16026 -14968 -13255 -10963 -8192 -5063 -1713 1713 5063 8192 10963 13255 14968 16026
+ *                 and S_k = floor(16384 sin(2 pi k / 30) + 0.5):
+ *                   0 3406 6664 9630 12176 14189 15582 16294 16294 15582 14189 12176 9630 6664 3406
+ *                   0 -3406 -6664 -9630 -12176 -14189 -15582 -16294 -16294 -15582 -14189 -12176 -9630 -6664 -3406
+ *                 (the 12-degree discretisation of the ORB paper; no atan2, so nothing can differ in the last bit).
+ *   smoothing     the separable 7-tap filter [18 34 49 54 49 34 18] (sum 256): horizontal pass, vertical pass, then (v + 32768) >> 16.
+ *                 Defined for pixels at least 3 from every edge; nothing nearer an edge is ever read (the pattern reaches 13, and
+ *                 13 + 3 < 31).
+ *   pattern       mix = splitmix64's output function (sfmba_pnp_ransac).  A coordinate is mix(k) % 13 + mix(k+1) % 13 - 12 with k
+ *                 advancing by 2 from 0; a pair takes four coordinates x0 y0 x1 y1 and is skipped if either point has x^2 + y^2 > 169
+ *                 or the two points coincide; the first 256 accepted pairs form the pattern.  Rotation into bin k:
+ *                 x' = (C_k x - S_k y + 8192) >> 14, y' = (S_k x + C_k y + 8192) >> 14 (arithmetic shift); every rotated point has
+ *                 |x'|, |y'| <= 13.
+ *   descriptor    bit i = 1 iff B(x + x0', y + y0') < B(x + x1', y + y1') with B the smoothed level; bit i is bit i % 8 of byte i / 8.
+ *   key point     x = (float)(x_l * s_l) and y likewise (one double multiply each), size = (float)(31 s_l), angle = 12 bin degrees,
+ *                 response = (float)R, octave = l.
+ *
+ * Outputs: kp_ptr [n_images + 1], kp [cap], desc [cap][32]; desc and kp_ptr go into sfmba_match_features as they come (as desc /
+ * img_ptr with desc_bytes = 32).  Optional (NULL or not): dbg_level_xy [cap][2] = (x_l, y_l), dbg_bin [cap], dbg_harris [cap] = R,
+ * dbg_candidates [n_images][n_levels] = the number of candidates of every level.  Host pointers in and out, synchronous.
+ * *total receives the number of key points; SFMBA_ERR_CAPACITY (kp_ptr and *total valid, nothing else written) if cap < *total;
+ * cap >= n_images * n_features always suffices.  SFMBA_ERR_INVALID_ARG for channels other than 1 or 3, a dimension outside 1..16384,
+ * an img_ptr that does not agree with the sizes, n_features < 1, n_levels outside 1..12, a scale_factor that is not finite or lies
+ * outside (1, 2], a fast_threshold outside 1..254.  Deterministic: the result does not depend on how the work is cut up (images go to
+ * the device in consecutive groups under a fixed scratch bound); a batch equals the concatenation of single-image calls.
+ * SFMBA_ABI_VERSION stays 6: adding a symbol is backward compatible.
+ */
+typedef struct sfmba_orb_keypoint { float x, y, size, angle, response; int32_t octave; } sfmba_orb_keypoint;
+SFMBA_API int sfmba_orb_extract(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/,
+                int n_features, float scale_factor, int n_levels, int fast_threshold,
+                int64_t* kp_ptr /*[n_images+1]*/, sfmba_orb_keypoint* kp, unsigned char* desc /*[cap][32]*/, int64_t cap, int64_t* total,
+                int32_t* dbg_level_xy /*[cap][2] or NULL*/, int32_t* dbg_bin /*[cap] or NULL*/, int64_t* dbg_harris /*[cap] or NULL*/,
+                int32_t* dbg_candidates /*[n_images][n_levels] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

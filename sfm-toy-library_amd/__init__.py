@@ -13,12 +13,12 @@ or a GPU is missing, it never falls back to a CPU implementation.
 from .structs import (SfmbaOptions, SfmbaSummary, SfmbaIteration, TERMINATION_NAMES,
                       CONVERGENCE, NO_CONVERGENCE, FAILURE, LINEAR_CHOLESKY, LINEAR_PCG, LINEAR_AUTO,
                       PRECISION_F64, PRECISION_F32J, CREATE_DETERMINISTIC, CREATE_ROW_SHARDED, CREATE_NO_PAIR_LIST)
-from .synthetic import make_problem, make_descriptors, make_pnp_scene, make_homography_scene, make_essential_scene, BAProblem, CONFIGS
+from .synthetic import make_problem, make_descriptors, make_pnp_scene, make_homography_scene, make_essential_scene, make_orb_scene, render_orb_view, BAProblem, CONFIGS
 from .problem_io import save_problem, load_problem, save_bal, load_bal
 
 __all__ = [
     "SfmbaOptions", "SfmbaSummary", "SfmbaIteration", "TERMINATION_NAMES",
     "CONVERGENCE", "NO_CONVERGENCE", "FAILURE", "LINEAR_CHOLESKY", "LINEAR_PCG", "LINEAR_AUTO",
     "PRECISION_F64", "PRECISION_F32J", "CREATE_DETERMINISTIC", "CREATE_ROW_SHARDED", "CREATE_NO_PAIR_LIST",
-    "make_problem", "make_descriptors", "make_pnp_scene", "make_homography_scene", "make_essential_scene", "BAProblem", "CONFIGS", "save_problem", "load_problem", "save_bal", "load_bal",
+    "make_problem", "make_descriptors", "make_pnp_scene", "make_homography_scene", "make_essential_scene", "make_orb_scene", "render_orb_view", "BAProblem", "CONFIGS", "save_problem", "load_problem", "save_bal", "load_bal",
 ]

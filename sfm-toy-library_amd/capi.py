@@ -35,7 +35,7 @@ SYMBOLS = [
     "sfmba_problem_create_ex", "sfmba_comm_abort", "sfmba_comm_reduce_scatter", "sfmba_problem_set_reduce_scatter",
     "sfmba_comm_allgather", "sfmba_problem_set_allgather", "sfmba_comm_size", "sfmba_device_warmup",
     "sfmba_match_features", "sfmba_problem_set_step_probe", "sfmba_problem_get_step_probe", "sfmba_pnp_ransac",
-    "sfmba_homography_ransac", "sfmba_essential_ransac",
+    "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_orb_extract",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -181,6 +181,56 @@ def match_features(descs, pairs=None, ratio=float(np.float32(0.8)), cap=None, de
     _check(rc)
     n = total.value
     return pl, pr, ptr, q[:n].copy(), t[:n].copy(), d[:n].copy()
+
+
+ORB_KEYPOINT = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32), ("response", np.float32),
+                         ("octave", np.int32)])          # sfmba_orb_keypoint
+
+
+def orb_extract(images, n_features=5000, scale_factor=1.2, n_levels=8, fast_threshold=20, cap=None, debug=False, device=0):
+    """sfmba_orb_extract: ORB-style key points and 32-byte descriptors of every image of a batch (the contract is in include/sfmba.h).
+
+    images: list of uint8 arrays, h x w (gray) or h x w x 3 (BGR), all of one kind.  Returns one tuple per image: (kp, desc) with kp a
+    record array of ORB_KEYPOINT and desc uint8 [n, 32]; with debug=True (kp, desc, level_xy int32 [n, 2], bin int32 [n], harris
+    int64 [n], candidates int32 [n_levels]).  cap=None sizes the outputs for n_features per image; a smaller cap is retried once
+    with the size the library reports."""
+    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+    kinds = {(im.ndim, im.shape[2] if im.ndim == 3 else 1) for im in imgs}
+    if len(kinds) > 1 or any(k not in ((2, 1), (3, 3)) for k in kinds):
+        raise ValueError("images must all be h x w or all be h x w x 3 uint8 arrays")
+    channels = kinds.pop()[1] if kinds else 1
+    n = len(imgs)
+    img_ptr = np.zeros(n + 1, dtype=np.int64)
+    img_ptr[1:] = np.cumsum([im.size for im in imgs])
+    flat = np.ascontiguousarray(np.concatenate([im.reshape(-1) for im in imgs]) if imgs else np.zeros(0, np.uint8))
+    wd = np.asarray([im.shape[1] for im in imgs], dtype=np.int32)
+    ht = np.asarray([im.shape[0] for im in imgs], dtype=np.int32)
+    cap = int(n * max(n_features, 0) if cap is None else cap)
+    lp, bp = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte)
+    kp_ptr = np.zeros(n + 1, dtype=np.int64)
+    total = C.c_int64(0)
+    cand = np.zeros((max(n, 1), max(n_levels, 1)), np.int32)
+    for _ in range(2):
+        kp = np.zeros(max(cap, 1), ORB_KEYPOINT)
+        desc = np.zeros((max(cap, 1), 32), np.uint8)
+        lxy, bn, hr = np.zeros((max(cap, 1), 2), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int64)
+        rc = lib().sfmba_orb_extract(C.c_int(device), C.c_int(n), _p(img_ptr, lp), flat.ctypes.data_as(bp), _p(wd, _ip), _p(ht, _ip),
+                                     C.c_int(channels), C.c_int(n_features), C.c_float(scale_factor), C.c_int(n_levels),
+                                     C.c_int(fast_threshold), _p(kp_ptr, lp), kp.ctypes.data_as(C.c_void_p), desc.ctypes.data_as(bp),
+                                     C.c_int64(cap), C.byref(total), _p(lxy, _ip) if debug else None, _p(bn, _ip) if debug else None,
+                                     _p(hr, lp) if debug else None, _p(cand, _ip) if debug else None)
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        cap = int(total.value)
+    _check(rc)
+    out = []
+    for i in range(n):
+        a, b = int(kp_ptr[i]), int(kp_ptr[i + 1])
+        if debug:
+            out.append((kp[a:b].copy(), desc[a:b].copy(), lxy[a:b].copy(), bn[a:b].copy(), hr[a:b].copy(), cand[i].copy()))
+        else:
+            out.append((kp[a:b].copy(), desc[a:b].copy()))
+    return out
 
 
 class _PnpResult(C.Structure):

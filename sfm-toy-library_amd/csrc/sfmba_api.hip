@@ -8,6 +8,7 @@
 #include "pnp_ransac.h"
 #include "homography_ransac.h"
 #include "essential_ransac.h"
+#include "orb_extract.h"
 #include <climits>
 #include <cmath>
 
@@ -484,6 +485,44 @@ int sfmba_match_features(int device, int n_images, const int64_t* img_ptr, const
     if (rc == MATCH_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "match_features: output capacity too small");
     if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "match_features: device allocation failed");
     if (rc) return fail(SFMBA_ERR_HIP, std::string("match_features: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+// ---- feature extraction (SfM::extractFeatures) ------------------------------------------------------------------------
+int sfmba_orb_extract(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                      int channels, int n_features, float scale_factor, int n_levels, int fast_threshold, int64_t* kp_ptr, sfmba_orb_keypoint* kp,
+                      unsigned char* desc, int64_t cap, int64_t* total, int32_t* dbg_level_xy, int32_t* dbg_bin, int64_t* dbg_harris,
+                      int32_t* dbg_candidates) {
+    if (n_images < 0 || cap < 0 || !img_ptr || !kp_ptr || !total || (n_images > 0 && (!width || !height)) || (cap > 0 && (!kp || !desc)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: channels must be 1 or 3");
+    if (n_features < 1) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: n_features must be >= 1");
+    if (n_levels < 1 || n_levels > 12) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: n_levels must be in 1..12");
+    if (!std::isfinite(scale_factor) || !(scale_factor > 1.0f) || scale_factor > 2.0f)
+        return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: scale_factor must be finite and in (1, 2]");
+    if (fast_threshold < 1 || fast_threshold > 254) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: fast_threshold must be in 1..254");
+    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
+            return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: an image dimension lies outside 1..16384");
+        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
+            return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: img_ptr does not agree with width * height * channels");
+    }
+    if (n_images > 0 && !pixels) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    // SFMBA_ORB_TIMING: one stderr line per call with the HIP-event times of its phases (tools/orb_bench.py)
+    double tm[ORB_T_COUNT];
+    const bool timing = std::getenv("SFMBA_ORB_TIMING") != nullptr;
+    rc = orb_extract(ck.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, n_features, scale_factor, n_levels, fast_threshold,
+                     kp_ptr, kp, desc, cap, total, dbg_level_xy, dbg_bin, dbg_harris, dbg_candidates, timing ? tm : nullptr);
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba orb] upload_ms %.6f pyramid_ms %.6f score_ms %.6f candidates_ms %.6f response_ms %.6f select_ms %.6f smooth_ms %.6f "
+                     "describe_ms %.6f download_ms %.6f groups %d\n", tm[ORB_T_UPLOAD], tm[ORB_T_PYRAMID], tm[ORB_T_SCORE], tm[ORB_T_CANDIDATES],
+                     tm[ORB_T_HARRIS], tm[ORB_T_SELECT], tm[ORB_T_SMOOTH], tm[ORB_T_DESCRIBE], tm[ORB_T_DOWNLOAD], (int)tm[ORB_T_GROUPS]);
+    if (rc == ORB_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "orb_extract: output capacity too small");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "orb_extract: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("orb_extract: ") + hipGetErrorString((hipError_t)rc));
     return SFMBA_OK;
 }
 // ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------

@@ -1,5 +1,6 @@
-// SfM2DFeatureUtilities.cpp -- host side of the feature matcher: flattens the descriptor matrices, calls the C ABI
-// (include/sfmba.h, sfmba_match_features) and rebuilds the reference's Matching lists.  See SfM2DFeatureUtilities.h.
+// SfM2DFeatureUtilities.cpp -- host side of the feature extractor and matcher: flattens the images / descriptor matrices, calls
+// the C ABI (include/sfmba.h, sfmba_orb_extract, sfmba_match_features) and rebuilds the reference's Features and Matching lists.
+// See SfM2DFeatureUtilities.h.
 #include "SfM2DFeatureUtilities.h"
 
 #include <cstdint>
@@ -83,6 +84,68 @@ bool matchPairs(const std::vector<const Features*>& images, const std::vector<in
 }
 
 }  // namespace
+
+Features SfM2DFeatureUtilities::extractFeatures(const cv::Mat& image) {
+    std::vector<Features> out;
+    if (!SfMFeatureExtraction::extractFeatures(std::vector<cv::Mat>(1, image), out)) return Features();
+    return out[0];
+}
+
+bool SfMFeatureExtraction::extractFeatures(const std::vector<cv::Mat>& images, std::vector<Features>& imageFeatures) {
+    const int ORB_FEATURES = 5000;                                            // ORB::create(5000), SfM2DFeatureUtilities.cpp:40
+    const float ORB_SCALE = 1.2f;                                             // OpenCV's defaults for the rest
+    const int ORB_LEVELS = 8, ORB_FAST_THRESHOLD = 20;
+    const size_t n = images.size();
+    imageFeatures.assign(n, Features());
+    if (n == 0) return true;
+    std::vector<int64_t> ptr(n + 1, 0), kp_ptr(n + 1, 0);
+    std::vector<int32_t> width(n), height(n);
+    const int type = images[0].type();
+    if (type != CV_8U && type != CV_8UC3) { std::fprintf(stderr, "extractFeatures: images must be CV_8U or CV_8UC3\n"); return false; }
+    const int channels = type == CV_8UC3 ? 3 : 1;
+    for (size_t i = 0; i < n; ++i) {
+        if (images[i].empty() || images[i].type() != type) { std::fprintf(stderr, "extractFeatures: empty image or image types differ\n"); return false; }
+        width[i] = images[i].cols; height[i] = images[i].rows;
+        ptr[i + 1] = ptr[i] + (int64_t)images[i].cols * images[i].rows * channels;
+    }
+    std::vector<unsigned char> pixels((size_t)ptr[n]);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t row = (size_t)width[i] * (size_t)channels;
+        for (int r = 0; r < height[i]; ++r)                                   // row by row: an OpenCV matrix need not be continuous
+            std::memcpy(&pixels[(size_t)ptr[i] + (size_t)r * row], images[i].ptr<unsigned char>(r), row);
+    }
+    std::vector<sfmba_orb_keypoint> kp;
+    std::vector<unsigned char> desc;
+    int64_t cap = (int64_t)n * ORB_FEATURES, total = 0;
+    int rc = SFMBA_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        kp.resize((size_t)cap + 1); desc.resize(((size_t)cap + 1) * 32);
+        rc = sfmba_orb_extract(0, (int)n, ptr.data(), pixels.data(), width.data(), height.data(), channels, ORB_FEATURES, ORB_SCALE, ORB_LEVELS,
+                               ORB_FAST_THRESHOLD, kp_ptr.data(), kp.data(), desc.data(), cap, &total, nullptr, nullptr, nullptr, nullptr);
+        if (rc == SFMBA_ERR_CAPACITY && attempt == 0) { cap = total; continue; }
+        break;
+    }
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "extractFeatures failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return false;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        Features& f = imageFeatures[i];
+        const int rows = (int)(kp_ptr[i + 1] - kp_ptr[i]);
+        f.keyPoints.reserve((size_t)rows);
+        f.points.reserve((size_t)rows);
+        if (rows > 0) f.descriptors = cv::Mat(rows, 32, CV_8U);
+        for (int r = 0; r < rows; ++r) {
+            const sfmba_orb_keypoint& k = kp[(size_t)kp_ptr[i] + (size_t)r];
+            cv::KeyPoint c;
+            c.pt = cv::Point2f(k.x, k.y); c.size = k.size; c.angle = k.angle; c.response = k.response; c.octave = k.octave; c.class_id = -1;
+            f.keyPoints.push_back(c);
+            f.points.push_back(c.pt);                                         // KeyPointsToPoints, SfMCommon.h
+            std::memcpy(f.descriptors.ptr<unsigned char>(r), &desc[((size_t)kp_ptr[i] + (size_t)r) * 32], 32);
+        }
+    }
+    return true;
+}
 
 Matching SfM2DFeatureUtilities::matchFeatures(const Features& featuresLeft, const Features& featuresRight) {
     std::vector<Matching> out;

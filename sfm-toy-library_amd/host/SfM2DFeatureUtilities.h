@@ -1,7 +1,7 @@
-// SfM2DFeatureUtilities.h -- the matching entry point of the reference with its own signature
-// (SfMToyLib/SfM2DFeatureUtilities.h:44-46), backed by the MI355X matcher (include/sfmba.h: sfmba_match_features), and the
-// body of SfM::createFeatureMatchMatrix (SfMToyLib/SfM.cpp:157-212) as a free-standing function over the members it reads
-// and writes.  Only matchFeatures is provided: extractFeatures (ORB detection) stays on the reference's OpenCV path.
+// SfM2DFeatureUtilities.h -- the two entry points of the reference with their own signatures
+// (SfMToyLib/SfM2DFeatureUtilities.h:42-46), backed by the MI355X extractor and matcher (include/sfmba.h: sfmba_orb_extract,
+// sfmba_match_features), and the bodies of SfM::extractFeatures (SfMToyLib/SfM.cpp:141-154) and SfM::createFeatureMatchMatrix
+// (SfM.cpp:157-212) as free-standing functions over the members they read and write.
 // In the reference createFeatureMatchMatrix is a private member function; a maintainer replaces its body by one call
 // (INTEGRATION.md section 5):
 //
@@ -11,6 +11,17 @@
 //
 // Results are identical to the reference's: the same DMatch entries in the same order (queryIdx, trainIdx, imgIdx = 0,
 // distance), for descriptors of type CV_8U.
+//
+// SfM::extractFeatures is replaced the same way, its loop over the images becoming one device call:
+//
+//   void SfM::extractFeatures() {
+//       SfMFeatureExtraction::extractFeatures(mImages, mImageFeatures);
+//   }
+//
+// The features are NOT cv::ORB's: the extractor runs the project's own deterministic ORB-style contract (include/sfmba.h,
+// sfmba_orb_extract: its own steered-BRIEF pattern, 30 orientation bins, Harris ranking of all suppressed FAST corners,
+// fixed-point resampling and smoothing, no mask) with the reference's parameters: 5000 features, scale 1.2, 8 levels, FAST
+// threshold 20.
 //
 // The consumer of the whole matrix, SfM::sortViewsForBaseline (SfMToyLib/SfM.cpp:333-364), is restated the same way:
 //
@@ -28,6 +39,12 @@ namespace sfmtoylib {
 class SfM2DFeatureUtilities {
 public:
     /**
+     * Key points, their coordinates (KeyPointsToPoints) and a CV_8U n x 32 descriptor matrix of one CV_8U (gray) or CV_8UC3 (BGR)
+     * image (SfM2DFeatureUtilities.cpp:46-51).  On a device error the features are empty and a line is written to stderr.
+     */
+    Features extractFeatures(const cv::Mat& image);                          // a member function in the reference too (its detector is a member)
+
+    /**
      * Brute-force Hamming 2-NN of every left descriptor among the right ones, pruned by the ratio test
      * (NN_MATCH_RATIO = 0.8f, SfM2DFeatureUtilities.cpp:53-71).  Fewer than 2 right descriptors give no matches (the
      * reference's behaviour is undefined there).  On a device error the result is empty and a line is written to stderr.
@@ -35,6 +52,18 @@ public:
     static Matching matchFeatures(
             const Features& featuresLeft,
             const Features& featuresRight);
+};
+
+class SfMFeatureExtraction {
+public:
+    /**
+     * SfM::extractFeatures: imageFeatures[i] = extractFeatures(images[i]) for every image, in ONE device call instead of the
+     * reference's serial loop.  All images must be of one type (CV_8U or CV_8UC3).  Returns false on a device error
+     * (imageFeatures is then sized but every entry is empty; a line is written to stderr).
+     */
+    static bool extractFeatures(
+            const std::vector<cv::Mat>& images,
+            std::vector<Features>&      imageFeatures);
 };
 
 class SfMFeatureMatching {

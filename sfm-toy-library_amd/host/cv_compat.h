@@ -3,7 +3,7 @@
 // The reference's data model (SfMToyLib/SfMCommon.h:55-99) is built on cv::Matx34f, cv::Point3f,
 // cv::Point2f and a CV_32F 3x3 cv::Mat.  OpenCV is not installable in this environment, so this header
 // provides layout- and API-compatible stand-ins for exactly the members adjustBundle() touches
-// (BA.cpp:111-221), plus CV_8U descriptor matrices for matchFeatures().  Building with -DSFMBA_HAVE_OPENCV uses the real headers instead; the shim source
+// (BA.cpp:111-221), plus CV_8U descriptor matrices for matchFeatures() and CV_8U / CV_8UC3 images for extractFeatures().  Building with -DSFMBA_HAVE_OPENCV uses the real headers instead; the shim source
 // is identical in both cases.
 #pragma once
 #ifdef SFMBA_HAVE_OPENCV
@@ -13,7 +13,7 @@
 #include <cstring>
 #include <vector>
 
-enum { CV_8U = 0, CV_32F = 5 };     // OpenCV's depth codes (single channel); global, as OpenCV's macros are
+enum { CV_8U = 0, CV_32F = 5, CV_8UC3 = 16 };     // OpenCV's type codes (CV_8UC3: three interleaved bytes, BGR); global, as OpenCV's macros are
 
 namespace cv {
 
@@ -48,7 +48,8 @@ struct KeyPoint { Point2f pt; float size = 0, angle = -1, response = 0; int octa
 struct DMatch { int queryIdx = -1, trainIdx = -1, imgIdx = -1; float distance = 0; DMatch() {} DMatch(int q, int t, float d) : queryIdx(q), trainIdx(t), distance(d) {} };
 
 // Dense row-major matrix, continuous, zero-initialised: a CV_32F one is what Intrinsics::K needs (K.at<float>(r, c),
-// BA.cpp:138,151-153,188-189), a CV_8U one holds binary descriptors (Features::descriptors, one row per key point).
+// BA.cpp:138,151-153,188-189), a CV_8U one holds binary descriptors (Features::descriptors, one row per key point) or a gray
+// image, a CV_8UC3 one a BGR image (cols counts pixels, a row is 3 cols bytes).
 class Mat {
 public:
     Mat() : rows(0), cols(0), type_(CV_32F) {}
@@ -62,7 +63,7 @@ public:
     bool empty() const { return data_.empty(); }
     int rows, cols;
 private:
-    static size_t elem(int type) { return type == CV_8U ? 1 : 4; }
+    static size_t elem(int type) { return type == CV_8U ? 1 : type == CV_8UC3 ? 3 : 4; }
     unsigned char* bytes() { return reinterpret_cast<unsigned char*>(data_.data()); }
     const unsigned char* bytes() const { return reinterpret_cast<const unsigned char*>(data_.data()); }
     int type_;

@@ -360,3 +360,58 @@ int sfmba_shim_sort_views_for_baseline(int n_images, const int64_t* img_ptr, con
     }
     return n;
 }
+
+namespace {
+cv::Mat buildImage(int w, int h, int channels, const unsigned char* px) {
+    cv::Mat m(h, w, channels == 3 ? CV_8UC3 : CV_8U);
+    for (int r = 0; r < h; ++r) std::memcpy(m.ptr<unsigned char>(r), px + (size_t)r * w * channels, (size_t)w * channels);
+    return m;
+}
+// kp [cap][7] = pt.x pt.y size angle response octave class_id, points [cap][2], desc [cap][32]; -2 if the members disagree
+int64_t flattenFeatures(const sfmtoylib::Features& f, int64_t at, int64_t cap, float* kp, float* points, unsigned char* desc) {
+    const size_t n = f.keyPoints.size();
+    if (f.points.size() != n || (n > 0 && (f.descriptors.rows != (int)n || f.descriptors.cols != 32 || f.descriptors.type() != CV_8U))) return -2;
+    if (n == 0 && !f.descriptors.empty()) return -2;
+    for (size_t r = 0; r < n; ++r, ++at) {
+        if (at >= cap) continue;
+        const cv::KeyPoint& k = f.keyPoints[r];
+        float* o = kp + 7 * at;
+        o[0] = k.pt.x; o[1] = k.pt.y; o[2] = k.size; o[3] = k.angle; o[4] = k.response; o[5] = (float)k.octave; o[6] = (float)k.class_id;
+        points[2 * at] = f.points[r].x; points[2 * at + 1] = f.points[r].y;
+        std::memcpy(desc + 32 * at, f.descriptors.ptr<unsigned char>((int)r), 32);
+    }
+    return at;
+}
+}  // namespace
+
+// Flat-array driver of sfmtoylib::SfM2DFeatureUtilities::extractFeatures (tests/test_gpu_orb_extract.py): one w x h image of 1 (gray)
+// or 3 (BGR) channels, rows tight.  Returns the number of key points (rows beyond cap are not written), -2 if the members of the
+// Features disagree.
+extern "C" __attribute__((visibility("default")))
+int64_t sfmba_shim_extract_features(int w, int h, int channels, const unsigned char* px, int64_t cap, float* kp, float* points, unsigned char* desc) {
+    using namespace sfmtoylib;
+    SfM2DFeatureUtilities util;
+    return flattenFeatures(util.extractFeatures(buildImage(w, h, channels, px)), 0, cap, kp, points, desc);
+}
+
+// Flat-array driver of sfmtoylib::SfMFeatureExtraction::extractFeatures: image i owns bytes img_ptr[i] .. img_ptr[i+1]-1 of px;
+// kp_ptr [n_images + 1] receives the CSR of the flattened rows.  Returns the number of key points, -1 if the call reported failure,
+// -2 on an inconsistent result.
+extern "C" __attribute__((visibility("default")))
+int64_t sfmba_shim_extract_features_batch(int n_images, const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h,
+                                          int channels, int64_t* kp_ptr, int64_t cap, float* kp, float* points, unsigned char* desc) {
+    using namespace sfmtoylib;
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_images; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    std::vector<Features> feats;
+    if (!SfMFeatureExtraction::extractFeatures(images, feats)) return -1;
+    if (feats.size() != (size_t)n_images) return -2;
+    int64_t at = 0;
+    kp_ptr[0] = 0;
+    for (int i = 0; i < n_images; ++i) {
+        at = flattenFeatures(feats[(size_t)i], at, cap, kp, points, desc);
+        if (at < 0) return -2;
+        kp_ptr[i + 1] = at;
+    }
+    return at;
+}

@@ -343,3 +343,59 @@ def make_essential_scene(n, outlier_frac, seed, noise=0.2, planar=False, size=(1
     right[bad, 0] = rng.uniform(0, w, k)
     right[bad, 1] = rng.uniform(0, h, k)
     return dict(left=left, right=right, K=K, R=R, t=t, bad=bad)
+
+
+def make_orb_scene(seed, n=900):
+    """A planar scene for sfmba_orb_extract: n rotated soft-edged rectangles on gray 128.  A dict of arrays [n]: cx, cy (centres,
+    uniform in +-700 scene units), hx, hy (half sizes, uniform in 4..40), angle (uniform in 0..pi), amp (uniform in 20..90 with a
+    random sign).  Draw order: cx, cy, hx, hy, angle, amp magnitude, amp sign."""
+    rng = np.random.default_rng(seed)
+    cx, cy = rng.uniform(-700, 700, n), rng.uniform(-700, 700, n)
+    hx, hy = rng.uniform(4, 40, n), rng.uniform(4, 40, n)
+    angle = rng.uniform(0, np.pi, n)
+    amp = rng.uniform(20, 90, n) * np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    return dict(cx=cx, cy=cy, hx=hx, hy=hy, angle=angle, amp=amp)
+
+
+def orb_view_to_scene(xy, w, h, theta, scale, tx, ty):
+    """Scene point seen by pixel (x, y) of a w x h view: scale * Rot(theta) * (x - w/2, y - h/2) + (tx, ty).  xy [.., 2]."""
+    xy = np.asarray(xy, np.float64)
+    u, v = xy[..., 0] - 0.5 * w, xy[..., 1] - 0.5 * h
+    c, s = np.cos(theta), np.sin(theta)
+    return np.stack([scale * (c * u - s * v) + tx, scale * (s * u + c * v) + ty], axis=-1)
+
+
+def orb_scene_to_view(pq, w, h, theta, scale, tx, ty):
+    """The inverse of orb_view_to_scene: the pixel that sees scene point pq [.., 2]."""
+    pq = np.asarray(pq, np.float64)
+    a, b = (pq[..., 0] - tx) / scale, (pq[..., 1] - ty) / scale
+    c, s = np.cos(theta), np.sin(theta)
+    return np.stack([c * a + s * b + 0.5 * w, -s * a + c * b + 0.5 * h], axis=-1)
+
+
+def render_orb_view(scene, w, h, theta=0.0, scale=1.0, tx=0.0, ty=0.0):
+    """uint8 [h, w] rendering of make_orb_scene: every rectangle adds amp * min(1, max(0, inside depth / 1 unit)) to gray 128 (an
+    edge ramp one scene unit wide), the sum is rounded and clipped to 0..255.  numpy only."""
+    ys, xs = np.mgrid[0:h, 0:w]
+    P = orb_view_to_scene(np.stack([xs, ys], axis=-1), w, h, theta, scale, tx, ty)
+    px, py = P[..., 0], P[..., 1]
+    img = np.full((h, w), 128.0)
+    reach = scale * 0.5 * np.hypot(w, h) + 60.0
+    for i in range(len(scene["cx"])):
+        cx, cy = scene["cx"][i], scene["cy"][i]
+        if np.hypot(cx - tx, cy - ty) > reach:
+            continue
+        r = np.hypot(scene["hx"][i], scene["hy"][i])
+        # bounding box of the rectangle in the view: only those pixels are touched
+        corner = orb_scene_to_view(np.array([cx, cy]), w, h, theta, scale, tx, ty)
+        rr = r / scale + 2.0
+        x0, x1 = int(max(0, np.floor(corner[0] - rr))), int(min(w, np.ceil(corner[0] + rr) + 1))
+        y0, y1 = int(max(0, np.floor(corner[1] - rr))), int(min(h, np.ceil(corner[1] + rr) + 1))
+        if x0 >= x1 or y0 >= y1:
+            continue
+        c, s = np.cos(scene["angle"][i]), np.sin(scene["angle"][i])
+        dx, dy = px[y0:y1, x0:x1] - cx, py[y0:y1, x0:x1] - cy
+        a, b = c * dx + s * dy, -s * dx + c * dy
+        depth = np.minimum(scene["hx"][i] - np.abs(a), scene["hy"][i] - np.abs(b))
+        img[y0:y1, x0:x1] += scene["amp"][i] * np.clip(depth, 0.0, 1.0)
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
