@@ -485,6 +485,31 @@ SFMBA_API int sfmba_triangulate(int device, int64_t n, const float* left_xy, con
                                 float* points3d, unsigned char* keep, float* reproj_err);
 
 /*
+ * The same for the match lists of MANY pairs in one call -- the (good view, new view) pairs of one added view (SfM.cpp:413-444),
+ * as sfmba_match_features / sfmba_essential_ransac hand them over: nothing is aligned on the host.
+ *   img_ptr, pts, pair_left, pair_right, pair_ptr, query_idx, train_idx
+ *                 exactly the arrays of sfmba_homography_ransac below (same checks, same refusals, left == right allowed).  Entry e of
+ *                 pair p is the match pts[img_ptr[pair_left[p]] + query_idx[e]] -> pts[img_ptr[pair_right[p]] + train_idx[e]].
+ *                 total = pair_ptr[n_pairs]; entries in front of pair_ptr[0] belong to no pair and are written as not kept.
+ *   mask          [total] or NULL: the `inlier` array sfmba_essential_ransac returns.  An entry with mask == 0 gets keep = 0, a zero
+ *                 point and zero errors, and is not listed.
+ *   K [9], P_left / P_right [n_pairs][12], max_reproj_px (finite, >= 0)
+ *                 as sfmba_triangulate takes them, one camera pair per pair.
+ *   points3d [total][3], keep [total], reproj_err [total][2] or NULL
+ *                 for every pair, byte for byte what sfmba_triangulate writes for that pair's aligned points and cameras.
+ *   kept_ptr [n_pairs + 1], kept_idx [total]
+ *                 kept_idx[kept_ptr[p] .. kept_ptr[p+1]-1] = the positions in the flattened list of the kept entries of pair p,
+ *                 ascending; only the first kept_ptr[n_pairs] entries of kept_idx are defined.
+ * Host pointers, synchronous.  SFMBA_ERR_INVALID_ARG (nothing written) for what sfmba_homography_ransac refuses, for a non-finite or
+ * negative max_reproj_px and for 2^31 - 257 or more entries; n_pairs == 0 or no entry in any pair: SFMBA_OK, kept_ptr all zero.
+ */
+SFMBA_API int sfmba_triangulate_pairs(int device, int n_images, const int64_t* img_ptr, const float* pts /*[img_ptr[n_images]][2]*/,
+                                      const float* K, int n_pairs, const int32_t* pair_left, const int32_t* pair_right,
+                                      const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx,
+                                      const unsigned char* mask, const float* P_left, const float* P_right, float max_reproj_px,
+                                      float* points3d, unsigned char* keep, float* reproj_err, int64_t* kept_ptr, int64_t* kept_idx);
+
+/*
  * The two association loops of the incremental pipeline, results identical to the reference's loops
  * entry for entry and in the same order.
  *

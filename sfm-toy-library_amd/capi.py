@@ -35,7 +35,7 @@ SYMBOLS = [
     "sfmba_problem_create_ex", "sfmba_comm_abort", "sfmba_comm_reduce_scatter", "sfmba_problem_set_reduce_scatter",
     "sfmba_comm_allgather", "sfmba_problem_set_allgather", "sfmba_comm_size", "sfmba_device_warmup",
     "sfmba_match_features", "sfmba_problem_set_step_probe", "sfmba_problem_get_step_probe", "sfmba_pnp_ransac",
-    "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_orb_extract",
+    "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_orb_extract", "sfmba_triangulate_pairs",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -72,6 +72,54 @@ def triangulate(K, P_left, P_right, left_xy, right_xy, max_reproj_px=10.0, devic
                                    Pl.ctypes.data_as(fp), Pr.ctypes.data_as(fp), C.c_float(max_reproj_px), X.ctypes.data_as(fp),
                                    keep.ctypes.data_as(C.POINTER(C.c_ubyte)), err.ctypes.data_as(fp) if reproj_err else None))
     return X, keep.astype(bool), err
+
+
+def triangulate_pairs(pts_per_image, pairs, matches, K, P_left, P_right, mask=None, max_reproj_px=10.0, reproj_err=True, device=0):
+    """sfmba_triangulate_pairs: triangulateViews for the match lists of many pairs in one call (the contract is in include/sfmba.h).
+
+    pts_per_image, pairs, matches: as homography_ransac takes them.  K [3, 3]; P_left / P_right [n_pairs, 3, 4], one camera pair per
+    pair.  mask: None or [total] (the concatenated `inlier` arrays of essential_ransac); total = pair_ptr[-1].  Returns a dict:
+    points3d [total, 3] float32, keep [total] bool, err [total, 2] float32 (None with reproj_err=False), kept_ptr [n_pairs + 1]
+    int64, kept_idx [kept_ptr[-1]] int64, pair_ptr (as given)."""
+    ps = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 2) for x in pts_per_image]
+    if len(matches) == 6:
+        pl, pr, ptr, q, t = matches[:5]
+    else:
+        if pairs is None:
+            pairs = [(i, j) for i in range(len(ps)) for j in range(i + 1, len(ps))]
+        pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        pl, pr = pairs[:, 0], pairs[:, 1]
+        ptr, q, t = matches
+    pl, pr, q, t = _i(pl), _i(pr), _i(q), _i(t)
+    ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+    n_pairs = len(pl)
+    if len(pr) != n_pairs or len(ptr) != n_pairs + 1 or len(q) != len(t) or (n_pairs and len(q) < ptr[-1]):
+        raise ValueError("pair_left / pair_right / pair_ptr / query_idx / train_idx do not fit together")
+    total = int(ptr[-1])
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    Pl = np.ascontiguousarray(P_left, dtype=np.float32).reshape(-1)
+    Pr = np.ascontiguousarray(P_right, dtype=np.float32).reshape(-1)
+    if len(Pl) != 12 * n_pairs or len(Pr) != 12 * n_pairs:
+        raise ValueError("P_left / P_right must hold one 3 x 4 matrix per pair")
+    if mask is not None:
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+        if len(mask) < total:
+            raise ValueError("mask must hold one entry per match")
+    img_ptr = np.zeros(len(ps) + 1, dtype=np.int64)
+    img_ptr[1:] = np.cumsum([len(x) for x in ps])
+    pts = np.ascontiguousarray(np.concatenate(ps, axis=0) if ps else np.zeros((0, 2), np.float32))
+    X = np.zeros((max(total, 1), 3), dtype=np.float32)
+    keep = np.zeros(max(total, 1), dtype=np.uint8)
+    err = np.zeros((max(total, 1), 2), dtype=np.float32) if reproj_err else None
+    kept_ptr = np.zeros(n_pairs + 1, dtype=np.int64)
+    kept_idx = np.zeros(max(total, 1), dtype=np.int64)
+    lp, fp, bp = C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+    _check(lib().sfmba_triangulate_pairs(C.c_int(device), C.c_int(len(ps)), _p(img_ptr, lp), _p(pts, fp), _p(K, fp), C.c_int(n_pairs), _p(pl, _ip),
+                                         _p(pr, _ip), _p(ptr, lp), _p(q, _ip), _p(t, _ip), _p(mask, bp) if mask is not None else None,
+                                         _p(Pl, fp), _p(Pr, fp), C.c_float(max_reproj_px), _p(X, fp), _p(keep, bp),
+                                         _p(err, fp) if reproj_err else None, _p(kept_ptr, lp), _p(kept_idx, lp)))
+    return dict(points3d=X[:total], keep=keep[:total].astype(bool), err=err[:total] if reproj_err else None, kept_ptr=kept_ptr,
+                kept_idx=kept_idx[:int(kept_ptr[-1])].copy(), pair_ptr=ptr)
 
 
 SFMBA_ERR_CAPACITY = 5

@@ -298,5 +298,11 @@ void launch_dup_blocks(hipStream_t s, int ncam, const int* blk_ptr, const long l
 // ---- triangulate.hip: two-view DLT triangulation + reprojection filter (SfMStereoUtilities::triangulateViews), device pointers
 void launch_triangulate(hipStream_t s, long long n, const float* d_left, const float* d_right, const float K[9], const float Pl[12],
                         const float Pr[12], float max_err, float* d_points3d, unsigned char* d_keep, float* d_err);
+// sfmba_triangulate_pairs behind its argument checks: HOST pointers, n_pairs >= 1, pair_ptr[0] < pair_ptr[n_pairs] < 2^31 - 257;
+// synchronous on s, also when it fails.  0 or a hipError_t.
+int triangulate_pairs(hipStream_t s, int device, int n_images, const int64_t* img_ptr, const float* pts, const float* K, int n_pairs,
+                      const int32_t* pair_left, const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx,
+                      const unsigned char* mask, const float* P_left, const float* P_right, float max_err, float* points3d, unsigned char* keep,
+                      float* reproj_err, int64_t* kept_ptr, int64_t* kept_idx);
 
 }  // namespace sfmba

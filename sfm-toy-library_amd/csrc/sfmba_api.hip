@@ -412,6 +412,53 @@ int sfmba_triangulate(int device, int64_t n, const float* left_xy, const float* 
     return SFMBA_OK;
 }
 
+int sfmba_triangulate_pairs(int device, int n_images, const int64_t* img_ptr, const float* pts, const float* K, int n_pairs, const int32_t* pair_left,
+                            const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx,
+                            const unsigned char* mask, const float* P_left, const float* P_right, float max_reproj_px, float* points3d,
+                            unsigned char* keep, float* reproj_err, int64_t* kept_ptr, int64_t* kept_idx) {
+    // every check comes before the first write: a refused call leaves the outputs as they were
+    if (n_images < 0 || n_pairs < 0 || !img_ptr || !pair_ptr || !K || !kept_ptr || (n_pairs > 0 && (!pair_left || !pair_right || !P_left || !P_right)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (!std::isfinite(max_reproj_px) || max_reproj_px < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "max_reproj_px must be finite and >= 0");
+    if (img_ptr[0] < 0 || pair_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr and pair_ptr must not be negative");
+    for (int i = 0; i < n_images; ++i)
+        if (img_ptr[i + 1] < img_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
+    for (int p = 0; p < n_pairs; ++p) {
+        if (pair_ptr[p + 1] < pair_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "pair_ptr not monotone");
+        if (pair_ptr[p + 1] - pair_ptr[p] > (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "triangulate_pairs: a pair has 2^31 or more matches");
+        if (pair_left[p] < 0 || pair_left[p] >= n_images || pair_right[p] < 0 || pair_right[p] >= n_images)
+            return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
+    }
+    const int64_t total = pair_ptr[n_pairs];
+    if (total > 0 && (!points3d || !keep || !kept_idx)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (total > pair_ptr[0] && (!query_idx || !train_idx || !pts)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    for (int p = 0; p < n_pairs; ++p) {
+        const int64_t nl = img_ptr[pair_left[p] + 1] - img_ptr[pair_left[p]], nr = img_ptr[pair_right[p] + 1] - img_ptr[pair_right[p]];
+        for (int64_t e = pair_ptr[p]; e < pair_ptr[p + 1]; ++e)
+            if (query_idx[e] < 0 || query_idx[e] >= nl || train_idx[e] < 0 || train_idx[e] >= nr)
+                return fail(SFMBA_ERR_INVALID_ARG, "triangulate_pairs: a query_idx / train_idx lies outside its image");
+    }
+    if (total >= (int64_t)INT_MAX - 256) return fail(SFMBA_ERR_INVALID_ARG, "triangulate_pairs: too many entries for one call (2^31)");
+    if (total == pair_ptr[0]) {                                       // no entry belongs to a pair: nothing runs on the device
+        if (const int rc = check_device(device)) return rc;
+        for (int64_t e = 0; e < total; ++e) {
+            points3d[3 * e] = points3d[3 * e + 1] = points3d[3 * e + 2] = 0.0f;
+            keep[e] = 0;
+            if (reproj_err) reproj_err[2 * e] = reproj_err[2 * e + 1] = 0.0f;
+        }
+        for (int p = 0; p <= n_pairs; ++p) kept_ptr[p] = 0;
+        return SFMBA_OK;
+    }
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    rc = triangulate_pairs(ck.kit.stream, device, n_images, img_ptr, pts, K, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx, mask,
+                           P_left, P_right, max_reproj_px, points3d, keep, reproj_err, kept_ptr, kept_idx);
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "triangulate_pairs: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("triangulate_pairs: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+
 // ---- association joins -----------------------------------------------------------------------
 static int assoc_result(int rc, const char* what) {
     if (rc == 0) return SFMBA_OK;

@@ -1,18 +1,23 @@
 // triangulate.hip -- two-view DLT triangulation + reprojection filter (gfx950), SURVEY 8(f) row 2.
 //
-// Device counterpart of SfMStereoUtilities::triangulateViews for ALIGNED matches
-// (SfMToyLib/SfMStereoUtilities.cpp:120-206): per match
-//   :145-149  undistortPoints with no distortion         x_n = (u - cx)/fx, y_n = (v - cy)/fy            (-> float)
-//                                                        (NaN, NaN) for a pixel that is not finite, see normalise_px
-//   :151-152  cv::triangulatePoints [OpenCV-upstream]    A = [x P3 - P1; y P3 - P2] of both views, 4x4, fp64;
-//                                                        X_h = right singular vector of the smallest singular value (-> float)
-//   :154-155  convertPointsFromHomogeneous               X = X_h.xyz / X_h.w                               (float)
-//   :157-169  projectPoints (Rodrigues(R) == R)          u = fx (R X + t)_x / (R X + t)_z + cx, fp64      (-> float)
-//   :183-190  kept unless a reprojection error > 10 px (MIN_REPROJECTION_ERROR, :42): a NaN error is kept
-// One lane per match, everything in registers: the 4x4 SVD is a one-sided (Hestenes) Jacobi iteration on the columns of A
-// with V accumulated -- 8 sweeps of the 6 column pairs, no LDS, no divergence beyond the rotation skip.  The pass is
-// HBM-trivial (16 B in, 13 B out per match); it exists so that the step in front of bundle adjustment need not leave the GPU.
+// Device counterpart of SfMStereoUtilities::triangulateViews (SfMToyLib/SfMStereoUtilities.cpp:120-206); the per-match arithmetic is
+// triangulate_match of triangulate_math.h, which both kernels here call.
+//   k_triangulate        ALIGNED matches of ONE pair (sfmba_triangulate): one lane per match, the cameras are kernel arguments.
+//   k_triangulate_pairs  the flattened match lists of MANY pairs (sfmba_triangulate_pairs) as sfmba_match_features returns them: one
+//                        lane per entry.  The lane finds its pair by a binary search in pair_ptr (the largest p with
+//                        pair_ptr[p] <= i: empty pairs are stepped over), gathers its two key points through query_idx /
+//                        train_idx and reads its pair's P_left / P_right from device memory into registers -- n_pairs is unbounded,
+//                        so they cannot be kernel arguments.  pair_ptr is a few KB that every lane walks the same way: it stays in
+//                        cache, and the log2(n_pairs) dependent reads are what a lane pays for needing no host-side tile table.
+//   kept list            a hipCUB exclusive scan over keep and k_tri_compact (entry i goes to slot pos[i]: ascending by
+//                        construction, no atomics decide anything); kept_ptr[p] = pos[pair_ptr[p]].
+// The pass is HBM-trivial (16 B in, 13 B out per match); it exists so that the step in front of bundle adjustment need not leave
+// the GPU, and its batched form so that an added view costs one call and not one per good view.
 #include "ba_kernels.h"
+#include "device_arena.h"
+#include "triangulate_math.h"
+
+#include <hipcub/hipcub.hpp>
 
 namespace sfmba {
 
@@ -24,88 +29,85 @@ struct TriCams {
     float Pr[12];
 };
 
-__device__ __forceinline__ void jacobi_pair(double A[4][4], double V[4][4], int p, int q) {
-    double app = 0.0, aqq = 0.0, apq = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { app += A[r][p] * A[r][p]; aqq += A[r][q] * A[r][q]; apq += A[r][p] * A[r][q]; }
-    if (fabs(apq) <= 1e-300 || fabs(apq) <= 1e-17 * sqrt(app * aqq)) return;
-    const double zeta = (aqq - app) / (2.0 * apq);
-    const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const double ap = A[r][p], aq = A[r][q];
-        A[r][p] = c * ap - s * aq; A[r][q] = s * ap + c * aq;
-        const double vp = V[r][p], vq = V[r][q];
-        V[r][p] = c * vp - s * vq; V[r][q] = s * vp + c * vq;
-    }
-}
-
-// undistortPoints without distortion still takes the normalised point through its homogeneous product with R = I
-// [OpenCV-upstream: xx = 1 x + 0 y + 0, yy = 0 x + 1 y + 0, ww = 1 / (0 x + 0 y + 1), (xx ww, yy ww)]: a finite pixel passes
-// unchanged, a pixel with a NaN or an infinite coordinate comes out as (NaN, NaN) through 0 * inf -- and then has a NaN point
-// and NaN errors, which the filter keeps.  Without this an infinite pixel met the rotation skip of jacobi_pair as inf <= inf,
-// left V the identity and gave the finite point (1, 0, 0), dropped on its infinite error.
-__device__ __forceinline__ float2 normalise_px(float2 p, double fx, double fy, double cx, double cy) {
-    const double x = ((double)p.x - cx) / fx, y = ((double)p.y - cy) / fy;
-    const bool finite = isfinite(x) && isfinite(y);
-    const double nan = __builtin_nan("");
-    return make_float2((float)(finite ? x : nan), (float)(finite ? y : nan));
-}
-
-__device__ __forceinline__ float2 project_px(const float* P, const float* K, const float X[3]) {
-    const double x = (double)P[0] * X[0] + (double)P[1] * X[1] + (double)P[2] * X[2] + (double)P[3];
-    const double y = (double)P[4] * X[0] + (double)P[5] * X[1] + (double)P[6] * X[2] + (double)P[7];
-    const double z = (double)P[8] * X[0] + (double)P[9] * X[1] + (double)P[10] * X[2] + (double)P[11];
-    return make_float2((float)((double)K[0] * x / z + (double)K[2]), (float)((double)K[4] * y / z + (double)K[5]));
-}
-
 __global__ __launch_bounds__(256) void k_triangulate(long long n, const float2* __restrict__ left, const float2* __restrict__ right,
                                                      TriCams cams, float max_err, float* __restrict__ points3d,
                                                      unsigned char* __restrict__ keep, float* __restrict__ err) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float2 l = left[i], r = right[i];
-    const double fx = cams.K[0], fy = cams.K[4], cx = cams.K[2], cy = cams.K[5];
-    const float2 nl = normalise_px(l, fx, fy, cx, cy), nr = normalise_px(r, fx, fy, cx, cy);
-    const double xl = (double)nl.x, yl = (double)nl.y, xr = (double)nr.x, yr = (double)nr.y;
-    double A[4][4], V[4][4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        A[0][c] = xl * (double)cams.Pl[8 + c] - (double)cams.Pl[c];
-        A[1][c] = yl * (double)cams.Pl[8 + c] - (double)cams.Pl[4 + c];
-        A[2][c] = xr * (double)cams.Pr[8 + c] - (double)cams.Pr[c];
-        A[3][c] = yr * (double)cams.Pr[8 + c] - (double)cams.Pr[4 + c];
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) V[rr][c] = (rr == c) ? 1.0 : 0.0;
-    }
-#pragma unroll 1
-    for (int sweep = 0; sweep < 8; ++sweep) {
-        jacobi_pair(A, V, 0, 1); jacobi_pair(A, V, 0, 2); jacobi_pair(A, V, 0, 3);
-        jacobi_pair(A, V, 1, 2); jacobi_pair(A, V, 1, 3); jacobi_pair(A, V, 2, 3);
-    }
-    // column of the smallest singular value (branch-free selection)
-    double best = 0.0, v[4] = { 0.0, 0.0, 0.0, 0.0 };
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        double nn = 0.0;
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) nn += A[rr][c] * A[rr][c];
-        const bool take = (c == 0) || (nn < best);
-        best = take ? nn : best;
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) v[rr] = take ? V[rr][c] : v[rr];
-    }
-    const float h[4] = { (float)v[0], (float)v[1], (float)v[2], (float)v[3] };
-    const float scale = h[3] != 0.0f ? 1.0f / h[3] : 1.0f;
-    const float X[3] = { h[0] * scale, h[1] * scale, h[2] * scale };
-    const float2 pl = project_px(cams.Pl, cams.K, X), pr = project_px(cams.Pr, cams.K, X);
-    const double el = sqrt((double)(pl.x - l.x) * (double)(pl.x - l.x) + (double)(pl.y - l.y) * (double)(pl.y - l.y));
-    const double er = sqrt((double)(pr.x - r.x) * (double)(pr.x - r.x) + (double)(pr.y - r.y) * (double)(pr.y - r.y));
+    float X[3];
+    double el, er;
+    const bool kept = triangulate_match(l, r, cams.K, cams.Pl, cams.Pr, max_err, X, el, er);
     points3d[3 * i] = X[0]; points3d[3 * i + 1] = X[1]; points3d[3 * i + 2] = X[2];
-    keep[i] = (el > (double)max_err || er > (double)max_err) ? 0 : 1;
+    keep[i] = kept ? 1 : 0;
     if (err) { err[2 * i] = (float)el; err[2 * i + 1] = (float)er; }
 }
+
+struct TriK { float v[9]; };
+
+// what a lane needs to find entry i: its pair p, x = pts[img_ptr[pair_left[p]] + query_idx[i]] -> x' likewise
+struct TriProblem {
+    const long long* img_ptr;
+    const float2* pts;
+    const int* pair_left;
+    const int* pair_right;
+    const long long* pair_ptr;
+    const int* query_idx;
+    const int* train_idx;
+    const unsigned char* mask;               // or nullptr
+    const float* P_left;                     // [n_pairs][12]
+    const float* P_right;
+};
+
+// Entries i in [first, total), first = pair_ptr[0].  A masked entry is left as the arena handed it out: zero point, zero errors,
+// keep 0; so is every entry in front of `first`, for which no lane runs.
+__global__ __launch_bounds__(256) void k_triangulate_pairs(long long first, long long total, int n_pairs, TriProblem pr, TriK K, float max_err,
+                                                           float* __restrict__ points3d, unsigned char* __restrict__ keep,
+                                                           float* __restrict__ err) {
+    const long long i = first + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    if (pr.mask && !pr.mask[i]) return;
+    // the largest p with pair_ptr[p] <= i; pair_ptr[n_pairs] = total > i, so p + 1 <= n_pairs
+    int lo = 0, hi = n_pairs;                // pair_ptr[lo] <= i < pair_ptr[hi]
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (pr.pair_ptr[mid] <= i) lo = mid; else hi = mid;
+    }
+    const long long p = lo;
+    const float2 l = pr.pts[pr.img_ptr[pr.pair_left[p]] + (long long)pr.query_idx[i]];
+    const float2 r = pr.pts[pr.img_ptr[pr.pair_right[p]] + (long long)pr.train_idx[i]];
+    float Pl[12], Pr[12];
+    const float4* sl = reinterpret_cast<const float4*>(pr.P_left + 12 * p);        // 48 B rows of a 256 B aligned array
+    const float4* sr = reinterpret_cast<const float4*>(pr.P_right + 12 * p);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float4 a = sl[j], b = sr[j];
+        Pl[4 * j] = a.x; Pl[4 * j + 1] = a.y; Pl[4 * j + 2] = a.z; Pl[4 * j + 3] = a.w;
+        Pr[4 * j] = b.x; Pr[4 * j + 1] = b.y; Pr[4 * j + 2] = b.z; Pr[4 * j + 3] = b.w;
+    }
+    float X[3];
+    double el, er;
+    const bool kept = triangulate_match(l, r, K.v, Pl, Pr, max_err, X, el, er);
+    points3d[3 * i] = X[0]; points3d[3 * i + 1] = X[1]; points3d[3 * i + 2] = X[2];
+    keep[i] = kept ? 1 : 0;
+    if (err) { err[2 * i] = (float)el; err[2 * i + 1] = (float)er; }
+}
+
+// pos = the exclusive scan of keep over [0, total]: kept entry i is number pos[i] of the list, pair p starts at pos[pair_ptr[p]]
+__global__ __launch_bounds__(256) void k_tri_compact(long long total, int n_pairs, const unsigned char* __restrict__ keep,
+                                                     const long long* __restrict__ pos, const long long* __restrict__ pair_ptr,
+                                                     long long* __restrict__ kept_idx, long long* __restrict__ kept_ptr) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total && keep[i]) kept_idx[pos[i]] = i;
+    if (i <= (long long)n_pairs) kept_ptr[i] = pos[pair_ptr[i]];
+}
+
+struct KeepToCount {
+    __host__ __device__ long long operator()(unsigned char k) const { return k ? 1 : 0; }
+};
+
+#define TRI_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
+#define TRI_ALLOC(ptr, T, n) do { ptr = arena.alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
 
 }  // namespace
 
@@ -117,6 +119,74 @@ void launch_triangulate(hipStream_t s, long long n, const float* d_left, const f
     for (int e = 0; e < 12; ++e) { cams.Pl[e] = Pl[e]; cams.Pr[e] = Pr[e]; }
     hipLaunchKernelGGL(k_triangulate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, reinterpret_cast<const float2*>(d_left),
                        reinterpret_cast<const float2*>(d_right), cams, max_err, d_points3d, d_keep, d_err);
+}
+
+int triangulate_pairs(hipStream_t s, int device, int n_images, const int64_t* img_ptr, const float* pts, const float* K, int n_pairs,
+                      const int32_t* pair_left, const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx,
+                      const unsigned char* mask, const float* P_left, const float* P_right, float max_err, float* points3d, unsigned char* keep,
+                      float* reproj_err, int64_t* kept_ptr, int64_t* kept_idx) {
+    const long long first = pair_ptr[0], total = pair_ptr[n_pairs], n_pts = img_ptr[n_images];
+    // total < 2^31 - 257 (the caller's check): the scan counts its items in an int, and a grid dimension holds 2^32 - 1 threads
+    DeviceArena arena(device);
+    // every return below, the early ones included, waits for what is queued on s before the arena's chunks go back to the cache
+    struct StreamDrain { hipStream_t s; ~StreamDrain() { (void)hipStreamSynchronize(s); } } drain{ s };
+    // allocations first (the arena zeroes them: masked entries and those in front of pair_ptr[0] stay zero), then the stream work
+    long long *d_img, *d_ptr, *d_pos, *d_kidx, *d_kptr;
+    float2* d_pts;
+    int *d_left, *d_right, *d_query, *d_train;
+    float *d_Pl, *d_Pr, *d_x, *d_e = nullptr;
+    unsigned char *d_mask = nullptr, *d_keep;
+    TRI_ALLOC(d_img, long long, (size_t)n_images + 1);
+    TRI_ALLOC(d_pts, float2, (size_t)n_pts);
+    TRI_ALLOC(d_left, int, (size_t)n_pairs);
+    TRI_ALLOC(d_right, int, (size_t)n_pairs);
+    TRI_ALLOC(d_ptr, long long, (size_t)n_pairs + 1);
+    TRI_ALLOC(d_query, int, (size_t)total);
+    TRI_ALLOC(d_train, int, (size_t)total);
+    if (mask) TRI_ALLOC(d_mask, unsigned char, (size_t)total);
+    TRI_ALLOC(d_Pl, float, (size_t)12 * n_pairs);
+    TRI_ALLOC(d_Pr, float, (size_t)12 * n_pairs);
+    TRI_ALLOC(d_x, float, (size_t)3 * total);
+    if (reproj_err) TRI_ALLOC(d_e, float, (size_t)2 * total);
+    TRI_ALLOC(d_keep, unsigned char, (size_t)total + 1);           // one past the end stays 0: the scan's last item
+    TRI_ALLOC(d_pos, long long, (size_t)total + 1);
+    TRI_ALLOC(d_kidx, long long, (size_t)total);
+    TRI_ALLOC(d_kptr, long long, (size_t)n_pairs + 1);
+    size_t scan_bytes = 0;
+    hipcub::TransformInputIterator<long long, KeepToCount, const unsigned char*> keep_in(d_keep, KeepToCount());
+    TRI_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, keep_in, d_pos, (int)(total + 1), s));
+    void* d_tmp = arena.alloc(scan_bytes ? scan_bytes : 1);
+    if (!d_tmp) return (int)hipErrorOutOfMemory;
+
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "the index arrays are uploaded as they are");
+    TRI_TRY(hipMemcpyAsync(d_img, img_ptr, sizeof(int64_t) * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
+    TRI_TRY(hipMemcpyAsync(d_ptr, pair_ptr, sizeof(int64_t) * ((size_t)n_pairs + 1), hipMemcpyHostToDevice, s));
+    TRI_TRY(hipMemcpyAsync(d_left, pair_left, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    TRI_TRY(hipMemcpyAsync(d_right, pair_right, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    TRI_TRY(hipMemcpyAsync(d_Pl, P_left, sizeof(float) * 12 * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    TRI_TRY(hipMemcpyAsync(d_Pr, P_right, sizeof(float) * 12 * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    if (n_pts > 0) TRI_TRY(hipMemcpyAsync(d_pts, pts, sizeof(float) * 2 * (size_t)n_pts, hipMemcpyHostToDevice, s));
+    TRI_TRY(hipMemcpyAsync(d_query, query_idx, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
+    TRI_TRY(hipMemcpyAsync(d_train, train_idx, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
+    if (mask) TRI_TRY(hipMemcpyAsync(d_mask, mask, (size_t)total, hipMemcpyHostToDevice, s));
+
+    const TriProblem pr{ d_img, d_pts, d_left, d_right, d_ptr, d_query, d_train, d_mask, d_Pl, d_Pr };
+    TriK Kv;
+    for (int e = 0; e < 9; ++e) Kv.v[e] = K[e];
+    hipLaunchKernelGGL(k_triangulate_pairs, dim3((unsigned)((total - first + 255) / 256)), dim3(256), 0, s, first, total, n_pairs, pr, Kv, max_err,
+                       d_x, d_keep, d_e);
+    TRI_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, scan_bytes, keep_in, d_pos, (int)(total + 1), s));
+    const long long lanes = total > (long long)n_pairs + 1 ? total : (long long)n_pairs + 1;
+    hipLaunchKernelGGL(k_tri_compact, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, total, n_pairs, d_keep, d_pos, d_ptr, d_kidx, d_kptr);
+    TRI_TRY(hipGetLastError());
+    TRI_TRY(hipMemcpyAsync(points3d, d_x, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToHost, s));
+    TRI_TRY(hipMemcpyAsync(keep, d_keep, (size_t)total, hipMemcpyDeviceToHost, s));
+    if (reproj_err) TRI_TRY(hipMemcpyAsync(reproj_err, d_e, sizeof(float) * 2 * (size_t)total, hipMemcpyDeviceToHost, s));
+    TRI_TRY(hipMemcpyAsync(kept_ptr, d_kptr, sizeof(int64_t) * ((size_t)n_pairs + 1), hipMemcpyDeviceToHost, s));
+    // only the first kept_ptr[n_pairs] entries are defined; the rest of the buffer comes back as the arena's zeros
+    TRI_TRY(hipMemcpyAsync(kept_idx, d_kidx, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, s));
+    TRI_TRY(hipStreamSynchronize(s));
+    return 0;
 }
 
 }  // namespace sfmba

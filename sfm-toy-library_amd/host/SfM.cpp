@@ -1,0 +1,394 @@
+// SfM.cpp -- see SfM.h: the reference's orchestration (SfMToyLib/SfM.cpp:63-469) restated over the shim members of this directory.
+#include "SfM.h"
+
+#include <dirent.h>
+
+#include <algorithm>
+#include <cctype>
+#include <chrono>
+#include <cstdlib>
+#include <cstdio>
+#include <fstream>
+#include <iostream>
+#include <map>
+
+#include "SfM2DFeatureUtilities.h"
+#include "SfMBundleAdjustmentUtils.h"
+#include "SfMExport.h"
+#include "SfMStereoUtilities.h"
+
+namespace sfmtoylib {
+
+namespace {
+
+// the next header token of a PNM file: white space and '#' comments skipped; empty at the end of the file
+std::string pnmToken(std::istream& in) {
+    std::string tok;
+    int c = in.get();
+    while (c != EOF && (std::isspace(c) || c == '#')) {
+        if (c == '#') while (c != EOF && c != '\n') c = in.get();
+        else c = in.get();
+    }
+    while (c != EOF && !std::isspace(c)) { tok.push_back((char)c); c = in.get(); }
+    return tok;                                        // the single white-space byte behind the token has been consumed
+}
+
+bool pnmNumber(const std::string& tok, long& value) {
+    if (tok.empty() || tok.size() > 9) return false;
+    for (char ch : tok) if (ch < '0' || ch > '9') return false;
+    value = std::atol(tok.c_str());
+    return true;
+}
+
+// P5 -> CV_8U, P6 -> CV_8UC3 with the bytes of a pixel turned from R, G, B into OpenCV's B, G, R
+bool readPnm(const std::string& path, cv::Mat& image) {
+    std::ifstream in(path.c_str(), std::ios::binary);
+    if (!in) return false;
+    const std::string magic = pnmToken(in);
+    if (magic != "P5" && magic != "P6") return false;
+    long w = 0, h = 0, maxval = 0;
+    if (!pnmNumber(pnmToken(in), w) || !pnmNumber(pnmToken(in), h) || !pnmNumber(pnmToken(in), maxval)) return false;
+    if (w < 1 || h < 1 || w > 16384 || h > 16384 || maxval != 255) return false;
+    const int channels = magic == "P6" ? 3 : 1;
+    image = cv::Mat((int)h, (int)w, channels == 3 ? CV_8UC3 : CV_8U);
+    for (int r = 0; r < (int)h; ++r) {
+        unsigned char* row = image.ptr<unsigned char>(r);
+        in.read(reinterpret_cast<char*>(row), (std::streamsize)(w * channels));
+        if (in.gcount() != (std::streamsize)(w * channels)) return false;
+        if (channels == 3)
+            for (long x = 0; x < w; ++x) std::swap(row[3 * x], row[3 * x + 2]);
+    }
+    return true;
+}
+
+// Adds the wall time of its scope to one entry of SfM::mStageMs; does nothing (no clock is read) when `sums` is null, which is the
+// case unless SFMBA_SFM_TIMING is set.
+struct StageClock {
+    double* sum;
+    std::chrono::steady_clock::time_point t0;
+    StageClock(double* sums, int stage) : sum(sums ? sums + stage : nullptr) { if (sum) t0 = std::chrono::steady_clock::now(); }
+    ~StageClock() { if (sum) *sum += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+};
+const char* const stageNames[] = { "extract", "match", "rank", "baseline_pose", "baseline_triangulate", "associate", "pnp", "pair_poses",
+                                   "triangulate", "merge", "adjust" };
+
+std::string lowerExtension(const std::string& name) {
+    const size_t dot = name.rfind('.');
+    std::string ext = dot == std::string::npos ? std::string() : name.substr(dot);
+    for (char& ch : ext) ch = (char)std::tolower((unsigned char)ch);
+    return ext;
+}
+
+}  // namespace
+
+SfM::SfM(const float downscale) :
+        mConsoleDebugLevel(LOG_INFO),
+        mDownscaleFactor(downscale),
+        mFeaturesGiven(false),
+        mCols(0), mRows(0),
+        mTiming(false) {
+    for (double& ms : mStageMs) ms = 0.0;
+}
+
+SfM::~SfM() {
+}
+
+bool SfM::setImagesDirectory(const std::string& directoryPath) {
+    DIR* dir = opendir(directoryPath.c_str());
+    if (!dir) {
+        std::cerr << "setImagesDirectory: " << directoryPath << " cannot be read as a directory" << std::endl;
+        return false;
+    }
+    std::vector<std::string> names;
+    while (const dirent* entry = readdir(dir)) {
+        const std::string ext = lowerExtension(entry->d_name);
+        if (ext == ".pgm" || ext == ".ppm") names.push_back(entry->d_name);
+    }
+    closedir(dir);
+    std::sort(names.begin(), names.end());
+    if (names.empty()) {
+        std::cerr << "setImagesDirectory: no .pgm / .ppm file in " << directoryPath << std::endl;
+        return false;
+    }
+    std::vector<cv::Mat> images(names.size());
+    for (size_t i = 0; i < names.size(); i++) {
+        const std::string path = directoryPath + "/" + names[i];
+        if (!readPnm(path, images[i])) {
+            std::cerr << "setImagesDirectory: " << path << " is not a complete binary PGM / PPM file of maxval 255" << std::endl;
+            return false;
+        }
+        if (images[i].type() != images[0].type()) {
+            std::cerr << "setImagesDirectory: " << path << " is not of the kind (gray / colour) of the files before it" << std::endl;
+            return false;
+        }
+    }
+    if (mConsoleDebugLevel <= LOG_DEBUG) std::cout << "[sfm] " << names.size() << " images read from " << directoryPath << std::endl;
+    setImages(images);
+    return true;
+}
+
+void SfM::setImages(const std::vector<cv::Mat>& images) {
+    mImages = images;
+    mImageFeatures.clear();
+    mFeaturesGiven = false;
+    mCols = images.empty() ? 0 : images[0].cols;
+    mRows = images.empty() ? 0 : images[0].rows;
+}
+
+void SfM::setFeatures(const std::vector<Features>& imageFeatures, int cols, int rows) {
+    mImages.clear();
+    mImageFeatures = imageFeatures;
+    mFeaturesGiven = true;
+    mCols = cols;
+    mRows = rows;
+}
+
+void SfM::say(unsigned int level, const std::string& line) const {
+    if (mConsoleDebugLevel > level) return;
+    (level >= LOG_WARN ? std::cerr : std::cout) << "[sfm] " << line << std::endl;
+}
+
+// K of the contract in SfM.h (integer halves of the image size), its inverse in closed form, no distortion; empty reconstruction
+void SfM::startRun(size_t n_views) {
+    const float focal = 2500.0f;
+    const float centre[2] = { (float)(mCols / 2), (float)(mRows / 2) };
+    cv::Mat K(3, 3, CV_32F), Kinv(3, 3, CV_32F);
+    for (int d = 0; d < 2; d++) {
+        K.at<float>(d, d) = focal;
+        K.at<float>(d, 2) = centre[d];
+        Kinv.at<float>(d, d) = 1.0f / focal;
+        Kinv.at<float>(d, 2) = -centre[d] / focal;
+    }
+    K.at<float>(2, 2) = Kinv.at<float>(2, 2) = 1.0f;
+    mIntrinsics.K = K;
+    mIntrinsics.Kinv = Kinv;
+    mIntrinsics.distortion = cv::Mat(1, 4, CV_32F);
+    mCameraPoses.assign(n_views, cv::Matx34f());
+    mDoneViews.clear();
+    mGoodViews.clear();
+    mReconstructionCloud.clear();
+    mAddedViews.clear();
+    mFeatureMatchMatrix.clear();
+    mTiming = std::getenv("SFMBA_SFM_TIMING") != nullptr;
+    for (double& ms : mStageMs) ms = 0.0;
+}
+
+ErrorCode SfM::runSfM() {
+    const size_t n_views = mFeaturesGiven ? mImageFeatures.size() : mImages.size();
+    if (n_views == 0) {
+        std::cerr << "runSfM: there are no images and no features" << std::endl;
+        return ERROR;
+    }
+    if (mDownscaleFactor != 1.0f) {
+        std::cerr << "runSfM: downscale " << mDownscaleFactor << " is refused, only 1 is supported (there is no resize stage)" << std::endl;
+        return ERROR;
+    }
+    startRun(n_views);
+    double* const sums = mTiming ? mStageMs : nullptr;
+
+    if (!mFeaturesGiven) {
+        say(LOG_INFO, "stage 1: features of " + std::to_string(n_views) + " images");
+        StageClock clock(sums, T_EXTRACT);
+        if (!SfMFeatureExtraction::extractFeatures(mImages, mImageFeatures)) return ERROR;
+    }
+    say(LOG_INFO, "stage 2: match matrix");
+    {
+        StageClock clock(sums, T_MATCH);
+        if (!SfMFeatureMatching::createFeatureMatchMatrix(mImageFeatures, mFeatureMatchMatrix)) return ERROR;
+    }
+    say(LOG_INFO, "stage 3: baseline pair");
+    if (!findBaselineTriangulation()) {
+        std::cerr << "runSfM: no pair of views could start the reconstruction" << std::endl;
+        return ERROR;
+    }
+    say(LOG_INFO, "stage 4: remaining views");
+    addMoreViewsToReconstruction();
+    say(LOG_INFO, "finished: " + std::to_string(mGoodViews.size()) + " of " + std::to_string(n_views) + " views registered, " +
+                  std::to_string(mReconstructionCloud.size()) + " points");
+
+    if (mTiming) {
+        std::fprintf(stderr, "[sfmba sfm] views %d", (int)n_views);
+        for (int stage = 0; stage < T_COUNT; stage++) std::fprintf(stderr, " %s_ms %.3f", stageNames[stage], mStageMs[stage]);
+        std::fprintf(stderr, "\n");
+    }
+    return OKAY;
+}
+
+// The ranked pairs in key order (lowest homography-inlier ratio first); the first one that has a pose with enough inliers AND
+// triangulates becomes the reconstruction.  Pose and cloud outlive a turn of the loop as they do in the reference: a failed pose call
+// leaves them untouched, so nothing of an abandoned candidate is carried along.
+bool SfM::findBaselineTriangulation() {
+    double* const sums = mTiming ? mStageMs : nullptr;
+    std::map<float, ImagePair> ranked;
+    {
+        StageClock clock(sums, T_RANK);
+        ranked = SfMFeatureMatching::sortViewsForBaseline(mImageFeatures, mFeatureMatchMatrix);
+    }
+    cv::Matx34f poseA = cv::Matx34f::eye(), poseB = cv::Matx34f::eye();
+    PointCloud seed;
+    for (std::map<float, ImagePair>::const_iterator it = ranked.begin(); it != ranked.end(); ++it) {
+        const int a = (int)it->second.left, b = (int)it->second.right;
+        const std::string name = "pair (" + std::to_string(a) + ", " + std::to_string(b) + ")";
+        Matching& entry = mFeatureMatchMatrix[a][b];
+        Matching inliers;
+        bool ok;
+        {
+            StageClock clock(sums, T_BASELINE_POSE);
+            ok = SfMStereoUtilities::findCameraMatricesFromMatch(mIntrinsics, entry, mImageFeatures[a], mImageFeatures[b], inliers, poseA, poseB);
+        }
+        if (!ok) {
+            say(LOG_WARN, name + " has no relative pose");
+            continue;
+        }
+        // the gate of the reference on the share of matches that survive the pose (float division, as there)
+        if ((float)inliers.size() / (float)entry.size() < POSE_INLIERS_MINIMAL_RATIO) {
+            say(LOG_TRACE, name + " keeps " + std::to_string(inliers.size()) + " of " + std::to_string(entry.size()) + " matches: too few");
+            continue;
+        }
+        entry.swap(inliers);                           // the match matrix holds the pruned list from here on
+        {
+            StageClock clock(sums, T_BASELINE_TRIANGULATE);
+            ok = SfMStereoUtilities::triangulateViews(mIntrinsics, it->second, entry, mImageFeatures[a], mImageFeatures[b], poseA, poseB, seed);
+        }
+        if (!ok) {
+            say(LOG_WARN, name + " could not be triangulated");
+            continue;
+        }
+        say(LOG_DEBUG, name + " starts the reconstruction with " + std::to_string(seed.size()) + " points");
+        mReconstructionCloud.swap(seed);
+        mCameraPoses[a] = poseA;
+        mCameraPoses[b] = poseB;
+        const int both[2] = { a, b };
+        mDoneViews.insert(both, both + 2);
+        mGoodViews.insert(both, both + 2);
+        adjustCurrentBundle();
+        return true;
+    }
+    return false;
+}
+
+void SfM::adjustCurrentBundle() {
+    StageClock clock(mTiming ? mStageMs : nullptr, T_ADJUST);
+    SfMBundleAdjustmentUtils::adjustBundle(mReconstructionCloud, mCameraPoses, mIntrinsics, mImageFeatures);
+}
+
+// The view to add next: most 2D-3D matches, the lowest index among equals (the map is walked in ascending view order and only a
+// strictly larger count replaces the candidate); when no view has a match, the lowest view that is not done.
+int SfM::nextView(const Images2D3DMatches& candidates) const {
+    int view = -1;
+    size_t most = 0;
+    for (Images2D3DMatches::const_iterator it = candidates.begin(); it != candidates.end(); ++it)
+        if (it->second.points2D.size() > most) {
+            most = it->second.points2D.size();
+            view = it->first;
+        }
+    for (int v = 0; view < 0 && v < (int)mCameraPoses.size(); v++)
+        if (mDoneViews.find(v) == mDoneViews.end()) view = v;
+    return view;
+}
+
+// New points of a freshly posed view: its pairs with every good view (ascending; the lower index is the left image, because only
+// the upper triangle of the match matrix is filled) go through ONE pose call, whose pruned lists replace the matrix entries -- an
+// empty list for a pair without a pose --, then through ONE triangulation call under the reconstruction's poses; the clouds are
+// merged in pair order.  Returns whether the triangulation call succeeded.
+bool SfM::triangulateAgainstGoodViews(int view) {
+    double* const sums = mTiming ? mStageMs : nullptr;
+    std::vector<const Features*> images;
+    for (size_t v = 0; v < mImageFeatures.size(); v++) images.push_back(&mImageFeatures[v]);
+    std::vector<int> left, right;
+    std::vector<const Matching*> lists;
+    std::vector<cv::Matx34f> poseLeft, poseRight;
+    for (std::set<int>::const_iterator g = mGoodViews.begin(); g != mGoodViews.end(); ++g) {
+        left.push_back(std::min(*g, view));
+        right.push_back(std::max(*g, view));
+        lists.push_back(&mFeatureMatchMatrix[left.back()][right.back()]);
+        poseLeft.push_back(mCameraPoses[left.back()]);
+        poseRight.push_back(mCameraPoses[right.back()]);
+    }
+    const size_t n_pairs = left.size();
+    std::vector<unsigned char> ok;
+    {
+        std::vector<Matching> pruned;
+        std::vector<cv::Matx34f> relLeft, relRight;    // the pairs' own relative poses: only their inlier sets are used
+        StageClock clock(sums, T_PAIR_POSES);
+        SfMStereoUtilities::findCameraMatricesFromMatchBatch(mIntrinsics, images, left, right, lists, ok, pruned, relLeft, relRight);
+        for (size_t p = 0; p < n_pairs; p++) mFeatureMatchMatrix[left[p]][right[p]].swap(pruned[p]);
+    }
+    std::vector<PointCloud> clouds;
+    bool triangulated;
+    {
+        StageClock clock(sums, T_TRIANGULATE);
+        triangulated = SfMStereoUtilities::triangulateViewsBatch(mIntrinsics, images, left, right, lists, poseLeft, poseRight, ok, clouds);
+    }
+    if (!triangulated) {
+        say(LOG_WARN, "view " + std::to_string(view) + ": the triangulation against the good views failed");
+        return false;
+    }
+    StageClock clock(sums, T_MERGE);
+    for (size_t p = 0; p < n_pairs; p++) {
+        SfMAssociation::mergeNewPointCloud(mReconstructionCloud, clouds[p], mFeatureMatchMatrix);
+        say(LOG_DEBUG, "views " + std::to_string(left[p]) + " / " + std::to_string(right[p]) + ": " + std::to_string(clouds[p].size()) +
+                       " points triangulated, cloud now " + std::to_string(mReconstructionCloud.size()));
+    }
+    return true;
+}
+
+void SfM::addMoreViewsToReconstruction() {
+    double* const sums = mTiming ? mStageMs : nullptr;
+    const size_t n_views = mCameraPoses.size();
+    while (mDoneViews.size() < n_views) {
+        Images2D3DMatches candidates;
+        {
+            StageClock clock(sums, T_ASSOCIATE);
+            candidates = SfMAssociation::find2D3DMatches(n_views, mDoneViews, mReconstructionCloud, mFeatureMatchMatrix, mImageFeatures);
+        }
+        const int view = nextView(candidates);
+        mDoneViews.insert(view);                       // done whatever follows: a view is tried once
+
+        AddedView turn = { view, false, 0 };
+        cv::Matx34f pose;
+        {
+            StageClock clock(sums, T_PNP);
+            turn.posed = SfMStereoUtilities::findCameraPoseFrom2D3DMatch(mIntrinsics, candidates[view], pose);
+        }
+        say(turn.posed ? LOG_DEBUG : LOG_WARN, "view " + std::to_string(view) + " with " + std::to_string(candidates[view].points2D.size()) +
+                                               " 2D-3D matches: " + (turn.posed ? "posed" : "no pose, left out"));
+        if (turn.posed) {
+            mCameraPoses[view] = pose;
+            const bool grown = triangulateAgainstGoodViews(view);
+            turn.cloudSize = mReconstructionCloud.size();
+            if (grown) adjustCurrentBundle();
+            mGoodViews.insert(view);
+        } else {
+            turn.cloudSize = mReconstructionCloud.size();
+        }
+        mAddedViews.push_back(turn);
+    }
+}
+
+bool SfM::saveCloudAndCamerasToPLY(const std::string& prefix) {
+#ifdef SFMBA_HAVE_OPENCV
+    return SfMExport::saveCloudAndCamerasToPLY(prefix, mReconstructionCloud, mCameraPoses, mImageFeatures, mImages);
+#else
+    // B, G, R bytes of every view: a colour image as it is, a gray one with its value in all three, gray 128 without images.  One
+    // row and one pixel of slack behind the last row: SfMExport rounds a feature to the nearest pixel without a bounds check.
+    std::vector<ImageBGR> images(mCameraPoses.size());
+    for (size_t v = 0; v < images.size(); v++) {
+        ImageBGR& out = images[v];
+        const cv::Mat* src = v < mImages.size() ? &mImages[v] : nullptr;
+        out.rows = src ? src->rows : mRows;
+        out.cols = src ? src->cols : mCols;
+        out.data.assign(((size_t)out.rows * out.cols + out.cols + 1) * 3, 128);
+        if (!src) continue;
+        for (int r = 0; r < out.rows; r++) {
+            const unsigned char* row = src->ptr<unsigned char>(r);
+            unsigned char* dst = out.data.data() + (size_t)r * out.cols * 3;
+            for (int c = 0; c < out.cols; c++)
+                for (int k = 0; k < 3; k++) dst[3 * c + k] = src->type() == CV_8UC3 ? row[3 * c + k] : row[c];
+        }
+    }
+    return SfMExport::saveCloudAndCamerasToPLY(prefix, mReconstructionCloud, mCameraPoses, mImageFeatures, images);
+#endif
+}
+
+}  // namespace sfmtoylib

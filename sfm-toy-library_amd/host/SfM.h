@@ -1,0 +1,122 @@
+// SfM.h -- sfmtoylib::SfM, the orchestrator of the reference (SfMToyLib/SfM.h:45-149, SfM.cpp:63-469), over the shim members of this
+// directory: from images (or features) to camera poses and a point cloud in one call, every stage on the MI355X.
+//
+// The control flow is the reference's, member for member.  Where the reference is undefined, or where a batched stage changes which
+// sample stream a pair draws, the behaviour is fixed here -- tests/sfm_loop.py restates it and tests/test_gpu_sfm_pipeline.py pins it:
+//
+//   K             f = 2500, centre = (cols / 2, rows / 2) of image 0 in integer division (SfM.cpp:70-72); with setFeatures the cols /
+//                 rows given there.  Kinv is the closed form, distortion 1 x 4 zeros.
+//   front end     SfMFeatureExtraction::extractFeatures (skipped after setFeatures), SfMFeatureMatching::createFeatureMatchMatrix and
+//                 sortViewsForBaseline.  A device failure in any of them makes runSfM return ERROR: the first two report it themselves;
+//                 sortViewsForBaseline returns a map and cannot, so its failure shows one step later -- every qualifying pair ranks
+//                 with 0 inliers, the pose calls of the baseline fail on the same device, and the ERROR is the baseline's
+//                 ("no pair of views could start the reconstruction").
+//   baseline      the map of sortViewsForBaseline in key order, each pair through the SINGLE-pair findCameraMatricesFromMatch (seed 0;
+//                 the loop leaves at the first pair that works, so it is serial by nature), the POSE_INLIERS_MINIMAL_RATIO gate, the
+//                 pruned matches written back to the match matrix, triangulateViews, adjustBundle.  No pair works: runSfM returns
+//                 ERROR (the reference goes on with an empty cloud).
+//   next view     the not-done view with the most 2D-3D matches, ties to the lowest index; every count 0: the lowest not-done view
+//                 (the reference reads an uninitialised variable).  It is marked done; findCameraPoseFrom2D3DMatch; on failure the
+//                 loop goes on: the view stays done and not good.
+//   new points    the good views in ascending order as ONE findCameraMatricesFromMatchBatch call (pair p draws seed p; left = the
+//                 lower view index).  EVERY pair's pruned list replaces its match-matrix entry, an empty list for a failed pair
+//                 (the reference's unconditional assignment, SfM.cpp:431).  Then ONE triangulateViewsBatch call with the GLOBAL
+//                 poses, SfMAssociation::mergeNewPointCloud pair by pair in that order, adjustBundle if the batch triangulated,
+//                 and the view becomes good.
+//   end           every view is done.
+// downscale != 1 is refused by runSfM (no resize kernel); there is no visual debugging.
+// An object holds all of a run's state (the stage times of SFMBA_SFM_TIMING included): different objects may run in different
+// threads; one object is not re-entrant.
+#pragma once
+#include <set>
+#include <string>
+#include <vector>
+
+#include "SfMCommon.h"
+#include "SfMAssociation.h"
+
+namespace sfmtoylib {
+
+enum ErrorCode {
+    OKAY = 0,
+    ERROR
+};
+
+enum { LOG_TRACE = 0, LOG_DEBUG, LOG_INFO, LOG_WARN, LOG_ERROR };      // SfMCommon.h:38-44 of the reference
+
+class SfM {
+public:
+    // one turn of the add-more-views loop
+    struct AddedView {
+        int    view;            // the view that was marked done
+        bool   posed;           // findCameraPoseFrom2D3DMatch's verdict
+        size_t cloudSize;       // the reconstruction cloud after the view's merges (as before them when posed is false)
+    };
+
+    SfM(const float downscale = 1.0);
+    virtual ~SfM();
+
+    /**
+     * Binary .pgm (P5 -> CV_8U) / .ppm (P6 -> CV_8UC3, stored B, G, R) files of the directory with maxval 255, in ascending
+     * file-name order (the extension decides which files are read, in either letter case).
+     * @return true on success; false (no image kept) when the directory cannot be read, holds no such file, a file is not a P5 / P6
+     *         file of maxval 255 with all its bytes, or the files are not all of one kind.
+     */
+    bool setImagesDirectory(const std::string& directoryPath);
+
+    /** The images themselves, all CV_8U or all CV_8UC3 (there is no imread here).  Forgets features given by setFeatures. */
+    void setImages(const std::vector<cv::Mat>& images);
+
+    /** Key points (+ points) and descriptors of every view and the image size: runSfM then skips the extraction. */
+    void setFeatures(const std::vector<Features>& imageFeatures, int cols, int rows);
+
+    /** Run the pipeline (the contract is at the top of this file); every call starts from the images / features again. */
+    ErrorCode runSfM();
+
+    /**
+     * <prefix>_points.ply and <prefix>_cameras.ply through SfMExport.  Gray images colour a point with its gray value; after
+     * setFeatures every point is gray 128.
+     */
+    bool saveCloudAndCamerasToPLY(const std::string& prefix);
+
+    void setConsoleDebugLevel(unsigned int consoleDebugLevel) { mConsoleDebugLevel = consoleDebugLevel < (unsigned int)LOG_ERROR ? consoleDebugLevel : (unsigned int)LOG_ERROR; }
+
+    const std::vector<cv::Mat>&     getImages() const { return mImages; }
+    const std::vector<Features>&    getImageFeatures() const { return mImageFeatures; }
+    const std::vector<cv::Matx34f>& getCameraPoses() const { return mCameraPoses; }
+    const PointCloud&               getPointCloud() const { return mReconstructionCloud; }
+    const Intrinsics&               getIntrinsics() const { return mIntrinsics; }
+    const std::set<int>&            getDoneViews() const { return mDoneViews; }
+    const std::set<int>&            getGoodViews() const { return mGoodViews; }
+    const std::vector<AddedView>&   getAddedViews() const { return mAddedViews; }
+
+private:
+    enum { T_EXTRACT, T_MATCH, T_RANK, T_BASELINE_POSE, T_BASELINE_TRIANGULATE, T_ASSOCIATE, T_PNP, T_PAIR_POSES, T_TRIANGULATE, T_MERGE,
+           T_ADJUST, T_COUNT };                  // the stages SFMBA_SFM_TIMING reports
+
+    void say(unsigned int level, const std::string& line) const;      // one console line if the debug level admits it
+    void startRun(size_t n_views);
+    bool findBaselineTriangulation();
+    void adjustCurrentBundle();
+    void addMoreViewsToReconstruction();
+    int  nextView(const Images2D3DMatches& candidates) const;
+    bool triangulateAgainstGoodViews(int view);
+
+    std::vector<cv::Mat>      mImages;
+    std::vector<Features>     mImageFeatures;
+    std::vector<cv::Matx34f>  mCameraPoses;
+    std::set<int>             mDoneViews;
+    std::set<int>             mGoodViews;
+    MatchMatrix               mFeatureMatchMatrix;
+    Intrinsics                mIntrinsics;
+    PointCloud                mReconstructionCloud;
+    std::vector<AddedView>    mAddedViews;
+    unsigned int              mConsoleDebugLevel;
+    float                     mDownscaleFactor;
+    bool                      mFeaturesGiven;
+    int                       mCols, mRows;      // of image 0, or as given to setFeatures
+    bool                      mTiming;           // SFMBA_SFM_TIMING was set when the run began
+    double                    mStageMs[T_COUNT]; // wall time per stage of the current run (all zero unless mTiming)
+};
+
+}  // namespace sfmtoylib

@@ -5,6 +5,10 @@
 // triangulation + 10 px reprojection filter runs on the GPU (sfmba_triangulate), and every surviving point is appended to
 // pointCloud with originatingViews[left] / [right] = those back references (:192-203).  Points are appended in match order.
 //
+// triangulateViewsBatch: the same for the pairs (good view, new view) of one added view (SfM.cpp:413-444) in ONE device call
+// (sfmba_triangulate_pairs): the match lists go as they are, the alignment happens on the device, and the kept entries come back as
+// a list per pair, in match order.
+//
 // findCameraPoseFrom2D3DMatch (SfMToyLib/SfMStereoUtilities.cpp:208-243): the reference calls cv::solvePnPRansac with
 // iterationsCount = 100, reprojectionError = RANSAC_THRESHOLD = 10 and confidence 0.99, then rejects the pose when fewer than
 // POSE_INLIERS_MINIMAL_RATIO of the matches are inliers.  Here sfmba_pnp_ransac evaluates all 100 hypotheses at once -- the
@@ -203,6 +207,78 @@ bool SfMStereoUtilities::triangulateViews(
         p.originatingViews[(int)imagePair.left]  = leftBackReference[i];
         p.originatingViews[(int)imagePair.right] = rightBackReference[i];
         pointCloud.push_back(p);
+    }
+    return true;
+}
+
+bool SfMStereoUtilities::triangulateViewsBatch(
+        const Intrinsics&                   intrinsics,
+        const std::vector<const Features*>& images,
+        const std::vector<int>&             left,
+        const std::vector<int>&             right,
+        const std::vector<const Matching*>& matches,
+        const std::vector<cv::Matx34f>&     Pleft,
+        const std::vector<cv::Matx34f>&     Pright,
+        std::vector<unsigned char>&         ok,
+        std::vector<PointCloud>&            pointClouds) {
+    const float  MIN_REPROJECTION_ERROR = 10.0f;    // SfMStereoUtilities.cpp:42
+    const size_t n_pairs = left.size();
+    ok.assign(n_pairs, 0);
+    pointClouds.assign(n_pairs, PointCloud());
+    if (intrinsics.K.empty()) {
+        std::cerr << "Intrinsics matrix (K) must be initialized." << std::endl;
+        return false;
+    }
+    if (right.size() != n_pairs || matches.size() != n_pairs || Pleft.size() != n_pairs || Pright.size() != n_pairs) {
+        std::cerr << "triangulateViews failed. (the lists of a batch differ in length)" << std::endl;
+        return false;
+    }
+    if (n_pairs == 0) return true;
+    float K[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) K[3 * r + c] = intrinsics.K.at<float>(r, c);
+    std::vector<int64_t> img_ptr(images.size() + 1, 0);
+    for (size_t i = 0; i < images.size(); i++) img_ptr[i + 1] = img_ptr[i] + (int64_t)images[i]->keyPoints.size();
+    std::vector<float> pts(2 * (size_t)img_ptr.back() + 2);
+    for (size_t i = 0; i < images.size(); i++)
+        for (size_t k = 0; k < images[i]->keyPoints.size(); k++) {
+            pts[2 * ((size_t)img_ptr[i] + k)]     = images[i]->keyPoints[k].pt.x;
+            pts[2 * ((size_t)img_ptr[i] + k) + 1] = images[i]->keyPoints[k].pt.y;
+        }
+    std::vector<int64_t> pair_ptr(n_pairs + 1, 0);
+    for (size_t p = 0; p < n_pairs; p++) pair_ptr[p + 1] = pair_ptr[p] + (int64_t)matches[p]->size();
+    const size_t total = (size_t)pair_ptr.back();
+    std::vector<int32_t> pl(left.begin(), left.end()), pr(right.begin(), right.end());
+    std::vector<int32_t> query(total + 1), train(total + 1);
+    std::vector<float> Pl(12 * n_pairs), Pr(12 * n_pairs);
+    for (size_t p = 0; p < n_pairs; p++) {
+        for (size_t e = 0; e < matches[p]->size(); e++) {
+            query[(size_t)pair_ptr[p] + e] = (*matches[p])[e].queryIdx;
+            train[(size_t)pair_ptr[p] + e] = (*matches[p])[e].trainIdx;
+        }
+        for (int e = 0; e < 12; e++) { Pl[12 * p + e] = Pleft[p].val[e]; Pr[12 * p + e] = Pright[p].val[e]; }
+    }
+    std::vector<float> points3d(3 * total + 3);
+    std::vector<unsigned char> keep(total + 1);
+    std::vector<int64_t> kept_ptr(n_pairs + 1), kept_idx(total + 1);
+    const int rc = sfmba_triangulate_pairs(0, (int)images.size(), img_ptr.data(), pts.data(), K, (int)n_pairs, pl.data(), pr.data(), pair_ptr.data(),
+                                           query.data(), train.data(), nullptr, Pl.data(), Pr.data(), MIN_REPROJECTION_ERROR, points3d.data(),
+                                           keep.data(), nullptr, kept_ptr.data(), kept_idx.data());
+    if (rc != SFMBA_OK) {
+        std::cerr << "triangulateViews failed. (sfmba rc=" << rc << ": " << sfmba_last_error() << ")" << std::endl;
+        return false;
+    }
+    for (size_t p = 0; p < n_pairs; p++) {
+        ok[p] = 1;
+        pointClouds[p].reserve((size_t)(kept_ptr[p + 1] - kept_ptr[p]));
+        for (int64_t k = kept_ptr[p]; k < kept_ptr[p + 1]; k++) {
+            const size_t i = (size_t)kept_idx[k];
+            Point3DInMap pt;
+            pt.p = cv::Point3f(points3d[3 * i], points3d[3 * i + 1], points3d[3 * i + 2]);
+            pt.originatingViews[left[p]]  = query[i];
+            pt.originatingViews[right[p]] = train[i];
+            pointClouds[p].push_back(pt);
+        }
     }
     return true;
 }

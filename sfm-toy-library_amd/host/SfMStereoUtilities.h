@@ -1,7 +1,7 @@
 // SfMStereoUtilities.h -- the homography-inlier count, the relative pose of a pair, the triangulation and the 2D-3D pose entry
 // points of the reference with their own signatures (SfMToyLib/SfMStereoUtilities.h:53-105), backed by the MI355X kernels
-// (include/sfmba.h: sfmba_homography_ransac, sfmba_essential_ransac, sfmba_triangulate, sfmba_pnp_ransac).  Every member of the
-// reference class has its counterpart here.
+// (include/sfmba.h: sfmba_homography_ransac, sfmba_essential_ransac, sfmba_triangulate, sfmba_triangulate_pairs,
+// sfmba_pnp_ransac).  Every member of the reference class has its counterpart here.
 #pragma once
 #include <vector>
 
@@ -86,6 +86,25 @@ public:
             const cv::Matx34f& Pleft,
             const cv::Matx34f& Pright,
             PointCloud&        pointCloud);
+
+    /**
+     * The same for a list of pairs in ONE device call -- the pairs (good view, new view) of one added view (SfM.cpp:413-444):
+     * pair p = images[left[p]] -> images[right[p]] with matches[p] under Pleft[p] / Pright[p]; pointClouds[p] receives exactly
+     * the points triangulateViews appends for that pair (same floats, same back references, same order), with
+     * originatingViews keyed by left[p] / right[p]; ok[p] = 1.
+     * @return false (every ok 0, every cloud empty; a line is written to stderr) when K is empty, the lists differ in length,
+     *         there is no HIP device or on a device error.
+     */
+    static bool triangulateViewsBatch(
+            const Intrinsics&                   intrinsics,
+            const std::vector<const Features*>& images,
+            const std::vector<int>&             left,
+            const std::vector<int>&             right,
+            const std::vector<const Matching*>& matches,
+            const std::vector<cv::Matx34f>&     Pleft,
+            const std::vector<cv::Matx34f>&     Pright,
+            std::vector<unsigned char>&         ok,
+            std::vector<PointCloud>&            pointClouds);
 
     /**
      * Find the camera pose of a new view from its 2D-3D matches (P3P RANSAC + refinement on the GPU).

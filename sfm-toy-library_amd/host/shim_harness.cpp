@@ -10,6 +10,7 @@
 #include "SfMAssociation.h"
 #include "SfMExport.h"
 #include "SfM2DFeatureUtilities.h"
+#include "SfM.h"
 
 extern "C" __attribute__((visibility("default")))
 void sfmba_shim_adjust_bundle(int n_views, float* poses /*[n_views][12]*/, float* K /*[9]*/, int n_pts, float* points /*[n_pts][3]*/,
@@ -178,6 +179,47 @@ int sfmba_shim_find_camera_matrices_batch(const float* K /*[9] or NULL*/, int n_
         for (const cv::DMatch& d : kept[p]) { pruned[2 * n] = d.queryIdx; pruned[2 * n + 1] = d.trainIdx; ++n; }
     }
     pruned_ptr[n_pairs] = n;
+    return all ? 1 : 0;
+}
+
+// Flat-array driver of sfmtoylib::SfMStereoUtilities::triangulateViewsBatch (tests/test_gpu_triangulate_pairs.py): the clouds come
+// back one after the other, cloud_ptr [n_pairs + 1] cutting points3d / left_ref / right_ref (points beyond cap are not written);
+// ok [n_pairs].  Returns 1 / 0 = the call's true / false.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_triangulate_views_batch(const float* K /*[9] or NULL*/, int n_images, const int64_t* img_ptr, const float* xy, int n_pairs,
+                                       const int32_t* left, const int32_t* right, const int64_t* pair_ptr, const int32_t* query,
+                                       const int32_t* train, const float* P_left /*[n_pairs][12]*/, const float* P_right, unsigned char* ok,
+                                       int64_t* cloud_ptr, int64_t cap, float* points3d, int32_t* left_ref, int32_t* right_ref) {
+    using namespace sfmtoylib;
+    const std::vector<Features> feats = buildKeyPoints(n_images, img_ptr, xy);
+    std::vector<const Features*> images;
+    for (const Features& f : feats) images.push_back(&f);
+    std::vector<Matching> lists((size_t)n_pairs);
+    std::vector<const Matching*> matches;
+    std::vector<cv::Matx34f> Pl((size_t)n_pairs), Pr((size_t)n_pairs);
+    for (int p = 0; p < n_pairs; ++p) {
+        for (int64_t e = pair_ptr[p]; e < pair_ptr[p + 1]; ++e) lists[p].push_back(cv::DMatch(query[e], train[e], 0.0f));
+        matches.push_back(&lists[p]);
+        for (int e = 0; e < 12; ++e) { Pl[p].val[e] = P_left[12 * p + e]; Pr[p].val[e] = P_right[12 * p + e]; }
+    }
+    std::vector<unsigned char> good;
+    std::vector<PointCloud> clouds;
+    const bool all = SfMStereoUtilities::triangulateViewsBatch(buildIntrinsics(K), images, std::vector<int>(left, left + n_pairs),
+                                                               std::vector<int>(right, right + n_pairs), matches, Pl, Pr, good, clouds);
+    int64_t n = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        ok[p] = good[p];
+        cloud_ptr[p] = n;
+        for (const Point3DInMap& pt : clouds[p]) {
+            if (n < cap) {
+                points3d[3 * n] = pt.p.x; points3d[3 * n + 1] = pt.p.y; points3d[3 * n + 2] = pt.p.z;
+                left_ref[n] = pt.originatingViews.at(left[p]);
+                right_ref[n] = pt.originatingViews.at(right[p]);
+            }
+            ++n;
+        }
+    }
+    cloud_ptr[n_pairs] = n;
     return all ? 1 : 0;
 }
 
@@ -414,4 +456,84 @@ int64_t sfmba_shim_extract_features_batch(int n_images, const int64_t* img_ptr, 
         kp_ptr[i + 1] = at;
     }
     return at;
+}
+
+// Flat-array driver of sfmtoylib::SfM (tests/test_gpu_sfm_pipeline.py): one run from images (channels = 1 or 3: image i owns bytes
+// img_ptr[i] .. img_ptr[i+1]-1 of px, w / h per image) or from features (channels = 0: view i owns rows kp_ptr[i] .. kp_ptr[i+1]-1 of
+// kp_xy [..][2] and desc [..][32]; cols / rows = the image size).  Back come the poses [n_views][12], K [9], the done / good flags
+// [n_views], the turns of the add-more-views loop (added_view / added_posed / added_cloud [n_views], *n_added of them) and the
+// cloud flattened with its views CSR.  ply_prefix != NULL: saveCloudAndCamerasToPLY(ply_prefix) after the run.
+// Returns runSfM's code (0 = OKAY, 1 = ERROR), -2 if an output capacity is too small, -3 if the PLY files could not be written.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm(float downscale, int n_views, int channels, const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h,
+                       const int64_t* kp_ptr, const float* kp_xy, const unsigned char* desc, int cols, int rows, int debug_level, float* poses,
+                       float* K, unsigned char* done, unsigned char* good, int* n_added, int32_t* added_view, unsigned char* added_posed,
+                       int64_t* added_cloud, int64_t cap_pts, int64_t cap_views, int64_t* n_pts, float* xyz, int64_t* view_ptr, int32_t* view_idx,
+                       int32_t* feat_idx, const char* ply_prefix) {
+    using namespace sfmtoylib;
+    SfM sfm(downscale);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    if (channels == 0) {
+        std::vector<Features> feats = buildDescriptors(n_views, kp_ptr, desc, 32);
+        for (int v = 0; v < n_views; ++v)
+            for (int64_t f = kp_ptr[v]; f < kp_ptr[v + 1]; ++f) {
+                cv::KeyPoint kp; kp.pt = cv::Point2f(kp_xy[2 * f], kp_xy[2 * f + 1]);
+                feats[v].keyPoints.push_back(kp); feats[v].points.push_back(kp.pt);
+            }
+        sfm.setFeatures(feats, cols, rows);
+    } else {
+        std::vector<cv::Mat> images;
+        for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+        sfm.setImages(images);
+    }
+    const ErrorCode code = sfm.runSfM();
+    *n_added = 0;
+    *n_pts = 0;
+    if (code != OKAY) return (int)code;
+    for (int v = 0; v < n_views; ++v) {
+        for (int e = 0; e < 12; ++e) poses[12 * v + e] = sfm.getCameraPoses()[v].val[e];
+        done[v] = sfm.getDoneViews().count(v) ? 1 : 0;
+        good[v] = sfm.getGoodViews().count(v) ? 1 : 0;
+    }
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) K[3 * r + c] = sfm.getIntrinsics().K.at<float>(r, c);
+    for (const SfM::AddedView& a : sfm.getAddedViews()) {
+        if (*n_added >= n_views) return -2;
+        added_view[*n_added] = a.view; added_posed[*n_added] = a.posed ? 1 : 0; added_cloud[*n_added] = (int64_t)a.cloudSize;
+        ++*n_added;
+    }
+    const PointCloud& cloud = sfm.getPointCloud();
+    if ((int64_t)cloud.size() > cap_pts) return -2;
+    *n_pts = (int64_t)cloud.size();
+    int64_t o = 0;
+    for (size_t i = 0; i < cloud.size(); ++i) {
+        xyz[3 * i] = cloud[i].p.x; xyz[3 * i + 1] = cloud[i].p.y; xyz[3 * i + 2] = cloud[i].p.z;
+        view_ptr[i] = o;
+        for (const auto& kv : cloud[i].originatingViews) { if (o >= cap_views) return -2; view_idx[o] = kv.first; feat_idx[o] = kv.second; ++o; }
+    }
+    view_ptr[cloud.size()] = o;
+    if (ply_prefix && !sfm.saveCloudAndCamerasToPLY(ply_prefix)) return -3;
+    return 0;
+}
+
+// Flat-array driver of sfmtoylib::SfM::setImagesDirectory (tests/test_sfm_scene_cpu.py; no device involved): the images come back
+// one after the other in px (cap bytes), w / h [cap_images], *channels = 1 or 3.  Returns the number of images, -1 when the call
+// reported failure, -2 if a capacity is too small.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_read_images_directory(const char* path, int cap_images, int64_t cap, int32_t* w, int32_t* h, int* channels, unsigned char* px) {
+    using namespace sfmtoylib;
+    SfM sfm;
+    sfm.setConsoleDebugLevel(LOG_ERROR);
+    if (!sfm.setImagesDirectory(path)) return -1;
+    const std::vector<cv::Mat>& images = sfm.getImages();
+    if ((int)images.size() > cap_images) return -2;
+    int64_t at = 0;
+    for (size_t i = 0; i < images.size(); ++i) {
+        const int ch = images[i].type() == CV_8UC3 ? 3 : 1;
+        const int64_t row = (int64_t)images[i].cols * ch;
+        if (at + row * images[i].rows > cap) return -2;
+        *channels = ch;
+        w[i] = images[i].cols; h[i] = images[i].rows;
+        for (int r = 0; r < images[i].rows; ++r, at += row) std::memcpy(px + at, images[i].ptr<unsigned char>(r), (size_t)row);
+    }
+    return (int)images.size();
 }
