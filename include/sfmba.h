@@ -810,6 +810,75 @@ SFMBA_API int sfmba_orb_extract(int device, int n_images, const int64_t* img_ptr
                 int32_t* dbg_level_xy /*[cap][2] or NULL*/, int32_t* dbg_bin /*[cap] or NULL*/, int64_t* dbg_harris /*[cap] or NULL*/,
                 int32_t* dbg_candidates /*[n_images][n_levels] or NULL*/);
 
+/* ---- reading photographs: baseline JPEG decode and bilinear resize (SfM::setImagesDirectory) -----------------------------------
+ * The reference reads every image with imread and shrinks it with resize(..., Size(), f, f) (SfMToyLib/SfM.cpp:125-129).  Here a
+ * whole list of files is decoded, and a whole list of images resized, in one call each.  THE CONTRACT IS INTEGER-EXACT: the decode
+ * equals libjpeg's default decode (integer "islow" inverse DCT, triangle chroma upsampling) of a baseline file bit for bit, the
+ * resize is our own fixed-point statement of cv::resize(..., INTER_LINEAR)'s sampling positions, and the device is held BIT FOR BIT
+ * to a CPU restatement of both (tests/jpeg_oracle.py).
+ *
+ *   files         file i owns bytes file_ptr[i] .. file_ptr[i+1]-1 of bytes.
+ *   accepted      baseline sequential DCT (SOF0), 8-bit samples, Huffman coding, 8-bit quantisation tables, one component (gray) or
+ *                 three (Y, Cb, Cr) in one interleaved scan with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1, any restart
+ *                 interval, width and height in 1..16384.  APPn and COM segments are skipped; EXIF ORIENTATION IS IGNORED.
+ *   status        per image, never a failure of the call: SFMBA_IMAGE_UNSUPPORTED for a well-formed file outside that scope
+ *                 (progressive, arithmetic coding, 12-bit samples, 16-bit quantisation tables, two or four components, other
+ *                 sampling factors, several scans, a side above 16384) and never a guess at its pixels; SFMBA_IMAGE_CORRUPT for a
+ *                 file that breaks its own syntax (truncated, a segment length past the end of the file, a missing table, a
+ *                 Huffman code that is not in the table, a coefficient index past 63, a DC value outside int16, zero dimensions,
+ *                 a missing restart marker).  Such an image has no pixels (out_ptr[i+1] == out_ptr[i]) and the fields of its
+ *                 sfmba_image_info besides status are 0; the other images of the batch are decoded normally.
+ *   host          headers and entropy decoding run on the host with at most min(n_images, 16) threads and yield int16 coefficients
+ *                 in natural order plus quantisers and geometry; the device never sees file bytes.
+ *   inverse DCT   per 8 x 8 block, coefficient times quantiser, then the two-pass integer transform with CONST_BITS = 13 and
+ *                 PASS1_BITS = 2 and the constants 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172: columns
+ *                 first with DESCALE(x, 11), then rows with DESCALE(x, 18), DESCALE(x, n) = (x + (1 << (n-1))) >> n; the sample is
+ *                 clamp(v + 128, 0, 255).  All intermediates are 32-bit two's complement with wrap-around (formed unsigned).
+ *   chroma        a component is ceil(W h / hmax) x ceil(H v / vmax) samples; the MCU padding beyond that is never read.
+ *                 2x1: out[2i] = (3 in[i] + in[i-1] + 1) >> 2, out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2, the first and the last
+ *                 output of a row copy the edge sample.  2x2: s[i] = 3 near[i] + far[i] with far the row above for the upper
+ *                 output row and the row below for the lower one (at the top and bottom the component's own edge row is repeated);
+ *                 out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4, at the edges (4 s + 8) >> 4 and
+ *                 (4 s + 7) >> 4.
+ *   colour        with cb, cr centred on 128: R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ *                 G = Y + ((-22554 cb - 46802 cr + 32768) >> 16) (arithmetic shifts), each clamped to 0..255.  Three components
+ *                 come back as B, G, R interleaved (CV_8UC3), one component as it is; rows tight.
+ *   resize        one factor for both axes, f = (double)factor.  ow = lrint(w f), oh = lrint(h f) (round-half-even); inv = 1 / f.
+ *                 Per output column x (rows likewise): fx = (x + 0.5) inv - 0.5, sx = floor(fx), a = fx - sx, or a = 0 where
+ *                 sx < 0 or sx >= w - 1 with the index clamped into 0..w-1; w1 = lrint(2048 a), w0 = 2048 - w1; the second sample
+ *                 is at min(sx + 1, w - 1).  The tables are built on the host in double.  Every channel:
+ *                 out = (wy0 (wx0 p00 + wx1 p01) + wy1 (wx0 p10 + wx1 p11) + (1 << 21)) >> 22, which fits 32 bits and lies within
+ *                 1 level of the exact bilinear value.
+ *
+ * sfmba_jpeg_info: headers only (up to the start of the scan), host only, no device needed; info [n_images].  A file whose headers
+ *   are in order reports SFMBA_IMAGE_OK here even when its scan data will prove corrupt in sfmba_jpeg_decode -- except that a frame
+ *   of more than 4 blocks of 8 x 8 per byte left in the file is SFMBA_IMAGE_CORRUPT already (a block takes at least 2 bits), so no
+ *   array is ever sized from a frame that its file cannot hold.
+ * sfmba_resized_size: ow, oh of the resize rule; SFMBA_ERR_INVALID_ARG when factor is not finite and > 0 or a result lies outside
+ *   1..16384.  Host only.
+ * sfmba_jpeg_decode: info [n_images] (the final status), out_ptr [n_images + 1] (byte offsets into out), out [cap].  With
+ *   factor != 1 every image is resized before its pixels leave the device; the result equals factor = 1 followed by
+ *   sfmba_resize_images byte for byte, and info then still reports the size of the file's own image.
+ * sfmba_resize_images: image i owns bytes img_ptr[i] .. img_ptr[i+1]-1 of px, height[i] rows of width[i] * channels bytes;
+ *   channels is 1 or 3.
+ * Both device calls: host pointers in and out, synchronous; *total receives the number of bytes; SFMBA_ERR_CAPACITY (info, out_ptr
+ * and *total valid, out untouched) if cap < *total.  SFMBA_ERR_INVALID_ARG (nothing written) for a factor that is not finite and
+ * > 0 or that gives an image a side outside 1..16384 (judged from the headers, before any scan is decoded), a source side outside 1..16384, an img_ptr that does not agree with the
+ * sizes, a decreasing file_ptr.  Deterministic: a batch equals the concatenation of single-image calls (images go to the device in
+ * consecutive groups under a fixed scratch bound).  SFMBA_ABI_VERSION stays 6: adding a symbol is backward compatible.
+ */
+enum { SFMBA_IMAGE_OK = 0, SFMBA_IMAGE_UNSUPPORTED = 1, SFMBA_IMAGE_CORRUPT = 2 };
+typedef struct sfmba_image_info { int status; int width, height, channels; int h_samp, v_samp; int restart_interval; } sfmba_image_info;
+SFMBA_API int sfmba_jpeg_info(int n_images, const int64_t* file_ptr /*[n_images+1], byte offsets*/, const unsigned char* bytes,
+                sfmba_image_info* info /*[n_images]*/);
+SFMBA_API int sfmba_resized_size(int width, int height, float factor, int32_t* out_width, int32_t* out_height);
+SFMBA_API int sfmba_jpeg_decode(int device, int n_images, const int64_t* file_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* bytes, float factor, sfmba_image_info* info /*[n_images]*/, int64_t* out_ptr /*[n_images+1]*/,
+                unsigned char* out /*[cap]*/, int64_t cap, int64_t* total);
+SFMBA_API int sfmba_resize_images(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* px, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/, float factor,
+                int64_t* out_ptr /*[n_images+1]*/, unsigned char* out /*[cap]*/, int64_t cap, int64_t* total);
+
 #ifdef __cplusplus
 }
 #endif

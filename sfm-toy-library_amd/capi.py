@@ -36,6 +36,7 @@ SYMBOLS = [
     "sfmba_comm_allgather", "sfmba_problem_set_allgather", "sfmba_comm_size", "sfmba_device_warmup",
     "sfmba_match_features", "sfmba_problem_set_step_probe", "sfmba_problem_get_step_probe", "sfmba_pnp_ransac",
     "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_orb_extract", "sfmba_triangulate_pairs",
+    "sfmba_jpeg_info", "sfmba_resized_size", "sfmba_jpeg_decode", "sfmba_resize_images",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -279,6 +280,106 @@ def orb_extract(images, n_features=5000, scale_factor=1.2, n_levels=8, fast_thre
         else:
             out.append((kp[a:b].copy(), desc[a:b].copy()))
     return out
+
+
+class _ImageInfo(C.Structure):
+    _fields_ = [("status", C.c_int), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("h_samp", C.c_int), ("v_samp", C.c_int),
+                ("restart_interval", C.c_int)]
+
+
+IMAGE_STATUS = ("OK", "UNSUPPORTED", "CORRUPT")          # SFMBA_IMAGE_* by value
+
+
+def _flat_files(files):
+    blobs = [bytes(f) for f in files]
+    ptr = np.zeros(len(blobs) + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum([len(b) for b in blobs])
+    flat = np.frombuffer(b"".join(blobs) or b"\0", dtype=np.uint8).copy()
+    return ptr, flat
+
+
+def _info_dicts(info):
+    return [{k: int(getattr(i, k)) for k, _ in _ImageInfo._fields_} for i in info]
+
+
+def jpeg_info(files):
+    """sfmba_jpeg_info: the header fields of every file (bytes objects) as dicts; host only, no device needed."""
+    ptr, flat = _flat_files(files)
+    info = (_ImageInfo * max(len(files), 1))()
+    _check(lib().sfmba_jpeg_info(C.c_int(len(files)), _p(ptr, C.POINTER(C.c_int64)), flat.ctypes.data_as(C.POINTER(C.c_ubyte)), info))
+    return _info_dicts(info)[:len(files)]
+
+
+def resized_size(width, height, factor):
+    """sfmba_resized_size: (ow, oh) of the resize rule; host only."""
+    ow, oh = C.c_int32(0), C.c_int32(0)
+    _check(lib().sfmba_resized_size(C.c_int(width), C.c_int(height), C.c_float(factor), C.byref(ow), C.byref(oh)))
+    return ow.value, oh.value
+
+
+def _split_images(out, out_ptr, shapes):
+    return [None if s is None else out[int(out_ptr[i]):int(out_ptr[i + 1])].reshape(s).copy() for i, s in enumerate(shapes)]
+
+
+def jpeg_decode(files, factor=1.0, cap=None, device=0):
+    """sfmba_jpeg_decode: (info dicts, images) for a list of JPEG files (bytes objects).  An image is a uint8 array h x w (gray) or
+    h x w x 3 (B, G, R), None where the status is not OK.  cap=None asks for the size first (a call with cap 0)."""
+    n = len(files)
+    ptr, flat = _flat_files(files)
+    lp, bp = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte)
+    info = (_ImageInfo * max(n, 1))()
+    out_ptr = np.zeros(n + 1, dtype=np.int64)
+    total = C.c_int64(0)
+    cap = 0 if cap is None else int(cap)
+    for _ in range(2):
+        out = np.zeros(max(cap, 1), np.uint8)
+        rc = lib().sfmba_jpeg_decode(C.c_int(device), C.c_int(n), _p(ptr, lp), flat.ctypes.data_as(bp), C.c_float(factor), info, _p(out_ptr, lp),
+                                     out.ctypes.data_as(bp), C.c_int64(cap), C.byref(total))
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        cap = int(total.value)
+    _check(rc)
+    infos = _info_dicts(info)[:n]
+    shapes = []
+    for i, d in enumerate(infos):
+        if d["status"] != 0:
+            shapes.append(None)
+            continue
+        ow, oh = (d["width"], d["height"]) if factor == 1.0 else resized_size(d["width"], d["height"], factor)
+        shapes.append((oh, ow) if d["channels"] == 1 else (oh, ow, 3))
+    return infos, _split_images(out, out_ptr, shapes)
+
+
+def resize_images(images, factor, cap=None, device=0):
+    """sfmba_resize_images: the resized uint8 images (all h x w or all h x w x 3) of a batch."""
+    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+    kinds = {(im.ndim, im.shape[2] if im.ndim == 3 else 1) for im in imgs}
+    if len(kinds) > 1 or any(k not in ((2, 1), (3, 3)) for k in kinds):
+        raise ValueError("images must all be h x w or all be h x w x 3 uint8 arrays")
+    channels = kinds.pop()[1] if kinds else 1
+    n = len(imgs)
+    img_ptr = np.zeros(n + 1, dtype=np.int64)
+    img_ptr[1:] = np.cumsum([im.size for im in imgs])
+    flat = np.ascontiguousarray(np.concatenate([im.reshape(-1) for im in imgs]) if imgs else np.zeros(1, np.uint8))
+    wd = np.asarray([im.shape[1] for im in imgs], dtype=np.int32)
+    ht = np.asarray([im.shape[0] for im in imgs], dtype=np.int32)
+    lp, bp = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte)
+    out_ptr = np.zeros(n + 1, dtype=np.int64)
+    total = C.c_int64(0)
+    cap = 0 if cap is None else int(cap)
+    for _ in range(2):
+        out = np.zeros(max(cap, 1), np.uint8)
+        rc = lib().sfmba_resize_images(C.c_int(device), C.c_int(n), _p(img_ptr, lp), flat.ctypes.data_as(bp), _p(wd, _ip), _p(ht, _ip), C.c_int(channels),
+                                       C.c_float(factor), _p(out_ptr, lp), out.ctypes.data_as(bp), C.c_int64(cap), C.byref(total))
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        cap = int(total.value)
+    _check(rc)
+    shapes = []
+    for im in imgs:
+        ow, oh = resized_size(im.shape[1], im.shape[0], factor)
+        shapes.append((oh, ow) if channels == 1 else (oh, ow, 3))
+    return _split_images(out, out_ptr, shapes)
 
 
 class _PnpResult(C.Structure):

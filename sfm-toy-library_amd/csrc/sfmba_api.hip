@@ -9,6 +9,8 @@
 #include "homography_ransac.h"
 #include "essential_ransac.h"
 #include "orb_extract.h"
+#include "jpeg_decode.h"
+#include "jpeg_math.h"
 #include <climits>
 #include <cmath>
 
@@ -686,5 +688,86 @@ int sfmba_essential_ransac(int device, int n_images, const int64_t* img_ptr, con
     if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "essential_ransac: device allocation failed");
     if (rc) return fail(SFMBA_ERR_HIP, std::string("essential_ransac: ") + hipGetErrorString((hipError_t)rc));
     return SFMBA_OK;
+}
+// ---- reading photographs (SfM::setImagesDirectory: imread + resize) ---------------------------------------------------
+static int check_file_ptr(int n_images, const int64_t* file_ptr, const unsigned char* bytes) {
+    if (n_images < 0 || !file_ptr) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (file_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "file_ptr must not be negative");
+    for (int i = 0; i < n_images; ++i)
+        if (file_ptr[i + 1] < file_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "file_ptr not monotone");
+    if (file_ptr[n_images] > file_ptr[0] && !bytes) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    return SFMBA_OK;
+}
+
+static int image_result(int rc, const char* what, const double* tm) {
+    if (rc == 0 && tm)
+        std::fprintf(stderr, "[sfmba %s] entropy_ms %.6f upload_ms %.6f idct_ms %.6f colour_ms %.6f resize_ms %.6f download_ms %.6f groups %d\n", what,
+                     tm[JPEG_T_ENTROPY], tm[JPEG_T_UPLOAD], tm[JPEG_T_IDCT], tm[JPEG_T_COLOUR], tm[JPEG_T_RESIZE], tm[JPEG_T_DOWNLOAD], (int)tm[JPEG_T_GROUPS]);
+    if (rc == 0) return SFMBA_OK;
+    if (rc == JPEG_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, std::string(what) + ": output capacity too small");
+    if (rc == JPEG_ERR_HOST_ALLOC) return fail(SFMBA_ERR_ALLOC, std::string(what) + ": host allocation of the coefficients failed");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, std::string(what) + ": device allocation failed");
+    return fail(SFMBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString((hipError_t)rc));
+}
+
+int sfmba_jpeg_info(int n_images, const int64_t* file_ptr, const unsigned char* bytes, sfmba_image_info* info) {
+    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
+    if (n_images > 0 && !info) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    std::vector<JpegHeader> hdr;
+    jpeg_parse_batch(n_images, file_ptr, bytes, hdr);
+    for (int i = 0; i < n_images; ++i) jpeg_fill_info(hdr[(size_t)i], &info[i]);
+    return SFMBA_OK;
+}
+
+int sfmba_resized_size(int width, int height, float factor, int32_t* out_width, int32_t* out_height) {
+    if (!out_width || !out_height) return fail(SFMBA_ERR_INVALID_ARG, "NULL argument");
+    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "factor must be finite and > 0");
+    if (width < 1 || width > JPEG_MAX_SIDE || height < 1 || height > JPEG_MAX_SIDE) return fail(SFMBA_ERR_INVALID_ARG, "an image dimension lies outside 1..16384");
+    const int ow = resized_length(width, factor), oh = resized_length(height, factor);
+    if (ow == 0 || oh == 0) return fail(SFMBA_ERR_INVALID_ARG, "the factor gives the image a side outside 1..16384");
+    *out_width = ow; *out_height = oh;
+    return SFMBA_OK;
+}
+
+int sfmba_jpeg_decode(int device, int n_images, const int64_t* file_ptr, const unsigned char* bytes, float factor, sfmba_image_info* info,
+                      int64_t* out_ptr, unsigned char* out, int64_t cap, int64_t* total) {
+    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
+    if (cap < 0 || !out_ptr || !total || (n_images > 0 && !info) || (cap > 0 && !out)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "jpeg_decode: factor must be finite and > 0");
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    // SFMBA_JPEG_TIMING: one stderr line per call with the host time of the entropy decode and the HIP-event times of the phases (tools/image_io_bench.py)
+    double tm[JPEG_T_COUNT];
+    const bool timing = std::getenv("SFMBA_JPEG_TIMING") != nullptr;
+    rc = jpeg_decode(ck.kit.stream, device, n_images, file_ptr, bytes, factor, info, out_ptr, out, cap, total, timing ? tm : nullptr);
+    if (rc == JPEG_ERR_SIZE) return fail(SFMBA_ERR_INVALID_ARG, "jpeg_decode: the factor gives an image a side outside 1..16384");
+    return image_result(rc, "jpeg_decode", timing ? tm : nullptr);
+}
+
+int sfmba_resize_images(int device, int n_images, const int64_t* img_ptr, const unsigned char* px, const int32_t* width, const int32_t* height,
+                        int channels, float factor, int64_t* out_ptr, unsigned char* out, int64_t cap, int64_t* total) {
+    if (n_images < 0 || cap < 0 || !img_ptr || !out_ptr || !total || (n_images > 0 && (!width || !height)) || (cap > 0 && !out))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, "resize_images: channels must be 1 or 3");
+    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "resize_images: factor must be finite and > 0");
+    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        if (width[i] < 1 || width[i] > JPEG_MAX_SIDE || height[i] < 1 || height[i] > JPEG_MAX_SIDE)
+            return fail(SFMBA_ERR_INVALID_ARG, "resize_images: an image dimension lies outside 1..16384");
+        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
+            return fail(SFMBA_ERR_INVALID_ARG, "resize_images: img_ptr does not agree with width * height * channels");
+        if (resized_length(width[i], factor) == 0 || resized_length(height[i], factor) == 0)
+            return fail(SFMBA_ERR_INVALID_ARG, "resize_images: the factor gives an image a side outside 1..16384");
+    }
+    if (n_images > 0 && !px) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    double tm[JPEG_T_COUNT];
+    const bool timing = std::getenv("SFMBA_JPEG_TIMING") != nullptr;
+    rc = resize_images(ck.kit.stream, device, n_images, img_ptr, px, width, height, channels, factor, out_ptr, out, cap, total, timing ? tm : nullptr);
+    if (rc == JPEG_ERR_SIZE) return fail(SFMBA_ERR_INVALID_ARG, "resize_images: the factor gives an image a side outside 1..16384");
+    return image_result(rc, "resize_images", timing ? tm : nullptr);
 }
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include "SfM2DFeatureUtilities.h"
 #include "SfMBundleAdjustmentUtils.h"
 #include "SfMExport.h"
+#include "SfMImageUtilities.h"
 #include "SfMStereoUtilities.h"
 
 namespace sfmtoylib {
@@ -85,6 +86,7 @@ SfM::SfM(const float downscale) :
         mConsoleDebugLevel(LOG_INFO),
         mDownscaleFactor(downscale),
         mFeaturesGiven(false),
+        mDownscaleApplied(false),
         mCols(0), mRows(0),
         mTiming(false) {
     for (double& ms : mStageMs) ms = 0.0;
@@ -102,28 +104,52 @@ bool SfM::setImagesDirectory(const std::string& directoryPath) {
     std::vector<std::string> names;
     while (const dirent* entry = readdir(dir)) {
         const std::string ext = lowerExtension(entry->d_name);
-        if (ext == ".pgm" || ext == ".ppm") names.push_back(entry->d_name);
+        if (ext == ".pgm" || ext == ".ppm" || ext == ".jpg" || ext == ".jpeg") names.push_back(entry->d_name);
     }
     closedir(dir);
     std::sort(names.begin(), names.end());
     if (names.empty()) {
-        std::cerr << "setImagesDirectory: no .pgm / .ppm file in " << directoryPath << std::endl;
+        std::cerr << "setImagesDirectory: no .pgm / .ppm / .jpg / .jpeg file in " << directoryPath << std::endl;
         return false;
     }
+    // the PNM files are read here; the JPEG files go to the device in ONE decode call, which also applies the downscale factor
     std::vector<cv::Mat> images(names.size());
+    std::vector<size_t> pnm, jpeg;
+    std::vector<std::string> jpegPaths;
     for (size_t i = 0; i < names.size(); i++) {
         const std::string path = directoryPath + "/" + names[i];
+        const std::string ext = lowerExtension(names[i]);
+        if (ext == ".jpg" || ext == ".jpeg") {
+            jpeg.push_back(i);
+            jpegPaths.push_back(path);
+            continue;
+        }
+        pnm.push_back(i);
         if (!readPnm(path, images[i])) {
             std::cerr << "setImagesDirectory: " << path << " is not a complete binary PGM / PPM file of maxval 255" << std::endl;
             return false;
         }
+    }
+    if (!jpeg.empty()) {
+        std::vector<cv::Mat> decoded;
+        if (!SfMImageUtilities::readImages(jpegPaths, mDownscaleFactor, decoded)) return false;
+        for (size_t k = 0; k < jpeg.size(); k++) images[jpeg[k]] = decoded[k];
+    }
+    for (size_t i = 0; i < names.size(); i++)
         if (images[i].type() != images[0].type()) {
-            std::cerr << "setImagesDirectory: " << path << " is not of the kind (gray / colour) of the files before it" << std::endl;
+            std::cerr << "setImagesDirectory: " << directoryPath << "/" << names[i] << " is not of the kind (gray / colour) of the files before it" << std::endl;
             return false;
         }
+    // the PNM images in ONE resize call; at factor 1 they touch no device
+    if (!pnm.empty() && mDownscaleFactor != 1.0f) {
+        std::vector<cv::Mat> full, resized;
+        for (size_t k = 0; k < pnm.size(); k++) full.push_back(images[pnm[k]]);
+        if (!SfMImageUtilities::resizeImages(full, mDownscaleFactor, resized)) return false;
+        for (size_t k = 0; k < pnm.size(); k++) images[pnm[k]] = resized[k];
     }
     if (mConsoleDebugLevel <= LOG_DEBUG) std::cout << "[sfm] " << names.size() << " images read from " << directoryPath << std::endl;
     setImages(images);
+    mDownscaleApplied = true;
     return true;
 }
 
@@ -131,6 +157,7 @@ void SfM::setImages(const std::vector<cv::Mat>& images) {
     mImages = images;
     mImageFeatures.clear();
     mFeaturesGiven = false;
+    mDownscaleApplied = false;
     mCols = images.empty() ? 0 : images[0].cols;
     mRows = images.empty() ? 0 : images[0].rows;
 }
@@ -139,6 +166,7 @@ void SfM::setFeatures(const std::vector<Features>& imageFeatures, int cols, int 
     mImages.clear();
     mImageFeatures = imageFeatures;
     mFeaturesGiven = true;
+    mDownscaleApplied = false;
     mCols = cols;
     mRows = rows;
 }
@@ -179,8 +207,9 @@ ErrorCode SfM::runSfM() {
         std::cerr << "runSfM: there are no images and no features" << std::endl;
         return ERROR;
     }
-    if (mDownscaleFactor != 1.0f) {
-        std::cerr << "runSfM: downscale " << mDownscaleFactor << " is refused, only 1 is supported (there is no resize stage)" << std::endl;
+    if (mDownscaleFactor != 1.0f && !mDownscaleApplied) {
+        std::cerr << "runSfM: downscale " << mDownscaleFactor << " is refused: only setImagesDirectory applies a factor, images given through setImages "
+                  << "and features are taken as they are" << std::endl;
         return ERROR;
     }
     startRun(n_views);

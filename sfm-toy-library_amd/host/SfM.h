@@ -24,7 +24,11 @@
 //                 poses, SfMAssociation::mergeNewPointCloud pair by pair in that order, adjustBundle if the batch triangulated,
 //                 and the view becomes good.
 //   end           every view is done.
-// downscale != 1 is refused by runSfM (no resize kernel); there is no visual debugging.
+//   downscale     the factor of the constructor is applied by setImagesDirectory at load time, as in the reference (SfM.cpp:125-129): the
+//                 JPEG files in ONE decode call that also resizes (SfMImageUtilities::readImages), the PNM images in ONE resize call;
+//                 K then comes from the resized image 0.  Images given through setImages and features given through setFeatures are
+//                 taken as they are: runSfM refuses downscale != 1 for them (there is nothing to resize in the second case).
+// There is no visual debugging.
 // An object holds all of a run's state (the stage times of SFMBA_SFM_TIMING included): different objects may run in different
 // threads; one object is not re-entrant.
 #pragma once
@@ -57,14 +61,17 @@ public:
     virtual ~SfM();
 
     /**
-     * Binary .pgm (P5 -> CV_8U) / .ppm (P6 -> CV_8UC3, stored B, G, R) files of the directory with maxval 255, in ascending
-     * file-name order (the extension decides which files are read, in either letter case).
+     * Binary .pgm (P5 -> CV_8U) / .ppm (P6 -> CV_8UC3, stored B, G, R) files of maxval 255 and baseline .jpg / .jpeg files (one
+     * component -> CV_8U, three -> CV_8UC3; the scope is that of sfmba_jpeg_decode, EXIF orientation is ignored) of the directory, in
+     * ascending file-name order across all extensions (the extension decides which files are read, in either letter case).  The
+     * downscale factor of the constructor is applied here, on the device; PNM files at factor 1 touch no device.
      * @return true on success; false (no image kept) when the directory cannot be read, holds no such file, a file is not a P5 / P6
-     *         file of maxval 255 with all its bytes, or the files are not all of one kind.
+     *         file of maxval 255 with all its bytes or not a decodable baseline JPEG, the files are not all of one kind, or the
+     *         device fails.
      */
     bool setImagesDirectory(const std::string& directoryPath);
 
-    /** The images themselves, all CV_8U or all CV_8UC3 (there is no imread here).  Forgets features given by setFeatures. */
+    /** The images themselves, all CV_8U or all CV_8UC3, taken as they are (no downscale).  Forgets features given by setFeatures. */
     void setImages(const std::vector<cv::Mat>& images);
 
     /** Key points (+ points) and descriptors of every view and the image size: runSfM then skips the extraction. */
@@ -114,6 +121,7 @@ private:
     unsigned int              mConsoleDebugLevel;
     float                     mDownscaleFactor;
     bool                      mFeaturesGiven;
+    bool                      mDownscaleApplied; // the images came from setImagesDirectory, which applied mDownscaleFactor
     int                       mCols, mRows;      // of image 0, or as given to setFeatures
     bool                      mTiming;           // SFMBA_SFM_TIMING was set when the run began
     double                    mStageMs[T_COUNT]; // wall time per stage of the current run (all zero unless mTiming)

@@ -1,0 +1,109 @@
+// SfMImageUtilities.cpp -- host side of the image reader: flattens the files / images, calls the C ABI (include/sfmba.h,
+// sfmba_jpeg_decode, sfmba_resize_images) and rebuilds the reference's list of cv::Mat.  See SfMImageUtilities.h.
+#include "SfMImageUtilities.h"
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+
+#include "../../include/sfmba.h"
+
+namespace sfmtoylib {
+
+namespace {
+
+cv::Mat imageFromBytes(int w, int h, int channels, const unsigned char* px) {
+    cv::Mat m(h, w, channels == 3 ? CV_8UC3 : CV_8U);
+    for (int r = 0; r < h; ++r) std::memcpy(m.ptr<unsigned char>(r), px + (size_t)r * w * channels, (size_t)w * channels);
+    return m;
+}
+
+const char* const statusNames[] = { "ok", "not a baseline JPEG this reader supports", "corrupt" };
+
+}  // namespace
+
+bool SfMImageUtilities::readImages(const std::vector<std::string>& paths, float downscale, std::vector<cv::Mat>& images) {
+    images.clear();
+    const size_t n = paths.size();
+    if (n == 0) return true;
+    std::vector<int64_t> ptr(n + 1, 0), out_ptr(n + 1, 0);
+    std::vector<unsigned char> bytes;
+    for (size_t i = 0; i < n; ++i) {
+        std::ifstream in(paths[i].c_str(), std::ios::binary);
+        if (!in) { std::fprintf(stderr, "readImages: %s cannot be read\n", paths[i].c_str()); return false; }
+        bytes.insert(bytes.end(), std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+        ptr[i + 1] = (int64_t)bytes.size();
+    }
+    std::vector<sfmba_image_info> info(n);
+    std::vector<unsigned char> px;
+    int64_t cap = 0, total = 0;
+    if (sfmba_jpeg_info((int)n, ptr.data(), bytes.data(), info.data()) == SFMBA_OK)          // sizes the output: one device call in the usual case
+        for (size_t i = 0; i < n; ++i) {
+            int32_t ow = info[i].width, oh = info[i].height;
+            if (info[i].status == SFMBA_IMAGE_OK && (downscale == 1.0f || sfmba_resized_size(info[i].width, info[i].height, downscale, &ow, &oh) == SFMBA_OK))
+                cap += (int64_t)ow * oh * info[i].channels;
+        }
+    int rc = SFMBA_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        px.resize((size_t)cap + 1);
+        rc = sfmba_jpeg_decode(0, (int)n, ptr.data(), bytes.data(), downscale, info.data(), out_ptr.data(), px.data(), cap, &total);
+        if (rc == SFMBA_ERR_CAPACITY && attempt == 0) { cap = total; continue; }
+        break;
+    }
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "readImages failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return false;
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (info[i].status != SFMBA_IMAGE_OK) {
+            std::fprintf(stderr, "readImages: %s is %s\n", paths[i].c_str(), statusNames[info[i].status == SFMBA_IMAGE_UNSUPPORTED ? 1 : 2]);
+            return false;
+        }
+    images.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        int32_t ow = info[i].width, oh = info[i].height;
+        if (downscale != 1.0f && sfmba_resized_size(info[i].width, info[i].height, downscale, &ow, &oh) != SFMBA_OK) { images.clear(); return false; }
+        if (out_ptr[i + 1] - out_ptr[i] != (int64_t)ow * oh * info[i].channels) { images.clear(); return false; }
+        images.push_back(imageFromBytes(ow, oh, info[i].channels, px.data() + out_ptr[i]));
+    }
+    return true;
+}
+
+bool SfMImageUtilities::resizeImages(const std::vector<cv::Mat>& images, float downscale, std::vector<cv::Mat>& out) {
+    out.clear();
+    const size_t n = images.size();
+    if (n == 0) return true;
+    const int type = images[0].type();
+    if (type != CV_8U && type != CV_8UC3) { std::fprintf(stderr, "resizeImages: images must be CV_8U or CV_8UC3\n"); return false; }
+    const int channels = type == CV_8UC3 ? 3 : 1;
+    std::vector<int64_t> ptr(n + 1, 0), out_ptr(n + 1, 0);
+    std::vector<int32_t> width(n), height(n), ow(n), oh(n);
+    int64_t cap = 0, total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (images[i].empty() || images[i].type() != type) { std::fprintf(stderr, "resizeImages: empty image or image types differ\n"); return false; }
+        width[i] = images[i].cols; height[i] = images[i].rows;
+        ptr[i + 1] = ptr[i] + (int64_t)images[i].cols * images[i].rows * channels;
+        if (sfmba_resized_size(width[i], height[i], downscale, &ow[i], &oh[i]) != SFMBA_OK) {
+            std::fprintf(stderr, "resizeImages: factor %g is refused (%s)\n", (double)downscale, sfmba_last_error());
+            return false;
+        }
+        cap += (int64_t)ow[i] * oh[i] * channels;
+    }
+    std::vector<unsigned char> src((size_t)ptr[n]), px((size_t)cap + 1);
+    for (size_t i = 0; i < n; ++i)
+        for (int r = 0; r < images[i].rows; ++r)                           // row by row: an OpenCV matrix need not be continuous
+            std::memcpy(&src[(size_t)ptr[i] + (size_t)r * width[i] * channels], images[i].ptr<unsigned char>(r), (size_t)width[i] * channels);
+    const int rc = sfmba_resize_images(0, (int)n, ptr.data(), src.data(), width.data(), height.data(), channels, downscale, out_ptr.data(), px.data(), cap,
+                                       &total);
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "resizeImages failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return false;
+    }
+    out.reserve(n);
+    for (size_t i = 0; i < n; ++i) out.push_back(imageFromBytes(ow[i], oh[i], channels, px.data() + out_ptr[i]));
+    return true;
+}
+
+}  // namespace sfmtoylib

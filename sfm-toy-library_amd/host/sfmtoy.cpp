@@ -1,0 +1,69 @@
+// sfmtoy.cpp -- the command-line program of the reference (main.cpp) over sfmtoylib::SfM of this directory: read the images of a
+// directory, run the pipeline on the MI355X, write <prefix>_points.ply and <prefix>_cameras.ply.  The arguments are parsed here
+// (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <string>
+
+#include "SfM.h"
+
+using namespace sfmtoylib;
+
+namespace {
+
+void usage(std::ostream& os, const char* program) {
+    os << "usage: " << program << " [options] <input-directory>\n"
+       << "  -h, --help                   this text\n"
+       << "  -p, --input-directory DIR    directory of .jpg / .jpeg / .pgm / .ppm images (also as the positional argument)\n"
+       << "  -s, --downscale F            factor applied to every image at load time (default 1)\n"
+       << "  -d, --console-debug N        console log level, 0 = trace .. 4 = error (default 2)\n"
+       << "  -o, --output-prefix PREFIX   PREFIX_points.ply and PREFIX_cameras.ply (default output)\n"
+       << "  -v, --visual-debug N         accepted and ignored: there is no visual debugging\n";
+}
+
+// "--name=value" or "-n value" / "--name value": true when argv[i] is this option, with the value in `value` (i then stands on
+// the last argument consumed); `missing` is set when the value is absent
+bool option(int argc, char** argv, int& i, const char* brief, const char* full, std::string& value, bool& missing) {
+    const std::string arg = argv[i], prefix = std::string(full) + "=";
+    if (arg.compare(0, prefix.size(), prefix) == 0) { value = arg.substr(prefix.size()); return true; }
+    if (arg != brief && arg != full) return false;
+    if (i + 1 >= argc) { missing = true; return true; }
+    value = argv[++i];
+    return true;
+}
+
+bool number(const std::string& text, double& value) {
+    char* end = nullptr;
+    value = std::strtod(text.c_str(), &end);
+    return !text.empty() && end && *end == '\0';
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    std::string directory, prefix = "output", text;
+    double downscale = 1.0, level = LOG_INFO, ignored = 0.0;
+    bool have_directory = false;
+    for (int i = 1; i < argc; ++i) {
+        bool missing = false, bad = false;
+        const std::string arg = argv[i];
+        if (arg == "-h" || arg == "--help") { usage(std::cout, argv[0]); return 0; }
+        if (option(argc, argv, i, "-p", "--input-directory", text, missing)) { directory = text; have_directory = !missing; }
+        else if (option(argc, argv, i, "-o", "--output-prefix", text, missing)) prefix = text;
+        else if (option(argc, argv, i, "-s", "--downscale", text, missing)) bad = !missing && (!number(text, downscale) || !(downscale > 0.0));
+        else if (option(argc, argv, i, "-d", "--console-debug", text, missing)) bad = !missing && (!number(text, level) || level < 0.0 || level > 4.0);
+        else if (option(argc, argv, i, "-v", "--visual-debug", text, missing)) bad = !missing && !number(text, ignored);
+        else if (arg.size() > 1 && arg[0] == '-') { std::cerr << argv[0] << ": unknown option " << arg << "\n"; usage(std::cerr, argv[0]); return 2; }
+        else if (!have_directory) { directory = arg; have_directory = true; }
+        else { std::cerr << argv[0] << ": more than one input directory\n"; usage(std::cerr, argv[0]); return 2; }
+        if (missing || bad) { std::cerr << argv[0] << ": " << arg << (missing ? " needs a value\n" : " has a value that cannot be used\n"); usage(std::cerr, argv[0]); return 2; }
+    }
+    if (!have_directory || directory.empty()) { std::cerr << argv[0] << ": no input directory\n"; usage(std::cerr, argv[0]); return 2; }
+
+    SfM sfm((float)downscale);
+    sfm.setConsoleDebugLevel((unsigned int)level);
+    if (!sfm.setImagesDirectory(directory)) return 1;
+    if (sfm.runSfM() != OKAY) return 1;
+    return sfm.saveCloudAndCamerasToPLY(prefix) ? 0 : 1;
+}

@@ -11,6 +11,7 @@
 #include "SfMExport.h"
 #include "SfM2DFeatureUtilities.h"
 #include "SfM.h"
+#include "SfMImageUtilities.h"
 
 extern "C" __attribute__((visibility("default")))
 void sfmba_shim_adjust_bundle(int n_views, float* poses /*[n_views][12]*/, float* K /*[9]*/, int n_pts, float* points /*[n_pts][3]*/,
@@ -458,6 +459,41 @@ int64_t sfmba_shim_extract_features_batch(int n_images, const int64_t* img_ptr, 
     return at;
 }
 
+namespace {
+// What a finished run leaves, flattened as sfmba_shim_run_sfm documents it.
+int flattenRun(sfmtoylib::SfM& sfm, sfmtoylib::ErrorCode code, int n_views, float* poses, float* K, unsigned char* done, unsigned char* good, int* n_added,
+               int32_t* added_view, unsigned char* added_posed, int64_t* added_cloud, int64_t cap_pts, int64_t cap_views, int64_t* n_pts, float* xyz,
+               int64_t* view_ptr, int32_t* view_idx, int32_t* feat_idx, const char* ply_prefix) {
+    using namespace sfmtoylib;
+    *n_added = 0;
+    *n_pts = 0;
+    if (code != OKAY) return (int)code;
+    for (int v = 0; v < n_views; ++v) {
+        for (int e = 0; e < 12; ++e) poses[12 * v + e] = sfm.getCameraPoses()[v].val[e];
+        done[v] = sfm.getDoneViews().count(v) ? 1 : 0;
+        good[v] = sfm.getGoodViews().count(v) ? 1 : 0;
+    }
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) K[3 * r + c] = sfm.getIntrinsics().K.at<float>(r, c);
+    for (const SfM::AddedView& a : sfm.getAddedViews()) {
+        if (*n_added >= n_views) return -2;
+        added_view[*n_added] = a.view; added_posed[*n_added] = a.posed ? 1 : 0; added_cloud[*n_added] = (int64_t)a.cloudSize;
+        ++*n_added;
+    }
+    const PointCloud& cloud = sfm.getPointCloud();
+    if ((int64_t)cloud.size() > cap_pts) return -2;
+    *n_pts = (int64_t)cloud.size();
+    int64_t o = 0;
+    for (size_t i = 0; i < cloud.size(); ++i) {
+        xyz[3 * i] = cloud[i].p.x; xyz[3 * i + 1] = cloud[i].p.y; xyz[3 * i + 2] = cloud[i].p.z;
+        view_ptr[i] = o;
+        for (const auto& kv : cloud[i].originatingViews) { if (o >= cap_views) return -2; view_idx[o] = kv.first; feat_idx[o] = kv.second; ++o; }
+    }
+    view_ptr[cloud.size()] = o;
+    if (ply_prefix && !sfm.saveCloudAndCamerasToPLY(ply_prefix)) return -3;
+    return 0;
+}
+}  // namespace
+
 // Flat-array driver of sfmtoylib::SfM (tests/test_gpu_sfm_pipeline.py): one run from images (channels = 1 or 3: image i owns bytes
 // img_ptr[i] .. img_ptr[i+1]-1 of px, w / h per image) or from features (channels = 0: view i owns rows kp_ptr[i] .. kp_ptr[i+1]-1 of
 // kp_xy [..][2] and desc [..][32]; cols / rows = the image size).  Back come the poses [n_views][12], K [9], the done / good flags
@@ -486,33 +522,8 @@ int sfmba_shim_run_sfm(float downscale, int n_views, int channels, const int64_t
         for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
         sfm.setImages(images);
     }
-    const ErrorCode code = sfm.runSfM();
-    *n_added = 0;
-    *n_pts = 0;
-    if (code != OKAY) return (int)code;
-    for (int v = 0; v < n_views; ++v) {
-        for (int e = 0; e < 12; ++e) poses[12 * v + e] = sfm.getCameraPoses()[v].val[e];
-        done[v] = sfm.getDoneViews().count(v) ? 1 : 0;
-        good[v] = sfm.getGoodViews().count(v) ? 1 : 0;
-    }
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) K[3 * r + c] = sfm.getIntrinsics().K.at<float>(r, c);
-    for (const SfM::AddedView& a : sfm.getAddedViews()) {
-        if (*n_added >= n_views) return -2;
-        added_view[*n_added] = a.view; added_posed[*n_added] = a.posed ? 1 : 0; added_cloud[*n_added] = (int64_t)a.cloudSize;
-        ++*n_added;
-    }
-    const PointCloud& cloud = sfm.getPointCloud();
-    if ((int64_t)cloud.size() > cap_pts) return -2;
-    *n_pts = (int64_t)cloud.size();
-    int64_t o = 0;
-    for (size_t i = 0; i < cloud.size(); ++i) {
-        xyz[3 * i] = cloud[i].p.x; xyz[3 * i + 1] = cloud[i].p.y; xyz[3 * i + 2] = cloud[i].p.z;
-        view_ptr[i] = o;
-        for (const auto& kv : cloud[i].originatingViews) { if (o >= cap_views) return -2; view_idx[o] = kv.first; feat_idx[o] = kv.second; ++o; }
-    }
-    view_ptr[cloud.size()] = o;
-    if (ply_prefix && !sfm.saveCloudAndCamerasToPLY(ply_prefix)) return -3;
-    return 0;
+    return flattenRun(sfm, sfm.runSfM(), n_views, poses, K, done, good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts, xyz,
+                      view_ptr, view_idx, feat_idx, ply_prefix);
 }
 
 // Flat-array driver of sfmtoylib::SfM::setImagesDirectory (tests/test_sfm_scene_cpu.py; no device involved): the images come back
@@ -536,4 +547,76 @@ int sfmba_shim_read_images_directory(const char* path, int cap_images, int64_t c
         for (int r = 0; r < images[i].rows; ++r, at += row) std::memcpy(px + at, images[i].ptr<unsigned char>(r), (size_t)row);
     }
     return (int)images.size();
+}
+
+namespace {
+// images one after the other in px (cap bytes), w / h [cap_images]; the number of images, -2 if a capacity is too small
+int flattenImages(const std::vector<cv::Mat>& images, int cap_images, int64_t cap, int32_t* w, int32_t* h, int* channels, unsigned char* px) {
+    if ((int)images.size() > cap_images) return -2;
+    int64_t at = 0;
+    for (size_t i = 0; i < images.size(); ++i) {
+        const int ch = images[i].type() == CV_8UC3 ? 3 : 1;
+        const int64_t row = (int64_t)images[i].cols * ch;
+        if (at + row * images[i].rows > cap) return -2;
+        *channels = ch;
+        w[i] = images[i].cols; h[i] = images[i].rows;
+        for (int r = 0; r < images[i].rows; ++r, at += row) std::memcpy(px + at, images[i].ptr<unsigned char>(r), (size_t)row);
+    }
+    return (int)images.size();
+}
+}  // namespace
+
+// Flat-array driver of sfmtoylib::SfMImageUtilities::readImages (tests/test_gpu_image_io.py): n_paths file paths, one downscale
+// factor.  The images come back as sfmba_shim_read_images_directory returns them.  Returns the number of images, -1 when the call
+// reported failure, -2 if a capacity is too small.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_read_images(int n_paths, const char* const* paths, float downscale, int cap_images, int64_t cap, int32_t* w, int32_t* h, int* channels,
+                           unsigned char* px) {
+    using namespace sfmtoylib;
+    std::vector<cv::Mat> images;
+    if (!SfMImageUtilities::readImages(std::vector<std::string>(paths, paths + n_paths), downscale, images)) return -1;
+    return flattenImages(images, cap_images, cap, w, h, channels, px);
+}
+
+// Flat-array driver of sfmtoylib::SfMImageUtilities::resizeImages: image i owns bytes img_ptr[i] .. img_ptr[i+1]-1 of src.  Returns as
+// sfmba_shim_read_images.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_resize_images(int n_images, const int64_t* img_ptr, const unsigned char* src, const int32_t* sw, const int32_t* sh, int src_channels,
+                             float downscale, int cap_images, int64_t cap, int32_t* w, int32_t* h, int* channels, unsigned char* px) {
+    using namespace sfmtoylib;
+    std::vector<cv::Mat> images, out;
+    for (int i = 0; i < n_images; ++i) images.push_back(buildImage(sw[i], sh[i], src_channels, src + img_ptr[i]));
+    if (!SfMImageUtilities::resizeImages(images, downscale, out)) return -1;
+    return flattenImages(out, cap_images, cap, w, h, channels, px);
+}
+
+// sfmba_shim_read_images_directory with the downscale factor of the constructor: SfM(downscale).setImagesDirectory(path).
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_read_images_directory_scaled(const char* path, float downscale, int cap_images, int64_t cap, int32_t* w, int32_t* h, int* channels,
+                                            unsigned char* px) {
+    using namespace sfmtoylib;
+    SfM sfm(downscale);
+    sfm.setConsoleDebugLevel(LOG_ERROR);
+    if (!sfm.setImagesDirectory(path)) return -1;
+    return flattenImages(sfm.getImages(), cap_images, cap, w, h, channels, px);
+}
+
+// sfmba_shim_run_sfm starting from a directory: SfM(downscale), setImagesDirectory(path), runSfM().  *n_views_out receives the number
+// of images read (the per-view outputs hold cap_view_count entries).  Returns as sfmba_shim_run_sfm, -1 when the directory could
+// not be read, -2 also when it holds more than cap_view_count images.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_directory(const char* path, float downscale, int debug_level, int cap_view_count, int* n_views_out, float* poses, float* K,
+                                 unsigned char* done, unsigned char* good, int* n_added, int32_t* added_view, unsigned char* added_posed,
+                                 int64_t* added_cloud, int64_t cap_pts, int64_t cap_views, int64_t* n_pts, float* xyz, int64_t* view_ptr,
+                                 int32_t* view_idx, int32_t* feat_idx, const char* ply_prefix) {
+    using namespace sfmtoylib;
+    SfM sfm(downscale);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    *n_views_out = 0;
+    if (!sfm.setImagesDirectory(path)) return -1;
+    const int n_views = (int)sfm.getImages().size();
+    *n_views_out = n_views;
+    if (n_views > cap_view_count) return -2;
+    return flattenRun(sfm, sfm.runSfM(), n_views, poses, K, done, good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts, xyz,
+                      view_ptr, view_idx, feat_idx, ply_prefix);
 }
