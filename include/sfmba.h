@@ -879,6 +879,60 @@ SFMBA_API int sfmba_resize_images(int device, int n_images, const int64_t* img_p
                 const unsigned char* px, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/, float factor,
                 int64_t* out_ptr /*[n_images+1]*/, unsigned char* out /*[cap]*/, int64_t cap, int64_t* total);
 
+/* ---- reading PNG files: inflate on the host, unfilter and unpack on the device (SfM::setImagesDirectory) --------------------------
+ * The reference's setImagesDirectory takes "jpg and png" (SfMToyLib/SfM.h, SfM.cpp:98-139).  Call conventions, status values, groups,
+ * SFMBA_ERR_CAPACITY and SFMBA_ERR_INVALID_ARG are exactly those of sfmba_jpeg_info / sfmba_jpeg_decode above; the resize is the same
+ * kernel and tables.  THE CONTRACT IS INTEGER-EXACT, our own statement, and the device is held BIT FOR BIT to a CPU restatement
+ * (tests/png_oracle.py); it equals Pillow's decode (convert("L" / "RGB"), >> 8 for 16-bit gray) for all 15 accepted pairs.
+ *
+ *   accepted      colour type 0 at depth 1, 2, 4, 8, 16; 2 at 8, 16; 3 at 1, 2, 4, 8; 4 at 8, 16; 6 at 8, 16; compression 0, filter
+ *                 method 0, no interlace, width and height in 1..16384; any number of IDAT chunks, consecutive.
+ *   chunks        every chunk's CRC is checked; ancillary chunks (tRNS, gAMA, sRGB, tEXt, ...) are skipped: NO GAMMA AND NO
+ *                 TRANSPARENCY PROCESSING.  Bytes after IEND, and bytes of the zlib stream after its Adler-32, are ignored.
+ *   status        per image, never a failure of the call.  SFMBA_IMAGE_UNSUPPORTED for a well-formed file outside that scope: Adam7
+ *                 interlace, a side above 16384, a critical chunk other than IHDR, PLTE, IDAT, IEND.  SFMBA_IMAGE_CORRUPT for a bad
+ *                 signature, a bad CRC, a chunk length past the end of the file, IHDR missing, not first, repeated or of wrong
+ *                 length, an illegal depth / colour type pair, a compression, filter or interlace method that does not exist, zero
+ *                 dimensions, colour type 3 without PLTE before IDAT, a PLTE that is empty, repeated, placed after IDAT, not a
+ *                 multiple of 3 long or of more than 256 entries, no IDAT, IDAT chunks that are not consecutive, IEND missing; a zlib
+ *                 header that is not deflate with a window of at most 32 K, that names a preset dictionary or whose check bits are
+ *                 wrong; an invalid deflate stream (reserved block type, stored-block length check, an over-subscribed or incomplete
+ *                 code -- a single code of length 1 and, for distances, no code at all are complete enough, as in zlib --, a code not
+ *                 in the table, a distance before the start of the output, input that ends early); an Adler-32 mismatch; an inflated
+ *                 length other than exactly height x (1 + rowbytes); a filter-type byte above 4 (checked by the host on the inflated
+ *                 stream).  Such an image has no pixels and the fields of its sfmba_png_info besides status are 0; the other images
+ *                 of the batch are decoded normally.
+ *   size gate     an image whose height x (1 + rowbytes) exceeds 1032 x the total of IDAT bytes + 64 is SFMBA_IMAGE_CORRUPT before
+ *                 anything is sized from it: a deflate stream cannot expand further.
+ *   host          chunk walk, CRC-32, zlib wrapper and the project's own inflate (stored, fixed and dynamic blocks, table-driven,
+ *                 into a buffer of exactly the expected size) run on the host with at most min(n_images, 16) threads; the device
+ *                 receives the inflated scanline stream, the palette and the geometry, never file bytes.
+ *   unfilter      rowbytes = ceil(width x samples x depth / 8), bpp = max(1, samples x depth / 8).  For byte x of a row: a = the
+ *                 reconstructed byte at x - bpp (0 when x < bpp), b = the reconstructed byte above (0 in row 0), c = the byte above
+ *                 at x - bpp (0 when either is outside).  Predictors: None 0, Sub a, Up b, Average (a + b) >> 1 on the 9-bit sum,
+ *                 Paeth with p = a + b - c, pa = |p - a|, pb = |p - b|, pc = |p - c|: a if pa <= pb and pa <= pc, else b if
+ *                 pb <= pc, else c.  The result is (filtered + predictor) & 255.
+ *   pixels        depth 16 keeps the high byte; depth 1, 2, 4 gray scales by 255, 85, 17, packed samples MSB first; a palette index
+ *                 looks up PLTE, an index at or past its length gives (0, 0, 0); alpha is dropped, not blended.  Colour types 0 and 4
+ *                 come back as one channel (CV_8U), types 2, 3 and 6 as B, G, R interleaved (CV_8UC3); rows tight.
+ *
+ * sfmba_png_info: the chunk walk only (signature, CRCs, IHDR, PLTE, the IDAT list, IEND, the size gate), host only, no device needed;
+ *   info [n_images].  A file whose chunks are in order reports SFMBA_IMAGE_OK here even when its zlib stream will prove corrupt in
+ *   sfmba_png_decode.  channels is the number of OUTPUT channels (1 or 3).
+ * sfmba_png_decode: as sfmba_jpeg_decode -- info [n_images] (the final status), out_ptr [n_images + 1], out [cap]; factor != 1 resizes
+ *   before the pixels leave the device and equals factor = 1 followed by sfmba_resize_images byte for byte; a factor that gives an
+ *   image a side outside 1..16384 is SFMBA_ERR_INVALID_ARG, judged from IHDR alone before anything is inflated.  A batch equals the
+ *   concatenation of single-image calls.  SFMBA_ABI_VERSION stays 6: adding a symbol is backward compatible.
+ */
+/* The struct and the first function share their name, which a typedef cannot do in C: the struct is a TAG only, written
+ * `struct sfmba_png_info` wherever it is meant. */
+struct sfmba_png_info { int status; int width, height, channels; int bit_depth, colour_type, interlace; };
+SFMBA_API int sfmba_png_info(int n_images, const int64_t* file_ptr /*[n_images+1], byte offsets*/, const unsigned char* bytes,
+                struct sfmba_png_info* info /*[n_images]*/);
+SFMBA_API int sfmba_png_decode(int device, int n_images, const int64_t* file_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* bytes, float factor, struct sfmba_png_info* info /*[n_images]*/, int64_t* out_ptr /*[n_images+1]*/,
+                unsigned char* out /*[cap]*/, int64_t cap, int64_t* total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ SYMBOLS = [
     "sfmba_match_features", "sfmba_problem_set_step_probe", "sfmba_problem_get_step_probe", "sfmba_pnp_ransac",
     "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_orb_extract", "sfmba_triangulate_pairs",
     "sfmba_jpeg_info", "sfmba_resized_size", "sfmba_jpeg_decode", "sfmba_resize_images",
+    "sfmba_png_info", "sfmba_png_decode",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -380,6 +381,52 @@ def resize_images(images, factor, cap=None, device=0):
         ow, oh = resized_size(im.shape[1], im.shape[0], factor)
         shapes.append((oh, ow) if channels == 1 else (oh, ow, 3))
     return _split_images(out, out_ptr, shapes)
+
+
+class _PngInfo(C.Structure):
+    _fields_ = [("status", C.c_int), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("bit_depth", C.c_int), ("colour_type", C.c_int),
+                ("interlace", C.c_int)]
+
+
+def _png_info_dicts(info):
+    return [{k: int(getattr(i, k)) for k, _ in _PngInfo._fields_} for i in info]
+
+
+def png_info(files):
+    """sfmba_png_info: the chunk walk of every file (bytes objects) as dicts; host only, no device needed."""
+    ptr, flat = _flat_files(files)
+    info = (_PngInfo * max(len(files), 1))()
+    _check(lib().sfmba_png_info(C.c_int(len(files)), _p(ptr, C.POINTER(C.c_int64)), flat.ctypes.data_as(C.POINTER(C.c_ubyte)), info))
+    return _png_info_dicts(info)[:len(files)]
+
+
+def png_decode(files, factor=1.0, cap=None, device=0):
+    """sfmba_png_decode: (info dicts, images) for a list of PNG files (bytes objects).  An image is a uint8 array h x w (colour types 0
+    and 4) or h x w x 3 (B, G, R), None where the status is not OK.  cap=None asks for the size first (a call with cap 0)."""
+    n = len(files)
+    ptr, flat = _flat_files(files)
+    lp, bp = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte)
+    info = (_PngInfo * max(n, 1))()
+    out_ptr = np.zeros(n + 1, dtype=np.int64)
+    total = C.c_int64(0)
+    cap = 0 if cap is None else int(cap)
+    for _ in range(2):
+        out = np.zeros(max(cap, 1), np.uint8)
+        rc = lib().sfmba_png_decode(C.c_int(device), C.c_int(n), _p(ptr, lp), flat.ctypes.data_as(bp), C.c_float(factor), info, _p(out_ptr, lp),
+                                    out.ctypes.data_as(bp), C.c_int64(cap), C.byref(total))
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        cap = int(total.value)
+    _check(rc)
+    infos = _png_info_dicts(info)[:n]
+    shapes = []
+    for d in infos:
+        if d["status"] != 0:
+            shapes.append(None)
+            continue
+        ow, oh = (d["width"], d["height"]) if factor == 1.0 else resized_size(d["width"], d["height"], factor)
+        shapes.append((oh, ow) if d["channels"] == 1 else (oh, ow, 3))
+    return infos, _split_images(out, out_ptr, shapes)
 
 
 class _PnpResult(C.Structure):

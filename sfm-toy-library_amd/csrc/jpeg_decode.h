@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/sfmba.h"
 #include "jpeg_entropy.h"
 
@@ -30,6 +32,39 @@ int jpeg_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr
 int resize_images(hipStream_t s, int device, int n_images, const int64_t* img_ptr, const unsigned char* px, const int32_t* width,
                   const int32_t* height, int channels, float factor, int64_t* out_ptr, unsigned char* out, int64_t cap, int64_t* total,
                   double* timing);
+
+// ---- shared with the PNG reader (png_decode.hip), which ends in the same resize ------------------------------------------------------
+// HIP-event time per phase, summed; inert without a timing array
+struct PhaseTimer {
+    hipStream_t s;
+    bool on;
+    std::vector<hipEvent_t> ev;
+    std::vector<int> phase;
+    void begin(int p) { if (on) { mark(); phase.push_back(p); } }
+    void end() { if (on) mark(); }
+    void mark() { hipEvent_t e = nullptr; if (hipEventCreate(&e) == hipSuccess) (void)hipEventRecord(e, s); ev.push_back(e); }
+    void collect(double* t) {
+        for (size_t i = 0; i < phase.size(); ++i) {
+            float ms = 0.f;
+            if (ev[2 * i] && ev[2 * i + 1] && hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) == hipSuccess) t[phase[i]] += ms;
+        }
+    }
+    ~PhaseTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+// What the resize of one image of a group needs.
+struct ResizeJob {
+    int w, h, ow, oh, channels;
+    long long src;              // first byte in the device source region (a multiple of 4)
+};
+
+// device bytes launch_resize allocates for one job
+long long resize_scratch(const ResizeJob& j);
+// Tables up, one k_resize launch over the jobs (the upload goes to phase JPEG_T_UPLOAD, the kernel to JPEG_T_RESIZE): *d_dst
+// receives the destination region, dst_off [jobs] the first byte of each result.  Returns 0 or a hipError_t; `s` is drained.
+class DeviceArena;
+int launch_resize(hipStream_t s, DeviceArena& arena, PhaseTimer& tm, const std::vector<ResizeJob>& jobs, float factor, const unsigned char* d_src,
+                  unsigned char** d_dst, std::vector<long long>& dst_off);
 
 // the header fields of sfmba_image_info (host only)
 void jpeg_fill_info(const JpegHeader& h, sfmba_image_info* info);

@@ -169,29 +169,7 @@ __global__ __launch_bounds__(LANES) void k_resize(const ResizeImage* __restrict_
 long long align4(long long n) { return (n + 3) & ~3ll; }
 unsigned grid_quads(long long n) { return (unsigned)((n + 4 * LANES - 1) / (4 * LANES)); }
 
-// HIP-event time per phase, summed; inert without a timing array
-struct PhaseTimer {
-    hipStream_t s;
-    bool on;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> phase;
-    void begin(int p) { if (on) { mark(); phase.push_back(p); } }
-    void end() { if (on) mark(); }
-    void mark() { hipEvent_t e = nullptr; if (hipEventCreate(&e) == hipSuccess) (void)hipEventRecord(e, s); ev.push_back(e); }
-    void collect(double* t) {
-        for (size_t i = 0; i < phase.size(); ++i) {
-            float ms = 0.f;
-            if (ev[2 * i] && ev[2 * i + 1] && hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) == hipSuccess) t[phase[i]] += ms;
-        }
-    }
-    ~PhaseTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-};
-
-// What the resize of one image of a group needs.
-struct ResizeJob {
-    int w, h, ow, oh, channels;
-    long long src;              // first byte in the device source region
-};
+}  // namespace
 
 long long resize_scratch(const ResizeJob& j) { return align4((long long)j.ow * j.oh * j.channels) + 8ll * (j.ow + j.oh); }
 
@@ -233,6 +211,8 @@ int launch_resize(hipStream_t s, DeviceArena& arena, PhaseTimer& tm, const std::
     JPEG_TRY(hipStreamSynchronize(s));                         // the host tables leave scope here
     return 0;
 }
+
+namespace {
 
 double now_ms() { return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 

@@ -1,12 +1,11 @@
 // jpeg_entropy.cpp -- see jpeg_entropy.h: header parse and Huffman decode of baseline JPEG files on the host.
 #include "jpeg_entropy.h"
+#include "host_pool.h"
 
 #include <algorithm>
 #include <atomic>
 #include <cstring>
 #include <new>
-#include <system_error>
-#include <thread>
 
 namespace sfmba {
 
@@ -282,31 +281,20 @@ bool jpeg_scan_batch(int n_images, const int64_t* file_ptr, const unsigned char*
                      std::vector<std::vector<int16_t> >& coef) {
     coef.assign((size_t)std::max(n_images, 0), std::vector<int16_t>());
     if (n_images <= 0) return true;
-    std::atomic<int> next(0);
     std::atomic<bool> alloc_failed(false);
-    auto work = [&]() {
-        for (int i = next.fetch_add(1); i < n_images; i = next.fetch_add(1)) {
-            JpegHeader& h = headers[(size_t)i];
-            if (h.status != JPEG_OK) continue;
-            std::vector<int16_t>& c = coef[(size_t)i];
-            try {
-                c.resize(64 * (size_t)h.blocks);
-            } catch (const std::bad_alloc&) {                  // nothing may leave a worker thread
-                alloc_failed = true;
-                continue;
-            }
-            h.status = jpeg_decode_scan(bytes + file_ptr[i], (size_t)(file_ptr[i + 1] - file_ptr[i]), h, c.data());
-            if (h.status != JPEG_OK) std::vector<int16_t>().swap(c);
+    host_pool_for(n_images, max_threads, [&](int i) {
+        JpegHeader& h = headers[(size_t)i];
+        if (h.status != JPEG_OK) return;
+        std::vector<int16_t>& c = coef[(size_t)i];
+        try {
+            c.resize(64 * (size_t)h.blocks);
+        } catch (const std::bad_alloc&) {                  // nothing may leave a worker thread
+            alloc_failed = true;
+            return;
         }
-    };
-    const int n_threads = std::max(1, std::min(n_images, std::min(max_threads, 16)));
-    std::vector<std::thread> pool;
-    try {
-        for (int t = 1; t < n_threads; ++t) pool.emplace_back(work);
-    } catch (const std::system_error&) {                       // fewer threads than asked for: the rest of the work is done here
-    }
-    work();
-    for (std::thread& t : pool) t.join();
+        h.status = jpeg_decode_scan(bytes + file_ptr[i], (size_t)(file_ptr[i + 1] - file_ptr[i]), h, c.data());
+        if (h.status != JPEG_OK) std::vector<int16_t>().swap(c);
+    });
     return !alloc_failed;
 }
 

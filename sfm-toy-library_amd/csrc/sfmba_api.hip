@@ -11,6 +11,7 @@
 #include "orb_extract.h"
 #include "jpeg_decode.h"
 #include "jpeg_math.h"
+#include "png_decode.h"
 #include <climits>
 #include <cmath>
 
@@ -705,7 +706,7 @@ static int image_result(int rc, const char* what, const double* tm) {
                      tm[JPEG_T_ENTROPY], tm[JPEG_T_UPLOAD], tm[JPEG_T_IDCT], tm[JPEG_T_COLOUR], tm[JPEG_T_RESIZE], tm[JPEG_T_DOWNLOAD], (int)tm[JPEG_T_GROUPS]);
     if (rc == 0) return SFMBA_OK;
     if (rc == JPEG_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, std::string(what) + ": output capacity too small");
-    if (rc == JPEG_ERR_HOST_ALLOC) return fail(SFMBA_ERR_ALLOC, std::string(what) + ": host allocation of the coefficients failed");
+    if (rc == JPEG_ERR_HOST_ALLOC) return fail(SFMBA_ERR_ALLOC, std::string(what) + ": host allocation failed");
     if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, std::string(what) + ": device allocation failed");
     return fail(SFMBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString((hipError_t)rc));
 }
@@ -769,5 +770,33 @@ int sfmba_resize_images(int device, int n_images, const int64_t* img_ptr, const 
     rc = resize_images(ck.kit.stream, device, n_images, img_ptr, px, width, height, channels, factor, out_ptr, out, cap, total, timing ? tm : nullptr);
     if (rc == JPEG_ERR_SIZE) return fail(SFMBA_ERR_INVALID_ARG, "resize_images: the factor gives an image a side outside 1..16384");
     return image_result(rc, "resize_images", timing ? tm : nullptr);
+}
+
+int sfmba_png_info(int n_images, const int64_t* file_ptr, const unsigned char* bytes, struct sfmba_png_info* info) {
+    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
+    if (n_images > 0 && !info) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    std::vector<PngHeader> hdr;
+    png_parse_batch(n_images, file_ptr, bytes, hdr);
+    for (int i = 0; i < n_images; ++i) png_fill_info(hdr[(size_t)i], &info[i]);
+    return SFMBA_OK;
+}
+
+int sfmba_png_decode(int device, int n_images, const int64_t* file_ptr, const unsigned char* bytes, float factor, struct sfmba_png_info* info,
+                     int64_t* out_ptr, unsigned char* out, int64_t cap, int64_t* total) {
+    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
+    if (cap < 0 || !out_ptr || !total || (n_images > 0 && !info) || (cap > 0 && !out)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "png_decode: factor must be finite and > 0");
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    // SFMBA_PNG_TIMING: one stderr line per call with the host time of the inflate and the HIP-event times of the phases (tools/image_io_bench.py)
+    double tm[PNG_T_COUNT];
+    const bool timing = std::getenv("SFMBA_PNG_TIMING") != nullptr;
+    rc = png_decode(ck.kit.stream, device, n_images, file_ptr, bytes, factor, info, out_ptr, out, cap, total, timing ? tm : nullptr);
+    if (rc == JPEG_ERR_SIZE) return fail(SFMBA_ERR_INVALID_ARG, "png_decode: the factor gives an image a side outside 1..16384");
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba png_decode] inflate_ms %.6f upload_ms %.6f unfilter_ms %.6f pixels_ms %.6f resize_ms %.6f download_ms %.6f groups %d\n",
+                     tm[PNG_T_INFLATE], tm[PNG_T_UPLOAD], tm[PNG_T_UNFILTER], tm[PNG_T_PIXELS], tm[PNG_T_RESIZE], tm[PNG_T_DOWNLOAD], (int)tm[PNG_T_GROUPS]);
+    return image_result(rc, "png_decode", nullptr);
 }
 }  // extern "C"

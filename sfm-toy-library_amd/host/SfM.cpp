@@ -104,22 +104,23 @@ bool SfM::setImagesDirectory(const std::string& directoryPath) {
     std::vector<std::string> names;
     while (const dirent* entry = readdir(dir)) {
         const std::string ext = lowerExtension(entry->d_name);
-        if (ext == ".pgm" || ext == ".ppm" || ext == ".jpg" || ext == ".jpeg") names.push_back(entry->d_name);
+        if (ext == ".pgm" || ext == ".ppm" || ext == ".jpg" || ext == ".jpeg" || ext == ".png") names.push_back(entry->d_name);
     }
     closedir(dir);
     std::sort(names.begin(), names.end());
     if (names.empty()) {
-        std::cerr << "setImagesDirectory: no .pgm / .ppm / .jpg / .jpeg file in " << directoryPath << std::endl;
+        std::cerr << "setImagesDirectory: no .pgm / .ppm / .jpg / .jpeg / .png file in " << directoryPath << std::endl;
         return false;
     }
-    // the PNM files are read here; the JPEG files go to the device in ONE decode call, which also applies the downscale factor
+    // the PNM files are read here; the JPEG and the PNG files go to the device in ONE decode call each, which also applies the
+    // downscale factor
     std::vector<cv::Mat> images(names.size());
     std::vector<size_t> pnm, jpeg;
     std::vector<std::string> jpegPaths;
     for (size_t i = 0; i < names.size(); i++) {
         const std::string path = directoryPath + "/" + names[i];
         const std::string ext = lowerExtension(names[i]);
-        if (ext == ".jpg" || ext == ".jpeg") {
+        if (ext == ".jpg" || ext == ".jpeg" || ext == ".png") {
             jpeg.push_back(i);
             jpegPaths.push_back(path);
             continue;

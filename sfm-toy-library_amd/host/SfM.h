@@ -25,7 +25,8 @@
 //                 and the view becomes good.
 //   end           every view is done.
 //   downscale     the factor of the constructor is applied by setImagesDirectory at load time, as in the reference (SfM.cpp:125-129): the
-//                 JPEG files in ONE decode call that also resizes (SfMImageUtilities::readImages), the PNM images in ONE resize call;
+//                 JPEG files and the PNG files in ONE decode call each that also resizes (SfMImageUtilities::readImages), the PNM
+//                 images in ONE resize call;
 //                 K then comes from the resized image 0.  Images given through setImages and features given through setFeatures are
 //                 taken as they are: runSfM refuses downscale != 1 for them (there is nothing to resize in the second case).
 // There is no visual debugging.
@@ -62,11 +63,13 @@ public:
 
     /**
      * Binary .pgm (P5 -> CV_8U) / .ppm (P6 -> CV_8UC3, stored B, G, R) files of maxval 255 and baseline .jpg / .jpeg files (one
-     * component -> CV_8U, three -> CV_8UC3; the scope is that of sfmba_jpeg_decode, EXIF orientation is ignored) of the directory, in
+     * component -> CV_8U, three -> CV_8UC3; the scope is that of sfmba_jpeg_decode, EXIF orientation is ignored) and non-interlaced
+     * .png files (gray with or without alpha -> CV_8U, colour and palette -> CV_8UC3; the scope is that of sfmba_png_decode: 16-bit
+     * samples keep their high byte, alpha is dropped, no gamma) of the directory, in
      * ascending file-name order across all extensions (the extension decides which files are read, in either letter case).  The
      * downscale factor of the constructor is applied here, on the device; PNM files at factor 1 touch no device.
      * @return true on success; false (no image kept) when the directory cannot be read, holds no such file, a file is not a P5 / P6
-     *         file of maxval 255 with all its bytes or not a decodable baseline JPEG, the files are not all of one kind, or the
+     *         file of maxval 255 with all its bytes or not a decodable baseline JPEG / PNG, the files are not all of one kind, or the
      *         device fails.
      */
     bool setImagesDirectory(const std::string& directoryPath);

@@ -1,5 +1,5 @@
 // SfMImageUtilities.cpp -- host side of the image reader: flattens the files / images, calls the C ABI (include/sfmba.h,
-// sfmba_jpeg_decode, sfmba_resize_images) and rebuilds the reference's list of cv::Mat.  See SfMImageUtilities.h.
+// sfmba_jpeg_decode, sfmba_png_decode, sfmba_resize_images) and rebuilds the reference's list of cv::Mat.  See SfMImageUtilities.h.
 #include "SfMImageUtilities.h"
 
 #include <cstdint>
@@ -20,35 +20,40 @@ cv::Mat imageFromBytes(int w, int h, int channels, const unsigned char* px) {
     return m;
 }
 
-const char* const statusNames[] = { "ok", "not a baseline JPEG this reader supports", "corrupt" };
+const char* const statusNames[] = { "ok", "outside the scope of this reader (baseline JPEG, non-interlaced PNG)", "corrupt" };
 
-}  // namespace
+bool isPng(const std::vector<unsigned char>& f) {
+    static const unsigned char SIGNATURE[8] = { 0x89, 0x50, 0x4E, 0x47, 0x0D, 0x0A, 0x1A, 0x0A };
+    return f.size() >= 8 && std::memcmp(f.data(), SIGNATURE, 8) == 0;
+}
+bool isJpeg(const std::vector<unsigned char>& f) { return f.size() >= 2 && f[0] == 0xFF && f[1] == 0xD8; }
 
-bool SfMImageUtilities::readImages(const std::vector<std::string>& paths, float downscale, std::vector<cv::Mat>& images) {
-    images.clear();
-    const size_t n = paths.size();
+// The files `which` of one format in ONE decode call (sfmba_jpeg_* or sfmba_png_*: both info structs begin with status, width,
+// height, channels); images[which[k]] receives file k.
+template <typename Info, typename InfoFn, typename DecodeFn>
+bool decodeFiles(const std::vector<std::string>& paths, const std::vector<std::vector<unsigned char> >& files, const std::vector<size_t>& which,
+                 float downscale, InfoFn infoFn, DecodeFn decodeFn, std::vector<cv::Mat>& images) {
+    const size_t n = which.size();
     if (n == 0) return true;
     std::vector<int64_t> ptr(n + 1, 0), out_ptr(n + 1, 0);
     std::vector<unsigned char> bytes;
-    for (size_t i = 0; i < n; ++i) {
-        std::ifstream in(paths[i].c_str(), std::ios::binary);
-        if (!in) { std::fprintf(stderr, "readImages: %s cannot be read\n", paths[i].c_str()); return false; }
-        bytes.insert(bytes.end(), std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
-        ptr[i + 1] = (int64_t)bytes.size();
+    for (size_t k = 0; k < n; ++k) {
+        bytes.insert(bytes.end(), files[which[k]].begin(), files[which[k]].end());
+        ptr[k + 1] = (int64_t)bytes.size();
     }
-    std::vector<sfmba_image_info> info(n);
+    std::vector<Info> info(n);
     std::vector<unsigned char> px;
     int64_t cap = 0, total = 0;
-    if (sfmba_jpeg_info((int)n, ptr.data(), bytes.data(), info.data()) == SFMBA_OK)          // sizes the output: one device call in the usual case
-        for (size_t i = 0; i < n; ++i) {
-            int32_t ow = info[i].width, oh = info[i].height;
-            if (info[i].status == SFMBA_IMAGE_OK && (downscale == 1.0f || sfmba_resized_size(info[i].width, info[i].height, downscale, &ow, &oh) == SFMBA_OK))
-                cap += (int64_t)ow * oh * info[i].channels;
+    if (infoFn((int)n, ptr.data(), bytes.data(), info.data()) == SFMBA_OK)          // sizes the output: one device call in the usual case
+        for (size_t k = 0; k < n; ++k) {
+            int32_t ow = info[k].width, oh = info[k].height;
+            if (info[k].status == SFMBA_IMAGE_OK && (downscale == 1.0f || sfmba_resized_size(info[k].width, info[k].height, downscale, &ow, &oh) == SFMBA_OK))
+                cap += (int64_t)ow * oh * info[k].channels;
         }
     int rc = SFMBA_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
         px.resize((size_t)cap + 1);
-        rc = sfmba_jpeg_decode(0, (int)n, ptr.data(), bytes.data(), downscale, info.data(), out_ptr.data(), px.data(), cap, &total);
+        rc = decodeFn(0, (int)n, ptr.data(), bytes.data(), downscale, info.data(), out_ptr.data(), px.data(), cap, &total);
         if (rc == SFMBA_ERR_CAPACITY && attempt == 0) { cap = total; continue; }
         break;
     }
@@ -56,18 +61,43 @@ bool SfMImageUtilities::readImages(const std::vector<std::string>& paths, float 
         std::fprintf(stderr, "readImages failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
         return false;
     }
-    for (size_t i = 0; i < n; ++i)
-        if (info[i].status != SFMBA_IMAGE_OK) {
-            std::fprintf(stderr, "readImages: %s is %s\n", paths[i].c_str(), statusNames[info[i].status == SFMBA_IMAGE_UNSUPPORTED ? 1 : 2]);
+    for (size_t k = 0; k < n; ++k)
+        if (info[k].status != SFMBA_IMAGE_OK) {
+            std::fprintf(stderr, "readImages: %s is %s\n", paths[which[k]].c_str(), statusNames[info[k].status == SFMBA_IMAGE_UNSUPPORTED ? 1 : 2]);
             return false;
         }
-    images.reserve(n);
-    for (size_t i = 0; i < n; ++i) {
-        int32_t ow = info[i].width, oh = info[i].height;
-        if (downscale != 1.0f && sfmba_resized_size(info[i].width, info[i].height, downscale, &ow, &oh) != SFMBA_OK) { images.clear(); return false; }
-        if (out_ptr[i + 1] - out_ptr[i] != (int64_t)ow * oh * info[i].channels) { images.clear(); return false; }
-        images.push_back(imageFromBytes(ow, oh, info[i].channels, px.data() + out_ptr[i]));
+    for (size_t k = 0; k < n; ++k) {
+        int32_t ow = info[k].width, oh = info[k].height;
+        if (downscale != 1.0f && sfmba_resized_size(info[k].width, info[k].height, downscale, &ow, &oh) != SFMBA_OK) return false;
+        if (out_ptr[k + 1] - out_ptr[k] != (int64_t)ow * oh * info[k].channels) return false;
+        images[which[k]] = imageFromBytes(ow, oh, info[k].channels, px.data() + out_ptr[k]);
     }
+    return true;
+}
+
+}  // namespace
+
+bool SfMImageUtilities::readImages(const std::vector<std::string>& paths, float downscale, std::vector<cv::Mat>& images) {
+    images.clear();
+    const size_t n = paths.size();
+    if (n == 0) return true;
+    // the signature decides, not the name: 89 50 4E 47 0D 0A 1A 0A is PNG, FF D8 is JPEG
+    std::vector<std::vector<unsigned char> > files(n);
+    std::vector<size_t> jpeg, png;
+    for (size_t i = 0; i < n; ++i) {
+        std::ifstream in(paths[i].c_str(), std::ios::binary);
+        if (!in) { std::fprintf(stderr, "readImages: %s cannot be read\n", paths[i].c_str()); return false; }
+        files[i].assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+        if (isPng(files[i])) png.push_back(i);
+        else if (isJpeg(files[i])) jpeg.push_back(i);
+        else { std::fprintf(stderr, "readImages: %s is neither a JPEG nor a PNG file\n", paths[i].c_str()); return false; }
+    }
+    // one call per format; the results go back in path order
+    std::vector<cv::Mat> out(n);
+    if (!decodeFiles<sfmba_image_info>(paths, files, jpeg, downscale, sfmba_jpeg_info, sfmba_jpeg_decode, out) ||
+        !decodeFiles<struct sfmba_png_info>(paths, files, png, downscale, sfmba_png_info, sfmba_png_decode, out))
+        return false;
+    images.swap(out);
     return true;
 }
 

@@ -15,7 +15,7 @@ namespace {
 void usage(std::ostream& os, const char* program) {
     os << "usage: " << program << " [options] <input-directory>\n"
        << "  -h, --help                   this text\n"
-       << "  -p, --input-directory DIR    directory of .jpg / .jpeg / .pgm / .ppm images (also as the positional argument)\n"
+       << "  -p, --input-directory DIR    directory of .jpg / .jpeg / .png / .pgm / .ppm images (also as the positional argument)\n"
        << "  -s, --downscale F            factor applied to every image at load time (default 1)\n"
        << "  -d, --console-debug N        console log level, 0 = trace .. 4 = error (default 2)\n"
        << "  -o, --output-prefix PREFIX   PREFIX_points.ply and PREFIX_cameras.ply (default output)\n"

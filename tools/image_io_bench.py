@@ -7,6 +7,12 @@
   (d) with --pipeline: sfmtoylib::SfM from the directory of the seven photographs at factor 1 in a fresh deterministic process:
       runSfM's code, the views registered, the cloud size and the RMS reprojection error of the cloud in the final cameras
 
+  (e) with --png: the same seven photographs (their decoded pixels) written as PNG files with a random filter type per row, decoded by
+      sfmba_png_decode in ONE call, and one 1024 x 768 x 3 image likewise: host chunk walk + inflate (wall clock, at most 16 threads)
+      and the HIP-event times of upload, unfilter kernel, pixel kernel and download (SFMBA_PNG_TIMING); whether the unfilter kernel is
+      shorter than the host inflate of the same call; Pillow's decode of the same files on the host where Pillow is importable, for
+      scale only
+
 Medians over --reps calls after --warmup.  Every repetition is compared byte for byte with the first.  The 1024 x 768 images are the
 decoded photographs enlarged by the resize itself (factor 2), so the tool needs nothing but the repository.
 """
@@ -25,9 +31,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 PHASES = ("entropy_ms", "upload_ms", "idct_ms", "colour_ms", "resize_ms", "download_ms")
+PNG_PHASES = ("inflate_ms", "upload_ms", "unfilter_ms", "pixels_ms", "resize_ms", "download_ms")
 
 
-def timed(what, fn):
+def timed(what, fn, phases=PHASES):
     """fn() with the library's stderr timing line of `what` captured: (result, phases, wall ms)."""
     with tempfile.TemporaryFile() as f:
         sys.stderr.flush()
@@ -42,17 +49,17 @@ def timed(what, fn):
             os.close(saved)
         f.seek(0)
         text = f.read().decode()
-    m = re.findall(r"\[sfmba " + what + r"\] " + " ".join(k + r" (\S+)" for k in PHASES), text)
+    m = re.findall(r"\[sfmba " + what + r"\] " + " ".join(k + r" (\S+)" for k in phases), text)
     if not m:
         raise RuntimeError("no timing line from the library: %r" % text)
-    return res, dict(zip(PHASES, map(float, m[-1]))), wall
+    return res, dict(zip(phases, map(float, m[-1]))), wall
 
 
-def measure(what, fn, same, warmup, reps):
+def measure(what, fn, same, warmup, reps, phases=PHASES):
     first = None
     rows = []
     for r in range(warmup + reps):
-        res, ph, wall = timed(what, fn)
+        res, ph, wall = timed(what, fn, phases)
         if first is None:
             first = res
         elif not same(first, res):
@@ -71,9 +78,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--pipeline", action="store_true")
+    ap.add_argument("--png", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     os.environ["SFMBA_JPEG_TIMING"] = "1"
+    os.environ["SFMBA_PNG_TIMING"] = "1"
     import jpeg_cases as jc
     from sfm_toy_library_amd import capi
     lines = []
@@ -102,6 +111,32 @@ def main():
         say("%s of 1024 x 768 x 3 at 0.5, one call" % label)
         say("    upload %.3f ms | resize kernel %.3f ms (%.1f GB/s over the %d bytes read and written once) | download %.3f ms | call %.3f ms"
             % (med["upload_ms"], med["resize_ms"], moved / med["resize_ms"] / 1e6, moved, med["download_ms"], med["call_ms"]))
+
+    if args.png:
+        import png_oracle as po
+        rng = np.random.default_rng(7)
+        for label, imgs in (("(e) PNG decode, the 7 photographs of 512 x 384 x 3", photos), ("    PNG decode, 1 image of 1024 x 768 x 3", big[:1])):
+            pngs = [po.write_png(im[:, :, ::-1], 2, 8, rng=rng) for im in imgs]
+            cap = sum(im.size for im in imgs)
+            (_, got), med = measure("png_decode", lambda: capi.png_decode(pngs, cap=cap), lambda a, b: same_images(a[1], b[1]), args.warmup, args.reps, PNG_PHASES)
+            assert same_images(got, imgs)
+            say("%s (%d file bytes, random filter types per row), one call" % (label, sum(map(len, pngs))))
+            say("    host inflate %.3f ms | upload %.3f ms | unfilter kernel %.3f ms | pixel kernel %.3f ms | download %.3f ms | call %.3f ms"
+                % (med["inflate_ms"], med["upload_ms"], med["unfilter_ms"], med["pixels_ms"], med["download_ms"], med["call_ms"]))
+            say("    the unfilter kernel is %s than the host inflate of the same call (%.2f x)"
+                % ("SHORTER" if med["unfilter_ms"] < med["inflate_ms"] else "NOT shorter", med["unfilter_ms"] / med["inflate_ms"]))
+            try:
+                import io
+                from PIL import Image
+                t = []
+                for _ in range(args.reps):
+                    t0 = time.perf_counter()
+                    for data in pngs:
+                        Image.open(io.BytesIO(data)).load()
+                    t.append(1e3 * (time.perf_counter() - t0))
+                say("    Pillow on the host, one file after another, for scale: %.3f ms" % float(np.median(t)))
+            except ImportError:
+                say("    (Pillow is not importable here)")
 
     if args.pipeline:
         import shutil
