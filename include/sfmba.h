@@ -149,7 +149,7 @@ typedef struct sfmba_options {
     /* ---- ABI v4: behaviour switches that were environment variables only (a C caller could not set them per problem or
        thread-safely).  0 = library default, 1 = on, -1 = off.  ABI v4 let the environment variable named beside each switch
        override the field; since ABI v5 NOTHING below sfmba_problem_create* reads the environment: the fields are the only way
-       (what is still read from the environment, when a problem is BUILT: SFMBA_DETERMINISTIC, SFMBA_PAIR_LPB, SFMBA_PAIR_LIMIT,
+       (what is still read from the environment, when a problem is BUILT: SFMBA_DETERMINISTIC, SFMBA_PAIR_LPB, SFMBA_PAIR_LOADS, SFMBA_PAIR_LIMIT,
        SFMBA_BUILD_TIMING). ---- */
     int    pcg_coarse_space;          /* SFMBA_PCG_COARSE         default on : two-level CG preconditioner (8 gauge vectors).  Where the reduced
                                          matrix is sparsely filled (< 1/2 of its blocks) with >= 90 % of the blocks within a quarter of the cyclic camera

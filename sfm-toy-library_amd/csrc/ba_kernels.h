@@ -115,6 +115,8 @@ struct DeviceStructure {
     const int* pair_pt;       // [npair] the point slot of every pair of observations (qa < qb) of one point, grouped by block, ascending point inside a
                               //         block (the pair pass needs nothing else per pair: the cameras follow from the block)
     int pair_lpb;             // lanes per 6x6 block in the pair pass: 64 (k_schur_pairs) or 16 (k_schur_pairs_sub_f), from the mean pairs per block
+    int pair_quad;            // fp32 wave-per-chunk pass: 1 = the four lanes of a quad fetch one point-table entry per load, through LDS (the default),
+                              //       0 = every lane fetches its own entry (SFMBA_PAIR_LOADS=lane, k_schur_pairs_lane)
     int npairwg;
     const int2* pwg_blocks;   // [npairwg] {first block, #blocks <= 4} per workgroup of the pair pass (XCD-grouped rows)
     int pwg_group;            // blocks per workgroup entry (SFMBA_PAIR_WAVES, or 64 / pair_lpb)

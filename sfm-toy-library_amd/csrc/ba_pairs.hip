@@ -111,8 +111,14 @@ __device__ __forceinline__ void pair_epilogue(const DeviceStructure& ds, const D
 // summed in its rank-2 form (sfmba_device.h: obs_factored_ab, pair_product_ab): 139 wave instructions per 64 pairs, 96 registers (five
 // waves per SIMD; tools/pair_isa_count.py counts them from the compiler's output).  A block of several chunks leaves its partial sums in
 // pair_partial; k_schur_combine (the next launch) adds them and runs the epilogue.
-template <typename T, int MODE>
-__global__ __launch_bounds__(64, (sizeof(T) == 4 ? 4 : 2)) void k_schur_pairs(DeviceStructure ds, DeviceBuffers db) {
+// QUAD (fp32 mode, the default): the round's 64 point-table entries are fetched by quads -- four loads in which the four lanes of a quad
+// read one contiguous 64-byte entry, 16 lines per load where a per-lane gather walks 64 (three such gathers per round without it) -- and
+// transposed through 4 144 bytes of LDS private to the wave (sfmba_device.h: ptrec_quad_fetch / ptrec_quad_take): 162 instructions per
+// round, 7 of them LDS, 94 registers.  Measured at BASELINE config 3 (profiles/pair_coop_loads_ab.txt): cache accesses per wave 1 178 -> 481,
+// the texture addresser 68 % -> 50 % busy, 48.9 -> 46.0 us per launch.  Every lane ends up with the bytes its own loads would bring.
+template <typename T, int MODE, bool QUAD>
+__device__ __forceinline__ void schur_pairs_wave(const DeviceStructure& ds, const DeviceBuffers& db) {
+    static_assert(!QUAD || sizeof(T) == 4, "the quad fetch is that of the 64-byte entry");
     __shared__ double tile[36];
     const int lane = threadIdx.x & 63;
     const int4 dsc = ds.pwg_desc[blockIdx.x];       // one load: block, row camera, pair range of the chunk
@@ -153,13 +159,32 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 4 : 2)) void k_schur_pairs(De
         const int mine = 16 * s + g;
         const int plast = pbeg < p1 ? p1 - 1 : 0;
         const PtRecA<T>* ent_next = PA + ds.pair_pt[pbeg + mine < p1 ? pbeg + mine : plast];
+        // QUAD: the entry's byte offset is carried instead (arithmetic on the loaded slot as well), and the entry comes through LDS: the four
+        // lanes of a quad fetch the entries of the quad's four pairs piece by piece (sfmba_device.h, ptrec_quad_fetch) -- 64 lines per round
+        // instead of 192, the same bytes in every lane.
         auto rounds = [&](auto&& body) {
-            for (int p0 = pbeg; p0 < p1; p0 += 64) {
-                const PtRecA<T> pa = load_ptrec(ent_next);
-                const int p = p0 + 64 + mine;
-                const int pt = ds.pair_pt[p < p1 ? p : plast];
-                body(pa, p0 + mine < p1);               // (pair inside the chunk?)
-                ent_next = PA + pt;
+            if constexpr (QUAD) {
+                __shared__ int4 coop[PTQ_PIECES];
+                unsigned off_next = (unsigned)(ent_next - PA) * 64u;
+                for (int p0 = pbeg; p0 < p1; p0 += 64) {
+                    unsigned w = 16u * (unsigned)lane;
+                    asm volatile("" : "+v"(w));         // the LDS addresses and the piece offset are formed anew every round (five instructions): carried, they cost the fifth wave (98 registers)
+                    ptrec_quad_fetch(PA, off_next, w, coop);
+                    wave_lds_fence();
+                    const PtRecA<T> pa = ptrec_quad_take(w, coop);
+                    const int p = p0 + 64 + mine;
+                    const int pt = ds.pair_pt[p < p1 ? p : plast];
+                    body(pa, p0 + mine < p1);
+                    off_next = (unsigned)pt * 64u;
+                }
+            } else {
+                for (int p0 = pbeg; p0 < p1; p0 += 64) {
+                    const PtRecA<T> pa = load_ptrec(ent_next);
+                    const int p = p0 + 64 + mine;
+                    const int pt = ds.pair_pt[p < p1 ? p : plast];
+                    body(pa, p0 + mine < p1);               // (pair inside the chunk?)
+                    ent_next = PA + pt;
+                }
             }
         };
         if constexpr (sizeof(T) == 4) {
@@ -208,6 +233,16 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? 4 : 2)) void k_schur_pairs(De
     if (len >= 1) tile[base] = -own[0];
     wave_lds_fence();
     pair_epilogue<MODE>(ds, db, b, cj, tile, lane);
+}
+// fp32: the quad fetch.  The per-lane loads stay selectable (SFMBA_PAIR_LOADS=lane when the problem is built; DeviceStructure::pair_quad) as the
+// kernel below: the reference of tests/test_gpu_pair_coop_loads.py and the other side of an A/B measurement.
+template <typename T, int MODE>
+__global__ __launch_bounds__(64, (sizeof(T) == 4 ? 4 : 2)) void k_schur_pairs(DeviceStructure ds, DeviceBuffers db) {
+    schur_pairs_wave<T, MODE, sizeof(T) == 4>(ds, db);
+}
+template <typename T, int MODE>
+__global__ __launch_bounds__(64, 4) void k_schur_pairs_lane(DeviceStructure ds, DeviceBuffers db) {
+    schur_pairs_wave<T, MODE, false>(ds, db);
 }
 
 // the blocks of several chunks: their partial sums added in chunk order, then the epilogue of k_schur_pairs
@@ -445,7 +480,10 @@ void launch_schur_pairs(hipStream_t s, const DeviceStructure& ds, const DeviceBu
         if (mode == 1) hipLaunchKernelGGL((k_schur_pairs_sub_f<T, 1, 16>), grid, dim3(64), 0, s, ds, db);
         else hipLaunchKernelGGL((k_schur_pairs_sub_f<T, 0, 16>), grid, dim3(64), 0, s, ds, db);
     } else {
-        if (mode == 1) hipLaunchKernelGGL((k_schur_pairs<T, 1>), grid, dim3(64), 0, s, ds, db);
+        if (sizeof(T) == 4 && !ds.pair_quad) {
+            if (mode == 1) hipLaunchKernelGGL((k_schur_pairs_lane<float, 1>), grid, dim3(64), 0, s, ds, db);
+            else hipLaunchKernelGGL((k_schur_pairs_lane<float, 0>), grid, dim3(64), 0, s, ds, db);
+        } else if (mode == 1) hipLaunchKernelGGL((k_schur_pairs<T, 1>), grid, dim3(64), 0, s, ds, db);
         else hipLaunchKernelGGL((k_schur_pairs<T, 0>), grid, dim3(64), 0, s, ds, db);
         if (ds.nmulti > 0) {
             if (mode == 1) hipLaunchKernelGGL(k_schur_combine<1>, dim3(ds.nmulti), dim3(64), 0, s, ds, db);

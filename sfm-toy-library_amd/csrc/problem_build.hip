@@ -198,7 +198,7 @@ static int build_structure(sfmba_problem* p, const ObsSource& src, const double*
     std::vector<int2> blk_cams, pwg_blocks;
     std::vector<double> cam0, pts0;
     std::vector<char> blob;
-    int pair_lpb = 64, blocks_per_wg = 1;
+    int pair_lpb = 64, blocks_per_wg = 1, pair_quad = 1;
     size_t pair_slot_cap = 0;
     // (SFMBA_PAIR_LIMIT: a test hook that lowers the threshold so that the matrix-free path runs at test size; read when a problem is built)
     long long pair_limit = (long long)1 << 31;
@@ -299,6 +299,11 @@ static int build_structure(sfmba_problem* p, const ObsSource& src, const double*
         }
         if (const char* e = std::getenv("SFMBA_PAIR_LPB")) { const int v = std::atoi(e); if (v == 64 || v == 16) pair_lpb = v; }
         blocks_per_wg = pair_lpb == 64 ? 1 : 64 / pair_lpb;
+        // How the fp32 wave-per-chunk pass fetches its point-table entries: SFMBA_PAIR_LOADS=lane keeps one entry per lane (three gathers of 64 lines
+        // a round), the default `quad` lets the four lanes of a quad fetch one entry per load (four loads of 16 lines, csrc/sfmba_device.h: ptrec_quad_fetch).
+        // The quad form addresses the table by a 32-bit byte offset, so a table of 4 GB or more (2^26 points) keeps the per-lane loads.
+        if (const char* e = std::getenv("SFMBA_PAIR_LOADS")) { if (std::strcmp(e, "lane") == 0) pair_quad = 0; }
+        if ((long long)npt * 64 >= ((long long)1 << 32)) pair_quad = 0;
         {
             std::vector<std::vector<int2>> per_xcd(8);
             for (int ja = brow0; ja < (p->no_pairs ? brow0 : brow1); ++ja) {       // (a row-sharded rank: its own block rows only -- all pairs of each of their blocks; no pair list: no pair pass)
@@ -585,7 +590,7 @@ static int build_structure(sfmba_problem* p, const ObsSource& src, const double*
     ds.nchunk_coarse = (int)chunks_coarse.size(); ds.chunks_coarse = p->d_chunks_coarse; ds.cam_chunk_ptr = p->d_cam_chunk_ptr;
     ds.obs_pt = p->d_obs_pt;
     ds.nblock = nblock; ds.blk_cams = p->d_blk_cams; ds.blk_ptr = p->d_blk_ptr; ds.pair_pt = p->d_pair_pt;
-    ds.npairwg = (int)pwg_blocks.size(); ds.pwg_blocks = p->d_pwg_blocks; ds.pair_lpb = pair_lpb;
+    ds.npairwg = (int)pwg_blocks.size(); ds.pwg_blocks = p->d_pwg_blocks; ds.pair_lpb = pair_lpb; ds.pair_quad = pair_quad;
     ds.pwg_group = blocks_per_wg; ds.pwg_desc = p->d_pwg_desc;
     ds.pwg_chunk = pair_lpb == 64 ? p->d_pwg_chunk : nullptr; ds.nmulti = 0; ds.multi_slots = p->d_multi_slots;      // counts: after the wait at the end
     ds.ndupwg = 0; ds.dup_blocks = p->d_dup_blocks;          // count: after the wait at the end

@@ -57,16 +57,55 @@ template <> struct alignas(8)  PtRecB<float>  { float t[3]; float yf[3]; };
 template <> struct alignas(16) PtRecB<double> { double t[3]; double yf[3]; };
 // One entry in three (fp32 mode) 16-byte loads: left to itself the compiler loads the two member arrays separately (16 + 8 and, at an
 // 8-byte-aligned offset, 16 + 8 bytes: four requests per lane, and the vector-memory pipe walks one line per lane and request).
-__device__ __forceinline__ PtRecA<float> load_ptrec(const PtRecA<float>* p) {
-    const int4* q = reinterpret_cast<const int4*>(p);
-    const int4 c0 = q[0], c1 = q[1], c2 = q[2];
+__device__ __forceinline__ PtRecA<float> unpack_ptrec(const int4& c0, const int4& c1, const int4& c2) {
     PtRecA<float> r;
     r.X[0] = __hiloint2double(c0.y, c0.x); r.X[1] = __hiloint2double(c0.w, c0.z); r.X[2] = __hiloint2double(c1.y, c1.x);
     r.L[0] = __int_as_float(c1.z); r.L[1] = __int_as_float(c1.w);
     r.L[2] = __int_as_float(c2.x); r.L[3] = __int_as_float(c2.y); r.L[4] = __int_as_float(c2.z); r.L[5] = __int_as_float(c2.w);
     return r;
 }
+__device__ __forceinline__ PtRecA<float> load_ptrec(const PtRecA<float>* p) {
+    const int4* q = reinterpret_cast<const int4*>(p);
+    const int4 c0 = q[0], c1 = q[1], c2 = q[2];
+    return unpack_ptrec(c0, c1, c2);
+}
 __device__ __forceinline__ PtRecA<double> load_ptrec(const PtRecA<double>* p) { return *p; }
+
+// The same entry for all 64 lanes of a wave with a quarter of the lines: the vector-memory pipe walks one line per lane and request when every
+// lane is on another entry (three requests of 64 lines), but the four lanes of a quad fetching the four 16-byte pieces of ONE entry touch 16
+// lines per request -- four requests (one per lane of the quad) bring the 64 entries, and a private piece of LDS hands every lane its own.
+//   fetch: `off` = 64 * (this lane's point slot).  Request k takes piece s = lane & 3 of the entry of lane 4 g + k (g = lane >> 2; its offset by a
+//          DPP quad broadcast) and stores it in plane k at 16 * lane: 8 consecutive lanes store 128 contiguous bytes -- no bank conflict.
+//   take : lane 4 g + s reads its three pieces (the pad piece is not read) from plane s at 64 g + 16 p.  Planes are PTQ_PLANE = 1040 bytes apart, so
+//          piece p of lane l is in 16-byte bank slot (l + p) mod 16 and the 16 lanes of every ds_read_b128 group fall into 16 different slots.
+// Between the two: wave_lds_fence() (ba_common.h).  The reads of one round are ahead of the next round's stores in the wave's LDS queue.
+// The table is addressed as base + 32-bit byte offset (one address register per request): tables below 4 GB (problem_build.hip).
+constexpr int PTQ_PLANE = 1040 / 16;                    // in 16-byte pieces
+constexpr int PTQ_PIECES = 3 * PTQ_PLANE + 64;          // 4 144 bytes per wave
+template <int K> __device__ __forceinline__ unsigned quad_bcast(unsigned v) {       // the value of lane K of this lane's quad
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, K * 0x55, 0xf, 0xf, true);      // quad_perm [K,K,K,K]
+}
+// (w = 16 * lane: the lane's store address, from which the piece offset 16 s = w & 48 and the read address w + 64 * 16 s follow in one instruction each)
+__device__ __forceinline__ void ptrec_quad_fetch(const PtRecA<float>* PA, unsigned off, unsigned w, int4* lds) {
+    const char* base = reinterpret_cast<const char*>(PA);
+    const unsigned piece = w & 48u;
+    const int4 c0 = *reinterpret_cast<const int4*>(base + (quad_bcast<0>(off) + piece));
+    const int4 c1 = *reinterpret_cast<const int4*>(base + (quad_bcast<1>(off) + piece));
+    const int4 c2 = *reinterpret_cast<const int4*>(base + (quad_bcast<2>(off) + piece));
+    const int4 c3 = *reinterpret_cast<const int4*>(base + (quad_bcast<3>(off) + piece));
+    int4* mine = reinterpret_cast<int4*>(reinterpret_cast<char*>(lds) + w);
+    mine[0] = c0; mine[PTQ_PLANE] = c1; mine[2 * PTQ_PLANE] = c2; mine[3 * PTQ_PLANE] = c3;
+}
+__device__ __forceinline__ PtRecA<float> ptrec_quad_take(unsigned w, const int4* lds) {
+    // whole 16-byte reads: left to itself the compiler narrows them to the members (ds_read2_b64 + ds_read_b64 + two ds_read_b128, other bank rules)
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    const v4i* e = reinterpret_cast<const v4i*>(reinterpret_cast<const char*>(lds) + (((w & 48u) << 6) + w));      // 1040 s + 64 g = w + 1024 s
+    v4i c0 = e[0], c1 = e[1], c2 = e[2];
+    asm("" : "+v"(c0));
+    asm("" : "+v"(c1));
+    asm("" : "+v"(c2));
+    return unpack_ptrec(make_int4(c0.x, c0.y, c0.z, c0.w), make_int4(c1.x, c1.y, c1.z, c1.w), make_int4(c2.x, c2.y, c2.z, c2.w));
+}
 static_assert(sizeof(PtRecA<float>) == 64 && sizeof(PtRecA<double>) == 80 && sizeof(PtRecB<float>) == 24 && sizeof(PtRecB<double>) == 48, "point table layout");
 
 // Camera tables are stored in component quads (AoSoA): values 4c .. 4c+3 of camera j are the 32 contiguous bytes at

@@ -33,6 +33,8 @@ def classify(op):
         return "other VALU"
     if op.startswith("global_load") or op.startswith("buffer_load") or op.startswith("flat_load") or op.startswith("s_load"):
         return "load"
+    if op.startswith("ds_"):
+        return "LDS"
     if op.startswith("s_waitcnt"):
         return "wait"
     if op.startswith("s_"):
@@ -40,7 +42,7 @@ def classify(op):
     return "other"
 
 
-ORDER = ["fp64", "convert", "select", "packed fp32", "scalar fp32", "other VALU", "v_mov", "v_pk_mov", "load", "wait", "SALU / branch", "other"]
+ORDER = ["fp64", "convert", "select", "packed fp32", "scalar fp32", "other VALU", "v_mov", "v_pk_mov", "load", "LDS", "wait", "SALU / branch", "other"]
 
 
 def kernels(asm):
