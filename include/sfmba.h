@@ -576,6 +576,36 @@ SFMBA_API int sfmba_match_features(int device, int n_images, const int64_t* img_
                 int64_t* pair_ptr, int32_t* query_idx, int32_t* train_idx, float* distance, int64_t cap, int64_t* total);
 
 /*
+ * The same for FLOAT descriptors (SIFT, SURF, RootSIFT, learned ones): what cv::BFMatcher does with NORM_L2 -- an exact brute-force
+ * L2 2-NN and the ratio test.  The encodings, the output order, the capacity protocol and the pair semantics are those of
+ * sfmba_match_features; only these points differ:
+ *
+ *   rows          image i owns rows img_ptr[i] .. img_ptr[i+1]-1 of desc; a row is dims floats (1 <= dims <= 512), rows packed
+ *                 back to back.  An image holds fewer than 2^22 rows.  Every value must be finite.
+ *   s(q, j)       the squared distance, defined operation by operation: acc = 0.0f; for k = 0 .. dims-1 in ascending order
+ *                 t = a[k] - b[k] (one fp32 subtraction), acc = fmaf(t, t, acc) (one fused fp32 operation); s = acc.  IEEE
+ *                 behaviour throughout: subnormals are kept, nothing is flushed, nothing is reassociated.  From finite inputs s is
+ *                 never NaN; it may be +inf.
+ *   2-NN          the two smallest (s, j) in lexicographic order: a tie on s goes to the lower train index; +inf orders last.
+ *   ratio test    dist = the correctly rounded fp32 square root of s.  q is kept iff the train image has >= 2 rows and
+ *                 (double)dist_best < ratio * (double)dist_second.  So a best of +inf is dropped, a finite best against an
+ *                 infinite second is kept, and two exact duplicates of the query (0 and 0) are dropped.
+ *   output        (query_idx = q, train_idx = j_best, distance = dist_best).
+ *
+ * SFMBA_ERR_INVALID_ARG, before anything is written: dims outside 1..512, a non-finite value in desc (the message names the image
+ * and the row), a ratio that is not finite or <= 0, an image with >= 2^22 rows, a pair index out of range, more than 2^31 - 1
+ * query rows (summed over the pairs) in one call.  SFMBA_ERR_CAPACITY as for sfmba_match_features.
+ * Deterministic: the result does not depend on how the work is cut up; no atomics, no arrival order.  The work is cut into batches
+ * of query tiles (512 query rows of one pair) in pair-list order, at most 256 tiles per batch (a fixed 64 MiB bound on the
+ * per-slice scratch, 16 bytes per query row and slice); a batch of n tiles splits every train image into
+ * min(ceil(2048 / n), ceil(max train rows of the batch / 256), 32) slices (at least 1).  Inside a slice the train rows go through
+ * LDS in stages of min(256, floor(8192 / dp / 16) * 16) rows, dp = dims rounded up to a multiple of 32, in groups of 16.
+ */
+SFMBA_API int sfmba_match_features_l2(int device, int n_images, const int64_t* img_ptr, const float* desc, int dims,
+                int n_pairs, const int32_t* pair_left, const int32_t* pair_right, double ratio,
+                int64_t* pair_ptr, int32_t* query_idx, int32_t* train_idx, float* distance, int64_t cap, int64_t* total);
+
+/*
  * Pose a not-yet-registered view from its 2D-3D matches (SfMStereoUtilities::findCameraPoseFrom2D3DMatch,
  * SfMToyLib/SfMStereoUtilities.cpp:208-243: cv::solvePnPRansac + the inlier-ratio gate) for a batch of views in one call.
  * The reference's result depends on OpenCV's global RNG; THIS CONTRACT IS OUR OWN, deterministic one -- it is not, and does not

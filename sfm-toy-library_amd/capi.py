@@ -37,7 +37,7 @@ SYMBOLS = [
     "sfmba_match_features", "sfmba_problem_set_step_probe", "sfmba_problem_get_step_probe", "sfmba_pnp_ransac",
     "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_orb_extract", "sfmba_triangulate_pairs",
     "sfmba_jpeg_info", "sfmba_resized_size", "sfmba_jpeg_decode", "sfmba_resize_images",
-    "sfmba_png_info", "sfmba_png_decode",
+    "sfmba_png_info", "sfmba_png_decode", "sfmba_match_features_l2",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -225,6 +225,41 @@ def match_features(descs, pairs=None, ratio=float(np.float32(0.8)), cap=None, de
         rc = lib().sfmba_match_features(C.c_int(device), C.c_int(len(descs)), _p(img_ptr, lp), flat.ctypes.data_as(C.POINTER(C.c_ubyte)),
                                         C.c_int(B), C.c_int(len(pl)), _p(pl, _ip), _p(pr, _ip), C.c_double(ratio), _p(ptr, lp), _p(q, _ip),
                                         _p(t, _ip), _p(d, fp), C.c_int64(cap), C.byref(total))
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        cap = int(total.value)
+    _check(rc)
+    n = total.value
+    return pl, pr, ptr, q[:n].copy(), t[:n].copy(), d[:n].copy()
+
+
+def match_features_l2(descs, pairs=None, ratio=float(np.float32(0.8)), cap=None, device=0):
+    """sfmba_match_features_l2: brute-force exact L2 2-NN + ratio test over float descriptors (see include/sfmba.h).
+
+    descs: list of float32 arrays [n_i, dims] (one per image, the same dims for all).  pairs, ratio and the return value are those of
+    match_features: (pair_left, pair_right, pair_ptr [n_pairs+1], query_idx, train_idx, distance float32)."""
+    descs = [np.asarray(d, dtype=np.float32) for d in descs]
+    nd = {d.shape[1] for d in descs if d.ndim == 2}
+    if any(d.ndim != 2 for d in descs) or len(nd) > 1:
+        raise ValueError("descs must be 2-D float32 arrays with one row length")
+    D = nd.pop() if nd else 128
+    if pairs is None:
+        pairs = [(i, j) for i in range(len(descs)) for j in range(i + 1, len(descs))]
+    pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    pl, pr = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+    img_ptr = np.zeros(len(descs) + 1, dtype=np.int64)
+    img_ptr[1:] = np.cumsum([d.shape[0] for d in descs])
+    flat = np.ascontiguousarray(np.concatenate(descs, axis=0) if descs else np.zeros((0, D), np.float32))
+    if cap is None:                      # at most one entry per query row of a pair with >= 2 train rows: one call, no retry
+        cap = int(sum(descs[l].shape[0] for l, r in zip(pl, pr) if 0 <= r < len(descs) and descs[r].shape[0] >= 2 and 0 <= l < len(descs)))
+    lp, fp = C.POINTER(C.c_int64), C.POINTER(C.c_float)
+    ptr = np.zeros(len(pl) + 1, dtype=np.int64)
+    total = C.c_int64(0)
+    for _ in range(2):
+        q, t, d = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float32)
+        rc = lib().sfmba_match_features_l2(C.c_int(device), C.c_int(len(descs)), _p(img_ptr, lp), flat.ctypes.data_as(fp),
+                                           C.c_int(D), C.c_int(len(pl)), _p(pl, _ip), _p(pr, _ip), C.c_double(ratio), _p(ptr, lp), _p(q, _ip),
+                                           _p(t, _ip), _p(d, fp), C.c_int64(cap), C.byref(total))
         if rc != SFMBA_ERR_CAPACITY:
             break
         cap = int(total.value)

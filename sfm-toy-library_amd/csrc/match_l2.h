@@ -1,0 +1,30 @@
+// match_l2.h -- brute-force exact L2 2-NN + ratio test over float descriptors behind sfmba_match_features_l2 (match_l2.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace sfmba {
+
+// return values besides 0 (ok) and positive hipError_t codes
+enum { MATCH_L2_ERR_CAPACITY = -1 };
+
+// Scratch for the per-slice top-2 keys of one batch (two 64-bit keys = 16 bytes per query row and slice): the pair list is cut
+// into batches of query tiles so that this bound holds whatever the number of pairs (feature matching).
+constexpr size_t MATCH_L2_SCRATCH_BYTES = (size_t)64 << 20;
+constexpr int MATCH_L2_MAX_DIMS = 512;
+constexpr int MATCH_L2_TILE = 512;              // query rows per block: 256 lanes x 2 queries
+constexpr int MATCH_L2_MAX_SLICES = 32;         // train slices per query tile, at most
+constexpr int MATCH_L2_MIN_SLICE_ROWS = 256;    // a slice is not made shorter than this many train rows (when the image has them)
+constexpr int MATCH_L2_TARGET_BLOCKS = 2048;    // slices are added until a batch launches about this many blocks
+constexpr int MATCH_L2_BATCH_TILES = (int)(MATCH_L2_SCRATCH_BYTES / (16 * (size_t)MATCH_L2_MAX_SLICES * MATCH_L2_TILE));   // 256
+constexpr int MATCH_L2_PAD = 32;                // rows are stored padded with zeros to a multiple of this many floats
+constexpr int MATCH_L2_STAGE_FLOATS = 8192;     // train rows staged in LDS at a time: 8192 / padded dims (256 .. 16 rows), 32 KiB
+constexpr int MATCH_L2_GROUP = 16;              // train rows whose accumulators a lane holds at once
+
+// Host pointers in and out; arguments already validated (see include/sfmba.h for the contract).  timing (may be NULL):
+// { upload ms, top-2 + merge kernels ms, compaction ms, download ms, batches } from HIP events on `s`.
+int match_features_l2(hipStream_t s, int device, int n_images, const int64_t* img_ptr, const float* desc, int dims,
+                      int n_pairs, const int32_t* pair_left, const int32_t* pair_right, double ratio, int64_t* pair_ptr,
+                      int32_t* query_idx, int32_t* train_idx, float* distance, int64_t cap, int64_t* total, double* timing);
+
+}  // namespace sfmba

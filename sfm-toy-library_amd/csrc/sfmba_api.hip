@@ -4,6 +4,7 @@
 // There is NO CPU fallback in this library: without a HIP device every entry point returns SFMBA_ERR_NO_DEVICE.
 #include "association.h"
 #include "feature_match.h"
+#include "match_l2.h"
 #include "lm_loop.h"
 #include "pnp_ransac.h"
 #include "homography_ransac.h"
@@ -535,6 +536,52 @@ int sfmba_match_features(int device, int n_images, const int64_t* img_ptr, const
     if (rc == MATCH_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "match_features: output capacity too small");
     if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "match_features: device allocation failed");
     if (rc) return fail(SFMBA_ERR_HIP, std::string("match_features: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+// ---- the same for float descriptors: exact L2 2-NN (cv::BFMatcher with NORM_L2) ---------------------------------------------
+int sfmba_match_features_l2(int device, int n_images, const int64_t* img_ptr, const float* desc, int dims, int n_pairs,
+                            const int32_t* pair_left, const int32_t* pair_right, double ratio, int64_t* pair_ptr, int32_t* query_idx,
+                            int32_t* train_idx, float* distance, int64_t cap, int64_t* total) {
+    if (n_images < 0 || n_pairs < 0 || cap < 0 || !img_ptr || !pair_ptr || !total || (n_pairs > 0 && (!pair_left || !pair_right)) ||
+        (cap > 0 && (!query_idx || !train_idx)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (dims < 1 || dims > MATCH_L2_MAX_DIMS) return fail(SFMBA_ERR_INVALID_ARG, "dims must be in 1..512");
+    if (!std::isfinite(ratio) || !(ratio > 0.0)) return fail(SFMBA_ERR_INVALID_ARG, "ratio must be finite and > 0");
+    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        const int64_t n = img_ptr[i + 1] - img_ptr[i];
+        if (n < 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
+        if (n >= ((int64_t)1 << 22)) return fail(SFMBA_ERR_INVALID_ARG, "an image has 2^22 or more descriptor rows");
+    }
+    if (img_ptr[n_images] > 0 && !desc) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    int64_t rows = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        const int l = pair_left[p], r = pair_right[p];
+        if (l < 0 || l >= n_images || r < 0 || r >= n_images) return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
+        if (img_ptr[r + 1] - img_ptr[r] >= 2) rows += img_ptr[l + 1] - img_ptr[l];
+    }
+    if (rows >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "match_features_l2: too many query rows in one call (2^31)");
+    for (int i = 0; i < n_images; ++i)                      // the contract is stated for finite values only
+        for (int64_t r = img_ptr[i]; r < img_ptr[i + 1]; ++r) {
+            const float* row = desc + (size_t)r * (size_t)dims;
+            for (int k = 0; k < dims; ++k)
+                if (!std::isfinite(row[k]))
+                    return fail(SFMBA_ERR_INVALID_ARG, "match_features_l2: non-finite descriptor value in image " + std::to_string(i) + ", row " +
+                                                           std::to_string((long long)(r - img_ptr[i])));
+        }
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    // SFMBA_MATCH_TIMING: one stderr line per call with the HIP-event times of its phases (tools/match_l2_bench.py)
+    double tm[5];
+    const bool timing = std::getenv("SFMBA_MATCH_TIMING") != nullptr;
+    rc = match_features_l2(ck.kit.stream, device, n_images, img_ptr, desc, dims, n_pairs, pair_left, pair_right, ratio, pair_ptr, query_idx,
+                           train_idx, distance, cap, total, timing ? tm : nullptr);
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba match_l2] upload_ms %.6f top2_ms %.6f compact_ms %.6f download_ms %.6f batches %d\n", tm[0], tm[1], tm[2], tm[3], (int)tm[4]);
+    if (rc == MATCH_L2_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "match_features_l2: output capacity too small");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "match_features_l2: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("match_features_l2: ") + hipGetErrorString((hipError_t)rc));
     return SFMBA_OK;
 }
 // ---- feature extraction (SfM::extractFeatures) ------------------------------------------------------------------------

@@ -85,6 +85,7 @@ std::string lowerExtension(const std::string& name) {
 SfM::SfM(const float downscale) :
         mConsoleDebugLevel(LOG_INFO),
         mDownscaleFactor(downscale),
+        mMergeFeatureMatchDistance(20.0f),                 // MERGE_CLOUD_FEATURE_MIN_MATCH_DISTANCE, SfM.cpp:51
         mFeaturesGiven(false),
         mDownscaleApplied(false),
         mCols(0), mRows(0),
@@ -356,7 +357,7 @@ bool SfM::triangulateAgainstGoodViews(int view) {
     }
     StageClock clock(sums, T_MERGE);
     for (size_t p = 0; p < n_pairs; p++) {
-        SfMAssociation::mergeNewPointCloud(mReconstructionCloud, clouds[p], mFeatureMatchMatrix);
+        SfMAssociation::mergeNewPointCloud(mReconstructionCloud, clouds[p], mFeatureMatchMatrix, nullptr, nullptr, nullptr, mMergeFeatureMatchDistance);
         say(LOG_DEBUG, "views " + std::to_string(left[p]) + " / " + std::to_string(right[p]) + ": " + std::to_string(clouds[p].size()) +
                        " points triangulated, cloud now " + std::to_string(mReconstructionCloud.size()));
     }

@@ -23,6 +23,10 @@
 //                 (the reference's unconditional assignment, SfM.cpp:431).  Then ONE triangulateViewsBatch call with the GLOBAL
 //                 poses, SfMAssociation::mergeNewPointCloud pair by pair in that order, adjustBundle if the batch triangulated,
 //                 and the view becomes good.
+//   merge         a match confirms a merge only if its distance is below setMergeFeatureMatchDistance's value, by default 20, the
+//                 reference's MERGE_CLOUD_FEATURE_MIN_MATCH_DISTANCE (SfM.cpp:51).  That constant is on the Hamming scale of ORB.
+//                 FLOAT descriptors given through setFeatures (CV_32F: matched by L2 distance) need a value on their own scale --
+//                 SIFT-scale distances are 100 to 300, and with 20 no new point would ever be confirmed into a track.
 //   end           every view is done.
 //   downscale     the factor of the constructor is applied by setImagesDirectory at load time, as in the reference (SfM.cpp:125-129): the
 //                 JPEG files and the PNG files in ONE decode call each that also resizes (SfMImageUtilities::readImages), the PNM
@@ -77,8 +81,17 @@ public:
     /** The images themselves, all CV_8U or all CV_8UC3, taken as they are (no downscale).  Forgets features given by setFeatures. */
     void setImages(const std::vector<cv::Mat>& images);
 
-    /** Key points (+ points) and descriptors of every view and the image size: runSfM then skips the extraction. */
+    /**
+     * Key points (+ points) and descriptors of every view and the image size: runSfM then skips the extraction.  The descriptors
+     * are all CV_8U (Hamming) or all CV_32F (L2; see setMergeFeatureMatchDistance).
+     */
     void setFeatures(const std::vector<Features>& imageFeatures, int cols, int rows);
+
+    /**
+     * The distance below which a feature match confirms a merge in SfMAssociation::mergeNewPointCloud.  Default 20, the reference's
+     * constant for ORB's Hamming distances; float descriptors need a value on the scale of their own L2 distances.
+     */
+    void setMergeFeatureMatchDistance(float maxDistance) { mMergeFeatureMatchDistance = maxDistance; }
 
     /** Run the pipeline (the contract is at the top of this file); every call starts from the images / features again. */
     ErrorCode runSfM();
@@ -123,6 +136,7 @@ private:
     std::vector<AddedView>    mAddedViews;
     unsigned int              mConsoleDebugLevel;
     float                     mDownscaleFactor;
+    float                     mMergeFeatureMatchDistance;
     bool                      mFeaturesGiven;
     bool                      mDownscaleApplied; // the images came from setImagesDirectory, which applied mDownscaleFactor
     int                       mCols, mRows;      // of image 0, or as given to setFeatures

@@ -1,5 +1,5 @@
 // SfM2DFeatureUtilities.cpp -- host side of the feature extractor and matcher: flattens the images / descriptor matrices, calls
-// the C ABI (include/sfmba.h, sfmba_orb_extract, sfmba_match_features) and rebuilds the reference's Features and Matching lists.
+// the C ABI (include/sfmba.h, sfmba_orb_extract, sfmba_match_features, sfmba_match_features_l2) and rebuilds the reference's Features and Matching lists.
 // See SfM2DFeatureUtilities.h.
 #include "SfM2DFeatureUtilities.h"
 
@@ -18,25 +18,29 @@ const double NN_MATCH_RATIO = 0.8f;     // SfM2DFeatureUtilities.cpp:35 -- a flo
 
 struct FlatDescriptors {
     std::vector<int64_t> ptr;
-    std::vector<unsigned char> bytes;
+    std::vector<unsigned char> bytes;       // the rows back to back: rowBytes bytes each (CV_8U) or rowBytes / 4 floats each (CV_32F)
     int rowBytes = 32;
+    int type = CV_8U;
 };
 
-// The descriptors of images[0..n-1] back to back; false (with a stderr line) if one is not CV_8U or the row lengths differ.
+// The descriptors of images[0..n-1] back to back; false (with a stderr line) if one is neither CV_8U nor CV_32F, the types are
+// mixed or the row lengths differ.  Decided before any device call.
 bool flatten(const std::vector<const Features*>& images, FlatDescriptors& f) {
     f.ptr.assign(images.size() + 1, 0);
-    int cols = -1;
+    int cols = -1, type = -1;
     for (size_t i = 0; i < images.size(); ++i) {
         const cv::Mat& d = images[i]->descriptors;
         const int rows = d.empty() ? 0 : d.rows;
         if (rows > 0) {
-            if (d.type() != CV_8U) { std::fprintf(stderr, "matchFeatures: descriptors must be CV_8U\n"); return false; }
+            if (d.type() != CV_8U && d.type() != CV_32F) { std::fprintf(stderr, "matchFeatures: descriptors must be CV_8U or CV_32F\n"); return false; }
+            if (type >= 0 && d.type() != type) { std::fprintf(stderr, "matchFeatures: descriptor types differ (CV_8U and CV_32F mixed)\n"); return false; }
             if (cols >= 0 && d.cols != cols) { std::fprintf(stderr, "matchFeatures: descriptor lengths differ\n"); return false; }
-            cols = d.cols;
+            cols = d.cols; type = d.type();
         }
         f.ptr[i + 1] = f.ptr[i] + rows;
     }
-    if (cols >= 0) f.rowBytes = cols;
+    if (type >= 0) f.type = type;
+    if (cols >= 0) f.rowBytes = cols * (f.type == CV_32F ? (int)sizeof(float) : 1);
     f.bytes.resize((size_t)f.ptr.back() * (size_t)f.rowBytes);
     for (size_t i = 0; i < images.size(); ++i) {
         const cv::Mat& d = images[i]->descriptors;
@@ -46,7 +50,8 @@ bool flatten(const std::vector<const Features*>& images, FlatDescriptors& f) {
     return true;
 }
 
-// One device call for the pair list; out[p] receives the Matching of pair p.
+// One device call for the pair list; out[p] receives the Matching of pair p.  CV_8U rows: Hamming (sfmba_match_features);
+// CV_32F rows: L2, what cv::BFMatcher does with NORM_L2 (sfmba_match_features_l2).
 bool matchPairs(const std::vector<const Features*>& images, const std::vector<int32_t>& left, const std::vector<int32_t>& right,
                 std::vector<Matching>& out) {
     out.assign(left.size(), Matching());
@@ -62,8 +67,13 @@ bool matchPairs(const std::vector<const Features*>& images, const std::vector<in
     int rc = SFMBA_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
         query.resize((size_t)cap + 1); train.resize((size_t)cap + 1); dist.resize((size_t)cap + 1);
-        rc = sfmba_match_features(0, (int)images.size(), f.ptr.data(), f.bytes.data(), f.rowBytes, n_pairs, left.data(), right.data(),
-                                  NN_MATCH_RATIO, ptr.data(), query.data(), train.data(), dist.data(), cap, &total);
+        if (f.type == CV_32F)
+            rc = sfmba_match_features_l2(0, (int)images.size(), f.ptr.data(), reinterpret_cast<const float*>(f.bytes.data()),
+                                         f.rowBytes / (int)sizeof(float), n_pairs, left.data(), right.data(), NN_MATCH_RATIO, ptr.data(),
+                                         query.data(), train.data(), dist.data(), cap, &total);
+        else
+            rc = sfmba_match_features(0, (int)images.size(), f.ptr.data(), f.bytes.data(), f.rowBytes, n_pairs, left.data(), right.data(),
+                                      NN_MATCH_RATIO, ptr.data(), query.data(), train.data(), dist.data(), cap, &total);
         if (rc == SFMBA_ERR_CAPACITY && attempt == 0) { cap = total; continue; }
         break;
     }

@@ -1,6 +1,6 @@
 // SfM2DFeatureUtilities.h -- the two entry points of the reference with their own signatures
-// (SfMToyLib/SfM2DFeatureUtilities.h:42-46), backed by the MI355X extractor and matcher (include/sfmba.h: sfmba_orb_extract,
-// sfmba_match_features), and the bodies of SfM::extractFeatures (SfMToyLib/SfM.cpp:141-154) and SfM::createFeatureMatchMatrix
+// (SfMToyLib/SfM2DFeatureUtilities.h:42-46), backed by the MI355X extractor and matchers (include/sfmba.h: sfmba_orb_extract,
+// sfmba_match_features, sfmba_match_features_l2), and the bodies of SfM::extractFeatures (SfMToyLib/SfM.cpp:141-154) and SfM::createFeatureMatchMatrix
 // (SfM.cpp:157-212) as free-standing functions over the members they read and write.
 // In the reference createFeatureMatchMatrix is a private member function; a maintainer replaces its body by one call
 // (INTEGRATION.md section 5):
@@ -10,7 +10,9 @@
 //   }
 //
 // Results are identical to the reference's: the same DMatch entries in the same order (queryIdx, trainIdx, imgIdx = 0,
-// distance), for descriptors of type CV_8U.
+// distance), for descriptors of type CV_8U.  Descriptors a caller brings through SfM::setFeatures may also be CV_32F (SIFT, SURF,
+// RootSIFT, learned ones): they are matched by exact L2 distance, as cv::BFMatcher does with NORM_L2 (the contract is
+// sfmba_match_features_l2's).  All non-empty descriptor matrices of a call must be of one type and one length.
 //
 // SfM::extractFeatures is replaced the same way, its loop over the images becoming one device call:
 //
@@ -45,8 +47,8 @@ public:
     Features extractFeatures(const cv::Mat& image);                          // a member function in the reference too (its detector is a member)
 
     /**
-     * Brute-force Hamming 2-NN of every left descriptor among the right ones, pruned by the ratio test
-     * (NN_MATCH_RATIO = 0.8f, SfM2DFeatureUtilities.cpp:53-71).  Fewer than 2 right descriptors give no matches (the
+     * Brute-force 2-NN (Hamming for CV_8U descriptors, L2 for CV_32F ones) of every left descriptor among the right ones, pruned
+     * by the ratio test (NN_MATCH_RATIO = 0.8f, SfM2DFeatureUtilities.cpp:53-71).  Mixed types are refused (empty result).  Fewer than 2 right descriptors give no matches (the
      * reference's behaviour is undefined there).  On a device error the result is empty and a line is written to stderr.
      */
     static Matching matchFeatures(

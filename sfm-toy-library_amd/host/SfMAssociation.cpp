@@ -15,7 +15,7 @@ namespace sfmtoylib {
 namespace {
 
 const float MERGE_CLOUD_POINT_MIN_MATCH_DISTANCE   = 0.01f;     // SfM.cpp:50
-const float MERGE_CLOUD_FEATURE_MIN_MATCH_DISTANCE = 20.0f;     // SfM.cpp:51
+// MERGE_CLOUD_FEATURE_MIN_MATCH_DISTANCE = 20 (SfM.cpp:51) is the default of mergeNewPointCloud's maxFeatureMatchDistance
 
 struct FlatCloudViews {
     std::vector<int64_t> ptr;
@@ -99,9 +99,9 @@ namespace {
 // (SfM.cpp:566-578), answered from an index built once per consulted pair instead of a scan per question.
 class PairIndex {
 public:
-    explicit PairIndex(const Matching& m) {
+    PairIndex(const Matching& m, float maxDistance) {
         for (size_t pos = 0; pos < m.size(); ++pos) {
-            if (!(m[pos].distance < MERGE_CLOUD_FEATURE_MIN_MATCH_DISTANCE)) continue;
+            if (!(m[pos].distance < maxDistance)) continue;
             const uint64_t key = ((uint64_t)(uint32_t)m[pos].queryIdx << 32) | (uint32_t)m[pos].trainIdx;
             first_.emplace(key, pos);                      // emplace keeps the FIRST position of a duplicate key
         }
@@ -117,7 +117,8 @@ private:
 }  // namespace
 
 bool SfMAssociation::mergeNewPointCloud(PointCloud& recon, const PointCloud& cloud, const MatchMatrix& featureMatchMatrix,
-                                        MatchMatrix* mergeMatchMatrix, size_t* newPointsOut, size_t* mergedPointsOut) {
+                                        MatchMatrix* mergeMatchMatrix, size_t* newPointsOut, size_t* mergedPointsOut,
+                                        float maxFeatureMatchDistance) {
     const size_t n_exist = recon.size(), n_new = cloud.size();
     size_t newPoints = 0, mergedPoints = 0;
     if (newPointsOut) *newPointsOut = 0;
@@ -152,7 +153,7 @@ bool SfMAssociation::mergeNewPointCloud(PointCloud& recon, const PointCloud& clo
         const Matching& m = featureMatchMatrix[(size_t)l][(size_t)r];
         if (m.empty()) return nullptr;
         auto it = indices.find(std::make_pair(l, r));
-        if (it == indices.end()) it = indices.emplace(std::make_pair(l, r), PairIndex(m)).first;
+        if (it == indices.end()) it = indices.emplace(std::make_pair(l, r), PairIndex(m, maxFeatureMatchDistance)).first;
         return &it->second;
     };
     std::vector<long> appendedAt(n_new, -1);               // position in recon of new point k, if it was appended

@@ -41,6 +41,8 @@ public:
      * one whose 2D features are confirmed by the match matrix adds its views to that point; a new point close to nothing is
      * appended; anything else is dropped.  mergeMatchMatrix (optional) receives the matches the reference collects for
      * its debug display (SfM.cpp:571); newPoints / mergedPoints the two counters it prints (SfM.cpp:626-628).
+     * maxFeatureMatchDistance: a match confirms only if its distance is below this (the reference's
+     * MERGE_CLOUD_FEATURE_MIN_MATCH_DISTANCE = 20, SfM.cpp:51, a Hamming-scale value: float descriptors need their own).
      * Returns false on a device error (reconstructionCloud untouched).
      */
     static bool mergeNewPointCloud(
@@ -49,7 +51,8 @@ public:
             const MatchMatrix& featureMatchMatrix,
             MatchMatrix*       mergeMatchMatrix = nullptr,
             size_t*            newPoints        = nullptr,
-            size_t*            mergedPoints     = nullptr);
+            size_t*            mergedPoints     = nullptr,
+            float              maxFeatureMatchDistance = 20.0f);
 };
 
 }  // namespace sfmtoylib

@@ -278,19 +278,21 @@ int64_t sfmba_shim_find_2d3d(int n_views, const unsigned char* done, int n_pt, c
 // Flat-array driver of sfmtoylib::SfMAssociation::mergeNewPointCloud.  The merged reconstruction cloud comes back flattened
 // (out_n points, views CSR); counts[0..1] = new / merged points; merge_pairs = (left, right, query, train) of the matches pushed to
 // the merge match matrix, row-major over the matrix.  Returns 0, -1 on device failure, -2 if an output capacity is too small.
+// sfmba_shim_merge_ex takes the feature-match distance below which a match confirms; sfmba_shim_merge is the default (20).
 extern "C" __attribute__((visibility("default")))
-int sfmba_shim_merge(int n_views, int n_exist, const float* ex_xyz, const int64_t* ex_view_ptr, const int32_t* ex_view_idx, const int32_t* ex_feat_idx,
-                     int n_new, const float* nw_xyz, const int64_t* nw_view_ptr, const int32_t* nw_view_idx, const int32_t* nw_feat_idx,
-                     int n_pairs, const int32_t* left, const int32_t* right, const int64_t* pair_ptr, const int32_t* query, const int32_t* train,
-                     const float* dist, int cap_pts, int64_t cap_views, int* out_n, float* out_xyz, int64_t* out_view_ptr, int32_t* out_view_idx,
-                     int32_t* out_feat_idx, int64_t* counts, int64_t cap_merge, int32_t* merge_pairs /*[cap_merge][4]*/, int64_t* n_merge) {
+int sfmba_shim_merge_ex(int n_views, int n_exist, const float* ex_xyz, const int64_t* ex_view_ptr, const int32_t* ex_view_idx, const int32_t* ex_feat_idx,
+                        int n_new, const float* nw_xyz, const int64_t* nw_view_ptr, const int32_t* nw_view_idx, const int32_t* nw_feat_idx,
+                        int n_pairs, const int32_t* left, const int32_t* right, const int64_t* pair_ptr, const int32_t* query, const int32_t* train,
+                        const float* dist, int cap_pts, int64_t cap_views, int* out_n, float* out_xyz, int64_t* out_view_ptr, int32_t* out_view_idx,
+                        int32_t* out_feat_idx, int64_t* counts, int64_t cap_merge, int32_t* merge_pairs /*[cap_merge][4]*/, int64_t* n_merge,
+                        float max_feature_match_distance) {
     using namespace sfmtoylib;
     PointCloud recon = buildCloud(n_exist, ex_xyz, ex_view_ptr, ex_view_idx, ex_feat_idx);
     const PointCloud fresh = buildCloud(n_new, nw_xyz, nw_view_ptr, nw_view_idx, nw_feat_idx);
     const MatchMatrix mm = buildMatchMatrix(n_views, n_pairs, left, right, pair_ptr, query, train, dist);
     MatchMatrix merged;
     size_t np = 0, nm = 0;
-    if (!SfMAssociation::mergeNewPointCloud(recon, fresh, mm, &merged, &np, &nm)) return -1;
+    if (!SfMAssociation::mergeNewPointCloud(recon, fresh, mm, &merged, &np, &nm, max_feature_match_distance)) return -1;
     counts[0] = (int64_t)np; counts[1] = (int64_t)nm;
     if ((int)recon.size() > cap_pts) return -2;
     *out_n = (int)recon.size();
@@ -310,6 +312,17 @@ int sfmba_shim_merge(int n_views, int n_exist, const float* ex_xyz, const int64_
             }
     *n_merge = m;
     return 0;
+}
+
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_merge(int n_views, int n_exist, const float* ex_xyz, const int64_t* ex_view_ptr, const int32_t* ex_view_idx, const int32_t* ex_feat_idx,
+                     int n_new, const float* nw_xyz, const int64_t* nw_view_ptr, const int32_t* nw_view_idx, const int32_t* nw_feat_idx,
+                     int n_pairs, const int32_t* left, const int32_t* right, const int64_t* pair_ptr, const int32_t* query, const int32_t* train,
+                     const float* dist, int cap_pts, int64_t cap_views, int* out_n, float* out_xyz, int64_t* out_view_ptr, int32_t* out_view_idx,
+                     int32_t* out_feat_idx, int64_t* counts, int64_t cap_merge, int32_t* merge_pairs /*[cap_merge][4]*/, int64_t* n_merge) {
+    return sfmba_shim_merge_ex(n_views, n_exist, ex_xyz, ex_view_ptr, ex_view_idx, ex_feat_idx, n_new, nw_xyz, nw_view_ptr, nw_view_idx, nw_feat_idx,
+                               n_pairs, left, right, pair_ptr, query, train, dist, cap_pts, cap_views, out_n, out_xyz, out_view_ptr, out_view_idx,
+                               out_feat_idx, counts, cap_merge, merge_pairs, n_merge, 20.0f);
 }
 
 // Flat-array driver of sfmtoylib::SfMExport::saveCloudAndCamerasToPLY (tests/test_ply_export.py).  images: n_views images of
@@ -346,12 +359,40 @@ std::vector<Features> buildDescriptors(int n_images, const int64_t* img_ptr, con
     }
     return feats;
 }
+std::vector<Features> buildFloatDescriptors(int n_images, const int64_t* img_ptr, const float* desc, int dims) {
+    std::vector<Features> feats((size_t)n_images);
+    for (int i = 0; i < n_images; ++i) {
+        const int rows = (int)(img_ptr[i + 1] - img_ptr[i]);
+        if (rows == 0) continue;                                  // an image without key points: an empty matrix
+        feats[i].descriptors = cv::Mat(rows, dims, CV_32F);
+        for (int r = 0; r < rows; ++r) std::memcpy(feats[i].descriptors.ptr<float>(r), desc + (size_t)(img_ptr[i] + r) * dims, sizeof(float) * (size_t)dims);
+    }
+    return feats;
+}
 int64_t flattenMatching(const Matching& m, int64_t at, int64_t cap, int32_t* query, int32_t* train, int32_t* img, float* dist) {
     for (const cv::DMatch& d : m) {
         if (at < cap) { query[at] = d.queryIdx; train[at] = d.trainIdx; img[at] = d.imgIdx; dist[at] = d.distance; }
         ++at;
     }
     return at;
+}
+// createFeatureMatchMatrix flattened: sizes [n_images * n_images] (row-major) and the entries in that order; -1 if the call reported
+// failure, -2 if the matrix is not n_images x n_images
+int64_t flattenMatchMatrix(const std::vector<sfmtoylib::Features>& feats, int n_images, int64_t* sizes, int64_t cap, int32_t* query, int32_t* train,
+                           int32_t* img_idx, float* dist) {
+    using namespace sfmtoylib;
+    MatchMatrix mm;
+    if (!SfMFeatureMatching::createFeatureMatchMatrix(feats, mm)) return -1;
+    if (mm.size() != (size_t)n_images) return -2;
+    int64_t n = 0;
+    for (int l = 0; l < n_images; ++l) {
+        if (mm[l].size() != (size_t)n_images) return -2;
+        for (int r = 0; r < n_images; ++r) {
+            sizes[(size_t)l * n_images + r] = (int64_t)mm[l][r].size();
+            n = flattenMatching(mm[l][r], n, cap, query, train, img_idx, dist);
+        }
+    }
+    return n;
 }
 }  // namespace
 
@@ -372,19 +413,34 @@ extern "C" __attribute__((visibility("default")))
 int64_t sfmba_shim_feature_match_matrix(int n_images, const int64_t* img_ptr, const unsigned char* desc, int desc_bytes, int64_t* sizes,
                                         int64_t cap, int32_t* query, int32_t* train, int32_t* img_idx, float* dist) {
     using namespace sfmtoylib;
-    const std::vector<Features> feats = buildDescriptors(n_images, img_ptr, desc, desc_bytes);
+    return flattenMatchMatrix(buildDescriptors(n_images, img_ptr, desc, desc_bytes), n_images, sizes, cap, query, train, img_idx, dist);
+}
+
+// The same two drivers for CV_32F descriptors of `dims` columns (tests/test_gpu_match_l2.py).
+extern "C" __attribute__((visibility("default")))
+int64_t sfmba_shim_match_features_f32(const int64_t* img_ptr /*[3]*/, const float* desc, int dims, int64_t cap, int32_t* query, int32_t* train,
+                                      int32_t* img_idx, float* dist) {
+    using namespace sfmtoylib;
+    const std::vector<Features> feats = buildFloatDescriptors(2, img_ptr, desc, dims);
+    return flattenMatching(SfM2DFeatureUtilities::matchFeatures(feats[0], feats[1]), 0, cap, query, train, img_idx, dist);
+}
+
+extern "C" __attribute__((visibility("default")))
+int64_t sfmba_shim_feature_match_matrix_f32(int n_images, const int64_t* img_ptr, const float* desc, int dims, int64_t* sizes, int64_t cap,
+                                            int32_t* query, int32_t* train, int32_t* img_idx, float* dist) {
+    return flattenMatchMatrix(buildFloatDescriptors(n_images, img_ptr, desc, dims), n_images, sizes, cap, query, train, img_idx, dist);
+}
+
+// createFeatureMatchMatrix over images whose descriptor matrices are of BOTH kinds: image i has rows[i] rows, CV_32F where is_f32[i],
+// CV_8U otherwise (all zero, 32 columns).  The shim must refuse before any device call (tests/test_match_l2_oracle_cpu.py): -1.
+extern "C" __attribute__((visibility("default")))
+int64_t sfmba_shim_feature_match_matrix_mixed(int n_images, const int32_t* rows, const unsigned char* is_f32) {
+    using namespace sfmtoylib;
+    std::vector<Features> feats((size_t)n_images);
+    for (int i = 0; i < n_images; ++i)
+        if (rows[i] > 0) feats[i].descriptors = cv::Mat(rows[i], 32, is_f32[i] ? CV_32F : CV_8U);
     MatchMatrix mm;
-    if (!SfMFeatureMatching::createFeatureMatchMatrix(feats, mm)) return -1;
-    if (mm.size() != (size_t)n_images) return -2;
-    int64_t n = 0;
-    for (int l = 0; l < n_images; ++l) {
-        if (mm[l].size() != (size_t)n_images) return -2;
-        for (int r = 0; r < n_images; ++r) {
-            sizes[(size_t)l * n_images + r] = (int64_t)mm[l][r].size();
-            n = flattenMatching(mm[l][r], n, cap, query, train, img_idx, dist);
-        }
-    }
-    return n;
+    return SfMFeatureMatching::createFeatureMatchMatrix(feats, mm) ? 0 : -1;
 }
 
 // Flat-array driver of sfmtoylib::SfMFeatureMatching::sortViewsForBaseline: the map comes back in key order as keys [cap] and
@@ -460,6 +516,14 @@ int64_t sfmba_shim_extract_features_batch(int n_images, const int64_t* img_ptr, 
 }
 
 namespace {
+// the key points (+ points) of view v: rows kp_ptr[v] .. kp_ptr[v+1]-1 of kp_xy [..][2]
+void addKeyPoints(std::vector<sfmtoylib::Features>& feats, const int64_t* kp_ptr, const float* kp_xy) {
+    for (size_t v = 0; v < feats.size(); ++v)
+        for (int64_t f = kp_ptr[v]; f < kp_ptr[v + 1]; ++f) {
+            cv::KeyPoint kp; kp.pt = cv::Point2f(kp_xy[2 * f], kp_xy[2 * f + 1]);
+            feats[v].keyPoints.push_back(kp); feats[v].points.push_back(kp.pt);
+        }
+}
 // What a finished run leaves, flattened as sfmba_shim_run_sfm documents it.
 int flattenRun(sfmtoylib::SfM& sfm, sfmtoylib::ErrorCode code, int n_views, float* poses, float* K, unsigned char* done, unsigned char* good, int* n_added,
                int32_t* added_view, unsigned char* added_posed, int64_t* added_cloud, int64_t cap_pts, int64_t cap_views, int64_t* n_pts, float* xyz,
@@ -511,11 +575,7 @@ int sfmba_shim_run_sfm(float downscale, int n_views, int channels, const int64_t
     sfm.setConsoleDebugLevel((unsigned)debug_level);
     if (channels == 0) {
         std::vector<Features> feats = buildDescriptors(n_views, kp_ptr, desc, 32);
-        for (int v = 0; v < n_views; ++v)
-            for (int64_t f = kp_ptr[v]; f < kp_ptr[v + 1]; ++f) {
-                cv::KeyPoint kp; kp.pt = cv::Point2f(kp_xy[2 * f], kp_xy[2 * f + 1]);
-                feats[v].keyPoints.push_back(kp); feats[v].points.push_back(kp.pt);
-            }
+        addKeyPoints(feats, kp_ptr, kp_xy);
         sfm.setFeatures(feats, cols, rows);
     } else {
         std::vector<cv::Mat> images;
@@ -524,6 +584,24 @@ int sfmba_shim_run_sfm(float downscale, int n_views, int channels, const int64_t
     }
     return flattenRun(sfm, sfm.runSfM(), n_views, poses, K, done, good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts, xyz,
                       view_ptr, view_idx, feat_idx, ply_prefix);
+}
+
+// sfmba_shim_run_sfm from features with CV_32F descriptors of `dims` columns (desc [..][dims]) and the merge distance of
+// SfM::setMergeFeatureMatchDistance (tests/test_gpu_match_l2_pipeline.py).  Outputs and return value as sfmba_shim_run_sfm.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_f32(int n_views, const int64_t* kp_ptr, const float* kp_xy, const float* desc, int dims, float merge_distance, int cols, int rows,
+                           int debug_level, float* poses, float* K, unsigned char* done, unsigned char* good, int* n_added, int32_t* added_view,
+                           unsigned char* added_posed, int64_t* added_cloud, int64_t cap_pts, int64_t cap_views, int64_t* n_pts, float* xyz,
+                           int64_t* view_ptr, int32_t* view_idx, int32_t* feat_idx) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    sfm.setMergeFeatureMatchDistance(merge_distance);
+    std::vector<Features> feats = buildFloatDescriptors(n_views, kp_ptr, desc, dims);
+    addKeyPoints(feats, kp_ptr, kp_xy);
+    sfm.setFeatures(feats, cols, rows);
+    return flattenRun(sfm, sfm.runSfM(), n_views, poses, K, done, good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts, xyz,
+                      view_ptr, view_idx, feat_idx, nullptr);
 }
 
 // Flat-array driver of sfmtoylib::SfM::setImagesDirectory (tests/test_sfm_scene_cpu.py; no device involved): the images come back
