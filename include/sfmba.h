@@ -840,6 +840,78 @@ SFMBA_API int sfmba_orb_extract(int device, int n_images, const int64_t* img_ptr
                 int32_t* dbg_level_xy /*[cap][2] or NULL*/, int32_t* dbg_bin /*[cap] or NULL*/, int64_t* dbg_harris /*[cap] or NULL*/,
                 int32_t* dbg_candidates /*[n_images][n_levels] or NULL*/);
 
+/*
+ * Extract FLOAT descriptors of a batch of images in one call: a Fast-Hessian detector and a SURF-style descriptor of 64 floats, the
+ * extractor that goes with sfmba_match_features_l2 (the reference's lineage ran SURF_GPU in front of BruteForceMatcher_GPU<L2<float>>,
+ * legacy/SfMToyLib_Old/GPUSURFFeatureMatcher.cpp:56).  THIS CONTRACT IS OUR OWN -- it is not, and does not claim to be,
+ * cv::xfeatures2d::SURF.  Everything up to the final normalisation is box sums over an integral image of 8-bit pixels, exact integer
+ * arithmetic, so the device is held BIT FOR BIT to a CPU restatement of itself (tests/surf_oracle.py).  Departures from SURF: no
+ * sub-pixel or sub-scale interpolation of the extremum, one Gaussian over the whole descriptor window, orientation from the weighted
+ * resultant of the Haar responses in 30 bins.  Match quality under rotation and scale is reported (README), not guaranteed.
+ *
+ *   images        as sfmba_orb_extract: image i owns bytes img_ptr[i] .. img_ptr[i+1]-1 of pixels, rows tight; the same gray rule.
+ *   box sum       Box(y0, x0, h, w) = the sum of the gray values over rows y0 .. y0+h-1 and columns x0 .. x0+w-1, pixels outside the
+ *                 image counting 0: the four coordinates are clamped into [0, height] x [0, width] of the integral image, and nothing
+ *                 outside the integral image is ever read.  The integral image is kept mod 2^32; every box used is below 2^32.
+ *                 All integer quantities below are int64 unless stated otherwise.
+ *   layers        octave o (0-based) has four filter sizes L = 3 (2^(o+1) (i + 1) + 1), i = 0..3: 9 15 21 27 / 15 27 39 51 /
+ *                 27 51 75 99 / 51 99 147 195.  Lobe l = L / 3, b = (L - 1) / 2.  Grid step s = 2^o, positions x = s i, y = s j inside
+ *                 the image.
+ *   responses     Dyy = Box(y-b, x-l+1, L, 2l-1) - 3 Box(y-(l-1)/2, x-l+1, l, 2l-1),
+ *                 Dxx = Box(y-l+1, x-b, 2l-1, L) - 3 Box(y-l+1, x-(l-1)/2, 2l-1, l),
+ *                 Dxy = Box(y-l, x+1, l, l) + Box(y+1, x-l, l, l) - Box(y-l, x-l, l, l) - Box(y+1, x+1, l, l),
+ *                 N = 100 Dxx Dyy - 81 Dxy^2 (|N| < 2^53), H = (double)N / (double)(100 L^4): one IEEE division, the only
+ *                 floating-point operation of the detector.  laplacian = (Dxx + Dyy >= 0) ? 1 : -1.
+ *   candidates    the middle layers m = 1, 2 of every octave are searched.  With bt = (L_{m+1} - 1) / 2, a grid position is a
+ *                 candidate iff x - s - bt >= 0, x + s + bt <= width - 1 and likewise in y (none of the 27 filters involved is clipped;
+ *                 an image narrower or lower than 24 has no key points), H > (double)hessian_threshold, and H is strictly greater than
+ *                 all 26 neighbours: grid steps +-s in the layers m-1, m, m+1 of the same octave.  Equal neighbours drop each other.
+ *   selection     per image the first n_features candidates in the total order (H descending, then octave, layer, y, x ascending);
+ *                 that is also the output order.
+ *   Haar          HaarX(y, x, p) = Box(y-p, x, 2p, p) - Box(y-p, x-p, 2p, p), HaarY(y, x, p) = Box(y, x-p, p, 2p) - Box(y-p, x-p, p, 2p).
+ *                 The scale sigma = 0.4 l is held as a rational: r = floor((4 l + 5) / 10), rnd(i) = floor((4 l i + 5) / 10), floor
+ *                 division throughout, also for negatives.
+ *   orientation   (upright == 0) over integer (i, j) with i^2 + j^2 < 36 (109 samples): mx += Wg(i,j) HaarX(y + rnd(j), x + rnd(i), 2r),
+ *                 my likewise with HaarY.  Wg(i,j) = floor(65536 exp(-(i^2 + j^2) / 12.5) + 0.5), as [|j|][|i|] for 0..5:
+ *                   65536 60497 47589 31900 18221 8869 / 60497 55846 43930 29447 16821 8187 / 47589 43930 34557 23164 13231 6440 /
+ *                   31900 29447 23164 15527 8869 4317 / 18221 16821 13231 8869 5066 2466 / 8869 8187 6440 4317 2466 1200
+ *                 The bin is the lowest k in 0..29 that maximises mx C_k + my S_k with the C_k, S_k of sfmba_orb_extract.
+ *                 upright == 1: bin 0, moments reported as 0.
+ *   descriptor    with C, S of the bin and d = 5 * 16384, for i, j in -10..9, a = 2i + 1, b = 2j + 1:
+ *                 ox = floor((2 l (C a - S b) + d) / (2d)), oy = floor((2 l (S a + C b) + d) / (2d)); hx, hy = HaarX / HaarY(y + oy,
+ *                 x + ox, r); dx = C hx + S hy, dy = -S hx + C hy; w = Wd(a,b) = floor(4096 exp(-(a^2 + b^2) / 87.12) + 0.5), as
+ *                 [(|b|-1)/2][(|a|-1)/2] for |a|, |b| = 1, 3, .. 19:
+ *                   4003 3652 3039 2307 1598 1010 582 306 147 64 / 3652 3331 2772 2105 1458 921 531 279 134 59 /
+ *                   3039 2772 2307 1752 1213 767 442 232 111 49 / 2307 2105 1752 1330 921 582 335 176 85 37 /
+ *                   1598 1458 1213 921 638 403 232 122 59 26 / 1010 921 767 582 403 255 147 77 37 16 /
+ *                   582 531 442 335 232 147 85 44 21 9 / 306 279 232 176 122 77 44 23 11 5 /
+ *                   147 134 111 85 59 37 21 11 5 2 / 64 59 49 37 26 16 9 5 2 1
+ *                 Sub-region p = floor((i + 10) / 5), q = floor((j + 10) / 5), base = (4q + p) 4: v[base] += w dx, v[base+1] += w dy,
+ *                 v[base+2] += w |dx|, v[base+3] += w |dy|.  Every |v| stays below 2^53 for n_octaves <= 4 (bound 4.8e14).
+ *   normalisation M = max |v|, sh = max(0, bitlength(M) - 23), t_d = v_d >> sh (arithmetic shift), n2 = sum t_d^2 (exact, below 2^52),
+ *                 desc_d = (float)((double)t_d / sqrt((double)n2)): a correctly rounded double square root, one double division, one
+ *                 rounding to float.  n2 == 0 gives 64 zeros.  No step has a multiply followed by an add.
+ *   key point     x = (float)x, y = (float)y, size = (float)L, angle = 12 bin degrees, response = (float)H, octave = o, layer = m,
+ *                 laplacian as above.
+ *
+ * Outputs: kp_ptr [n_images + 1], kp [cap], desc [cap][64]; desc and kp_ptr go into sfmba_match_features_l2 as they come (as desc /
+ * img_ptr with dims = 64).  Optional (NULL or not): dbg_bin [cap], dbg_moments [cap][2] = (mx, my), dbg_sums [cap][64] = v,
+ * dbg_candidates [n_images][n_octaves][2] = the number of candidates of layers 1 and 2 of every octave before the cut.  Host pointers
+ * in and out, synchronous.  *total receives the number of key points; SFMBA_ERR_CAPACITY (kp_ptr and *total valid, nothing else
+ * written) if cap < *total; cap >= n_images * n_features always suffices.  SFMBA_ERR_INVALID_ARG (nothing written) for whatever
+ * sfmba_orb_extract refuses about images, n_features < 1, n_octaves outside 1..4, a hessian_threshold that is not finite or is
+ * negative, upright other than 0 or 1.  Deterministic: the same arguments give the same bytes, the result does not depend on how the
+ * work is cut up (images go to the device in consecutive groups under a fixed scratch bound); a batch equals the concatenation of
+ * single-image calls.  SFMBA_ABI_VERSION stays as it is: adding a symbol is backward compatible.
+ */
+typedef struct sfmba_surf_keypoint { float x, y, size, angle, response; int32_t octave, layer, laplacian; } sfmba_surf_keypoint;
+SFMBA_API int sfmba_surf_extract(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/,
+                int n_features, int n_octaves /*1..4*/, float hessian_threshold, int upright /*0 or 1*/,
+                int64_t* kp_ptr /*[n_images+1]*/, sfmba_surf_keypoint* kp, float* desc /*[cap][64]*/, int64_t cap, int64_t* total,
+                int32_t* dbg_bin /*[cap] or NULL*/, int64_t* dbg_moments /*[cap][2] or NULL*/, int64_t* dbg_sums /*[cap][64] or NULL*/,
+                int32_t* dbg_candidates /*[n_images][n_octaves][2] or NULL*/);
+
 /* ---- reading photographs: baseline JPEG decode and bilinear resize (SfM::setImagesDirectory) -----------------------------------
  * The reference reads every image with imread and shrinks it with resize(..., Size(), f, f) (SfMToyLib/SfM.cpp:125-129).  Here a
  * whole list of files is decoded, and a whole list of images resized, in one call each.  THE CONTRACT IS INTEGER-EXACT: the decode

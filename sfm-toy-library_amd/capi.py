@@ -37,7 +37,7 @@ SYMBOLS = [
     "sfmba_match_features", "sfmba_problem_set_step_probe", "sfmba_problem_get_step_probe", "sfmba_pnp_ransac",
     "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_orb_extract", "sfmba_triangulate_pairs",
     "sfmba_jpeg_info", "sfmba_resized_size", "sfmba_jpeg_decode", "sfmba_resize_images",
-    "sfmba_png_info", "sfmba_png_decode", "sfmba_match_features_l2",
+    "sfmba_png_info", "sfmba_png_decode", "sfmba_match_features_l2", "sfmba_surf_extract",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -313,6 +313,55 @@ def orb_extract(images, n_features=5000, scale_factor=1.2, n_levels=8, fast_thre
         a, b = int(kp_ptr[i]), int(kp_ptr[i + 1])
         if debug:
             out.append((kp[a:b].copy(), desc[a:b].copy(), lxy[a:b].copy(), bn[a:b].copy(), hr[a:b].copy(), cand[i].copy()))
+        else:
+            out.append((kp[a:b].copy(), desc[a:b].copy()))
+    return out
+
+
+SURF_KEYPOINT = np.dtype([("x", np.float32), ("y", np.float32), ("size", np.float32), ("angle", np.float32), ("response", np.float32),
+                          ("octave", np.int32), ("layer", np.int32), ("laplacian", np.int32)])          # sfmba_surf_keypoint
+
+
+def surf_extract(images, n_features=5000, n_octaves=4, hessian_threshold=100.0, upright=0, cap=None, debug=False, device=0):
+    """sfmba_surf_extract: Fast-Hessian key points and 64-float descriptors of every image of a batch (the contract is in include/sfmba.h).
+
+    images: as orb_extract.  Returns one tuple per image: (kp, desc) with kp a record array of SURF_KEYPOINT and desc float32 [n, 64];
+    with debug=True (kp, desc, bin int32 [n], moments int64 [n, 2], sums int64 [n, 64], candidates int32 [n_octaves, 2]).  cap=None
+    sizes the outputs for n_features per image; a smaller cap is retried once with the size the library reports."""
+    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+    kinds = {(im.ndim, im.shape[2] if im.ndim == 3 else 1) for im in imgs}
+    if len(kinds) > 1 or any(k not in ((2, 1), (3, 3)) for k in kinds):
+        raise ValueError("images must all be h x w or all be h x w x 3 uint8 arrays")
+    channels = kinds.pop()[1] if kinds else 1
+    n = len(imgs)
+    img_ptr = np.zeros(n + 1, dtype=np.int64)
+    img_ptr[1:] = np.cumsum([im.size for im in imgs])
+    flat = np.ascontiguousarray(np.concatenate([im.reshape(-1) for im in imgs]) if imgs else np.zeros(0, np.uint8))
+    wd = np.asarray([im.shape[1] for im in imgs], dtype=np.int32)
+    ht = np.asarray([im.shape[0] for im in imgs], dtype=np.int32)
+    cap = int(n * max(n_features, 0) if cap is None else cap)
+    lp, bp, fp = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte), C.POINTER(C.c_float)
+    kp_ptr = np.zeros(n + 1, dtype=np.int64)
+    total = C.c_int64(0)
+    cand = np.zeros((max(n, 1), max(n_octaves, 1), 2), np.int32)
+    for _ in range(2):
+        kp = np.zeros(max(cap, 1), SURF_KEYPOINT)
+        desc = np.zeros((max(cap, 1), 64), np.float32)
+        bn, mom, sm = np.zeros(max(cap, 1), np.int32), np.zeros((max(cap, 1), 2), np.int64), np.zeros((max(cap, 1), 64), np.int64)
+        rc = lib().sfmba_surf_extract(C.c_int(device), C.c_int(n), _p(img_ptr, lp), flat.ctypes.data_as(bp), _p(wd, _ip), _p(ht, _ip),
+                                      C.c_int(channels), C.c_int(n_features), C.c_int(n_octaves), C.c_float(hessian_threshold),
+                                      C.c_int(upright), _p(kp_ptr, lp), kp.ctypes.data_as(C.c_void_p), desc.ctypes.data_as(fp),
+                                      C.c_int64(cap), C.byref(total), _p(bn, _ip) if debug else None, _p(mom, lp) if debug else None,
+                                      _p(sm, lp) if debug else None, _p(cand, _ip) if debug else None)
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        cap = int(total.value)
+    _check(rc)
+    out = []
+    for i in range(n):
+        a, b = int(kp_ptr[i]), int(kp_ptr[i + 1])
+        if debug:
+            out.append((kp[a:b].copy(), desc[a:b].copy(), bn[a:b].copy(), mom[a:b].copy(), sm[a:b].copy(), cand[i].copy()))
         else:
             out.append((kp[a:b].copy(), desc[a:b].copy()))
     return out

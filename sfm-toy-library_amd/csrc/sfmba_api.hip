@@ -10,6 +10,7 @@
 #include "homography_ransac.h"
 #include "essential_ransac.h"
 #include "orb_extract.h"
+#include "surf_extract.h"
 #include "jpeg_decode.h"
 #include "jpeg_math.h"
 #include "png_decode.h"
@@ -620,6 +621,43 @@ int sfmba_orb_extract(int device, int n_images, const int64_t* img_ptr, const un
     if (rc == ORB_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "orb_extract: output capacity too small");
     if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "orb_extract: device allocation failed");
     if (rc) return fail(SFMBA_ERR_HIP, std::string("orb_extract: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+// ---- float descriptors: Fast-Hessian detect and SURF-style describe, the extractor in front of sfmba_match_features_l2 ---------
+int sfmba_surf_extract(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                       int channels, int n_features, int n_octaves, float hessian_threshold, int upright, int64_t* kp_ptr, sfmba_surf_keypoint* kp,
+                       float* desc, int64_t cap, int64_t* total, int32_t* dbg_bin, int64_t* dbg_moments, int64_t* dbg_sums, int32_t* dbg_candidates) {
+    if (n_images < 0 || cap < 0 || !img_ptr || !kp_ptr || !total || (n_images > 0 && (!width || !height)) || (cap > 0 && (!kp || !desc)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: channels must be 1 or 3");
+    if (n_features < 1) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: n_features must be >= 1");
+    if (n_octaves < 1 || n_octaves > 4) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: n_octaves must be in 1..4");
+    if (!std::isfinite(hessian_threshold) || hessian_threshold < 0.0f)
+        return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: hessian_threshold must be finite and >= 0");
+    if (upright != 0 && upright != 1) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: upright must be 0 or 1");
+    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
+            return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: an image dimension lies outside 1..16384");
+        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
+            return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: img_ptr does not agree with width * height * channels");
+    }
+    if (n_images > 0 && !pixels) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    // SFMBA_SURF_TIMING: one stderr line per call with the HIP-event times of its phases (tools/surf_bench.py)
+    double tm[SURF_T_COUNT];
+    const bool timing = std::getenv("SFMBA_SURF_TIMING") != nullptr;
+    rc = surf_extract(ck.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, n_features, n_octaves, hessian_threshold, upright,
+                      kp_ptr, kp, desc, cap, total, dbg_bin, dbg_moments, dbg_sums, dbg_candidates, timing ? tm : nullptr);
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba surf] upload_ms %.6f integral_ms %.6f response_ms %.6f candidates_ms %.6f select_ms %.6f describe_ms %.6f "
+                     "download_ms %.6f groups %d response_bytes %.0f\n", tm[SURF_T_UPLOAD], tm[SURF_T_INTEGRAL], tm[SURF_T_RESPONSE],
+                     tm[SURF_T_CANDIDATES], tm[SURF_T_SELECT], tm[SURF_T_DESCRIBE], tm[SURF_T_DOWNLOAD], (int)tm[SURF_T_GROUPS], tm[SURF_T_RESPONSE_BYTES]);
+    if (rc == SURF_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "surf_extract: output capacity too small");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "surf_extract: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("surf_extract: ") + hipGetErrorString((hipError_t)rc));
     return SFMBA_OK;
 }
 // ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------

@@ -86,6 +86,7 @@ SfM::SfM(const float downscale) :
         mConsoleDebugLevel(LOG_INFO),
         mDownscaleFactor(downscale),
         mMergeFeatureMatchDistance(20.0f),                 // MERGE_CLOUD_FEATURE_MIN_MATCH_DISTANCE, SfM.cpp:51
+        mFeatureType(FEATURES_ORB),
         mFeaturesGiven(false),
         mDownscaleApplied(false),
         mCols(0), mRows(0),
@@ -220,7 +221,7 @@ ErrorCode SfM::runSfM() {
     if (!mFeaturesGiven) {
         say(LOG_INFO, "stage 1: features of " + std::to_string(n_views) + " images");
         StageClock clock(sums, T_EXTRACT);
-        if (!SfMFeatureExtraction::extractFeatures(mImages, mImageFeatures)) return ERROR;
+        if (!SfMFeatureExtraction::extractFeatures(mImages, mImageFeatures, mFeatureType)) return ERROR;
     }
     say(LOG_INFO, "stage 2: match matrix");
     {

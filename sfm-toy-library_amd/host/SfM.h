@@ -27,6 +27,10 @@
 //                 reference's MERGE_CLOUD_FEATURE_MIN_MATCH_DISTANCE (SfM.cpp:51).  That constant is on the Hamming scale of ORB.
 //                 FLOAT descriptors given through setFeatures (CV_32F: matched by L2 distance) need a value on their own scale --
 //                 SIFT-scale distances are 100 to 300, and with 20 no new point would ever be confirmed into a track.
+//                 The other way round for setFeatureType(FEATURES_SURF): its descriptors are of unit length, their distances are
+//                 <= 2, so the default 20 CONFIRMS EVERY MATCH.  A better default is not chosen here: nobody has measured one.
+//   features      setFeatureType chooses the extractor of a run from images: FEATURES_ORB (the default; binary rows, Hamming) or
+//                 FEATURES_SURF (sfmba_surf_extract: 64 floats, the L2 branch of the matcher).  It has no effect after setFeatures.
 //   end           every view is done.
 //   downscale     the factor of the constructor is applied by setImagesDirectory at load time, as in the reference (SfM.cpp:125-129): the
 //                 JPEG files and the PNG files in ONE decode call each that also resizes (SfMImageUtilities::readImages), the PNM
@@ -43,6 +47,7 @@
 
 #include "SfMCommon.h"
 #include "SfMAssociation.h"
+#include "SfM2DFeatureUtilities.h"
 
 namespace sfmtoylib {
 
@@ -93,6 +98,13 @@ public:
      */
     void setMergeFeatureMatchDistance(float maxDistance) { mMergeFeatureMatchDistance = maxDistance; }
 
+    /**
+     * The extractor runSfM uses on images: FEATURES_ORB (default) or FEATURES_SURF (float rows of unit length, matched by L2).  The
+     * merge distance stays what setMergeFeatureMatchDistance says; its default 20 confirms every match of unit-length descriptors
+     * (their distances are <= 2).
+     */
+    void setFeatureType(FeatureType type) { mFeatureType = type; }
+
     /** Run the pipeline (the contract is at the top of this file); every call starts from the images / features again. */
     ErrorCode runSfM();
 
@@ -137,6 +149,7 @@ private:
     unsigned int              mConsoleDebugLevel;
     float                     mDownscaleFactor;
     float                     mMergeFeatureMatchDistance;
+    FeatureType               mFeatureType;
     bool                      mFeaturesGiven;
     bool                      mDownscaleApplied; // the images came from setImagesDirectory, which applied mDownscaleFactor
     int                       mCols, mRows;      // of image 0, or as given to setFeatures

@@ -1,5 +1,5 @@
 // SfM2DFeatureUtilities.cpp -- host side of the feature extractor and matcher: flattens the images / descriptor matrices, calls
-// the C ABI (include/sfmba.h, sfmba_orb_extract, sfmba_match_features, sfmba_match_features_l2) and rebuilds the reference's Features and Matching lists.
+// the C ABI (include/sfmba.h, sfmba_orb_extract, sfmba_surf_extract, sfmba_match_features, sfmba_match_features_l2) and rebuilds the reference's Features and Matching lists.
 // See SfM2DFeatureUtilities.h.
 #include "SfM2DFeatureUtilities.h"
 
@@ -101,13 +101,27 @@ Features SfM2DFeatureUtilities::extractFeatures(const cv::Mat& image) {
     return out[0];
 }
 
+Features SfM2DFeatureUtilities::extractFeatures(const cv::Mat& image, FeatureType type) {
+    std::vector<Features> out;
+    if (!SfMFeatureExtraction::extractFeatures(std::vector<cv::Mat>(1, image), out, type)) return Features();
+    return out[0];
+}
+
 bool SfMFeatureExtraction::extractFeatures(const std::vector<cv::Mat>& images, std::vector<Features>& imageFeatures) {
+    return extractFeatures(images, imageFeatures, FEATURES_ORB);
+}
+
+bool SfMFeatureExtraction::extractFeatures(const std::vector<cv::Mat>& images, std::vector<Features>& imageFeatures, FeatureType featureType) {
     const int ORB_FEATURES = 5000;                                            // ORB::create(5000), SfM2DFeatureUtilities.cpp:40
     const float ORB_SCALE = 1.2f;                                             // OpenCV's defaults for the rest
     const int ORB_LEVELS = 8, ORB_FAST_THRESHOLD = 20;
+    const int SURF_FEATURES = 5000, SURF_OCTAVES = 4, SURF_UPRIGHT = 0;       // the float-descriptor unit's defaults
+    const float SURF_THRESHOLD = 100.0f;
     const size_t n = images.size();
     imageFeatures.assign(n, Features());
+    if (featureType != FEATURES_ORB && featureType != FEATURES_SURF) { std::fprintf(stderr, "extractFeatures: unknown feature type\n"); return false; }
     if (n == 0) return true;
+    const bool surf = featureType == FEATURES_SURF;
     std::vector<int64_t> ptr(n + 1, 0), kp_ptr(n + 1, 0);
     std::vector<int32_t> width(n), height(n);
     const int type = images[0].type();
@@ -125,13 +139,21 @@ bool SfMFeatureExtraction::extractFeatures(const std::vector<cv::Mat>& images, s
             std::memcpy(&pixels[(size_t)ptr[i] + (size_t)r * row], images[i].ptr<unsigned char>(r), row);
     }
     std::vector<sfmba_orb_keypoint> kp;
+    std::vector<sfmba_surf_keypoint> skp;
     std::vector<unsigned char> desc;
-    int64_t cap = (int64_t)n * ORB_FEATURES, total = 0;
+    std::vector<float> sdesc;
+    int64_t cap = (int64_t)n * (surf ? SURF_FEATURES : ORB_FEATURES), total = 0;
     int rc = SFMBA_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        kp.resize((size_t)cap + 1); desc.resize(((size_t)cap + 1) * 32);
-        rc = sfmba_orb_extract(0, (int)n, ptr.data(), pixels.data(), width.data(), height.data(), channels, ORB_FEATURES, ORB_SCALE, ORB_LEVELS,
-                               ORB_FAST_THRESHOLD, kp_ptr.data(), kp.data(), desc.data(), cap, &total, nullptr, nullptr, nullptr, nullptr);
+        if (surf) {
+            skp.resize((size_t)cap + 1); sdesc.resize(((size_t)cap + 1) * 64);
+            rc = sfmba_surf_extract(0, (int)n, ptr.data(), pixels.data(), width.data(), height.data(), channels, SURF_FEATURES, SURF_OCTAVES,
+                                    SURF_THRESHOLD, SURF_UPRIGHT, kp_ptr.data(), skp.data(), sdesc.data(), cap, &total, nullptr, nullptr, nullptr, nullptr);
+        } else {
+            kp.resize((size_t)cap + 1); desc.resize(((size_t)cap + 1) * 32);
+            rc = sfmba_orb_extract(0, (int)n, ptr.data(), pixels.data(), width.data(), height.data(), channels, ORB_FEATURES, ORB_SCALE, ORB_LEVELS,
+                                   ORB_FAST_THRESHOLD, kp_ptr.data(), kp.data(), desc.data(), cap, &total, nullptr, nullptr, nullptr, nullptr);
+        }
         if (rc == SFMBA_ERR_CAPACITY && attempt == 0) { cap = total; continue; }
         break;
     }
@@ -144,14 +166,21 @@ bool SfMFeatureExtraction::extractFeatures(const std::vector<cv::Mat>& images, s
         const int rows = (int)(kp_ptr[i + 1] - kp_ptr[i]);
         f.keyPoints.reserve((size_t)rows);
         f.points.reserve((size_t)rows);
-        if (rows > 0) f.descriptors = cv::Mat(rows, 32, CV_8U);
+        if (rows > 0) f.descriptors = surf ? cv::Mat(rows, 64, CV_32F) : cv::Mat(rows, 32, CV_8U);
         for (int r = 0; r < rows; ++r) {
-            const sfmba_orb_keypoint& k = kp[(size_t)kp_ptr[i] + (size_t)r];
+            const size_t at = (size_t)kp_ptr[i] + (size_t)r;
             cv::KeyPoint c;
-            c.pt = cv::Point2f(k.x, k.y); c.size = k.size; c.angle = k.angle; c.response = k.response; c.octave = k.octave; c.class_id = -1;
+            if (surf) {
+                const sfmba_surf_keypoint& k = skp[at];
+                c.pt = cv::Point2f(k.x, k.y); c.size = k.size; c.angle = k.angle; c.response = k.response; c.octave = k.octave; c.class_id = k.laplacian;
+                std::memcpy(f.descriptors.ptr<unsigned char>(r), &sdesc[at * 64], 64 * sizeof(float));
+            } else {
+                const sfmba_orb_keypoint& k = kp[at];
+                c.pt = cv::Point2f(k.x, k.y); c.size = k.size; c.angle = k.angle; c.response = k.response; c.octave = k.octave; c.class_id = -1;
+                std::memcpy(f.descriptors.ptr<unsigned char>(r), &desc[at * 32], 32);
+            }
             f.keyPoints.push_back(c);
             f.points.push_back(c.pt);                                         // KeyPointsToPoints, SfMCommon.h
-            std::memcpy(f.descriptors.ptr<unsigned char>(r), &desc[((size_t)kp_ptr[i] + (size_t)r) * 32], 32);
         }
     }
     return true;

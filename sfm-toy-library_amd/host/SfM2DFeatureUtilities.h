@@ -25,6 +25,12 @@
 // fixed-point resampling and smoothing, no mask) with the reference's parameters: 5000 features, scale 1.2, 8 levels, FAST
 // threshold 20.
 //
+// FLOAT DESCRIPTORS: extractFeatures takes an extractor choice, FeatureType.  FEATURES_ORB (the default everywhere) is the unit
+// above; FEATURES_SURF runs the project's Fast-Hessian / SURF-style contract (include/sfmba.h, sfmba_surf_extract -- not
+// cv::xfeatures2d::SURF: no sub-pixel or sub-scale interpolation, one Gaussian over the descriptor window, 30 orientation bins)
+// with 5000 features, 4 octaves, threshold 100, oriented.  Its descriptors are CV_32F rows of 64 of unit length, which matchFeatures
+// and createFeatureMatchMatrix take through their L2 branch.
+//
 // The consumer of the whole matrix, SfM::sortViewsForBaseline (SfMToyLib/SfM.cpp:333-364), is restated the same way:
 //
 //   map<float, ImagePair> SfM::sortViewsForBaseline() {
@@ -38,6 +44,8 @@
 
 namespace sfmtoylib {
 
+enum FeatureType { FEATURES_ORB = 0, FEATURES_SURF = 1 };
+
 class SfM2DFeatureUtilities {
 public:
     /**
@@ -45,6 +53,12 @@ public:
      * image (SfM2DFeatureUtilities.cpp:46-51).  On a device error the features are empty and a line is written to stderr.
      */
     Features extractFeatures(const cv::Mat& image);                          // a member function in the reference too (its detector is a member)
+
+    /**
+     * The same with the extractor named: FEATURES_ORB is the call above; FEATURES_SURF gives a CV_32F n x 64 descriptor matrix
+     * (key point: size = the filter size L, octave = the octave, class_id = the sign of the Laplacian, as OpenCV's SURF stores it).
+     */
+    Features extractFeatures(const cv::Mat& image, FeatureType type);
 
     /**
      * Brute-force 2-NN (Hamming for CV_8U descriptors, L2 for CV_32F ones) of every left descriptor among the right ones, pruned
@@ -66,6 +80,12 @@ public:
     static bool extractFeatures(
             const std::vector<cv::Mat>& images,
             std::vector<Features>&      imageFeatures);
+
+    /** The same with the extractor named (FEATURES_ORB: the call above).  An unknown type is refused (false, a stderr line). */
+    static bool extractFeatures(
+            const std::vector<cv::Mat>& images,
+            std::vector<Features>&      imageFeatures,
+            FeatureType                 type);
 };
 
 class SfMFeatureMatching {

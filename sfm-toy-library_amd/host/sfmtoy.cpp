@@ -19,6 +19,9 @@ void usage(std::ostream& os, const char* program) {
        << "  -s, --downscale F            factor applied to every image at load time (default 1)\n"
        << "  -d, --console-debug N        console log level, 0 = trace .. 4 = error (default 2)\n"
        << "  -o, --output-prefix PREFIX   PREFIX_points.ply and PREFIX_cameras.ply (default output)\n"
+       << "  -f, --features orb|surf      the extractor: orb (binary rows, Hamming; the default) or surf (64 floats, L2)\n"
+       << "  -m, --merge-distance F       distance below which a match confirms a merge (default 20: ORB's Hamming scale; unit-length\n"
+       << "                               float rows never lie further than 2 apart, so 20 confirms every match of theirs)\n"
        << "  -v, --visual-debug N         accepted and ignored: there is no visual debugging\n";
 }
 
@@ -43,7 +46,8 @@ bool number(const std::string& text, double& value) {
 
 int main(int argc, char** argv) {
     std::string directory, prefix = "output", text;
-    double downscale = 1.0, level = LOG_INFO, ignored = 0.0;
+    double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0;
+    FeatureType features = FEATURES_ORB;
     bool have_directory = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
@@ -53,6 +57,11 @@ int main(int argc, char** argv) {
         else if (option(argc, argv, i, "-o", "--output-prefix", text, missing)) prefix = text;
         else if (option(argc, argv, i, "-s", "--downscale", text, missing)) bad = !missing && (!number(text, downscale) || !(downscale > 0.0));
         else if (option(argc, argv, i, "-d", "--console-debug", text, missing)) bad = !missing && (!number(text, level) || level < 0.0 || level > 4.0);
+        else if (option(argc, argv, i, "-f", "--features", text, missing)) {
+            bad = !missing && text != "orb" && text != "surf";
+            features = text == "surf" ? FEATURES_SURF : FEATURES_ORB;
+        }
+        else if (option(argc, argv, i, "-m", "--merge-distance", text, missing)) bad = !missing && (!number(text, merge) || !(merge >= 0.0) || !(merge <= 3.0e38));
         else if (option(argc, argv, i, "-v", "--visual-debug", text, missing)) bad = !missing && !number(text, ignored);
         else if (arg.size() > 1 && arg[0] == '-') { std::cerr << argv[0] << ": unknown option " << arg << "\n"; usage(std::cerr, argv[0]); return 2; }
         else if (!have_directory) { directory = arg; have_directory = true; }
@@ -63,6 +72,8 @@ int main(int argc, char** argv) {
 
     SfM sfm((float)downscale);
     sfm.setConsoleDebugLevel((unsigned int)level);
+    sfm.setFeatureType(features);
+    sfm.setMergeFeatureMatchDistance((float)merge);
     if (!sfm.setImagesDirectory(directory)) return 1;
     if (sfm.runSfM() != OKAY) return 1;
     return sfm.saveCloudAndCamerasToPLY(prefix) ? 0 : 1;

@@ -516,6 +516,53 @@ int64_t sfmba_shim_extract_features_batch(int n_images, const int64_t* img_ptr, 
 }
 
 namespace {
+// flattenFeatures for the float rows of FEATURES_SURF: desc [cap][64] floats
+int64_t flattenFloatFeatures(const sfmtoylib::Features& f, int64_t at, int64_t cap, float* kp, float* points, float* desc) {
+    const size_t n = f.keyPoints.size();
+    if (f.points.size() != n || (n > 0 && (f.descriptors.rows != (int)n || f.descriptors.cols != 64 || f.descriptors.type() != CV_32F))) return -2;
+    if (n == 0 && !f.descriptors.empty()) return -2;
+    for (size_t r = 0; r < n; ++r, ++at) {
+        if (at >= cap) continue;
+        const cv::KeyPoint& k = f.keyPoints[r];
+        float* o = kp + 7 * at;
+        o[0] = k.pt.x; o[1] = k.pt.y; o[2] = k.size; o[3] = k.angle; o[4] = k.response; o[5] = (float)k.octave; o[6] = (float)k.class_id;
+        points[2 * at] = f.points[r].x; points[2 * at + 1] = f.points[r].y;
+        std::memcpy(desc + 64 * at, f.descriptors.ptr<unsigned char>((int)r), 64 * sizeof(float));
+    }
+    return at;
+}
+}  // namespace
+
+// sfmba_shim_extract_features through extractFeatures(image, FEATURES_SURF) (tests/test_gpu_surf_extract.py): desc [cap][64] floats,
+// kp [cap][7] with class_id = the sign of the Laplacian.
+extern "C" __attribute__((visibility("default")))
+int64_t sfmba_shim_extract_features_surf(int w, int h, int channels, const unsigned char* px, int64_t cap, float* kp, float* points, float* desc) {
+    using namespace sfmtoylib;
+    SfM2DFeatureUtilities util;
+    return flattenFloatFeatures(util.extractFeatures(buildImage(w, h, channels, px), FEATURES_SURF), 0, cap, kp, points, desc);
+}
+
+// sfmba_shim_extract_features_batch through extractFeatures(images, imageFeatures, FEATURES_SURF).
+extern "C" __attribute__((visibility("default")))
+int64_t sfmba_shim_extract_features_surf_batch(int n_images, const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h,
+                                               int channels, int64_t* kp_ptr, int64_t cap, float* kp, float* points, float* desc) {
+    using namespace sfmtoylib;
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_images; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    std::vector<Features> feats;
+    if (!SfMFeatureExtraction::extractFeatures(images, feats, FEATURES_SURF)) return -1;
+    if (feats.size() != (size_t)n_images) return -2;
+    int64_t at = 0;
+    kp_ptr[0] = 0;
+    for (int i = 0; i < n_images; ++i) {
+        at = flattenFloatFeatures(feats[(size_t)i], at, cap, kp, points, desc);
+        if (at < 0) return -2;
+        kp_ptr[i + 1] = at;
+    }
+    return at;
+}
+
+namespace {
 // the key points (+ points) of view v: rows kp_ptr[v] .. kp_ptr[v+1]-1 of kp_xy [..][2]
 void addKeyPoints(std::vector<sfmtoylib::Features>& feats, const int64_t* kp_ptr, const float* kp_xy) {
     for (size_t v = 0; v < feats.size(); ++v)
@@ -602,6 +649,25 @@ int sfmba_shim_run_sfm_f32(int n_views, const int64_t* kp_ptr, const float* kp_x
     sfm.setFeatures(feats, cols, rows);
     return flattenRun(sfm, sfm.runSfM(), n_views, poses, K, done, good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts, xyz,
                       view_ptr, view_idx, feat_idx, nullptr);
+}
+
+// sfmba_shim_run_sfm from images with the extractor of SfM::setFeatureType (0 = FEATURES_ORB, 1 = FEATURES_SURF) and the merge
+// distance of SfM::setMergeFeatureMatchDistance (tests/test_gpu_surf_pipeline.py).  Outputs and return value as sfmba_shim_run_sfm.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_typed(int feature_type, float merge_distance, int n_views, int channels, const int64_t* img_ptr, const unsigned char* px,
+                             const int32_t* w, const int32_t* h, int debug_level, float* poses, float* K, unsigned char* done, unsigned char* good,
+                             int* n_added, int32_t* added_view, unsigned char* added_posed, int64_t* added_cloud, int64_t cap_pts, int64_t cap_views,
+                             int64_t* n_pts, float* xyz, int64_t* view_ptr, int32_t* view_idx, int32_t* feat_idx, const char* ply_prefix) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    sfm.setFeatureType((FeatureType)feature_type);
+    sfm.setMergeFeatureMatchDistance(merge_distance);
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    sfm.setImages(images);
+    return flattenRun(sfm, sfm.runSfM(), n_views, poses, K, done, good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts, xyz,
+                      view_ptr, view_idx, feat_idx, ply_prefix);
 }
 
 // Flat-array driver of sfmtoylib::SfM::setImagesDirectory (tests/test_sfm_scene_cpu.py; no device involved): the images come back
