@@ -912,6 +912,94 @@ SFMBA_API int sfmba_surf_extract(int device, int n_images, const int64_t* img_pt
                 int32_t* dbg_bin /*[cap] or NULL*/, int64_t* dbg_moments /*[cap][2] or NULL*/, int64_t* dbg_sums /*[cap][64] or NULL*/,
                 int32_t* dbg_candidates /*[n_images][n_octaves][2] or NULL*/);
 
+/* ---- dense depth maps and a dense cloud: plane-sweep stereo and a consistency filter (SfM::densify) ----------------------------
+ * The reference stops at the sparse cloud of the matched key points (its legacy tree densified with optical-flow matches).  Here a
+ * list of jobs -- a reference image, 1..4 source images, a depth range -- is swept in one call, and a second call turns the depth
+ * maps of a set of images into coloured points.  THE CONTRACT IS OUR OWN AND EQUALS NOBODY'S; it is stated so that the device is held
+ * BIT FOR BIT to a CPU restatement (tests/depth_oracle.py): coordinates are fp64 with EVERY OPERATION ROUNDED ON ITS OWN (no fused
+ * multiply-add anywhere; csrc/depth_math.h switches the compiler's contraction off), everything between the coordinate and the score
+ * is exact integer arithmetic, the score is a handful of IEEE fp64 operations.  Below, a sum written a + b + c is ((a + b) + c).
+ *
+ *   images        as sfmba_orb_extract takes them: image i owns bytes img_ptr[i] .. img_ptr[i+1]-1 of pixels, height[i] rows of
+ *                 width[i] * channels bytes; 3 channels (BGR) are reduced to gray by sfmba_orb_extract's rule
+ *                 (1868 b + 9617 g + 4899 r + 8192) >> 14.  Images may differ in size.
+ *   cameras       one K [9] row-major of which only fx = K[0], fy = K[4], cx = K[2], cy = K[5] are read; P [n_images][12] row-major
+ *                 3 x 4, P = [R | t] with x_cam = R X + t (as sfmba_triangulate_pairs takes them).  Every float is converted to
+ *                 double exactly on entry.
+ *
+ * sfmba_depth_sweep
+ *   jobs          job j has the reference image job_ref[j], the sources job_src[job_src_ptr[j] .. job_src_ptr[j+1]-1] (1 to 4,
+ *                 distinct, none equal to the reference) and the range 0 < z_near[j] < z_far[j] (finite floats, converted to double).
+ *                 Shared: n_planes D in 2..256, radius r in 1..4 (the window holds n = (2r+1)^2 pixels), min_std in 0..127,
+ *                 min_score in [-1, 1], min_sources in 1..4.
+ *   planes        fronto-parallel to the reference camera, uniform in inverse depth: wn = 1 / z_near, wf = 1 / z_far,
+ *                 step = (wn - wf) / (double)(D - 1), w_k = wf + ((double)k step), k = 0 .. D-1 (k = 0 is the far plane).
+ *   warp          per (job, source s), on the host: Rrel = R_s R_r^T, trel = t_s - Rrel t_r, M = K Rrel, A = M Kinv, b = K trel with
+ *                 K = [fx 0 cx; 0 fy cy; 0 0 1] and Kinv = [1/fx 0 -(cx/fx); 0 1/fy -(cy/fy); 0 0 1].  Every entry of a 3 x 3
+ *                 product is (x_i0 y_0j + x_i1 y_1j) + x_i2 y_2j, a matrix-vector product likewise; the zeros and the one of K and
+ *                 Kinv take part like any other entry.
+ *   sample        for reference pixel (u, v), plane k, source s of size ws x hs: q_i = ((A_i0 u + A_i1 v) + A_i2) + (w_k b_i),
+ *                 u' = q_0 / q_2, v' = q_1 / q_2.  VALID iff q_2 > 0, 0 <= u' <= ws-1 and 0 <= v' <= hs-1 (a NaN fails).  Then
+ *                 su = (int)floor(16 u' + 0.5), x0 = su >> 4, fx = su & 15, x1 = min(x0 + 1, ws-1), y likewise from v', and
+ *                 J = ((16-fx)(16-fy) I00 + fx (16-fy) I10 + (16-fx) fy I01 + fx fy I11 + 8) >> 4 with Iab the source's gray value at
+ *                 (x_a, y_b): a 12-bit integer 0..4080.  A sample depends on (u, v, k, s) only, never on the window that reads it.
+ *   window        over the (2r+1)^2 pixels around (u, v): SI, SII of the reference's gray values, SJ, SJJ, SIJ of the samples of one
+ *                 source.  With r <= 4: SI <= 20655, SII <= 5267025, SJ <= 330480, SIJ <= 84272400, SJJ <= 81 * 4080^2 =
+ *                 1348358400 < 2^31.  In int64: varI = n SII - SI^2, varJ = n SJJ - SJ^2, num = n SIJ - SI SJ.
+ *   takes part    a reference pixel takes part iff its window lies inside the reference image and varI >= n^2 min_std^2 and varI > 0.
+ *   score         source s COUNTS for (pixel, plane) iff all n samples of the window are valid and varJ > 0; its score is then
+ *                 (double)num / sqrt((double)varI * (double)varJ): one product, a correctly rounded square root, one division.
+ *   plane cost    C_k = (the scores of the counting sources summed in list order, starting from the first) / (double)count; the
+ *                 plane is VALID iff count >= min_sources.  k* = the lowest k with the largest C_k among the valid planes.  The
+ *                 pixel is ACCEPTED iff a valid plane exists and C_k* >= (double)min_score.
+ *   refinement    if 0 < k* < D-1, planes k*-1 and k*+1 are both valid and den = (C- - 2 C0) + C+ < 0 (C-, C0, C+ the costs at
+ *                 k*-1, k*, k*+1): delta = (0.5 (C- - C+)) / den; otherwise delta = 0.  w = w_k* + (delta step),
+ *                 depth = (float)(1 / w).
+ *   outputs       per job, concatenated in job order, each in the reference image's row-major order (the caller sizes them from the
+ *                 reference images): depth float [h][w], 0 where the pixel is not accepted; score float [h][w] = (float)C_k*, 0
+ *                 where no plane was valid; plane int16 [h][w] = k*, -1 where no plane was valid (may be NULL).  A pixel that does
+ *                 not take part has 0, 0, -1.
+ *   SFMBA_ERR_INVALID_ARG (nothing written): whatever sfmba_orb_extract refuses about images; fx, fy, cx, cy or a pose entry that is
+ *                 not finite, fx or fy <= 0; n_planes, radius, min_std, min_score (NaN included), min_sources outside the ranges
+ *                 above; a job whose reference or source index is out of range, that has fewer than 1 or more than 4 sources, that
+ *                 lists a source twice or its own reference, or whose range is not 0 < z_near < z_far with both finite; a
+ *                 job_src_ptr that does not start at 0.
+ *   Host pointers in and out, synchronous.  Deterministic; jobs go to the device in consecutive groups under a fixed scratch bound and
+ *   the result does not depend on the grouping: a batch equals the concatenation of single-job calls.
+ *
+ * sfmba_depth_fuse
+ *   inputs        the same images, K and P; depth [n_images]: per image NULL (no map) or a float [h][w] map as the sweep wrote it
+ *                 (0 = no depth); per image i the check images chk[chk_ptr[i] .. chk_ptr[i+1]-1] (0 to 4, distinct, none equal to
+ *                 i); rel_tol >= 0 (finite), min_consistent in 0..4.
+ *   per pixel     (u, v) of image i with z = (double)depth > 0: xn = ((double)u - cx) / fx, yn = ((double)v - cy) / fy,
+ *                 d = (z xn - t_0, z yn - t_1, z - t_2), X_j = (R_0j d_0 + R_1j d_1) + R_2j d_2 (R, t of image i).  For check image
+ *                 s of size ws x hs: q_i = ((R_i0 X_0 + R_i1 X_1) + R_i2 X_2) + t_i (R, t of s).  The pixel AGREES with s iff
+ *                 q_2 > 0; px = floor(((fx q_0) / q_2 + cx) + 0.5) and py = floor(((fy q_1) / q_2 + cy) + 0.5) satisfy
+ *                 0 <= px <= ws-1, 0 <= py <= hs-1 (tested in double; a NaN fails); s has a map; its value zs at (px, py) is > 0; and
+ *                 |zs - q_2| <= (double)rel_tol q_2.  The pixel is KEPT iff the number of agreeing check images >= min_consistent.
+ *   outputs       the kept pixels in (image, row, column) order: xyz float [cap][3] = (float) of X; bgr uint8 [cap][3] = the pixel's
+ *                 own colour (a gray image gives g, g, g); src_image int32 [cap]; src_pixel int32 [cap] = v width + u;
+ *                 pt_ptr [n_images + 1].  *total receives the number of points; SFMBA_ERR_CAPACITY (pt_ptr and *total valid,
+ *                 nothing else written) if cap < *total.
+ *   NO DE-DUPLICATION ACROSS VIEWS: a surface point seen by three views with maps appears three times.
+ *   SFMBA_ERR_INVALID_ARG (nothing written): what the sweep refuses about images, K and P; rel_tol negative or not finite;
+ *                 min_consistent outside 0..4; a check list longer than 4, with an index out of range, a repeated index or the image
+ *                 itself; a chk_ptr that does not start at 0; more than 65535 images, or 2^31 or more pixels with a map, in one call.
+ *   Host pointers in and out, synchronous, deterministic.  SFMBA_ABI_VERSION stays 6: adding symbols is backward compatible.
+ */
+SFMBA_API int sfmba_depth_sweep(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/,
+                const float* K /*[9]*/, const float* P /*[n_images][12]*/, int n_jobs, const int32_t* job_ref /*[n_jobs]*/,
+                const int64_t* job_src_ptr /*[n_jobs+1]*/, const int32_t* job_src, const float* z_near /*[n_jobs]*/,
+                const float* z_far /*[n_jobs]*/, int n_planes /*2..256*/, int radius /*1..4*/, int min_std /*0..127*/,
+                float min_score /*[-1, 1]*/, int min_sources /*1..4*/, float* depth, float* score, int16_t* plane /*or NULL*/);
+SFMBA_API int sfmba_depth_fuse(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/,
+                const float* K /*[9]*/, const float* P /*[n_images][12]*/, const float* const* depth /*[n_images], each NULL or [h][w]*/,
+                const int64_t* chk_ptr /*[n_images+1]*/, const int32_t* chk, float rel_tol, int min_consistent /*0..4*/,
+                int64_t* pt_ptr /*[n_images+1]*/, float* xyz /*[cap][3]*/, unsigned char* bgr /*[cap][3]*/, int32_t* src_image /*[cap]*/,
+                int32_t* src_pixel /*[cap]*/, int64_t cap, int64_t* total);
+
 /* ---- reading photographs: baseline JPEG decode and bilinear resize (SfM::setImagesDirectory) -----------------------------------
  * The reference reads every image with imread and shrinks it with resize(..., Size(), f, f) (SfMToyLib/SfM.cpp:125-129).  Here a
  * whole list of files is decoded, and a whole list of images resized, in one call each.  THE CONTRACT IS INTEGER-EXACT: the decode

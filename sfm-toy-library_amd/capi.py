@@ -38,6 +38,7 @@ SYMBOLS = [
     "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_orb_extract", "sfmba_triangulate_pairs",
     "sfmba_jpeg_info", "sfmba_resized_size", "sfmba_jpeg_decode", "sfmba_resize_images",
     "sfmba_png_info", "sfmba_png_decode", "sfmba_match_features_l2", "sfmba_surf_extract",
+    "sfmba_depth_sweep", "sfmba_depth_fuse",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -365,6 +366,95 @@ def surf_extract(images, n_features=5000, n_octaves=4, hessian_threshold=100.0, 
         else:
             out.append((kp[a:b].copy(), desc[a:b].copy()))
     return out
+
+
+def _flat_images(images):
+    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+    kinds = {(im.ndim, im.shape[2] if im.ndim == 3 else 1) for im in imgs}
+    if len(kinds) > 1 or any(k not in ((2, 1), (3, 3)) for k in kinds):
+        raise ValueError("images must all be h x w or all be h x w x 3 uint8 arrays")
+    channels = kinds.pop()[1] if kinds else 1
+    img_ptr = np.zeros(len(imgs) + 1, dtype=np.int64)
+    img_ptr[1:] = np.cumsum([im.size for im in imgs])
+    flat = np.ascontiguousarray(np.concatenate([im.reshape(-1) for im in imgs]) if imgs else np.zeros(1, np.uint8))
+    wd = np.asarray([im.shape[1] for im in imgs], dtype=np.int32)
+    ht = np.asarray([im.shape[0] for im in imgs], dtype=np.int32)
+    return imgs, channels, img_ptr, flat, wd, ht
+
+
+def _csr(lists):
+    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum([len(x) for x in lists])
+    flat = np.asarray([v for x in lists for v in x] or [0], dtype=np.int32)
+    return ptr, flat
+
+
+def depth_sweep(images, K, P, jobs, n_planes=64, radius=3, min_std=2, min_score=0.6, min_sources=1, want_plane=True, device=0):
+    """sfmba_depth_sweep: plane-sweep stereo for a list of jobs in one call (the contract is in include/sfmba.h).
+
+    images: as orb_extract.  K [3, 3]; P [n_images, 3, 4].  jobs: list of (ref, sources, z_near, z_far).  Returns one tuple per job:
+    (depth float32 [h, w], score float32 [h, w], plane int16 [h, w]); plane is None with want_plane=False (NULL is passed)."""
+    imgs, channels, img_ptr, flat, wd, ht = _flat_images(images)
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1)
+    if len(P) != 12 * len(imgs):
+        raise ValueError("P must hold one 3 x 4 matrix per image")
+    ref = np.asarray([j[0] for j in jobs] or [0], dtype=np.int32)
+    src_ptr, src = _csr([list(j[1]) for j in jobs])
+    zn = np.asarray([j[2] for j in jobs] or [0], dtype=np.float32)
+    zf = np.asarray([j[3] for j in jobs] or [0], dtype=np.float32)
+    sizes = [(int(ht[r]), int(wd[r])) if 0 <= r < len(imgs) else (0, 0) for r in ref[:len(jobs)]]
+    n_px = sum(h * w for h, w in sizes)
+    depth, score, plane = np.zeros(max(n_px, 1), np.float32), np.zeros(max(n_px, 1), np.float32), np.zeros(max(n_px, 1), np.int16)
+    lp, bp, fp = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte), C.POINTER(C.c_float)
+    _check(lib().sfmba_depth_sweep(C.c_int(device), C.c_int(len(imgs)), _p(img_ptr, lp), flat.ctypes.data_as(bp), _p(wd, _ip), _p(ht, _ip),
+                                   C.c_int(channels), K.ctypes.data_as(fp), P.ctypes.data_as(fp), C.c_int(len(jobs)), _p(ref, _ip),
+                                   _p(src_ptr, lp), _p(src, _ip), zn.ctypes.data_as(fp), zf.ctypes.data_as(fp), C.c_int(n_planes),
+                                   C.c_int(radius), C.c_int(min_std), C.c_float(min_score), C.c_int(min_sources), depth.ctypes.data_as(fp),
+                                   score.ctypes.data_as(fp), plane.ctypes.data_as(C.POINTER(C.c_int16)) if want_plane else None))
+    out, at = [], 0
+    for h, w in sizes:
+        n = h * w
+        out.append((depth[at:at + n].reshape(h, w).copy(), score[at:at + n].reshape(h, w).copy(),
+                    plane[at:at + n].reshape(h, w).copy() if want_plane else None))
+        at += n
+    return out
+
+
+def depth_fuse(images, K, P, depth_maps, checks, rel_tol=0.01, min_consistent=1, cap=None, device=0):
+    """sfmba_depth_fuse: the depth maps of a set of images -> one coloured cloud (the contract is in include/sfmba.h).
+
+    depth_maps: per image None or float32 [h, w]; checks: per image the list of its check images.  Returns a dict: xyz float32 [n, 3],
+    bgr uint8 [n, 3], src_image int32 [n], src_pixel int32 [n], pt_ptr int64 [n_images + 1].  cap=None asks for the size first (cap 0);
+    a short cap is retried once with the size the library reports."""
+    imgs, channels, img_ptr, flat, wd, ht = _flat_images(images)
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1)
+    if len(P) != 12 * len(imgs) or len(depth_maps) != len(imgs) or len(checks) != len(imgs):
+        raise ValueError("P, depth_maps and checks must hold one entry per image")
+    maps = [None if m is None else np.ascontiguousarray(m, dtype=np.float32) for m in depth_maps]
+    for m, im in zip(maps, imgs):
+        if m is not None and m.shape != im.shape[:2]:
+            raise ValueError("a depth map must have its image's size")
+    fp, lp, bp = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_ubyte)
+    ptrs = (fp * max(len(imgs), 1))(*[None if m is None else m.ctypes.data_as(fp) for m in maps])
+    chk_ptr, chk = _csr([list(c) for c in checks])
+    pt_ptr = np.zeros(len(imgs) + 1, dtype=np.int64)
+    total = C.c_int64(0)
+    cap = 0 if cap is None else int(cap)
+    for _ in range(2):
+        xyz, bgr = np.zeros((max(cap, 1), 3), np.float32), np.zeros((max(cap, 1), 3), np.uint8)
+        si, sp = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        rc = lib().sfmba_depth_fuse(C.c_int(device), C.c_int(len(imgs)), _p(img_ptr, lp), flat.ctypes.data_as(bp), _p(wd, _ip), _p(ht, _ip),
+                                    C.c_int(channels), K.ctypes.data_as(fp), P.ctypes.data_as(fp), ptrs, _p(chk_ptr, lp), _p(chk, _ip),
+                                    C.c_float(rel_tol), C.c_int(min_consistent), _p(pt_ptr, lp), xyz.ctypes.data_as(fp), bgr.ctypes.data_as(bp),
+                                    _p(si, _ip), _p(sp, _ip), C.c_int64(cap), C.byref(total))
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        cap = int(total.value)
+    _check(rc)
+    n = int(total.value)
+    return {"xyz": xyz[:n].copy(), "bgr": bgr[:n].copy(), "src_image": si[:n].copy(), "src_pixel": sp[:n].copy(), "pt_ptr": pt_ptr.copy()}
 
 
 class _ImageInfo(C.Structure):

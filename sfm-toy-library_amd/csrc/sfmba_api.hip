@@ -11,6 +11,7 @@
 #include "essential_ransac.h"
 #include "orb_extract.h"
 #include "surf_extract.h"
+#include "depth_sweep.h"
 #include "jpeg_decode.h"
 #include "jpeg_math.h"
 #include "png_decode.h"
@@ -658,6 +659,121 @@ int sfmba_surf_extract(int device, int n_images, const int64_t* img_ptr, const u
     if (rc == SURF_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "surf_extract: output capacity too small");
     if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "surf_extract: device allocation failed");
     if (rc) return fail(SFMBA_ERR_HIP, std::string("surf_extract: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+// ---- dense depth maps and a dense cloud: plane-sweep stereo and the consistency filter (SfM::densify) ---------------------------
+namespace {
+// what both dense calls refuse about the images, K and P; 0 or the failure
+int depth_check_images(const char* who, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                       int channels, const float* K, const float* P) {
+    const std::string w(who);
+    if (n_images < 0 || !img_ptr || !K || (n_images > 0 && (!width || !height || !P || !pixels))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, w + ": channels must be 1 or 3");
+    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
+            return fail(SFMBA_ERR_INVALID_ARG, w + ": an image dimension lies outside 1..16384");
+        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
+            return fail(SFMBA_ERR_INVALID_ARG, w + ": img_ptr does not agree with width * height * channels");
+        for (int q = 0; q < 12; ++q)
+            if (!std::isfinite(P[(size_t)i * 12 + q])) return fail(SFMBA_ERR_INVALID_ARG, w + ": non-finite pose of image " + std::to_string(i));
+    }
+    for (int q : { 0, 4, 2, 5 })
+        if (!std::isfinite(K[q])) return fail(SFMBA_ERR_INVALID_ARG, w + ": fx, fy, cx and cy must be finite");
+    if (!(K[0] > 0.0f) || !(K[4] > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, w + ": fx and fy must be > 0");
+    return 0;
+}
+// a CSR list of 0 / 1 .. 4 other images per row; 0 or the failure
+int depth_check_lists(const char* who, const char* what, int n_images, int n_rows, const int32_t* row_image, const int64_t* ptr, const int32_t* idx,
+                      int min_len) {
+    const std::string w(who);
+    if (!ptr || ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, w + ": " + what + " pointer array must start at 0");
+    for (int j = 0; j < n_rows; ++j) {
+        const int64_t n = ptr[j + 1] - ptr[j];
+        if (n < min_len || n > 4) return fail(SFMBA_ERR_INVALID_ARG, w + ": a row has " + std::to_string((long long)n) + " " + what + " images, outside " +
+                                                                       std::to_string(min_len) + "..4");
+        if (n > 0 && !idx) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+        const int own = row_image ? row_image[j] : j;
+        for (int64_t a = ptr[j]; a < ptr[j + 1]; ++a) {
+            if (idx[a] < 0 || idx[a] >= n_images) return fail(SFMBA_ERR_INVALID_ARG, w + ": " + what + " image index out of range");
+            if (idx[a] == own) return fail(SFMBA_ERR_INVALID_ARG, w + ": a " + what + " image equals the image it belongs to");
+            for (int64_t c = ptr[j]; c < a; ++c)
+                if (idx[c] == idx[a]) return fail(SFMBA_ERR_INVALID_ARG, w + ": a " + what + " image is listed twice");
+        }
+    }
+    return 0;
+}
+}  // namespace
+int sfmba_depth_sweep(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                      int channels, const float* K, const float* P, int n_jobs, const int32_t* job_ref, const int64_t* job_src_ptr,
+                      const int32_t* job_src, const float* z_near, const float* z_far, int n_planes, int radius, int min_std, float min_score,
+                      int min_sources, float* depth, float* score, int16_t* plane) {
+    if (n_jobs < 0 || (n_jobs > 0 && (!job_ref || !job_src_ptr || !job_src || !z_near || !z_far))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (int rc = depth_check_images("depth_sweep", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    if (n_planes < 2 || n_planes > 256) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: n_planes must be in 2..256");
+    if (radius < 1 || radius > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: radius must be in 1..4");
+    if (min_std < 0 || min_std > 127) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_std must be in 0..127");
+    if (!(min_score >= -1.0f) || !(min_score <= 1.0f)) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_score must be in [-1, 1]");
+    if (min_sources < 1 || min_sources > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_sources must be in 1..4");
+    int64_t out_px = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (job_ref[j] < 0 || job_ref[j] >= n_images) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: reference image index out of range");
+        if (!std::isfinite(z_near[j]) || !std::isfinite(z_far[j]) || !(z_near[j] > 0.0f) || !(z_near[j] < z_far[j]))
+            return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: a job needs 0 < z_near < z_far, both finite");
+        out_px += (int64_t)width[job_ref[j]] * height[job_ref[j]];
+    }
+    if (n_jobs > 0)
+        if (int rc = depth_check_lists("depth_sweep", "source", n_images, n_jobs, job_ref, job_src_ptr, job_src, 1)) return rc;
+    if (out_px > 0 && (!depth || !score)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (n_jobs == 0) return check_device(device);
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    // SFMBA_DEPTH_TIMING: one stderr line per call with the HIP-event times of its phases (tools/dense_bench.py)
+    double tm[DEPTH_T_COUNT];
+    const bool timing = std::getenv("SFMBA_DEPTH_TIMING") != nullptr;
+    rc = depth_sweep(ck.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, K, P, n_jobs, job_ref, job_src_ptr, job_src, z_near,
+                     z_far, n_planes, radius, min_std, min_score, min_sources, depth, score, plane, timing ? tm : nullptr);
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba depth_sweep] upload_ms %.6f gray_ms %.6f sweep_ms %.6f download_ms %.6f groups %d\n", tm[DEPTH_T_UPLOAD],
+                     tm[DEPTH_T_GRAY], tm[DEPTH_T_SWEEP], tm[DEPTH_T_DOWNLOAD], (int)tm[DEPTH_T_GROUPS]);
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "depth_sweep: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("depth_sweep: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+int sfmba_depth_fuse(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                     int channels, const float* K, const float* P, const float* const* depth, const int64_t* chk_ptr, const int32_t* chk,
+                     float rel_tol, int min_consistent, int64_t* pt_ptr, float* xyz, unsigned char* bgr, int32_t* src_image, int32_t* src_pixel,
+                     int64_t cap, int64_t* total) {
+    if (cap < 0 || !pt_ptr || !total || (n_images > 0 && !depth) || (cap > 0 && (!xyz || !bgr || !src_image || !src_pixel)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (int rc = depth_check_images("depth_fuse", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    if (n_images > 65535) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: more than 65535 images in one call");
+    if (!std::isfinite(rel_tol) || rel_tol < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: rel_tol must be finite and >= 0");
+    if (min_consistent < 0 || min_consistent > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: min_consistent must be in 0..4");
+    if (int rc = depth_check_lists("depth_fuse", "check", n_images, n_images, nullptr, chk_ptr, chk, 0)) return rc;
+    int64_t px = 0;
+    for (int i = 0; i < n_images; ++i)
+        if (depth[i]) px += (int64_t)width[i] * height[i];
+    if (px >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: too many pixels with a depth map in one call (2^31)");
+    if (px == 0) {
+        for (int i = 0; i <= n_images; ++i) pt_ptr[i] = 0;
+        *total = 0;
+        return check_device(device);
+    }
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    double tm[FUSE_T_COUNT];
+    const bool timing = std::getenv("SFMBA_DEPTH_TIMING") != nullptr;
+    rc = depth_fuse(ck.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, K, P, depth, chk_ptr, chk, rel_tol, min_consistent,
+                    pt_ptr, xyz, bgr, src_image, src_pixel, cap, total, timing ? tm : nullptr);
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba depth_fuse] upload_ms %.6f flag_ms %.6f scan_ms %.6f emit_ms %.6f download_ms %.6f\n", tm[FUSE_T_UPLOAD],
+                     tm[FUSE_T_FLAG], tm[FUSE_T_SCAN], tm[FUSE_T_EMIT], tm[FUSE_T_DOWNLOAD]);
+    if (rc == DEPTH_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "depth_fuse: output capacity too small");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "depth_fuse: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("depth_fuse: ") + hipGetErrorString((hipError_t)rc));
     return SFMBA_OK;
 }
 // ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------

@@ -5,12 +5,14 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <chrono>
 #include <cstdlib>
 #include <cstdio>
 #include <fstream>
 #include <iostream>
 #include <map>
+#include <utility>
 
 #include "SfM2DFeatureUtilities.h"
 #include "SfMBundleAdjustmentUtils.h"
@@ -90,6 +92,7 @@ SfM::SfM(const float downscale) :
         mFeaturesGiven(false),
         mDownscaleApplied(false),
         mCols(0), mRows(0),
+        mRunOkay(false),
         mTiming(false) {
     for (double& ms : mStageMs) ms = 0.0;
 }
@@ -159,6 +162,7 @@ bool SfM::setImagesDirectory(const std::string& directoryPath) {
 void SfM::setImages(const std::vector<cv::Mat>& images) {
     mImages = images;
     mImageFeatures.clear();
+    mRunOkay = false;
     mFeaturesGiven = false;
     mDownscaleApplied = false;
     mCols = images.empty() ? 0 : images[0].cols;
@@ -168,6 +172,7 @@ void SfM::setImages(const std::vector<cv::Mat>& images) {
 void SfM::setFeatures(const std::vector<Features>& imageFeatures, int cols, int rows) {
     mImages.clear();
     mImageFeatures = imageFeatures;
+    mRunOkay = false;
     mFeaturesGiven = true;
     mDownscaleApplied = false;
     mCols = cols;
@@ -200,6 +205,10 @@ void SfM::startRun(size_t n_views) {
     mReconstructionCloud.clear();
     mAddedViews.clear();
     mFeatureMatchMatrix.clear();
+    mDepthMaps.clear();
+    mDenseCloud = DenseCloud();
+    mDenseJobs.clear();
+    mRunOkay = false;
     mTiming = std::getenv("SFMBA_SFM_TIMING") != nullptr;
     for (double& ms : mStageMs) ms = 0.0;
 }
@@ -243,6 +252,7 @@ ErrorCode SfM::runSfM() {
         for (int stage = 0; stage < T_COUNT; stage++) std::fprintf(stderr, " %s_ms %.3f", stageNames[stage], mStageMs[stage]);
         std::fprintf(stderr, "\n");
     }
+    mRunOkay = true;
     return OKAY;
 }
 
@@ -396,6 +406,117 @@ void SfM::addMoreViewsToReconstruction() {
         }
         mAddedViews.push_back(turn);
     }
+}
+
+ErrorCode SfM::densify(const DenseParams& params) {
+    mDepthMaps.clear();
+    mDenseCloud = DenseCloud();
+    mDenseJobs.clear();
+    if (mFeaturesGiven || mImages.empty()) {
+        std::cerr << "densify: there are no pixels: the run started from setFeatures, and depth maps need the images" << std::endl;
+        return ERROR;
+    }
+    if (!mRunOkay || mCameraPoses.size() != mImages.size()) {
+        std::cerr << "densify: needs a runSfM on these images that returned OKAY" << std::endl;
+        return ERROR;
+    }
+    if (params.maxSources < 1 || params.maxSources > 4) {
+        std::cerr << "densify: maxSources must be in 1..4" << std::endl;
+        return ERROR;
+    }
+    const std::vector<int> good(mGoodViews.begin(), mGoodViews.end());
+    // camera centres and the sorted depths of every good view's own cloud points, in double
+    std::map<int, std::vector<double> > centre, depths;
+    for (int v : good) {
+        const cv::Matx34f& P = mCameraPoses[(size_t)v];
+        std::vector<double>& C = centre[v];
+        for (int j = 0; j < 3; j++) C.push_back(-(((double)P(0, j) * (double)P(0, 3) + (double)P(1, j) * (double)P(1, 3)) + (double)P(2, j) * (double)P(2, 3)));
+        depths[v];
+    }
+    for (const Point3DInMap& point : mReconstructionCloud)
+        for (const auto& origin : point.originatingViews) {
+            if (!depths.count(origin.first)) continue;
+            const cv::Matx34f& P = mCameraPoses[(size_t)origin.first];
+            const double z = (((double)P(2, 0) * (double)point.p.x + (double)P(2, 1) * (double)point.p.y) + (double)P(2, 2) * (double)point.p.z) + (double)P(2, 3);
+            if (std::isfinite(z) && z > 0.0) depths[origin.first].push_back(z);
+        }
+    for (int v : good) {
+        std::vector<double>& z = depths[v];
+        std::sort(z.begin(), z.end());
+        const size_t m = z.size();
+        if (m < 8) continue;
+        std::vector<std::pair<double, int> > others;
+        for (int o : good) {
+            if (o == v) continue;
+            const double dx = centre[o][0] - centre[v][0], dy = centre[o][1] - centre[v][1], dz = centre[o][2] - centre[v][2];
+            others.push_back(std::make_pair((dx * dx + dy * dy) + dz * dz, o));
+        }
+        if (others.empty()) continue;
+        std::sort(others.begin(), others.end());           // ascending distance, then index
+        DenseJob job;
+        job.reference = v;
+        for (size_t k = 0; k < others.size() && (int)k < params.maxSources; k++) job.sources.push_back(others[k].second);
+        job.zNear = (float)(z[(5 * m) / 100] / 1.25);
+        job.zFar = (float)(z[std::min(m - 1, (95 * m) / 100)] * 1.25);
+        mDenseJobs.push_back(job);
+    }
+    say(LOG_INFO, "dense: " + std::to_string(mDenseJobs.size()) + " sweep jobs over " + std::to_string(good.size()) + " good views");
+
+    const bool timing = std::getenv("SFMBA_SFM_TIMING") != nullptr;
+    double ms[2] = { 0.0, 0.0 };
+    std::vector<cv::Mat> depthMaps, scores;
+    {
+        StageClock clock(timing ? ms : nullptr, 0);
+        if (!SfMDenseUtilities::computeDepthMaps(mImages, mIntrinsics, mCameraPoses, mDenseJobs, params, depthMaps, scores)) {
+            mDenseJobs.clear();
+            return ERROR;
+        }
+    }
+    std::vector<cv::Mat> perView(mImages.size());
+    std::vector<std::vector<int> > checks(mImages.size());
+    for (size_t j = 0; j < mDenseJobs.size(); j++) {
+        perView[(size_t)mDenseJobs[j].reference] = depthMaps[j];
+        checks[(size_t)mDenseJobs[j].reference] = mDenseJobs[j].sources;
+    }
+    bool ok = true;
+    DenseCloud cloud;
+    if (!mDenseJobs.empty()) {
+        StageClock clock(timing ? ms : nullptr, 1);
+        cloud = SfMDenseUtilities::fuseDepthMaps(mImages, mIntrinsics, mCameraPoses, perView, checks, params, &ok);
+    }
+    if (!ok) {
+        mDenseJobs.clear();
+        return ERROR;
+    }
+    mDepthMaps = perView;
+    mDenseCloud = cloud;
+    say(LOG_INFO, "dense: " + std::to_string(mDenseCloud.points.size()) + " points");
+    if (timing)
+        std::fprintf(stderr, "[sfmba sfm dense] jobs %d dense_sweep_ms %.3f dense_fuse_ms %.3f points %lld\n", (int)mDenseJobs.size(), ms[0], ms[1],
+                     (long long)mDenseCloud.points.size());
+    return OKAY;
+}
+
+bool SfM::saveDenseCloudToPLY(const std::string& prefix) {
+    std::ofstream file(prefix + "_dense.ply");
+    // the header of the points file (SfMExport.cpp), padding included
+    file << "ply                 " << std::endl
+         << "format ascii 1.0    " << std::endl
+         << "element vertex " << mDenseCloud.points.size() << std::endl
+         << "property float x    " << std::endl
+         << "property float y    " << std::endl
+         << "property float z    " << std::endl
+         << "property uchar red  " << std::endl
+         << "property uchar green" << std::endl
+         << "property uchar blue " << std::endl
+         << "end_header          " << std::endl;
+    for (size_t i = 0; i < mDenseCloud.points.size(); i++) {
+        const cv::Point3f& p = mDenseCloud.points[i];
+        const unsigned char* bgr = &mDenseCloud.bgr[3 * i];
+        file << p.x << " " << p.y << " " << p.z << " " << (int)bgr[2] << " " << (int)bgr[1] << " " << (int)bgr[0] << " " << std::endl;
+    }
+    file.close();
+    return !file.fail();
 }
 
 bool SfM::saveCloudAndCamerasToPLY(const std::string& prefix) {

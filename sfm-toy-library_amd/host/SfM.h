@@ -37,6 +37,17 @@
 //                 images in ONE resize call;
 //                 K then comes from the resized image 0.  Images given through setImages and features given through setFeatures are
 //                 taken as they are: runSfM refuses downscale != 1 for them (there is nothing to resize in the second case).
+//   dense         densify() after a runSfM that returned OKAY on images: one plane-sweep job per good view (include/sfmba.h,
+//                 sfmba_depth_sweep), ALL jobs in ONE sweep call, then ONE sfmba_depth_fuse call over the depth maps.
+//                 Sources: the up-to-maxSources (default 2) other good views whose camera centres are nearest, listed by ascending
+//                 distance, ties to the lower index; centres C_j = -((R_0j t_0 + R_1j t_1) + R_2j t_2) and squared distances
+//                 (dx^2 + dy^2) + dz^2 in double.  Depth range: the camera-space z = ((R_20 X + R_21 Y) + R_22 Z) + t_2 (double) of
+//                 every cloud point that lists the view in originatingViews, the non-positive and non-finite ones dropped, sorted;
+//                 with m values z_near = (float)(z[(5 m) / 100] / 1.25), z_far = (float)(z[min(m - 1, (95 m) / 100)] * 1.25)
+//                 (integer division); a view with m < 8, or without another good view, gets no job and no depth map.  The check
+//                 views of the fuse are the job's sources.  The defaults of DenseParams (64 planes, radius 3, min_std 2,
+//                 min_score 0.6, min_sources 1, rel_tol 0.01, min_consistent 1) are first choices like the merge distance above:
+//                 nobody has tuned them.  Nothing is de-duplicated: a surface point seen by three views appears three times.
 // There is no visual debugging.
 // An object holds all of a run's state (the stage times of SFMBA_SFM_TIMING included): different objects may run in different
 // threads; one object is not re-entrant.
@@ -48,6 +59,7 @@
 #include "SfMCommon.h"
 #include "SfMAssociation.h"
 #include "SfM2DFeatureUtilities.h"
+#include "SfMDenseUtilities.h"
 
 namespace sfmtoylib {
 
@@ -114,6 +126,19 @@ public:
      */
     bool saveCloudAndCamerasToPLY(const std::string& prefix);
 
+    /**
+     * Dense depth maps of the good views and the fused dense cloud (the contract is at the top of this file).  Valid after a runSfM
+     * that returned OKAY on images; after setFeatures there are no pixels.  With SFMBA_SFM_TIMING set, one stderr line reports
+     * dense_sweep_ms and dense_fuse_ms.
+     * @return ERROR (nothing kept) without such a run, for maxSources outside 1..4, or when a device call fails or refuses.
+     */
+    ErrorCode densify(const DenseParams& params = DenseParams());
+
+    /**
+     * <prefix>_dense.ply: the dense cloud, ASCII, with the header and the number formatting of <prefix>_points.ply, colours R G B.
+     */
+    bool saveDenseCloudToPLY(const std::string& prefix);
+
     void setConsoleDebugLevel(unsigned int consoleDebugLevel) { mConsoleDebugLevel = consoleDebugLevel < (unsigned int)LOG_ERROR ? consoleDebugLevel : (unsigned int)LOG_ERROR; }
 
     const std::vector<cv::Mat>&     getImages() const { return mImages; }
@@ -124,6 +149,9 @@ public:
     const std::set<int>&            getDoneViews() const { return mDoneViews; }
     const std::set<int>&            getGoodViews() const { return mGoodViews; }
     const std::vector<AddedView>&   getAddedViews() const { return mAddedViews; }
+    const std::vector<cv::Mat>&     getDepthMaps() const { return mDepthMaps; }       // per view; an empty Mat where densify made no job
+    const DenseCloud&               getDenseCloud() const { return mDenseCloud; }
+    const std::vector<DenseJob>&    getDenseJobs() const { return mDenseJobs; }       // the jobs of the last densify, ascending view
 
 private:
     enum { T_EXTRACT, T_MATCH, T_RANK, T_BASELINE_POSE, T_BASELINE_TRIANGULATE, T_ASSOCIATE, T_PNP, T_PAIR_POSES, T_TRIANGULATE, T_MERGE,
@@ -153,6 +181,10 @@ private:
     bool                      mFeaturesGiven;
     bool                      mDownscaleApplied; // the images came from setImagesDirectory, which applied mDownscaleFactor
     int                       mCols, mRows;      // of image 0, or as given to setFeatures
+    std::vector<cv::Mat>      mDepthMaps;
+    DenseCloud                mDenseCloud;
+    std::vector<DenseJob>     mDenseJobs;
+    bool                      mRunOkay;          // the last runSfM returned OKAY and nothing was set since
     bool                      mTiming;           // SFMBA_SFM_TIMING was set when the run began
     double                    mStageMs[T_COUNT]; // wall time per stage of the current run (all zero unless mTiming)
 };

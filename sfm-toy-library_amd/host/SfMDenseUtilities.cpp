@@ -1,0 +1,149 @@
+// SfMDenseUtilities.cpp -- host side of the dense stage: flattens the containers, calls the C ABI (include/sfmba.h), rebuilds the
+// results.  See SfMDenseUtilities.h.
+#include "SfMDenseUtilities.h"
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+
+#include "../../include/sfmba.h"
+
+namespace sfmtoylib {
+
+namespace {
+
+struct FlatScene {
+    std::vector<int64_t>       ptr;
+    std::vector<unsigned char> px;
+    std::vector<int32_t>       w, h;
+    std::vector<float>         P;
+    float                      K[9];
+    int                        channels;
+};
+
+bool flattenScene(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses, FlatScene& f) {
+    if (images.empty() || poses.size() != images.size()) return false;
+    f.channels = images[0].type() == CV_8UC3 ? 3 : 1;
+    f.ptr.assign(1, 0);
+    for (const cv::Mat& m : images) {
+        if (m.type() != images[0].type() || (m.type() != CV_8U && m.type() != CV_8UC3)) return false;
+        f.ptr.push_back(f.ptr.back() + (int64_t)m.rows * m.cols * f.channels);
+        f.w.push_back(m.cols);
+        f.h.push_back(m.rows);
+    }
+    f.px.resize((size_t)f.ptr.back());
+    for (size_t i = 0; i < images.size(); ++i)
+        for (int r = 0; r < images[i].rows; ++r)
+            std::memcpy(f.px.data() + f.ptr[i] + (size_t)r * images[i].cols * f.channels, images[i].ptr<unsigned char>(r),
+                        (size_t)images[i].cols * f.channels);
+    for (const cv::Matx34f& p : poses)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) f.P.push_back(p(r, c));
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) f.K[3 * r + c] = intrinsics.K.at<float>(r, c);
+    return true;
+}
+
+}  // namespace
+
+bool SfMDenseUtilities::computeDepthMaps(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
+                                         const std::vector<DenseJob>& jobs, const DenseParams& params, std::vector<cv::Mat>& depthMaps,
+                                         std::vector<cv::Mat>& scores) {
+    depthMaps.clear();
+    scores.clear();
+    FlatScene f;
+    if (!flattenScene(images, intrinsics, poses, f)) {
+        std::fprintf(stderr, "computeDepthMaps: one pose per image and images of one kind (CV_8U or CV_8UC3) are needed\n");
+        return false;
+    }
+    std::vector<int32_t> ref, src;
+    std::vector<int64_t> srcPtr(1, 0);
+    std::vector<float> zNear, zFar;
+    int64_t pixels = 0;
+    for (const DenseJob& j : jobs) {
+        if (j.reference < 0 || j.reference >= (int)images.size()) {
+            std::fprintf(stderr, "computeDepthMaps: a job's reference view is out of range\n");
+            return false;
+        }
+        ref.push_back(j.reference);
+        for (int s : j.sources) src.push_back(s);
+        srcPtr.push_back((int64_t)src.size());
+        zNear.push_back(j.zNear);
+        zFar.push_back(j.zFar);
+        pixels += (int64_t)images[(size_t)j.reference].rows * images[(size_t)j.reference].cols;
+    }
+    if (jobs.empty()) return true;
+    src.push_back(0);                                      // never read: keeps data() non-null
+    std::vector<float> depth((size_t)pixels), score((size_t)pixels);
+    const int rc = sfmba_depth_sweep(0, (int)images.size(), f.ptr.data(), f.px.data(), f.w.data(), f.h.data(), f.channels, f.K, f.P.data(),
+                                     (int)jobs.size(), ref.data(), srcPtr.data(), src.data(), zNear.data(), zFar.data(), params.planes, params.radius,
+                                     params.minStd, params.minScore, params.minSources, depth.data(), score.data(), nullptr);
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "computeDepthMaps failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return false;
+    }
+    size_t at = 0;
+    for (const DenseJob& j : jobs) {
+        const cv::Mat& image = images[(size_t)j.reference];
+        const size_t n = (size_t)image.rows * image.cols;
+        cv::Mat d(image.rows, image.cols, CV_32F), s(image.rows, image.cols, CV_32F);
+        std::memcpy(d.ptr<float>(0), depth.data() + at, n * sizeof(float));
+        std::memcpy(s.ptr<float>(0), score.data() + at, n * sizeof(float));
+        depthMaps.push_back(d);
+        scores.push_back(s);
+        at += n;
+    }
+    return true;
+}
+
+DenseCloud SfMDenseUtilities::fuseDepthMaps(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
+                                            const std::vector<cv::Mat>& depthMaps, const std::vector<std::vector<int> >& checks,
+                                            const DenseParams& params, bool* ok) {
+    DenseCloud cloud;
+    if (ok) *ok = false;
+    FlatScene f;
+    if (!flattenScene(images, intrinsics, poses, f) || depthMaps.size() != images.size() || checks.size() != images.size()) {
+        std::fprintf(stderr, "fuseDepthMaps: one pose, one depth map (or an empty Mat) and one check list per image are needed\n");
+        return cloud;
+    }
+    std::vector<const float*> maps(images.size(), nullptr);
+    std::vector<int64_t> chkPtr(1, 0);
+    std::vector<int32_t> chk;
+    for (size_t i = 0; i < images.size(); ++i) {
+        const cv::Mat& m = depthMaps[i];
+        if (!m.empty()) {
+            if (m.type() != CV_32F || m.rows != images[i].rows || m.cols != images[i].cols) {
+                std::fprintf(stderr, "fuseDepthMaps: a depth map is not CV_32F of its image's size\n");
+                return cloud;
+            }
+            maps[i] = m.ptr<float>(0);
+        }
+        for (int s : checks[i]) chk.push_back(s);
+        chkPtr.push_back((int64_t)chk.size());
+    }
+    chk.push_back(0);                                      // never read: keeps data() non-null
+    std::vector<int64_t> ptPtr(images.size() + 1, 0);
+    std::vector<float> xyz;
+    std::vector<int32_t> view, pixel;
+    int64_t total = 0, cap = 0;                            // the first call reports the size
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        xyz.resize((size_t)cap * 3 + 1); cloud.bgr.resize((size_t)cap * 3 + 1); view.resize((size_t)cap + 1); pixel.resize((size_t)cap + 1);
+        const int rc = sfmba_depth_fuse(0, (int)images.size(), f.ptr.data(), f.px.data(), f.w.data(), f.h.data(), f.channels, f.K, f.P.data(),
+                                        maps.data(), chkPtr.data(), chk.data(), params.relTol, params.minConsistent, ptPtr.data(), xyz.data(),
+                                        cloud.bgr.data(), view.data(), pixel.data(), cap, &total);
+        if (rc == SFMBA_OK) break;
+        if (rc == SFMBA_ERR_CAPACITY && attempt == 0) { cap = total; continue; }
+        std::fprintf(stderr, "fuseDepthMaps failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        cloud.bgr.clear();
+        return cloud;
+    }
+    cloud.bgr.resize((size_t)total * 3);
+    cloud.points.reserve((size_t)total);
+    for (int64_t i = 0; i < total; ++i) cloud.points.push_back(cv::Point3f(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]));
+    cloud.views.assign(view.begin(), view.begin() + total);
+    cloud.pixels.assign(pixel.begin(), pixel.begin() + total);
+    if (ok) *ok = true;
+    return cloud;
+}
+
+}  // namespace sfmtoylib

@@ -1,5 +1,6 @@
 // sfmtoy.cpp -- the command-line program of the reference (main.cpp) over sfmtoylib::SfM of this directory: read the images of a
-// directory, run the pipeline on the MI355X, write <prefix>_points.ply and <prefix>_cameras.ply.  The arguments are parsed here
+// directory, run the pipeline on the MI355X, write <prefix>_points.ply and <prefix>_cameras.ply -- and, with -D, densify and write
+// <prefix>_dense.ply.  The arguments are parsed here
 // (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
 #include <cstdlib>
 #include <cstring>
@@ -22,6 +23,7 @@ void usage(std::ostream& os, const char* program) {
        << "  -f, --features orb|surf      the extractor: orb (binary rows, Hamming; the default) or surf (64 floats, L2)\n"
        << "  -m, --merge-distance F       distance below which a match confirms a merge (default 20: ORB's Hamming scale; unit-length\n"
        << "                               float rows never lie further than 2 apart, so 20 confirms every match of theirs)\n"
+       << "  -D, --dense                  also densify (plane-sweep depth maps of the registered views, fused) and write PREFIX_dense.ply\n"
        << "  -v, --visual-debug N         accepted and ignored: there is no visual debugging\n";
 }
 
@@ -48,11 +50,12 @@ int main(int argc, char** argv) {
     std::string directory, prefix = "output", text;
     double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0;
     FeatureType features = FEATURES_ORB;
-    bool have_directory = false;
+    bool have_directory = false, dense = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
         const std::string arg = argv[i];
         if (arg == "-h" || arg == "--help") { usage(std::cout, argv[0]); return 0; }
+        if (arg == "-D" || arg == "--dense") { dense = true; continue; }
         if (option(argc, argv, i, "-p", "--input-directory", text, missing)) { directory = text; have_directory = !missing; }
         else if (option(argc, argv, i, "-o", "--output-prefix", text, missing)) prefix = text;
         else if (option(argc, argv, i, "-s", "--downscale", text, missing)) bad = !missing && (!number(text, downscale) || !(downscale > 0.0));
@@ -76,5 +79,8 @@ int main(int argc, char** argv) {
     sfm.setMergeFeatureMatchDistance((float)merge);
     if (!sfm.setImagesDirectory(directory)) return 1;
     if (sfm.runSfM() != OKAY) return 1;
-    return sfm.saveCloudAndCamerasToPLY(prefix) ? 0 : 1;
+    if (!sfm.saveCloudAndCamerasToPLY(prefix)) return 1;
+    if (!dense) return 0;
+    if (sfm.densify() != OKAY) return 1;
+    return sfm.saveDenseCloudToPLY(prefix) ? 0 : 1;
 }

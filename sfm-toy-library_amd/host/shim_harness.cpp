@@ -670,6 +670,75 @@ int sfmba_shim_run_sfm_typed(int feature_type, float merge_distance, int n_views
                       view_ptr, view_idx, feat_idx, ply_prefix);
 }
 
+// sfmba_shim_run_sfm_typed followed by SfM::densify() with the default DenseParams (tests/test_gpu_depth_pipeline.py).  On top of
+// sfmba_shim_run_sfm's outputs: the jobs densify made (*n_jobs of them: job_ref / z_near / z_far [n_views], job_src_ptr [n_views + 1],
+// job_src [4 n_views]), has_map [n_views], the depth maps of ALL views one after the other in view order (depth [sum of w h]; zeros
+// where a view has none) and the dense cloud (cap_dense rows: dense_xyz [..][3], dense_bgr [..][3], dense_view, dense_pixel).
+// ply_prefix != NULL: saveCloudAndCamerasToPLY and saveDenseCloudToPLY.  Returns as sfmba_shim_run_sfm; 10 + densify's code when the
+// run was OKAY and densify was not.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_dense(int feature_type, float merge_distance, int n_views, int channels, const int64_t* img_ptr, const unsigned char* px,
+                             const int32_t* w, const int32_t* h, int debug_level, float* poses, float* K, unsigned char* done, unsigned char* good,
+                             int* n_added, int32_t* added_view, unsigned char* added_posed, int64_t* added_cloud, int64_t cap_pts, int64_t cap_views,
+                             int64_t* n_pts, float* xyz, int64_t* view_ptr, int32_t* view_idx, int32_t* feat_idx, const char* ply_prefix, int* n_jobs,
+                             int32_t* job_ref, int64_t* job_src_ptr, int32_t* job_src, float* z_near, float* z_far, unsigned char* has_map, float* depth,
+                             int64_t cap_dense, int64_t* n_dense, float* dense_xyz, unsigned char* dense_bgr, int32_t* dense_view, int32_t* dense_pixel) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    sfm.setFeatureType((FeatureType)feature_type);
+    sfm.setMergeFeatureMatchDistance(merge_distance);
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    sfm.setImages(images);
+    *n_jobs = 0;
+    *n_dense = 0;
+    const int rc = flattenRun(sfm, sfm.runSfM(), n_views, poses, K, done, good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts,
+                              xyz, view_ptr, view_idx, feat_idx, ply_prefix);
+    if (rc != 0) return rc;
+    const ErrorCode code = sfm.densify();
+    if (code != OKAY) return 10 + (int)code;
+    job_src_ptr[0] = 0;
+    for (const DenseJob& j : sfm.getDenseJobs()) {
+        const int at = (*n_jobs)++;
+        job_ref[at] = j.reference; z_near[at] = j.zNear; z_far[at] = j.zFar;
+        job_src_ptr[at + 1] = job_src_ptr[at];
+        for (int s : j.sources) job_src[job_src_ptr[at + 1]++] = s;
+    }
+    size_t at = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const size_t n = (size_t)w[v] * h[v];
+        const cv::Mat& m = sfm.getDepthMaps()[(size_t)v];
+        has_map[v] = m.empty() ? 0 : 1;
+        if (m.empty()) std::memset(depth + at, 0, n * sizeof(float));
+        else std::memcpy(depth + at, m.ptr<float>(0), n * sizeof(float));
+        at += n;
+    }
+    const DenseCloud& cloud = sfm.getDenseCloud();
+    *n_dense = (int64_t)cloud.points.size();
+    if (*n_dense > cap_dense) return -2;
+    for (size_t i = 0; i < cloud.points.size(); ++i) {
+        dense_xyz[3 * i] = cloud.points[i].x; dense_xyz[3 * i + 1] = cloud.points[i].y; dense_xyz[3 * i + 2] = cloud.points[i].z;
+        for (int k = 0; k < 3; ++k) dense_bgr[3 * i + k] = cloud.bgr[3 * i + k];
+        dense_view[i] = cloud.views[i]; dense_pixel[i] = cloud.pixels[i];
+    }
+    if (ply_prefix && !sfm.saveDenseCloudToPLY(ply_prefix)) return -3;
+    return 0;
+}
+
+// SfM::densify() where it has to refuse (tests/test_depth_oracle_cpu.py; no device involved): what = 0 after setFeatures (there are
+// no pixels), 1 on images without a run, 2 on a fresh object.  Returns densify's code.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_densify_refusal(int what) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel(LOG_ERROR);
+    if (what == 0) sfm.setFeatures(std::vector<Features>(2), 640, 480);
+    if (what == 1) sfm.setImages(std::vector<cv::Mat>(2, cv::Mat(8, 8, CV_8U)));
+    const int code = (int)sfm.densify();
+    return code == 0 || !sfm.getDepthMaps().empty() || !sfm.getDenseCloud().points.empty() ? 100 + code : code;
+}
+
 // Flat-array driver of sfmtoylib::SfM::setImagesDirectory (tests/test_sfm_scene_cpu.py; no device involved): the images come back
 // one after the other in px (cap bytes), w / h [cap_images], *channels = 1 or 3.  Returns the number of images, -1 when the call
 // reported failure, -2 if a capacity is too small.
