@@ -1000,6 +1000,92 @@ SFMBA_API int sfmba_depth_fuse(int device, int n_images, const int64_t* img_ptr 
                 int64_t* pt_ptr /*[n_images+1]*/, float* xyz /*[cap][3]*/, unsigned char* bgr /*[cap][3]*/, int32_t* src_image /*[cap]*/,
                 int32_t* src_pixel /*[cap]*/, int64_t cap, int64_t* total);
 
+/* ---- matching by optical flow: pyramidal Lucas-Kanade and the snap to key points (SfMFeatureMatching::createFlowMatchMatrix) -----
+ * The reference's legacy tree matched video-like input without descriptors (legacy/SfMToyLib_Old/OFFeatureMatcher.cpp): it tracked
+ * the key points of image i into image j with gpu::PyrLKOpticalFlow::sparse, snapped every flow end point to a key point of j
+ * within 2 px, applied a 0.7 ratio test and dropped duplicates in query order.  Here a list of image pairs is tracked in one call and
+ * snapped in a second.  THE TRACKER'S CONTRACT IS OUR OWN AND EQUALS NOBODY'S (OpenCV's tracker is float arithmetic in an unstated
+ * order); like the dense unit's it is stated so that the device is held BIT FOR BIT to a CPU restatement (tests/flow_oracle.py):
+ * integer-exact samples at 1/16 px, exact window sums, a handful of fp64 operations, EVERY ONE ROUNDED ON ITS OWN (no fused
+ * multiply-add anywhere; csrc/flow_math.h switches the compiler's contraction off).
+ *
+ * sfmba_flow_track
+ *   images        as sfmba_orb_extract takes them, with the same BGR -> gray rule.  Images may differ in size.
+ *   pairs         pair p tracks from image pair_src[p] into image pair_dst[p] (src == dst is allowed) and owns the points
+ *                 pt_ptr[p] .. pt_ptr[p+1]-1 of pts float [.][2]: finite coordinates (x, y) in the source image.
+ *                 Shared: n_levels L in 1..8, radius r in 1..10 (the window holds n = (2r+1)^2 pixels), max_iters in 1..64,
+ *                 min_eig >= 0 (a finite float).
+ *   pyramid       per image, once per group of pairs that names it: level 0 is the gray image; level l+1 has the size
+ *                 ((w+1)>>1, (h+1)>>1) and its pixel (x, y) is (sum_ij k_i k_j I_l(clamp(2x+i-2), clamp(2y+j-2)) + 128) >> 8 with
+ *                 k = 1 4 6 4 1, i, j = 0..4, coordinates clamped to the image: exact integer arithmetic.
+ *   sampler       S(I, su, sv) clamps su to [0, 16 (w-1)] and sv to [0, 16 (h-1)] and then applies the 1/16 px bilinear rule of
+ *                 sfmba_depth_sweep's sample: a 12-bit integer 0..4080, defined for every (su, sv).
+ *   per point     from level L-1 down to level 0.  The displacement dq is an integer 2-vector in 1/16 px of the current level; it
+ *                 starts at 0 and doubles on each step down a level.  At level l, per coordinate, c = floor(16 (x / 2^l) + 0.5)
+ *                 with x converted to double exactly (the scaling is exact; c saturates at +-2^28, which no output can tell from
+ *                 the exact value: such a centre reads the clamped edge wherever dq takes it and never has status 1).
+ *                 T(i, j) = S(src_l, c + 16 (i, j)) for i, j in -r-1 .. r+1; over i, j in -r .. r:
+ *                 gx = T(i+1, j) - T(i-1, j), gy = T(i, j+1) - T(i, j-1), Gxx = sum gx^2, Gyy = sum gy^2, Gxy = sum gx gy, exact
+ *                 in int64 (each below 441 * 4080^2 = 7341062400 < 2^33).  In fp64: det = (double)Gxx (double)Gyy -
+ *                 (double)Gxy (double)Gxy, df = (double)(Gxx - Gyy), lam = ((double)(Gxx + Gyy) - sqrt(df df + 4.0 ((double)Gxy
+ *                 (double)Gxy))) 0.5.  The level is TRACKABLE iff det > 0 and lam >= ((double)min_eig (double)n) 1024.0 --
+ *                 1024 = (2 * 16)^2 is the scale of a central difference of x16 samples, so min_eig is a per-pixel squared gradient
+ *                 in (gray levels / px)^2.  A level that is not trackable carries dq on unchanged.
+ *   iteration     on a trackable level, at most max_iters times: J(i, j) = S(dst_l, c + dq + 16 (i, j)), D = T - J,
+ *                 bx = sum D gx, by = sum D gy (exact int64); nx = (double)Gyy (double)bx - (double)Gxy (double)by,
+ *                 ny = (double)Gxx (double)by - (double)Gxy (double)bx; sx = floor((32.0 nx) / det + 0.5) clamped to +-16 r, sy
+ *                 likewise (32 = 16 units per pixel times 2 for the central difference).  If sx == 0 and sy == 0 the level ends
+ *                 (that evaluation counts as an iteration), otherwise dq += (sx, sy).  No oscillation rule: a point may run to
+ *                 max_iters on a two-cycle of +-1/16 px.
+ *   outputs       per point, in input order: next float [.][2] = (float)((double)x + (double)dq_x / 16.0), y likewise (dq of
+ *                 level 0); status uint8 = 1 iff level 0 was trackable and c_0 + dq lies in [0, 16 (w_dst-1)] x [0, 16 (h_dst-1)],
+ *                 tested unclamped; err float = (float)((double)(sum |T - J|) / (16.0 (double)n)) over the window at level 0 with
+ *                 the final dq (one more evaluation after the last step) when level 0 was trackable, 0 otherwise.
+ *   debug         each may be NULL.  dbg_G int64 [.][L][3] = Gxx, Gyy, Gxy and dbg_state int32 [.][L][4] = the trackable flag, the
+ *                 iterations run and the dq leaving the level, per (point, level l; l = 0 is the finest).  dbg_pyramid uint8: image
+ *                 i's levels 0 .. L-1 back to back (each row-major), images in order; only images that a pair names are written.
+ *   SFMBA_ERR_INVALID_ARG (nothing written): whatever sfmba_orb_extract refuses about images; n_levels, radius, max_iters or
+ *                 min_eig (NaN included) outside the ranges above; a pair index out of range; a pt_ptr that does not start at 0 or
+ *                 decreases; a point coordinate that is not finite; 2^31 or more points in one call.
+ *   Host pointers in and out, synchronous.  Deterministic; pairs go to the device in consecutive groups under a fixed scratch bound
+ *   (512 MiB of images, pyramids and per-point arrays) and the result does not depend on the grouping: a batch equals the
+ *   concatenation of single-pair calls.
+ *   First choices that nobody has tuned: L = 4, r = 7, max_iters = 20, min_eig = 1.
+ *
+ * sfmba_flow_match
+ *   inputs        per pair p the tracker's next, status and err with the same pt_ptr (queries); per image i its key points
+ *                 kp_xy[kp_ptr[i] .. kp_ptr[i+1]-1] float [.][2], fewer than 2^22 per image; pair p's train set is that of image
+ *                 pair_dst[p].  max_err (finite), radius > 0 (finite), ratio > 0 (finite).  The reference's values: 12, 2, 0.7.
+ *   eligible      query q iff status[q] != 0 and err[q] < max_err.
+ *   distance      s(q, j) = dx dx + dy dy with dx = (double)next_x - (double)kp_x, dy likewise; j is IN RANGE iff
+ *                 s <= (double)radius (double)radius.
+ *   candidate     none in range: no candidate.  Exactly one: that one.  Two or more: of the two smallest (s, j) in lexicographic
+ *                 order the best is the candidate iff sqrt(s_best) < ratio sqrt(s_second), with correctly rounded fp64 roots -- so
+ *                 two coincident key points give 0 < 0 and the query is dropped.
+ *   duplicates    among the candidates of a pair that name the same train index the lowest q wins (the reference's
+ *                 found_in_imgpts_j set, walked in query order; on the device an integer atomicMin per train key point, which does
+ *                 not depend on the arrival order).
+ *   output        (query_idx = q - pt_ptr[p], train_idx = j, distance = (float)sqrt(s_best)) in ascending q within a pair, with the
+ *                 pair_ptr CSR, the capacity protocol and *total of sfmba_match_features.
+ *   SFMBA_ERR_INVALID_ARG (nothing written): max_err, radius or ratio not finite, radius or ratio <= 0; a pair index out of range;
+ *                 a pt_ptr or kp_ptr that does not start at 0 or decreases; 2^22 or more key points in one image; 2^31 or more
+ *                 queries in one call.
+ *   Host pointers in and out, synchronous, deterministic.  The call is one batch: 45 bytes of device memory per query and 4 per (pair,
+ *   train key point).  SFMBA_ABI_VERSION stays 6: adding symbols is backward compatible.
+ */
+SFMBA_API int sfmba_flow_track(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/,
+                int n_pairs, const int32_t* pair_src /*[n_pairs]*/, const int32_t* pair_dst /*[n_pairs]*/,
+                const int64_t* pt_ptr /*[n_pairs+1]*/, const float* pts /*[pt_ptr[n_pairs]][2]*/, int n_levels /*1..8*/,
+                int radius /*1..10*/, int max_iters /*1..64*/, float min_eig /*>= 0*/, float* next /*[.][2]*/,
+                unsigned char* status /*[.]*/, float* err /*[.]*/, int64_t* dbg_G /*[.][n_levels][3] or NULL*/,
+                int32_t* dbg_state /*[.][n_levels][4] or NULL*/, unsigned char* dbg_pyramid /*or NULL*/);
+SFMBA_API int sfmba_flow_match(int device, int n_images, const int64_t* kp_ptr /*[n_images+1]*/, const float* kp_xy /*[kp_ptr[n_images]][2]*/,
+                int n_pairs, const int32_t* pair_dst /*[n_pairs]*/, const int64_t* pt_ptr /*[n_pairs+1]*/, const float* next /*[.][2]*/,
+                const unsigned char* status /*[.]*/, const float* err /*[.]*/, float max_err, float radius, double ratio,
+                int64_t* pair_ptr /*[n_pairs+1]*/, int32_t* query_idx, int32_t* train_idx, float* distance /*or NULL*/, int64_t cap,
+                int64_t* total);
+
 /* ---- reading photographs: baseline JPEG decode and bilinear resize (SfM::setImagesDirectory) -----------------------------------
  * The reference reads every image with imread and shrinks it with resize(..., Size(), f, f) (SfMToyLib/SfM.cpp:125-129).  Here a
  * whole list of files is decoded, and a whole list of images resized, in one call each.  THE CONTRACT IS INTEGER-EXACT: the decode

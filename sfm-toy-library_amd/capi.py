@@ -38,7 +38,7 @@ SYMBOLS = [
     "sfmba_homography_ransac", "sfmba_essential_ransac", "sfmba_orb_extract", "sfmba_triangulate_pairs",
     "sfmba_jpeg_info", "sfmba_resized_size", "sfmba_jpeg_decode", "sfmba_resize_images",
     "sfmba_png_info", "sfmba_png_decode", "sfmba_match_features_l2", "sfmba_surf_extract",
-    "sfmba_depth_sweep", "sfmba_depth_fuse",
+    "sfmba_depth_sweep", "sfmba_depth_fuse", "sfmba_flow_track", "sfmba_flow_match",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -455,6 +455,106 @@ def depth_fuse(images, K, P, depth_maps, checks, rel_tol=0.01, min_consistent=1,
     _check(rc)
     n = int(total.value)
     return {"xyz": xyz[:n].copy(), "bgr": bgr[:n].copy(), "src_image": si[:n].copy(), "src_pixel": sp[:n].copy(), "pt_ptr": pt_ptr.copy()}
+
+
+def _flow_pairs(pairs, lists, width):
+    pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if len(lists) != len(pairs):
+        raise ValueError("one point list per pair")
+    rows = [np.asarray(x, dtype=np.float32).reshape(-1, width) for x in lists]
+    ptr = np.zeros(len(pairs) + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum([len(r) for r in rows])
+    flat = np.ascontiguousarray(np.concatenate(rows, axis=0) if rows else np.zeros((0, width), np.float32))
+    if not len(flat):
+        flat = np.zeros((1, width), np.float32)
+    return np.ascontiguousarray(pairs[:, 0]) if len(pairs) else np.zeros(1, np.int32), \
+        np.ascontiguousarray(pairs[:, 1]) if len(pairs) else np.zeros(1, np.int32), ptr, flat, len(pairs)
+
+
+def flow_pyramid_sizes(w, h, n_levels):
+    """(w, h) of the n_levels pyramid levels of a w x h image (sfmba_flow_track)."""
+    out = []
+    for _ in range(n_levels):
+        out.append((w, h))
+        w, h = (w + 1) >> 1, (h + 1) >> 1
+    return out
+
+
+def flow_track(images, pairs, points, n_levels=4, radius=7, max_iters=20, min_eig=1.0, debug=False, device=0):
+    """sfmba_flow_track: pyramidal Lucas-Kanade tracking of the points of a list of image pairs (the contract is in include/sfmba.h).
+
+    images: as orb_extract.  pairs: list of (src, dst) image indices; points: per pair a float32 array [n, 2] of (x, y) in the source
+    image.  Returns one tuple per pair: (next float32 [n, 2], status uint8 [n], err float32 [n]); with debug=True a pair of lists:
+    per pair (next, status, err, G int64 [n, L, 3], state int32 [n, L, 4]) and per image its L pyramid levels (uint8 [h_l, w_l]; of
+    an image that no pair names, zeros)."""
+    imgs, channels, img_ptr, flat, wd, ht = _flat_images(images)
+    ps, pd, pt_ptr, pts, n_pairs = _flow_pairs(pairs, points, 2)
+    n = int(pt_ptr[-1])
+    L = max(int(n_levels), 1)
+    nxt, status, err = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32)
+    G, state = np.zeros((max(n, 1), L, 3), np.int64), np.zeros((max(n, 1), L, 4), np.int32)
+    in_range = 1 <= n_levels <= 8
+    sizes = [flow_pyramid_sizes(int(w), int(h), L if in_range else 1) for w, h in zip(wd, ht)]
+    pyr = np.zeros(max(sum(w * h for s in sizes for w, h in s), 1), np.uint8)
+    lp, bp, fp = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte), C.POINTER(C.c_float)
+    _check(lib().sfmba_flow_track(C.c_int(device), C.c_int(len(imgs)), _p(img_ptr, lp), flat.ctypes.data_as(bp), _p(wd, _ip), _p(ht, _ip),
+                                  C.c_int(channels), C.c_int(n_pairs), _p(ps, _ip), _p(pd, _ip), _p(pt_ptr, lp), pts.ctypes.data_as(fp),
+                                  C.c_int(n_levels), C.c_int(radius), C.c_int(max_iters), C.c_float(min_eig), nxt.ctypes.data_as(fp),
+                                  status.ctypes.data_as(bp), err.ctypes.data_as(fp), _p(G, lp) if debug else None,
+                                  _p(state, _ip) if debug else None, pyr.ctypes.data_as(bp) if debug else None))
+    out = []
+    for p in range(n_pairs):
+        a, b = int(pt_ptr[p]), int(pt_ptr[p + 1])
+        row = (nxt[a:b].copy(), status[a:b].copy(), err[a:b].copy())
+        out.append(row + (G[a:b].copy(), state[a:b].copy()) if debug else row)
+    if not debug:
+        return out
+    levels, at = [], 0
+    for s in sizes:
+        levels.append([])
+        for w, h in s:
+            levels[-1].append(pyr[at:at + w * h].reshape(h, w).copy())
+            at += w * h
+    return out, levels
+
+
+def flow_match(keypoints, pairs, tracked, max_err=12.0, radius=2.0, ratio=0.7, cap=None, device=0):
+    """sfmba_flow_match: snap the tracker's end points to the key points of the destination image, ratio test, first come first served
+    (the contract is in include/sfmba.h).
+
+    keypoints: per image a float32 array [n_i, 2]; pairs: the (src, dst) list the tracker was given; tracked: per pair (next, status,
+    err, ...) as flow_track returns it.  Returns (pair_ptr int64 [n_pairs+1], query_idx, train_idx, distance float32).  cap=None sizes
+    the outputs for one entry per query; a smaller cap is retried once with the size the library reports."""
+    kps = [np.asarray(k, dtype=np.float32).reshape(-1, 2) for k in keypoints]
+    kp_ptr = np.zeros(len(kps) + 1, dtype=np.int64)
+    kp_ptr[1:] = np.cumsum([len(k) for k in kps])
+    kp = np.ascontiguousarray(np.concatenate(kps, axis=0) if kps else np.zeros((0, 2), np.float32))
+    if not len(kp):
+        kp = np.zeros((1, 2), np.float32)
+    _, pd, pt_ptr, nxt, n_pairs = _flow_pairs(pairs, [t[0] for t in tracked], 2)
+    n = int(pt_ptr[-1])
+    status = np.ascontiguousarray(np.concatenate([np.asarray(t[1], np.uint8).reshape(-1) for t in tracked] + [np.zeros(0, np.uint8)]))
+    err = np.ascontiguousarray(np.concatenate([np.asarray(t[2], np.float32).reshape(-1) for t in tracked] + [np.zeros(0, np.float32)]))
+    if len(status) != n or len(err) != n:
+        raise ValueError("next, status and err of a pair must have one length")
+    if not n:
+        status, err = np.zeros(1, np.uint8), np.zeros(1, np.float32)
+    cap = n if cap is None else int(cap)
+    lp, bp, fp = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte), C.POINTER(C.c_float)
+    ptr = np.zeros(n_pairs + 1, dtype=np.int64)
+    total = C.c_int64(0)
+    for _ in range(2):
+        q, t, d = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float32)
+        rc = lib().sfmba_flow_match(C.c_int(device), C.c_int(len(kps)), _p(kp_ptr, lp), kp.ctypes.data_as(fp), C.c_int(n_pairs), _p(pd, _ip),
+                                    _p(pt_ptr, lp), nxt.ctypes.data_as(fp), status.ctypes.data_as(bp), err.ctypes.data_as(fp),
+                                    C.c_float(max_err), C.c_float(radius), C.c_double(ratio), _p(ptr, lp), _p(q, _ip), _p(t, _ip), _p(d, fp),
+                                    C.c_int64(cap), C.byref(total))
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        cap = int(total.value)
+    _check(rc)
+    m = int(total.value)
+    return ptr, q[:m].copy(), t[:m].copy(), d[:m].copy()
 
 
 class _ImageInfo(C.Structure):

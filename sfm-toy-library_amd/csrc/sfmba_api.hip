@@ -12,6 +12,8 @@
 #include "orb_extract.h"
 #include "surf_extract.h"
 #include "depth_sweep.h"
+#include "flow_track.h"
+#include "flow_math.h"
 #include "jpeg_decode.h"
 #include "jpeg_math.h"
 #include "png_decode.h"
@@ -774,6 +776,98 @@ int sfmba_depth_fuse(int device, int n_images, const int64_t* img_ptr, const uns
     if (rc == DEPTH_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "depth_fuse: output capacity too small");
     if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "depth_fuse: device allocation failed");
     if (rc) return fail(SFMBA_ERR_HIP, std::string("depth_fuse: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+// ---- matching by optical flow: pyramidal Lucas-Kanade and the snap to key points (SfMFeatureMatching::createFlowMatchMatrix) -----
+namespace {
+// what both flow calls refuse about the pair list and the points' CSR; 0 or the failure
+int flow_check_pairs(const char* who, int n_images, int n_pairs, const int32_t* pair_a, const int32_t* pair_b, const int64_t* pt_ptr) {
+    const std::string w(who);
+    if (n_images < 0 || n_pairs < 0 || !pt_ptr || (n_pairs > 0 && !pair_b)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (pt_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, w + ": pt_ptr must start at 0");
+    for (int p = 0; p < n_pairs; ++p) {
+        if ((pair_a && (pair_a[p] < 0 || pair_a[p] >= n_images)) || pair_b[p] < 0 || pair_b[p] >= n_images)
+            return fail(SFMBA_ERR_INVALID_ARG, w + ": pair index out of range");
+        if (pt_ptr[p + 1] < pt_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, w + ": pt_ptr not monotone");
+    }
+    if (pt_ptr[n_pairs] >= (int64_t)1 << 31) return fail(SFMBA_ERR_INVALID_ARG, w + ": 2^31 or more points in one call");
+    return 0;
+}
+}  // namespace
+int sfmba_flow_track(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                     int channels, int n_pairs, const int32_t* pair_src, const int32_t* pair_dst, const int64_t* pt_ptr, const float* pts,
+                     int n_levels, int radius, int max_iters, float min_eig, float* next, unsigned char* status, float* err, int64_t* dbg_G,
+                     int32_t* dbg_state, unsigned char* dbg_pyramid) {
+    if (n_images < 0 || !img_ptr || (n_images > 0 && (!width || !height)) || (n_pairs > 0 && !pair_src))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: channels must be 1 or 3");
+    if (n_levels < 1 || n_levels > FLOW_MAX_LEVELS) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: n_levels must be in 1..8");
+    if (radius < 1 || radius > FLOW_MAX_RADIUS) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: radius must be in 1..10");
+    if (max_iters < 1 || max_iters > FLOW_MAX_ITERS) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: max_iters must be in 1..64");
+    if (!std::isfinite(min_eig) || min_eig < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: min_eig must be finite and >= 0");
+    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
+            return fail(SFMBA_ERR_INVALID_ARG, "flow_track: an image dimension lies outside 1..16384");
+        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
+            return fail(SFMBA_ERR_INVALID_ARG, "flow_track: img_ptr does not agree with width * height * channels");
+    }
+    if (n_images > 0 && !pixels) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (int rc = flow_check_pairs("flow_track", n_images, n_pairs, pair_src, pair_dst, pt_ptr)) return rc;
+    const int64_t n_pts = pt_ptr[n_pairs];
+    if (n_pts > 0 && (!pts || !next || !status || !err)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    for (int64_t q = 0; q < 2 * n_pts; ++q)
+        if (!std::isfinite(pts[q])) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: non-finite coordinate of point " + std::to_string((long long)(q / 2)));
+    if (n_pairs == 0) return check_device(device);
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    // SFMBA_FLOW_TIMING: one stderr line per call with the HIP-event times of its phases (tools/flow_bench.py)
+    double tm[FLOW_T_COUNT];
+    const bool timing = std::getenv("SFMBA_FLOW_TIMING") != nullptr;
+    rc = flow_track(ck.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, n_pairs, pair_src, pair_dst, pt_ptr, pts, n_levels,
+                    radius, max_iters, min_eig, next, status, err, dbg_G, dbg_state, dbg_pyramid, timing ? tm : nullptr);
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba flow_track] upload_ms %.6f gray_ms %.6f pyramid_ms %.6f track_ms %.6f download_ms %.6f groups %d\n",
+                     tm[FLOW_T_UPLOAD], tm[FLOW_T_GRAY], tm[FLOW_T_PYRAMID], tm[FLOW_T_TRACK], tm[FLOW_T_DOWNLOAD], (int)tm[FLOW_T_GROUPS]);
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "flow_track: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("flow_track: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+int sfmba_flow_match(int device, int n_images, const int64_t* kp_ptr, const float* kp_xy, int n_pairs, const int32_t* pair_dst,
+                     const int64_t* pt_ptr, const float* next, const unsigned char* status, const float* err, float max_err, float radius,
+                     double ratio, int64_t* pair_ptr, int32_t* query_idx, int32_t* train_idx, float* distance, int64_t cap, int64_t* total) {
+    if (cap < 0 || !kp_ptr || !pair_ptr || !total || (cap > 0 && (!query_idx || !train_idx))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (!std::isfinite(max_err)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: max_err must be finite");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: radius must be finite and > 0");
+    if (!std::isfinite(ratio) || !(ratio > 0.0)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: ratio must be finite and > 0");
+    if (int rc = flow_check_pairs("flow_match", n_images, n_pairs, nullptr, pair_dst, pt_ptr)) return rc;
+    if (kp_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: kp_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        const int64_t n = kp_ptr[i + 1] - kp_ptr[i];
+        if (n < 0) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: kp_ptr not monotone");
+        if (n >= ((int64_t)1 << 22)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: an image has 2^22 or more key points");
+    }
+    const int64_t n_pts = pt_ptr[n_pairs];
+    if ((n_pts > 0 && (!next || !status || !err)) || (kp_ptr[n_images] > 0 && !kp_xy)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (n_pts == 0) {
+        for (int p = 0; p <= n_pairs; ++p) pair_ptr[p] = 0;
+        *total = 0;
+        return check_device(device);
+    }
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    double tm[FLOWM_T_COUNT];
+    const bool timing = std::getenv("SFMBA_FLOW_TIMING") != nullptr;
+    rc = flow_match(ck.kit.stream, device, n_images, kp_ptr, kp_xy, n_pairs, pair_dst, pt_ptr, next, status, err, max_err, radius, ratio, pair_ptr,
+                    query_idx, train_idx, distance, cap, total, timing ? tm : nullptr);
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba flow_match] upload_ms %.6f near_ms %.6f compact_ms %.6f download_ms %.6f\n", tm[FLOWM_T_UPLOAD], tm[FLOWM_T_NEAR],
+                     tm[FLOWM_T_COMPACT], tm[FLOWM_T_DOWNLOAD]);
+    if (rc == FLOW_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "flow_match: output capacity too small");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "flow_match: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("flow_match: ") + hipGetErrorString((hipError_t)rc));
     return SFMBA_OK;
 }
 // ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------

@@ -89,6 +89,8 @@ SfM::SfM(const float downscale) :
         mDownscaleFactor(downscale),
         mMergeFeatureMatchDistance(20.0f),                 // MERGE_CLOUD_FEATURE_MIN_MATCH_DISTANCE, SfM.cpp:51
         mFeatureType(FEATURES_ORB),
+        mMatcherType(MATCHER_DESCRIPTORS),
+        mFlowPairWindow(0),
         mFeaturesGiven(false),
         mDownscaleApplied(false),
         mCols(0), mRows(0),
@@ -224,6 +226,14 @@ ErrorCode SfM::runSfM() {
                   << "and features are taken as they are" << std::endl;
         return ERROR;
     }
+    if (mMatcherType == MATCHER_FLOW && mFeaturesGiven) {
+        std::cerr << "runSfM: MATCHER_FLOW tracks the key points through the images, and setFeatures gave none" << std::endl;
+        return ERROR;
+    }
+    if (mMatcherType == MATCHER_FLOW && mFlowPairWindow < 0) {
+        std::cerr << "runSfM: the flow pair window must be >= 0" << std::endl;
+        return ERROR;
+    }
     startRun(n_views);
     double* const sums = mTiming ? mStageMs : nullptr;
 
@@ -235,7 +245,9 @@ ErrorCode SfM::runSfM() {
     say(LOG_INFO, "stage 2: match matrix");
     {
         StageClock clock(sums, T_MATCH);
-        if (!SfMFeatureMatching::createFeatureMatchMatrix(mImageFeatures, mFeatureMatchMatrix)) return ERROR;
+        if (mMatcherType == MATCHER_FLOW) {
+            if (!SfMFeatureMatching::createFlowMatchMatrix(mImages, mImageFeatures, mFeatureMatchMatrix, mFlowPairWindow)) return ERROR;
+        } else if (!SfMFeatureMatching::createFeatureMatchMatrix(mImageFeatures, mFeatureMatchMatrix)) return ERROR;
     }
     say(LOG_INFO, "stage 3: baseline pair");
     if (!findBaselineTriangulation()) {

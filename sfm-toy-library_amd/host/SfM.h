@@ -31,6 +31,13 @@
 //                 <= 2, so the default 20 CONFIRMS EVERY MATCH.  A better default is not chosen here: nobody has measured one.
 //   features      setFeatureType chooses the extractor of a run from images: FEATURES_ORB (the default; binary rows, Hamming) or
 //                 FEATURES_SURF (sfmba_surf_extract: 64 floats, the L2 branch of the matcher).  It has no effect after setFeatures.
+//   matcher       setMatcherType chooses stage 2 of a run from images: MATCHER_DESCRIPTORS (the default: the 2-NN ratio-test matcher over
+//                 the descriptors) or MATCHER_FLOW (SfMFeatureMatching::createFlowMatchMatrix: the key points of whichever extractor
+//                 is selected, tracked from image i into image j by pyramidal Lucas-Kanade and snapped to j's key points), for
+//                 video-like input.  setFlowPairWindow(k), k > 0, matches only views at most k apart; the other entries of the
+//                 matrix stay empty and everything downstream reads the matrix as it is.  A flow match's distance is its snap
+//                 distance in pixels, at most 2, so the default merge distance 20 CONFIRMS EVERY FLOW MATCH.  After setFeatures
+//                 there are no pixels to track in: runSfM returns ERROR for MATCHER_FLOW.
 //   end           every view is done.
 //   downscale     the factor of the constructor is applied by setImagesDirectory at load time, as in the reference (SfM.cpp:125-129): the
 //                 JPEG files and the PNG files in ONE decode call each that also resizes (SfMImageUtilities::readImages), the PNM
@@ -106,7 +113,8 @@ public:
 
     /**
      * The distance below which a feature match confirms a merge in SfMAssociation::mergeNewPointCloud.  Default 20, the reference's
-     * constant for ORB's Hamming distances; float descriptors need a value on the scale of their own L2 distances.
+     * constant for ORB's Hamming distances; float descriptors need a value on the scale of their own L2 distances.  With
+     * MATCHER_FLOW a match's distance is its snap distance in pixels (<= 2): the default 20 confirms every flow match.
      */
     void setMergeFeatureMatchDistance(float maxDistance) { mMergeFeatureMatchDistance = maxDistance; }
 
@@ -116,6 +124,15 @@ public:
      * (their distances are <= 2).
      */
     void setFeatureType(FeatureType type) { mFeatureType = type; }
+
+    /**
+     * The matcher of stage 2: MATCHER_DESCRIPTORS (default) or MATCHER_FLOW (optical flow between the images, for frame sequences;
+     * see `matcher` at the top of this file).  MATCHER_FLOW needs the images: after setFeatures runSfM returns ERROR.
+     */
+    void setMatcherType(MatcherType type) { mMatcherType = type; }
+
+    /** MATCHER_FLOW only: k > 0 matches view i with views i+1 .. i+k only; 0 (default) matches all pairs.  Negative: runSfM returns ERROR. */
+    void setFlowPairWindow(int window) { mFlowPairWindow = window; }
 
     /** Run the pipeline (the contract is at the top of this file); every call starts from the images / features again. */
     ErrorCode runSfM();
@@ -178,6 +195,8 @@ private:
     float                     mDownscaleFactor;
     float                     mMergeFeatureMatchDistance;
     FeatureType               mFeatureType;
+    MatcherType               mMatcherType;
+    int                       mFlowPairWindow;
     bool                      mFeaturesGiven;
     bool                      mDownscaleApplied; // the images came from setImagesDirectory, which applied mDownscaleFactor
     int                       mCols, mRows;      // of image 0, or as given to setFeatures

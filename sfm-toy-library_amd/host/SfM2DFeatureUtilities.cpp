@@ -1,5 +1,5 @@
 // SfM2DFeatureUtilities.cpp -- host side of the feature extractor and matcher: flattens the images / descriptor matrices, calls
-// the C ABI (include/sfmba.h, sfmba_orb_extract, sfmba_surf_extract, sfmba_match_features, sfmba_match_features_l2) and rebuilds the reference's Features and Matching lists.
+// the C ABI (include/sfmba.h, sfmba_orb_extract, sfmba_surf_extract, sfmba_match_features, sfmba_match_features_l2, sfmba_flow_track, sfmba_flow_match) and rebuilds the reference's Features and Matching lists.
 // See SfM2DFeatureUtilities.h.
 #include "SfM2DFeatureUtilities.h"
 
@@ -15,6 +15,13 @@ namespace sfmtoylib {
 namespace {
 
 const double NN_MATCH_RATIO = 0.8f;     // SfM2DFeatureUtilities.cpp:35 -- a float literal widened to double
+
+// the tracker's parameters: first choices that nobody has tuned
+const int FLOW_LEVELS = 4, FLOW_RADIUS = 7, FLOW_MAX_ITERS = 20;
+const float FLOW_MIN_EIG = 1.0f;
+// the snap's are the reference's (legacy/SfMToyLib_Old/OFFeatureMatcher.cpp): error below 12, a key point within 2 px, ratio 0.7
+const float FLOW_MAX_ERR = 12.0f, FLOW_SNAP_RADIUS = 2.0f;
+const double FLOW_RATIO = 0.7;
 
 struct FlatDescriptors {
     std::vector<int64_t> ptr;
@@ -93,6 +100,31 @@ bool matchPairs(const std::vector<const Features*>& images, const std::vector<in
     return true;
 }
 
+// The pixels of images[0..n-1] back to back, as the image calls of include/sfmba.h take them; false (with a stderr line) unless all
+// are non-empty and of one type, CV_8U or CV_8UC3.
+bool flattenImages(const std::vector<cv::Mat>& images, const char* who, std::vector<int64_t>& ptr, std::vector<int32_t>& width,
+                   std::vector<int32_t>& height, int& channels, std::vector<unsigned char>& pixels) {
+    const size_t n = images.size();
+    ptr.assign(n + 1, 0);
+    width.assign(n, 0);
+    height.assign(n, 0);
+    const int type = images[0].type();
+    if (type != CV_8U && type != CV_8UC3) { std::fprintf(stderr, "%s: images must be CV_8U or CV_8UC3\n", who); return false; }
+    channels = type == CV_8UC3 ? 3 : 1;
+    for (size_t i = 0; i < n; ++i) {
+        if (images[i].empty() || images[i].type() != type) { std::fprintf(stderr, "%s: empty image or image types differ\n", who); return false; }
+        width[i] = images[i].cols; height[i] = images[i].rows;
+        ptr[i + 1] = ptr[i] + (int64_t)images[i].cols * images[i].rows * channels;
+    }
+    pixels.resize((size_t)ptr[n]);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t row = (size_t)width[i] * (size_t)channels;
+        for (int r = 0; r < height[i]; ++r)                                   // row by row: an OpenCV matrix need not be continuous
+            std::memcpy(&pixels[(size_t)ptr[i] + (size_t)r * row], images[i].ptr<unsigned char>(r), row);
+    }
+    return true;
+}
+
 }  // namespace
 
 Features SfM2DFeatureUtilities::extractFeatures(const cv::Mat& image) {
@@ -122,22 +154,11 @@ bool SfMFeatureExtraction::extractFeatures(const std::vector<cv::Mat>& images, s
     if (featureType != FEATURES_ORB && featureType != FEATURES_SURF) { std::fprintf(stderr, "extractFeatures: unknown feature type\n"); return false; }
     if (n == 0) return true;
     const bool surf = featureType == FEATURES_SURF;
-    std::vector<int64_t> ptr(n + 1, 0), kp_ptr(n + 1, 0);
-    std::vector<int32_t> width(n), height(n);
-    const int type = images[0].type();
-    if (type != CV_8U && type != CV_8UC3) { std::fprintf(stderr, "extractFeatures: images must be CV_8U or CV_8UC3\n"); return false; }
-    const int channels = type == CV_8UC3 ? 3 : 1;
-    for (size_t i = 0; i < n; ++i) {
-        if (images[i].empty() || images[i].type() != type) { std::fprintf(stderr, "extractFeatures: empty image or image types differ\n"); return false; }
-        width[i] = images[i].cols; height[i] = images[i].rows;
-        ptr[i + 1] = ptr[i] + (int64_t)images[i].cols * images[i].rows * channels;
-    }
-    std::vector<unsigned char> pixels((size_t)ptr[n]);
-    for (size_t i = 0; i < n; ++i) {
-        const size_t row = (size_t)width[i] * (size_t)channels;
-        for (int r = 0; r < height[i]; ++r)                                   // row by row: an OpenCV matrix need not be continuous
-            std::memcpy(&pixels[(size_t)ptr[i] + (size_t)r * row], images[i].ptr<unsigned char>(r), row);
-    }
+    std::vector<int64_t> ptr, kp_ptr(n + 1, 0);
+    std::vector<int32_t> width, height;
+    std::vector<unsigned char> pixels;
+    int channels = 1;
+    if (!flattenImages(images, "extractFeatures", ptr, width, height, channels, pixels)) return false;
     std::vector<sfmba_orb_keypoint> kp;
     std::vector<sfmba_surf_keypoint> skp;
     std::vector<unsigned char> desc;
@@ -203,6 +224,64 @@ bool SfMFeatureMatching::createFeatureMatchMatrix(const std::vector<Features>& i
     std::vector<Matching> out;
     if (!matchPairs(images, left, right, out)) return false;
     for (size_t p = 0; p < left.size(); ++p) featureMatchMatrix[(size_t)left[p]][(size_t)right[p]].swap(out[p]);
+    return true;
+}
+
+bool SfMFeatureMatching::createFlowMatchMatrix(const std::vector<cv::Mat>& images, const std::vector<Features>& imageFeatures,
+                                               MatchMatrix& featureMatchMatrix, int pairWindow) {
+    const size_t numImages = imageFeatures.size();
+    featureMatchMatrix.assign(numImages, std::vector<Matching>(numImages));
+    if (images.size() != numImages) { std::fprintf(stderr, "createFlowMatchMatrix: %zu images but %zu feature sets\n", images.size(), numImages); return false; }
+    if (pairWindow < 0) { std::fprintf(stderr, "createFlowMatchMatrix: the pair window must be >= 0\n"); return false; }
+    if (numImages == 0) return true;
+    std::vector<int64_t> ptr, kp_ptr(numImages + 1, 0);
+    std::vector<int32_t> width, height;
+    std::vector<unsigned char> pixels;
+    int channels = 1;
+    if (!flattenImages(images, "createFlowMatchMatrix", ptr, width, height, channels, pixels)) return false;
+    std::vector<float> kp;
+    for (size_t i = 0; i < numImages; ++i) {
+        kp_ptr[i + 1] = kp_ptr[i] + (int64_t)imageFeatures[i].points.size();
+        for (const cv::Point2f& p : imageFeatures[i].points) { kp.push_back(p.x); kp.push_back(p.y); }
+    }
+    // pair (i, j), i < j, tracks i's key points into j; a window k > 0 keeps j - i <= k
+    std::vector<int32_t> src, dst;
+    std::vector<int64_t> pt_ptr(1, 0);
+    std::vector<float> pts;
+    for (size_t i = 0; i < numImages; i++)
+        for (size_t j = i + 1; j < numImages && (pairWindow == 0 || j - i <= (size_t)pairWindow); j++) {
+            src.push_back((int32_t)i); dst.push_back((int32_t)j);
+            pts.insert(pts.end(), kp.begin() + 2 * kp_ptr[i], kp.begin() + 2 * kp_ptr[i + 1]);
+            pt_ptr.push_back(pt_ptr.back() + (kp_ptr[i + 1] - kp_ptr[i]));
+        }
+    const int n_pairs = (int)src.size();
+    const size_t n_pts = (size_t)pt_ptr.back();
+    std::vector<float> next(2 * n_pts + 2), err(n_pts + 1), dist(n_pts + 1);
+    std::vector<unsigned char> status(n_pts + 1);
+    std::vector<int64_t> pair_ptr((size_t)n_pairs + 1, 0);
+    std::vector<int32_t> query(n_pts + 1), train(n_pts + 1);
+    int64_t total = 0;
+    kp.resize(kp.size() + 2);
+    pts.resize(pts.size() + 2);
+    int rc = sfmba_flow_track(0, (int)numImages, ptr.data(), pixels.data(), width.data(), height.data(), channels, n_pairs, src.data(), dst.data(),
+                              pt_ptr.data(), pts.data(), FLOW_LEVELS, FLOW_RADIUS, FLOW_MAX_ITERS, FLOW_MIN_EIG, next.data(), status.data(), err.data(),
+                              nullptr, nullptr, nullptr);
+    if (rc == SFMBA_OK)                                   // at most one match per query: the capacity always suffices
+        rc = sfmba_flow_match(0, (int)numImages, kp_ptr.data(), kp.data(), n_pairs, dst.data(), pt_ptr.data(), next.data(), status.data(), err.data(),
+                              FLOW_MAX_ERR, FLOW_SNAP_RADIUS, FLOW_RATIO, pair_ptr.data(), query.data(), train.data(), dist.data(), (int64_t)n_pts, &total);
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "createFlowMatchMatrix failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return false;
+    }
+    for (int p = 0; p < n_pairs; ++p) {
+        Matching& m = featureMatchMatrix[(size_t)src[(size_t)p]][(size_t)dst[(size_t)p]];
+        m.reserve((size_t)(pair_ptr[(size_t)p + 1] - pair_ptr[(size_t)p]));
+        for (int64_t e = pair_ptr[(size_t)p]; e < pair_ptr[(size_t)p + 1]; ++e) {
+            cv::DMatch d(query[(size_t)e], train[(size_t)e], dist[(size_t)e]);
+            d.imgIdx = 0;
+            m.push_back(d);
+        }
+    }
     return true;
 }
 

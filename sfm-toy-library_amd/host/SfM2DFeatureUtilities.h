@@ -1,6 +1,6 @@
 // SfM2DFeatureUtilities.h -- the two entry points of the reference with their own signatures
 // (SfMToyLib/SfM2DFeatureUtilities.h:42-46), backed by the MI355X extractor and matchers (include/sfmba.h: sfmba_orb_extract,
-// sfmba_match_features, sfmba_match_features_l2), and the bodies of SfM::extractFeatures (SfMToyLib/SfM.cpp:141-154) and SfM::createFeatureMatchMatrix
+// sfmba_match_features, sfmba_match_features_l2, sfmba_flow_track, sfmba_flow_match), and the bodies of SfM::extractFeatures (SfMToyLib/SfM.cpp:141-154) and SfM::createFeatureMatchMatrix
 // (SfM.cpp:157-212) as free-standing functions over the members they read and write.
 // In the reference createFeatureMatchMatrix is a private member function; a maintainer replaces its body by one call
 // (INTEGRATION.md section 5):
@@ -45,6 +45,7 @@
 namespace sfmtoylib {
 
 enum FeatureType { FEATURES_ORB = 0, FEATURES_SURF = 1 };
+enum MatcherType { MATCHER_DESCRIPTORS = 0, MATCHER_FLOW = 1 };
 
 class SfM2DFeatureUtilities {
 public:
@@ -98,6 +99,23 @@ public:
     static bool createFeatureMatchMatrix(
             const std::vector<Features>& imageFeatures,
             MatchMatrix&                 featureMatchMatrix);
+
+    /**
+     * MATCHING BY OPTICAL FLOW, for video-like input (what the reference's legacy tree did in OFFeatureMatcher.cpp with
+     * gpu::PyrLKOpticalFlow::sparse): the same matrix without descriptors.  Entry [i][j], i < j, comes from tracking image i's key
+     * points (imageFeatures[i].points) into image j with the pyramidal Lucas-Kanade tracker of include/sfmba.h (sfmba_flow_track),
+     * snapping every end point to a key point of j within 2 px, a 0.7 ratio test among the key points in range and first come first
+     * served per key point of j (sfmba_flow_match; tracking error below 12) -- ONE track call and ONE match call for the whole pair
+     * list.  pairWindow k > 0 restricts the list to j - i <= k and leaves the other entries empty; 0 means all pairs.  A match's
+     * distance is the snap distance in pixels (<= 2).  The tracker runs at 4 levels, radius 7, at most 20 iterations, min_eig 1:
+     * first choices that nobody has tuned.  The images are all CV_8U or all CV_8UC3, one per feature set; the descriptors are not read.
+     * Returns false on a refusal or a device error (the matrix is then sized but empty; a line is written to stderr).
+     */
+    static bool createFlowMatchMatrix(
+            const std::vector<cv::Mat>&  images,
+            const std::vector<Features>& imageFeatures,
+            MatchMatrix&                 featureMatchMatrix,
+            int                          pairWindow = 0);
 
     /**
      * SfM::sortViewsForBaseline: every pair i < j keyed by its homography-inlier ratio (float)inliers / (float)matches, pairs with

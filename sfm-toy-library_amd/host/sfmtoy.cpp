@@ -1,5 +1,5 @@
 // sfmtoy.cpp -- the command-line program of the reference (main.cpp) over sfmtoylib::SfM of this directory: read the images of a
-// directory, run the pipeline on the MI355X, write <prefix>_points.ply and <prefix>_cameras.ply -- and, with -D, densify and write
+// directory, run the pipeline on the MI355X (-M flow: with the optical-flow matcher), write <prefix>_points.ply and <prefix>_cameras.ply -- and, with -D, densify and write
 // <prefix>_dense.ply.  The arguments are parsed here
 // (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
 #include <cstdlib>
@@ -23,6 +23,9 @@ void usage(std::ostream& os, const char* program) {
        << "  -f, --features orb|surf      the extractor: orb (binary rows, Hamming; the default) or surf (64 floats, L2)\n"
        << "  -m, --merge-distance F       distance below which a match confirms a merge (default 20: ORB's Hamming scale; unit-length\n"
        << "                               float rows never lie further than 2 apart, so 20 confirms every match of theirs)\n"
+       << "  -M, --matcher NAME           stage 2: descriptors (2-NN ratio test; the default) or flow (pyramidal Lucas-Kanade between\n"
+       << "                               the images and a snap to key points, for frame sequences; a match's distance is <= 2 px)\n"
+       << "  -w, --flow-window N          with -M flow: match view i with views i+1 .. i+N only (default 0: all pairs)\n"
        << "  -D, --dense                  also densify (plane-sweep depth maps of the registered views, fused) and write PREFIX_dense.ply\n"
        << "  -v, --visual-debug N         accepted and ignored: there is no visual debugging\n";
 }
@@ -48,8 +51,9 @@ bool number(const std::string& text, double& value) {
 
 int main(int argc, char** argv) {
     std::string directory, prefix = "output", text;
-    double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0;
+    double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0;
     FeatureType features = FEATURES_ORB;
+    MatcherType matcher = MATCHER_DESCRIPTORS;
     bool have_directory = false, dense = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
@@ -64,6 +68,12 @@ int main(int argc, char** argv) {
             bad = !missing && text != "orb" && text != "surf";
             features = text == "surf" ? FEATURES_SURF : FEATURES_ORB;
         }
+        else if (option(argc, argv, i, "-M", "--matcher", text, missing)) {
+            bad = !missing && text != "descriptors" && text != "flow";
+            matcher = text == "flow" ? MATCHER_FLOW : MATCHER_DESCRIPTORS;
+        }
+        else if (option(argc, argv, i, "-w", "--flow-window", text, missing))
+            bad = !missing && (!number(text, window) || !(window >= 0.0) || !(window <= 1.0e6) || window != (double)(int)window);
         else if (option(argc, argv, i, "-m", "--merge-distance", text, missing)) bad = !missing && (!number(text, merge) || !(merge >= 0.0) || !(merge <= 3.0e38));
         else if (option(argc, argv, i, "-v", "--visual-debug", text, missing)) bad = !missing && !number(text, ignored);
         else if (arg.size() > 1 && arg[0] == '-') { std::cerr << argv[0] << ": unknown option " << arg << "\n"; usage(std::cerr, argv[0]); return 2; }
@@ -76,6 +86,8 @@ int main(int argc, char** argv) {
     SfM sfm((float)downscale);
     sfm.setConsoleDebugLevel((unsigned int)level);
     sfm.setFeatureType(features);
+    sfm.setMatcherType(matcher);
+    sfm.setFlowPairWindow((int)window);
     sfm.setMergeFeatureMatchDistance((float)merge);
     if (!sfm.setImagesDirectory(directory)) return 1;
     if (sfm.runSfM() != OKAY) return 1;

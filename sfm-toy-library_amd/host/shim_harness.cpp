@@ -739,6 +739,68 @@ int sfmba_shim_densify_refusal(int what) {
     return code == 0 || !sfm.getDepthMaps().empty() || !sfm.getDenseCloud().points.empty() ? 100 + code : code;
 }
 
+// Flat-array driver of sfmtoylib::SfMFeatureMatching::createFlowMatchMatrix (tests/test_gpu_flow_pipeline.py): the images as
+// sfmba_shim_run_sfm takes them, view i's key points in rows kp_ptr[i] .. kp_ptr[i+1]-1 of kp_xy [..][2], the pair window.  Outputs as
+// sfmba_shim_feature_match_matrix.  Returns the number of matches, -1 if the call reported failure, -2 if the matrix is not
+// n_images x n_images.
+extern "C" __attribute__((visibility("default")))
+int64_t sfmba_shim_flow_match_matrix(int n_images, int channels, const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h,
+                                     const int64_t* kp_ptr, const float* kp_xy, int window, int64_t* sizes, int64_t cap, int32_t* query, int32_t* train,
+                                     int32_t* img_idx, float* dist) {
+    using namespace sfmtoylib;
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_images; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    std::vector<Features> feats((size_t)n_images);
+    addKeyPoints(feats, kp_ptr, kp_xy);
+    MatchMatrix mm;
+    if (!SfMFeatureMatching::createFlowMatchMatrix(images, feats, mm, window)) return -1;
+    if (mm.size() != (size_t)n_images) return -2;
+    int64_t n = 0;
+    for (int l = 0; l < n_images; ++l) {
+        if (mm[l].size() != (size_t)n_images) return -2;
+        for (int r = 0; r < n_images; ++r) {
+            sizes[(size_t)l * n_images + r] = (int64_t)mm[l][r].size();
+            n = flattenMatching(mm[l][r], n, cap, query, train, img_idx, dist);
+        }
+    }
+    return n;
+}
+
+// sfmba_shim_run_sfm_typed with the matcher of SfM::setMatcherType (0 = MATCHER_DESCRIPTORS, 1 = MATCHER_FLOW) and the window of
+// SfM::setFlowPairWindow (tests/test_gpu_flow_pipeline.py).  Outputs and return value as sfmba_shim_run_sfm.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_matcher(int feature_type, int matcher_type, int flow_window, float merge_distance, int n_views, int channels,
+                               const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h, int debug_level, float* poses, float* K,
+                               unsigned char* done, unsigned char* good, int* n_added, int32_t* added_view, unsigned char* added_posed,
+                               int64_t* added_cloud, int64_t cap_pts, int64_t cap_views, int64_t* n_pts, float* xyz, int64_t* view_ptr,
+                               int32_t* view_idx, int32_t* feat_idx, const char* ply_prefix) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    sfm.setFeatureType((FeatureType)feature_type);
+    sfm.setMatcherType((MatcherType)matcher_type);
+    sfm.setFlowPairWindow(flow_window);
+    sfm.setMergeFeatureMatchDistance(merge_distance);
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    sfm.setImages(images);
+    return flattenRun(sfm, sfm.runSfM(), n_views, poses, K, done, good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts, xyz,
+                      view_ptr, view_idx, feat_idx, ply_prefix);
+}
+
+// SfM::runSfM with MATCHER_FLOW where it has to refuse (tests/test_flow_oracle_cpu.py; no device involved): what = 0 after setFeatures
+// (there are no pixels to track in), 1 on images with a negative pair window.  Returns runSfM's code.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_flow_refusal(int what) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel(LOG_ERROR);
+    sfm.setMatcherType(MATCHER_FLOW);
+    if (what == 0) sfm.setFeatures(std::vector<Features>(2), 640, 480);
+    if (what == 1) { sfm.setImages(std::vector<cv::Mat>(2, cv::Mat(8, 8, CV_8U))); sfm.setFlowPairWindow(-1); }
+    return (int)sfm.runSfM();
+}
+
 // Flat-array driver of sfmtoylib::SfM::setImagesDirectory (tests/test_sfm_scene_cpu.py; no device involved): the images come back
 // one after the other in px (cap bytes), w / h [cap_images], *channels = 1 or 3.  Returns the number of images, -1 when the call
 // reported failure, -2 if a capacity is too small.
