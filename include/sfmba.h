@@ -981,7 +981,8 @@ SFMBA_API int sfmba_surf_extract(int device, int n_images, const int64_t* img_pt
  *                 own colour (a gray image gives g, g, g); src_image int32 [cap]; src_pixel int32 [cap] = v width + u;
  *                 pt_ptr [n_images + 1].  *total receives the number of points; SFMBA_ERR_CAPACITY (pt_ptr and *total valid,
  *                 nothing else written) if cap < *total.
- *   NO DE-DUPLICATION ACROSS VIEWS: a surface point seen by three views with maps appears three times.
+ *   NO DE-DUPLICATION ACROSS VIEWS: a surface point seen by three views with maps appears three times (sfmba_cloud_merge below
+ *                 makes one point per occupied voxel of such a cloud).
  *   SFMBA_ERR_INVALID_ARG (nothing written): what the sweep refuses about images, K and P; rel_tol negative or not finite;
  *                 min_consistent outside 0..4; a check list longer than 4, with an index out of range, a repeated index or the image
  *                 itself; a chk_ptr that does not start at 0; more than 65535 images, or 2^31 or more pixels with a map, in one call.
@@ -999,6 +1000,60 @@ SFMBA_API int sfmba_depth_fuse(int device, int n_images, const int64_t* img_ptr 
                 const int64_t* chk_ptr /*[n_images+1]*/, const int32_t* chk, float rel_tol, int min_consistent /*0..4*/,
                 int64_t* pt_ptr /*[n_images+1]*/, float* xyz /*[cap][3]*/, unsigned char* bgr /*[cap][3]*/, int32_t* src_image /*[cap]*/,
                 int32_t* src_pixel /*[cap]*/, int64_t cap, int64_t* total);
+
+/* ---- one oriented point per surface element: a normal per depth pixel and the voxel merge (SfM::mergeDenseCloud) ---------------
+ * sfmba_depth_fuse leaves a surface point once per view that saw it, and without a normal.  These two calls close the chain from
+ * images to a model: a normal per depth pixel, and one point per occupied voxel.  THE CONTRACT IS OUR OWN, stated so that the device
+ * is held BIT FOR BIT to a CPU restatement (tests/cloud_oracle.py): per element a handful of fp64 operations, EVERY ONE ROUNDED ON
+ * ITS OWN (csrc/cloud_math.h switches the compiler's contraction off), and NOTHING BUT INTEGERS IS SUMMED over a voxel, so the
+ * result does not depend on the order of accumulation.  Below, a sum written a + b + c is ((a + b) + c).
+ *
+ * sfmba_depth_normals
+ *   inputs        n_images, width, height, K (only fx, fy, cx, cy are read) and P [n_images][12] as sfmba_depth_fuse takes them;
+ *                 depth [n_images]: per image NULL (no map) or a float [h][w] map (0 = no depth); max_rel_step >= 0 (finite).
+ *   output        normal [n_images]: per image with a map a float [h][w][3]; a pixel without a normal gets (0, 0, 0).  The entry of
+ *                 an image without a map is not read and may be NULL.
+ *   per pixel     (u, v) with z0 = (double)depth > 0.  Camera point p(u, v) = (z xn, z yn, z), xn = ((double)u - cx) / fx,
+ *                 yn = ((double)v - cy) / fy (the back-projection of the fuse).  A neighbour is USABLE iff it lies inside the image,
+ *                 its depth zn > 0 and |zn - z0| <= (double)max_rel_step z0.  du = pE - pW if both (u+1, v) and (u-1, v) are
+ *                 usable, pE - p0 if only east is, p0 - pW if only west is, otherwise the pixel has no normal; dv likewise with
+ *                 south (v+1) and north (v-1).  c = dv x du, every component (a b) - (c d) with both products rounded.  If
+ *                 (c_0 p0_0 + c_1 p0_1) + c_2 p0_2 > 0, c is negated: the normal faces the camera.  len = sqrt((c_0^2 + c_1^2) +
+ *                 c_2^2); no normal unless len > 0 and finite.  n_cam = c / len, n_j = (R_0j n_0 + R_1j n_1) + R_2j n_2 with R of the
+ *                 image; (float)n_j is stored.
+ *   SFMBA_ERR_INVALID_ARG (nothing written): what the fuse refuses about sizes, K and P (a dimension outside 1..16384, a pose entry
+ *                 or fx, fy, cx, cy not finite, fx or fy <= 0, more than 65535 images, 2^31 or more pixels with a map);
+ *                 max_rel_step negative or not finite; an image with a map and a NULL output.
+ *
+ * sfmba_cloud_merge
+ *   inputs        n points, 0 <= n < 2^31: xyz float [n][3]; bgr uint8 [n][3] or NULL; normal float [n][3] or NULL; voxel > 0
+ *                 (a finite float); min_count >= 1.
+ *   quantise      per axis a: t = (double)x_a / (double)voxel, q_a = floor(t 1024.0 + 0.5).  A point is SKIPPED iff a coordinate is
+ *                 not finite or a q_a lies outside [-2^30, 2^30), tested in double (an infinite or NaN t fails).  Its voxel index
+ *                 is i_a = q_a >> 10 (arithmetic: the floor), in [-2^20, 2^20).
+ *   key           ((i_x + 2^20) << 42) | ((i_y + 2^20) << 21) | (i_z + 2^20).
+ *   normal quanta m_a = floor((double)n_a 16384.0 + 0.5) clamped to [-2^20, 2^20]; a NaN gives 0.
+ *   per voxel     over its non-skipped members, c their number: int64 sums Sq_a of q_a, Sb, Sg, Sr of the colours, Sm_a of m_a;
+ *                 first = the lowest input index among them.  All sums are integers.  BOUNDS: |q_a| <= 2^30 and c < 2^31 give
+ *                 |Sq_a| < 2^61; |m_a| <= 2^20 gives |Sm_a| < 2^51 (exact as a double); a colour sum is < 2^39 and 2 S + c < 2^41.
+ *   outputs       the voxels with c >= min_count in ASCENDING KEY order: xyz_out float [cap][3] = (float)((((double)Sq_a /
+ *                 (double)c) / 1024.0) (double)voxel); bgr_out = (2 S + c) / (2 c) in integers; normal_out = (float)((double)Sm_a /
+ *                 L) with L = sqrt(((double)Sm_0^2 + Sm_1^2) + Sm_2^2), (0, 0, 0) when L == 0; count int32 [cap]; first int32 [cap];
+ *                 voxel_of int32 [n] (may be NULL) = the output index of every input point, -1 for a skipped point and for a point
+ *                 whose voxel min_count dropped; *total = the number of output voxels; *n_skipped = the number of skipped points.
+ *                 SFMBA_ERR_CAPACITY if cap < *total: *total, *n_skipped and voxel_of are valid, nothing else is written.  bgr_out /
+ *                 normal_out are not written, and may be NULL, where bgr / normal is NULL.
+ *   SFMBA_ERR_INVALID_ARG (nothing written): voxel not finite or <= 0; min_count < 1; n < 0 or n >= 2^31 - 1; cap < 0; a NULL xyz
+ *                 with n > 0, total or n_skipped; with cap > 0 a NULL xyz_out, count, first, or the output of a given input.
+ *   Both: host pointers in and out, synchronous, deterministic.  SFMBA_ABI_VERSION stays 6: adding symbols is backward compatible.
+ */
+SFMBA_API int sfmba_depth_normals(int device, int n_images, const int32_t* width, const int32_t* height, const float* K /*[9]*/,
+                const float* P /*[n_images][12]*/, const float* const* depth /*[n_images], each NULL or [h][w]*/, float max_rel_step,
+                float* const* normal /*[n_images], each [h][w][3]; NULL allowed where depth is NULL*/);
+SFMBA_API int sfmba_cloud_merge(int device, int64_t n, const float* xyz /*[n][3]*/, const unsigned char* bgr /*[n][3] or NULL*/,
+                const float* normal /*[n][3] or NULL*/, float voxel, int min_count, float* xyz_out /*[cap][3]*/,
+                unsigned char* bgr_out /*[cap][3]*/, float* normal_out /*[cap][3]*/, int32_t* count /*[cap]*/, int32_t* first /*[cap]*/,
+                int32_t* voxel_of /*[n] or NULL*/, int64_t cap, int64_t* total, int64_t* n_skipped);
 
 /* ---- matching by optical flow: pyramidal Lucas-Kanade and the snap to key points (SfMFeatureMatching::createFlowMatchMatrix) -----
  * The reference's legacy tree matched video-like input without descriptors (legacy/SfMToyLib_Old/OFFeatureMatcher.cpp): it tracked

@@ -39,6 +39,7 @@ SYMBOLS = [
     "sfmba_jpeg_info", "sfmba_resized_size", "sfmba_jpeg_decode", "sfmba_resize_images",
     "sfmba_png_info", "sfmba_png_decode", "sfmba_match_features_l2", "sfmba_surf_extract",
     "sfmba_depth_sweep", "sfmba_depth_fuse", "sfmba_flow_track", "sfmba_flow_match",
+    "sfmba_depth_normals", "sfmba_cloud_merge",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -555,6 +556,62 @@ def flow_match(keypoints, pairs, tracked, max_err=12.0, radius=2.0, ratio=0.7, c
     _check(rc)
     m = int(total.value)
     return ptr, q[:m].copy(), t[:m].copy(), d[:m].copy()
+
+
+def depth_normals(K, P, depth_maps, max_rel_step=0.05, device=0):
+    """sfmba_depth_normals: a normal per depth pixel (the contract is in include/sfmba.h).
+
+    K [3, 3]; P [n_images, 3, 4]; depth_maps: per image None or float32 [h, w] (a None entry counts as a 1 x 1 image without a map).
+    Returns per image None or float32 [h, w, 3]; (0, 0, 0) where a pixel has no normal."""
+    maps = [None if m is None else np.ascontiguousarray(m, dtype=np.float32) for m in depth_maps]
+    n = len(maps)
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1)
+    if len(P) != 12 * n or any(m is not None and m.ndim != 2 for m in maps):
+        raise ValueError("P must hold one 3 x 4 matrix per image, and a depth map is h x w")
+    wd = np.asarray([1 if m is None else m.shape[1] for m in maps] or [1], dtype=np.int32)
+    ht = np.asarray([1 if m is None else m.shape[0] for m in maps] or [1], dtype=np.int32)
+    out = [None if m is None else np.zeros(m.shape + (3,), np.float32) for m in maps]
+    fp = C.POINTER(C.c_float)
+    dptr = (fp * max(n, 1))(*[None if m is None else m.ctypes.data_as(fp) for m in maps])
+    optr = (fp * max(n, 1))(*[None if o is None else o.ctypes.data_as(fp) for o in out])
+    _check(lib().sfmba_depth_normals(C.c_int(device), C.c_int(n), _p(wd, _ip), _p(ht, _ip), K.ctypes.data_as(fp), P.ctypes.data_as(fp), dptr,
+                                     C.c_float(max_rel_step), optr))
+    return out
+
+
+def cloud_merge(xyz, bgr=None, normal=None, voxel=1.0, min_count=1, cap=None, want_voxel_of=True, device=0):
+    """sfmba_cloud_merge: one point per occupied voxel of a cloud (the contract is in include/sfmba.h).
+
+    xyz float32 [n, 3]; bgr uint8 [n, 3] or None; normal float32 [n, 3] or None.  Returns a dict: xyz float32 [m, 3], bgr uint8 [m, 3] or
+    None, normal float32 [m, 3] or None, count int32 [m], first int32 [m], voxel_of int32 [n] or None, n_skipped.  cap=None asks for the
+    size first (cap 0); a short cap is retried once with the size the library reports."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    n = len(xyz)
+    bgr = None if bgr is None else np.ascontiguousarray(bgr, dtype=np.uint8).reshape(-1, 3)
+    normal = None if normal is None else np.ascontiguousarray(normal, dtype=np.float32).reshape(-1, 3)
+    if (bgr is not None and len(bgr) != n) or (normal is not None and len(normal) != n):
+        raise ValueError("bgr and normal must hold one row per point")
+    fp, bp, lp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte), C.POINTER(C.c_int64)
+    voxel_of = np.zeros(max(n, 1), np.int32) if want_voxel_of else None
+    total, skipped = C.c_int64(0), C.c_int64(0)
+    cap = 0 if cap is None else int(cap)
+    for _ in range(2):
+        oxyz, obgr, onrm = np.zeros((max(cap, 1), 3), np.float32), np.zeros((max(cap, 1), 3), np.uint8), np.zeros((max(cap, 1), 3), np.float32)
+        cnt, first = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        rc = lib().sfmba_cloud_merge(C.c_int(device), C.c_int64(n), xyz.ctypes.data_as(fp), None if bgr is None else bgr.ctypes.data_as(bp),
+                                     None if normal is None else normal.ctypes.data_as(fp), C.c_float(voxel), C.c_int(min_count),
+                                     oxyz.ctypes.data_as(fp), None if bgr is None else obgr.ctypes.data_as(bp),
+                                     None if normal is None else onrm.ctypes.data_as(fp), _p(cnt, _ip), _p(first, _ip),
+                                     _p(voxel_of, _ip) if want_voxel_of else None, C.c_int64(cap), C.byref(total), C.byref(skipped))
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        cap = int(total.value)
+    _check(rc)
+    m = int(total.value)
+    return {"xyz": oxyz[:m].copy(), "bgr": None if bgr is None else obgr[:m].copy(), "normal": None if normal is None else onrm[:m].copy(),
+            "count": cnt[:m].copy(), "first": first[:m].copy(), "voxel_of": voxel_of[:n].copy() if want_voxel_of else None,
+            "n_skipped": int(skipped.value)}
 
 
 class _ImageInfo(C.Structure):

@@ -278,6 +278,11 @@ int build_pair_lists(hipStream_t s, DeviceArena* arena, DeviceArena* scratch, in
 int build_camera_major(hipStream_t s, DeviceArena* arena, DeviceArena* scratch, int nobs, int ncam, const int* d_obs_cam, const int* d_obs_pt,
                        int** d_cam_obs, int** d_cam_obs_pt, int** d_cam_ptr);
 int build_camera_major_xy(hipStream_t s, DeviceArena* arena, int nobs, int xy_bytes, const int* d_cam_obs, const void* d_obs_xy, void** d_cam_obs_xy);
+// Stable radix sort of n (64-bit key, int) pairs over the key bits [0, end_bit) with the configuration the structure build sorts with
+// (Onesweep above 2^15 items), for units that sort pairs of their own (cloud_merge.hip).  tmp == nullptr: only *tmp_bytes is set.
+// Enqueue only.  Returns 0, or a hipError_t value.
+int sort_pairs_u64(hipStream_t s, void* tmp, size_t* tmp_bytes, const unsigned long long* k_in, unsigned long long* k_out, const int* v_in, int* v_out,
+                   unsigned n, int end_bit);
 // unsorted observation arrays of a build: the old ones (device) followed by the new ones (one uploaded buffer)
 struct StageObs {
     int n_old = 0, n_new = 0;

@@ -12,6 +12,7 @@
 #include "orb_extract.h"
 #include "surf_extract.h"
 #include "depth_sweep.h"
+#include "cloud_merge.h"
 #include "flow_track.h"
 #include "flow_math.h"
 #include "jpeg_decode.h"
@@ -665,18 +666,13 @@ int sfmba_surf_extract(int device, int n_images, const int64_t* img_ptr, const u
 }
 // ---- dense depth maps and a dense cloud: plane-sweep stereo and the consistency filter (SfM::densify) ---------------------------
 namespace {
-// what both dense calls refuse about the images, K and P; 0 or the failure
-int depth_check_images(const char* who, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
-                       int channels, const float* K, const float* P) {
+// what every dense call refuses about the sizes, K and P; 0 or the failure
+int depth_check_cameras(const char* who, int n_images, const int32_t* width, const int32_t* height, const float* K, const float* P) {
     const std::string w(who);
-    if (n_images < 0 || !img_ptr || !K || (n_images > 0 && (!width || !height || !P || !pixels))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, w + ": channels must be 1 or 3");
-    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    if (n_images < 0 || !K || (n_images > 0 && (!width || !height || !P))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
     for (int i = 0; i < n_images; ++i) {
         if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
             return fail(SFMBA_ERR_INVALID_ARG, w + ": an image dimension lies outside 1..16384");
-        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
-            return fail(SFMBA_ERR_INVALID_ARG, w + ": img_ptr does not agree with width * height * channels");
         for (int q = 0; q < 12; ++q)
             if (!std::isfinite(P[(size_t)i * 12 + q])) return fail(SFMBA_ERR_INVALID_ARG, w + ": non-finite pose of image " + std::to_string(i));
     }
@@ -684,6 +680,18 @@ int depth_check_images(const char* who, int n_images, const int64_t* img_ptr, co
         if (!std::isfinite(K[q])) return fail(SFMBA_ERR_INVALID_ARG, w + ": fx, fy, cx and cy must be finite");
     if (!(K[0] > 0.0f) || !(K[4] > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, w + ": fx and fy must be > 0");
     return 0;
+}
+// what the sweep and the fuse refuse about the images, K and P; 0 or the failure
+int depth_check_images(const char* who, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                       int channels, const float* K, const float* P) {
+    const std::string w(who);
+    if (n_images < 0 || !img_ptr || !K || (n_images > 0 && (!width || !height || !P || !pixels))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, w + ": channels must be 1 or 3");
+    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i)
+        if (width[i] >= 1 && height[i] >= 1 && img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
+            return fail(SFMBA_ERR_INVALID_ARG, w + ": img_ptr does not agree with width * height * channels");
+    return depth_check_cameras(who, n_images, width, height, K, P);
 }
 // a CSR list of 0 / 1 .. 4 other images per row; 0 or the failure
 int depth_check_lists(const char* who, const char* what, int n_images, int n_rows, const int32_t* row_image, const int64_t* ptr, const int32_t* idx,
@@ -868,6 +876,67 @@ int sfmba_flow_match(int device, int n_images, const int64_t* kp_ptr, const floa
     if (rc == FLOW_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "flow_match: output capacity too small");
     if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "flow_match: device allocation failed");
     if (rc) return fail(SFMBA_ERR_HIP, std::string("flow_match: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+// ---- one oriented point per surface element: a normal per depth pixel and the voxel merge (SfM::mergeDenseCloud) ------------------
+int sfmba_depth_normals(int device, int n_images, const int32_t* width, const int32_t* height, const float* K, const float* P,
+                        const float* const* depth, float max_rel_step, float* const* normal) {
+    if ((n_images > 0 && (!depth || !normal))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (int rc = depth_check_cameras("depth_normals", n_images, width, height, K, P)) return rc;
+    if (n_images > 65535) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: more than 65535 images in one call");
+    if (!std::isfinite(max_rel_step) || max_rel_step < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: max_rel_step must be finite and >= 0");
+    int64_t px = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (!depth[i]) continue;
+        if (!normal[i]) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: an image with a depth map needs an output map");
+        px += (int64_t)width[i] * height[i];
+    }
+    if (px >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: too many pixels with a depth map in one call (2^31)");
+    if (px == 0) return check_device(device);
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    // SFMBA_CLOUD_TIMING: one stderr line per call with the HIP-event times of its phases (tools/cloud_bench.py)
+    double tm[NORMALS_T_COUNT];
+    const bool timing = std::getenv("SFMBA_CLOUD_TIMING") != nullptr;
+    rc = depth_normals(ck.kit.stream, device, n_images, width, height, K, P, depth, max_rel_step, normal, timing ? tm : nullptr);
+    if (rc == 0 && timing)
+        std::fprintf(stderr, "[sfmba depth_normals] upload_ms %.6f kernel_ms %.6f download_ms %.6f\n", tm[NORMALS_T_UPLOAD], tm[NORMALS_T_KERNEL],
+                     tm[NORMALS_T_DOWNLOAD]);
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "depth_normals: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("depth_normals: ") + hipGetErrorString((hipError_t)rc));
+    return SFMBA_OK;
+}
+int sfmba_cloud_merge(int device, int64_t n, const float* xyz, const unsigned char* bgr, const float* normal, float voxel, int min_count,
+                      float* xyz_out, unsigned char* bgr_out, float* normal_out, int32_t* count, int32_t* first, int32_t* voxel_of, int64_t cap,
+                      int64_t* total, int64_t* n_skipped) {
+    if (n < 0 || cap < 0 || !total || !n_skipped || (n > 0 && !xyz) ||
+        (cap > 0 && (!xyz_out || !count || !first || (bgr && !bgr_out) || (normal && !normal_out))))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (n >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "cloud_merge: too many points in one call (2^31)");
+    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "cloud_merge: voxel must be finite and > 0");
+    if (min_count < 1) return fail(SFMBA_ERR_INVALID_ARG, "cloud_merge: min_count must be >= 1");
+    if (n == 0) {
+        *total = 0;
+        *n_skipped = 0;
+        return check_device(device);
+    }
+    CallKit ck;
+    int rc = ck.open(device);
+    if (rc) return rc;
+    double tm[MERGE_T_COUNT];
+    const bool timing = std::getenv("SFMBA_CLOUD_TIMING") != nullptr;
+    rc = cloud_merge(ck.kit.stream, device, (int)n, xyz, bgr, normal, voxel, min_count, xyz_out, bgr_out, normal_out, count, first, voxel_of, cap, total,
+                     n_skipped, timing ? tm : nullptr);
+    if ((rc == 0 || rc == CLOUD_ERR_CAPACITY) && timing)
+        std::fprintf(stderr,
+                     "[sfmba cloud_merge] upload_ms %.6f quantise_ms %.6f sort_ms %.6f runs_ms %.6f reduce_ms %.6f compact_ms %.6f finalise_ms %.6f "
+                     "download_ms %.6f points %lld voxels %lld\n",
+                     tm[MERGE_T_UPLOAD], tm[MERGE_T_QUANTISE], tm[MERGE_T_SORT], tm[MERGE_T_RUNS], tm[MERGE_T_REDUCE], tm[MERGE_T_COMPACT],
+                     tm[MERGE_T_FINALISE], tm[MERGE_T_DOWNLOAD], (long long)n, (long long)*total);
+    if (rc == CLOUD_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "cloud_merge: output capacity too small");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "cloud_merge: device allocation failed");
+    if (rc) return fail(SFMBA_ERR_HIP, std::string("cloud_merge: ") + hipGetErrorString((hipError_t)rc));
     return SFMBA_OK;
 }
 // ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------

@@ -139,6 +139,11 @@ __global__ __launch_bounds__(256) void k_pm_paircount(int npt, const int* __rest
 typedef rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, (size_t)1 << 15> OnesweepAbove32k;
 static int bits_for(unsigned long long n) { int b = 1; while (b < 63 && ((unsigned long long)1 << b) < n) ++b; return b; }
 
+int sort_pairs_u64(hipStream_t s, void* tmp, size_t* tmp_bytes, const unsigned long long* k_in, unsigned long long* k_out, const int* v_in, int* v_out,
+                   unsigned n, int end_bit) {
+    return (int)rocprim::radix_sort_pairs<OnesweepAbove32k>(tmp, *tmp_bytes, k_in, k_out, v_in, v_out, n, 0u, (unsigned)end_bit, s);
+}
+
 int build_point_major(hipStream_t s, DeviceArena* arena, DeviceArena* scratch_arena, int n, int npt, int ncam, int xy_bytes, const int* u_pt, const int* u_cam,
                       const int* u_perm, const void* u_xy, PointMajor* out) {
     out->obs_pt = arena->alloc_n<int>((size_t)2 * n);

@@ -209,6 +209,7 @@ void SfM::startRun(size_t n_views) {
     mFeatureMatchMatrix.clear();
     mDepthMaps.clear();
     mDenseCloud = DenseCloud();
+    mMergedCloud = MergedCloud();
     mDenseJobs.clear();
     mRunOkay = false;
     mTiming = std::getenv("SFMBA_SFM_TIMING") != nullptr;
@@ -423,6 +424,7 @@ void SfM::addMoreViewsToReconstruction() {
 ErrorCode SfM::densify(const DenseParams& params) {
     mDepthMaps.clear();
     mDenseCloud = DenseCloud();
+    mMergedCloud = MergedCloud();
     mDenseJobs.clear();
     if (mFeaturesGiven || mImages.empty()) {
         std::cerr << "densify: there are no pixels: the run started from setFeatures, and depth maps need the images" << std::endl;
@@ -526,6 +528,82 @@ bool SfM::saveDenseCloudToPLY(const std::string& prefix) {
         const cv::Point3f& p = mDenseCloud.points[i];
         const unsigned char* bgr = &mDenseCloud.bgr[3 * i];
         file << p.x << " " << p.y << " " << p.z << " " << (int)bgr[2] << " " << (int)bgr[1] << " " << (int)bgr[0] << " " << std::endl;
+    }
+    file.close();
+    return !file.fail();
+}
+
+ErrorCode SfM::mergeDenseCloud(float voxel, int minCount, float maxRelStep) {
+    mMergedCloud = MergedCloud();
+    if (mDenseJobs.empty() || mDepthMaps.size() != mImages.size()) {
+        std::cerr << "mergeDenseCloud: needs a densify on these images that returned OKAY" << std::endl;
+        return ERROR;
+    }
+    if (!std::isfinite(voxel) || voxel < 0.0f || minCount < 1) {
+        std::cerr << "mergeDenseCloud: voxel must be finite and >= 0 (0 = auto), minCount >= 1" << std::endl;
+        return ERROR;
+    }
+    if (voxel == 0.0f) {
+        // the footprint of a pixel at the typical depth: the median over the jobs of the geometric mean of a job's depth range
+        std::vector<double> g;
+        for (const DenseJob& job : mDenseJobs) g.push_back(std::sqrt((double)job.zNear * (double)job.zFar));
+        std::sort(g.begin(), g.end());
+        voxel = (float)(g[g.size() / 2] / (double)mIntrinsics.K.at<float>(0, 0));
+    }
+    const bool timing = std::getenv("SFMBA_SFM_TIMING") != nullptr;
+    double ms[2] = { 0.0, 0.0 };
+    std::vector<cv::Mat> normalMaps;
+    {
+        StageClock clock(timing ? ms : nullptr, 0);
+        if (!SfMDenseUtilities::computeNormals(mImages, mIntrinsics, mCameraPoses, mDepthMaps, maxRelStep, normalMaps)) return ERROR;
+    }
+    Points3f normals;
+    normals.reserve(mDenseCloud.points.size());
+    for (size_t i = 0; i < mDenseCloud.points.size(); i++) {
+        const float* n = normalMaps[(size_t)mDenseCloud.views[i]].ptr<float>(0) + 3 * (size_t)mDenseCloud.pixels[i];
+        normals.push_back(cv::Point3f(n[0], n[1], n[2]));
+    }
+    bool ok = true;
+    MergedCloud merged;
+    {
+        StageClock clock(timing ? ms : nullptr, 1);
+        merged = SfMDenseUtilities::mergeCloud(mDenseCloud, normals, voxel, minCount, &ok);
+    }
+    if (!ok) return ERROR;
+    mMergedCloud = merged;
+    say(LOG_INFO, "dense: " + std::to_string(mDenseCloud.points.size()) + " points merged into " + std::to_string(mMergedCloud.points.size()) +
+                      " at voxel " + std::to_string(voxel));
+    if (timing)
+        std::fprintf(stderr, "[sfmba sfm merge] voxel %.9g merge_normals_ms %.3f merge_cloud_ms %.3f points %lld merged %lld\n", (double)voxel, ms[0],
+                     ms[1], (long long)mDenseCloud.points.size(), (long long)mMergedCloud.points.size());
+    return OKAY;
+}
+
+bool SfM::saveMergedDenseCloudToPLY(const std::string& prefix) {
+    std::ofstream file(prefix + "_dense_merged.ply");
+    const bool haveNormals = mMergedCloud.normals.size() == mMergedCloud.points.size();
+    const bool haveBgr = mMergedCloud.bgr.size() == 3 * mMergedCloud.points.size();
+    // the header of the points file (SfMExport.cpp), padding included, with the normal between position and colour
+    file << "ply                 " << std::endl
+         << "format ascii 1.0    " << std::endl
+         << "element vertex " << mMergedCloud.points.size() << std::endl
+         << "property float x    " << std::endl
+         << "property float y    " << std::endl
+         << "property float z    " << std::endl
+         << "property float nx   " << std::endl
+         << "property float ny   " << std::endl
+         << "property float nz   " << std::endl
+         << "property uchar red  " << std::endl
+         << "property uchar green" << std::endl
+         << "property uchar blue " << std::endl
+         << "end_header          " << std::endl;
+    for (size_t i = 0; i < mMergedCloud.points.size(); i++) {
+        const cv::Point3f& p = mMergedCloud.points[i];
+        const cv::Point3f n = haveNormals ? mMergedCloud.normals[i] : cv::Point3f(0.0f, 0.0f, 0.0f);
+        const unsigned char none[3] = { 0, 0, 0 };
+        const unsigned char* bgr = haveBgr ? &mMergedCloud.bgr[3 * i] : none;
+        file << p.x << " " << p.y << " " << p.z << " " << n.x << " " << n.y << " " << n.z << " " << (int)bgr[2] << " " << (int)bgr[1] << " "
+             << (int)bgr[0] << " " << std::endl;
     }
     file.close();
     return !file.fail();

@@ -55,6 +55,12 @@
 //                 views of the fuse are the job's sources.  The defaults of DenseParams (64 planes, radius 3, min_std 2,
 //                 min_score 0.6, min_sources 1, rel_tol 0.01, min_consistent 1) are first choices like the merge distance above:
 //                 nobody has tuned them.  Nothing is de-duplicated: a surface point seen by three views appears three times.
+//   merged        mergeDenseCloud(voxel, minCount, maxRelStep) after a densify that returned OKAY: ONE sfmba_depth_normals call over
+//                 the depth maps, every dense point takes the normal of its own pixel (through views / pixels of the dense cloud),
+//                 then ONE sfmba_cloud_merge (include/sfmba.h): one oriented point per occupied voxel.  voxel == 0 means AUTO, the
+//                 footprint of a pixel at the typical depth: g_j = sqrt((double)zNear_j * (double)zFar_j) over the jobs of the
+//                 densify, sorted ascending, voxel = (float)(g[n / 2] / (double)fx) (integer division).  The dense cloud itself is
+//                 not changed.
 // There is no visual debugging.
 // An object holds all of a run's state (the stage times of SFMBA_SFM_TIMING included): different objects may run in different
 // threads; one object is not re-entrant.
@@ -156,6 +162,20 @@ public:
      */
     bool saveDenseCloudToPLY(const std::string& prefix);
 
+    /**
+     * One oriented point per occupied voxel of the dense cloud (the contract is at the top of this file).  Valid after a densify
+     * that returned OKAY.  voxel: the edge length, 0 = auto; minCount: a voxel needs this many dense points.  maxRelStep (a
+     * neighbouring pixel takes part in a normal if its depth differs by at most this share) defaults to 0.05: a first choice that
+     * nobody has tuned.  With SFMBA_SFM_TIMING set, one stderr line reports merge_normals_ms and merge_cloud_ms.
+     * @return ERROR (nothing kept) without such a densify, for voxel < 0 or not finite, minCount < 1, or when a device call fails.
+     */
+    ErrorCode mergeDenseCloud(float voxel = 0.0f, int minCount = 1, float maxRelStep = 0.05f);
+
+    /**
+     * <prefix>_dense_merged.ply: the merged cloud, ASCII, in the style of the other writers: x y z, nx ny nz, red green blue.
+     */
+    bool saveMergedDenseCloudToPLY(const std::string& prefix);
+
     void setConsoleDebugLevel(unsigned int consoleDebugLevel) { mConsoleDebugLevel = consoleDebugLevel < (unsigned int)LOG_ERROR ? consoleDebugLevel : (unsigned int)LOG_ERROR; }
 
     const std::vector<cv::Mat>&     getImages() const { return mImages; }
@@ -169,6 +189,7 @@ public:
     const std::vector<cv::Mat>&     getDepthMaps() const { return mDepthMaps; }       // per view; an empty Mat where densify made no job
     const DenseCloud&               getDenseCloud() const { return mDenseCloud; }
     const std::vector<DenseJob>&    getDenseJobs() const { return mDenseJobs; }       // the jobs of the last densify, ascending view
+    const MergedCloud&              getMergedDenseCloud() const { return mMergedCloud; }
 
 private:
     enum { T_EXTRACT, T_MATCH, T_RANK, T_BASELINE_POSE, T_BASELINE_TRIANGULATE, T_ASSOCIATE, T_PNP, T_PAIR_POSES, T_TRIANGULATE, T_MERGE,
@@ -203,6 +224,7 @@ private:
     std::vector<cv::Mat>      mDepthMaps;
     DenseCloud                mDenseCloud;
     std::vector<DenseJob>     mDenseJobs;
+    MergedCloud               mMergedCloud;
     bool                      mRunOkay;          // the last runSfM returned OKAY and nothing was set since
     bool                      mTiming;           // SFMBA_SFM_TIMING was set when the run began
     double                    mStageMs[T_COUNT]; // wall time per stage of the current run (all zero unless mTiming)

@@ -146,4 +146,89 @@ DenseCloud SfMDenseUtilities::fuseDepthMaps(const std::vector<cv::Mat>& images, 
     return cloud;
 }
 
+bool SfMDenseUtilities::computeNormals(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
+                                       const std::vector<cv::Mat>& depthMaps, float maxRelStep, std::vector<cv::Mat>& normals) {
+    normals.clear();
+    if (images.empty() || poses.size() != images.size() || depthMaps.size() != images.size()) {
+        std::fprintf(stderr, "computeNormals: one pose and one depth map (or an empty Mat) per image are needed\n");
+        return false;
+    }
+    std::vector<int32_t> w, h;
+    std::vector<float> P;
+    float K[9];
+    for (size_t i = 0; i < images.size(); ++i) {
+        w.push_back(images[i].cols);
+        h.push_back(images[i].rows);
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) P.push_back(poses[i](r, c));
+    }
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) K[3 * r + c] = intrinsics.K.at<float>(r, c);
+    std::vector<cv::Mat> out(images.size());
+    std::vector<const float*> maps(images.size(), nullptr);
+    std::vector<float*> outs(images.size(), nullptr);
+    for (size_t i = 0; i < images.size(); ++i) {
+        const cv::Mat& m = depthMaps[i];
+        if (m.empty()) continue;
+        if (m.type() != CV_32F || m.rows != images[i].rows || m.cols != images[i].cols) {
+            std::fprintf(stderr, "computeNormals: a depth map is not CV_32F of its image's size\n");
+            return false;
+        }
+        out[i] = cv::Mat(m.rows, m.cols, CV_32FC3);
+        maps[i] = m.ptr<float>(0);
+        outs[i] = out[i].ptr<float>(0);
+    }
+    const int rc = sfmba_depth_normals(0, (int)images.size(), w.data(), h.data(), K, P.data(), maps.data(), maxRelStep, outs.data());
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "computeNormals failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return false;
+    }
+    normals.swap(out);
+    return true;
+}
+
+MergedCloud SfMDenseUtilities::mergeCloud(const DenseCloud& cloud, const Points3f& normals, float voxel, int minCount, bool* ok) {
+    MergedCloud merged;
+    if (ok) *ok = false;
+    const size_t n = cloud.points.size();
+    const bool haveBgr = !cloud.bgr.empty() || n == 0, haveNormals = !normals.empty();
+    if ((haveBgr && cloud.bgr.size() != 3 * n) || (haveNormals && normals.size() != n)) {
+        std::fprintf(stderr, "mergeCloud: three colour bytes per point (or none at all) and one normal per point (or none at all) are needed\n");
+        return merged;
+    }
+    std::vector<float> xyz(3 * n + 1), nrm(haveNormals ? 3 * n + 1 : 0);
+    for (size_t i = 0; i < n; ++i) {
+        xyz[3 * i] = cloud.points[i].x; xyz[3 * i + 1] = cloud.points[i].y; xyz[3 * i + 2] = cloud.points[i].z;
+        if (haveNormals) { nrm[3 * i] = normals[i].x; nrm[3 * i + 1] = normals[i].y; nrm[3 * i + 2] = normals[i].z; }
+    }
+    std::vector<unsigned char> bgrIn(cloud.bgr);
+    bgrIn.push_back(0);                                    // never read: keeps data() non-null
+    std::vector<float> oxyz, onrm;
+    std::vector<unsigned char> obgr;
+    std::vector<int32_t> count, first;
+    int64_t total = 0, skipped = 0, cap = 0;               // the first call reports the size
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        oxyz.resize((size_t)cap * 3 + 1); onrm.resize((size_t)cap * 3 + 1); obgr.resize((size_t)cap * 3 + 1);
+        count.resize((size_t)cap + 1); first.resize((size_t)cap + 1);
+        const int rc = sfmba_cloud_merge(0, (int64_t)n, xyz.data(), haveBgr ? bgrIn.data() : nullptr, haveNormals ? nrm.data() : nullptr, voxel,
+                                         minCount, oxyz.data(), obgr.data(), onrm.data(), count.data(), first.data(), nullptr, cap, &total,
+                                         &skipped);
+        if (rc == SFMBA_OK) break;
+        if (rc == SFMBA_ERR_CAPACITY && attempt == 0) { cap = total; continue; }
+        std::fprintf(stderr, "mergeCloud failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return merged;
+    }
+    merged.voxel = voxel;
+    merged.skipped = (long long)skipped;
+    merged.points.reserve((size_t)total);
+    for (int64_t i = 0; i < total; ++i) merged.points.push_back(cv::Point3f(oxyz[3 * i], oxyz[3 * i + 1], oxyz[3 * i + 2]));
+    if (haveBgr) merged.bgr.assign(obgr.begin(), obgr.begin() + 3 * total);
+    if (haveNormals)
+        for (int64_t i = 0; i < total; ++i) merged.normals.push_back(cv::Point3f(onrm[3 * i], onrm[3 * i + 1], onrm[3 * i + 2]));
+    merged.counts.assign(count.begin(), count.begin() + total);
+    merged.first.assign(first.begin(), first.begin() + total);
+    if (ok) *ok = true;
+    return merged;
+}
+
 }  // namespace sfmtoylib

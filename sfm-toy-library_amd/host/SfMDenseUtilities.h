@@ -1,7 +1,9 @@
 // SfMDenseUtilities.h -- dense depth maps and a dense cloud over the C ABI's sfmba_depth_sweep / sfmba_depth_fuse (include/sfmba.h
 // holds the contract): plane-sweep stereo for a list of jobs in ONE device call, and the consistency filter that turns the depth maps
 // of a set of views into coloured points in ONE device call.  The reference stops at the sparse cloud; this is the stage between
-// "camera poses" and "a model" (SfM::densify drives it).  Both functions are thin: they flatten, call and rebuild.
+// "camera poses" and "a model" (SfM::densify drives it).  Both functions are thin: they flatten, call and rebuild.  So are the two
+// that follow them, over sfmba_depth_normals / sfmba_cloud_merge: a normal per depth pixel, and one oriented point per occupied voxel
+// of the fused cloud (SfM::mergeDenseCloud drives them).
 #pragma once
 #include <vector>
 
@@ -29,12 +31,25 @@ struct DenseParams {
     DenseParams() : planes(64), radius(3), minStd(2), minScore(0.6f), minSources(1), relTol(0.01f), minConsistent(1), maxSources(2) {}
 };
 
-// The fused points in (view, row, column) order.  A surface point seen by three views appears three times: nothing is de-duplicated.
+// The fused points in (view, row, column) order.  A surface point seen by three views appears three times: nothing is de-duplicated
+// (mergeCloud below, over sfmba_cloud_merge, makes one point per occupied voxel of such a cloud).
 struct DenseCloud {
     Points3f                   points;
     std::vector<unsigned char> bgr;      // 3 per point: the pixel's own colour (a gray image gives g, g, g)
     std::vector<int>           views;    // the view a point comes from
     std::vector<int>           pixels;   // ... and its pixel there, row * cols + column
+};
+
+// One point per occupied voxel, in ascending voxel key order (include/sfmba.h, sfmba_cloud_merge).
+struct MergedCloud {
+    Points3f                   points;   // the mean of the voxel's members, on a grid of 1/1024 voxel
+    std::vector<unsigned char> bgr;      // 3 per point: the rounded mean colour; empty if the input had none
+    Points3f                   normals;  // unit length, or (0, 0, 0) where the members' normals cancel or none had one; empty if none given
+    std::vector<int>           counts;   // members per point
+    std::vector<int>           first;    // the lowest input index among the members
+    float                      voxel;    // the edge length merged with
+    long long                  skipped;  // input points outside the grid or not finite
+    MergedCloud() : voxel(0.0f), skipped(0) {}
 };
 
 class SfMDenseUtilities {
@@ -55,6 +70,22 @@ public:
     static DenseCloud fuseDepthMaps(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
                                     const std::vector<cv::Mat>& depthMaps, const std::vector<std::vector<int> >& checks,
                                     const DenseParams& params, bool* ok = nullptr);
+
+    /**
+     * One normal map (CV_32FC3, world coordinates, (0, 0, 0) where a pixel has none) per view with a depth map, an empty Mat for the
+     * others: ONE sfmba_depth_normals call.  images give the sizes only (their pixels are not read); depthMaps as fuseDepthMaps takes
+     * them.  maxRelStep: a neighbour takes part in a pixel's differences if its depth differs by at most this share.
+     * @return false (normals empty) when the device call fails or refuses an argument; the reason goes to stderr.
+     */
+    static bool computeNormals(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
+                               const std::vector<cv::Mat>& depthMaps, float maxRelStep, std::vector<cv::Mat>& normals);
+
+    /**
+     * One point per voxel of edge `voxel` that holds at least minCount points of the cloud: ONE sfmba_cloud_merge call (two when the
+     * first reports the size).  normals: one per point of the cloud, or empty.
+     * @param ok  if not null, receives false when the device call fails or refuses an argument (the result is then empty).
+     */
+    static MergedCloud mergeCloud(const DenseCloud& cloud, const Points3f& normals, float voxel, int minCount, bool* ok = nullptr);
 };
 
 }  // namespace sfmtoylib

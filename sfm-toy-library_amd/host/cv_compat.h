@@ -13,7 +13,7 @@
 #include <cstring>
 #include <vector>
 
-enum { CV_8U = 0, CV_32F = 5, CV_8UC3 = 16 };     // OpenCV's type codes (CV_8UC3: three interleaved bytes, BGR); global, as OpenCV's macros are
+enum { CV_8U = 0, CV_32F = 5, CV_8UC3 = 16, CV_32FC3 = 21 };     // OpenCV's type codes (CV_8UC3: three interleaved bytes, BGR; CV_32FC3: three floats); global, as OpenCV's macros are
 
 namespace cv {
 
@@ -49,7 +49,7 @@ struct DMatch { int queryIdx = -1, trainIdx = -1, imgIdx = -1; float distance = 
 
 // Dense row-major matrix, continuous, zero-initialised: a CV_32F one is what Intrinsics::K needs (K.at<float>(r, c),
 // BA.cpp:138,151-153,188-189), a CV_8U one holds binary descriptors (Features::descriptors, one row per key point) or a gray
-// image, a CV_8UC3 one a BGR image (cols counts pixels, a row is 3 cols bytes).
+// image, a CV_8UC3 one a BGR image (cols counts pixels, a row is 3 cols bytes), a CV_32FC3 one a normal map (a row is 3 cols floats).
 class Mat {
 public:
     Mat() : rows(0), cols(0), type_(CV_32F) {}
@@ -63,7 +63,7 @@ public:
     bool empty() const { return data_.empty(); }
     int rows, cols;
 private:
-    static size_t elem(int type) { return type == CV_8U ? 1 : type == CV_8UC3 ? 3 : 4; }
+    static size_t elem(int type) { return type == CV_8U ? 1 : type == CV_8UC3 ? 3 : type == CV_32FC3 ? 12 : 4; }
     unsigned char* bytes() { return reinterpret_cast<unsigned char*>(data_.data()); }
     const unsigned char* bytes() const { return reinterpret_cast<const unsigned char*>(data_.data()); }
     int type_;

@@ -726,6 +726,78 @@ int sfmba_shim_run_sfm_dense(int feature_type, float merge_distance, int n_views
     return 0;
 }
 
+// setImages, runSfM, densify() and mergeDenseCloud(voxel, min_count, max_rel_step) in one call (tests/test_gpu_cloud_pipeline.py).
+// Back come the poses [n_views][12], K [9], the jobs densify made (*n_jobs of them: job_ref / z_near / z_far [n_views], job_src_ptr
+// [n_views + 1], job_src [4 n_views]),
+// has_map [n_views], the depth maps of ALL views in view order (depth [sum of w h]; zeros where a view has none), the dense cloud as
+// it stands AFTER the merge (cap_dense rows) with *dense_unchanged = 1 iff it equals, byte for byte, the copy taken before the merge,
+// and the merged cloud (cap_dense rows: merged_xyz / merged_normal [..][3] floats, merged_bgr [..][3], merged_count, merged_first;
+// *voxel_used, *n_skipped).  ply_prefix != NULL: all four PLY files.  Returns runSfM's code, 10 + densify's code, 20 +
+// mergeDenseCloud's code, -2 if a capacity is too small, -3 if a PLY file could not be written.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_merged(int n_views, int channels, const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h,
+                              int debug_level, float voxel, int min_count, float max_rel_step, const char* ply_prefix, float* poses, float* K, int* n_jobs,
+                              int32_t* job_ref, int64_t* job_src_ptr, int32_t* job_src, float* z_near, float* z_far, unsigned char* has_map, float* depth, int64_t cap_dense, int64_t* n_dense, float* dense_xyz,
+                              unsigned char* dense_bgr, int32_t* dense_view, int32_t* dense_pixel, int* dense_unchanged, int64_t* n_merged,
+                              float* merged_xyz, unsigned char* merged_bgr, float* merged_normal, int32_t* merged_count, int32_t* merged_first,
+                              float* voxel_used, int64_t* n_skipped) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    sfm.setImages(images);
+    *n_jobs = 0; *n_dense = 0; *n_merged = 0; *dense_unchanged = 0; *n_skipped = 0; *voxel_used = 0.0f;
+    ErrorCode code = sfm.runSfM();
+    if (code != OKAY) return (int)code;
+    for (int v = 0; v < n_views; ++v)
+        for (int e = 0; e < 12; ++e) poses[12 * v + e] = sfm.getCameraPoses()[v].val[e];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) K[3 * r + c] = sfm.getIntrinsics().K.at<float>(r, c);
+    if (ply_prefix && !sfm.saveCloudAndCamerasToPLY(ply_prefix)) return -3;
+    if ((code = sfm.densify()) != OKAY) return 10 + (int)code;
+    job_src_ptr[0] = 0;
+    for (const DenseJob& j : sfm.getDenseJobs()) {
+        const int at = (*n_jobs)++;
+        job_ref[at] = j.reference; z_near[at] = j.zNear; z_far[at] = j.zFar;
+        job_src_ptr[at + 1] = job_src_ptr[at];
+        for (int s : j.sources) job_src[job_src_ptr[at + 1]++] = s;
+    }
+    const DenseCloud before = sfm.getDenseCloud();
+    if ((code = sfm.mergeDenseCloud(voxel, min_count, max_rel_step)) != OKAY) return 20 + (int)code;
+    size_t at = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const size_t n = (size_t)w[v] * h[v];
+        const cv::Mat& m = sfm.getDepthMaps()[(size_t)v];
+        has_map[v] = m.empty() ? 0 : 1;
+        if (m.empty()) std::memset(depth + at, 0, n * sizeof(float));
+        else std::memcpy(depth + at, m.ptr<float>(0), n * sizeof(float));
+        at += n;
+    }
+    const DenseCloud& cloud = sfm.getDenseCloud();
+    const MergedCloud& merged = sfm.getMergedDenseCloud();
+    *n_dense = (int64_t)cloud.points.size();
+    *n_merged = (int64_t)merged.points.size();
+    if (*n_dense > cap_dense || *n_merged > cap_dense) return -2;
+    bool same = cloud.points.size() == before.points.size() && cloud.bgr == before.bgr && cloud.views == before.views && cloud.pixels == before.pixels;
+    for (size_t i = 0; i < cloud.points.size(); ++i) {
+        dense_xyz[3 * i] = cloud.points[i].x; dense_xyz[3 * i + 1] = cloud.points[i].y; dense_xyz[3 * i + 2] = cloud.points[i].z;
+        for (int k = 0; k < 3; ++k) dense_bgr[3 * i + k] = cloud.bgr[3 * i + k];
+        dense_view[i] = cloud.views[i]; dense_pixel[i] = cloud.pixels[i];
+        same = same && std::memcmp(&cloud.points[i], &before.points[i], sizeof(cv::Point3f)) == 0;
+    }
+    *dense_unchanged = same ? 1 : 0;
+    for (size_t i = 0; i < merged.points.size(); ++i) {
+        merged_xyz[3 * i] = merged.points[i].x; merged_xyz[3 * i + 1] = merged.points[i].y; merged_xyz[3 * i + 2] = merged.points[i].z;
+        merged_normal[3 * i] = merged.normals[i].x; merged_normal[3 * i + 1] = merged.normals[i].y; merged_normal[3 * i + 2] = merged.normals[i].z;
+        for (int k = 0; k < 3; ++k) merged_bgr[3 * i + k] = merged.bgr[3 * i + k];
+        merged_count[i] = merged.counts[i]; merged_first[i] = merged.first[i];
+    }
+    *voxel_used = merged.voxel;
+    *n_skipped = (int64_t)merged.skipped;
+    if (ply_prefix && (!sfm.saveDenseCloudToPLY(ply_prefix) || !sfm.saveMergedDenseCloudToPLY(ply_prefix))) return -3;
+    return 0;
+}
+
 // SfM::densify() where it has to refuse (tests/test_depth_oracle_cpu.py; no device involved): what = 0 after setFeatures (there are
 // no pixels), 1 on images without a run, 2 on a fresh object.  Returns densify's code.
 extern "C" __attribute__((visibility("default")))
