@@ -1,0 +1,673 @@
+// api_frontend.hip -- C ABI of include/sfmba.h, the front-end entry points (everything in front of bundle adjustment: image files,
+// features, matches, RANSAC, triangulation, association, dense depth, flow, cloud merge): argument checks and dispatch.  The work
+// is in the unit each wrapper names; the error state, the device checks and the problem / solver entry points are in sfmba_api.hip.
+//
+// Every wrapper reads: checks, open, call, timing line, mapped result.  Every check comes before the first write: a refused call
+// leaves the outputs as they were.  What several entry points refuse in the same words is one check_* function below.
+#include "association.h"
+#include "cloud_merge.h"
+#include "depth_sweep.h"
+#include "essential_ransac.h"
+#include "feature_match.h"
+#include "flow_math.h"
+#include "flow_track.h"
+#include "homography_ransac.h"
+#include "jpeg_decode.h"
+#include "jpeg_math.h"
+#include "match_l2.h"
+#include "orb_extract.h"
+#include "png_decode.h"
+#include "pnp_ransac.h"
+#include "problem.h"
+#include "surf_extract.h"
+#include <climits>
+#include <cmath>
+
+using namespace sfmba;
+
+namespace {
+// A CallKit and the unit's timing array: tm() is the array when the environment switch `env` is set (one stderr line per call with
+// the HIP-event times of its phases, parsed by tools/*_bench.py), NULL otherwise
+template <int N> struct TimedCall : CallKit {
+    double t[N];
+    const bool on;
+    explicit TimedCall(const char* env) : on(std::getenv(env) != nullptr) {}
+    double* tm() { return on ? t : nullptr; }
+};
+
+// what a unit returned -> SFMBA_OK or the failure; too_large is the unit's own text for UNIT_ERR_TOO_LARGE
+int unit_result(int rc, const char* who, const char* too_large = "") {
+    if (rc == 0) return SFMBA_OK;
+    const std::string w = std::string(who) + ": ";
+    if (rc == UNIT_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, w + "output capacity too small");
+    if (rc == UNIT_ERR_TOO_LARGE) return fail(SFMBA_ERR_INVALID_ARG, w + too_large);
+    if (rc == UNIT_ERR_SIZE) return fail(SFMBA_ERR_INVALID_ARG, w + "the factor gives an image a side outside 1..16384");
+    if (rc == UNIT_ERR_HOST_ALLOC) return fail(SFMBA_ERR_ALLOC, w + "host allocation failed");
+    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, w + "device allocation failed");
+    return fail(SFMBA_ERR_HIP, w + hipGetErrorString((hipError_t)rc));
+}
+
+// ---- one function per argument shape that several entry points share; each returns 0 or the failure ----------------------------
+// a batch of 8-bit images (n_images >= 0, img_ptr and, for n_images > 0, width and height are not NULL)
+int check_images(const char* who, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                 int channels) {
+    const std::string w(who);
+    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, w + ": channels must be 1 or 3");
+    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
+            return fail(SFMBA_ERR_INVALID_ARG, w + ": an image dimension lies outside 1..16384");
+        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
+            return fail(SFMBA_ERR_INVALID_ARG, w + ": img_ptr does not agree with width * height * channels");
+    }
+    if (n_images > 0 && !pixels) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    return 0;
+}
+// a match list over the points of n_images images (n_images, n_pairs >= 0, img_ptr and pair_ptr and, for n_pairs > 0, pair_left and
+// pair_right are not NULL)
+int check_match_list(const char* who, int n_images, const int64_t* img_ptr, const float* pts, int n_pairs, const int32_t* pair_left,
+                     const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx) {
+    const std::string w(who);
+    if (img_ptr[0] < 0 || pair_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr and pair_ptr must not be negative");
+    for (int i = 0; i < n_images; ++i)
+        if (img_ptr[i + 1] < img_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
+    for (int p = 0; p < n_pairs; ++p) {
+        if (pair_ptr[p + 1] < pair_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "pair_ptr not monotone");
+        if (pair_ptr[p + 1] - pair_ptr[p] > (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, w + ": a pair has 2^31 or more matches");
+        if (pair_left[p] < 0 || pair_left[p] >= n_images || pair_right[p] < 0 || pair_right[p] >= n_images)
+            return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
+    }
+    if (pair_ptr[n_pairs] > pair_ptr[0] && (!query_idx || !train_idx || !pts)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    for (int p = 0; p < n_pairs; ++p) {
+        const int64_t nl = img_ptr[pair_left[p] + 1] - img_ptr[pair_left[p]], nr = img_ptr[pair_right[p] + 1] - img_ptr[pair_right[p]];
+        for (int64_t e = pair_ptr[p]; e < pair_ptr[p + 1]; ++e)
+            if (query_idx[e] < 0 || query_idx[e] >= nl || train_idx[e] < 0 || train_idx[e] >= nr)
+                return fail(SFMBA_ERR_INVALID_ARG, w + ": a query_idx / train_idx lies outside its image");
+    }
+    return 0;
+}
+// the descriptor rows of n_images images and the pairs to match (the same preconditions); the limit on the rows of one image is
+// worded per matcher and stays with it
+int check_desc_rows(const char* who, int n_images, const int64_t* img_ptr, const void* desc, int n_pairs, const int32_t* pair_left,
+                    const int32_t* pair_right) {
+    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i)
+        if (img_ptr[i + 1] < img_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
+    if (img_ptr[n_images] > 0 && !desc) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    int64_t rows = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        const int l = pair_left[p], r = pair_right[p];
+        if (l < 0 || l >= n_images || r < 0 || r >= n_images) return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
+        if (img_ptr[r + 1] - img_ptr[r] >= 2) rows += img_ptr[l + 1] - img_ptr[l];
+    }
+    if (rows >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": too many query rows in one call (2^31)");
+    return 0;
+}
+bool too_many_rows(int n_images, const int64_t* img_ptr) {
+    for (int i = 0; i < n_images; ++i)
+        if (img_ptr[i + 1] - img_ptr[i] >= ((int64_t)1 << 22)) return true;
+    return false;
+}
+int check_ransac(int n_hyp, float threshold_px) {
+    if (n_hyp < 1 || n_hyp > 65536) return fail(SFMBA_ERR_INVALID_ARG, "n_hyp must be in 1..65536");
+    if (!std::isfinite(threshold_px) || !(threshold_px > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "threshold_px must be finite and > 0");
+    return 0;
+}
+int check_focal(const float* K) {
+    if (!std::isfinite(K[0]) || !(K[0] > 0.0f) || !std::isfinite(K[4]) || !(K[4] > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "fx and fy must be finite and > 0");
+    return 0;
+}
+// what every dense call refuses about the sizes, K and P
+int depth_check_cameras(const char* who, int n_images, const int32_t* width, const int32_t* height, const float* K, const float* P) {
+    const std::string w(who);
+    if (n_images < 0 || !K || (n_images > 0 && (!width || !height || !P))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    for (int i = 0; i < n_images; ++i) {
+        if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
+            return fail(SFMBA_ERR_INVALID_ARG, w + ": an image dimension lies outside 1..16384");
+        for (int q = 0; q < 12; ++q)
+            if (!std::isfinite(P[(size_t)i * 12 + q])) return fail(SFMBA_ERR_INVALID_ARG, w + ": non-finite pose of image " + std::to_string(i));
+    }
+    for (int q : { 0, 4, 2, 5 })
+        if (!std::isfinite(K[q])) return fail(SFMBA_ERR_INVALID_ARG, w + ": fx, fy, cx and cy must be finite");
+    if (!(K[0] > 0.0f) || !(K[4] > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, w + ": fx and fy must be > 0");
+    return 0;
+}
+// what the sweep and the fuse refuse about the images, K and P
+int depth_check_images(const char* who, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                       int channels, const float* K, const float* P) {
+    if (n_images < 0 || !img_ptr || !K || (n_images > 0 && (!width || !height || !P || !pixels))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = check_images(who, n_images, img_ptr, pixels, width, height, channels)) return rc;
+    return depth_check_cameras(who, n_images, width, height, K, P);
+}
+// a CSR list of 0 / 1 .. 4 other images per row
+int depth_check_lists(const char* who, const char* what, int n_images, int n_rows, const int32_t* row_image, const int64_t* ptr, const int32_t* idx,
+                      int min_len) {
+    const std::string w(who);
+    if (!ptr || ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, w + ": " + what + " pointer array must start at 0");
+    for (int j = 0; j < n_rows; ++j) {
+        const int64_t n = ptr[j + 1] - ptr[j];
+        if (n < min_len || n > 4) return fail(SFMBA_ERR_INVALID_ARG, w + ": a row has " + std::to_string((long long)n) + " " + what + " images, outside " +
+                                                                       std::to_string(min_len) + "..4");
+        if (n > 0 && !idx) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+        const int own = row_image ? row_image[j] : j;
+        for (int64_t a = ptr[j]; a < ptr[j + 1]; ++a) {
+            if (idx[a] < 0 || idx[a] >= n_images) return fail(SFMBA_ERR_INVALID_ARG, w + ": " + what + " image index out of range");
+            if (idx[a] == own) return fail(SFMBA_ERR_INVALID_ARG, w + ": a " + what + " image equals the image it belongs to");
+            for (int64_t c = ptr[j]; c < a; ++c)
+                if (idx[c] == idx[a]) return fail(SFMBA_ERR_INVALID_ARG, w + ": a " + what + " image is listed twice");
+        }
+    }
+    return 0;
+}
+// what both flow calls refuse about the pair list and the points' CSR
+int flow_check_pairs(const char* who, int n_images, int n_pairs, const int32_t* pair_a, const int32_t* pair_b, const int64_t* pt_ptr) {
+    const std::string w(who);
+    if (n_images < 0 || n_pairs < 0 || !pt_ptr || (n_pairs > 0 && !pair_b)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (pt_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, w + ": pt_ptr must start at 0");
+    for (int p = 0; p < n_pairs; ++p) {
+        if ((pair_a && (pair_a[p] < 0 || pair_a[p] >= n_images)) || pair_b[p] < 0 || pair_b[p] >= n_images)
+            return fail(SFMBA_ERR_INVALID_ARG, w + ": pair index out of range");
+        if (pt_ptr[p + 1] < pt_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, w + ": pt_ptr not monotone");
+    }
+    if (pt_ptr[n_pairs] >= (int64_t)1 << 31) return fail(SFMBA_ERR_INVALID_ARG, w + ": 2^31 or more points in one call");
+    return 0;
+}
+// the files of a batch, back to back in `bytes`
+int check_file_ptr(int n_images, const int64_t* file_ptr, const unsigned char* bytes) {
+    if (n_images < 0 || !file_ptr) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (file_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "file_ptr must not be negative");
+    for (int i = 0; i < n_images; ++i)
+        if (file_ptr[i + 1] < file_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "file_ptr not monotone");
+    if (file_ptr[n_images] > file_ptr[0] && !bytes) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    return 0;
+}
+// the timing line of the two calls that end in jpeg_decode.hip
+void image_timing_line(const char* what, const double* tm) {
+    std::fprintf(stderr, "[sfmba %s] entropy_ms %.6f upload_ms %.6f idct_ms %.6f colour_ms %.6f resize_ms %.6f download_ms %.6f groups %d\n", what,
+                 tm[JPEG_T_ENTROPY], tm[JPEG_T_UPLOAD], tm[JPEG_T_IDCT], tm[JPEG_T_COLOUR], tm[JPEG_T_RESIZE], tm[JPEG_T_DOWNLOAD], (int)tm[JPEG_T_GROUPS]);
+}
+}  // namespace
+
+extern "C" {
+// ---- triangulation (SfMStereoUtilities::triangulateViews) --------------------------------------------------------------------------
+int sfmba_triangulate(int device, int64_t n, const float* left_xy, const float* right_xy, const float* K, const float* P_left,
+                      const float* P_right, float max_reproj_px, float* points3d, unsigned char* keep, float* reproj_err) {
+    if (n < 0 || !K || !P_left || !P_right || (n > 0 && (!left_xy || !right_xy || !points3d || !keep)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (n == 0) return check_device(device);
+    DeviceArena arena(device);
+    CallKit ck;
+    if (const int rc = ck.open(device)) return rc;
+    const HostKit& kit = ck.kit;
+    float* d_l = arena.alloc_n<float>((size_t)2 * n);
+    float* d_r = arena.alloc_n<float>((size_t)2 * n);
+    float* d_x = arena.alloc_n<float>((size_t)3 * n);
+    float* d_e = reproj_err ? arena.alloc_n<float>((size_t)2 * n) : nullptr;
+    unsigned char* d_k = arena.alloc_n<unsigned char>((size_t)n);
+    if (!d_l || !d_r || !d_x || !d_k || (reproj_err && !d_e)) return fail(SFMBA_ERR_ALLOC, "device allocation failed");
+    HIP_TRY(hipMemcpyAsync(d_l, left_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, kit.stream));
+    HIP_TRY(hipMemcpyAsync(d_r, right_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, kit.stream));
+    launch_triangulate(kit.stream, (long long)n, d_l, d_r, K, P_left, P_right, max_reproj_px, d_x, d_k, d_e);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(points3d, d_x, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, kit.stream));
+    HIP_TRY(hipMemcpyAsync(keep, d_k, (size_t)n, hipMemcpyDeviceToHost, kit.stream));
+    if (reproj_err) HIP_TRY(hipMemcpyAsync(reproj_err, d_e, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, kit.stream));
+    HIP_TRY(hipStreamSynchronize(kit.stream));
+    return SFMBA_OK;
+}
+
+int sfmba_triangulate_pairs(int device, int n_images, const int64_t* img_ptr, const float* pts, const float* K, int n_pairs, const int32_t* pair_left,
+                            const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx,
+                            const unsigned char* mask, const float* P_left, const float* P_right, float max_reproj_px, float* points3d,
+                            unsigned char* keep, float* reproj_err, int64_t* kept_ptr, int64_t* kept_idx) {
+    if (n_images < 0 || n_pairs < 0 || !img_ptr || !pair_ptr || !K || !kept_ptr || (n_pairs > 0 && (!pair_left || !pair_right || !P_left || !P_right)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (!std::isfinite(max_reproj_px) || max_reproj_px < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "max_reproj_px must be finite and >= 0");
+    if (const int rc = check_match_list("triangulate_pairs", n_images, img_ptr, pts, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx)) return rc;
+    const int64_t total = pair_ptr[n_pairs];
+    if (total > 0 && (!points3d || !keep || !kept_idx)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (total >= (int64_t)INT_MAX - 256) return fail(SFMBA_ERR_INVALID_ARG, "triangulate_pairs: too many entries for one call (2^31)");
+    if (total == pair_ptr[0]) {                                       // no entry belongs to a pair: nothing runs on the device
+        if (const int rc = check_device(device)) return rc;
+        for (int64_t e = 0; e < total; ++e) {
+            points3d[3 * e] = points3d[3 * e + 1] = points3d[3 * e + 2] = 0.0f;
+            keep[e] = 0;
+            if (reproj_err) reproj_err[2 * e] = reproj_err[2 * e + 1] = 0.0f;
+        }
+        for (int p = 0; p <= n_pairs; ++p) kept_ptr[p] = 0;
+        return SFMBA_OK;
+    }
+    CallKit ck;
+    if (const int rc = ck.open(device)) return rc;
+    return unit_result(triangulate_pairs(ck.kit.stream, device, n_images, img_ptr, pts, K, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx,
+                                         mask, P_left, P_right, max_reproj_px, points3d, keep, reproj_err, kept_ptr, kept_idx), "triangulate_pairs");
+}
+
+// ---- association joins -----------------------------------------------------------------------
+int sfmba_find_2d3d_matches(int device, int n_views, const unsigned char* view_done, int n_pt, const int64_t* view_ptr,
+                            const int32_t* view_idx, const int32_t* feat_idx, int n_pairs, const int32_t* pair_left,
+                            const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx,
+                            int64_t* out_ptr, int32_t* out_point, int32_t* out_feature, int64_t cap, int64_t* total) {
+    if (n_views < 0 || n_pt < 0 || n_pairs < 0 || cap < 0 || !out_ptr || !total || (n_views > 0 && !view_done) || !view_ptr ||
+        (n_pairs > 0 && (!pair_left || !pair_right || !pair_ptr)) || (cap > 0 && (!out_point || !out_feature)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (view_ptr[0] != 0 || (n_pairs > 0 && pair_ptr[0] != 0)) return fail(SFMBA_ERR_INVALID_ARG, "CSR pointers must start at 0");
+    for (int i = 0; i < n_pt; ++i) if (view_ptr[i + 1] < view_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "view_ptr not monotone");
+    for (int p = 0; p < n_pairs; ++p) if (pair_ptr[p + 1] < pair_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "pair_ptr not monotone");
+    if ((view_ptr[n_pt] > 0 && (!view_idx || !feat_idx)) || (n_pairs > 0 && pair_ptr[n_pairs] > 0 && (!query_idx || !train_idx)))
+        return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    CallKit ck;
+    if (const int rc = ck.open(device)) return rc;
+    return unit_result(assoc_find_2d3d(ck.kit.stream, device, n_views, view_done, n_pt, view_ptr, view_idx, feat_idx, n_pairs, pair_left, pair_right,
+                                       pair_ptr, query_idx, train_idx, out_ptr, out_point, out_feature, cap, total),
+                       "find_2d3d_matches", "problem too large for 32-bit indices");
+}
+
+int sfmba_merge_candidates(int device, int n_exist, const float* exist_xyz, int n_new, const float* new_xyz, float max_dist,
+                           int64_t* cand_ptr, int32_t* cand_idx, int64_t cap, int64_t* total) {
+    if (n_exist < 0 || n_new < 0 || cap < 0 || !cand_ptr || !total || (n_exist > 0 && !exist_xyz) || (n_new > 0 && !new_xyz) || (cap > 0 && !cand_idx))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    CallKit ck;
+    if (const int rc = ck.open(device)) return rc;
+    return unit_result(assoc_radius_candidates(ck.kit.stream, device, n_exist, exist_xyz, n_new, new_xyz, max_dist, cand_ptr, cand_idx, cap, total),
+                       "merge_candidates", "problem too large for 32-bit indices");
+}
+
+// ---- feature match matrix (SfM::createFeatureMatchMatrix) ---------------------------------------------------------
+int sfmba_match_features(int device, int n_images, const int64_t* img_ptr, const unsigned char* desc, int desc_bytes, int n_pairs,
+                         const int32_t* pair_left, const int32_t* pair_right, double ratio, int64_t* pair_ptr, int32_t* query_idx,
+                         int32_t* train_idx, float* distance, int64_t cap, int64_t* total) {
+    if (n_images < 0 || n_pairs < 0 || cap < 0 || !img_ptr || !pair_ptr || !total || (n_pairs > 0 && (!pair_left || !pair_right)) ||
+        (cap > 0 && (!query_idx || !train_idx)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (desc_bytes < 1 || desc_bytes > 64) return fail(SFMBA_ERR_INVALID_ARG, "desc_bytes must be in 1..64");
+    if (!std::isfinite(ratio) || !(ratio > 0.0)) return fail(SFMBA_ERR_INVALID_ARG, "ratio must be finite and > 0");
+    if (const int rc = check_desc_rows("match_features", n_images, img_ptr, desc, n_pairs, pair_left, pair_right)) return rc;
+    if (too_many_rows(n_images, img_ptr))
+        return fail(SFMBA_ERR_INVALID_ARG, "an image has 2^22 or more descriptor rows (the train index is packed in 22 bits)");
+    TimedCall<5> c("SFMBA_MATCH_TIMING");          // (tools/match_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = match_features(c.kit.stream, device, n_images, img_ptr, desc, desc_bytes, n_pairs, pair_left, pair_right, ratio, pair_ptr, query_idx,
+                                  train_idx, distance, cap, total, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba match] upload_ms %.6f top2_ms %.6f compact_ms %.6f download_ms %.6f batches %d\n", c.t[0], c.t[1], c.t[2], c.t[3],
+                     (int)c.t[4]);
+    return unit_result(rc, "match_features");
+}
+// ---- the same for float descriptors: exact L2 2-NN (cv::BFMatcher with NORM_L2) ---------------------------------------------
+int sfmba_match_features_l2(int device, int n_images, const int64_t* img_ptr, const float* desc, int dims, int n_pairs,
+                            const int32_t* pair_left, const int32_t* pair_right, double ratio, int64_t* pair_ptr, int32_t* query_idx,
+                            int32_t* train_idx, float* distance, int64_t cap, int64_t* total) {
+    if (n_images < 0 || n_pairs < 0 || cap < 0 || !img_ptr || !pair_ptr || !total || (n_pairs > 0 && (!pair_left || !pair_right)) ||
+        (cap > 0 && (!query_idx || !train_idx)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (dims < 1 || dims > MATCH_L2_MAX_DIMS) return fail(SFMBA_ERR_INVALID_ARG, "dims must be in 1..512");
+    if (!std::isfinite(ratio) || !(ratio > 0.0)) return fail(SFMBA_ERR_INVALID_ARG, "ratio must be finite and > 0");
+    if (const int rc = check_desc_rows("match_features_l2", n_images, img_ptr, desc, n_pairs, pair_left, pair_right)) return rc;
+    if (too_many_rows(n_images, img_ptr)) return fail(SFMBA_ERR_INVALID_ARG, "an image has 2^22 or more descriptor rows");
+    for (int i = 0; i < n_images; ++i)                      // the contract is stated for finite values only
+        for (int64_t r = img_ptr[i]; r < img_ptr[i + 1]; ++r) {
+            const float* row = desc + (size_t)r * (size_t)dims;
+            for (int k = 0; k < dims; ++k)
+                if (!std::isfinite(row[k]))
+                    return fail(SFMBA_ERR_INVALID_ARG, "match_features_l2: non-finite descriptor value in image " + std::to_string(i) + ", row " +
+                                                           std::to_string((long long)(r - img_ptr[i])));
+        }
+    TimedCall<5> c("SFMBA_MATCH_TIMING");          // (tools/match_l2_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = match_features_l2(c.kit.stream, device, n_images, img_ptr, desc, dims, n_pairs, pair_left, pair_right, ratio, pair_ptr, query_idx,
+                                     train_idx, distance, cap, total, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba match_l2] upload_ms %.6f top2_ms %.6f compact_ms %.6f download_ms %.6f batches %d\n", c.t[0], c.t[1], c.t[2], c.t[3],
+                     (int)c.t[4]);
+    return unit_result(rc, "match_features_l2");
+}
+// ---- feature extraction (SfM::extractFeatures) ------------------------------------------------------------------------
+int sfmba_orb_extract(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                      int channels, int n_features, float scale_factor, int n_levels, int fast_threshold, int64_t* kp_ptr, sfmba_orb_keypoint* kp,
+                      unsigned char* desc, int64_t cap, int64_t* total, int32_t* dbg_level_xy, int32_t* dbg_bin, int64_t* dbg_harris,
+                      int32_t* dbg_candidates) {
+    if (n_images < 0 || cap < 0 || !img_ptr || !kp_ptr || !total || (n_images > 0 && (!width || !height)) || (cap > 0 && (!kp || !desc)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = check_images("orb_extract", n_images, img_ptr, pixels, width, height, channels)) return rc;
+    if (n_features < 1) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: n_features must be >= 1");
+    if (n_levels < 1 || n_levels > 12) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: n_levels must be in 1..12");
+    if (!std::isfinite(scale_factor) || !(scale_factor > 1.0f) || scale_factor > 2.0f)
+        return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: scale_factor must be finite and in (1, 2]");
+    if (fast_threshold < 1 || fast_threshold > 254) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: fast_threshold must be in 1..254");
+    TimedCall<ORB_T_COUNT> c("SFMBA_ORB_TIMING");          // (tools/orb_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = orb_extract(c.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, n_features, scale_factor, n_levels,
+                               fast_threshold, kp_ptr, kp, desc, cap, total, dbg_level_xy, dbg_bin, dbg_harris, dbg_candidates, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba orb] upload_ms %.6f pyramid_ms %.6f score_ms %.6f candidates_ms %.6f response_ms %.6f select_ms %.6f smooth_ms %.6f "
+                     "describe_ms %.6f download_ms %.6f groups %d\n", c.t[ORB_T_UPLOAD], c.t[ORB_T_PYRAMID], c.t[ORB_T_SCORE], c.t[ORB_T_CANDIDATES],
+                     c.t[ORB_T_HARRIS], c.t[ORB_T_SELECT], c.t[ORB_T_SMOOTH], c.t[ORB_T_DESCRIBE], c.t[ORB_T_DOWNLOAD], (int)c.t[ORB_T_GROUPS]);
+    return unit_result(rc, "orb_extract");
+}
+// ---- float descriptors: Fast-Hessian detect and SURF-style describe, the extractor in front of sfmba_match_features_l2 ---------
+int sfmba_surf_extract(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                       int channels, int n_features, int n_octaves, float hessian_threshold, int upright, int64_t* kp_ptr, sfmba_surf_keypoint* kp,
+                       float* desc, int64_t cap, int64_t* total, int32_t* dbg_bin, int64_t* dbg_moments, int64_t* dbg_sums, int32_t* dbg_candidates) {
+    if (n_images < 0 || cap < 0 || !img_ptr || !kp_ptr || !total || (n_images > 0 && (!width || !height)) || (cap > 0 && (!kp || !desc)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = check_images("surf_extract", n_images, img_ptr, pixels, width, height, channels)) return rc;
+    if (n_features < 1) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: n_features must be >= 1");
+    if (n_octaves < 1 || n_octaves > 4) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: n_octaves must be in 1..4");
+    if (!std::isfinite(hessian_threshold) || hessian_threshold < 0.0f)
+        return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: hessian_threshold must be finite and >= 0");
+    if (upright != 0 && upright != 1) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: upright must be 0 or 1");
+    TimedCall<SURF_T_COUNT> c("SFMBA_SURF_TIMING");          // (tools/surf_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = surf_extract(c.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, n_features, n_octaves, hessian_threshold,
+                                upright, kp_ptr, kp, desc, cap, total, dbg_bin, dbg_moments, dbg_sums, dbg_candidates, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba surf] upload_ms %.6f integral_ms %.6f response_ms %.6f candidates_ms %.6f select_ms %.6f describe_ms %.6f "
+                     "download_ms %.6f groups %d response_bytes %.0f\n", c.t[SURF_T_UPLOAD], c.t[SURF_T_INTEGRAL], c.t[SURF_T_RESPONSE],
+                     c.t[SURF_T_CANDIDATES], c.t[SURF_T_SELECT], c.t[SURF_T_DESCRIBE], c.t[SURF_T_DOWNLOAD], (int)c.t[SURF_T_GROUPS],
+                     c.t[SURF_T_RESPONSE_BYTES]);
+    return unit_result(rc, "surf_extract");
+}
+// ---- dense depth maps and a dense cloud: plane-sweep stereo and the consistency filter (SfM::densify) ---------------------------
+int sfmba_depth_sweep(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                      int channels, const float* K, const float* P, int n_jobs, const int32_t* job_ref, const int64_t* job_src_ptr,
+                      const int32_t* job_src, const float* z_near, const float* z_far, int n_planes, int radius, int min_std, float min_score,
+                      int min_sources, float* depth, float* score, int16_t* plane) {
+    if (n_jobs < 0 || (n_jobs > 0 && (!job_ref || !job_src_ptr || !job_src || !z_near || !z_far))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = depth_check_images("depth_sweep", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    if (n_planes < 2 || n_planes > 256) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: n_planes must be in 2..256");
+    if (radius < 1 || radius > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: radius must be in 1..4");
+    if (min_std < 0 || min_std > 127) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_std must be in 0..127");
+    if (!(min_score >= -1.0f) || !(min_score <= 1.0f)) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_score must be in [-1, 1]");
+    if (min_sources < 1 || min_sources > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_sources must be in 1..4");
+    int64_t out_px = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (job_ref[j] < 0 || job_ref[j] >= n_images) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: reference image index out of range");
+        if (!std::isfinite(z_near[j]) || !std::isfinite(z_far[j]) || !(z_near[j] > 0.0f) || !(z_near[j] < z_far[j]))
+            return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: a job needs 0 < z_near < z_far, both finite");
+        out_px += (int64_t)width[job_ref[j]] * height[job_ref[j]];
+    }
+    if (n_jobs > 0)
+        if (const int rc = depth_check_lists("depth_sweep", "source", n_images, n_jobs, job_ref, job_src_ptr, job_src, 1)) return rc;
+    if (out_px > 0 && (!depth || !score)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (n_jobs == 0) return check_device(device);
+    TimedCall<DEPTH_T_COUNT> c("SFMBA_DEPTH_TIMING");          // (tools/dense_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = depth_sweep(c.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, K, P, n_jobs, job_ref, job_src_ptr, job_src,
+                               z_near, z_far, n_planes, radius, min_std, min_score, min_sources, depth, score, plane, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba depth_sweep] upload_ms %.6f gray_ms %.6f sweep_ms %.6f download_ms %.6f groups %d\n", c.t[DEPTH_T_UPLOAD],
+                     c.t[DEPTH_T_GRAY], c.t[DEPTH_T_SWEEP], c.t[DEPTH_T_DOWNLOAD], (int)c.t[DEPTH_T_GROUPS]);
+    return unit_result(rc, "depth_sweep");
+}
+int sfmba_depth_fuse(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                     int channels, const float* K, const float* P, const float* const* depth, const int64_t* chk_ptr, const int32_t* chk,
+                     float rel_tol, int min_consistent, int64_t* pt_ptr, float* xyz, unsigned char* bgr, int32_t* src_image, int32_t* src_pixel,
+                     int64_t cap, int64_t* total) {
+    if (cap < 0 || !pt_ptr || !total || (n_images > 0 && !depth) || (cap > 0 && (!xyz || !bgr || !src_image || !src_pixel)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = depth_check_images("depth_fuse", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    if (n_images > 65535) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: more than 65535 images in one call");
+    if (!std::isfinite(rel_tol) || rel_tol < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: rel_tol must be finite and >= 0");
+    if (min_consistent < 0 || min_consistent > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: min_consistent must be in 0..4");
+    if (const int rc = depth_check_lists("depth_fuse", "check", n_images, n_images, nullptr, chk_ptr, chk, 0)) return rc;
+    int64_t px = 0;
+    for (int i = 0; i < n_images; ++i)
+        if (depth[i]) px += (int64_t)width[i] * height[i];
+    if (px >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: too many pixels with a depth map in one call (2^31)");
+    if (px == 0) {
+        for (int i = 0; i <= n_images; ++i) pt_ptr[i] = 0;
+        *total = 0;
+        return check_device(device);
+    }
+    TimedCall<FUSE_T_COUNT> c("SFMBA_DEPTH_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = depth_fuse(c.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, K, P, depth, chk_ptr, chk, rel_tol, min_consistent,
+                              pt_ptr, xyz, bgr, src_image, src_pixel, cap, total, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba depth_fuse] upload_ms %.6f flag_ms %.6f scan_ms %.6f emit_ms %.6f download_ms %.6f\n", c.t[FUSE_T_UPLOAD],
+                     c.t[FUSE_T_FLAG], c.t[FUSE_T_SCAN], c.t[FUSE_T_EMIT], c.t[FUSE_T_DOWNLOAD]);
+    return unit_result(rc, "depth_fuse");
+}
+// ---- matching by optical flow: pyramidal Lucas-Kanade and the snap to key points (SfMFeatureMatching::createFlowMatchMatrix) -----
+int sfmba_flow_track(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                     int channels, int n_pairs, const int32_t* pair_src, const int32_t* pair_dst, const int64_t* pt_ptr, const float* pts,
+                     int n_levels, int radius, int max_iters, float min_eig, float* next, unsigned char* status, float* err, int64_t* dbg_G,
+                     int32_t* dbg_state, unsigned char* dbg_pyramid) {
+    if (n_images < 0 || !img_ptr || (n_images > 0 && (!width || !height)) || (n_pairs > 0 && !pair_src))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = check_images("flow_track", n_images, img_ptr, pixels, width, height, channels)) return rc;
+    if (n_levels < 1 || n_levels > FLOW_MAX_LEVELS) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: n_levels must be in 1..8");
+    if (radius < 1 || radius > FLOW_MAX_RADIUS) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: radius must be in 1..10");
+    if (max_iters < 1 || max_iters > FLOW_MAX_ITERS) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: max_iters must be in 1..64");
+    if (!std::isfinite(min_eig) || min_eig < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: min_eig must be finite and >= 0");
+    if (const int rc = flow_check_pairs("flow_track", n_images, n_pairs, pair_src, pair_dst, pt_ptr)) return rc;
+    const int64_t n_pts = pt_ptr[n_pairs];
+    if (n_pts > 0 && (!pts || !next || !status || !err)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    for (int64_t q = 0; q < 2 * n_pts; ++q)
+        if (!std::isfinite(pts[q])) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: non-finite coordinate of point " + std::to_string((long long)(q / 2)));
+    if (n_pairs == 0) return check_device(device);
+    TimedCall<FLOW_T_COUNT> c("SFMBA_FLOW_TIMING");          // (tools/flow_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = flow_track(c.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, n_pairs, pair_src, pair_dst, pt_ptr, pts, n_levels,
+                              radius, max_iters, min_eig, next, status, err, dbg_G, dbg_state, dbg_pyramid, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba flow_track] upload_ms %.6f gray_ms %.6f pyramid_ms %.6f track_ms %.6f download_ms %.6f groups %d\n",
+                     c.t[FLOW_T_UPLOAD], c.t[FLOW_T_GRAY], c.t[FLOW_T_PYRAMID], c.t[FLOW_T_TRACK], c.t[FLOW_T_DOWNLOAD], (int)c.t[FLOW_T_GROUPS]);
+    return unit_result(rc, "flow_track");
+}
+int sfmba_flow_match(int device, int n_images, const int64_t* kp_ptr, const float* kp_xy, int n_pairs, const int32_t* pair_dst,
+                     const int64_t* pt_ptr, const float* next, const unsigned char* status, const float* err, float max_err, float radius,
+                     double ratio, int64_t* pair_ptr, int32_t* query_idx, int32_t* train_idx, float* distance, int64_t cap, int64_t* total) {
+    if (cap < 0 || !kp_ptr || !pair_ptr || !total || (cap > 0 && (!query_idx || !train_idx))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (!std::isfinite(max_err)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: max_err must be finite");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: radius must be finite and > 0");
+    if (!std::isfinite(ratio) || !(ratio > 0.0)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: ratio must be finite and > 0");
+    if (const int rc = flow_check_pairs("flow_match", n_images, n_pairs, nullptr, pair_dst, pt_ptr)) return rc;
+    if (kp_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: kp_ptr must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        const int64_t n = kp_ptr[i + 1] - kp_ptr[i];
+        if (n < 0) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: kp_ptr not monotone");
+        if (n >= ((int64_t)1 << 22)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: an image has 2^22 or more key points");
+    }
+    const int64_t n_pts = pt_ptr[n_pairs];
+    if ((n_pts > 0 && (!next || !status || !err)) || (kp_ptr[n_images] > 0 && !kp_xy)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (n_pts == 0) {
+        for (int p = 0; p <= n_pairs; ++p) pair_ptr[p] = 0;
+        *total = 0;
+        return check_device(device);
+    }
+    TimedCall<FLOWM_T_COUNT> c("SFMBA_FLOW_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = flow_match(c.kit.stream, device, n_images, kp_ptr, kp_xy, n_pairs, pair_dst, pt_ptr, next, status, err, max_err, radius, ratio, pair_ptr,
+                              query_idx, train_idx, distance, cap, total, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba flow_match] upload_ms %.6f near_ms %.6f compact_ms %.6f download_ms %.6f\n", c.t[FLOWM_T_UPLOAD], c.t[FLOWM_T_NEAR],
+                     c.t[FLOWM_T_COMPACT], c.t[FLOWM_T_DOWNLOAD]);
+    return unit_result(rc, "flow_match");
+}
+// ---- one oriented point per surface element: a normal per depth pixel and the voxel merge (SfM::mergeDenseCloud) ------------------
+int sfmba_depth_normals(int device, int n_images, const int32_t* width, const int32_t* height, const float* K, const float* P,
+                        const float* const* depth, float max_rel_step, float* const* normal) {
+    if ((n_images > 0 && (!depth || !normal))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = depth_check_cameras("depth_normals", n_images, width, height, K, P)) return rc;
+    if (n_images > 65535) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: more than 65535 images in one call");
+    if (!std::isfinite(max_rel_step) || max_rel_step < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: max_rel_step must be finite and >= 0");
+    int64_t px = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (!depth[i]) continue;
+        if (!normal[i]) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: an image with a depth map needs an output map");
+        px += (int64_t)width[i] * height[i];
+    }
+    if (px >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: too many pixels with a depth map in one call (2^31)");
+    if (px == 0) return check_device(device);
+    TimedCall<NORMALS_T_COUNT> c("SFMBA_CLOUD_TIMING");          // (tools/cloud_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = depth_normals(c.kit.stream, device, n_images, width, height, K, P, depth, max_rel_step, normal, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba depth_normals] upload_ms %.6f kernel_ms %.6f download_ms %.6f\n", c.t[NORMALS_T_UPLOAD], c.t[NORMALS_T_KERNEL],
+                     c.t[NORMALS_T_DOWNLOAD]);
+    return unit_result(rc, "depth_normals");
+}
+int sfmba_cloud_merge(int device, int64_t n, const float* xyz, const unsigned char* bgr, const float* normal, float voxel, int min_count,
+                      float* xyz_out, unsigned char* bgr_out, float* normal_out, int32_t* count, int32_t* first, int32_t* voxel_of, int64_t cap,
+                      int64_t* total, int64_t* n_skipped) {
+    if (n < 0 || cap < 0 || !total || !n_skipped || (n > 0 && !xyz) ||
+        (cap > 0 && (!xyz_out || !count || !first || (bgr && !bgr_out) || (normal && !normal_out))))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (n >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "cloud_merge: too many points in one call (2^31)");
+    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "cloud_merge: voxel must be finite and > 0");
+    if (min_count < 1) return fail(SFMBA_ERR_INVALID_ARG, "cloud_merge: min_count must be >= 1");
+    if (n == 0) {
+        *total = 0;
+        *n_skipped = 0;
+        return check_device(device);
+    }
+    TimedCall<MERGE_T_COUNT> c("SFMBA_CLOUD_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = cloud_merge(c.kit.stream, device, (int)n, xyz, bgr, normal, voxel, min_count, xyz_out, bgr_out, normal_out, count, first, voxel_of, cap,
+                               total, n_skipped, c.tm());
+    if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on)          // (a capacity failure has run every phase but the download)
+        std::fprintf(stderr,
+                     "[sfmba cloud_merge] upload_ms %.6f quantise_ms %.6f sort_ms %.6f runs_ms %.6f reduce_ms %.6f compact_ms %.6f finalise_ms %.6f "
+                     "download_ms %.6f points %lld voxels %lld\n",
+                     c.t[MERGE_T_UPLOAD], c.t[MERGE_T_QUANTISE], c.t[MERGE_T_SORT], c.t[MERGE_T_RUNS], c.t[MERGE_T_REDUCE], c.t[MERGE_T_COMPACT],
+                     c.t[MERGE_T_FINALISE], c.t[MERGE_T_DOWNLOAD], (long long)n, (long long)*total);
+    return unit_result(rc, "cloud_merge");
+}
+// ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------
+int sfmba_pnp_ransac(int device, int n_prob, const int64_t* prob_ptr, const float* xyz, const float* uv, const float* K, int n_hyp,
+                     float threshold_px, uint64_t seed, int max_refine_iters, double* pose, unsigned char* inlier,
+                     sfmba_pnp_result* result, double* hyp_pose, int32_t* hyp_count) {
+    if (n_prob < 0 || !prob_ptr || !K || (n_prob > 0 && (!pose || !result))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = check_ransac(n_hyp, threshold_px)) return rc;
+    if (const int rc = check_focal(K)) return rc;
+    if (max_refine_iters < 0) return fail(SFMBA_ERR_INVALID_ARG, "max_refine_iters must be >= 0");
+    if (prob_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "prob_ptr must not be negative");
+    for (int p = 0; p < n_prob; ++p) {
+        if (prob_ptr[p + 1] < prob_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "prob_ptr not monotone");
+        if (prob_ptr[p + 1] - prob_ptr[p] >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "pnp_ransac: a problem has 2^31 or more points");
+    }
+    if (prob_ptr[n_prob] > 0 && (!xyz || !uv || !inlier)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (n_prob == 0) return check_device(device);
+    TimedCall<3> c("SFMBA_PNP_TIMING");          // (tools/pnp_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = pnp_ransac(c.kit.stream, device, n_prob, prob_ptr, xyz, uv, K, n_hyp, threshold_px, seed, max_refine_iters, pose, inlier, result,
+                              hyp_pose, hyp_count, c.tm());
+    if (rc == 0 && c.on) std::fprintf(stderr, "[sfmba pnp] upload_ms %.6f kernels_ms %.6f download_ms %.6f\n", c.t[0], c.t[1], c.t[2]);
+    return unit_result(rc, "pnp_ransac", "too many problems x hypotheses for one call");
+}
+// ---- baseline pair ranking (SfMStereoUtilities::findHomographyInliers) ------------------------------------------------
+int sfmba_homography_ransac(int device, int n_images, const int64_t* img_ptr, const float* pts, int n_pairs, const int32_t* pair_left,
+                            const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx, int n_hyp,
+                            float threshold_px, uint64_t seed, double* H, unsigned char* inlier, sfmba_homography_result* result, double* hyp_H,
+                            int32_t* hyp_count) {
+    if (n_images < 0 || n_pairs < 0 || !img_ptr || !pair_ptr || (n_pairs > 0 && (!pair_left || !pair_right || !H || !result)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = check_ransac(n_hyp, threshold_px)) return rc;
+    if (const int rc = check_match_list("homography_ransac", n_images, img_ptr, pts, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx)) return rc;
+    if (pair_ptr[n_pairs] > pair_ptr[0] && !inlier) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (n_pairs == 0) return check_device(device);
+    TimedCall<5> c("SFMBA_HOMOGRAPHY_TIMING");          // (tools/homography_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = homography_ransac(c.kit.stream, device, n_images, img_ptr, pts, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx, n_hyp,
+                                     threshold_px, seed, H, inlier, result, hyp_H, hyp_count, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba homography] upload_ms %.6f hypotheses_ms %.6f score_ms %.6f select_ms %.6f download_ms %.6f\n", c.t[0], c.t[1], c.t[2],
+                     c.t[3], c.t[4]);
+    return unit_result(rc, "homography_ransac", "too many pairs x hypotheses for one call");
+}
+// ---- pose of an image pair (SfMStereoUtilities::findCameraMatricesFromMatch): same checks, same refusals, and K ---------------------
+int sfmba_essential_ransac(int device, int n_images, const int64_t* img_ptr, const float* pts, int n_pairs, const int32_t* pair_left,
+                           const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx, const float* K,
+                           int n_hyp, float threshold_px, uint64_t seed, double* E, double* pose, unsigned char* inlier,
+                           sfmba_essential_result* result, double* hyp_E, int32_t* hyp_count, int32_t* hyp_nsol) {
+    if (n_images < 0 || n_pairs < 0 || !img_ptr || !pair_ptr || !K || (n_pairs > 0 && (!pair_left || !pair_right || !E || !pose || !result)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = check_ransac(n_hyp, threshold_px)) return rc;
+    if (const int rc = check_focal(K)) return rc;
+    if (const int rc = check_match_list("essential_ransac", n_images, img_ptr, pts, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx)) return rc;
+    if (pair_ptr[n_pairs] > pair_ptr[0] && !inlier) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (n_pairs == 0) return check_device(device);
+    TimedCall<5> c("SFMBA_ESSENTIAL_TIMING");          // (tools/essential_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = essential_ransac(c.kit.stream, device, n_images, img_ptr, pts, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx, K, n_hyp,
+                                    threshold_px, seed, E, pose, inlier, result, hyp_E, hyp_count, hyp_nsol, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba essential] upload_ms %.6f hypotheses_ms %.6f score_ms %.6f select_ms %.6f download_ms %.6f\n", c.t[0], c.t[1], c.t[2],
+                     c.t[3], c.t[4]);
+    return unit_result(rc, "essential_ransac", "too many pairs x hypotheses for one call");
+}
+// ---- reading photographs (SfM::setImagesDirectory: imread + resize) ---------------------------------------------------
+int sfmba_jpeg_info(int n_images, const int64_t* file_ptr, const unsigned char* bytes, sfmba_image_info* info) {
+    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
+    if (n_images > 0 && !info) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    std::vector<JpegHeader> hdr;
+    jpeg_parse_batch(n_images, file_ptr, bytes, hdr);
+    for (int i = 0; i < n_images; ++i) jpeg_fill_info(hdr[(size_t)i], &info[i]);
+    return SFMBA_OK;
+}
+
+int sfmba_resized_size(int width, int height, float factor, int32_t* out_width, int32_t* out_height) {
+    if (!out_width || !out_height) return fail(SFMBA_ERR_INVALID_ARG, "NULL argument");
+    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "factor must be finite and > 0");
+    if (width < 1 || width > JPEG_MAX_SIDE || height < 1 || height > JPEG_MAX_SIDE) return fail(SFMBA_ERR_INVALID_ARG, "an image dimension lies outside 1..16384");
+    const int ow = resized_length(width, factor), oh = resized_length(height, factor);
+    if (ow == 0 || oh == 0) return fail(SFMBA_ERR_INVALID_ARG, "the factor gives the image a side outside 1..16384");
+    *out_width = ow; *out_height = oh;
+    return SFMBA_OK;
+}
+
+int sfmba_jpeg_decode(int device, int n_images, const int64_t* file_ptr, const unsigned char* bytes, float factor, sfmba_image_info* info,
+                      int64_t* out_ptr, unsigned char* out, int64_t cap, int64_t* total) {
+    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
+    if (cap < 0 || !out_ptr || !total || (n_images > 0 && !info) || (cap > 0 && !out)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "jpeg_decode: factor must be finite and > 0");
+    // the entropy decode runs on the host: its line has that time in front of the HIP-event times (tools/image_io_bench.py)
+    TimedCall<JPEG_T_COUNT> c("SFMBA_JPEG_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = jpeg_decode(c.kit.stream, device, n_images, file_ptr, bytes, factor, info, out_ptr, out, cap, total, c.tm());
+    if (rc == 0 && c.on) image_timing_line("jpeg_decode", c.t);
+    return unit_result(rc, "jpeg_decode");
+}
+
+int sfmba_resize_images(int device, int n_images, const int64_t* img_ptr, const unsigned char* px, const int32_t* width, const int32_t* height,
+                        int channels, float factor, int64_t* out_ptr, unsigned char* out, int64_t cap, int64_t* total) {
+    if (n_images < 0 || cap < 0 || !img_ptr || !out_ptr || !total || (n_images > 0 && (!width || !height)) || (cap > 0 && !out))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "resize_images: factor must be finite and > 0");
+    if (const int rc = check_images("resize_images", n_images, img_ptr, px, width, height, channels)) return rc;
+    for (int i = 0; i < n_images; ++i)
+        if (resized_length(width[i], factor) == 0 || resized_length(height[i], factor) == 0)
+            return fail(SFMBA_ERR_INVALID_ARG, "resize_images: the factor gives an image a side outside 1..16384");
+    TimedCall<JPEG_T_COUNT> c("SFMBA_JPEG_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = resize_images(c.kit.stream, device, n_images, img_ptr, px, width, height, channels, factor, out_ptr, out, cap, total, c.tm());
+    if (rc == 0 && c.on) image_timing_line("resize_images", c.t);
+    return unit_result(rc, "resize_images");
+}
+
+int sfmba_png_info(int n_images, const int64_t* file_ptr, const unsigned char* bytes, struct sfmba_png_info* info) {
+    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
+    if (n_images > 0 && !info) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    std::vector<PngHeader> hdr;
+    png_parse_batch(n_images, file_ptr, bytes, hdr);
+    for (int i = 0; i < n_images; ++i) png_fill_info(hdr[(size_t)i], &info[i]);
+    return SFMBA_OK;
+}
+
+int sfmba_png_decode(int device, int n_images, const int64_t* file_ptr, const unsigned char* bytes, float factor, struct sfmba_png_info* info,
+                     int64_t* out_ptr, unsigned char* out, int64_t cap, int64_t* total) {
+    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
+    if (cap < 0 || !out_ptr || !total || (n_images > 0 && !info) || (cap > 0 && !out)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "png_decode: factor must be finite and > 0");
+    // the inflate runs on the host: its line has that time in front of the HIP-event times (tools/image_io_bench.py)
+    TimedCall<PNG_T_COUNT> c("SFMBA_PNG_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = png_decode(c.kit.stream, device, n_images, file_ptr, bytes, factor, info, out_ptr, out, cap, total, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba png_decode] inflate_ms %.6f upload_ms %.6f unfilter_ms %.6f pixels_ms %.6f resize_ms %.6f download_ms %.6f groups %d\n",
+                     c.t[PNG_T_INFLATE], c.t[PNG_T_UPLOAD], c.t[PNG_T_UNFILTER], c.t[PNG_T_PIXELS], c.t[PNG_T_RESIZE], c.t[PNG_T_DOWNLOAD], (int)c.t[PNG_T_GROUPS]);
+    return unit_result(rc, "png_decode");
+}
+}  // extern "C"

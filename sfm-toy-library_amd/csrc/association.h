@@ -3,10 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unit_common.h"
+
 namespace sfmba {
 
-// return values besides 0 (ok) and positive hipError_t codes
-enum { ASSOC_ERR_CAPACITY = -1, ASSOC_ERR_TOO_LARGE = -2 };
+// return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 // Host pointers in and out; see include/sfmba.h for the meaning of the arrays.
 int assoc_find_2d3d(hipStream_t s, int device, int n_views, const unsigned char* view_done, int n_pt, const int64_t* view_ptr,

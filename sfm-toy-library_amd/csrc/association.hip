@@ -205,14 +205,11 @@ __global__ __launch_bounds__(256) void k_cand_low(long long n, const u64* __rest
     if (e < n) idx[e] = (int)(unsigned)(sorted[e] & 0xffffffffull);
 }
 
-#define AS_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define AS_ALLOC(ptr, T, n) do { ptr = scratch.alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 template <typename T>
 int upload(DeviceArena& scratch, hipStream_t s, T** d, const T* h, size_t n) {
     *d = scratch.alloc_n<T>(n);
     if (!*d) return (int)hipErrorOutOfMemory;
-    if (n) AS_TRY(hipMemcpyAsync(*d, h, sizeof(T) * n, hipMemcpyHostToDevice, s));
+    if (n) UNIT_TRY(hipMemcpyAsync(*d, h, sizeof(T) * n, hipMemcpyHostToDevice, s));
     return 0;
 }
 
@@ -232,9 +229,9 @@ int assoc_find_2d3d(hipStream_t s, int device, int n_views, const unsigned char*
     *total = 0;
     const long long n = (long long)nvs * n_pt;
     if (n == 0) return 0;
-    if (n >= INT_MAX || (long long)n_views * n_views >= INT_MAX) return ASSOC_ERR_TOO_LARGE;
+    if (n >= INT_MAX || (long long)n_views * n_views >= INT_MAX) return UNIT_ERR_TOO_LARGE;
     const long long n_match = n_pairs > 0 ? pair_ptr[n_pairs] : 0, n_ov = view_ptr[n_pt];
-    if (n_match >= INT_MAX) return ASSOC_ERR_TOO_LARGE;
+    if (n_match >= INT_MAX) return UNIT_ERR_TOO_LARGE;
     // pair table: [left][right] -> pair index; only the entries the reference consults (left <= right), first occurrence
     std::vector<int> tab((size_t)n_views * n_views, -1), pair_ok((size_t)std::max(n_pairs, 1), 0);
     for (int p = 0; p < n_pairs; ++p) {
@@ -245,7 +242,7 @@ int assoc_find_2d3d(hipStream_t s, int device, int n_views, const unsigned char*
     }
     // the probe sequence works on a 32-bit slot index (mask = 2^bits - 1, bits <= 31): more than 2^29 matches would need
     // bits >= 32, where `1u << bits` is undefined -- refuse instead
-    if (4 * n_match > (1ll << 31)) return ASSOC_ERR_TOO_LARGE;
+    if (4 * n_match > (1ll << 31)) return UNIT_ERR_TOO_LARGE;
     unsigned bits = 4;
     while ((1ull << bits) < (u64)(4 * std::max(n_match, 1ll))) ++bits;
     const unsigned mask = (1u << bits) - 1u;
@@ -264,15 +261,15 @@ int assoc_find_2d3d(hipStream_t s, int device, int n_views, const unsigned char*
     if ((rc = upload(scratch, s, &d_pptr, reinterpret_cast<const long long*>(pair_ptr), (size_t)n_pairs + 1))) return rc;
     if ((rc = upload(scratch, s, &d_q, query_idx, (size_t)n_match))) return rc;
     if ((rc = upload(scratch, s, &d_t, train_idx, (size_t)n_match))) return rc;
-    AS_ALLOC(d_keys, u64, (size_t)n_slot);
-    AS_ALLOC(d_vals, int, (size_t)n_slot);
-    AS_ALLOC(d_hit, int, (size_t)n);
-    AS_ALLOC(d_flag, int, (size_t)n);
-    AS_ALLOC(d_pos, int, (size_t)n);
-    AS_ALLOC(d_optr, long long, (size_t)nvs + 1);
+    UNIT_ALLOC(scratch, d_keys, u64, (size_t)n_slot);
+    UNIT_ALLOC(scratch, d_vals, int, (size_t)n_slot);
+    UNIT_ALLOC(scratch, d_hit, int, (size_t)n);
+    UNIT_ALLOC(scratch, d_flag, int, (size_t)n);
+    UNIT_ALLOC(scratch, d_pos, int, (size_t)n);
+    UNIT_ALLOC(scratch, d_optr, long long, (size_t)nvs + 1);
     const long long ocap = std::min<long long>(std::max<long long>(cap, 0), n);
-    AS_ALLOC(d_opt, int, (size_t)std::max<long long>(ocap, 1));
-    AS_ALLOC(d_ofe, int, (size_t)std::max<long long>(ocap, 1));
+    UNIT_ALLOC(scratch, d_opt, int, (size_t)std::max<long long>(ocap, 1));
+    UNIT_ALLOC(scratch, d_ofe, int, (size_t)std::max<long long>(ocap, 1));
 
     hipLaunchKernelGGL(k_table_clear, dim3(grid_for(n_slot)), dim3(256), 0, s, d_keys, d_vals, n_slot);
     if (n_match > 0)
@@ -280,15 +277,15 @@ int assoc_find_2d3d(hipStream_t s, int device, int n_views, const unsigned char*
     hipLaunchKernelGGL(k_find_2d3d, dim3(grid_for(n)), dim3(256), 0, s, n_views, nvs, d_nd, n_pt, d_vptr, d_vidx, d_fidx, d_tab, d_q, d_t,
                        d_keys, d_vals, mask, d_hit, d_flag);
     size_t tmp_bytes = 0;
-    AS_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_flag, d_pos, (int)n, s));
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_flag, d_pos, (int)n, s));
     void* d_tmp = scratch.alloc(tmp_bytes ? tmp_bytes : 1);
     if (!d_tmp) return (int)hipErrorOutOfMemory;
-    AS_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos, (int)n, s));
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos, (int)n, s));
     hipLaunchKernelGGL(k_find_scatter, dim3(grid_for(n)), dim3(256), 0, s, nvs, n_pt, d_hit, d_flag, d_pos, d_opt, d_ofe, d_optr, ocap);
-    AS_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     std::vector<long long> optr((size_t)nvs + 1);
-    AS_TRY(hipMemcpyAsync(optr.data(), d_optr, sizeof(long long) * optr.size(), hipMemcpyDeviceToHost, s));
-    AS_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipMemcpyAsync(optr.data(), d_optr, sizeof(long long) * optr.size(), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipStreamSynchronize(s));
     // per-view pointers in the caller's view numbering: done views get empty ranges
     const long long tot = optr[(size_t)nvs];
     *total = tot;
@@ -300,11 +297,11 @@ int assoc_find_2d3d(hipStream_t s, int device, int n_views, const unsigned char*
         }
         out_ptr[n_views] = tot;
     }
-    if (tot > cap) return ASSOC_ERR_CAPACITY;
+    if (tot > cap) return UNIT_ERR_CAPACITY;
     if (tot > 0) {
-        AS_TRY(hipMemcpyAsync(out_point, d_opt, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        AS_TRY(hipMemcpyAsync(out_feature, d_ofe, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        AS_TRY(hipStreamSynchronize(s));
+        UNIT_TRY(hipMemcpyAsync(out_point, d_opt, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(out_feature, d_ofe, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipStreamSynchronize(s));
     }
     return 0;
 }
@@ -314,79 +311,79 @@ int assoc_radius_candidates(hipStream_t s, int device, int n_exist, const float*
     for (int k = 0; k <= n_new; ++k) cand_ptr[k] = 0;
     *total = 0;
     if (n_new == 0) return 0;
-    if ((long long)n_exist + n_new >= INT_MAX / 32) return ASSOC_ERR_TOO_LARGE;
+    if ((long long)n_exist + n_new >= INT_MAX / 32) return UNIT_ERR_TOO_LARGE;
     if (!(max_dist > 0.0f)) return 0;             // norm >= 0 is never < a non-positive (or NaN) threshold
     const int n_all = n_exist + n_new;
     DeviceArena scratch(device);
     float* d_xyz;
-    AS_ALLOC(d_xyz, float, (size_t)3 * n_all);
-    if (n_exist) AS_TRY(hipMemcpyAsync(d_xyz, exist_xyz, sizeof(float) * 3 * (size_t)n_exist, hipMemcpyHostToDevice, s));
-    AS_TRY(hipMemcpyAsync(d_xyz + 3 * (size_t)n_exist, new_xyz, sizeof(float) * 3 * (size_t)n_new, hipMemcpyHostToDevice, s));
+    UNIT_ALLOC(scratch, d_xyz, float, (size_t)3 * n_all);
+    if (n_exist) UNIT_TRY(hipMemcpyAsync(d_xyz, exist_xyz, sizeof(float) * 3 * (size_t)n_exist, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_xyz + 3 * (size_t)n_exist, new_xyz, sizeof(float) * 3 * (size_t)n_new, hipMemcpyHostToDevice, s));
     // cell edge a hair above the threshold: a pair that passes the float-difference test has a true coordinate difference
     // below max_dist (1 + 2^-24), so its cells differ by at most one along every axis (association)
     const double cell = (double)max_dist * (1.0 + 1.0 / 524288.0);
     const double inv_cell = 1.0 / cell;
     u64 *d_k0, *d_k1, *d_total;
     int *d_i0, *d_i1;
-    AS_ALLOC(d_k0, u64, (size_t)n_all); AS_ALLOC(d_k1, u64, (size_t)n_all);
-    AS_ALLOC(d_i0, int, (size_t)n_all); AS_ALLOC(d_i1, int, (size_t)n_all);
-    AS_ALLOC(d_total, u64, 1);
+    UNIT_ALLOC(scratch, d_k0, u64, (size_t)n_all); UNIT_ALLOC(scratch, d_k1, u64, (size_t)n_all);
+    UNIT_ALLOC(scratch, d_i0, int, (size_t)n_all); UNIT_ALLOC(scratch, d_i1, int, (size_t)n_all);
+    UNIT_ALLOC(scratch, d_total, u64, 1);
     hipLaunchKernelGGL(k_cell_keys, dim3(grid_for(n_all)), dim3(256), 0, s, n_all, d_xyz, inv_cell, d_k0, d_i0);
     size_t tmp_bytes = 0;
-    AS_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_k0, d_k1, d_i0, d_i1, n_all, 0, 64, s));
+    UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_k0, d_k1, d_i0, d_i1, n_all, 0, 64, s));
     void* d_tmp = scratch.alloc(tmp_bytes ? tmp_bytes : 1);
     if (!d_tmp) return (int)hipErrorOutOfMemory;
-    AS_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k0, d_k1, d_i0, d_i1, n_all, 0, 64, s));
-    AS_TRY(hipMemsetAsync(d_total, 0, sizeof(u64), s));
+    UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k0, d_k1, d_i0, d_i1, n_all, 0, 64, s));
+    UNIT_TRY(hipMemsetAsync(d_total, 0, sizeof(u64), s));
     const long long n_probe = (long long)n_new * 27;
     hipLaunchKernelGGL(k_radius_probe<true>, dim3(grid_for(n_probe)), dim3(256), 0, s, n_exist, n_new, d_xyz, inv_cell, (double)max_dist, n_all,
                        d_k1, d_i1, d_total, (u64*)nullptr, 0ull);
-    AS_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     u64 h_total = 0;
-    AS_TRY(hipMemcpyAsync(&h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
-    AS_TRY(hipStreamSynchronize(s));
-    if (h_total >= (u64)INT_MAX) return ASSOC_ERR_TOO_LARGE;
+    UNIT_TRY(hipMemcpyAsync(&h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipStreamSynchronize(s));
+    if (h_total >= (u64)INT_MAX) return UNIT_ERR_TOO_LARGE;
     long long n_cand = (long long)h_total;
     long long* d_ptr;
-    AS_ALLOC(d_ptr, long long, (size_t)n_new + 1);
+    UNIT_ALLOC(scratch, d_ptr, long long, (size_t)n_new + 1);
     u64* d_sorted = nullptr;
     if (n_cand > 0) {
         u64 *d_c0, *d_c1;
-        AS_ALLOC(d_c0, u64, (size_t)n_cand); AS_ALLOC(d_c1, u64, (size_t)n_cand);
-        AS_TRY(hipMemsetAsync(d_total, 0, sizeof(u64), s));
+        UNIT_ALLOC(scratch, d_c0, u64, (size_t)n_cand); UNIT_ALLOC(scratch, d_c1, u64, (size_t)n_cand);
+        UNIT_TRY(hipMemsetAsync(d_total, 0, sizeof(u64), s));
         hipLaunchKernelGGL(k_radius_probe<false>, dim3(grid_for(n_probe)), dim3(256), 0, s, n_exist, n_new, d_xyz, inv_cell, (double)max_dist, n_all,
                            d_k1, d_i1, d_total, d_c0, (u64)n_cand);
         size_t sb = 0;
-        AS_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, sb, d_c0, d_c1, (int)n_cand, 0, 64, s));
+        UNIT_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, sb, d_c0, d_c1, (int)n_cand, 0, 64, s));
         void* st = scratch.alloc(sb ? sb : 1);
         if (!st) return (int)hipErrorOutOfMemory;
-        AS_TRY(hipcub::DeviceRadixSort::SortKeys(st, sb, d_c0, d_c1, (int)n_cand, 0, 64, s));
+        UNIT_TRY(hipcub::DeviceRadixSort::SortKeys(st, sb, d_c0, d_c1, (int)n_cand, 0, 64, s));
         // duplicates can only come from two neighbour cells colliding in the hashed key range: removed here
         long long* d_nsel;
-        AS_ALLOC(d_nsel, long long, 1);
+        UNIT_ALLOC(scratch, d_nsel, long long, 1);
         size_t ub = 0;
-        AS_TRY(hipcub::DeviceSelect::Unique(nullptr, ub, d_c1, d_c0, d_nsel, (int)n_cand, s));
+        UNIT_TRY(hipcub::DeviceSelect::Unique(nullptr, ub, d_c1, d_c0, d_nsel, (int)n_cand, s));
         void* ut = scratch.alloc(ub ? ub : 1);
         if (!ut) return (int)hipErrorOutOfMemory;
-        AS_TRY(hipcub::DeviceSelect::Unique(ut, ub, d_c1, d_c0, d_nsel, (int)n_cand, s));
+        UNIT_TRY(hipcub::DeviceSelect::Unique(ut, ub, d_c1, d_c0, d_nsel, (int)n_cand, s));
         long long nsel = 0;
-        AS_TRY(hipMemcpyAsync(&nsel, d_nsel, sizeof(long long), hipMemcpyDeviceToHost, s));
-        AS_TRY(hipStreamSynchronize(s));
+        UNIT_TRY(hipMemcpyAsync(&nsel, d_nsel, sizeof(long long), hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipStreamSynchronize(s));
         n_cand = nsel;
         d_sorted = d_c0;
     }
     hipLaunchKernelGGL(k_cand_ptr, dim3(grid_for(n_new + 1)), dim3(256), 0, s, n_new, n_cand, d_sorted, d_ptr);
-    AS_TRY(hipGetLastError());
-    AS_TRY(hipMemcpyAsync(cand_ptr, d_ptr, sizeof(long long) * ((size_t)n_new + 1), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipGetLastError());
+    UNIT_TRY(hipMemcpyAsync(cand_ptr, d_ptr, sizeof(long long) * ((size_t)n_new + 1), hipMemcpyDeviceToHost, s));
     *total = n_cand;
-    if (n_cand > cap) { AS_TRY(hipStreamSynchronize(s)); return ASSOC_ERR_CAPACITY; }
+    if (n_cand > cap) { UNIT_TRY(hipStreamSynchronize(s)); return UNIT_ERR_CAPACITY; }
     if (n_cand > 0) {
         int* d_low;
-        AS_ALLOC(d_low, int, (size_t)n_cand);
+        UNIT_ALLOC(scratch, d_low, int, (size_t)n_cand);
         hipLaunchKernelGGL(k_cand_low, dim3(grid_for(n_cand)), dim3(256), 0, s, n_cand, d_sorted, d_low);
-        AS_TRY(hipMemcpyAsync(cand_idx, d_low, sizeof(int) * (size_t)n_cand, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(cand_idx, d_low, sizeof(int) * (size_t)n_cand, hipMemcpyDeviceToHost, s));
     }
-    AS_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipStreamSynchronize(s));
     return 0;
 }
 

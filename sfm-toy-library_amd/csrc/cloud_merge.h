@@ -4,12 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unit_common.h"
+
 #include "../../include/sfmba.h"
 
 namespace sfmba {
 
-// return values besides 0 (ok) and positive hipError_t codes
-enum { CLOUD_ERR_CAPACITY = -1 };
+// return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 // a run of the sorted order with more members than this is reduced by a whole wave, a shorter one by a single lane
 constexpr int CLOUD_SHORT_RUN = 32;

@@ -23,7 +23,6 @@
 #include "cloud_math.h"
 #include "ba_kernels.h"    // sort_pairs_u64
 #include "device_arena.h"
-#include "jpeg_decode.h"   // PhaseTimer
 
 #include <hipcub/hipcub.hpp>
 
@@ -192,9 +191,6 @@ __global__ __launch_bounds__(LANES) void k_cloud_finalise(int n_runs, const int*
     first[o] = is[beg];
 }
 
-#define CLOUD_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define CLOUD_ALLOC(arena, ptr, T, n) do { ptr = (arena).alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 unsigned blocks_for(long long n) { return (unsigned)((n + LANES - 1) / LANES); }
 
 }  // namespace
@@ -223,15 +219,15 @@ int depth_normals(hipStream_t s, int device, int n_images, const int32_t* width,
     DeviceArena scratch(device);
     NormalImage* d_tab;
     float *d_maps, *d_normal;
-    CLOUD_ALLOC(scratch, d_tab, NormalImage, tab.size());
-    CLOUD_ALLOC(scratch, d_maps, float, (size_t)n_dom);
-    CLOUD_ALLOC(scratch, d_normal, float, (size_t)n_dom * 3);
+    UNIT_ALLOC(scratch, d_tab, NormalImage, tab.size());
+    UNIT_ALLOC(scratch, d_maps, float, (size_t)n_dom);
+    UNIT_ALLOC(scratch, d_normal, float, (size_t)n_dom * 3);
 
     tm.begin(NORMALS_T_UPLOAD);
-    CLOUD_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(NormalImage) * tab.size(), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(NormalImage) * tab.size(), hipMemcpyHostToDevice, s));
     for (int i = 0; i < n_images; ++i)
         if (depth[i])
-            CLOUD_TRY(hipMemcpyAsync(d_maps + tab[(size_t)i].off, depth[i], sizeof(float) * (size_t)width[i] * height[i], hipMemcpyHostToDevice, s));
+            UNIT_TRY(hipMemcpyAsync(d_maps + tab[(size_t)i].off, depth[i], sizeof(float) * (size_t)width[i] * height[i], hipMemcpyHostToDevice, s));
     tm.end();
 
     NormalParams prm;
@@ -239,15 +235,15 @@ int depth_normals(hipStream_t s, int device, int n_images, const int32_t* width,
     prm.max_rel_step = (double)max_rel_step;
     tm.begin(NORMALS_T_KERNEL);
     hipLaunchKernelGGL(k_depth_normals, dim3(blocks_for(max_px), (unsigned)n_images), dim3(LANES), 0, s, d_tab, prm, d_maps, d_normal);
-    CLOUD_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     tm.end();
     tm.begin(NORMALS_T_DOWNLOAD);
     for (int i = 0; i < n_images; ++i)
         if (depth[i])
-            CLOUD_TRY(hipMemcpyAsync(normal[i], d_normal + 3 * tab[(size_t)i].off, sizeof(float) * 3 * (size_t)width[i] * height[i],
+            UNIT_TRY(hipMemcpyAsync(normal[i], d_normal + 3 * tab[(size_t)i].off, sizeof(float) * 3 * (size_t)width[i] * height[i],
                                      hipMemcpyDeviceToHost, s));
     tm.end();
-    CLOUD_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipStreamSynchronize(s));
     if (timing) tm.collect(timing);
     return 0;
 }
@@ -267,37 +263,37 @@ int cloud_merge(hipStream_t s, int device, int n, const float* xyz, const unsign
     unsigned char* d_bgr = nullptr;
     u64 *d_k0, *d_k1;
     int *d_i0, *d_i1, *d_head, *d_rank, *d_start, *d_info;
-    CLOUD_ALLOC(scratch, d_xyz, float, N * 3);
-    if (bgr) CLOUD_ALLOC(scratch, d_bgr, unsigned char, N * 3);
-    if (normal) CLOUD_ALLOC(scratch, d_normal, float, N * 3);
-    CLOUD_ALLOC(scratch, d_k0, u64, N);
-    CLOUD_ALLOC(scratch, d_k1, u64, N);
-    CLOUD_ALLOC(scratch, d_i0, int, N);
-    CLOUD_ALLOC(scratch, d_i1, int, N);
-    CLOUD_ALLOC(scratch, d_head, int, N + 1);                 // voxel_of reuses it once the runs are known
-    CLOUD_ALLOC(scratch, d_rank, int, N + 1);
-    CLOUD_ALLOC(scratch, d_start, int, N + 1);
-    CLOUD_ALLOC(scratch, d_info, int, 4);                     // n_runs, n_valid, n_long: zero as handed out
+    UNIT_ALLOC(scratch, d_xyz, float, N * 3);
+    if (bgr) UNIT_ALLOC(scratch, d_bgr, unsigned char, N * 3);
+    if (normal) UNIT_ALLOC(scratch, d_normal, float, N * 3);
+    UNIT_ALLOC(scratch, d_k0, u64, N);
+    UNIT_ALLOC(scratch, d_k1, u64, N);
+    UNIT_ALLOC(scratch, d_i0, int, N);
+    UNIT_ALLOC(scratch, d_i1, int, N);
+    UNIT_ALLOC(scratch, d_head, int, N + 1);                 // voxel_of reuses it once the runs are known
+    UNIT_ALLOC(scratch, d_rank, int, N + 1);
+    UNIT_ALLOC(scratch, d_start, int, N + 1);
+    UNIT_ALLOC(scratch, d_info, int, 4);                     // n_runs, n_valid, n_long: zero as handed out
     size_t sort_bytes = 0, scan_a = 0, scan_b = 0;
     // every bit of a key is significant: an index carries the bias 2^20 in its field, and the key of a skipped point has bit 63
     const int end_bit = 64;
     if (int rc = sort_pairs_u64(s, nullptr, &sort_bytes, d_k0, d_k1, d_i0, d_i1, (unsigned)n, end_bit)) return rc;
-    CLOUD_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_a, d_head, d_rank, n, s));
-    CLOUD_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, d_head, d_rank, n + 1, s));
+    UNIT_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_a, d_head, d_rank, n, s));
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, d_head, d_rank, n + 1, s));
     const size_t tmp_bytes = std::max(std::max(sort_bytes, scan_a), std::max(scan_b, (size_t)1));
     void* d_tmp = scratch.alloc(tmp_bytes);
     if (!d_tmp) return (int)hipErrorOutOfMemory;
 
     tm.begin(MERGE_T_UPLOAD);
-    CLOUD_TRY(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * N * 3, hipMemcpyHostToDevice, s));
-    if (bgr) CLOUD_TRY(hipMemcpyAsync(d_bgr, bgr, N * 3, hipMemcpyHostToDevice, s));
-    if (normal) CLOUD_TRY(hipMemcpyAsync(d_normal, normal, sizeof(float) * N * 3, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * N * 3, hipMemcpyHostToDevice, s));
+    if (bgr) UNIT_TRY(hipMemcpyAsync(d_bgr, bgr, N * 3, hipMemcpyHostToDevice, s));
+    if (normal) UNIT_TRY(hipMemcpyAsync(d_normal, normal, sizeof(float) * N * 3, hipMemcpyHostToDevice, s));
     tm.end();
 
     const double vox = (double)voxel;
     tm.begin(MERGE_T_QUANTISE);
     hipLaunchKernelGGL(k_cloud_keys, dim3(blocks_for(n)), dim3(LANES), 0, s, n, d_xyz, vox, d_k0, d_i0);
-    CLOUD_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     tm.end();
     tm.begin(MERGE_T_SORT);
     {
@@ -309,16 +305,16 @@ int cloud_merge(hipStream_t s, int device, int n, const float* xyz, const unsign
     const int* is = d_i1;
     tm.begin(MERGE_T_RUNS);
     hipLaunchKernelGGL(k_cloud_heads, dim3(blocks_for(n)), dim3(LANES), 0, s, n, ks, d_head);
-    CLOUD_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     {
         size_t bytes = scan_a;
-        CLOUD_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, bytes, d_head, d_rank, n, s));
+        UNIT_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, bytes, d_head, d_rank, n, s));
     }
     hipLaunchKernelGGL(k_cloud_starts, dim3(blocks_for(n)), dim3(LANES), 0, s, n, ks, d_head, d_rank, d_start, d_info);
-    CLOUD_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     int info[2] = { 0, 0 };
-    CLOUD_TRY(hipMemcpyAsync(info, d_info, sizeof(info), hipMemcpyDeviceToHost, s));
-    CLOUD_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipMemcpyAsync(info, d_info, sizeof(info), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipStreamSynchronize(s));
     tm.end();
     const int n_runs = info[0], n_valid = info[1];
     *n_skipped = (int64_t)n - n_valid;
@@ -333,67 +329,67 @@ int cloud_merge(hipStream_t s, int device, int n, const float* xyz, const unsign
     sums.stride = n_runs;
     sums.m = nullptr;
     sums.b = nullptr;
-    CLOUD_ALLOC(scratch, sums.q, long long, R * 3);
-    if (normal) CLOUD_ALLOC(scratch, sums.m, long long, R * 3);
-    if (bgr) CLOUD_ALLOC(scratch, sums.b, long long, R * 3);
+    UNIT_ALLOC(scratch, sums.q, long long, R * 3);
+    if (normal) UNIT_ALLOC(scratch, sums.m, long long, R * 3);
+    if (bgr) UNIT_ALLOC(scratch, sums.b, long long, R * 3);
     const int long_cap = n_valid / (CLOUD_SHORT_RUN + 1) + 1;
     int *d_long, *d_keep, *d_pos;
-    CLOUD_ALLOC(scratch, d_long, int, (size_t)long_cap);
-    CLOUD_ALLOC(scratch, d_keep, int, R + 1);                 // zeroed: the last flag stays 0
-    CLOUD_ALLOC(scratch, d_pos, int, R + 1);
+    UNIT_ALLOC(scratch, d_long, int, (size_t)long_cap);
+    UNIT_ALLOC(scratch, d_keep, int, R + 1);                 // zeroed: the last flag stays 0
+    UNIT_ALLOC(scratch, d_pos, int, R + 1);
     const MergeIn in{ d_xyz, d_bgr, d_normal, vox };
 
     tm.begin(MERGE_T_REDUCE);
     hipLaunchKernelGGL(k_cloud_reduce_short, dim3(blocks_for(n_runs)), dim3(LANES), 0, s, n_runs, d_start, is, in, sums, d_long, long_cap, d_info + 2);
-    CLOUD_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     if (n_valid > CLOUD_SHORT_RUN) {
         const unsigned grid = (unsigned)std::min<long long>(LONG_BLOCKS, ((long long)long_cap + LANES / WAVE - 1) / (LANES / WAVE));
         hipLaunchKernelGGL(k_cloud_reduce_long, dim3(grid), dim3(LANES), 0, s, d_start, is, in, sums, d_long, long_cap, d_info + 2);
-        CLOUD_TRY(hipGetLastError());
+        UNIT_TRY(hipGetLastError());
     }
     tm.end();
     tm.begin(MERGE_T_COMPACT);
     hipLaunchKernelGGL(k_cloud_keep, dim3(blocks_for(n_runs)), dim3(LANES), 0, s, n_runs, d_start, min_count, d_keep);
-    CLOUD_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     {
         size_t bytes = scan_b;                                // sized for n + 1 >= n_runs + 1 items
-        CLOUD_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, d_keep, d_pos, n_runs + 1, s));
+        UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, d_keep, d_pos, n_runs + 1, s));
     }
     int tot = 0;
-    CLOUD_TRY(hipMemcpyAsync(&tot, d_pos + n_runs, sizeof(int), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipMemcpyAsync(&tot, d_pos + n_runs, sizeof(int), hipMemcpyDeviceToHost, s));
     if (voxel_of) {
         int* d_vox = d_head;                                  // the head flags are spent
         hipLaunchKernelGGL(k_cloud_voxel_of, dim3(blocks_for(n)), dim3(LANES), 0, s, n, n_valid, is, d_rank, d_keep, d_pos, d_vox);
-        CLOUD_TRY(hipGetLastError());
-        CLOUD_TRY(hipMemcpyAsync(voxel_of, d_vox, sizeof(int) * N, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipGetLastError());
+        UNIT_TRY(hipMemcpyAsync(voxel_of, d_vox, sizeof(int) * N, hipMemcpyDeviceToHost, s));
     }
-    CLOUD_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipStreamSynchronize(s));
     tm.end();
     *total = tot;
-    if (tot > cap) return CLOUD_ERR_CAPACITY;
+    if (tot > cap) return UNIT_ERR_CAPACITY;
     if (tot > 0) {
         const size_t T = (size_t)tot;
         float *d_oxyz, *d_onrm = nullptr;
         unsigned char* d_obgr = nullptr;
         int *d_count, *d_first;
-        CLOUD_ALLOC(scratch, d_oxyz, float, T * 3);
-        if (bgr) CLOUD_ALLOC(scratch, d_obgr, unsigned char, T * 3);
-        if (normal) CLOUD_ALLOC(scratch, d_onrm, float, T * 3);
-        CLOUD_ALLOC(scratch, d_count, int, T);
-        CLOUD_ALLOC(scratch, d_first, int, T);
+        UNIT_ALLOC(scratch, d_oxyz, float, T * 3);
+        if (bgr) UNIT_ALLOC(scratch, d_obgr, unsigned char, T * 3);
+        if (normal) UNIT_ALLOC(scratch, d_onrm, float, T * 3);
+        UNIT_ALLOC(scratch, d_count, int, T);
+        UNIT_ALLOC(scratch, d_first, int, T);
         tm.begin(MERGE_T_FINALISE);
         hipLaunchKernelGGL(k_cloud_finalise, dim3(blocks_for(n_runs)), dim3(LANES), 0, s, n_runs, d_start, is, d_keep, d_pos, sums, vox, d_oxyz, d_obgr,
                            d_onrm, d_count, d_first);
-        CLOUD_TRY(hipGetLastError());
+        UNIT_TRY(hipGetLastError());
         tm.end();
         tm.begin(MERGE_T_DOWNLOAD);
-        CLOUD_TRY(hipMemcpyAsync(xyz_out, d_oxyz, sizeof(float) * T * 3, hipMemcpyDeviceToHost, s));
-        if (bgr && bgr_out) CLOUD_TRY(hipMemcpyAsync(bgr_out, d_obgr, T * 3, hipMemcpyDeviceToHost, s));
-        if (normal && normal_out) CLOUD_TRY(hipMemcpyAsync(normal_out, d_onrm, sizeof(float) * T * 3, hipMemcpyDeviceToHost, s));
-        CLOUD_TRY(hipMemcpyAsync(count, d_count, sizeof(int) * T, hipMemcpyDeviceToHost, s));
-        CLOUD_TRY(hipMemcpyAsync(first, d_first, sizeof(int) * T, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(xyz_out, d_oxyz, sizeof(float) * T * 3, hipMemcpyDeviceToHost, s));
+        if (bgr && bgr_out) UNIT_TRY(hipMemcpyAsync(bgr_out, d_obgr, T * 3, hipMemcpyDeviceToHost, s));
+        if (normal && normal_out) UNIT_TRY(hipMemcpyAsync(normal_out, d_onrm, sizeof(float) * T * 3, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(count, d_count, sizeof(int) * T, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(first, d_first, sizeof(int) * T, hipMemcpyDeviceToHost, s));
         tm.end();
-        CLOUD_TRY(hipStreamSynchronize(s));
+        UNIT_TRY(hipStreamSynchronize(s));
     }
     if (timing) tm.collect(timing);
     return 0;

@@ -4,12 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unit_common.h"
+
 #include "../../include/sfmba.h"
 
 namespace sfmba {
 
-// return values besides 0 (ok) and positive hipError_t codes
-enum { DEPTH_ERR_CAPACITY = -1 };
+// return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 // Jobs go to the device in consecutive groups.  A group's arrays (the pixels of the images its jobs name, their gray planes, the
 // three output maps) stay within this bound; a job that exceeds it alone forms a group of its own.

@@ -19,7 +19,6 @@
 #include "depth_sweep.h"
 #include "depth_math.h"
 #include "device_arena.h"
-#include "jpeg_decode.h"   // PhaseTimer
 
 #include <hipcub/hipcub.hpp>
 
@@ -222,9 +221,6 @@ __global__ void k_fuse_ptr(const FuseImage* __restrict__ tab, int n_images, long
     pt_ptr[i] = pos[i < n_images ? tab[i].dom_off : n_dom];
 }
 
-#define DEPTH_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define DEPTH_ALLOC(arena, ptr, T, n) do { ptr = (arena).alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 long long align64(long long n) { return (n + 63) & ~63ll; }
 
 template <int R>
@@ -309,16 +305,16 @@ int depth_sweep(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
         unsigned char *d_raw = nullptr, *d_gray;
         float *d_depth, *d_score;
         int16_t* d_plane;
-        DEPTH_ALLOC(scratch, d_tab, DepthJob, (size_t)nj);
-        DEPTH_ALLOC(scratch, d_gtab, GrayJob, used.size());
-        DEPTH_ALLOC(scratch, d_gray, unsigned char, (size_t)gray_bytes);
-        if (channels == 3) DEPTH_ALLOC(scratch, d_raw, unsigned char, (size_t)raw_bytes);
-        DEPTH_ALLOC(scratch, d_depth, float, (size_t)out_px);
-        DEPTH_ALLOC(scratch, d_score, float, (size_t)out_px);
-        DEPTH_ALLOC(scratch, d_plane, int16_t, (size_t)out_px);
+        UNIT_ALLOC(scratch, d_tab, DepthJob, (size_t)nj);
+        UNIT_ALLOC(scratch, d_gtab, GrayJob, used.size());
+        UNIT_ALLOC(scratch, d_gray, unsigned char, (size_t)gray_bytes);
+        if (channels == 3) UNIT_ALLOC(scratch, d_raw, unsigned char, (size_t)raw_bytes);
+        UNIT_ALLOC(scratch, d_depth, float, (size_t)out_px);
+        UNIT_ALLOC(scratch, d_score, float, (size_t)out_px);
+        UNIT_ALLOC(scratch, d_plane, int16_t, (size_t)out_px);
 
         tm.begin(DEPTH_T_UPLOAD);
-        DEPTH_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(DepthJob) * tab.size(), hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(DepthJob) * tab.size(), hipMemcpyHostToDevice, s));
         std::vector<GrayJob> gtab(used.size());
         long long raw_at = 0, max_px = 0;
         for (size_t q = 0; q < used.size(); ++q) {
@@ -327,19 +323,19 @@ int depth_sweep(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
             gtab[q] = GrayJob{ raw_at, slot[(size_t)i], px };
             max_px = std::max(max_px, px);
             if (channels == 3) {
-                DEPTH_TRY(hipMemcpyAsync(d_raw + raw_at, pixels + img_ptr[i], (size_t)px * 3, hipMemcpyHostToDevice, s));
+                UNIT_TRY(hipMemcpyAsync(d_raw + raw_at, pixels + img_ptr[i], (size_t)px * 3, hipMemcpyHostToDevice, s));
                 raw_at += align64(px * 3);
             } else {
-                DEPTH_TRY(hipMemcpyAsync(d_gray + slot[(size_t)i], pixels + img_ptr[i], (size_t)px, hipMemcpyHostToDevice, s));
+                UNIT_TRY(hipMemcpyAsync(d_gray + slot[(size_t)i], pixels + img_ptr[i], (size_t)px, hipMemcpyHostToDevice, s));
             }
         }
-        if (channels == 3) DEPTH_TRY(hipMemcpyAsync(d_gtab, gtab.data(), sizeof(GrayJob) * gtab.size(), hipMemcpyHostToDevice, s));
+        if (channels == 3) UNIT_TRY(hipMemcpyAsync(d_gtab, gtab.data(), sizeof(GrayJob) * gtab.size(), hipMemcpyHostToDevice, s));
         tm.end();
         if (channels == 3) {
             tm.begin(DEPTH_T_GRAY);
             const unsigned gx = (unsigned)std::min<long long>((max_px + LANES - 1) / LANES, 4096);
             hipLaunchKernelGGL(k_depth_gray, dim3(gx, (unsigned)used.size()), dim3(LANES), 0, s, d_gtab, d_raw, d_gray);
-            DEPTH_TRY(hipGetLastError());
+            UNIT_TRY(hipGetLastError());
             tm.end();
         }
         tm.begin(DEPTH_T_SWEEP);
@@ -351,15 +347,15 @@ int depth_sweep(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
         case 3: launch_sweep<3>(s, tiles, (unsigned)nj, d_tab, d_gray, n_planes, min_std, ms, min_sources, d_depth, d_score, d_plane); break;
         default: launch_sweep<4>(s, tiles, (unsigned)nj, d_tab, d_gray, n_planes, min_std, ms, min_sources, d_depth, d_score, d_plane); break;
         }
-        DEPTH_TRY(hipGetLastError());
+        UNIT_TRY(hipGetLastError());
         tm.end();
         tm.begin(DEPTH_T_DOWNLOAD);
         const size_t at = (size_t)out_off[(size_t)j0];
-        DEPTH_TRY(hipMemcpyAsync(depth + at, d_depth, sizeof(float) * (size_t)out_px, hipMemcpyDeviceToHost, s));
-        DEPTH_TRY(hipMemcpyAsync(score + at, d_score, sizeof(float) * (size_t)out_px, hipMemcpyDeviceToHost, s));
-        if (plane) DEPTH_TRY(hipMemcpyAsync(plane + at, d_plane, sizeof(int16_t) * (size_t)out_px, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(depth + at, d_depth, sizeof(float) * (size_t)out_px, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(score + at, d_score, sizeof(float) * (size_t)out_px, hipMemcpyDeviceToHost, s));
+        if (plane) UNIT_TRY(hipMemcpyAsync(plane + at, d_plane, sizeof(int16_t) * (size_t)out_px, hipMemcpyDeviceToHost, s));
         tm.end();
-        DEPTH_TRY(hipStreamSynchronize(s));                    // the group's arena goes back to the cache below
+        UNIT_TRY(hipStreamSynchronize(s));                    // the group's arena goes back to the cache below
         j0 = j1;
     }
     if (timing) {
@@ -406,24 +402,24 @@ int depth_fuse(hipStream_t s, int device, int n_images, const int64_t* img_ptr, 
     unsigned char* d_raw;
     int *d_flag, *d_pos;
     long long* d_ptr;
-    DEPTH_ALLOC(scratch, d_tab, FuseImage, tab.size());
-    DEPTH_ALLOC(scratch, d_maps, float, (size_t)n_dom);
-    DEPTH_ALLOC(scratch, d_raw, unsigned char, (size_t)raw_bytes);
-    DEPTH_ALLOC(scratch, d_flag, int, (size_t)n_dom + 1);     // handed out zeroed: the last flag stays 0
-    DEPTH_ALLOC(scratch, d_pos, int, (size_t)n_dom + 1);
-    DEPTH_ALLOC(scratch, d_ptr, long long, (size_t)n_images + 1);
+    UNIT_ALLOC(scratch, d_tab, FuseImage, tab.size());
+    UNIT_ALLOC(scratch, d_maps, float, (size_t)n_dom);
+    UNIT_ALLOC(scratch, d_raw, unsigned char, (size_t)raw_bytes);
+    UNIT_ALLOC(scratch, d_flag, int, (size_t)n_dom + 1);     // handed out zeroed: the last flag stays 0
+    UNIT_ALLOC(scratch, d_pos, int, (size_t)n_dom + 1);
+    UNIT_ALLOC(scratch, d_ptr, long long, (size_t)n_images + 1);
     size_t tmp_bytes = 0;
-    DEPTH_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_flag, d_pos, (int)(n_dom + 1), s));
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_flag, d_pos, (int)(n_dom + 1), s));
     void* d_tmp = scratch.alloc(std::max(tmp_bytes, (size_t)1));
     if (!d_tmp) return (int)hipErrorOutOfMemory;
 
     tm.begin(FUSE_T_UPLOAD);
-    DEPTH_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(FuseImage) * tab.size(), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(FuseImage) * tab.size(), hipMemcpyHostToDevice, s));
     for (int i = 0; i < n_images; ++i) {
         if (!depth[i]) continue;
         const size_t px = (size_t)width[i] * height[i];
-        DEPTH_TRY(hipMemcpyAsync(d_maps + tab[(size_t)i].depth_off, depth[i], sizeof(float) * px, hipMemcpyHostToDevice, s));
-        DEPTH_TRY(hipMemcpyAsync(d_raw + tab[(size_t)i].raw_off, pixels + img_ptr[i], px * channels, hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_maps + tab[(size_t)i].depth_off, depth[i], sizeof(float) * px, hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_raw + tab[(size_t)i].raw_off, pixels + img_ptr[i], px * channels, hipMemcpyHostToDevice, s));
     }
     tm.end();
 
@@ -435,38 +431,38 @@ int depth_fuse(hipStream_t s, int device, int n_images, const int64_t* img_ptr, 
     const dim3 grid((unsigned)((max_px + LANES - 1) / LANES), (unsigned)n_images);
     tm.begin(FUSE_T_FLAG);
     hipLaunchKernelGGL(k_fuse_flag, grid, dim3(LANES), 0, s, d_tab, prm, d_maps, d_flag);
-    DEPTH_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     tm.end();
     tm.begin(FUSE_T_SCAN);
-    DEPTH_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos, (int)(n_dom + 1), s));
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos, (int)(n_dom + 1), s));
     hipLaunchKernelGGL(k_fuse_ptr, dim3((unsigned)((n_images + 1 + LANES - 1) / LANES)), dim3(LANES), 0, s, d_tab, n_images, n_dom, d_pos, d_ptr);
-    DEPTH_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     static_assert(sizeof(long long) == sizeof(int64_t), "pt_ptr leaves as it is");
-    DEPTH_TRY(hipMemcpyAsync(pt_ptr, d_ptr, sizeof(int64_t) * ((size_t)n_images + 1), hipMemcpyDeviceToHost, s));
-    DEPTH_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipMemcpyAsync(pt_ptr, d_ptr, sizeof(int64_t) * ((size_t)n_images + 1), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipStreamSynchronize(s));
     tm.end();
     const long long tot = pt_ptr[n_images];
     *total = tot;
-    if (tot > cap) return DEPTH_ERR_CAPACITY;
+    if (tot > cap) return UNIT_ERR_CAPACITY;
     if (tot > 0) {
         float* d_xyz;
         unsigned char* d_bgr;
         int *d_img, *d_pix;
-        DEPTH_ALLOC(scratch, d_xyz, float, (size_t)tot * 3);
-        DEPTH_ALLOC(scratch, d_bgr, unsigned char, (size_t)tot * 3);
-        DEPTH_ALLOC(scratch, d_img, int, (size_t)tot);
-        DEPTH_ALLOC(scratch, d_pix, int, (size_t)tot);
+        UNIT_ALLOC(scratch, d_xyz, float, (size_t)tot * 3);
+        UNIT_ALLOC(scratch, d_bgr, unsigned char, (size_t)tot * 3);
+        UNIT_ALLOC(scratch, d_img, int, (size_t)tot);
+        UNIT_ALLOC(scratch, d_pix, int, (size_t)tot);
         tm.begin(FUSE_T_EMIT);
         hipLaunchKernelGGL(k_fuse_emit, grid, dim3(LANES), 0, s, d_tab, prm, d_maps, d_raw, d_flag, d_pos, d_xyz, d_bgr, d_img, d_pix);
-        DEPTH_TRY(hipGetLastError());
+        UNIT_TRY(hipGetLastError());
         tm.end();
         tm.begin(FUSE_T_DOWNLOAD);
-        DEPTH_TRY(hipMemcpyAsync(xyz, d_xyz, sizeof(float) * (size_t)tot * 3, hipMemcpyDeviceToHost, s));
-        DEPTH_TRY(hipMemcpyAsync(bgr, d_bgr, (size_t)tot * 3, hipMemcpyDeviceToHost, s));
-        DEPTH_TRY(hipMemcpyAsync(src_image, d_img, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        DEPTH_TRY(hipMemcpyAsync(src_pixel, d_pix, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(xyz, d_xyz, sizeof(float) * (size_t)tot * 3, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(bgr, d_bgr, (size_t)tot * 3, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(src_image, d_img, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(src_pixel, d_pix, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
         tm.end();
-        DEPTH_TRY(hipStreamSynchronize(s));
+        UNIT_TRY(hipStreamSynchronize(s));
     }
     if (timing) tm.collect(timing);
     return 0;

@@ -3,12 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unit_common.h"
+
 #include "../../include/sfmba.h"
 
 namespace sfmba {
 
-// return values besides 0 (ok) and positive hipError_t codes
-enum { ESS_ERR_TOO_LARGE = -1 };
+// return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 constexpr int ESS_HYP_THREADS = 64;          // hypotheses: one lane each, one wave per block; the lanes' work areas fill 100 KiB of LDS
 constexpr int ESS_TILE = 64;                 // hypotheses per score block: one per lane of a wave

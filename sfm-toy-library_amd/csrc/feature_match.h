@@ -3,10 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unit_common.h"
+
 namespace sfmba {
 
-// return values besides 0 (ok) and positive hipError_t codes
-enum { MATCH_ERR_CAPACITY = -1 };
+// return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 // Scratch for the per-slice top-2 keys of one batch (8 bytes per query row and slice): the pair list is cut into batches of
 // query tiles so that this bound holds whatever the number of pairs (feature matching).

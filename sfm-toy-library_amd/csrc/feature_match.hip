@@ -159,9 +159,6 @@ __global__ __launch_bounds__(256) void k_match_scatter(long long n_rows, const i
     out_d[o] = (float)(k >> 22);
 }
 
-#define FM_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define FM_ALLOC(ptr, T, n) do { ptr = scratch.alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 unsigned grid_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 template <int W>
@@ -200,9 +197,7 @@ int match_features(hipStream_t s, int device, int n_images, const int64_t* img_p
     DeviceArena scratch(device);
     const int W = desc_bytes <= 32 ? 8 : 16;
     const long long n_desc = img_ptr[n_images];
-    hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 5; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } eg{ ev };
-    if (timing) for (int i = 0; i < 5; ++i) FM_TRY(hipEventCreate(&ev[i]));
+    PhaseTimer tm{ s, timing != nullptr, {}, {} };
     // allocations first (the arena zeroes them), then the stream work
     const int n_items = (int)items.size();
     const int n_batches = (n_items + MATCH_BATCH_TILES - 1) / MATCH_BATCH_TILES;
@@ -224,44 +219,44 @@ int match_features(hipStream_t s, int device, int n_images, const int64_t* img_p
     unsigned* d_best;
     int *d_flag, *d_pos, *d_qidx;
     long long *d_prow, *d_pptr;
-    FM_ALLOC(d_desc, uint32_t, (size_t)n_desc * W);
-    FM_ALLOC(d_pairs, MatchPair, pairs.size());
-    FM_ALLOC(d_items, MatchItem, items.size());
-    FM_ALLOC(d_keys, uint2, (size_t)key_slots);
-    FM_ALLOC(d_best, unsigned, (size_t)n_rows);
-    FM_ALLOC(d_flag, int, (size_t)n_rows);
-    FM_ALLOC(d_qidx, int, (size_t)n_rows);
-    FM_ALLOC(d_pos, int, (size_t)n_rows + 1);
-    FM_ALLOC(d_prow, long long, prow.size());
-    FM_ALLOC(d_pptr, long long, prow.size());
+    UNIT_ALLOC(scratch, d_desc, uint32_t, (size_t)n_desc * W);
+    UNIT_ALLOC(scratch, d_pairs, MatchPair, pairs.size());
+    UNIT_ALLOC(scratch, d_items, MatchItem, items.size());
+    UNIT_ALLOC(scratch, d_keys, uint2, (size_t)key_slots);
+    UNIT_ALLOC(scratch, d_best, unsigned, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_flag, int, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_qidx, int, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_pos, int, (size_t)n_rows + 1);
+    UNIT_ALLOC(scratch, d_prow, long long, prow.size());
+    UNIT_ALLOC(scratch, d_pptr, long long, prow.size());
     size_t tmp_bytes = 0;
-    FM_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
+    UNIT_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
     void* d_tmp = scratch.alloc(tmp_bytes ? tmp_bytes : 1);
     if (!d_tmp) return (int)hipErrorOutOfMemory;
     const long long ocap = std::min<long long>(std::max<long long>(cap, 0), n_rows);
     int *d_oq, *d_ot;
     float* d_od;
-    FM_ALLOC(d_oq, int, (size_t)std::max(ocap, 1ll));
-    FM_ALLOC(d_ot, int, (size_t)std::max(ocap, 1ll));
-    FM_ALLOC(d_od, float, (size_t)std::max(ocap, 1ll));
+    UNIT_ALLOC(scratch, d_oq, int, (size_t)std::max(ocap, 1ll));
+    UNIT_ALLOC(scratch, d_ot, int, (size_t)std::max(ocap, 1ll));
+    UNIT_ALLOC(scratch, d_od, float, (size_t)std::max(ocap, 1ll));
 
     // upload: rows of exactly 4 W bytes go as they are, others are padded with zero bytes on the host
-    if (timing) FM_TRY(hipEventRecord(ev[0], s));
+    tm.begin(0);
     std::vector<uint32_t> padded;
     if (n_desc > 0) {
         if (desc_bytes == 4 * W) {
-            FM_TRY(hipMemcpyAsync(d_desc, desc, (size_t)n_desc * desc_bytes, hipMemcpyHostToDevice, s));
+            UNIT_TRY(hipMemcpyAsync(d_desc, desc, (size_t)n_desc * desc_bytes, hipMemcpyHostToDevice, s));
         } else {
             padded.assign((size_t)n_desc * W, 0u);
             unsigned char* dst = reinterpret_cast<unsigned char*>(padded.data());
             for (long long i = 0; i < n_desc; ++i) std::memcpy(dst + (size_t)i * 4 * W, desc + (size_t)i * desc_bytes, (size_t)desc_bytes);
-            FM_TRY(hipMemcpyAsync(d_desc, padded.data(), padded.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            UNIT_TRY(hipMemcpyAsync(d_desc, padded.data(), padded.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         }
     }
-    FM_TRY(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(MatchPair) * pairs.size(), hipMemcpyHostToDevice, s));
-    FM_TRY(hipMemcpyAsync(d_items, items.data(), sizeof(MatchItem) * items.size(), hipMemcpyHostToDevice, s));
-    FM_TRY(hipMemcpyAsync(d_prow, prow.data(), sizeof(long long) * prow.size(), hipMemcpyHostToDevice, s));
-    if (timing) FM_TRY(hipEventRecord(ev[1], s));
+    UNIT_TRY(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(MatchPair) * pairs.size(), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_items, items.data(), sizeof(MatchItem) * items.size(), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_prow, prow.data(), sizeof(long long) * prow.size(), hipMemcpyHostToDevice, s));
+    tm.next(1);
 
     for (int b = 0; b < n_batches; ++b) {
         const int i0 = b * MATCH_BATCH_TILES, nb = std::min(n_items, i0 + MATCH_BATCH_TILES) - i0;
@@ -271,31 +266,27 @@ int match_features(hipStream_t s, int device, int n_images, const int64_t* img_p
         hipLaunchKernelGGL(k_match_merge, dim3((unsigned)nb), dim3(LANES), 0, s, d_pairs, d_items + i0, slices[(size_t)b], stride, d_keys, ratio,
                            d_best, d_flag, d_qidx);
     }
-    if (timing) FM_TRY(hipEventRecord(ev[2], s));
-    FM_TRY(hipMemsetAsync(d_pos, 0, sizeof(int), s));
-    FM_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
+    tm.next(2);
+    UNIT_TRY(hipMemsetAsync(d_pos, 0, sizeof(int), s));
+    UNIT_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
     hipLaunchKernelGGL(k_match_pair_ptr, dim3(grid_for(n_pairs + 1)), dim3(256), 0, s, n_pairs, d_prow, d_pos, d_pptr);
     hipLaunchKernelGGL(k_match_scatter, dim3(grid_for(n_rows)), dim3(256), 0, s, n_rows, d_flag, d_pos, d_best, d_qidx, ocap, d_oq, d_ot, d_od);
-    FM_TRY(hipGetLastError());
-    if (timing) FM_TRY(hipEventRecord(ev[3], s));
-    FM_TRY(hipMemcpyAsync(pair_ptr, d_pptr, sizeof(long long) * prow.size(), hipMemcpyDeviceToHost, s));
-    FM_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipGetLastError());
+    tm.next(3);
+    UNIT_TRY(hipMemcpyAsync(pair_ptr, d_pptr, sizeof(long long) * prow.size(), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipStreamSynchronize(s));
     const long long tot = pair_ptr[n_pairs];
     *total = tot;
-    if (tot > cap) return MATCH_ERR_CAPACITY;
+    if (tot > cap) return UNIT_ERR_CAPACITY;
     if (tot > 0) {
-        FM_TRY(hipMemcpyAsync(query_idx, d_oq, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        FM_TRY(hipMemcpyAsync(train_idx, d_ot, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        if (distance) FM_TRY(hipMemcpyAsync(distance, d_od, sizeof(float) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(query_idx, d_oq, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(train_idx, d_ot, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        if (distance) UNIT_TRY(hipMemcpyAsync(distance, d_od, sizeof(float) * (size_t)tot, hipMemcpyDeviceToHost, s));
     }
-    if (timing) FM_TRY(hipEventRecord(ev[4], s));
-    FM_TRY(hipStreamSynchronize(s));
+    tm.end();
+    UNIT_TRY(hipStreamSynchronize(s));
     if (timing) {
-        for (int i = 0; i < 4; ++i) {
-            float ms = 0.f;
-            FM_TRY(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-            timing[i] = ms;
-        }
+        tm.collect(timing);
         timing[4] = n_batches;
     }
     return 0;

@@ -4,12 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unit_common.h"
+
 #include "../../include/sfmba.h"
 
 namespace sfmba {
 
-// return values besides 0 (ok) and positive hipError_t codes
-enum { FLOW_ERR_CAPACITY = -1 };
+// return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 // Pairs go to the device in consecutive groups.  A group's arrays (the pixels of the images its pairs name, their pyramids, the
 // points and what is written per point) stay within this bound; a pair that exceeds it alone forms a group of its own.

@@ -23,7 +23,6 @@
 #include "flow_track.h"
 #include "flow_math.h"
 #include "device_arena.h"
-#include "jpeg_decode.h"   // PhaseTimer
 
 #include <hipcub/hipcub.hpp>
 
@@ -262,9 +261,6 @@ __global__ __launch_bounds__(LANES) void k_flow_scatter(long long n_rows, const 
     out_d[o] = dist[r];
 }
 
-#define FLOW_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define FLOW_ALLOC(arena, ptr, T, n) do { ptr = (arena).alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 long long align64(long long n) { return (n + 63) & ~63ll; }
 unsigned grid_for(long long n) { return (unsigned)((n + LANES - 1) / LANES); }
 
@@ -349,35 +345,35 @@ int flow_track(hipStream_t s, int device, int n_images, const int64_t* img_ptr, 
         float *d_pts, *d_next, *d_err;
         long long* d_G = nullptr;
         int* d_state = nullptr;
-        FLOW_ALLOC(scratch, d_tab, FlowImage, tab.size());
-        FLOW_ALLOC(scratch, d_ptab, FlowPair, ptab.size());
-        FLOW_ALLOC(scratch, d_pyr, unsigned char, (size_t)pyr_bytes);
-        if (channels == 3) FLOW_ALLOC(scratch, d_raw, unsigned char, (size_t)raw_bytes);
-        FLOW_ALLOC(scratch, d_pts, float, (size_t)n_pts * 2);
-        FLOW_ALLOC(scratch, d_next, float, (size_t)n_pts * 2);
-        FLOW_ALLOC(scratch, d_status, unsigned char, (size_t)n_pts);
-        FLOW_ALLOC(scratch, d_err, float, (size_t)n_pts);
-        if (dbg_G) FLOW_ALLOC(scratch, d_G, long long, (size_t)n_pts * L * 3);
-        if (dbg_state) FLOW_ALLOC(scratch, d_state, int, (size_t)n_pts * L * 4);
+        UNIT_ALLOC(scratch, d_tab, FlowImage, tab.size());
+        UNIT_ALLOC(scratch, d_ptab, FlowPair, ptab.size());
+        UNIT_ALLOC(scratch, d_pyr, unsigned char, (size_t)pyr_bytes);
+        if (channels == 3) UNIT_ALLOC(scratch, d_raw, unsigned char, (size_t)raw_bytes);
+        UNIT_ALLOC(scratch, d_pts, float, (size_t)n_pts * 2);
+        UNIT_ALLOC(scratch, d_next, float, (size_t)n_pts * 2);
+        UNIT_ALLOC(scratch, d_status, unsigned char, (size_t)n_pts);
+        UNIT_ALLOC(scratch, d_err, float, (size_t)n_pts);
+        if (dbg_G) UNIT_ALLOC(scratch, d_G, long long, (size_t)n_pts * L * 3);
+        if (dbg_state) UNIT_ALLOC(scratch, d_state, int, (size_t)n_pts * L * 4);
 
         tm.begin(FLOW_T_UPLOAD);
-        FLOW_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(FlowImage) * tab.size(), hipMemcpyHostToDevice, s));
-        FLOW_TRY(hipMemcpyAsync(d_ptab, ptab.data(), sizeof(FlowPair) * ptab.size(), hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(FlowImage) * tab.size(), hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_ptab, ptab.data(), sizeof(FlowPair) * ptab.size(), hipMemcpyHostToDevice, s));
         long long max_px = 0;
         for (size_t q = 0; q < used.size(); ++q) {
             const int i = used[q];
             const long long px = (long long)width[i] * height[i];
             max_px = std::max(max_px, px);
-            if (channels == 3) FLOW_TRY(hipMemcpyAsync(d_raw + tab[q].raw_off, pixels + img_ptr[i], (size_t)px * 3, hipMemcpyHostToDevice, s));
-            else               FLOW_TRY(hipMemcpyAsync(d_pyr + tab[q].off[0], pixels + img_ptr[i], (size_t)px, hipMemcpyHostToDevice, s));
+            if (channels == 3) UNIT_TRY(hipMemcpyAsync(d_raw + tab[q].raw_off, pixels + img_ptr[i], (size_t)px * 3, hipMemcpyHostToDevice, s));
+            else               UNIT_TRY(hipMemcpyAsync(d_pyr + tab[q].off[0], pixels + img_ptr[i], (size_t)px, hipMemcpyHostToDevice, s));
         }
         const size_t at = (size_t)pt_ptr[p0];
-        if (n_pts > 0) FLOW_TRY(hipMemcpyAsync(d_pts, pts + 2 * at, sizeof(float) * 2 * (size_t)n_pts, hipMemcpyHostToDevice, s));
+        if (n_pts > 0) UNIT_TRY(hipMemcpyAsync(d_pts, pts + 2 * at, sizeof(float) * 2 * (size_t)n_pts, hipMemcpyHostToDevice, s));
         tm.end();
         if (channels == 3) {
             tm.begin(FLOW_T_GRAY);
             hipLaunchKernelGGL(k_flow_gray, dim3(std::min(grid_for(max_px), 4096u), (unsigned)used.size()), dim3(LANES), 0, s, d_tab, d_raw, d_pyr);
-            FLOW_TRY(hipGetLastError());
+            UNIT_TRY(hipGetLastError());
             tm.end();
         }
         tm.begin(FLOW_T_PYRAMID);
@@ -385,22 +381,22 @@ int flow_track(hipStream_t s, int device, int n_images, const int64_t* img_ptr, 
             long long lvl_px = 1;
             for (const FlowImage& T : tab) lvl_px = std::max(lvl_px, (long long)T.w[l] * T.h[l]);
             hipLaunchKernelGGL(k_flow_pyr, dim3(std::min(grid_for(lvl_px), 4096u), (unsigned)used.size()), dim3(LANES), 0, s, d_tab, d_pyr, l);
-            FLOW_TRY(hipGetLastError());
+            UNIT_TRY(hipGetLastError());
         }
         tm.end();
         if (n_pts > 0) {
             tm.begin(FLOW_T_TRACK);
             hipLaunchKernelGGL(k_flow_track, dim3((unsigned)n_pts), dim3(WAVE), 0, s, d_tab, d_ptab, np_, d_pyr, d_pts, L, radius, max_iters, min_eig,
                                d_next, d_status, d_err, d_G, d_state);
-            FLOW_TRY(hipGetLastError());
+            UNIT_TRY(hipGetLastError());
             tm.end();
             tm.begin(FLOW_T_DOWNLOAD);
-            FLOW_TRY(hipMemcpyAsync(next + 2 * at, d_next, sizeof(float) * 2 * (size_t)n_pts, hipMemcpyDeviceToHost, s));
-            FLOW_TRY(hipMemcpyAsync(status + at, d_status, (size_t)n_pts, hipMemcpyDeviceToHost, s));
-            FLOW_TRY(hipMemcpyAsync(err + at, d_err, sizeof(float) * (size_t)n_pts, hipMemcpyDeviceToHost, s));
+            UNIT_TRY(hipMemcpyAsync(next + 2 * at, d_next, sizeof(float) * 2 * (size_t)n_pts, hipMemcpyDeviceToHost, s));
+            UNIT_TRY(hipMemcpyAsync(status + at, d_status, (size_t)n_pts, hipMemcpyDeviceToHost, s));
+            UNIT_TRY(hipMemcpyAsync(err + at, d_err, sizeof(float) * (size_t)n_pts, hipMemcpyDeviceToHost, s));
             static_assert(sizeof(long long) == sizeof(int64_t), "dbg_G leaves as it is");
-            if (dbg_G) FLOW_TRY(hipMemcpyAsync(dbg_G + at * L * 3, d_G, sizeof(int64_t) * (size_t)n_pts * L * 3, hipMemcpyDeviceToHost, s));
-            if (dbg_state) FLOW_TRY(hipMemcpyAsync(dbg_state + at * L * 4, d_state, sizeof(int32_t) * (size_t)n_pts * L * 4, hipMemcpyDeviceToHost, s));
+            if (dbg_G) UNIT_TRY(hipMemcpyAsync(dbg_G + at * L * 3, d_G, sizeof(int64_t) * (size_t)n_pts * L * 3, hipMemcpyDeviceToHost, s));
+            if (dbg_state) UNIT_TRY(hipMemcpyAsync(dbg_state + at * L * 4, d_state, sizeof(int32_t) * (size_t)n_pts * L * 4, hipMemcpyDeviceToHost, s));
             tm.end();
         }
         if (dbg_pyramid) {
@@ -409,13 +405,13 @@ int flow_track(hipStream_t s, int device, int n_images, const int64_t* img_ptr, 
                 long long o = dbg_off[(size_t)used[q]];
                 for (int l = 0; l < L; ++l) {
                     const size_t b = (size_t)tab[q].w[l] * tab[q].h[l];
-                    FLOW_TRY(hipMemcpyAsync(dbg_pyramid + o, d_pyr + tab[q].off[l], b, hipMemcpyDeviceToHost, s));
+                    UNIT_TRY(hipMemcpyAsync(dbg_pyramid + o, d_pyr + tab[q].off[l], b, hipMemcpyDeviceToHost, s));
                     o += (long long)b;
                 }
             }
             tm.end();
         }
-        FLOW_TRY(hipStreamSynchronize(s));                     // the group's arena goes back to the cache below
+        UNIT_TRY(hipStreamSynchronize(s));                     // the group's arena goes back to the cache below
         p0 = p1;
     }
     if (timing) {
@@ -461,40 +457,40 @@ int flow_match(hipStream_t s, int device, int n_images, const int64_t* kp_ptr, c
     int *d_cand, *d_flag, *d_qidx, *d_pos;
     unsigned* d_winner;
     long long *d_prow, *d_pptr;
-    FLOW_ALLOC(scratch, d_pairs, MatchPair, pairs.size());
-    FLOW_ALLOC(scratch, d_tiles, MatchTile, tiles.size());
-    FLOW_ALLOC(scratch, d_next, float, (size_t)n_rows * 2);
-    FLOW_ALLOC(scratch, d_err, float, (size_t)n_rows);
-    FLOW_ALLOC(scratch, d_status, unsigned char, (size_t)n_rows);
-    FLOW_ALLOC(scratch, d_kp, float, (size_t)std::max(n_kp, 1ll) * 2);
-    FLOW_ALLOC(scratch, d_cand, int, (size_t)n_rows);
-    FLOW_ALLOC(scratch, d_dist, float, (size_t)n_rows);
-    FLOW_ALLOC(scratch, d_winner, unsigned, (size_t)std::max(n_win, 1ll));
-    FLOW_ALLOC(scratch, d_flag, int, (size_t)n_rows);
-    FLOW_ALLOC(scratch, d_qidx, int, (size_t)n_rows);
-    FLOW_ALLOC(scratch, d_pos, int, (size_t)n_rows + 1);           // handed out zeroed: pos[0] stays 0
-    FLOW_ALLOC(scratch, d_prow, long long, prow.size());
-    FLOW_ALLOC(scratch, d_pptr, long long, prow.size());
+    UNIT_ALLOC(scratch, d_pairs, MatchPair, pairs.size());
+    UNIT_ALLOC(scratch, d_tiles, MatchTile, tiles.size());
+    UNIT_ALLOC(scratch, d_next, float, (size_t)n_rows * 2);
+    UNIT_ALLOC(scratch, d_err, float, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_status, unsigned char, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_kp, float, (size_t)std::max(n_kp, 1ll) * 2);
+    UNIT_ALLOC(scratch, d_cand, int, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_dist, float, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_winner, unsigned, (size_t)std::max(n_win, 1ll));
+    UNIT_ALLOC(scratch, d_flag, int, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_qidx, int, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_pos, int, (size_t)n_rows + 1);           // handed out zeroed: pos[0] stays 0
+    UNIT_ALLOC(scratch, d_prow, long long, prow.size());
+    UNIT_ALLOC(scratch, d_pptr, long long, prow.size());
     size_t tmp_bytes = 0;
-    FLOW_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
+    UNIT_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
     void* d_tmp = scratch.alloc(tmp_bytes ? tmp_bytes : 1);
     if (!d_tmp) return (int)hipErrorOutOfMemory;
     const long long ocap = std::min<long long>(std::max<long long>(cap, 0), n_rows);
     int *d_oq, *d_ot;
     float* d_od;
-    FLOW_ALLOC(scratch, d_oq, int, (size_t)std::max(ocap, 1ll));
-    FLOW_ALLOC(scratch, d_ot, int, (size_t)std::max(ocap, 1ll));
-    FLOW_ALLOC(scratch, d_od, float, (size_t)std::max(ocap, 1ll));
+    UNIT_ALLOC(scratch, d_oq, int, (size_t)std::max(ocap, 1ll));
+    UNIT_ALLOC(scratch, d_ot, int, (size_t)std::max(ocap, 1ll));
+    UNIT_ALLOC(scratch, d_od, float, (size_t)std::max(ocap, 1ll));
 
     tm.begin(FLOWM_T_UPLOAD);
-    FLOW_TRY(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(MatchPair) * pairs.size(), hipMemcpyHostToDevice, s));
-    FLOW_TRY(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(MatchTile) * tiles.size(), hipMemcpyHostToDevice, s));
-    FLOW_TRY(hipMemcpyAsync(d_prow, prow.data(), sizeof(long long) * prow.size(), hipMemcpyHostToDevice, s));
-    FLOW_TRY(hipMemcpyAsync(d_next, next, sizeof(float) * 2 * (size_t)n_rows, hipMemcpyHostToDevice, s));
-    FLOW_TRY(hipMemcpyAsync(d_err, err, sizeof(float) * (size_t)n_rows, hipMemcpyHostToDevice, s));
-    FLOW_TRY(hipMemcpyAsync(d_status, status, (size_t)n_rows, hipMemcpyHostToDevice, s));
-    if (n_kp > 0) FLOW_TRY(hipMemcpyAsync(d_kp, kp_xy, sizeof(float) * 2 * (size_t)n_kp, hipMemcpyHostToDevice, s));
-    FLOW_TRY(hipMemsetAsync(d_winner, 0xff, sizeof(unsigned) * (size_t)std::max(n_win, 1ll), s));     // above every query index
+    UNIT_TRY(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(MatchPair) * pairs.size(), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(MatchTile) * tiles.size(), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_prow, prow.data(), sizeof(long long) * prow.size(), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_next, next, sizeof(float) * 2 * (size_t)n_rows, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_err, err, sizeof(float) * (size_t)n_rows, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_status, status, (size_t)n_rows, hipMemcpyHostToDevice, s));
+    if (n_kp > 0) UNIT_TRY(hipMemcpyAsync(d_kp, kp_xy, sizeof(float) * 2 * (size_t)n_kp, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemsetAsync(d_winner, 0xff, sizeof(unsigned) * (size_t)std::max(n_win, 1ll), s));     // above every query index
     tm.end();
 
     tm.begin(FLOWM_T_NEAR);
@@ -502,27 +498,27 @@ int flow_match(hipStream_t s, int device, int n_images, const int64_t* kp_ptr, c
     hipLaunchKernelGGL(k_flow_near, dim3(n_tiles), dim3(FLOW_MATCH_QUERIES), 0, s, d_pairs, d_tiles, d_next, d_status, d_err, d_kp, max_err, radius, ratio,
                        d_cand, d_dist, d_winner);
     hipLaunchKernelGGL(k_flow_winner, dim3(n_tiles), dim3(FLOW_MATCH_QUERIES), 0, s, d_pairs, d_tiles, d_cand, d_winner, d_flag, d_qidx);
-    FLOW_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     tm.end();
     tm.begin(FLOWM_T_COMPACT);
-    FLOW_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
+    UNIT_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
     hipLaunchKernelGGL(k_flow_pair_ptr, dim3(grid_for(n_pairs + 1)), dim3(LANES), 0, s, n_pairs, d_prow, d_pos, d_pptr);
     hipLaunchKernelGGL(k_flow_scatter, dim3(grid_for(n_rows)), dim3(LANES), 0, s, n_rows, d_flag, d_pos, d_cand, d_dist, d_qidx, ocap, d_oq, d_ot, d_od);
-    FLOW_TRY(hipGetLastError());
+    UNIT_TRY(hipGetLastError());
     static_assert(sizeof(long long) == sizeof(int64_t), "pair_ptr leaves as it is");
-    FLOW_TRY(hipMemcpyAsync(pair_ptr, d_pptr, sizeof(int64_t) * prow.size(), hipMemcpyDeviceToHost, s));
-    FLOW_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipMemcpyAsync(pair_ptr, d_pptr, sizeof(int64_t) * prow.size(), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipStreamSynchronize(s));
     tm.end();
     const long long tot = pair_ptr[n_pairs];
     *total = tot;
-    if (tot > cap) return FLOW_ERR_CAPACITY;
+    if (tot > cap) return UNIT_ERR_CAPACITY;
     if (tot > 0) {
         tm.begin(FLOWM_T_DOWNLOAD);
-        FLOW_TRY(hipMemcpyAsync(query_idx, d_oq, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        FLOW_TRY(hipMemcpyAsync(train_idx, d_ot, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        if (distance) FLOW_TRY(hipMemcpyAsync(distance, d_od, sizeof(float) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(query_idx, d_oq, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(train_idx, d_ot, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        if (distance) UNIT_TRY(hipMemcpyAsync(distance, d_od, sizeof(float) * (size_t)tot, hipMemcpyDeviceToHost, s));
         tm.end();
-        FLOW_TRY(hipStreamSynchronize(s));
+        UNIT_TRY(hipStreamSynchronize(s));
     }
     if (timing) tm.collect(timing);
     return 0;

@@ -3,12 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unit_common.h"
+
 #include "../../include/sfmba.h"
 
 namespace sfmba {
 
-// return values besides 0 (ok) and positive hipError_t codes
-enum { HOM_ERR_TOO_LARGE = -1 };
+// return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 constexpr int HOM_TILE = 64;                 // hypotheses per score block: one per lane of a wave
 constexpr int HOM_CHUNK = 1024;              // correspondences a score block stages in LDS at a time (one float4 each)

@@ -180,17 +180,13 @@ __global__ __launch_bounds__(HOM_SELECT_THREADS) void k_hom_select(int n_hyp, Ho
     }
 }
 
-#define HOM_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define HOM_ALLOC(ptr, T, n) do { ptr = arena.alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 }  // namespace
 
 int homography_ransac(hipStream_t s, int device, int n_images, const int64_t* img_ptr, const float* pts, int n_pairs, const int32_t* pair_left,
                       const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx, int n_hyp,
                       float threshold_px, uint64_t seed, double* H, unsigned char* inlier, sfmba_homography_result* result, double* hyp_H,
                       int32_t* hyp_count, double* timing) {
-    constexpr int N_EV = 6;
-    if (timing) for (int i = 0; i < N_EV - 1; ++i) timing[i] = 0.0;
+    if (timing) for (int i = 0; i < 5; ++i) timing[i] = 0.0;
     if (n_pairs <= 0) return 0;
     const long long total = pair_ptr[n_pairs];             // entries in front of pair_ptr[0] belong to no pair: uploaded, never read
     const long long n_pts = img_ptr[n_images];
@@ -202,12 +198,10 @@ int homography_ransac(hipStream_t s, int device, int n_images, const int64_t* im
     const long long max_threads = 0xffffffffll;
     if (max_n > (long long)INT_MAX || (long long)n_pairs * tiles * HOM_SCORE_THREADS > max_threads || n_items + HYP_THREADS > max_threads ||
         (long long)n_pairs * HOM_SELECT_THREADS > max_threads)
-        return HOM_ERR_TOO_LARGE;
+        return UNIT_ERR_TOO_LARGE;
 
     DeviceArena arena(device);
-    hipEvent_t ev[N_EV] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < N_EV; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } eg{ ev };
-    if (timing) for (int i = 0; i < N_EV; ++i) HOM_TRY(hipEventCreate(&ev[i]));
+    PhaseTimer tm{ s, timing != nullptr, {}, {} };
     // allocations first (the arena zeroes them: the masks of status 1 / 2 pairs stay zero), then the stream work
     long long *d_img, *d_ptr;
     float2* d_pts;
@@ -216,60 +210,54 @@ int homography_ransac(hipStream_t s, int device, int n_images, const int64_t* im
     float* d_hf;
     unsigned char* d_inl;
     sfmba_homography_result* d_res;
-    HOM_ALLOC(d_img, long long, (size_t)n_images + 1);
-    HOM_ALLOC(d_pts, float2, (size_t)n_pts);
-    HOM_ALLOC(d_left, int, (size_t)n_pairs);
-    HOM_ALLOC(d_right, int, (size_t)n_pairs);
-    HOM_ALLOC(d_ptr, long long, (size_t)n_pairs + 1);
-    HOM_ALLOC(d_query, int, (size_t)total);
-    HOM_ALLOC(d_train, int, (size_t)total);
-    HOM_ALLOC(d_hH, double, (size_t)9 * n_items);
-    HOM_ALLOC(d_hf, float, (size_t)HOM_HF_STRIDE * n_items);
-    HOM_ALLOC(d_count, int, (size_t)n_items);
-    HOM_ALLOC(d_H, double, (size_t)9 * n_pairs);
-    HOM_ALLOC(d_inl, unsigned char, (size_t)total);
-    HOM_ALLOC(d_res, sfmba_homography_result, (size_t)n_pairs);
+    UNIT_ALLOC(arena, d_img, long long, (size_t)n_images + 1);
+    UNIT_ALLOC(arena, d_pts, float2, (size_t)n_pts);
+    UNIT_ALLOC(arena, d_left, int, (size_t)n_pairs);
+    UNIT_ALLOC(arena, d_right, int, (size_t)n_pairs);
+    UNIT_ALLOC(arena, d_ptr, long long, (size_t)n_pairs + 1);
+    UNIT_ALLOC(arena, d_query, int, (size_t)total);
+    UNIT_ALLOC(arena, d_train, int, (size_t)total);
+    UNIT_ALLOC(arena, d_hH, double, (size_t)9 * n_items);
+    UNIT_ALLOC(arena, d_hf, float, (size_t)HOM_HF_STRIDE * n_items);
+    UNIT_ALLOC(arena, d_count, int, (size_t)n_items);
+    UNIT_ALLOC(arena, d_H, double, (size_t)9 * n_pairs);
+    UNIT_ALLOC(arena, d_inl, unsigned char, (size_t)total);
+    UNIT_ALLOC(arena, d_res, sfmba_homography_result, (size_t)n_pairs);
 
-    if (timing) HOM_TRY(hipEventRecord(ev[0], s));
+    tm.begin(0);
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "the index arrays are uploaded as they are");
-    HOM_TRY(hipMemcpyAsync(d_img, img_ptr, sizeof(int64_t) * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
-    HOM_TRY(hipMemcpyAsync(d_ptr, pair_ptr, sizeof(int64_t) * ((size_t)n_pairs + 1), hipMemcpyHostToDevice, s));
-    HOM_TRY(hipMemcpyAsync(d_left, pair_left, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-    HOM_TRY(hipMemcpyAsync(d_right, pair_right, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-    if (n_pts > 0) HOM_TRY(hipMemcpyAsync(d_pts, pts, sizeof(float) * 2 * (size_t)n_pts, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_img, img_ptr, sizeof(int64_t) * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_ptr, pair_ptr, sizeof(int64_t) * ((size_t)n_pairs + 1), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_left, pair_left, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_right, pair_right, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    if (n_pts > 0) UNIT_TRY(hipMemcpyAsync(d_pts, pts, sizeof(float) * 2 * (size_t)n_pts, hipMemcpyHostToDevice, s));
     if (total > 0) {
-        HOM_TRY(hipMemcpyAsync(d_query, query_idx, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
-        HOM_TRY(hipMemcpyAsync(d_train, train_idx, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_query, query_idx, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_train, train_idx, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
     }
-    if (timing) HOM_TRY(hipEventRecord(ev[1], s));
+    tm.next(1);
     const HomProblem pr{ d_img, d_pts, d_left, d_right, d_ptr, d_query, d_train };
     const float thr2 = threshold_px * threshold_px;
     hipLaunchKernelGGL(k_hom_hypotheses, dim3((unsigned)((n_items + HYP_THREADS - 1) / HYP_THREADS)), dim3(HYP_THREADS), 0, s, n_items, n_hyp, pr,
                        seed, d_hH, d_hf, d_count);
-    if (timing) HOM_TRY(hipEventRecord(ev[2], s));
+    tm.next(2);
     const long long max_chunks = (max_n + HOM_CHUNK - 1) / HOM_CHUNK;
     if (max_chunks > 0)
         hipLaunchKernelGGL(k_hom_score, dim3((unsigned)(n_pairs * tiles), (unsigned)std::min<long long>(max_chunks, HOM_MAX_CHUNK_BLOCKS)),
                            dim3(HOM_SCORE_THREADS), 0, s, n_hyp, tiles, pr, thr2, d_hf, d_count);
-    if (timing) HOM_TRY(hipEventRecord(ev[3], s));
+    tm.next(3);
     hipLaunchKernelGGL(k_hom_select, dim3((unsigned)n_pairs), dim3(HOM_SELECT_THREADS), 0, s, n_hyp, pr, thr2, d_hH, d_hf, d_count, d_H,
                        d_inl, d_res);
-    HOM_TRY(hipGetLastError());
-    if (timing) HOM_TRY(hipEventRecord(ev[4], s));
-    HOM_TRY(hipMemcpyAsync(H, d_H, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-    HOM_TRY(hipMemcpyAsync(result, d_res, sizeof(sfmba_homography_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-    if (total > 0) HOM_TRY(hipMemcpyAsync(inlier, d_inl, (size_t)total, hipMemcpyDeviceToHost, s));
-    if (hyp_H) HOM_TRY(hipMemcpyAsync(hyp_H, d_hH, sizeof(double) * 9 * (size_t)n_items, hipMemcpyDeviceToHost, s));
-    if (hyp_count) HOM_TRY(hipMemcpyAsync(hyp_count, d_count, sizeof(int) * (size_t)n_items, hipMemcpyDeviceToHost, s));
-    if (timing) HOM_TRY(hipEventRecord(ev[5], s));
-    HOM_TRY(hipStreamSynchronize(s));
-    if (timing) {
-        for (int i = 0; i < N_EV - 1; ++i) {
-            float ms = 0.f;
-            HOM_TRY(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-            timing[i] = ms;
-        }
-    }
+    UNIT_TRY(hipGetLastError());
+    tm.next(4);
+    UNIT_TRY(hipMemcpyAsync(H, d_H, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipMemcpyAsync(result, d_res, sizeof(sfmba_homography_result) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+    if (total > 0) UNIT_TRY(hipMemcpyAsync(inlier, d_inl, (size_t)total, hipMemcpyDeviceToHost, s));
+    if (hyp_H) UNIT_TRY(hipMemcpyAsync(hyp_H, d_hH, sizeof(double) * 9 * (size_t)n_items, hipMemcpyDeviceToHost, s));
+    if (hyp_count) UNIT_TRY(hipMemcpyAsync(hyp_count, d_count, sizeof(int) * (size_t)n_items, hipMemcpyDeviceToHost, s));
+    tm.end();
+    UNIT_TRY(hipStreamSynchronize(s));
+    if (timing) tm.collect(timing);
     return 0;
 }
 

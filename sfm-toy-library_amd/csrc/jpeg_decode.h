@@ -8,12 +8,11 @@
 
 #include "../../include/sfmba.h"
 #include "jpeg_entropy.h"
+#include "unit_common.h"
 
 namespace sfmba {
 
-// return values besides 0 (ok) and positive hipError_t codes
-enum { JPEG_ERR_CAPACITY = -1, JPEG_ERR_SIZE = -2, JPEG_ERR_HOST_ALLOC = -3 };      // _SIZE: the factor gives an image a side outside 1..16384 (nothing
-                                                                                    // was written); _HOST_ALLOC: no host memory for the coefficients
+// return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 // Images go to the device in consecutive groups.  A group's arrays (coefficients, component planes, decoded pixels, resize tables
 // and resized pixels) stay within this bound; an image that exceeds it alone forms a group of its own.
@@ -34,24 +33,6 @@ int resize_images(hipStream_t s, int device, int n_images, const int64_t* img_pt
                   double* timing);
 
 // ---- shared with the PNG reader (png_decode.hip), which ends in the same resize ------------------------------------------------------
-// HIP-event time per phase, summed; inert without a timing array
-struct PhaseTimer {
-    hipStream_t s;
-    bool on;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> phase;
-    void begin(int p) { if (on) { mark(); phase.push_back(p); } }
-    void end() { if (on) mark(); }
-    void mark() { hipEvent_t e = nullptr; if (hipEventCreate(&e) == hipSuccess) (void)hipEventRecord(e, s); ev.push_back(e); }
-    void collect(double* t) {
-        for (size_t i = 0; i < phase.size(); ++i) {
-            float ms = 0.f;
-            if (ev[2 * i] && ev[2 * i + 1] && hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) == hipSuccess) t[phase[i]] += ms;
-        }
-    }
-    ~PhaseTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-};
-
 // What the resize of one image of a group needs.
 struct ResizeJob {
     int w, h, ow, oh, channels;

@@ -161,11 +161,6 @@ __global__ __launch_bounds__(LANES) void k_resize(const ResizeImage* __restrict_
     else for (int i = 0; i < 4 && q + i < n; ++i) o[i] = (unsigned char)v[i];
 }
 
-// On a failure the stream `s` of the enclosing function is drained before the return: the group's arena and the host tables go out
-// of scope with it, and nothing queued may still use them.
-#define JPEG_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipStreamSynchronize(s); return (int)e_; } } while (0)
-#define JPEG_ALLOC(arena, ptr, T, n) do { ptr = (arena).alloc_n<T>(n); if (!ptr) { (void)hipStreamSynchronize(s); return (int)hipErrorOutOfMemory; } } while (0)
-
 long long align4(long long n) { return (n + 3) & ~3ll; }
 unsigned grid_quads(long long n) { return (unsigned)((n + 4 * LANES - 1) / (4 * LANES)); }
 
@@ -197,18 +192,18 @@ int launch_resize(hipStream_t s, DeviceArena& arena, PhaseTimer& tm, const std::
     }
     ResizeImage* d_tab;
     ResizeEntry* d_entries;
-    JPEG_ALLOC(arena, d_tab, ResizeImage, tab.size());
-    JPEG_ALLOC(arena, d_entries, ResizeEntry, entries.size());
-    JPEG_ALLOC(arena, *d_dst, unsigned char, (size_t)off);
+    UNIT_DRAIN_ALLOC(arena, d_tab, ResizeImage, tab.size());
+    UNIT_DRAIN_ALLOC(arena, d_entries, ResizeEntry, entries.size());
+    UNIT_DRAIN_ALLOC(arena, *d_dst, unsigned char, (size_t)off);
     tm.begin(JPEG_T_UPLOAD);
-    JPEG_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(ResizeImage) * tab.size(), hipMemcpyHostToDevice, s));
-    JPEG_TRY(hipMemcpyAsync(d_entries, entries.data(), sizeof(ResizeEntry) * entries.size(), hipMemcpyHostToDevice, s));
+    UNIT_DRAIN_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(ResizeImage) * tab.size(), hipMemcpyHostToDevice, s));
+    UNIT_DRAIN_TRY(hipMemcpyAsync(d_entries, entries.data(), sizeof(ResizeEntry) * entries.size(), hipMemcpyHostToDevice, s));
     tm.end();
     tm.begin(JPEG_T_RESIZE);
     hipLaunchKernelGGL(k_resize, dim3(grid_quads(max_bytes), (unsigned)jobs.size()), dim3(LANES), 0, s, d_tab, d_entries, d_src, *d_dst);
-    JPEG_TRY(hipGetLastError());
+    UNIT_DRAIN_TRY(hipGetLastError());
     tm.end();
-    JPEG_TRY(hipStreamSynchronize(s));                         // the host tables leave scope here
+    UNIT_DRAIN_TRY(hipStreamSynchronize(s));                         // the host tables leave scope here
     return 0;
 }
 
@@ -242,9 +237,9 @@ int jpeg_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr
         if (H.status != JPEG_OK) continue;
         ow[(size_t)i] = resize ? resized_length(H.width, factor) : H.width;
         oh[(size_t)i] = resize ? resized_length(H.height, factor) : H.height;
-        if (ow[(size_t)i] == 0 || oh[(size_t)i] == 0) return JPEG_ERR_SIZE;
+        if (ow[(size_t)i] == 0 || oh[(size_t)i] == 0) return UNIT_ERR_SIZE;
     }
-    if (!jpeg_scan_batch(n_images, file_ptr, bytes, 16, hdr, coef)) return JPEG_ERR_HOST_ALLOC;
+    if (!jpeg_scan_batch(n_images, file_ptr, bytes, 16, hdr, coef)) return UNIT_ERR_HOST_ALLOC;
     if (timing) timing[JPEG_T_ENTROPY] = now_ms() - t0;
 
     out_ptr[0] = 0;
@@ -254,7 +249,7 @@ int jpeg_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr
         out_ptr[i + 1] = out_ptr[i] + (H.status == JPEG_OK ? (long long)ow[(size_t)i] * oh[(size_t)i] * H.ncomp : 0);
     }
     *total = out_ptr[n_images];
-    if (*total > cap) return JPEG_ERR_CAPACITY;
+    if (*total > cap) return UNIT_ERR_CAPACITY;
 
     PhaseTimer tm{ s, timing != nullptr, {}, {} };
     int n_groups = 0;
@@ -316,29 +311,29 @@ int jpeg_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr
         unsigned short* d_quant;
         int16_t* d_coef;
         unsigned char *d_planes, *d_full;
-        JPEG_ALLOC(scratch, d_planes_tab, JpegPlane, planes.size());
-        JPEG_ALLOC(scratch, d_images, JpegImage, images.size());
-        JPEG_ALLOC(scratch, d_quant, unsigned short, quant.size());
-        JPEG_ALLOC(scratch, d_coef, int16_t, (size_t)n_coef);
-        JPEG_ALLOC(scratch, d_planes, unsigned char, (size_t)n_plane);
-        JPEG_ALLOC(scratch, d_full, unsigned char, (size_t)n_out);
+        UNIT_DRAIN_ALLOC(scratch, d_planes_tab, JpegPlane, planes.size());
+        UNIT_DRAIN_ALLOC(scratch, d_images, JpegImage, images.size());
+        UNIT_DRAIN_ALLOC(scratch, d_quant, unsigned short, quant.size());
+        UNIT_DRAIN_ALLOC(scratch, d_coef, int16_t, (size_t)n_coef);
+        UNIT_DRAIN_ALLOC(scratch, d_planes, unsigned char, (size_t)n_plane);
+        UNIT_DRAIN_ALLOC(scratch, d_full, unsigned char, (size_t)n_out);
         tm.begin(JPEG_T_UPLOAD);
-        JPEG_TRY(hipMemcpyAsync(d_planes_tab, planes.data(), sizeof(JpegPlane) * planes.size(), hipMemcpyHostToDevice, s));
-        JPEG_TRY(hipMemcpyAsync(d_images, images.data(), sizeof(JpegImage) * images.size(), hipMemcpyHostToDevice, s));
-        JPEG_TRY(hipMemcpyAsync(d_quant, quant.data(), sizeof(unsigned short) * quant.size(), hipMemcpyHostToDevice, s));
+        UNIT_DRAIN_TRY(hipMemcpyAsync(d_planes_tab, planes.data(), sizeof(JpegPlane) * planes.size(), hipMemcpyHostToDevice, s));
+        UNIT_DRAIN_TRY(hipMemcpyAsync(d_images, images.data(), sizeof(JpegImage) * images.size(), hipMemcpyHostToDevice, s));
+        UNIT_DRAIN_TRY(hipMemcpyAsync(d_quant, quant.data(), sizeof(unsigned short) * quant.size(), hipMemcpyHostToDevice, s));
         for (size_t g = 0; g < member.size(); ++g) {
             const std::vector<int16_t>& c = coef[(size_t)member[g]];
-            JPEG_TRY(hipMemcpyAsync(d_coef + coef_off[g], c.data(), sizeof(int16_t) * c.size(), hipMemcpyHostToDevice, s));
+            UNIT_DRAIN_TRY(hipMemcpyAsync(d_coef + coef_off[g], c.data(), sizeof(int16_t) * c.size(), hipMemcpyHostToDevice, s));
         }
         tm.end();
         tm.begin(JPEG_T_IDCT);
         hipLaunchKernelGGL(k_jpeg_idct, dim3((unsigned)((max_blocks + BLOCKS_PER_GROUP - 1) / BLOCKS_PER_GROUP), (unsigned)planes.size()), dim3(LANES), 0, s,
                            d_planes_tab, d_coef, d_quant, d_planes);
-        JPEG_TRY(hipGetLastError());
+        UNIT_DRAIN_TRY(hipGetLastError());
         tm.end();
         tm.begin(JPEG_T_COLOUR);
         hipLaunchKernelGGL(k_jpeg_colour, dim3(grid_quads(max_px), (unsigned)images.size()), dim3(LANES), 0, s, d_images, d_planes, d_full);
-        JPEG_TRY(hipGetLastError());
+        UNIT_DRAIN_TRY(hipGetLastError());
         tm.end();
         const unsigned char* d_result = d_full;
         std::vector<long long> result_off(member.size());
@@ -352,10 +347,10 @@ int jpeg_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr
         tm.begin(JPEG_T_DOWNLOAD);
         for (size_t g = 0; g < member.size(); ++g) {
             const int i = member[g];
-            JPEG_TRY(hipMemcpyAsync(out + out_ptr[i], d_result + result_off[g], (size_t)(out_ptr[i + 1] - out_ptr[i]), hipMemcpyDeviceToHost, s));
+            UNIT_DRAIN_TRY(hipMemcpyAsync(out + out_ptr[i], d_result + result_off[g], (size_t)(out_ptr[i + 1] - out_ptr[i]), hipMemcpyDeviceToHost, s));
         }
         tm.end();
-        JPEG_TRY(hipStreamSynchronize(s));                     // the host tables and the group's arena go away below
+        UNIT_DRAIN_TRY(hipStreamSynchronize(s));                     // the host tables and the group's arena go away below
     }
     if (timing) {
         tm.collect(timing);
@@ -373,12 +368,12 @@ int resize_images(hipStream_t s, int device, int n_images, const int64_t* img_pt
     for (int i = 0; i < n_images; ++i) {
         ResizeJob& J = all[(size_t)i];
         J = ResizeJob{ width[i], height[i], resized_length(width[i], factor), resized_length(height[i], factor), channels, 0 };
-        if (J.ow == 0 || J.oh == 0) return JPEG_ERR_SIZE;                       // before the first write
+        if (J.ow == 0 || J.oh == 0) return UNIT_ERR_SIZE;                       // before the first write
         optr[(size_t)i + 1] = optr[(size_t)i] + (int64_t)J.ow * J.oh * channels;
     }
     for (int i = 0; i <= n_images; ++i) out_ptr[i] = optr[(size_t)i];
     *total = out_ptr[n_images];
-    if (*total > cap) return JPEG_ERR_CAPACITY;
+    if (*total > cap) return UNIT_ERR_CAPACITY;
 
     PhaseTimer tm{ s, timing != nullptr, {}, {} };
     int n_groups = 0;
@@ -393,19 +388,19 @@ int resize_images(hipStream_t s, int device, int n_images, const int64_t* img_pt
         for (ResizeJob& J : jobs) { J.src = n_src; n_src += align4((long long)J.w * J.h * channels); }
         DeviceArena scratch(device);
         unsigned char *d_src, *d_dst = nullptr;
-        JPEG_ALLOC(scratch, d_src, unsigned char, (size_t)n_src);
+        UNIT_DRAIN_ALLOC(scratch, d_src, unsigned char, (size_t)n_src);
         tm.begin(JPEG_T_UPLOAD);
         for (int i = i0; i < i1; ++i)
-            JPEG_TRY(hipMemcpyAsync(d_src + jobs[(size_t)(i - i0)].src, px + img_ptr[i], (size_t)(img_ptr[i + 1] - img_ptr[i]), hipMemcpyHostToDevice, s));
+            UNIT_DRAIN_TRY(hipMemcpyAsync(d_src + jobs[(size_t)(i - i0)].src, px + img_ptr[i], (size_t)(img_ptr[i + 1] - img_ptr[i]), hipMemcpyHostToDevice, s));
         tm.end();
         std::vector<long long> dst_off;
         const int rc = launch_resize(s, scratch, tm, jobs, factor, d_src, &d_dst, dst_off);
         if (rc) return rc;
         tm.begin(JPEG_T_DOWNLOAD);
         for (int i = i0; i < i1; ++i)
-            JPEG_TRY(hipMemcpyAsync(out + out_ptr[i], d_dst + dst_off[(size_t)(i - i0)], (size_t)(out_ptr[i + 1] - out_ptr[i]), hipMemcpyDeviceToHost, s));
+            UNIT_DRAIN_TRY(hipMemcpyAsync(out + out_ptr[i], d_dst + dst_off[(size_t)(i - i0)], (size_t)(out_ptr[i + 1] - out_ptr[i]), hipMemcpyDeviceToHost, s));
         tm.end();
-        JPEG_TRY(hipStreamSynchronize(s));
+        UNIT_DRAIN_TRY(hipStreamSynchronize(s));
         i0 = i1;
     }
     if (timing) {

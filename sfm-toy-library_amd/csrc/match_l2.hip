@@ -202,9 +202,6 @@ __global__ __launch_bounds__(256) void k_l2_scatter(long long n_rows, const int*
     out_d[o] = best_d[r];
 }
 
-#define L2_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define L2_ALLOC(ptr, T, n) do { ptr = scratch.alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 unsigned grid_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -238,9 +235,7 @@ int match_features_l2(hipStream_t s, int device, int n_images, const int64_t* im
     const int dp = (dims + MATCH_L2_PAD - 1) / MATCH_L2_PAD * MATCH_L2_PAD;
     const int stage_rows = std::min(256, MATCH_L2_STAGE_FLOATS / dp / GROUP * GROUP);     // 256 at dp = 32 .. 16 at dp = 512
     const long long n_desc = img_ptr[n_images];
-    hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-    struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 5; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } eg{ ev };
-    if (timing) for (int i = 0; i < 5; ++i) L2_TRY(hipEventCreate(&ev[i]));
+    PhaseTimer tm{ s, timing != nullptr, {}, {} };
     // allocations first (the arena zeroes them), then the stream work
     const int n_items = (int)items.size();
     const int n_batches = (n_items + MATCH_L2_BATCH_TILES - 1) / MATCH_L2_BATCH_TILES;
@@ -262,44 +257,44 @@ int match_features_l2(hipStream_t s, int device, int n_images, const int64_t* im
     float* d_bestd;
     int *d_bestt, *d_flag, *d_pos, *d_qidx;
     long long *d_prow, *d_pptr;
-    L2_ALLOC(d_desc, float, (size_t)std::max(n_desc, 1ll) * dp);
-    L2_ALLOC(d_pairs, L2Pair, pairs.size());
-    L2_ALLOC(d_items, L2Item, items.size());
-    L2_ALLOC(d_keys, ulonglong2, (size_t)key_slots);
-    L2_ALLOC(d_bestt, int, (size_t)n_rows);
-    L2_ALLOC(d_bestd, float, (size_t)n_rows);
-    L2_ALLOC(d_flag, int, (size_t)n_rows);
-    L2_ALLOC(d_qidx, int, (size_t)n_rows);
-    L2_ALLOC(d_pos, int, (size_t)n_rows + 1);
-    L2_ALLOC(d_prow, long long, prow.size());
-    L2_ALLOC(d_pptr, long long, prow.size());
+    UNIT_ALLOC(scratch, d_desc, float, (size_t)std::max(n_desc, 1ll) * dp);
+    UNIT_ALLOC(scratch, d_pairs, L2Pair, pairs.size());
+    UNIT_ALLOC(scratch, d_items, L2Item, items.size());
+    UNIT_ALLOC(scratch, d_keys, ulonglong2, (size_t)key_slots);
+    UNIT_ALLOC(scratch, d_bestt, int, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_bestd, float, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_flag, int, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_qidx, int, (size_t)n_rows);
+    UNIT_ALLOC(scratch, d_pos, int, (size_t)n_rows + 1);
+    UNIT_ALLOC(scratch, d_prow, long long, prow.size());
+    UNIT_ALLOC(scratch, d_pptr, long long, prow.size());
     size_t tmp_bytes = 0;
-    L2_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
+    UNIT_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
     void* d_tmp = scratch.alloc(tmp_bytes ? tmp_bytes : 1);
     if (!d_tmp) return (int)hipErrorOutOfMemory;
     const long long ocap = std::min<long long>(std::max<long long>(cap, 0), n_rows);
     int *d_oq, *d_ot;
     float* d_od;
-    L2_ALLOC(d_oq, int, (size_t)std::max(ocap, 1ll));
-    L2_ALLOC(d_ot, int, (size_t)std::max(ocap, 1ll));
-    L2_ALLOC(d_od, float, (size_t)std::max(ocap, 1ll));
+    UNIT_ALLOC(scratch, d_oq, int, (size_t)std::max(ocap, 1ll));
+    UNIT_ALLOC(scratch, d_ot, int, (size_t)std::max(ocap, 1ll));
+    UNIT_ALLOC(scratch, d_od, float, (size_t)std::max(ocap, 1ll));
 
     // upload: rows of exactly dp floats go as they are, others are padded with zeros on the host
-    if (timing) L2_TRY(hipEventRecord(ev[0], s));
+    tm.begin(0);
     std::vector<float> padded;
     if (n_desc > 0) {
         if (dims == dp) {
-            L2_TRY(hipMemcpyAsync(d_desc, desc, (size_t)n_desc * dp * sizeof(float), hipMemcpyHostToDevice, s));
+            UNIT_TRY(hipMemcpyAsync(d_desc, desc, (size_t)n_desc * dp * sizeof(float), hipMemcpyHostToDevice, s));
         } else {
             padded.assign((size_t)n_desc * dp, 0.0f);
             for (long long i = 0; i < n_desc; ++i) std::memcpy(&padded[(size_t)i * dp], desc + (size_t)i * dims, (size_t)dims * sizeof(float));
-            L2_TRY(hipMemcpyAsync(d_desc, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice, s));
+            UNIT_TRY(hipMemcpyAsync(d_desc, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice, s));
         }
     }
-    L2_TRY(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(L2Pair) * pairs.size(), hipMemcpyHostToDevice, s));
-    L2_TRY(hipMemcpyAsync(d_items, items.data(), sizeof(L2Item) * items.size(), hipMemcpyHostToDevice, s));
-    L2_TRY(hipMemcpyAsync(d_prow, prow.data(), sizeof(long long) * prow.size(), hipMemcpyHostToDevice, s));
-    if (timing) L2_TRY(hipEventRecord(ev[1], s));
+    UNIT_TRY(hipMemcpyAsync(d_pairs, pairs.data(), sizeof(L2Pair) * pairs.size(), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_items, items.data(), sizeof(L2Item) * items.size(), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_prow, prow.data(), sizeof(long long) * prow.size(), hipMemcpyHostToDevice, s));
+    tm.next(1);
 
     for (int b = 0; b < n_batches; ++b) {
         const int i0 = b * MATCH_L2_BATCH_TILES, nb = std::min(n_items, i0 + MATCH_L2_BATCH_TILES) - i0;
@@ -310,31 +305,27 @@ int match_features_l2(hipStream_t s, int device, int n_images, const int64_t* im
         hipLaunchKernelGGL(k_l2_merge, dim3((unsigned)nb), dim3(LANES), 0, s, d_pairs, d_items + i0, slices[(size_t)b], stride, d_keys, ratio,
                            d_bestt, d_bestd, d_flag, d_qidx);
     }
-    if (timing) L2_TRY(hipEventRecord(ev[2], s));
-    L2_TRY(hipMemsetAsync(d_pos, 0, sizeof(int), s));
-    L2_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
+    tm.next(2);
+    UNIT_TRY(hipMemsetAsync(d_pos, 0, sizeof(int), s));
+    UNIT_TRY(hipcub::DeviceScan::InclusiveSum(d_tmp, tmp_bytes, d_flag, d_pos + 1, (int)n_rows, s));
     hipLaunchKernelGGL(k_l2_pair_ptr, dim3(grid_for(n_pairs + 1)), dim3(256), 0, s, n_pairs, d_prow, d_pos, d_pptr);
     hipLaunchKernelGGL(k_l2_scatter, dim3(grid_for(n_rows)), dim3(256), 0, s, n_rows, d_flag, d_pos, d_bestt, d_bestd, d_qidx, ocap, d_oq, d_ot, d_od);
-    L2_TRY(hipGetLastError());
-    if (timing) L2_TRY(hipEventRecord(ev[3], s));
-    L2_TRY(hipMemcpyAsync(pair_ptr, d_pptr, sizeof(long long) * prow.size(), hipMemcpyDeviceToHost, s));
-    L2_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipGetLastError());
+    tm.next(3);
+    UNIT_TRY(hipMemcpyAsync(pair_ptr, d_pptr, sizeof(long long) * prow.size(), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipStreamSynchronize(s));
     const long long tot = pair_ptr[n_pairs];
     *total = tot;
-    if (tot > cap) return MATCH_L2_ERR_CAPACITY;
+    if (tot > cap) return UNIT_ERR_CAPACITY;
     if (tot > 0) {
-        L2_TRY(hipMemcpyAsync(query_idx, d_oq, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        L2_TRY(hipMemcpyAsync(train_idx, d_ot, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        if (distance) L2_TRY(hipMemcpyAsync(distance, d_od, sizeof(float) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(query_idx, d_oq, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(train_idx, d_ot, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        if (distance) UNIT_TRY(hipMemcpyAsync(distance, d_od, sizeof(float) * (size_t)tot, hipMemcpyDeviceToHost, s));
     }
-    if (timing) L2_TRY(hipEventRecord(ev[4], s));
-    L2_TRY(hipStreamSynchronize(s));
+    tm.end();
+    UNIT_TRY(hipStreamSynchronize(s));
     if (timing) {
-        for (int i = 0; i < 4; ++i) {
-            float ms = 0.f;
-            L2_TRY(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-            timing[i] = ms;
-        }
+        tm.collect(timing);
         timing[4] = n_batches;
     }
     return 0;

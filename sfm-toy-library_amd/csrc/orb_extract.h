@@ -3,12 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unit_common.h"
+
 #include "../../include/sfmba.h"
 
 namespace sfmba {
 
-// return values besides 0 (ok) and positive hipError_t codes
-enum { ORB_ERR_CAPACITY = -1 };
+// return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 // The score and the smoothing kernels work on tiles of this many pixels of a level (plus a 3-pixel halo), one block of 256 lanes
 // per tile, four pixels per lane.

@@ -316,9 +316,6 @@ __global__ __launch_bounds__(LANES) void k_orb_pack(long long total, int n_image
     R[o] = R_in[src];
 }
 
-#define ORB_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define ORB_ALLOC(arena, ptr, T, n) do { ptr = (arena).alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 long long align4(long long n) { return (n + 3) & ~3ll; }
 // no two candidates touch (each is strictly above its 8 neighbours), so a 2 x 2 cell of the admissible area holds at most one
 long long candidate_bound(int w, int h) {
@@ -332,24 +329,6 @@ const signed char* pattern_table() {
     std::call_once(once, [] { table.resize((size_t)ORB_BINS * ORB_PAIRS * 4); orb_build_pattern(table.data()); });
     return table.data();
 }
-
-// HIP-event time per phase, summed; inert without a timing array
-struct PhaseTimer {
-    hipStream_t s;
-    bool on;
-    std::vector<hipEvent_t> ev;
-    std::vector<int> phase;
-    void begin(int p) { if (on) { mark(); phase.push_back(p); } }
-    void end() { if (on) mark(); }
-    void mark() { hipEvent_t e = nullptr; if (hipEventCreate(&e) == hipSuccess) (void)hipEventRecord(e, s); ev.push_back(e); }
-    void collect(double* t) {
-        for (size_t i = 0; i < phase.size(); ++i) {
-            float ms = 0.f;
-            if (ev[2 * i] && ev[2 * i + 1] && hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]) == hipSuccess) t[phase[i]] += ms;
-        }
-    }
-    ~PhaseTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-};
 
 struct ImagePlan {
     int levels;                                     // levels with key points (a prefix: sizes do not grow)
@@ -403,17 +382,17 @@ int orb_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
     unsigned char* d_sdesc;
     int *d_sxy, *d_sbin, *d_ccount;
     long long *d_sR, *d_stage_cur;
-    ORB_ALLOC(keep, d_table, signed char, (size_t)ORB_BINS * ORB_PAIRS * 4);
-    ORB_ALLOC(keep, d_skp, sfmba_orb_keypoint, (size_t)stage_rows);
-    ORB_ALLOC(keep, d_sdesc, unsigned char, (size_t)stage_rows * ORB_DESC_BYTES);
-    ORB_ALLOC(keep, d_sxy, int, (size_t)stage_rows * 2);
-    ORB_ALLOC(keep, d_sbin, int, (size_t)stage_rows);
-    ORB_ALLOC(keep, d_sR, long long, (size_t)stage_rows);
-    ORB_ALLOC(keep, d_ccount, int, (size_t)n_images * n_levels);
-    ORB_ALLOC(keep, d_stage_cur, long long, (size_t)n_images);
+    UNIT_ALLOC(keep, d_table, signed char, (size_t)ORB_BINS * ORB_PAIRS * 4);
+    UNIT_ALLOC(keep, d_skp, sfmba_orb_keypoint, (size_t)stage_rows);
+    UNIT_ALLOC(keep, d_sdesc, unsigned char, (size_t)stage_rows * ORB_DESC_BYTES);
+    UNIT_ALLOC(keep, d_sxy, int, (size_t)stage_rows * 2);
+    UNIT_ALLOC(keep, d_sbin, int, (size_t)stage_rows);
+    UNIT_ALLOC(keep, d_sR, long long, (size_t)stage_rows);
+    UNIT_ALLOC(keep, d_ccount, int, (size_t)n_images * n_levels);
+    UNIT_ALLOC(keep, d_stage_cur, long long, (size_t)n_images);
     tm.begin(ORB_T_UPLOAD);
-    ORB_TRY(hipMemcpyAsync(d_table, pattern_table(), (size_t)ORB_BINS * ORB_PAIRS * 4, hipMemcpyHostToDevice, s));
-    ORB_TRY(hipMemcpyAsync(d_stage_cur, stage_base.data(), sizeof(long long) * (size_t)n_images, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_table, pattern_table(), (size_t)ORB_BINS * ORB_PAIRS * 4, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_stage_cur, stage_base.data(), sizeof(long long) * (size_t)n_images, hipMemcpyHostToDevice, s));
     tm.end();
 
     int n_groups = 0;
@@ -460,42 +439,42 @@ int orb_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
         unsigned char *d_raw = nullptr, *d_pyr[2], *d_score, *d_smooth, *d_flag;
         int *d_pos, *d_total;
         uint64_t *d_key[2], *d_ent[2];
-        ORB_ALLOC(scratch, d_tab, OrbLevel, tab.size());
-        ORB_ALLOC(scratch, d_seg, OrbSegment, (size_t)ng);
-        if (channels == 3) ORB_ALLOC(scratch, d_raw, unsigned char, (size_t)r0 * 3);
-        ORB_ALLOC(scratch, d_pyr[0], unsigned char, (size_t)r0);
-        ORB_ALLOC(scratch, d_pyr[1], unsigned char, (size_t)r0);
-        ORB_ALLOC(scratch, d_score, unsigned char, (size_t)r0);
-        ORB_ALLOC(scratch, d_smooth, unsigned char, (size_t)r0);
-        ORB_ALLOC(scratch, d_flag, unsigned char, (size_t)r0 + 4);
-        ORB_ALLOC(scratch, d_pos, int, (size_t)r0 + 4);
-        ORB_ALLOC(scratch, d_total, int, 1);
+        UNIT_ALLOC(scratch, d_tab, OrbLevel, tab.size());
+        UNIT_ALLOC(scratch, d_seg, OrbSegment, (size_t)ng);
+        if (channels == 3) UNIT_ALLOC(scratch, d_raw, unsigned char, (size_t)r0 * 3);
+        UNIT_ALLOC(scratch, d_pyr[0], unsigned char, (size_t)r0);
+        UNIT_ALLOC(scratch, d_pyr[1], unsigned char, (size_t)r0);
+        UNIT_ALLOC(scratch, d_score, unsigned char, (size_t)r0);
+        UNIT_ALLOC(scratch, d_smooth, unsigned char, (size_t)r0);
+        UNIT_ALLOC(scratch, d_flag, unsigned char, (size_t)r0 + 4);
+        UNIT_ALLOC(scratch, d_pos, int, (size_t)r0 + 4);
+        UNIT_ALLOC(scratch, d_total, int, 1);
         for (int b = 0; b < 2; ++b) {
-            ORB_ALLOC(scratch, d_key[b], uint64_t, (size_t)cand_cap);
-            ORB_ALLOC(scratch, d_ent[b], uint64_t, (size_t)cand_cap);
+            UNIT_ALLOC(scratch, d_key[b], uint64_t, (size_t)cand_cap);
+            UNIT_ALLOC(scratch, d_ent[b], uint64_t, (size_t)cand_cap);
         }
         int img_bits = 1;
         while ((1 << img_bits) < ng) ++img_bits;
         size_t scan_bytes = 0, sort_bytes = 0, sort2_bytes = 0;
         hipcub::TransformInputIterator<int, ToInt, const unsigned char*> flags_in(d_flag, ToInt());
-        ORB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, flags_in, d_pos, (int)(r0 + 1), s));
+        UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, flags_in, d_pos, (int)(r0 + 1), s));
         {
             hipcub::DoubleBuffer<uint64_t> k(d_key[0], d_key[1]), e(d_ent[0], d_ent[1]);
-            ORB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, e, (int)std::max(cand_cap, 1ll), 0, 64, s));
-            ORB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort2_bytes, e, k, (int)std::max(cand_cap, 1ll), 32, 32 + img_bits, s));
+            UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, e, (int)std::max(cand_cap, 1ll), 0, 64, s));
+            UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort2_bytes, e, k, (int)std::max(cand_cap, 1ll), 32, 32 + img_bits, s));
         }
         const size_t tmp_bytes = std::max(std::max(scan_bytes, sort_bytes), std::max(sort2_bytes, (size_t)1));
         void* d_tmp = scratch.alloc(tmp_bytes);
         if (!d_tmp) return (int)hipErrorOutOfMemory;
 
         tm.begin(ORB_T_UPLOAD);
-        ORB_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(OrbLevel) * tab.size(), hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(OrbLevel) * tab.size(), hipMemcpyHostToDevice, s));
         for (int i = 0; i < ng; ++i) {
             const OrbLevel& T = tab[(size_t)i];
             if (T.w == 0) continue;
             const size_t px = (size_t)T.w * T.h;
-            if (channels == 3) ORB_TRY(hipMemcpyAsync(d_raw + 3 * T.off, pixels + img_ptr[i0 + i], 3 * px, hipMemcpyHostToDevice, s));
-            else               ORB_TRY(hipMemcpyAsync(d_pyr[0] + T.off, pixels + img_ptr[i0 + i], px, hipMemcpyHostToDevice, s));
+            if (channels == 3) UNIT_TRY(hipMemcpyAsync(d_raw + 3 * T.off, pixels + img_ptr[i0 + i], 3 * px, hipMemcpyHostToDevice, s));
+            else               UNIT_TRY(hipMemcpyAsync(d_pyr[0] + T.off, pixels + img_ptr[i0 + i], px, hipMemcpyHostToDevice, s));
         }
         tm.end();
 
@@ -523,15 +502,15 @@ int orb_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
             hipLaunchKernelGGL(k_orb_score, g_tiles, dim3(LANES), 0, s, t_l, cur, fast_threshold, d_score);
             tm.end();
             tm.begin(ORB_T_CANDIDATES);
-            ORB_TRY(hipMemsetAsync(d_flag, 0, (size_t)rl + 4, s));
+            UNIT_TRY(hipMemsetAsync(d_flag, 0, (size_t)rl + 4, s));
             hipLaunchKernelGGL(k_orb_flags, g_quads, dim3(LANES), 0, s, t_l, d_score, d_flag);
-            ORB_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, scan_bytes, flags_in, d_pos, (int)(rl + 1), s));
+            UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, scan_bytes, flags_in, d_pos, (int)(rl + 1), s));
             hipLaunchKernelGGL(k_orb_counts, dim3((unsigned)((ng + LANES - 1) / LANES)), dim3(LANES), 0, s, ng, l, n_levels, t_l, d_pos, d_seg,
                                d_stage_cur, d_ccount);
-            ORB_TRY(hipGetLastError());
+            UNIT_TRY(hipGetLastError());
             int n_cand = 0;
-            ORB_TRY(hipMemcpyAsync(&n_cand, d_pos + rl, sizeof(int), hipMemcpyDeviceToHost, s));
-            ORB_TRY(hipStreamSynchronize(s));
+            UNIT_TRY(hipMemcpyAsync(&n_cand, d_pos + rl, sizeof(int), hipMemcpyDeviceToHost, s));
+            UNIT_TRY(hipStreamSynchronize(s));
             if (n_cand < 0 || n_cand > cand_cap) return (int)hipErrorUnknown;          // cannot happen: candidate_bound
             if (n_cand == 0 || quota[l] == 0) { tm.end(); continue; }         // nothing to rank or describe at this level
             hipLaunchKernelGGL(k_orb_compact, g_quads, dim3(LANES), 0, s, t_l, d_flag, d_pos, n_cand, d_ent[0]);
@@ -542,8 +521,8 @@ int orb_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
             tm.begin(ORB_T_SELECT);
             hipcub::DoubleBuffer<uint64_t> k(d_key[0], d_key[1]), e(d_ent[0], d_ent[1]);
             size_t bytes1 = sort_bytes, bytes2 = sort2_bytes;
-            ORB_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, bytes1, k, e, n_cand, 0, 64, s));
-            if (ng > 1) ORB_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, bytes2, e, k, n_cand, 32, 32 + img_bits, s));
+            UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, bytes1, k, e, n_cand, 0, 64, s));
+            if (ng > 1) UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, bytes2, e, k, n_cand, 32, 32 + img_bits, s));
             tm.end();
             tm.begin(ORB_T_SMOOTH);
             hipLaunchKernelGGL(k_orb_smooth, g_tiles, dim3(LANES), 0, s, t_l, cur, d_smooth);
@@ -552,19 +531,19 @@ int orb_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
             const long long waves = std::min<long long>(quota[l], n_cand);
             hipLaunchKernelGGL(k_orb_describe, dim3((unsigned)((waves + LANES / 64 - 1) / (LANES / 64)), (unsigned)ng), dim3(LANES), 0, s, t_l, d_seg,
                                cur, d_smooth, e.Current(), k.Current(), d_table, l, scale[l], d_skp, d_sdesc, d_sxy, d_sbin, d_sR);
-            ORB_TRY(hipGetLastError());
+            UNIT_TRY(hipGetLastError());
             tm.end();
             // the next level's scan and sorts reuse d_pos, d_seg and the sort buffers: in stream order, behind this level's kernels
         }
-        ORB_TRY(hipStreamSynchronize(s));                      // the group's arena goes back to the cache below
+        UNIT_TRY(hipStreamSynchronize(s));                      // the group's arena goes back to the cache below
         i0 = i1;
     }
 
     // kp_ptr from the per-level candidate counts, then the packed rows
     tm.begin(ORB_T_DOWNLOAD);
     std::vector<int> ccount((size_t)n_images * n_levels, 0);
-    ORB_TRY(hipMemcpyAsync(ccount.data(), d_ccount, sizeof(int) * ccount.size(), hipMemcpyDeviceToHost, s));
-    ORB_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipMemcpyAsync(ccount.data(), d_ccount, sizeof(int) * ccount.size(), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < n_images; ++i) {
         long long n = 0;
         for (int l = 0; l < n_levels; ++l) n += std::min(ccount[(size_t)i * n_levels + l], quota[l]);
@@ -572,34 +551,34 @@ int orb_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
     }
     const long long tot = kp_ptr[n_images];
     *total = tot;
-    if (tot > cap) return ORB_ERR_CAPACITY;
+    if (tot > cap) return UNIT_ERR_CAPACITY;
     if (dbg_candidates) std::memcpy(dbg_candidates, ccount.data(), sizeof(int) * ccount.size());
     if (tot > 0) {
         long long *d_kptr, *d_sbase, *d_oR;
         sfmba_orb_keypoint* d_okp;
         unsigned char* d_odesc;
         int *d_oxy, *d_obin;
-        ORB_ALLOC(keep, d_kptr, long long, (size_t)n_images + 1);
-        ORB_ALLOC(keep, d_sbase, long long, (size_t)n_images + 1);
-        ORB_ALLOC(keep, d_okp, sfmba_orb_keypoint, (size_t)tot);
-        ORB_ALLOC(keep, d_odesc, unsigned char, (size_t)tot * ORB_DESC_BYTES);
-        ORB_ALLOC(keep, d_oxy, int, (size_t)tot * 2);
-        ORB_ALLOC(keep, d_obin, int, (size_t)tot);
-        ORB_ALLOC(keep, d_oR, long long, (size_t)tot);
+        UNIT_ALLOC(keep, d_kptr, long long, (size_t)n_images + 1);
+        UNIT_ALLOC(keep, d_sbase, long long, (size_t)n_images + 1);
+        UNIT_ALLOC(keep, d_okp, sfmba_orb_keypoint, (size_t)tot);
+        UNIT_ALLOC(keep, d_odesc, unsigned char, (size_t)tot * ORB_DESC_BYTES);
+        UNIT_ALLOC(keep, d_oxy, int, (size_t)tot * 2);
+        UNIT_ALLOC(keep, d_obin, int, (size_t)tot);
+        UNIT_ALLOC(keep, d_oR, long long, (size_t)tot);
         static_assert(sizeof(long long) == sizeof(int64_t), "kp_ptr goes to the device as it is");
-        ORB_TRY(hipMemcpyAsync(d_kptr, kp_ptr, sizeof(long long) * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
-        ORB_TRY(hipMemcpyAsync(d_sbase, stage_base.data(), sizeof(long long) * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_kptr, kp_ptr, sizeof(long long) * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_sbase, stage_base.data(), sizeof(long long) * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_orb_pack, dim3((unsigned)((tot + LANES - 1) / LANES)), dim3(LANES), 0, s, tot, n_images, d_kptr, d_sbase, d_skp, d_sdesc,
                            d_sxy, d_sbin, d_sR, d_okp, d_odesc, d_oxy, d_obin, d_oR);
-        ORB_TRY(hipGetLastError());
-        ORB_TRY(hipMemcpyAsync(kp, d_okp, sizeof(sfmba_orb_keypoint) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        ORB_TRY(hipMemcpyAsync(desc, d_odesc, (size_t)tot * ORB_DESC_BYTES, hipMemcpyDeviceToHost, s));
-        if (dbg_level_xy) ORB_TRY(hipMemcpyAsync(dbg_level_xy, d_oxy, sizeof(int) * 2 * (size_t)tot, hipMemcpyDeviceToHost, s));
-        if (dbg_bin) ORB_TRY(hipMemcpyAsync(dbg_bin, d_obin, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
-        if (dbg_harris) ORB_TRY(hipMemcpyAsync(dbg_harris, d_oR, sizeof(long long) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipGetLastError());
+        UNIT_TRY(hipMemcpyAsync(kp, d_okp, sizeof(sfmba_orb_keypoint) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(desc, d_odesc, (size_t)tot * ORB_DESC_BYTES, hipMemcpyDeviceToHost, s));
+        if (dbg_level_xy) UNIT_TRY(hipMemcpyAsync(dbg_level_xy, d_oxy, sizeof(int) * 2 * (size_t)tot, hipMemcpyDeviceToHost, s));
+        if (dbg_bin) UNIT_TRY(hipMemcpyAsync(dbg_bin, d_obin, sizeof(int) * (size_t)tot, hipMemcpyDeviceToHost, s));
+        if (dbg_harris) UNIT_TRY(hipMemcpyAsync(dbg_harris, d_oR, sizeof(long long) * (size_t)tot, hipMemcpyDeviceToHost, s));
     }
     tm.end();
-    ORB_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipStreamSynchronize(s));
     if (timing) {
         tm.collect(timing);
         timing[ORB_T_GROUPS] = n_groups;

@@ -14,7 +14,7 @@ namespace sfmba {
 enum { PNG_T_INFLATE = JPEG_T_ENTROPY, PNG_T_UPLOAD = JPEG_T_UPLOAD, PNG_T_UNFILTER = JPEG_T_IDCT, PNG_T_PIXELS = JPEG_T_COLOUR,
        PNG_T_RESIZE = JPEG_T_RESIZE, PNG_T_DOWNLOAD = JPEG_T_DOWNLOAD, PNG_T_GROUPS = JPEG_T_GROUPS, PNG_T_COUNT = JPEG_T_COUNT };
 
-// Host pointers in and out; arguments already validated (see include/sfmba.h for the contract).  Returns 0, a JPEG_ERR_* value or a
+// Host pointers in and out; arguments already validated (see include/sfmba.h for the contract).  Returns 0, a UNIT_ERR_* value or a
 // positive hipError_t.  timing (may be NULL): [PNG_T_COUNT] = host wall milliseconds of the chunk walk + inflate, then HIP-event
 // milliseconds on `s` summed over groups -- upload, unfilter kernel, pixel kernel, resize kernel, download -- and the number of groups.
 int png_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr, const unsigned char* bytes, float factor,

@@ -200,9 +200,6 @@ __global__ __launch_bounds__(PIXEL_LANES) void k_png_pixels(const PngImage* __re
     }
 }
 
-#define PNG_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipStreamSynchronize(s); return (int)e_; } } while (0)
-#define PNG_ALLOC(arena, ptr, T, n) do { ptr = (arena).alloc_n<T>(n); if (!ptr) { (void)hipStreamSynchronize(s); return (int)hipErrorOutOfMemory; } } while (0)
-
 long long align4(long long n) { return (n + 3) & ~3ll; }
 double now_ms() { return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -231,9 +228,9 @@ int png_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr,
         if (H.status != PNG_OK) continue;
         ow[(size_t)i] = resize ? resized_length(H.width, factor) : H.width;
         oh[(size_t)i] = resize ? resized_length(H.height, factor) : H.height;
-        if (ow[(size_t)i] == 0 || oh[(size_t)i] == 0) return JPEG_ERR_SIZE;
+        if (ow[(size_t)i] == 0 || oh[(size_t)i] == 0) return UNIT_ERR_SIZE;
     }
-    if (!png_inflate_batch(n_images, file_ptr, bytes, 16, hdr, streams)) return JPEG_ERR_HOST_ALLOC;
+    if (!png_inflate_batch(n_images, file_ptr, bytes, 16, hdr, streams)) return UNIT_ERR_HOST_ALLOC;
     if (timing) timing[PNG_T_INFLATE] = now_ms() - t0;
 
     out_ptr[0] = 0;
@@ -243,7 +240,7 @@ int png_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr,
         out_ptr[i + 1] = out_ptr[i] + (H.status == PNG_OK ? (long long)ow[(size_t)i] * oh[(size_t)i] * H.channels : 0);
     }
     *total = out_ptr[n_images];
-    if (*total > cap) return JPEG_ERR_CAPACITY;
+    if (*total > cap) return UNIT_ERR_CAPACITY;
 
     PhaseTimer tm{ s, timing != nullptr, {}, {} };
     int n_groups = 0;
@@ -285,26 +282,26 @@ int png_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr,
         DeviceArena scratch(device);
         PngImage* d_images;
         unsigned char *d_palettes, *d_streams, *d_full;
-        PNG_ALLOC(scratch, d_images, PngImage, images.size());
-        PNG_ALLOC(scratch, d_palettes, unsigned char, palettes.size());
-        PNG_ALLOC(scratch, d_streams, unsigned char, (size_t)n_stream);
-        PNG_ALLOC(scratch, d_full, unsigned char, (size_t)n_out);
+        UNIT_DRAIN_ALLOC(scratch, d_images, PngImage, images.size());
+        UNIT_DRAIN_ALLOC(scratch, d_palettes, unsigned char, palettes.size());
+        UNIT_DRAIN_ALLOC(scratch, d_streams, unsigned char, (size_t)n_stream);
+        UNIT_DRAIN_ALLOC(scratch, d_full, unsigned char, (size_t)n_out);
         tm.begin(PNG_T_UPLOAD);
-        PNG_TRY(hipMemcpyAsync(d_images, images.data(), sizeof(PngImage) * images.size(), hipMemcpyHostToDevice, s));
-        PNG_TRY(hipMemcpyAsync(d_palettes, palettes.data(), palettes.size(), hipMemcpyHostToDevice, s));
+        UNIT_DRAIN_TRY(hipMemcpyAsync(d_images, images.data(), sizeof(PngImage) * images.size(), hipMemcpyHostToDevice, s));
+        UNIT_DRAIN_TRY(hipMemcpyAsync(d_palettes, palettes.data(), palettes.size(), hipMemcpyHostToDevice, s));
         for (size_t g = 0; g < member.size(); ++g) {
             const std::vector<unsigned char>& st = streams[(size_t)member[g]];
-            PNG_TRY(hipMemcpyAsync(d_streams + images[g].stream, st.data(), st.size(), hipMemcpyHostToDevice, s));
+            UNIT_DRAIN_TRY(hipMemcpyAsync(d_streams + images[g].stream, st.data(), st.size(), hipMemcpyHostToDevice, s));
         }
         tm.end();
         tm.begin(PNG_T_UNFILTER);
         hipLaunchKernelGGL(k_png_unfilter, dim3((unsigned)images.size()), dim3(WAVE), 0, s, d_images, d_streams);
-        PNG_TRY(hipGetLastError());
+        UNIT_DRAIN_TRY(hipGetLastError());
         tm.end();
         tm.begin(PNG_T_PIXELS);
         hipLaunchKernelGGL(k_png_pixels, dim3((unsigned)((max_px + PIXEL_LANES - 1) / PIXEL_LANES), (unsigned)images.size()), dim3(PIXEL_LANES), 0, s,
                            d_images, d_streams, d_palettes, d_full);
-        PNG_TRY(hipGetLastError());
+        UNIT_DRAIN_TRY(hipGetLastError());
         tm.end();
         const unsigned char* d_result = d_full;
         std::vector<long long> result_off(member.size());
@@ -318,10 +315,10 @@ int png_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr,
         tm.begin(PNG_T_DOWNLOAD);
         for (size_t g = 0; g < member.size(); ++g) {
             const int i = member[g];
-            PNG_TRY(hipMemcpyAsync(out + out_ptr[i], d_result + result_off[g], (size_t)(out_ptr[i + 1] - out_ptr[i]), hipMemcpyDeviceToHost, s));
+            UNIT_DRAIN_TRY(hipMemcpyAsync(out + out_ptr[i], d_result + result_off[g], (size_t)(out_ptr[i + 1] - out_ptr[i]), hipMemcpyDeviceToHost, s));
         }
         tm.end();
-        PNG_TRY(hipStreamSynchronize(s));                      // the host tables and the group's arena go away below
+        UNIT_DRAIN_TRY(hipStreamSynchronize(s));                      // the host tables and the group's arena go away below
     }
     if (timing) {
         tm.collect(timing);

@@ -358,9 +358,6 @@ __global__ __launch_bounds__(PNP_REFINE_THREADS) void k_pnp_select_refine(int n_
     }
 }
 
-#define PNP_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define PNP_ALLOC(ptr, T, n) do { ptr = arena.alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 }  // namespace
 
 int pnp_ransac(hipStream_t s, int device, int n_prob, const int64_t* prob_ptr, const float* xyz, const float* uv, const float* K,
@@ -377,13 +374,11 @@ int pnp_ransac(hipStream_t s, int device, int n_prob, const int64_t* prob_ptr, c
     const long long max_threads = 0xffffffffll;
     if (max_n >= (long long)INT_MAX || (long long)n_prob * tiles * PNP_SCORE_THREADS > max_threads || n_items + HYP_THREADS > max_threads ||
         (long long)n_prob * PNP_REFINE_THREADS > max_threads)
-        return PNP_ERR_TOO_LARGE;
+        return UNIT_ERR_TOO_LARGE;
     const PnpIntrinsics k{ (double)K[0], (double)K[4], (double)K[2], (double)K[5] };
 
     DeviceArena arena(device);
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    struct EventGuard { hipEvent_t* e; ~EventGuard() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } eg{ ev };
-    if (timing) for (int i = 0; i < 4; ++i) PNP_TRY(hipEventCreate(&ev[i]));
+    PhaseTimer tm{ s, timing != nullptr, {}, {} };
     // allocations first (the arena zeroes them: the masks of status 1 / 2 problems stay zero), then the stream work
     long long* d_ptr;
     float *d_xyz, *d_uv, *d_kp;
@@ -391,24 +386,24 @@ int pnp_ransac(hipStream_t s, int device, int n_prob, const int64_t* prob_ptr, c
     int* d_count;
     unsigned char* d_inl;
     sfmba_pnp_result* d_res;
-    PNP_ALLOC(d_ptr, long long, (size_t)n_prob + 1);
-    PNP_ALLOC(d_xyz, float, (size_t)3 * total);
-    PNP_ALLOC(d_uv, float, (size_t)2 * total);
-    PNP_ALLOC(d_hpose, double, (size_t)12 * n_items);
-    PNP_ALLOC(d_kp, float, (size_t)12 * n_items);
-    PNP_ALLOC(d_count, int, (size_t)n_items);
-    PNP_ALLOC(d_pose, double, (size_t)12 * n_prob);
-    PNP_ALLOC(d_inl, unsigned char, (size_t)total);
-    PNP_ALLOC(d_res, sfmba_pnp_result, (size_t)n_prob);
+    UNIT_ALLOC(arena, d_ptr, long long, (size_t)n_prob + 1);
+    UNIT_ALLOC(arena, d_xyz, float, (size_t)3 * total);
+    UNIT_ALLOC(arena, d_uv, float, (size_t)2 * total);
+    UNIT_ALLOC(arena, d_hpose, double, (size_t)12 * n_items);
+    UNIT_ALLOC(arena, d_kp, float, (size_t)12 * n_items);
+    UNIT_ALLOC(arena, d_count, int, (size_t)n_items);
+    UNIT_ALLOC(arena, d_pose, double, (size_t)12 * n_prob);
+    UNIT_ALLOC(arena, d_inl, unsigned char, (size_t)total);
+    UNIT_ALLOC(arena, d_res, sfmba_pnp_result, (size_t)n_prob);
 
-    if (timing) PNP_TRY(hipEventRecord(ev[0], s));
+    tm.begin(0);
     static_assert(sizeof(long long) == sizeof(int64_t), "prob_ptr is uploaded as it is");
-    PNP_TRY(hipMemcpyAsync(d_ptr, prob_ptr, sizeof(int64_t) * ((size_t)n_prob + 1), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_ptr, prob_ptr, sizeof(int64_t) * ((size_t)n_prob + 1), hipMemcpyHostToDevice, s));
     if (total > 0) {
-        PNP_TRY(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * (size_t)total, hipMemcpyHostToDevice, s));
-        PNP_TRY(hipMemcpyAsync(d_uv, uv, sizeof(float) * 2 * (size_t)total, hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * (size_t)total, hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_uv, uv, sizeof(float) * 2 * (size_t)total, hipMemcpyHostToDevice, s));
     }
-    if (timing) PNP_TRY(hipEventRecord(ev[1], s));
+    tm.next(1);
     const float thr2 = threshold_px * threshold_px;
     hipLaunchKernelGGL(k_pnp_hypotheses, dim3((unsigned)((n_items + HYP_THREADS - 1) / HYP_THREADS)), dim3(HYP_THREADS), 0, s, n_items, n_hyp,
                        d_ptr, d_xyz, d_uv, k, seed, d_hpose, d_kp, d_count);
@@ -418,22 +413,16 @@ int pnp_ransac(hipStream_t s, int device, int n_prob, const int64_t* prob_ptr, c
                            dim3(PNP_SCORE_THREADS), 0, s, n_hyp, tiles, d_ptr, d_xyz, d_uv, (float)k.cx, (float)k.cy, thr2, d_kp, d_count);
     hipLaunchKernelGGL(k_pnp_select_refine, dim3((unsigned)n_prob), dim3(PNP_REFINE_THREADS), 0, s, n_hyp, d_ptr, d_xyz, d_uv, k, thr2,
                        max_refine_iters, d_hpose, d_kp, d_count, d_pose, d_inl, d_res);
-    PNP_TRY(hipGetLastError());
-    if (timing) PNP_TRY(hipEventRecord(ev[2], s));
-    PNP_TRY(hipMemcpyAsync(pose, d_pose, sizeof(double) * 12 * (size_t)n_prob, hipMemcpyDeviceToHost, s));
-    PNP_TRY(hipMemcpyAsync(result, d_res, sizeof(sfmba_pnp_result) * (size_t)n_prob, hipMemcpyDeviceToHost, s));
-    if (total > 0) PNP_TRY(hipMemcpyAsync(inlier, d_inl, (size_t)total, hipMemcpyDeviceToHost, s));
-    if (hyp_pose) PNP_TRY(hipMemcpyAsync(hyp_pose, d_hpose, sizeof(double) * 12 * (size_t)n_items, hipMemcpyDeviceToHost, s));
-    if (hyp_count) PNP_TRY(hipMemcpyAsync(hyp_count, d_count, sizeof(int) * (size_t)n_items, hipMemcpyDeviceToHost, s));
-    if (timing) PNP_TRY(hipEventRecord(ev[3], s));
-    PNP_TRY(hipStreamSynchronize(s));
-    if (timing) {
-        for (int i = 0; i < 3; ++i) {
-            float ms = 0.f;
-            PNP_TRY(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-            timing[i] = ms;
-        }
-    }
+    UNIT_TRY(hipGetLastError());
+    tm.next(2);
+    UNIT_TRY(hipMemcpyAsync(pose, d_pose, sizeof(double) * 12 * (size_t)n_prob, hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipMemcpyAsync(result, d_res, sizeof(sfmba_pnp_result) * (size_t)n_prob, hipMemcpyDeviceToHost, s));
+    if (total > 0) UNIT_TRY(hipMemcpyAsync(inlier, d_inl, (size_t)total, hipMemcpyDeviceToHost, s));
+    if (hyp_pose) UNIT_TRY(hipMemcpyAsync(hyp_pose, d_hpose, sizeof(double) * 12 * (size_t)n_items, hipMemcpyDeviceToHost, s));
+    if (hyp_count) UNIT_TRY(hipMemcpyAsync(hyp_count, d_count, sizeof(int) * (size_t)n_items, hipMemcpyDeviceToHost, s));
+    tm.end();
+    UNIT_TRY(hipStreamSynchronize(s));
+    if (timing) tm.collect(timing);
     return 0;
 }
 

@@ -1,5 +1,5 @@
 // problem.h -- internal: the sfmba_problem handle and what the units behind include/sfmba.h need of each other
-// (problem_build.hip, lm_solve.hip, sharded_solve.hip, comm_rccl.hip, sfmba_api.hip).  Nothing here is part of the ABI.
+// (problem_build.hip, lm_solve.hip, sharded_solve.hip, comm_rccl.hip, sfmba_api.hip, api_frontend.hip).  Nothing here is part of the ABI.
 #pragma once
 #include "../../include/sfmba.h"
 #include "ba_kernels.h"
@@ -145,6 +145,17 @@ int check_device(int device);
 // The refusal every entry point opens with: NULL, then poisoned (a failed append), then -- where the call needs observations -- empty
 int check_handle(const sfmba_problem* p, bool may_be_empty = true);
 int flush_reset(sfmba_problem* p);      // the device side of sfmba_problem_reset, for the callers that are not a solve (sfmba_api.hip)
+
+// `device` checked and current, a stream + pinned block on it for the duration of one call of an entry point without a problem handle
+struct CallKit {
+    HostKit kit;
+    int open(int device) {
+        if (const int rc = check_device(device)) return rc;
+        HIP_TRY(hipSetDevice(device));
+        return hostkit_acquire(device, &kit) ? SFMBA_OK : fail(SFMBA_ERR_HIP, "stream creation failed");
+    }
+    ~CallKit() { if (kit.stream) (void)hipStreamSynchronize(kit.stream); hostkit_release(kit); }
+};
 
 // What the passes of a ROW-SHARDED rank see (include/sfmba.h, SFMBA_CREATE_ROW_SHARDED): the point passes its own points (pt_order lists
 // them), the camera-major passes its share of the chunks; everything else the whole problem.

@@ -1,25 +1,9 @@
-// sfmba_api.hip -- C ABI of include/sfmba.h: argument checks and dispatch.  The work is in problem_build.hip (structure build),
-// lm_solve.hip (LM driver), sharded_solve.hip (multi-GPU and matrix-free loops), comm_rccl.hip and the kernel units.
+// sfmba_api.hip -- C ABI of include/sfmba.h: the error state, the device checks and the problem / solver entry points (argument
+// checks and dispatch).  The work is in problem_build.hip (structure build), lm_solve.hip (LM driver), sharded_solve.hip (multi-GPU
+// and matrix-free loops), comm_rccl.hip and the kernel units; the front-end entry points are in api_frontend.hip.
 //
 // There is NO CPU fallback in this library: without a HIP device every entry point returns SFMBA_ERR_NO_DEVICE.
-#include "association.h"
-#include "feature_match.h"
-#include "match_l2.h"
 #include "lm_loop.h"
-#include "pnp_ransac.h"
-#include "homography_ransac.h"
-#include "essential_ransac.h"
-#include "orb_extract.h"
-#include "surf_extract.h"
-#include "depth_sweep.h"
-#include "cloud_merge.h"
-#include "flow_track.h"
-#include "flow_math.h"
-#include "jpeg_decode.h"
-#include "jpeg_math.h"
-#include "png_decode.h"
-#include <climits>
-#include <cmath>
 
 using namespace sfmba;
 
@@ -61,19 +45,6 @@ int sfmba::flush_reset(sfmba_problem* p) {
     HIP_TRY(hipMemcpyAsync(p->db.pts[0], p->d_pts0, sizeof(double) * 3 * (size_t)p->ds.npt, hipMemcpyDeviceToDevice, p->stream));
     return upload_default_state(p);
 }
-
-namespace {
-// `device` checked and current, a stream + pinned block on it for the duration of one call of the wrappers below
-struct CallKit {
-    HostKit kit;
-    int open(int device) {
-        if (const int rc = check_device(device)) return rc;
-        HIP_TRY(hipSetDevice(device));
-        return hostkit_acquire(device, &kit) ? SFMBA_OK : fail(SFMBA_ERR_HIP, "stream creation failed");
-    }
-    ~CallKit() { if (kit.stream) (void)hipStreamSynchronize(kit.stream); hostkit_release(kit); }
-};
-}  // namespace
 
 extern "C" {
 void sfmba_options_default(sfmba_options* o) {
@@ -393,774 +364,5 @@ int sfmba_dense_spd_solve(int device, int n, const double* A, const double* b, d
     if (info) *info = hinfo;
     if (iters) *iters = it;
     return SFMBA_OK;
-}
-
-int sfmba_triangulate(int device, int64_t n, const float* left_xy, const float* right_xy, const float* K, const float* P_left,
-                      const float* P_right, float max_reproj_px, float* points3d, unsigned char* keep, float* reproj_err) {
-    if (n < 0 || !K || !P_left || !P_right || (n > 0 && (!left_xy || !right_xy || !points3d || !keep)))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (n == 0) return check_device(device);
-    DeviceArena arena(device);
-    CallKit ck;
-    if (const int rc = ck.open(device)) return rc;
-    const HostKit& kit = ck.kit;
-    float* d_l = arena.alloc_n<float>((size_t)2 * n);
-    float* d_r = arena.alloc_n<float>((size_t)2 * n);
-    float* d_x = arena.alloc_n<float>((size_t)3 * n);
-    float* d_e = reproj_err ? arena.alloc_n<float>((size_t)2 * n) : nullptr;
-    unsigned char* d_k = arena.alloc_n<unsigned char>((size_t)n);
-    if (!d_l || !d_r || !d_x || !d_k || (reproj_err && !d_e)) return fail(SFMBA_ERR_ALLOC, "device allocation failed");
-    HIP_TRY(hipMemcpyAsync(d_l, left_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, kit.stream));
-    HIP_TRY(hipMemcpyAsync(d_r, right_xy, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, kit.stream));
-    launch_triangulate(kit.stream, (long long)n, d_l, d_r, K, P_left, P_right, max_reproj_px, d_x, d_k, d_e);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(points3d, d_x, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, kit.stream));
-    HIP_TRY(hipMemcpyAsync(keep, d_k, (size_t)n, hipMemcpyDeviceToHost, kit.stream));
-    if (reproj_err) HIP_TRY(hipMemcpyAsync(reproj_err, d_e, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToHost, kit.stream));
-    HIP_TRY(hipStreamSynchronize(kit.stream));
-    return SFMBA_OK;
-}
-
-int sfmba_triangulate_pairs(int device, int n_images, const int64_t* img_ptr, const float* pts, const float* K, int n_pairs, const int32_t* pair_left,
-                            const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx,
-                            const unsigned char* mask, const float* P_left, const float* P_right, float max_reproj_px, float* points3d,
-                            unsigned char* keep, float* reproj_err, int64_t* kept_ptr, int64_t* kept_idx) {
-    // every check comes before the first write: a refused call leaves the outputs as they were
-    if (n_images < 0 || n_pairs < 0 || !img_ptr || !pair_ptr || !K || !kept_ptr || (n_pairs > 0 && (!pair_left || !pair_right || !P_left || !P_right)))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (!std::isfinite(max_reproj_px) || max_reproj_px < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "max_reproj_px must be finite and >= 0");
-    if (img_ptr[0] < 0 || pair_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr and pair_ptr must not be negative");
-    for (int i = 0; i < n_images; ++i)
-        if (img_ptr[i + 1] < img_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
-    for (int p = 0; p < n_pairs; ++p) {
-        if (pair_ptr[p + 1] < pair_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "pair_ptr not monotone");
-        if (pair_ptr[p + 1] - pair_ptr[p] > (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "triangulate_pairs: a pair has 2^31 or more matches");
-        if (pair_left[p] < 0 || pair_left[p] >= n_images || pair_right[p] < 0 || pair_right[p] >= n_images)
-            return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
-    }
-    const int64_t total = pair_ptr[n_pairs];
-    if (total > 0 && (!points3d || !keep || !kept_idx)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    if (total > pair_ptr[0] && (!query_idx || !train_idx || !pts)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    for (int p = 0; p < n_pairs; ++p) {
-        const int64_t nl = img_ptr[pair_left[p] + 1] - img_ptr[pair_left[p]], nr = img_ptr[pair_right[p] + 1] - img_ptr[pair_right[p]];
-        for (int64_t e = pair_ptr[p]; e < pair_ptr[p + 1]; ++e)
-            if (query_idx[e] < 0 || query_idx[e] >= nl || train_idx[e] < 0 || train_idx[e] >= nr)
-                return fail(SFMBA_ERR_INVALID_ARG, "triangulate_pairs: a query_idx / train_idx lies outside its image");
-    }
-    if (total >= (int64_t)INT_MAX - 256) return fail(SFMBA_ERR_INVALID_ARG, "triangulate_pairs: too many entries for one call (2^31)");
-    if (total == pair_ptr[0]) {                                       // no entry belongs to a pair: nothing runs on the device
-        if (const int rc = check_device(device)) return rc;
-        for (int64_t e = 0; e < total; ++e) {
-            points3d[3 * e] = points3d[3 * e + 1] = points3d[3 * e + 2] = 0.0f;
-            keep[e] = 0;
-            if (reproj_err) reproj_err[2 * e] = reproj_err[2 * e + 1] = 0.0f;
-        }
-        for (int p = 0; p <= n_pairs; ++p) kept_ptr[p] = 0;
-        return SFMBA_OK;
-    }
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    rc = triangulate_pairs(ck.kit.stream, device, n_images, img_ptr, pts, K, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx, mask,
-                           P_left, P_right, max_reproj_px, points3d, keep, reproj_err, kept_ptr, kept_idx);
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "triangulate_pairs: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("triangulate_pairs: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-
-// ---- association joins -----------------------------------------------------------------------
-static int assoc_result(int rc, const char* what) {
-    if (rc == 0) return SFMBA_OK;
-    if (rc == ASSOC_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, std::string(what) + ": output capacity too small");
-    if (rc == ASSOC_ERR_TOO_LARGE) return fail(SFMBA_ERR_INVALID_ARG, std::string(what) + ": problem too large for 32-bit indices");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, std::string(what) + ": device allocation failed");
-    return fail(SFMBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString((hipError_t)rc));
-}
-
-int sfmba_find_2d3d_matches(int device, int n_views, const unsigned char* view_done, int n_pt, const int64_t* view_ptr,
-                            const int32_t* view_idx, const int32_t* feat_idx, int n_pairs, const int32_t* pair_left,
-                            const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx,
-                            int64_t* out_ptr, int32_t* out_point, int32_t* out_feature, int64_t cap, int64_t* total) {
-    if (n_views < 0 || n_pt < 0 || n_pairs < 0 || cap < 0 || !out_ptr || !total || (n_views > 0 && !view_done) || !view_ptr ||
-        (n_pairs > 0 && (!pair_left || !pair_right || !pair_ptr)) || (cap > 0 && (!out_point || !out_feature)))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (view_ptr[0] != 0 || (n_pairs > 0 && pair_ptr[0] != 0)) return fail(SFMBA_ERR_INVALID_ARG, "CSR pointers must start at 0");
-    for (int i = 0; i < n_pt; ++i) if (view_ptr[i + 1] < view_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "view_ptr not monotone");
-    for (int p = 0; p < n_pairs; ++p) if (pair_ptr[p + 1] < pair_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "pair_ptr not monotone");
-    if ((view_ptr[n_pt] > 0 && (!view_idx || !feat_idx)) || (n_pairs > 0 && pair_ptr[n_pairs] > 0 && (!query_idx || !train_idx)))
-        return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    CallKit ck;
-    if (const int rc = ck.open(device)) return rc;
-    return assoc_result(assoc_find_2d3d(ck.kit.stream, device, n_views, view_done, n_pt, view_ptr, view_idx, feat_idx, n_pairs, pair_left, pair_right,
-                                        pair_ptr, query_idx, train_idx, out_ptr, out_point, out_feature, cap, total), "find_2d3d_matches");
-}
-
-int sfmba_merge_candidates(int device, int n_exist, const float* exist_xyz, int n_new, const float* new_xyz, float max_dist,
-                           int64_t* cand_ptr, int32_t* cand_idx, int64_t cap, int64_t* total) {
-    if (n_exist < 0 || n_new < 0 || cap < 0 || !cand_ptr || !total || (n_exist > 0 && !exist_xyz) || (n_new > 0 && !new_xyz) || (cap > 0 && !cand_idx))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    CallKit ck;
-    if (const int rc = ck.open(device)) return rc;
-    return assoc_result(assoc_radius_candidates(ck.kit.stream, device, n_exist, exist_xyz, n_new, new_xyz, max_dist, cand_ptr, cand_idx, cap, total),
-                        "merge_candidates");
-}
-
-// ---- feature match matrix (SfM::createFeatureMatchMatrix) ---------------------------------------------------------
-int sfmba_match_features(int device, int n_images, const int64_t* img_ptr, const unsigned char* desc, int desc_bytes, int n_pairs,
-                         const int32_t* pair_left, const int32_t* pair_right, double ratio, int64_t* pair_ptr, int32_t* query_idx,
-                         int32_t* train_idx, float* distance, int64_t cap, int64_t* total) {
-    if (n_images < 0 || n_pairs < 0 || cap < 0 || !img_ptr || !pair_ptr || !total || (n_pairs > 0 && (!pair_left || !pair_right)) ||
-        (cap > 0 && (!query_idx || !train_idx)))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (desc_bytes < 1 || desc_bytes > 64) return fail(SFMBA_ERR_INVALID_ARG, "desc_bytes must be in 1..64");
-    if (!std::isfinite(ratio) || !(ratio > 0.0)) return fail(SFMBA_ERR_INVALID_ARG, "ratio must be finite and > 0");
-    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
-    for (int i = 0; i < n_images; ++i) {
-        const int64_t n = img_ptr[i + 1] - img_ptr[i];
-        if (n < 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
-        if (n >= ((int64_t)1 << 22)) return fail(SFMBA_ERR_INVALID_ARG, "an image has 2^22 or more descriptor rows (the train index is packed in 22 bits)");
-    }
-    if (img_ptr[n_images] > 0 && !desc) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    int64_t rows = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        const int l = pair_left[p], r = pair_right[p];
-        if (l < 0 || l >= n_images || r < 0 || r >= n_images) return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
-        if (img_ptr[r + 1] - img_ptr[r] >= 2) rows += img_ptr[l + 1] - img_ptr[l];
-    }
-    if (rows >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "match_features: too many query rows in one call (2^31)");
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_MATCH_TIMING: one stderr line per call with the HIP-event times of its phases (tools/match_bench.py)
-    double tm[5];
-    const bool timing = std::getenv("SFMBA_MATCH_TIMING") != nullptr;
-    rc = match_features(ck.kit.stream, device, n_images, img_ptr, desc, desc_bytes, n_pairs, pair_left, pair_right, ratio, pair_ptr, query_idx,
-                        train_idx, distance, cap, total, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba match] upload_ms %.6f top2_ms %.6f compact_ms %.6f download_ms %.6f batches %d\n", tm[0], tm[1], tm[2], tm[3], (int)tm[4]);
-    if (rc == MATCH_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "match_features: output capacity too small");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "match_features: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("match_features: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-// ---- the same for float descriptors: exact L2 2-NN (cv::BFMatcher with NORM_L2) ---------------------------------------------
-int sfmba_match_features_l2(int device, int n_images, const int64_t* img_ptr, const float* desc, int dims, int n_pairs,
-                            const int32_t* pair_left, const int32_t* pair_right, double ratio, int64_t* pair_ptr, int32_t* query_idx,
-                            int32_t* train_idx, float* distance, int64_t cap, int64_t* total) {
-    if (n_images < 0 || n_pairs < 0 || cap < 0 || !img_ptr || !pair_ptr || !total || (n_pairs > 0 && (!pair_left || !pair_right)) ||
-        (cap > 0 && (!query_idx || !train_idx)))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (dims < 1 || dims > MATCH_L2_MAX_DIMS) return fail(SFMBA_ERR_INVALID_ARG, "dims must be in 1..512");
-    if (!std::isfinite(ratio) || !(ratio > 0.0)) return fail(SFMBA_ERR_INVALID_ARG, "ratio must be finite and > 0");
-    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
-    for (int i = 0; i < n_images; ++i) {
-        const int64_t n = img_ptr[i + 1] - img_ptr[i];
-        if (n < 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
-        if (n >= ((int64_t)1 << 22)) return fail(SFMBA_ERR_INVALID_ARG, "an image has 2^22 or more descriptor rows");
-    }
-    if (img_ptr[n_images] > 0 && !desc) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    int64_t rows = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        const int l = pair_left[p], r = pair_right[p];
-        if (l < 0 || l >= n_images || r < 0 || r >= n_images) return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
-        if (img_ptr[r + 1] - img_ptr[r] >= 2) rows += img_ptr[l + 1] - img_ptr[l];
-    }
-    if (rows >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "match_features_l2: too many query rows in one call (2^31)");
-    for (int i = 0; i < n_images; ++i)                      // the contract is stated for finite values only
-        for (int64_t r = img_ptr[i]; r < img_ptr[i + 1]; ++r) {
-            const float* row = desc + (size_t)r * (size_t)dims;
-            for (int k = 0; k < dims; ++k)
-                if (!std::isfinite(row[k]))
-                    return fail(SFMBA_ERR_INVALID_ARG, "match_features_l2: non-finite descriptor value in image " + std::to_string(i) + ", row " +
-                                                           std::to_string((long long)(r - img_ptr[i])));
-        }
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_MATCH_TIMING: one stderr line per call with the HIP-event times of its phases (tools/match_l2_bench.py)
-    double tm[5];
-    const bool timing = std::getenv("SFMBA_MATCH_TIMING") != nullptr;
-    rc = match_features_l2(ck.kit.stream, device, n_images, img_ptr, desc, dims, n_pairs, pair_left, pair_right, ratio, pair_ptr, query_idx,
-                           train_idx, distance, cap, total, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba match_l2] upload_ms %.6f top2_ms %.6f compact_ms %.6f download_ms %.6f batches %d\n", tm[0], tm[1], tm[2], tm[3], (int)tm[4]);
-    if (rc == MATCH_L2_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "match_features_l2: output capacity too small");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "match_features_l2: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("match_features_l2: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-// ---- feature extraction (SfM::extractFeatures) ------------------------------------------------------------------------
-int sfmba_orb_extract(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
-                      int channels, int n_features, float scale_factor, int n_levels, int fast_threshold, int64_t* kp_ptr, sfmba_orb_keypoint* kp,
-                      unsigned char* desc, int64_t cap, int64_t* total, int32_t* dbg_level_xy, int32_t* dbg_bin, int64_t* dbg_harris,
-                      int32_t* dbg_candidates) {
-    if (n_images < 0 || cap < 0 || !img_ptr || !kp_ptr || !total || (n_images > 0 && (!width || !height)) || (cap > 0 && (!kp || !desc)))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: channels must be 1 or 3");
-    if (n_features < 1) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: n_features must be >= 1");
-    if (n_levels < 1 || n_levels > 12) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: n_levels must be in 1..12");
-    if (!std::isfinite(scale_factor) || !(scale_factor > 1.0f) || scale_factor > 2.0f)
-        return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: scale_factor must be finite and in (1, 2]");
-    if (fast_threshold < 1 || fast_threshold > 254) return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: fast_threshold must be in 1..254");
-    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
-    for (int i = 0; i < n_images; ++i) {
-        if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
-            return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: an image dimension lies outside 1..16384");
-        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
-            return fail(SFMBA_ERR_INVALID_ARG, "orb_extract: img_ptr does not agree with width * height * channels");
-    }
-    if (n_images > 0 && !pixels) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_ORB_TIMING: one stderr line per call with the HIP-event times of its phases (tools/orb_bench.py)
-    double tm[ORB_T_COUNT];
-    const bool timing = std::getenv("SFMBA_ORB_TIMING") != nullptr;
-    rc = orb_extract(ck.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, n_features, scale_factor, n_levels, fast_threshold,
-                     kp_ptr, kp, desc, cap, total, dbg_level_xy, dbg_bin, dbg_harris, dbg_candidates, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba orb] upload_ms %.6f pyramid_ms %.6f score_ms %.6f candidates_ms %.6f response_ms %.6f select_ms %.6f smooth_ms %.6f "
-                     "describe_ms %.6f download_ms %.6f groups %d\n", tm[ORB_T_UPLOAD], tm[ORB_T_PYRAMID], tm[ORB_T_SCORE], tm[ORB_T_CANDIDATES],
-                     tm[ORB_T_HARRIS], tm[ORB_T_SELECT], tm[ORB_T_SMOOTH], tm[ORB_T_DESCRIBE], tm[ORB_T_DOWNLOAD], (int)tm[ORB_T_GROUPS]);
-    if (rc == ORB_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "orb_extract: output capacity too small");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "orb_extract: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("orb_extract: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-// ---- float descriptors: Fast-Hessian detect and SURF-style describe, the extractor in front of sfmba_match_features_l2 ---------
-int sfmba_surf_extract(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
-                       int channels, int n_features, int n_octaves, float hessian_threshold, int upright, int64_t* kp_ptr, sfmba_surf_keypoint* kp,
-                       float* desc, int64_t cap, int64_t* total, int32_t* dbg_bin, int64_t* dbg_moments, int64_t* dbg_sums, int32_t* dbg_candidates) {
-    if (n_images < 0 || cap < 0 || !img_ptr || !kp_ptr || !total || (n_images > 0 && (!width || !height)) || (cap > 0 && (!kp || !desc)))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: channels must be 1 or 3");
-    if (n_features < 1) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: n_features must be >= 1");
-    if (n_octaves < 1 || n_octaves > 4) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: n_octaves must be in 1..4");
-    if (!std::isfinite(hessian_threshold) || hessian_threshold < 0.0f)
-        return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: hessian_threshold must be finite and >= 0");
-    if (upright != 0 && upright != 1) return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: upright must be 0 or 1");
-    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
-    for (int i = 0; i < n_images; ++i) {
-        if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
-            return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: an image dimension lies outside 1..16384");
-        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
-            return fail(SFMBA_ERR_INVALID_ARG, "surf_extract: img_ptr does not agree with width * height * channels");
-    }
-    if (n_images > 0 && !pixels) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_SURF_TIMING: one stderr line per call with the HIP-event times of its phases (tools/surf_bench.py)
-    double tm[SURF_T_COUNT];
-    const bool timing = std::getenv("SFMBA_SURF_TIMING") != nullptr;
-    rc = surf_extract(ck.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, n_features, n_octaves, hessian_threshold, upright,
-                      kp_ptr, kp, desc, cap, total, dbg_bin, dbg_moments, dbg_sums, dbg_candidates, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba surf] upload_ms %.6f integral_ms %.6f response_ms %.6f candidates_ms %.6f select_ms %.6f describe_ms %.6f "
-                     "download_ms %.6f groups %d response_bytes %.0f\n", tm[SURF_T_UPLOAD], tm[SURF_T_INTEGRAL], tm[SURF_T_RESPONSE],
-                     tm[SURF_T_CANDIDATES], tm[SURF_T_SELECT], tm[SURF_T_DESCRIBE], tm[SURF_T_DOWNLOAD], (int)tm[SURF_T_GROUPS], tm[SURF_T_RESPONSE_BYTES]);
-    if (rc == SURF_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "surf_extract: output capacity too small");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "surf_extract: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("surf_extract: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-// ---- dense depth maps and a dense cloud: plane-sweep stereo and the consistency filter (SfM::densify) ---------------------------
-namespace {
-// what every dense call refuses about the sizes, K and P; 0 or the failure
-int depth_check_cameras(const char* who, int n_images, const int32_t* width, const int32_t* height, const float* K, const float* P) {
-    const std::string w(who);
-    if (n_images < 0 || !K || (n_images > 0 && (!width || !height || !P))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    for (int i = 0; i < n_images; ++i) {
-        if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
-            return fail(SFMBA_ERR_INVALID_ARG, w + ": an image dimension lies outside 1..16384");
-        for (int q = 0; q < 12; ++q)
-            if (!std::isfinite(P[(size_t)i * 12 + q])) return fail(SFMBA_ERR_INVALID_ARG, w + ": non-finite pose of image " + std::to_string(i));
-    }
-    for (int q : { 0, 4, 2, 5 })
-        if (!std::isfinite(K[q])) return fail(SFMBA_ERR_INVALID_ARG, w + ": fx, fy, cx and cy must be finite");
-    if (!(K[0] > 0.0f) || !(K[4] > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, w + ": fx and fy must be > 0");
-    return 0;
-}
-// what the sweep and the fuse refuse about the images, K and P; 0 or the failure
-int depth_check_images(const char* who, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
-                       int channels, const float* K, const float* P) {
-    const std::string w(who);
-    if (n_images < 0 || !img_ptr || !K || (n_images > 0 && (!width || !height || !P || !pixels))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, w + ": channels must be 1 or 3");
-    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
-    for (int i = 0; i < n_images; ++i)
-        if (width[i] >= 1 && height[i] >= 1 && img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
-            return fail(SFMBA_ERR_INVALID_ARG, w + ": img_ptr does not agree with width * height * channels");
-    return depth_check_cameras(who, n_images, width, height, K, P);
-}
-// a CSR list of 0 / 1 .. 4 other images per row; 0 or the failure
-int depth_check_lists(const char* who, const char* what, int n_images, int n_rows, const int32_t* row_image, const int64_t* ptr, const int32_t* idx,
-                      int min_len) {
-    const std::string w(who);
-    if (!ptr || ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, w + ": " + what + " pointer array must start at 0");
-    for (int j = 0; j < n_rows; ++j) {
-        const int64_t n = ptr[j + 1] - ptr[j];
-        if (n < min_len || n > 4) return fail(SFMBA_ERR_INVALID_ARG, w + ": a row has " + std::to_string((long long)n) + " " + what + " images, outside " +
-                                                                       std::to_string(min_len) + "..4");
-        if (n > 0 && !idx) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-        const int own = row_image ? row_image[j] : j;
-        for (int64_t a = ptr[j]; a < ptr[j + 1]; ++a) {
-            if (idx[a] < 0 || idx[a] >= n_images) return fail(SFMBA_ERR_INVALID_ARG, w + ": " + what + " image index out of range");
-            if (idx[a] == own) return fail(SFMBA_ERR_INVALID_ARG, w + ": a " + what + " image equals the image it belongs to");
-            for (int64_t c = ptr[j]; c < a; ++c)
-                if (idx[c] == idx[a]) return fail(SFMBA_ERR_INVALID_ARG, w + ": a " + what + " image is listed twice");
-        }
-    }
-    return 0;
-}
-}  // namespace
-int sfmba_depth_sweep(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
-                      int channels, const float* K, const float* P, int n_jobs, const int32_t* job_ref, const int64_t* job_src_ptr,
-                      const int32_t* job_src, const float* z_near, const float* z_far, int n_planes, int radius, int min_std, float min_score,
-                      int min_sources, float* depth, float* score, int16_t* plane) {
-    if (n_jobs < 0 || (n_jobs > 0 && (!job_ref || !job_src_ptr || !job_src || !z_near || !z_far))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (int rc = depth_check_images("depth_sweep", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
-    if (n_planes < 2 || n_planes > 256) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: n_planes must be in 2..256");
-    if (radius < 1 || radius > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: radius must be in 1..4");
-    if (min_std < 0 || min_std > 127) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_std must be in 0..127");
-    if (!(min_score >= -1.0f) || !(min_score <= 1.0f)) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_score must be in [-1, 1]");
-    if (min_sources < 1 || min_sources > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_sources must be in 1..4");
-    int64_t out_px = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        if (job_ref[j] < 0 || job_ref[j] >= n_images) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: reference image index out of range");
-        if (!std::isfinite(z_near[j]) || !std::isfinite(z_far[j]) || !(z_near[j] > 0.0f) || !(z_near[j] < z_far[j]))
-            return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: a job needs 0 < z_near < z_far, both finite");
-        out_px += (int64_t)width[job_ref[j]] * height[job_ref[j]];
-    }
-    if (n_jobs > 0)
-        if (int rc = depth_check_lists("depth_sweep", "source", n_images, n_jobs, job_ref, job_src_ptr, job_src, 1)) return rc;
-    if (out_px > 0 && (!depth || !score)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    if (n_jobs == 0) return check_device(device);
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_DEPTH_TIMING: one stderr line per call with the HIP-event times of its phases (tools/dense_bench.py)
-    double tm[DEPTH_T_COUNT];
-    const bool timing = std::getenv("SFMBA_DEPTH_TIMING") != nullptr;
-    rc = depth_sweep(ck.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, K, P, n_jobs, job_ref, job_src_ptr, job_src, z_near,
-                     z_far, n_planes, radius, min_std, min_score, min_sources, depth, score, plane, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba depth_sweep] upload_ms %.6f gray_ms %.6f sweep_ms %.6f download_ms %.6f groups %d\n", tm[DEPTH_T_UPLOAD],
-                     tm[DEPTH_T_GRAY], tm[DEPTH_T_SWEEP], tm[DEPTH_T_DOWNLOAD], (int)tm[DEPTH_T_GROUPS]);
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "depth_sweep: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("depth_sweep: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-int sfmba_depth_fuse(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
-                     int channels, const float* K, const float* P, const float* const* depth, const int64_t* chk_ptr, const int32_t* chk,
-                     float rel_tol, int min_consistent, int64_t* pt_ptr, float* xyz, unsigned char* bgr, int32_t* src_image, int32_t* src_pixel,
-                     int64_t cap, int64_t* total) {
-    if (cap < 0 || !pt_ptr || !total || (n_images > 0 && !depth) || (cap > 0 && (!xyz || !bgr || !src_image || !src_pixel)))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (int rc = depth_check_images("depth_fuse", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
-    if (n_images > 65535) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: more than 65535 images in one call");
-    if (!std::isfinite(rel_tol) || rel_tol < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: rel_tol must be finite and >= 0");
-    if (min_consistent < 0 || min_consistent > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: min_consistent must be in 0..4");
-    if (int rc = depth_check_lists("depth_fuse", "check", n_images, n_images, nullptr, chk_ptr, chk, 0)) return rc;
-    int64_t px = 0;
-    for (int i = 0; i < n_images; ++i)
-        if (depth[i]) px += (int64_t)width[i] * height[i];
-    if (px >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "depth_fuse: too many pixels with a depth map in one call (2^31)");
-    if (px == 0) {
-        for (int i = 0; i <= n_images; ++i) pt_ptr[i] = 0;
-        *total = 0;
-        return check_device(device);
-    }
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    double tm[FUSE_T_COUNT];
-    const bool timing = std::getenv("SFMBA_DEPTH_TIMING") != nullptr;
-    rc = depth_fuse(ck.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, K, P, depth, chk_ptr, chk, rel_tol, min_consistent,
-                    pt_ptr, xyz, bgr, src_image, src_pixel, cap, total, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba depth_fuse] upload_ms %.6f flag_ms %.6f scan_ms %.6f emit_ms %.6f download_ms %.6f\n", tm[FUSE_T_UPLOAD],
-                     tm[FUSE_T_FLAG], tm[FUSE_T_SCAN], tm[FUSE_T_EMIT], tm[FUSE_T_DOWNLOAD]);
-    if (rc == DEPTH_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "depth_fuse: output capacity too small");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "depth_fuse: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("depth_fuse: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-// ---- matching by optical flow: pyramidal Lucas-Kanade and the snap to key points (SfMFeatureMatching::createFlowMatchMatrix) -----
-namespace {
-// what both flow calls refuse about the pair list and the points' CSR; 0 or the failure
-int flow_check_pairs(const char* who, int n_images, int n_pairs, const int32_t* pair_a, const int32_t* pair_b, const int64_t* pt_ptr) {
-    const std::string w(who);
-    if (n_images < 0 || n_pairs < 0 || !pt_ptr || (n_pairs > 0 && !pair_b)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (pt_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, w + ": pt_ptr must start at 0");
-    for (int p = 0; p < n_pairs; ++p) {
-        if ((pair_a && (pair_a[p] < 0 || pair_a[p] >= n_images)) || pair_b[p] < 0 || pair_b[p] >= n_images)
-            return fail(SFMBA_ERR_INVALID_ARG, w + ": pair index out of range");
-        if (pt_ptr[p + 1] < pt_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, w + ": pt_ptr not monotone");
-    }
-    if (pt_ptr[n_pairs] >= (int64_t)1 << 31) return fail(SFMBA_ERR_INVALID_ARG, w + ": 2^31 or more points in one call");
-    return 0;
-}
-}  // namespace
-int sfmba_flow_track(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
-                     int channels, int n_pairs, const int32_t* pair_src, const int32_t* pair_dst, const int64_t* pt_ptr, const float* pts,
-                     int n_levels, int radius, int max_iters, float min_eig, float* next, unsigned char* status, float* err, int64_t* dbg_G,
-                     int32_t* dbg_state, unsigned char* dbg_pyramid) {
-    if (n_images < 0 || !img_ptr || (n_images > 0 && (!width || !height)) || (n_pairs > 0 && !pair_src))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: channels must be 1 or 3");
-    if (n_levels < 1 || n_levels > FLOW_MAX_LEVELS) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: n_levels must be in 1..8");
-    if (radius < 1 || radius > FLOW_MAX_RADIUS) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: radius must be in 1..10");
-    if (max_iters < 1 || max_iters > FLOW_MAX_ITERS) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: max_iters must be in 1..64");
-    if (!std::isfinite(min_eig) || min_eig < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: min_eig must be finite and >= 0");
-    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
-    for (int i = 0; i < n_images; ++i) {
-        if (width[i] < 1 || width[i] > 16384 || height[i] < 1 || height[i] > 16384)
-            return fail(SFMBA_ERR_INVALID_ARG, "flow_track: an image dimension lies outside 1..16384");
-        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
-            return fail(SFMBA_ERR_INVALID_ARG, "flow_track: img_ptr does not agree with width * height * channels");
-    }
-    if (n_images > 0 && !pixels) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    if (int rc = flow_check_pairs("flow_track", n_images, n_pairs, pair_src, pair_dst, pt_ptr)) return rc;
-    const int64_t n_pts = pt_ptr[n_pairs];
-    if (n_pts > 0 && (!pts || !next || !status || !err)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    for (int64_t q = 0; q < 2 * n_pts; ++q)
-        if (!std::isfinite(pts[q])) return fail(SFMBA_ERR_INVALID_ARG, "flow_track: non-finite coordinate of point " + std::to_string((long long)(q / 2)));
-    if (n_pairs == 0) return check_device(device);
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_FLOW_TIMING: one stderr line per call with the HIP-event times of its phases (tools/flow_bench.py)
-    double tm[FLOW_T_COUNT];
-    const bool timing = std::getenv("SFMBA_FLOW_TIMING") != nullptr;
-    rc = flow_track(ck.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, n_pairs, pair_src, pair_dst, pt_ptr, pts, n_levels,
-                    radius, max_iters, min_eig, next, status, err, dbg_G, dbg_state, dbg_pyramid, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba flow_track] upload_ms %.6f gray_ms %.6f pyramid_ms %.6f track_ms %.6f download_ms %.6f groups %d\n",
-                     tm[FLOW_T_UPLOAD], tm[FLOW_T_GRAY], tm[FLOW_T_PYRAMID], tm[FLOW_T_TRACK], tm[FLOW_T_DOWNLOAD], (int)tm[FLOW_T_GROUPS]);
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "flow_track: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("flow_track: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-int sfmba_flow_match(int device, int n_images, const int64_t* kp_ptr, const float* kp_xy, int n_pairs, const int32_t* pair_dst,
-                     const int64_t* pt_ptr, const float* next, const unsigned char* status, const float* err, float max_err, float radius,
-                     double ratio, int64_t* pair_ptr, int32_t* query_idx, int32_t* train_idx, float* distance, int64_t cap, int64_t* total) {
-    if (cap < 0 || !kp_ptr || !pair_ptr || !total || (cap > 0 && (!query_idx || !train_idx))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (!std::isfinite(max_err)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: max_err must be finite");
-    if (!std::isfinite(radius) || !(radius > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: radius must be finite and > 0");
-    if (!std::isfinite(ratio) || !(ratio > 0.0)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: ratio must be finite and > 0");
-    if (int rc = flow_check_pairs("flow_match", n_images, n_pairs, nullptr, pair_dst, pt_ptr)) return rc;
-    if (kp_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: kp_ptr must start at 0");
-    for (int i = 0; i < n_images; ++i) {
-        const int64_t n = kp_ptr[i + 1] - kp_ptr[i];
-        if (n < 0) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: kp_ptr not monotone");
-        if (n >= ((int64_t)1 << 22)) return fail(SFMBA_ERR_INVALID_ARG, "flow_match: an image has 2^22 or more key points");
-    }
-    const int64_t n_pts = pt_ptr[n_pairs];
-    if ((n_pts > 0 && (!next || !status || !err)) || (kp_ptr[n_images] > 0 && !kp_xy)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    if (n_pts == 0) {
-        for (int p = 0; p <= n_pairs; ++p) pair_ptr[p] = 0;
-        *total = 0;
-        return check_device(device);
-    }
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    double tm[FLOWM_T_COUNT];
-    const bool timing = std::getenv("SFMBA_FLOW_TIMING") != nullptr;
-    rc = flow_match(ck.kit.stream, device, n_images, kp_ptr, kp_xy, n_pairs, pair_dst, pt_ptr, next, status, err, max_err, radius, ratio, pair_ptr,
-                    query_idx, train_idx, distance, cap, total, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba flow_match] upload_ms %.6f near_ms %.6f compact_ms %.6f download_ms %.6f\n", tm[FLOWM_T_UPLOAD], tm[FLOWM_T_NEAR],
-                     tm[FLOWM_T_COMPACT], tm[FLOWM_T_DOWNLOAD]);
-    if (rc == FLOW_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "flow_match: output capacity too small");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "flow_match: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("flow_match: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-// ---- one oriented point per surface element: a normal per depth pixel and the voxel merge (SfM::mergeDenseCloud) ------------------
-int sfmba_depth_normals(int device, int n_images, const int32_t* width, const int32_t* height, const float* K, const float* P,
-                        const float* const* depth, float max_rel_step, float* const* normal) {
-    if ((n_images > 0 && (!depth || !normal))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (int rc = depth_check_cameras("depth_normals", n_images, width, height, K, P)) return rc;
-    if (n_images > 65535) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: more than 65535 images in one call");
-    if (!std::isfinite(max_rel_step) || max_rel_step < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: max_rel_step must be finite and >= 0");
-    int64_t px = 0;
-    for (int i = 0; i < n_images; ++i) {
-        if (!depth[i]) continue;
-        if (!normal[i]) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: an image with a depth map needs an output map");
-        px += (int64_t)width[i] * height[i];
-    }
-    if (px >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "depth_normals: too many pixels with a depth map in one call (2^31)");
-    if (px == 0) return check_device(device);
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_CLOUD_TIMING: one stderr line per call with the HIP-event times of its phases (tools/cloud_bench.py)
-    double tm[NORMALS_T_COUNT];
-    const bool timing = std::getenv("SFMBA_CLOUD_TIMING") != nullptr;
-    rc = depth_normals(ck.kit.stream, device, n_images, width, height, K, P, depth, max_rel_step, normal, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba depth_normals] upload_ms %.6f kernel_ms %.6f download_ms %.6f\n", tm[NORMALS_T_UPLOAD], tm[NORMALS_T_KERNEL],
-                     tm[NORMALS_T_DOWNLOAD]);
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "depth_normals: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("depth_normals: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-int sfmba_cloud_merge(int device, int64_t n, const float* xyz, const unsigned char* bgr, const float* normal, float voxel, int min_count,
-                      float* xyz_out, unsigned char* bgr_out, float* normal_out, int32_t* count, int32_t* first, int32_t* voxel_of, int64_t cap,
-                      int64_t* total, int64_t* n_skipped) {
-    if (n < 0 || cap < 0 || !total || !n_skipped || (n > 0 && !xyz) ||
-        (cap > 0 && (!xyz_out || !count || !first || (bgr && !bgr_out) || (normal && !normal_out))))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (n >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "cloud_merge: too many points in one call (2^31)");
-    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "cloud_merge: voxel must be finite and > 0");
-    if (min_count < 1) return fail(SFMBA_ERR_INVALID_ARG, "cloud_merge: min_count must be >= 1");
-    if (n == 0) {
-        *total = 0;
-        *n_skipped = 0;
-        return check_device(device);
-    }
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    double tm[MERGE_T_COUNT];
-    const bool timing = std::getenv("SFMBA_CLOUD_TIMING") != nullptr;
-    rc = cloud_merge(ck.kit.stream, device, (int)n, xyz, bgr, normal, voxel, min_count, xyz_out, bgr_out, normal_out, count, first, voxel_of, cap, total,
-                     n_skipped, timing ? tm : nullptr);
-    if ((rc == 0 || rc == CLOUD_ERR_CAPACITY) && timing)
-        std::fprintf(stderr,
-                     "[sfmba cloud_merge] upload_ms %.6f quantise_ms %.6f sort_ms %.6f runs_ms %.6f reduce_ms %.6f compact_ms %.6f finalise_ms %.6f "
-                     "download_ms %.6f points %lld voxels %lld\n",
-                     tm[MERGE_T_UPLOAD], tm[MERGE_T_QUANTISE], tm[MERGE_T_SORT], tm[MERGE_T_RUNS], tm[MERGE_T_REDUCE], tm[MERGE_T_COMPACT],
-                     tm[MERGE_T_FINALISE], tm[MERGE_T_DOWNLOAD], (long long)n, (long long)*total);
-    if (rc == CLOUD_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, "cloud_merge: output capacity too small");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "cloud_merge: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("cloud_merge: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-// ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------
-int sfmba_pnp_ransac(int device, int n_prob, const int64_t* prob_ptr, const float* xyz, const float* uv, const float* K, int n_hyp,
-                     float threshold_px, uint64_t seed, int max_refine_iters, double* pose, unsigned char* inlier,
-                     sfmba_pnp_result* result, double* hyp_pose, int32_t* hyp_count) {
-    if (n_prob < 0 || !prob_ptr || !K || (n_prob > 0 && (!pose || !result))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (n_hyp < 1 || n_hyp > 65536) return fail(SFMBA_ERR_INVALID_ARG, "n_hyp must be in 1..65536");
-    if (!std::isfinite(threshold_px) || !(threshold_px > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "threshold_px must be finite and > 0");
-    if (!std::isfinite(K[0]) || !(K[0] > 0.0f) || !std::isfinite(K[4]) || !(K[4] > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "fx and fy must be finite and > 0");
-    if (max_refine_iters < 0) return fail(SFMBA_ERR_INVALID_ARG, "max_refine_iters must be >= 0");
-    if (prob_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "prob_ptr must not be negative");
-    for (int p = 0; p < n_prob; ++p) {
-        if (prob_ptr[p + 1] < prob_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "prob_ptr not monotone");
-        if (prob_ptr[p + 1] - prob_ptr[p] >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "pnp_ransac: a problem has 2^31 or more points");
-    }
-    if (prob_ptr[n_prob] > 0 && (!xyz || !uv || !inlier)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    if (n_prob == 0) return check_device(device);
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_PNP_TIMING: one stderr line per call with the HIP-event times of its phases (tools/pnp_bench.py)
-    double tm[3];
-    const bool timing = std::getenv("SFMBA_PNP_TIMING") != nullptr;
-    rc = pnp_ransac(ck.kit.stream, device, n_prob, prob_ptr, xyz, uv, K, n_hyp, threshold_px, seed, max_refine_iters, pose, inlier, result,
-                    hyp_pose, hyp_count, timing ? tm : nullptr);
-    if (rc == 0 && timing) std::fprintf(stderr, "[sfmba pnp] upload_ms %.6f kernels_ms %.6f download_ms %.6f\n", tm[0], tm[1], tm[2]);
-    if (rc == PNP_ERR_TOO_LARGE) return fail(SFMBA_ERR_INVALID_ARG, "pnp_ransac: too many problems x hypotheses for one call");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "pnp_ransac: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("pnp_ransac: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-// ---- baseline pair ranking (SfMStereoUtilities::findHomographyInliers) ------------------------------------------------
-int sfmba_homography_ransac(int device, int n_images, const int64_t* img_ptr, const float* pts, int n_pairs, const int32_t* pair_left,
-                            const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx, int n_hyp,
-                            float threshold_px, uint64_t seed, double* H, unsigned char* inlier, sfmba_homography_result* result, double* hyp_H,
-                            int32_t* hyp_count) {
-    if (n_images < 0 || n_pairs < 0 || !img_ptr || !pair_ptr || (n_pairs > 0 && (!pair_left || !pair_right || !H || !result)))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (n_hyp < 1 || n_hyp > 65536) return fail(SFMBA_ERR_INVALID_ARG, "n_hyp must be in 1..65536");
-    if (!std::isfinite(threshold_px) || !(threshold_px > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "threshold_px must be finite and > 0");
-    if (img_ptr[0] < 0 || pair_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr and pair_ptr must not be negative");
-    for (int i = 0; i < n_images; ++i)
-        if (img_ptr[i + 1] < img_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
-    for (int p = 0; p < n_pairs; ++p) {
-        if (pair_ptr[p + 1] < pair_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "pair_ptr not monotone");
-        if (pair_ptr[p + 1] - pair_ptr[p] > (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "homography_ransac: a pair has 2^31 or more matches");
-        if (pair_left[p] < 0 || pair_left[p] >= n_images || pair_right[p] < 0 || pair_right[p] >= n_images)
-            return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
-    }
-    if (pair_ptr[n_pairs] > pair_ptr[0] && (!query_idx || !train_idx || !inlier || !pts)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    for (int p = 0; p < n_pairs; ++p) {
-        const int64_t nl = img_ptr[pair_left[p] + 1] - img_ptr[pair_left[p]], nr = img_ptr[pair_right[p] + 1] - img_ptr[pair_right[p]];
-        for (int64_t e = pair_ptr[p]; e < pair_ptr[p + 1]; ++e)
-            if (query_idx[e] < 0 || query_idx[e] >= nl || train_idx[e] < 0 || train_idx[e] >= nr)
-                return fail(SFMBA_ERR_INVALID_ARG, "homography_ransac: a query_idx / train_idx lies outside its image");
-    }
-    if (n_pairs == 0) return check_device(device);
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_HOMOGRAPHY_TIMING: one stderr line per call with the HIP-event times of its phases (tools/homography_bench.py)
-    double tm[5];
-    const bool timing = std::getenv("SFMBA_HOMOGRAPHY_TIMING") != nullptr;
-    rc = homography_ransac(ck.kit.stream, device, n_images, img_ptr, pts, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx, n_hyp,
-                           threshold_px, seed, H, inlier, result, hyp_H, hyp_count, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba homography] upload_ms %.6f hypotheses_ms %.6f score_ms %.6f select_ms %.6f download_ms %.6f\n", tm[0], tm[1], tm[2],
-                     tm[3], tm[4]);
-    if (rc == HOM_ERR_TOO_LARGE) return fail(SFMBA_ERR_INVALID_ARG, "homography_ransac: too many pairs x hypotheses for one call");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "homography_ransac: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("homography_ransac: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-// ---- pose of an image pair (SfMStereoUtilities::findCameraMatricesFromMatch) -------------------------------------------
-int sfmba_essential_ransac(int device, int n_images, const int64_t* img_ptr, const float* pts, int n_pairs, const int32_t* pair_left,
-                           const int32_t* pair_right, const int64_t* pair_ptr, const int32_t* query_idx, const int32_t* train_idx, const float* K,
-                           int n_hyp, float threshold_px, uint64_t seed, double* E, double* pose, unsigned char* inlier,
-                           sfmba_essential_result* result, double* hyp_E, int32_t* hyp_count, int32_t* hyp_nsol) {
-    if (n_images < 0 || n_pairs < 0 || !img_ptr || !pair_ptr || !K || (n_pairs > 0 && (!pair_left || !pair_right || !E || !pose || !result)))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (n_hyp < 1 || n_hyp > 65536) return fail(SFMBA_ERR_INVALID_ARG, "n_hyp must be in 1..65536");
-    if (!std::isfinite(threshold_px) || !(threshold_px > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "threshold_px must be finite and > 0");
-    if (!std::isfinite(K[0]) || !(K[0] > 0.0f) || !std::isfinite(K[4]) || !(K[4] > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "fx and fy must be finite and > 0");
-    if (img_ptr[0] < 0 || pair_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr and pair_ptr must not be negative");
-    for (int i = 0; i < n_images; ++i)
-        if (img_ptr[i + 1] < img_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr not monotone");
-    for (int p = 0; p < n_pairs; ++p) {
-        if (pair_ptr[p + 1] < pair_ptr[p]) return fail(SFMBA_ERR_INVALID_ARG, "pair_ptr not monotone");
-        if (pair_ptr[p + 1] - pair_ptr[p] > (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "essential_ransac: a pair has 2^31 or more matches");
-        if (pair_left[p] < 0 || pair_left[p] >= n_images || pair_right[p] < 0 || pair_right[p] >= n_images)
-            return fail(SFMBA_ERR_INVALID_ARG, "pair index out of range");
-    }
-    if (pair_ptr[n_pairs] > pair_ptr[0] && (!query_idx || !train_idx || !inlier || !pts)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    for (int p = 0; p < n_pairs; ++p) {
-        const int64_t nl = img_ptr[pair_left[p] + 1] - img_ptr[pair_left[p]], nr = img_ptr[pair_right[p] + 1] - img_ptr[pair_right[p]];
-        for (int64_t e = pair_ptr[p]; e < pair_ptr[p + 1]; ++e)
-            if (query_idx[e] < 0 || query_idx[e] >= nl || train_idx[e] < 0 || train_idx[e] >= nr)
-                return fail(SFMBA_ERR_INVALID_ARG, "essential_ransac: a query_idx / train_idx lies outside its image");
-    }
-    if (n_pairs == 0) return check_device(device);
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_ESSENTIAL_TIMING: one stderr line per call with the HIP-event times of its phases (tools/essential_bench.py)
-    double tm[5];
-    const bool timing = std::getenv("SFMBA_ESSENTIAL_TIMING") != nullptr;
-    rc = essential_ransac(ck.kit.stream, device, n_images, img_ptr, pts, n_pairs, pair_left, pair_right, pair_ptr, query_idx, train_idx, K, n_hyp,
-                          threshold_px, seed, E, pose, inlier, result, hyp_E, hyp_count, hyp_nsol, timing ? tm : nullptr);
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba essential] upload_ms %.6f hypotheses_ms %.6f score_ms %.6f select_ms %.6f download_ms %.6f\n", tm[0], tm[1], tm[2],
-                     tm[3], tm[4]);
-    if (rc == ESS_ERR_TOO_LARGE) return fail(SFMBA_ERR_INVALID_ARG, "essential_ransac: too many pairs x hypotheses for one call");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, "essential_ransac: device allocation failed");
-    if (rc) return fail(SFMBA_ERR_HIP, std::string("essential_ransac: ") + hipGetErrorString((hipError_t)rc));
-    return SFMBA_OK;
-}
-// ---- reading photographs (SfM::setImagesDirectory: imread + resize) ---------------------------------------------------
-static int check_file_ptr(int n_images, const int64_t* file_ptr, const unsigned char* bytes) {
-    if (n_images < 0 || !file_ptr) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (file_ptr[0] < 0) return fail(SFMBA_ERR_INVALID_ARG, "file_ptr must not be negative");
-    for (int i = 0; i < n_images; ++i)
-        if (file_ptr[i + 1] < file_ptr[i]) return fail(SFMBA_ERR_INVALID_ARG, "file_ptr not monotone");
-    if (file_ptr[n_images] > file_ptr[0] && !bytes) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    return SFMBA_OK;
-}
-
-static int image_result(int rc, const char* what, const double* tm) {
-    if (rc == 0 && tm)
-        std::fprintf(stderr, "[sfmba %s] entropy_ms %.6f upload_ms %.6f idct_ms %.6f colour_ms %.6f resize_ms %.6f download_ms %.6f groups %d\n", what,
-                     tm[JPEG_T_ENTROPY], tm[JPEG_T_UPLOAD], tm[JPEG_T_IDCT], tm[JPEG_T_COLOUR], tm[JPEG_T_RESIZE], tm[JPEG_T_DOWNLOAD], (int)tm[JPEG_T_GROUPS]);
-    if (rc == 0) return SFMBA_OK;
-    if (rc == JPEG_ERR_CAPACITY) return fail(SFMBA_ERR_CAPACITY, std::string(what) + ": output capacity too small");
-    if (rc == JPEG_ERR_HOST_ALLOC) return fail(SFMBA_ERR_ALLOC, std::string(what) + ": host allocation failed");
-    if (rc == (int)hipErrorOutOfMemory) return fail(SFMBA_ERR_ALLOC, std::string(what) + ": device allocation failed");
-    return fail(SFMBA_ERR_HIP, std::string(what) + ": " + hipGetErrorString((hipError_t)rc));
-}
-
-int sfmba_jpeg_info(int n_images, const int64_t* file_ptr, const unsigned char* bytes, sfmba_image_info* info) {
-    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
-    if (n_images > 0 && !info) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    std::vector<JpegHeader> hdr;
-    jpeg_parse_batch(n_images, file_ptr, bytes, hdr);
-    for (int i = 0; i < n_images; ++i) jpeg_fill_info(hdr[(size_t)i], &info[i]);
-    return SFMBA_OK;
-}
-
-int sfmba_resized_size(int width, int height, float factor, int32_t* out_width, int32_t* out_height) {
-    if (!out_width || !out_height) return fail(SFMBA_ERR_INVALID_ARG, "NULL argument");
-    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "factor must be finite and > 0");
-    if (width < 1 || width > JPEG_MAX_SIDE || height < 1 || height > JPEG_MAX_SIDE) return fail(SFMBA_ERR_INVALID_ARG, "an image dimension lies outside 1..16384");
-    const int ow = resized_length(width, factor), oh = resized_length(height, factor);
-    if (ow == 0 || oh == 0) return fail(SFMBA_ERR_INVALID_ARG, "the factor gives the image a side outside 1..16384");
-    *out_width = ow; *out_height = oh;
-    return SFMBA_OK;
-}
-
-int sfmba_jpeg_decode(int device, int n_images, const int64_t* file_ptr, const unsigned char* bytes, float factor, sfmba_image_info* info,
-                      int64_t* out_ptr, unsigned char* out, int64_t cap, int64_t* total) {
-    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
-    if (cap < 0 || !out_ptr || !total || (n_images > 0 && !info) || (cap > 0 && !out)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "jpeg_decode: factor must be finite and > 0");
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_JPEG_TIMING: one stderr line per call with the host time of the entropy decode and the HIP-event times of the phases (tools/image_io_bench.py)
-    double tm[JPEG_T_COUNT];
-    const bool timing = std::getenv("SFMBA_JPEG_TIMING") != nullptr;
-    rc = jpeg_decode(ck.kit.stream, device, n_images, file_ptr, bytes, factor, info, out_ptr, out, cap, total, timing ? tm : nullptr);
-    if (rc == JPEG_ERR_SIZE) return fail(SFMBA_ERR_INVALID_ARG, "jpeg_decode: the factor gives an image a side outside 1..16384");
-    return image_result(rc, "jpeg_decode", timing ? tm : nullptr);
-}
-
-int sfmba_resize_images(int device, int n_images, const int64_t* img_ptr, const unsigned char* px, const int32_t* width, const int32_t* height,
-                        int channels, float factor, int64_t* out_ptr, unsigned char* out, int64_t cap, int64_t* total) {
-    if (n_images < 0 || cap < 0 || !img_ptr || !out_ptr || !total || (n_images > 0 && (!width || !height)) || (cap > 0 && !out))
-        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (channels != 1 && channels != 3) return fail(SFMBA_ERR_INVALID_ARG, "resize_images: channels must be 1 or 3");
-    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "resize_images: factor must be finite and > 0");
-    if (img_ptr[0] != 0) return fail(SFMBA_ERR_INVALID_ARG, "img_ptr must start at 0");
-    for (int i = 0; i < n_images; ++i) {
-        if (width[i] < 1 || width[i] > JPEG_MAX_SIDE || height[i] < 1 || height[i] > JPEG_MAX_SIDE)
-            return fail(SFMBA_ERR_INVALID_ARG, "resize_images: an image dimension lies outside 1..16384");
-        if (img_ptr[i + 1] - img_ptr[i] != (int64_t)width[i] * height[i] * channels)
-            return fail(SFMBA_ERR_INVALID_ARG, "resize_images: img_ptr does not agree with width * height * channels");
-        if (resized_length(width[i], factor) == 0 || resized_length(height[i], factor) == 0)
-            return fail(SFMBA_ERR_INVALID_ARG, "resize_images: the factor gives an image a side outside 1..16384");
-    }
-    if (n_images > 0 && !px) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    double tm[JPEG_T_COUNT];
-    const bool timing = std::getenv("SFMBA_JPEG_TIMING") != nullptr;
-    rc = resize_images(ck.kit.stream, device, n_images, img_ptr, px, width, height, channels, factor, out_ptr, out, cap, total, timing ? tm : nullptr);
-    if (rc == JPEG_ERR_SIZE) return fail(SFMBA_ERR_INVALID_ARG, "resize_images: the factor gives an image a side outside 1..16384");
-    return image_result(rc, "resize_images", timing ? tm : nullptr);
-}
-
-int sfmba_png_info(int n_images, const int64_t* file_ptr, const unsigned char* bytes, struct sfmba_png_info* info) {
-    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
-    if (n_images > 0 && !info) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
-    std::vector<PngHeader> hdr;
-    png_parse_batch(n_images, file_ptr, bytes, hdr);
-    for (int i = 0; i < n_images; ++i) png_fill_info(hdr[(size_t)i], &info[i]);
-    return SFMBA_OK;
-}
-
-int sfmba_png_decode(int device, int n_images, const int64_t* file_ptr, const unsigned char* bytes, float factor, struct sfmba_png_info* info,
-                     int64_t* out_ptr, unsigned char* out, int64_t cap, int64_t* total) {
-    if (const int rc = check_file_ptr(n_images, file_ptr, bytes)) return rc;
-    if (cap < 0 || !out_ptr || !total || (n_images > 0 && !info) || (cap > 0 && !out)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (!std::isfinite(factor) || !(factor > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, "png_decode: factor must be finite and > 0");
-    CallKit ck;
-    int rc = ck.open(device);
-    if (rc) return rc;
-    // SFMBA_PNG_TIMING: one stderr line per call with the host time of the inflate and the HIP-event times of the phases (tools/image_io_bench.py)
-    double tm[PNG_T_COUNT];
-    const bool timing = std::getenv("SFMBA_PNG_TIMING") != nullptr;
-    rc = png_decode(ck.kit.stream, device, n_images, file_ptr, bytes, factor, info, out_ptr, out, cap, total, timing ? tm : nullptr);
-    if (rc == JPEG_ERR_SIZE) return fail(SFMBA_ERR_INVALID_ARG, "png_decode: the factor gives an image a side outside 1..16384");
-    if (rc == 0 && timing)
-        std::fprintf(stderr, "[sfmba png_decode] inflate_ms %.6f upload_ms %.6f unfilter_ms %.6f pixels_ms %.6f resize_ms %.6f download_ms %.6f groups %d\n",
-                     tm[PNG_T_INFLATE], tm[PNG_T_UPLOAD], tm[PNG_T_UNFILTER], tm[PNG_T_PIXELS], tm[PNG_T_RESIZE], tm[PNG_T_DOWNLOAD], (int)tm[PNG_T_GROUPS]);
-    return image_result(rc, "png_decode", nullptr);
 }
 }  // extern "C"

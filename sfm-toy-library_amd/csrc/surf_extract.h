@@ -4,12 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unit_common.h"
+
 #include "../../include/sfmba.h"
 
 namespace sfmba {
 
-// return values besides 0 (ok) and positive hipError_t codes
-enum { SURF_ERR_CAPACITY = -1 };
+// return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 // Images go to the device in consecutive groups.  A group's arrays (the input bytes, the integral images, the response maps of
 // every octave, the four candidate sort buffers) stay within this bound; an image that exceeds it alone forms a group of its own.

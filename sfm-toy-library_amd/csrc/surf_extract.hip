@@ -24,7 +24,6 @@
 #include "surf_extract.h"
 #include "surf_math.h"
 #include "device_arena.h"
-#include "jpeg_decode.h"   // PhaseTimer
 
 #include <hipcub/hipcub.hpp>
 
@@ -209,9 +208,6 @@ __global__ __launch_bounds__(LANES) void k_surf_describe(const SurfImage* __rest
     }
 }
 
-#define SURF_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define SURF_ALLOC(arena, ptr, T, n) do { ptr = (arena).alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 long long align64(long long n) { return (n + 63) & ~63ll; }
 
 // The candidates of a layer are strictly above their 8 neighbours of that layer, so no two touch: a 2 x 2 cell of the admissible grid
@@ -264,7 +260,7 @@ int surf_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr
     DeviceArena keep(device);
     int* d_counts;                                             // [n_images][n_octaves][2]
     const size_t n_counts = (size_t)n_images * n_octaves * 2;
-    SURF_ALLOC(keep, d_counts, int, n_counts);                 // handed out zeroed
+    UNIT_ALLOC(keep, d_counts, int, n_counts);                 // handed out zeroed
     std::vector<int> counts(n_counts, 0);
     // the rows of the call, staged on the host: nothing reaches the caller's arrays unless the whole call fits
     std::vector<sfmba_surf_keypoint> h_kp;
@@ -319,34 +315,34 @@ int surf_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr
         double* d_resp;
         int* d_ncand;
         uint64_t *d_key[2], *d_ent[2];
-        SURF_ALLOC(scratch, d_tab, SurfImage, (size_t)ng);
-        SURF_ALLOC(scratch, d_seg, SurfSegment, (size_t)ng);
-        SURF_ALLOC(scratch, d_raw, unsigned char, (size_t)raw_bytes);
-        SURF_ALLOC(scratch, d_int, uint32_t, (size_t)int_words);
-        SURF_ALLOC(scratch, d_resp, double, (size_t)resp_doubles);
-        SURF_ALLOC(scratch, d_ncand, int, 1);
+        UNIT_ALLOC(scratch, d_tab, SurfImage, (size_t)ng);
+        UNIT_ALLOC(scratch, d_seg, SurfSegment, (size_t)ng);
+        UNIT_ALLOC(scratch, d_raw, unsigned char, (size_t)raw_bytes);
+        UNIT_ALLOC(scratch, d_int, uint32_t, (size_t)int_words);
+        UNIT_ALLOC(scratch, d_resp, double, (size_t)resp_doubles);
+        UNIT_ALLOC(scratch, d_ncand, int, 1);
         for (int b = 0; b < 2; ++b) {
-            SURF_ALLOC(scratch, d_key[b], uint64_t, (size_t)cand_cap);
-            SURF_ALLOC(scratch, d_ent[b], uint64_t, (size_t)cand_cap);
+            UNIT_ALLOC(scratch, d_key[b], uint64_t, (size_t)cand_cap);
+            UNIT_ALLOC(scratch, d_ent[b], uint64_t, (size_t)cand_cap);
         }
         int img_bits = 1;
         while ((1 << img_bits) < ng) ++img_bits;
         size_t sort_a = 0, sort_b = 0, sort_c = 0;
         {
             hipcub::DoubleBuffer<uint64_t> k(d_key[0], d_key[1]), e(d_ent[0], d_ent[1]);
-            SURF_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_a, e, k, (int)cand_cap, 0, ENT_IMAGE_SHIFT + img_bits, s));
-            SURF_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, k, e, (int)cand_cap, 0, 64, s));
-            SURF_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_c, e, k, (int)cand_cap, ENT_IMAGE_SHIFT, ENT_IMAGE_SHIFT + img_bits, s));
+            UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_a, e, k, (int)cand_cap, 0, ENT_IMAGE_SHIFT + img_bits, s));
+            UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, k, e, (int)cand_cap, 0, 64, s));
+            UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_c, e, k, (int)cand_cap, ENT_IMAGE_SHIFT, ENT_IMAGE_SHIFT + img_bits, s));
         }
         const size_t tmp_bytes = std::max(std::max(sort_a, sort_b), std::max(sort_c, (size_t)1));
         void* d_tmp = scratch.alloc(tmp_bytes);
         if (!d_tmp) return (int)hipErrorOutOfMemory;
 
         tm.begin(SURF_T_UPLOAD);
-        SURF_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(SurfImage) * tab.size(), hipMemcpyHostToDevice, s));
+        UNIT_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(SurfImage) * tab.size(), hipMemcpyHostToDevice, s));
         for (int i = 0; i < ng; ++i)
             if (plan[(size_t)(i0 + i)].cand)
-                SURF_TRY(hipMemcpyAsync(d_raw + tab[(size_t)i].poff, pixels + img_ptr[i0 + i], (size_t)tab[(size_t)i].w * tab[(size_t)i].h * channels,
+                UNIT_TRY(hipMemcpyAsync(d_raw + tab[(size_t)i].poff, pixels + img_ptr[i0 + i], (size_t)tab[(size_t)i].w * tab[(size_t)i].h * channels,
                                         hipMemcpyHostToDevice, s));
         tm.end();
 
@@ -354,7 +350,7 @@ int surf_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr
         hipLaunchKernelGGL(k_surf_rows, dim3((unsigned)((max_rows + LANES / 64 - 1) / (LANES / 64)), (unsigned)ng), dim3(LANES), 0, s, d_tab, d_raw,
                            channels, d_int);
         hipLaunchKernelGGL(k_surf_cols, dim3((unsigned)((max_cols + LANES - 1) / LANES), (unsigned)ng), dim3(LANES), 0, s, d_tab, d_int);
-        SURF_TRY(hipGetLastError());
+        UNIT_TRY(hipGetLastError());
         tm.end();
         for (int o = 0; o < n_octaves; ++o) {
             if (max_plane[o] == 0) continue;
@@ -365,7 +361,7 @@ int surf_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr
             tm.begin(SURF_T_CANDIDATES);
             hipLaunchKernelGGL(k_surf_candidates, dim3(gx, (unsigned)ng, 2), dim3(LANES), 0, s, d_tab, d_resp, o, n_octaves, i0,
                                (double)hessian_threshold, (int)cand_cap, d_ncand, d_counts, d_ent[0], d_key[0]);
-            SURF_TRY(hipGetLastError());
+            UNIT_TRY(hipGetLastError());
             tm.end();
             if (timing)
                 for (int i = 0; i < ng; ++i)
@@ -380,10 +376,10 @@ int surf_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr
         // nothing is described, download otherwise) is closed behind it.
         tm.begin(SURF_T_SELECT);
         int n_cand = 0;
-        SURF_TRY(hipMemcpyAsync(&n_cand, d_ncand, sizeof(int), hipMemcpyDeviceToHost, s));
-        SURF_TRY(hipMemcpyAsync(counts.data() + (size_t)i0 * n_octaves * 2, d_counts + (size_t)i0 * n_octaves * 2, sizeof(int) * (size_t)ng * n_octaves * 2,
+        UNIT_TRY(hipMemcpyAsync(&n_cand, d_ncand, sizeof(int), hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipMemcpyAsync(counts.data() + (size_t)i0 * n_octaves * 2, d_counts + (size_t)i0 * n_octaves * 2, sizeof(int) * (size_t)ng * n_octaves * 2,
                                 hipMemcpyDeviceToHost, s));
-        SURF_TRY(hipStreamSynchronize(s));
+        UNIT_TRY(hipStreamSynchronize(s));
         if (n_cand < 0 || n_cand > cand_cap) return (int)hipErrorUnknown;          // cannot happen: candidate_bound
         std::vector<SurfSegment> seg((size_t)ng);
         long long begin = 0, rows = 0, max_kept = 0;
@@ -404,54 +400,54 @@ int surf_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr
         if (rows > 0 && kp_ptr[i1] <= cap) {
             hipcub::DoubleBuffer<uint64_t> k(d_key[0], d_key[1]), e(d_ent[0], d_ent[1]);
             size_t ba = sort_a, bb = sort_b, bc = sort_c;
-            SURF_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, ba, e, k, n_cand, 0, ENT_IMAGE_SHIFT + img_bits, s));
-            SURF_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, bb, k, e, n_cand, 0, 64, s));
-            if (ng > 1) SURF_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, bc, e, k, n_cand, ENT_IMAGE_SHIFT, ENT_IMAGE_SHIFT + img_bits, s));
+            UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, ba, e, k, n_cand, 0, ENT_IMAGE_SHIFT + img_bits, s));
+            UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, bb, k, e, n_cand, 0, 64, s));
+            if (ng > 1) UNIT_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, bc, e, k, n_cand, ENT_IMAGE_SHIFT, ENT_IMAGE_SHIFT + img_bits, s));
             tm.end();
 
             sfmba_surf_keypoint* d_kp;
             float* d_desc;
             int* d_bin;
             long long *d_mom, *d_sums;
-            SURF_ALLOC(scratch, d_kp, sfmba_surf_keypoint, (size_t)rows);
-            SURF_ALLOC(scratch, d_desc, float, (size_t)rows * SURF_DESC_DIMS);
-            SURF_ALLOC(scratch, d_bin, int, (size_t)rows);
-            SURF_ALLOC(scratch, d_mom, long long, (size_t)rows * 2);
-            SURF_ALLOC(scratch, d_sums, long long, (size_t)rows * SURF_DESC_DIMS);
+            UNIT_ALLOC(scratch, d_kp, sfmba_surf_keypoint, (size_t)rows);
+            UNIT_ALLOC(scratch, d_desc, float, (size_t)rows * SURF_DESC_DIMS);
+            UNIT_ALLOC(scratch, d_bin, int, (size_t)rows);
+            UNIT_ALLOC(scratch, d_mom, long long, (size_t)rows * 2);
+            UNIT_ALLOC(scratch, d_sums, long long, (size_t)rows * SURF_DESC_DIMS);
             tm.begin(SURF_T_DESCRIBE);
-            SURF_TRY(hipMemcpyAsync(d_seg, seg.data(), sizeof(SurfSegment) * seg.size(), hipMemcpyHostToDevice, s));
+            UNIT_TRY(hipMemcpyAsync(d_seg, seg.data(), sizeof(SurfSegment) * seg.size(), hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(k_surf_describe, dim3((unsigned)((max_kept + LANES / 64 - 1) / (LANES / 64)), (unsigned)ng), dim3(LANES), 0, s, d_tab, d_seg,
                                d_int, e.Current(), k.Current(), upright, d_kp, d_desc, d_bin, d_mom, d_sums);
-            SURF_TRY(hipGetLastError());
+            UNIT_TRY(hipGetLastError());
             tm.end();
             tm.begin(SURF_T_DOWNLOAD);
             const size_t end = (size_t)(row0 + rows);
             h_kp.resize(end);
             h_desc.resize(end * SURF_DESC_DIMS);
-            SURF_TRY(hipMemcpyAsync(h_kp.data() + row0, d_kp, sizeof(sfmba_surf_keypoint) * (size_t)rows, hipMemcpyDeviceToHost, s));
-            SURF_TRY(hipMemcpyAsync(h_desc.data() + (size_t)row0 * SURF_DESC_DIMS, d_desc, sizeof(float) * (size_t)rows * SURF_DESC_DIMS, hipMemcpyDeviceToHost, s));
+            UNIT_TRY(hipMemcpyAsync(h_kp.data() + row0, d_kp, sizeof(sfmba_surf_keypoint) * (size_t)rows, hipMemcpyDeviceToHost, s));
+            UNIT_TRY(hipMemcpyAsync(h_desc.data() + (size_t)row0 * SURF_DESC_DIMS, d_desc, sizeof(float) * (size_t)rows * SURF_DESC_DIMS, hipMemcpyDeviceToHost, s));
             if (dbg_bin) {
                 h_bin.resize(end);
-                SURF_TRY(hipMemcpyAsync(h_bin.data() + row0, d_bin, sizeof(int) * (size_t)rows, hipMemcpyDeviceToHost, s));
+                UNIT_TRY(hipMemcpyAsync(h_bin.data() + row0, d_bin, sizeof(int) * (size_t)rows, hipMemcpyDeviceToHost, s));
             }
             if (dbg_moments) {
                 h_mom.resize(end * 2);
-                SURF_TRY(hipMemcpyAsync(h_mom.data() + (size_t)row0 * 2, d_mom, sizeof(long long) * (size_t)rows * 2, hipMemcpyDeviceToHost, s));
+                UNIT_TRY(hipMemcpyAsync(h_mom.data() + (size_t)row0 * 2, d_mom, sizeof(long long) * (size_t)rows * 2, hipMemcpyDeviceToHost, s));
             }
             if (dbg_sums) {
                 h_sums.resize(end * SURF_DESC_DIMS);
-                SURF_TRY(hipMemcpyAsync(h_sums.data() + (size_t)row0 * SURF_DESC_DIMS, d_sums, sizeof(long long) * (size_t)rows * SURF_DESC_DIMS,
+                UNIT_TRY(hipMemcpyAsync(h_sums.data() + (size_t)row0 * SURF_DESC_DIMS, d_sums, sizeof(long long) * (size_t)rows * SURF_DESC_DIMS,
                                         hipMemcpyDeviceToHost, s));
             }
         }
         tm.end();
-        SURF_TRY(hipStreamSynchronize(s));                     // the group's arena goes back to the cache below
+        UNIT_TRY(hipStreamSynchronize(s));                     // the group's arena goes back to the cache below
         i0 = i1;
     }
 
     const long long tot = kp_ptr[n_images];
     *total = tot;
-    if (tot > cap) return SURF_ERR_CAPACITY;
+    if (tot > cap) return UNIT_ERR_CAPACITY;
     static_assert(sizeof(long long) == sizeof(int64_t), "the debug rows leave as they are");
     if (dbg_candidates) std::memcpy(dbg_candidates, counts.data(), sizeof(int) * counts.size());
     if (tot > 0) {

@@ -16,6 +16,7 @@
 #include "ba_kernels.h"
 #include "device_arena.h"
 #include "triangulate_math.h"
+#include "unit_common.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -106,9 +107,6 @@ struct KeepToCount {
     __host__ __device__ long long operator()(unsigned char k) const { return k ? 1 : 0; }
 };
 
-#define TRI_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-#define TRI_ALLOC(ptr, T, n) do { ptr = arena.alloc_n<T>(n); if (!ptr) return (int)hipErrorOutOfMemory; } while (0)
-
 }  // namespace
 
 void launch_triangulate(hipStream_t s, long long n, const float* d_left, const float* d_right, const float K[9], const float Pl[12],
@@ -136,56 +134,56 @@ int triangulate_pairs(hipStream_t s, int device, int n_images, const int64_t* im
     int *d_left, *d_right, *d_query, *d_train;
     float *d_Pl, *d_Pr, *d_x, *d_e = nullptr;
     unsigned char *d_mask = nullptr, *d_keep;
-    TRI_ALLOC(d_img, long long, (size_t)n_images + 1);
-    TRI_ALLOC(d_pts, float2, (size_t)n_pts);
-    TRI_ALLOC(d_left, int, (size_t)n_pairs);
-    TRI_ALLOC(d_right, int, (size_t)n_pairs);
-    TRI_ALLOC(d_ptr, long long, (size_t)n_pairs + 1);
-    TRI_ALLOC(d_query, int, (size_t)total);
-    TRI_ALLOC(d_train, int, (size_t)total);
-    if (mask) TRI_ALLOC(d_mask, unsigned char, (size_t)total);
-    TRI_ALLOC(d_Pl, float, (size_t)12 * n_pairs);
-    TRI_ALLOC(d_Pr, float, (size_t)12 * n_pairs);
-    TRI_ALLOC(d_x, float, (size_t)3 * total);
-    if (reproj_err) TRI_ALLOC(d_e, float, (size_t)2 * total);
-    TRI_ALLOC(d_keep, unsigned char, (size_t)total + 1);           // one past the end stays 0: the scan's last item
-    TRI_ALLOC(d_pos, long long, (size_t)total + 1);
-    TRI_ALLOC(d_kidx, long long, (size_t)total);
-    TRI_ALLOC(d_kptr, long long, (size_t)n_pairs + 1);
+    UNIT_ALLOC(arena, d_img, long long, (size_t)n_images + 1);
+    UNIT_ALLOC(arena, d_pts, float2, (size_t)n_pts);
+    UNIT_ALLOC(arena, d_left, int, (size_t)n_pairs);
+    UNIT_ALLOC(arena, d_right, int, (size_t)n_pairs);
+    UNIT_ALLOC(arena, d_ptr, long long, (size_t)n_pairs + 1);
+    UNIT_ALLOC(arena, d_query, int, (size_t)total);
+    UNIT_ALLOC(arena, d_train, int, (size_t)total);
+    if (mask) UNIT_ALLOC(arena, d_mask, unsigned char, (size_t)total);
+    UNIT_ALLOC(arena, d_Pl, float, (size_t)12 * n_pairs);
+    UNIT_ALLOC(arena, d_Pr, float, (size_t)12 * n_pairs);
+    UNIT_ALLOC(arena, d_x, float, (size_t)3 * total);
+    if (reproj_err) UNIT_ALLOC(arena, d_e, float, (size_t)2 * total);
+    UNIT_ALLOC(arena, d_keep, unsigned char, (size_t)total + 1);           // one past the end stays 0: the scan's last item
+    UNIT_ALLOC(arena, d_pos, long long, (size_t)total + 1);
+    UNIT_ALLOC(arena, d_kidx, long long, (size_t)total);
+    UNIT_ALLOC(arena, d_kptr, long long, (size_t)n_pairs + 1);
     size_t scan_bytes = 0;
     hipcub::TransformInputIterator<long long, KeepToCount, const unsigned char*> keep_in(d_keep, KeepToCount());
-    TRI_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, keep_in, d_pos, (int)(total + 1), s));
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, keep_in, d_pos, (int)(total + 1), s));
     void* d_tmp = arena.alloc(scan_bytes ? scan_bytes : 1);
     if (!d_tmp) return (int)hipErrorOutOfMemory;
 
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "the index arrays are uploaded as they are");
-    TRI_TRY(hipMemcpyAsync(d_img, img_ptr, sizeof(int64_t) * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
-    TRI_TRY(hipMemcpyAsync(d_ptr, pair_ptr, sizeof(int64_t) * ((size_t)n_pairs + 1), hipMemcpyHostToDevice, s));
-    TRI_TRY(hipMemcpyAsync(d_left, pair_left, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-    TRI_TRY(hipMemcpyAsync(d_right, pair_right, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-    TRI_TRY(hipMemcpyAsync(d_Pl, P_left, sizeof(float) * 12 * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-    TRI_TRY(hipMemcpyAsync(d_Pr, P_right, sizeof(float) * 12 * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-    if (n_pts > 0) TRI_TRY(hipMemcpyAsync(d_pts, pts, sizeof(float) * 2 * (size_t)n_pts, hipMemcpyHostToDevice, s));
-    TRI_TRY(hipMemcpyAsync(d_query, query_idx, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
-    TRI_TRY(hipMemcpyAsync(d_train, train_idx, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
-    if (mask) TRI_TRY(hipMemcpyAsync(d_mask, mask, (size_t)total, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_img, img_ptr, sizeof(int64_t) * ((size_t)n_images + 1), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_ptr, pair_ptr, sizeof(int64_t) * ((size_t)n_pairs + 1), hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_left, pair_left, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_right, pair_right, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_Pl, P_left, sizeof(float) * 12 * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_Pr, P_right, sizeof(float) * 12 * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+    if (n_pts > 0) UNIT_TRY(hipMemcpyAsync(d_pts, pts, sizeof(float) * 2 * (size_t)n_pts, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_query, query_idx, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
+    UNIT_TRY(hipMemcpyAsync(d_train, train_idx, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, s));
+    if (mask) UNIT_TRY(hipMemcpyAsync(d_mask, mask, (size_t)total, hipMemcpyHostToDevice, s));
 
     const TriProblem pr{ d_img, d_pts, d_left, d_right, d_ptr, d_query, d_train, d_mask, d_Pl, d_Pr };
     TriK Kv;
     for (int e = 0; e < 9; ++e) Kv.v[e] = K[e];
     hipLaunchKernelGGL(k_triangulate_pairs, dim3((unsigned)((total - first + 255) / 256)), dim3(256), 0, s, first, total, n_pairs, pr, Kv, max_err,
                        d_x, d_keep, d_e);
-    TRI_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, scan_bytes, keep_in, d_pos, (int)(total + 1), s));
+    UNIT_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, scan_bytes, keep_in, d_pos, (int)(total + 1), s));
     const long long lanes = total > (long long)n_pairs + 1 ? total : (long long)n_pairs + 1;
     hipLaunchKernelGGL(k_tri_compact, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, total, n_pairs, d_keep, d_pos, d_ptr, d_kidx, d_kptr);
-    TRI_TRY(hipGetLastError());
-    TRI_TRY(hipMemcpyAsync(points3d, d_x, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToHost, s));
-    TRI_TRY(hipMemcpyAsync(keep, d_keep, (size_t)total, hipMemcpyDeviceToHost, s));
-    if (reproj_err) TRI_TRY(hipMemcpyAsync(reproj_err, d_e, sizeof(float) * 2 * (size_t)total, hipMemcpyDeviceToHost, s));
-    TRI_TRY(hipMemcpyAsync(kept_ptr, d_kptr, sizeof(int64_t) * ((size_t)n_pairs + 1), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipGetLastError());
+    UNIT_TRY(hipMemcpyAsync(points3d, d_x, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipMemcpyAsync(keep, d_keep, (size_t)total, hipMemcpyDeviceToHost, s));
+    if (reproj_err) UNIT_TRY(hipMemcpyAsync(reproj_err, d_e, sizeof(float) * 2 * (size_t)total, hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipMemcpyAsync(kept_ptr, d_kptr, sizeof(int64_t) * ((size_t)n_pairs + 1), hipMemcpyDeviceToHost, s));
     // only the first kept_ptr[n_pairs] entries are defined; the rest of the buffer comes back as the arena's zeros
-    TRI_TRY(hipMemcpyAsync(kept_idx, d_kidx, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, s));
-    TRI_TRY(hipStreamSynchronize(s));
+    UNIT_TRY(hipMemcpyAsync(kept_idx, d_kidx, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipStreamSynchronize(s));
     return 0;
 }
 
