@@ -176,6 +176,13 @@ __global__ __launch_bounds__(256) void k_finalize(DeviceStructure ds, DeviceBuff
     __shared__ int is_last;
     const int gt = blockIdx.x * blockDim.x + threadIdx.x;
     const LMState* st = db.st;
+    // what the launch reads of the LM state, once and in front of its first store: read where they are used, the clamps and the radius came
+    // back after every store of a damped diagonal entry (six round trips in a row on the writer lane of every camera), and the
+    // accepted buffer's index was a vector load that the second half of a camera's loads waited for, each behind a pointer load of its own
+    const int cur = st->cur;
+    const double min_diag = st->min_diag, max_diag = st->max_diag, radius = st->radius, fscale = st->fscale;
+    const double* const cam_c = cur ? db.cam[1] : db.cam[0];
+    const double* const tab = cur ? db.camtab[1] : db.camtab[0];
     if (pcg && db.pcg_zero) { for (int i = gt; i < db.pcg_zero_n; i += gridDim.x * blockDim.x) db.pcg_zero[i] = 0.0; }      // (the symmetric CG's S~ W~ is accumulated with atomics)
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x >= 192) {
         // focal-focal entries were accumulated in the slotted buffer: the last wave of the last block owns them
@@ -185,10 +192,10 @@ __global__ __launch_bounds__(256) void k_finalize(DeviceStructure ds, DeviceBuff
         const double sff = foc[0], rhsf = foc[1], udf = foc[2], bcf = foc[3];
         if (threadIdx.x == 192) {
             const int fo = ds.d - 1;
-            const double dd = fmin(fmax(udf, st->min_diag), st->max_diag) / st->radius;
+            const double dd = fmin(fmax(udf, min_diag), max_diag) / radius;
             db.S[(size_t)fo * ds.ld + fo] = sff + dd;
             db.rhs[fo] = rhsf; db.udiag[fo] = udf; db.bc[fo] = bcf;
-            const double gg = fabs(bcf / st->fscale);
+            const double gg = fabs(bcf / fscale);
             if (gg > 0.0) atomic_max_nonneg(slot_ptr(db, ACC_GMAX), gg);
             if (!finite_d(sff + dd) || !finite_d(rhsf)) atomicAdd(slot_ptr(db, ACC_BAD_LIN), 1.0);
             if (pcg && !(sff + dd > 0.0)) atomicCAS(db.lin_info, 0, ds.d);
@@ -211,9 +218,8 @@ __global__ __launch_bounds__(256) void k_finalize(DeviceStructure ds, DeviceBuff
             for (int b = 0; b < 6; ++b) Sb[a][b] = (b >= a) ? db.S[(size_t)(row0 + a) * ds.ld + row0 + b] : 0.0;
         }
         if (pcg) {
-            const double* tab = db.camtab[st->cur];
 #pragma unroll
-            for (int e = 0; e < 6; ++e) camv[e] = db.pcg_W ? db.cam[st->cur][6 * (size_t)g + e] : 0.0;
+            for (int e = 0; e < 6; ++e) camv[e] = db.pcg_W ? cam_c[6 * (size_t)g + e] : 0.0;
 #pragma unroll
             for (int e = 0; e < 9; ++e) { Rm[e] = db.pcg_W ? tab[cam_tab_index(CT_R + e, g, ds.ncam)] : 0.0; Q9[e] = db.pair_G ? tab[cam_tab_index(CT_QD + e, g, ds.ncam)] : 0.0; }
             cq = db.pcg_W ? tab[cam_tab_index(CT_CQ, g, ds.ncam)] : 0.0;
@@ -243,7 +249,7 @@ __global__ __launch_bounds__(256) void k_finalize(DeviceStructure ds, DeviceBuff
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
             const int e = row0 + a;
-            const double dd = fmin(fmax(ud[a], st->min_diag), st->max_diag) / st->radius;
+            const double dd = fmin(fmax(ud[a], min_diag), max_diag) / radius;
             const double v = Sb[a][a] + dd;
             Sb[a][a] = v;
             if (writer) db.S[(size_t)e * ds.ld + e] = v;

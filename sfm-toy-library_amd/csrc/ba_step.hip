@@ -10,30 +10,77 @@ namespace sfmba {
 // ------------------------------------------------------------------------------------------
 // back-substitution + trial point
 // ------------------------------------------------------------------------------------------
-// One thread per camera: delta = scale * y ; trial camera = camera - delta ; step table; table of the trial camera
+// CU_LANES lanes per camera (the form of k_finalize's FIN_LANES): delta = scale * y ; trial camera = camera - delta ; step table; table
+// of the trial camera.  Every lane of a camera's group loads what the camera needs -- all of it, and what the focal entry's owner needs,
+// in ONE level in front of the first store -- and forms the step, the trial camera and its table with the same instructions; lane t then
+// stores its share of the ~90 scattered values (cam[nxt], camtab[nxt], steptab, the fp32 record: the 16- / 32-byte pieces t,
+// t + CU_LANES, ... of each, picked by selects).  A workgroup holds the 64 cameras of what was one wave of the one-lane-per-camera form,
+// so the grid spreads over ceil(ncam / 64) CUs and the three sums are still formed from ONE value per camera by the butterfly over those
+// 64 cameras (handed to the first wave through LDS): bit for bit the sums of the one-lane form up to 64 cameras; above, the sums of the
+// groups of 64 meet in the slots instead of in one workgroup.
+constexpr int CU_LANES = 4;
+constexpr int CU_CAMS = BLK / CU_LANES;
+static_assert(CU_CAMS == 64, "k_cam_update: the cameras of a workgroup are summed by one wave");
+
+// lane t of a group stores the pieces t, t + CU_LANES, ... (P values each) of v[N], which every lane of the group holds; at(e): where value e goes
+template <int N, int P, typename V, typename At>
+__device__ __forceinline__ void store_share(int t, const V (&v)[N], At at) {
+    static_assert(N % P == 0, "whole pieces");
+    constexpr int NP = N / P;
+#pragma unroll
+    for (int k0 = 0; k0 < NP; k0 += CU_LANES) {
+        V w[P];
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            w[r] = v[P * k0 + r];
+#pragma unroll
+            for (int u = 1; u < CU_LANES; ++u) if (k0 + u < NP) w[r] = (t == u) ? v[P * (k0 + u) + r] : w[r];
+        }
+        if (k0 + t < NP) {
+#pragma unroll
+            for (int r = 0; r < P; ++r) *at(P * (k0 + t) + r) = w[r];
+        }
+    }
+}
+
 __global__ __launch_bounds__(BLK) void k_cam_update(DeviceStructure ds, DeviceBuffers db) {
-    __shared__ double scratch[BLK / 64];
+    __shared__ double part[3][CU_CAMS];
     if (db.cg_gate && !db.cg_force && db.cg_gate[0] == 0) return;      // the CG batch in front of this launch was too short
     LMState* st = db.st;
     const int cur = st->cur, nxt = cur ^ 1;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    // (picked from the two kernel arguments: indexed by a loaded value the pointer itself is a load, and the one of the trial buffer sat behind a store)
+    const double* const cam_c = cur ? db.cam[1] : db.cam[0];
+    const double* const tab_c = cur ? db.camtab[1] : db.camtab[0];
+    double* const cam_n = cur ? db.cam[0] : db.cam[1];
+    double* const tab_n = cur ? db.camtab[0] : db.camtab[1];
+    const int jl = threadIdx.x / CU_LANES, t = threadIdx.x % CU_LANES;         // camera of the workgroup, lane of its group
+    const int j = blockIdx.x * CU_CAMS + jl;
+    const bool focal_owner = blockIdx.x == 0 && threadIdx.x == 0;
     double step2 = 0.0, xn2 = 0.0, gdot = 0.0;
+    // the focal entry's owner: its loads belong to the same level (behind the camera's stores they were a round trip of their own)
+    double f0 = 0.0, fsc = 0.0, zf = 0.0, bcf = 0.0;
+    if (focal_owner) {
+        f0 = st->focal[cur]; fsc = st->fscale;
+        zf = db.rhs[ds.d - 1];
+        if (db.pcg_vec) zf = db.pcg_linv[(size_t)ds.ncam * 36] * db.pcg_vec[(size_t)db.pcg_flags[2] * ds.ld + ds.d - 1];
+        if (db.pu32) bcf = db.bc[ds.d - 1];
+    }
     if (j < ds.ncam) {
         double dlt[6], cn[6], z[6];
         // every load of this camera before the first store (the stores below may alias as far as the compiler can tell: a load behind
-        // one of them waits for its own round trip -- six in a row in the loop this replaces)
+        // one of them waits for its own round trip)
         double c0[6], cs[6], xin[6], Lt[6][6], Q9[9];
 #pragma unroll
-        for (int e = 0; e < 6; ++e) { c0[e] = db.cam[cur][6 * j + e]; cs[e] = db.cscale[6 * j + e]; }
+        for (int e = 0; e < 6; ++e) { c0[e] = cam_c[6 * j + e]; cs[e] = db.cscale[6 * j + e]; }
         // Q = R K' and the first-order flag of the camera AT THE LINEARISATION POINT: the back-substitution re-evaluates the camera
         // block of an observation in the factored form A = P [ -[X_g]x | I ] diag(Q, I) (sfmba_device.h), so the step arrives as Q dw
 #pragma unroll
-        for (int e = 0; e < 9; ++e) Q9[e] = db.camtab[cur][cam_tab_index(CT_QD + e, j, ds.ncam)];
-        const double small_cur = db.camtab[cur][cam_tab_index(CT_SMALL, j, ds.ncam)];
+        for (int e = 0; e < 9; ++e) Q9[e] = tab_c[cam_tab_index(CT_QD + e, j, ds.ncam)];
+        const double small_cur = tab_c[cam_tab_index(CT_SMALL, j, ds.ncam)];
         double Rt_cur[12], bcj[6];
         if (db.pu32) {
 #pragma unroll
-            for (int e = 0; e < 12; ++e) Rt_cur[e] = db.camtab[cur][cam_tab_index(CT_R + e, j, ds.ncam)];
+            for (int e = 0; e < 12; ++e) Rt_cur[e] = tab_c[cam_tab_index(CT_R + e, j, ds.ncam)];
 #pragma unroll
             for (int e = 0; e < 6; ++e) bcj[e] = db.bc[6 * j + e];
         }
@@ -41,23 +88,23 @@ __global__ __launch_bounds__(BLK) void k_cam_update(DeviceStructure ds, DeviceBu
             const double* x = db.pcg_vec + (size_t)db.pcg_flags[2] * ds.ld + 6 * j;
             const double* Li = db.pcg_linv + (size_t)j * 36;
 #pragma unroll
-            for (int t = 0; t < 6; ++t) {
-                xin[t] = x[t];
+            for (int r = 0; r < 6; ++r) {
+                xin[r] = x[r];
 #pragma unroll
-                for (int c = 0; c < 6; ++c) Lt[t][c] = (c <= t) ? Li[t * 6 + c] : 0.0;
+                for (int c = 0; c < 6; ++c) Lt[r][c] = (c <= r) ? Li[r * 6 + c] : 0.0;
             }
 #pragma unroll
             for (int c = 0; c < 6; ++c) {
                 double v = 0.0;
 #pragma unroll
-                for (int t = 0; t < 6; ++t) if (t >= c) v += Lt[t][c] * xin[t];
+                for (int r = 0; r < 6; ++r) if (r >= c) v += Lt[r][c] * xin[r];
                 z[c] = v;
             }
         } else {
 #pragma unroll
             for (int c = 0; c < 6; ++c) z[c] = db.rhs[6 * j + c];
         }
-        if (db.probe_z) {
+        if (db.probe_z && t == 0) {
 #pragma unroll
             for (int e = 0; e < 6; ++e) db.probe_z[6 * j + e] = z[e];
         }
@@ -69,11 +116,8 @@ __global__ __launch_bounds__(BLK) void k_cam_update(DeviceStructure ds, DeviceBu
             step2 += df * df;
             xn2 += cn[e] * cn[e];
         }
-#pragma unroll
-        for (int e = 0; e < 6; ++e) db.cam[nxt][6 * j + e] = cn[e];
         double ctn[CT_STRIDE];
         make_cam_table(cn, cs, ctn);
-        for (int e = 0; e < CT_STRIDE; ++e) db.camtab[nxt][cam_tab_index(e, j, ds.ncam)] = ctn[e];
         double stb[ST_STRIDE] = {};
         for (int e = 0; e < 9; ++e) stb[ST_RN + e] = ctn[CT_R + e];
         for (int e = 0; e < 3; ++e) {
@@ -81,37 +125,41 @@ __global__ __launch_bounds__(BLK) void k_cam_update(DeviceStructure ds, DeviceBu
             stb[ST_DT + e] = dlt[3 + e]; stb[ST_TN + e] = ctn[CT_T + e];
         }
         stb[ST_SMALL] = small_cur;
-        for (int e = 0; e < ST_STRIDE; ++e) db.steptab[cam_tab_index(e, j, ds.ncam)] = stb[e];
+        store_share<6, 2>(t, cn, [&](int e) { return cam_n + 6 * (size_t)j + e; });
+        store_share<CT_STRIDE, 4>(t, ctn, [&](int e) { return tab_n + cam_tab_index(e, j, ds.ncam); });
+        store_share<ST_STRIDE, 4>(t, stb, [&](int e) { return db.steptab + cam_tab_index(e, j, ds.ncam); });
         if (db.pu32) {
             // the first sweep of k_point_update in F32J mode: what it needs of this camera as ONE 80-byte fp32 record; and the part of the model
             // cost change that sweep no longer forms per observation: sum_obs u . r = (step) . (gradient) = sum z_i bc_i in the scaled unknowns
-            float* rec = db.pu32 + 20 * (size_t)j;
+            float rec[20];
 #pragma unroll
             for (int e = 0; e < 12; ++e) rec[e] = (float)Rt_cur[e];
 #pragma unroll
             for (int e = 0; e < 8; ++e) rec[12 + e] = (float)stb[e];
+            store_share<20, 4>(t, rec, [&](int e) { return db.pu32 + 20 * (size_t)j + e; });
 #pragma unroll
             for (int e = 0; e < 6; ++e) gdot += z[e] * bcj[e];
         }
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const double f0 = st->focal[cur];
-        double zf = db.rhs[ds.d - 1];
-        if (db.pcg_vec) zf = db.pcg_linv[(size_t)ds.ncam * 36] * db.pcg_vec[(size_t)db.pcg_flags[2] * ds.ld + ds.d - 1];
+    if (focal_owner) {
         if (db.probe_z) db.probe_z[ds.d - 1] = zf;
-        const double fn = f0 - st->fscale * zf;
+        const double fn = f0 - fsc * zf;
         st->focal[nxt] = fn;
         const double df = f0 - fn;
         step2 += df * df;
         xn2 += fn * fn;
-        if (db.pu32) gdot += zf * db.bc[ds.d - 1];
+        if (db.pu32) gdot += zf * bcf;
     }
-    const double s2 = block_sum(step2, scratch);
-    const double x2 = block_sum(xn2, scratch);
-    if (threadIdx.x == 0) { atomicAdd(slot_ptr(db, ACC_STEP2), db.shared_weight * s2); atomicAdd(slot_ptr(db, ACC_XNEW2), db.shared_weight * x2); }
-    if (db.pu32) {
-        const double gd = block_sum(gdot, scratch);
-        if (threadIdx.x == 0) atomicAdd(slot_ptr(db, ACC_MODEL), db.shared_weight * gd);      // (sharded: the cameras are replicated, rank 0 counts them)
+    // one value per camera, summed as one wave of one lane per camera would sum them
+    if (t == 0) { part[0][jl] = step2; part[1][jl] = xn2; part[2][jl] = gdot; }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const double s2 = wave_sum(part[0][threadIdx.x]), x2 = wave_sum(part[1][threadIdx.x]), gd = wave_sum(part[2][threadIdx.x]);
+        if (threadIdx.x == 0) {
+            atomicAdd(slot_ptr(db, ACC_STEP2), db.shared_weight * s2);
+            atomicAdd(slot_ptr(db, ACC_XNEW2), db.shared_weight * x2);
+            if (db.pu32) atomicAdd(slot_ptr(db, ACC_MODEL), db.shared_weight * gd);      // (sharded: the cameras are replicated, rank 0 counts them)
+        }
     }
 }
 
@@ -401,7 +449,7 @@ __global__ __launch_bounds__(PBK, 4) void k_point_update(DeviceStructure ds, Dev
 }
 
 void launch_cam_update(hipStream_t s, const DeviceStructure& ds, const DeviceBuffers& db) {
-    hipLaunchKernelGGL(k_cam_update, dim3((ds.ncam + BLK - 1) / BLK), dim3(BLK), 0, s, ds, db);
+    hipLaunchKernelGGL(k_cam_update, dim3((ds.ncam + CU_CAMS - 1) / CU_CAMS), dim3(BLK), 0, s, ds, db);
 }
 
 template <typename T>
