@@ -298,6 +298,11 @@ SFMBA_API int  sfmba_problem_create_ex(int device, int precision, int flags,
  * results agree with that up to floating-point reordering, NOT bit for bit: newly observed cameras / points take the next free
  * slot in order of first observation (create assigns slots in ascending caller index), so the reduced system is a symmetric
  * permutation of create's and sums are taken in a different order.
+ * Slots are internal.  Every entry point speaks in caller indices, whatever the slots are: parameters and the point step of the
+ * probe in the caller's arrays, per-observation outputs in the caller's observation order, and the reduced unknowns of
+ * sfmba_problem_build_reduced (S, rhs, scale) and sfmba_problem_get_step_probe (z) with the ACTIVE cameras by ascending caller
+ * index, six unknowns each, the focal last -- where the slots do not ascend (after an out-of-order append) those two test hooks
+ * permute on the host on the way out; on a freshly created problem the device arrays go out as they are.
  * Failure contract: if the call fails after it has begun replacing the device structure (allocation or HIP error), the problem
  * is POISONED -- every later entry point on it returns SFMBA_ERR_INVALID_ARG ("poisoned") without touching the device and the
  * only valid call is sfmba_problem_destroy.  Argument errors (bad sizes, indices out of range) are detected first and leave the

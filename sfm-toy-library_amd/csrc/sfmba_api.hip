@@ -46,6 +46,33 @@ int sfmba::flush_reset(sfmba_problem* p) {
     return upload_default_state(p);
 }
 
+// The device keeps the reduced unknowns in SLOT order; the test hooks hand them out as include/sfmba.h states it: active cameras by
+// ascending caller index, focal last.  Empty when the slots already ascend (every fresh create: the device arrays go out as they are);
+// otherwise src[i] = the device unknown that unknown i of the caller is (an append that registered cameras out of index order).
+static std::vector<int> reduced_unknown_order(const sfmba_problem* p) {
+    const std::vector<int>& id = p->acam_id;
+    std::vector<int> src;
+    if (std::is_sorted(id.begin(), id.end())) return src;
+    const int ncam = (int)id.size();
+    std::vector<int> slots((size_t)ncam);
+    for (int j = 0; j < ncam; ++j) slots[(size_t)j] = j;
+    std::sort(slots.begin(), slots.end(), [&](int a, int b) { return id[(size_t)a] < id[(size_t)b]; });
+    src.resize((size_t)6 * ncam + 1);
+    for (int r = 0; r < ncam; ++r)
+        for (int c = 0; c < 6; ++c) src[6 * (size_t)r + c] = 6 * slots[(size_t)r] + c;
+    src[(size_t)6 * ncam] = 6 * ncam;
+    return src;
+}
+
+// out[i] = device[src[i]] for a vector of the reduced unknowns (src empty: a plain copy)
+static int download_reduced_vector(double* out, const double* d_vec, int d, const std::vector<int>& src) {
+    if (src.empty()) { HIP_TRY(hipMemcpy(out, d_vec, sizeof(double) * (size_t)d, hipMemcpyDeviceToHost)); return SFMBA_OK; }
+    std::vector<double> h((size_t)d);
+    HIP_TRY(hipMemcpy(h.data(), d_vec, sizeof(double) * (size_t)d, hipMemcpyDeviceToHost));
+    for (int i = 0; i < d; ++i) out[i] = h[(size_t)src[(size_t)i]];
+    return SFMBA_OK;
+}
+
 extern "C" {
 void sfmba_options_default(sfmba_options* o) {
     std::memset(o, 0, sizeof(*o));
@@ -244,7 +271,7 @@ int sfmba_problem_get_step_probe(sfmba_problem* p, double* z, double* dpt, sfmba
     if (p->probe.family == 0 || !p->d_probe) return SFMBA_OK;      // no back-substitution has run since the probe was enabled
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipStreamSynchronize(p->stream));
-    if (z) HIP_TRY(hipMemcpy(z, p->d_probe, sizeof(double) * (size_t)p->ds.d, hipMemcpyDeviceToHost));
+    if (z) { const int zrc = download_reduced_vector(z, p->d_probe, p->ds.d, reduced_unknown_order(p)); if (zrc) return zrc; }
     if (dpt) {
         const int npt = (int)p->apt_id.size();
         std::vector<double> h((size_t)3 * std::max(npt, 1));
@@ -325,9 +352,20 @@ int sfmba_problem_build_reduced(sfmba_problem* p, const sfmba_options* opt, doub
     HIP_TRY(dev_alloc(&d_scale, (size_t)d));
     launch_mirror_scale(p->stream, p->ds, p->db, d_full, d_scale);
     HIP_TRY(hipStreamSynchronize(p->stream));
-    if (S) HIP_TRY(hipMemcpy(S, d_full, sizeof(double) * (size_t)d * d, hipMemcpyDeviceToHost));
-    if (rhs) HIP_TRY(hipMemcpy(rhs, p->db.rhs, sizeof(double) * (size_t)d, hipMemcpyDeviceToHost));
-    if (scale) HIP_TRY(hipMemcpy(scale, d_scale, sizeof(double) * (size_t)d, hipMemcpyDeviceToHost));
+    const std::vector<int> src = reduced_unknown_order(p);
+    if (S) {
+        if (src.empty()) HIP_TRY(hipMemcpy(S, d_full, sizeof(double) * (size_t)d * d, hipMemcpyDeviceToHost));
+        else {
+            std::vector<double> h((size_t)d * d);
+            HIP_TRY(hipMemcpy(h.data(), d_full, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+            for (int r = 0; r < d; ++r) {
+                const double* row = &h[(size_t)src[(size_t)r] * d];
+                for (int c = 0; c < d; ++c) S[(size_t)r * d + c] = row[(size_t)src[(size_t)c]];
+            }
+        }
+    }
+    if (rhs) { rc = download_reduced_vector(rhs, p->db.rhs, d, src); if (rc) return rc; }
+    if (scale) { rc = download_reduced_vector(scale, d_scale, d, src); if (rc) return rc; }
     return SFMBA_OK;
 }
 
