@@ -1060,6 +1060,83 @@ SFMBA_API int sfmba_cloud_merge(int device, int64_t n, const float* xyz /*[n][3]
                 unsigned char* bgr_out /*[cap][3]*/, float* normal_out /*[cap][3]*/, int32_t* count /*[cap]*/, int32_t* first /*[cap]*/,
                 int32_t* voxel_of /*[n] or NULL*/, int64_t cap, int64_t* total, int64_t* n_skipped);
 
+/* ---- a surface from the depth maps: TSDF fusion and marching tetrahedra (SfM::meshDenseCloud) ------------------------------------
+ * The clouds above are a weak basis for a surface: the fuse leaves a surface element once per view, and the depth error keeps the
+ * duplicates apart.  These three calls average the depth maps along the viewing rays in a truncated signed distance grid and take
+ * the zero set of the grid out as a triangle mesh.  THE CONTRACT IS OUR OWN AND EQUALS NOBODY'S, stated so that the device is held
+ * BIT FOR BIT to a CPU restatement (tests/mesh_oracle.py): fp64 with EVERY OPERATION ROUNDED ON ITS OWN (csrc/mesh_math.h switches
+ * the compiler's contraction off), and NOTHING BUT INTEGERS IS SUMMED per voxel, so the result does not depend on the order of the
+ * images or of accumulation.  Below, a sum written a + b + c is ((a + b) + c).
+ *
+ * the grid        origin float [3] (finite), voxel > 0 (a finite float), nx, ny, nz each in 1..1024 with nx ny nz <= 2^26.  Grid
+ *                 vertex (i, j, k) lies at G_a = (double)origin_a + ((double)i_a (double)voxel); lin = (k ny + j) nx + i.
+ *
+ * sfmba_tsdf_integrate
+ *   inputs        images, K, P and depth [n_images] (each NULL or a float [h][w] map, 0 = no depth) as sfmba_depth_fuse takes them,
+ *                 except that pixels may be NULL (no colour; img_ptr and channels are then not read); trunc > 0 (a finite float),
+ *                 T = (double)trunc.
+ *   per vertex X and per image s with a map: q_i = ((R_i0 X_0 + R_i1 X_1) + R_i2 X_2) + t_i, needing q_2 > 0; the pixel
+ *                 px = floor(((fx q_0) / q_2 + cx) + 0.5), py likewise, both inside the image (tested in double; a NaN fails): the
+ *                 fuse's rule, one copy of the code; zs = (double)map[py][px] > 0; sdf = zs - q_2.  The image CONTRIBUTES iff
+ *                 sdf >= -T, with e = (int)floor((min(sdf, T) / T) 1024.0 + 0.5) in [-1024, 1024]: S += e, W += 1.  If also sdf <= T
+ *                 and pixels is given: Sb, Sg, Sr += the pixel's colour (a gray image gives g, g, g), Wc += 1.
+ *                 BOUNDS: at most 65535 images, so |S| < 2^26 and a colour sum < 2^24; everything is int32.
+ *   outputs       sum int32 [nz][ny][nx], weight int32 [nz][ny][nx]; csum int32 [nz][ny][nx][3] and cweight int32 [nz][ny][nx]:
+ *                 both given or both NULL, and both untouched when pixels is NULL.
+ *
+ * sfmba_tsdf_extract
+ *   inputs        such a grid from the host (csum and cweight both given or both NULL) and min_weight in 1..65535.
+ *   cells         a vertex is DEFINED iff W >= min_weight, its value is f = (double)S / (double)W, it is INSIDE iff S < 0.  Cell
+ *                 (i, j, k) exists for i < nx-1, j < ny-1, k < nz-1 and is ACTIVE iff all eight corners are defined.
+ *   tetrahedra    an active cell is split into the six tetrahedra of Kuhn's triangulation: tetrahedron p in 0..5 is the p-th
+ *                 permutation (a, b, c) of the axes (0, 1, 2) in lexicographic order, with local vertices v0 = corner,
+ *                 v1 = v0 + e_a, v2 = v1 + e_b, v3 = corner + (1, 1, 1).  Every edge runs from a grid vertex A to A + d, d in
+ *                 {0, 1}^3 \ {0}; its KEY is lin(A) * 8 + (d_x + 2 d_y + 4 d_z - 1) < 2^29.  Neighbouring cells split their common
+ *                 face alike.
+ *   triangles     I, O = the inside and the outside local indices, ascending; nothing if either is empty.  |I| = 1: one triangle
+ *                 on the edges (I0, O0), (I0, O1), (I0, O2).  |I| = 3: (I0, O0), (I1, O0), (I2, O0).  |I| = 2: the cycle
+ *                 c0 = (I0, O0), c1 = (I0, O1), c2 = (I1, O1), c3 = (I1, O0) gives (c0, c1, c2) then (c0, c2, c3).  ORIENTATION, in
+ *                 integers on the unit cell: with the doubled edge midpoints m = v_x + v_y of a triangle (A, B, C),
+ *                 n = (B - A) x (C - A) and d = |I| sum_{o in O} v_o - |O| sum_{i in I} v_i; if n . d < 0 the last two vertices are
+ *                 swapped (the product is never 0); then the triangle is rotated so that its lowest key comes first.  Normals face
+ *                 the outside, towards the cameras.  ORDER: cells in ascending lin of their corner, tetrahedra 0..5, then as above.
+ *   vertices      the keys that some triangle uses, in ASCENDING KEY ORDER.  With A the lower end and B = A + d:
+ *                 t = fA / (fA - fB), pos_a = (double)origin_a + (((double)i_a + (t (double)d_a)) (double)voxel), stored as (float);
+ *                 colour per channel (2 (S_A + S_B) + w) / (2 w) in integers with w = Wc_A + Wc_B, (0, 0, 0) when w == 0.
+ *                 Degenerate triangles are kept: S == 0 at a corner gives t == 0, so several keys land on one position.
+ *   outputs       xyz float [vcap][3]; bgr uint8 [vcap][3] (not written, and may be NULL, where csum is NULL); vkey int32 [vcap]
+ *                 (may be NULL); tri int32 [tcap][3], indices into the vertex list; *n_vertices, *n_triangles.
+ *                 SFMBA_ERR_CAPACITY if vcap < *n_vertices or tcap < *n_triangles: both totals are valid, nothing else is written.
+ *
+ * sfmba_tsdf_mesh
+ *   the inputs of integrate and min_weight, the outputs of extract, the grid never leaving the device; colour iff pixels is given.
+ *   EQUALS sfmba_tsdf_integrate FOLLOWED BY sfmba_tsdf_extract BYTE FOR BYTE.
+ *
+ *   SFMBA_ERR_INVALID_ARG (nothing written): whatever the fuse refuses about images, sizes, K and P (more than 65535 images and 2^31
+ *                 or more pixels with a map included); an origin that is not finite; voxel or trunc not finite or <= 0; a dimension
+ *                 outside 1..1024 or more than 2^26 voxels; min_weight outside 1..65535; in a grid handed to extract a negative
+ *                 weight or cweight, |S| > 1024 W, or a colour sum outside 0..255 Wc (found on the device, before anything is
+ *                 written); a negative capacity; a NULL origin, sum, weight, n_vertices, n_triangles, depth with n_images > 0, xyz
+ *                 (or bgr, where colours are made) with vcap > 0, tri with tcap > 0; csum without cweight or the reverse.
+ *   All three: host pointers in and out, synchronous, deterministic.  SFMBA_ABI_VERSION stays 6: adding symbols is backward compatible.
+ */
+SFMBA_API int sfmba_tsdf_integrate(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* pixels /*or NULL*/, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/,
+                const float* K /*[9]*/, const float* P /*[n_images][12]*/, const float* const* depth /*[n_images], each NULL or [h][w]*/,
+                const float* origin /*[3]*/, float voxel, int nx, int ny, int nz, float trunc, int32_t* sum /*[nz][ny][nx]*/,
+                int32_t* weight /*[nz][ny][nx]*/, int32_t* csum /*[nz][ny][nx][3] or NULL*/, int32_t* cweight /*[nz][ny][nx] or NULL*/);
+SFMBA_API int sfmba_tsdf_extract(int device, const float* origin /*[3]*/, float voxel, int nx, int ny, int nz,
+                const int32_t* sum /*[nz][ny][nx]*/, const int32_t* weight /*[nz][ny][nx]*/, const int32_t* csum /*[nz][ny][nx][3] or NULL*/,
+                const int32_t* cweight /*[nz][ny][nx] or NULL*/, int min_weight /*1..65535*/, float* xyz /*[vcap][3]*/,
+                unsigned char* bgr /*[vcap][3]*/, int32_t* vkey /*[vcap] or NULL*/, int64_t vcap, int32_t* tri /*[tcap][3]*/, int64_t tcap,
+                int64_t* n_vertices, int64_t* n_triangles);
+SFMBA_API int sfmba_tsdf_mesh(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* pixels /*or NULL*/, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/,
+                const float* K /*[9]*/, const float* P /*[n_images][12]*/, const float* const* depth /*[n_images], each NULL or [h][w]*/,
+                const float* origin /*[3]*/, float voxel, int nx, int ny, int nz, float trunc, int min_weight /*1..65535*/,
+                float* xyz /*[vcap][3]*/, unsigned char* bgr /*[vcap][3]*/, int32_t* vkey /*[vcap] or NULL*/, int64_t vcap,
+                int32_t* tri /*[tcap][3]*/, int64_t tcap, int64_t* n_vertices, int64_t* n_triangles);
+
 /* ---- matching by optical flow: pyramidal Lucas-Kanade and the snap to key points (SfMFeatureMatching::createFlowMatchMatrix) -----
  * The reference's legacy tree matched video-like input without descriptors (legacy/SfMToyLib_Old/OFFeatureMatcher.cpp): it tracked
  * the key points of image i into image j with gpu::PyrLKOpticalFlow::sparse, snapped every flow end point to a key point of j

@@ -39,7 +39,7 @@ SYMBOLS = [
     "sfmba_jpeg_info", "sfmba_resized_size", "sfmba_jpeg_decode", "sfmba_resize_images",
     "sfmba_png_info", "sfmba_png_decode", "sfmba_match_features_l2", "sfmba_surf_extract",
     "sfmba_depth_sweep", "sfmba_depth_fuse", "sfmba_flow_track", "sfmba_flow_match",
-    "sfmba_depth_normals", "sfmba_cloud_merge",
+    "sfmba_depth_normals", "sfmba_cloud_merge", "sfmba_tsdf_integrate", "sfmba_tsdf_extract", "sfmba_tsdf_mesh",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -612,6 +612,110 @@ def cloud_merge(xyz, bgr=None, normal=None, voxel=1.0, min_count=1, cap=None, wa
     return {"xyz": oxyz[:m].copy(), "bgr": None if bgr is None else obgr[:m].copy(), "normal": None if normal is None else onrm[:m].copy(),
             "count": cnt[:m].copy(), "first": first[:m].copy(), "voxel_of": voxel_of[:n].copy() if want_voxel_of else None,
             "n_skipped": int(skipped.value)}
+
+
+def _tsdf_views(images, K, P, depth_maps):
+    """The image arguments of sfmba_tsdf_integrate / sfmba_tsdf_mesh, in order, and what must stay alive beside them.  images None:
+    no colour (pixels NULL); the sizes then come from the maps, and an image without a map counts as 1 x 1."""
+    maps = [None if m is None else np.ascontiguousarray(m, dtype=np.float32) for m in depth_maps]
+    n = len(maps)
+    fp, lp, bp = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_ubyte)
+    if images is None:
+        channels, img_ptr, flat = 1, None, None
+        wd = np.asarray([1 if m is None else m.shape[1] for m in maps] or [1], dtype=np.int32)
+        ht = np.asarray([1 if m is None else m.shape[0] for m in maps] or [1], dtype=np.int32)
+    else:
+        imgs, channels, img_ptr, flat, wd, ht = _flat_images(images)
+        if len(imgs) != n or any(m is not None and m.shape != im.shape[:2] for m, im in zip(maps, imgs)):
+            raise ValueError("one depth map (or None) per image, of its image's size")
+        if not n:
+            wd, ht = np.ones(1, np.int32), np.ones(1, np.int32)
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1)
+    if len(P) != 12 * n:
+        raise ValueError("P must hold one 3 x 4 matrix per image")
+    if not n:
+        P = np.zeros(12, np.float32)
+    ptrs = (fp * max(n, 1))(*[None if m is None else m.ctypes.data_as(fp) for m in maps])
+    args = [C.c_int(n), None if img_ptr is None else _p(img_ptr, lp), None if flat is None else _p(flat, bp), _p(wd, _ip), _p(ht, _ip),
+            C.c_int(channels), _p(K, fp), _p(P, fp), ptrs]
+    return args, (maps, img_ptr, flat, wd, ht, K, P)
+
+
+def _tsdf_grid(origin, voxel, dims):
+    origin = np.ascontiguousarray(origin, dtype=np.float32).reshape(3)
+    nx, ny, nz = (int(v) for v in dims)
+    return [_p(origin, C.POINTER(C.c_float)), C.c_float(voxel), C.c_int(nx), C.c_int(ny), C.c_int(nz)], origin, (nz, ny, nx)
+
+
+def tsdf_integrate(images, K, P, depth_maps, origin, voxel, dims, trunc, colour=True, device=0):
+    """sfmba_tsdf_integrate: depth maps -> a truncated signed distance grid (the contract is in include/sfmba.h).
+
+    images: as orb_extract, or None (no colour); K [3, 3]; P [n_images, 3, 4]; depth_maps: per image None or float32 [h, w]; origin [3];
+    dims = (nx, ny, nz).  Returns a dict: sum, weight int32 [nz, ny, nx]; csum int32 [nz, ny, nx, 3] and cweight int32 [nz, ny, nx], both
+    None without images or with colour=False (NULL is passed)."""
+    views, keep = _tsdf_views(images, K, P, depth_maps)
+    grid, origin, shape = _tsdf_grid(origin, voxel, dims)
+    S, W = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+    with_colour = images is not None and colour
+    CS, CW = (np.zeros(shape + (3,), np.int32), np.zeros(shape, np.int32)) if with_colour else (None, None)
+    _check(lib().sfmba_tsdf_integrate(C.c_int(device), *views, *grid, C.c_float(trunc), _p(S, _ip), _p(W, _ip),
+                                      _p(CS, _ip) if with_colour else None, _p(CW, _ip) if with_colour else None))
+    return {"sum": S, "weight": W, "csum": CS, "cweight": CW}
+
+
+def _tsdf_mesh_call(call, colour, want_vkey, vcap, tcap):
+    """Runs call(xyz, bgr, vkey, vcap, tri, tcap, n_vertices, n_triangles) with the size-first protocol of depth_fuse."""
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+    nv, nt = C.c_int64(0), C.c_int64(0)
+    vcap, tcap = 0 if vcap is None else int(vcap), 0 if tcap is None else int(tcap)
+    for _ in range(2):
+        xyz, bgr = np.zeros((max(vcap, 1), 3), np.float32), np.zeros((max(vcap, 1), 3), np.uint8)
+        vkey, tri = np.zeros(max(vcap, 1), np.int32), np.zeros((max(tcap, 1), 3), np.int32)
+        rc = call(_p(xyz, fp), _p(bgr, bp) if colour else None, _p(vkey, _ip) if want_vkey else None, C.c_int64(vcap), _p(tri, _ip),
+                  C.c_int64(tcap), C.byref(nv), C.byref(nt))
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        vcap, tcap = int(nv.value), int(nt.value)
+    _check(rc)
+    v, t = int(nv.value), int(nt.value)
+    return {"xyz": xyz[:v].copy(), "bgr": bgr[:v].copy() if colour else None, "vkey": vkey[:v].copy() if want_vkey else None,
+            "tri": tri[:t].copy()}
+
+
+def tsdf_extract(origin, voxel, grid_sum, grid_weight, csum=None, cweight=None, min_weight=1, want_vkey=True, vcap=None, tcap=None, device=0):
+    """sfmba_tsdf_extract: the surface of a truncated signed distance grid by marching tetrahedra (the contract is in include/sfmba.h).
+
+    grid_sum, grid_weight int32 [nz, ny, nx]; csum int32 [nz, ny, nx, 3] and cweight int32 [nz, ny, nx] or both None.  Returns a dict:
+    xyz float32 [n, 3], bgr uint8 [n, 3] or None, vkey int32 [n] or None, tri int32 [m, 3].  vcap / tcap None asks for the sizes first
+    (capacity 0); short capacities are retried once with the sizes the library reports."""
+    S, W = np.ascontiguousarray(grid_sum, dtype=np.int32), np.ascontiguousarray(grid_weight, dtype=np.int32)
+    if S.ndim != 3 or W.shape != S.shape or (csum is None) != (cweight is None):
+        raise ValueError("sum and weight are [nz, ny, nx]; csum and cweight come together")
+    nz, ny, nx = S.shape
+    grid, origin, _ = _tsdf_grid(origin, voxel, (nx, ny, nz))
+    colour = csum is not None
+    if colour:
+        csum, cweight = np.ascontiguousarray(csum, dtype=np.int32), np.ascontiguousarray(cweight, dtype=np.int32)
+        if csum.shape != S.shape + (3,) or cweight.shape != S.shape:
+            raise ValueError("csum is [nz, ny, nx, 3] and cweight [nz, ny, nx]")
+
+    def call(*out):
+        return lib().sfmba_tsdf_extract(C.c_int(device), *grid, _p(S, _ip), _p(W, _ip), _p(csum, _ip) if colour else None,
+                                        _p(cweight, _ip) if colour else None, C.c_int(min_weight), *out)
+    return _tsdf_mesh_call(call, colour, want_vkey, vcap, tcap)
+
+
+def tsdf_mesh(images, K, P, depth_maps, origin, voxel, dims, trunc, min_weight=1, want_vkey=True, vcap=None, tcap=None, device=0):
+    """sfmba_tsdf_mesh: depth maps -> a triangle mesh, the grid never leaving the device; equals tsdf_integrate followed by
+    tsdf_extract byte for byte (the contract is in include/sfmba.h).  Arguments as tsdf_integrate takes them, the result as
+    tsdf_extract gives it; bgr is None when images is None."""
+    views, keep = _tsdf_views(images, K, P, depth_maps)
+    grid, origin, _ = _tsdf_grid(origin, voxel, dims)
+
+    def call(*out):
+        return lib().sfmba_tsdf_mesh(C.c_int(device), *views, *grid, C.c_float(trunc), C.c_int(min_weight), *out)
+    return _tsdf_mesh_call(call, images is not None, want_vkey, vcap, tcap)
 
 
 class _ImageInfo(C.Structure):

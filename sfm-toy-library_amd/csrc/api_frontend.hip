@@ -1,5 +1,5 @@
 // api_frontend.hip -- C ABI of include/sfmba.h, the front-end entry points (everything in front of bundle adjustment: image files,
-// features, matches, RANSAC, triangulation, association, dense depth, flow, cloud merge): argument checks and dispatch.  The work
+// features, matches, RANSAC, triangulation, association, dense depth, flow, cloud merge, mesh): argument checks and dispatch.  The work
 // is in the unit each wrapper names; the error state, the device checks and the problem / solver entry points are in sfmba_api.hip.
 //
 // Every wrapper reads: checks, open, call, timing line, mapped result.  Every check comes before the first write: a refused call
@@ -15,11 +15,13 @@
 #include "jpeg_decode.h"
 #include "jpeg_math.h"
 #include "match_l2.h"
+#include "mesh_math.h"
 #include "orb_extract.h"
 #include "png_decode.h"
 #include "pnp_ransac.h"
 #include "problem.h"
 #include "surf_extract.h"
+#include "tsdf_mesh.h"
 #include <climits>
 #include <cmath>
 
@@ -185,6 +187,53 @@ int check_file_ptr(int n_images, const int64_t* file_ptr, const unsigned char* b
 void image_timing_line(const char* what, const double* tm) {
     std::fprintf(stderr, "[sfmba %s] entropy_ms %.6f upload_ms %.6f idct_ms %.6f colour_ms %.6f resize_ms %.6f download_ms %.6f groups %d\n", what,
                  tm[JPEG_T_ENTROPY], tm[JPEG_T_UPLOAD], tm[JPEG_T_IDCT], tm[JPEG_T_COLOUR], tm[JPEG_T_RESIZE], tm[JPEG_T_DOWNLOAD], (int)tm[JPEG_T_GROUPS]);
+}
+// what the three mesh calls refuse about the grid, the views and the outputs; their failure text and their timing line
+int tsdf_check_grid(const char* who, const float* origin, float voxel, int nx, int ny, int nz) {
+    const std::string w(who);
+    if (!origin) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(origin[a])) return fail(SFMBA_ERR_INVALID_ARG, w + ": origin must be finite");
+    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, w + ": voxel must be finite and > 0");
+    if (nx < 1 || nx > MESH_MAX_DIM || ny < 1 || ny > MESH_MAX_DIM || nz < 1 || nz > MESH_MAX_DIM)
+        return fail(SFMBA_ERR_INVALID_ARG, w + ": a grid dimension lies outside 1..1024");
+    if ((int64_t)nx * ny * nz > (int64_t)MESH_MAX_VOXELS) return fail(SFMBA_ERR_INVALID_ARG, w + ": more than 2^26 voxels");
+    return 0;
+}
+// what the fuse refuses about images, sizes, K and P (the pixels may be missing here), and trunc
+int tsdf_check_views(const char* who, const TsdfViews& v) {
+    const std::string w(who);
+    if (v.n_images > 0 && !v.depth) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (v.pixels) {
+        if (const int rc = depth_check_images(who, v.n_images, v.img_ptr, v.pixels, v.width, v.height, v.channels, v.K, v.P)) return rc;
+    } else if (const int rc = depth_check_cameras(who, v.n_images, v.width, v.height, v.K, v.P)) {
+        return rc;
+    }
+    if (v.n_images > MESH_MAX_WEIGHT) return fail(SFMBA_ERR_INVALID_ARG, w + ": more than 65535 images in one call");
+    if (!std::isfinite(v.trunc) || !(v.trunc > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, w + ": trunc must be finite and > 0");
+    int64_t px = 0;
+    for (int i = 0; i < v.n_images; ++i)
+        if (v.depth[i]) px += (int64_t)v.width[i] * v.height[i];
+    if (px >= (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, w + ": too many pixels with a depth map in one call (2^31)");
+    return 0;
+}
+int tsdf_check_out(const char* who, int min_weight, bool colour, const TsdfMeshOut& o) {
+    if (o.vcap < 0 || o.tcap < 0 || !o.n_vertices || !o.n_triangles || (o.vcap > 0 && (!o.xyz || (colour && !o.bgr))) || (o.tcap > 0 && !o.tri))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (min_weight < 1 || min_weight > MESH_MAX_WEIGHT) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": min_weight must be in 1..65535");
+    return 0;
+}
+int tsdf_result(int rc, const char* who) {
+    if (rc == TSDF_ERR_GRID)
+        return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": the grid breaks 0 <= W, |S| <= 1024 W, 0 <= Wc or 0 <= colour sum <= 255 Wc");
+    return unit_result(rc, who);
+}
+void tsdf_timing_line(const char* what, const double* t, const TsdfGrid& g, long long nv, long long nt) {
+    std::fprintf(stderr,
+                 "[sfmba %s] upload_ms %.6f integrate_ms %.6f check_ms %.6f count_ms %.6f scan_ms %.6f flags_ms %.6f emit_ms %.6f vertices_ms %.6f "
+                 "download_ms %.6f voxels %lld vertices %lld triangles %lld\n",
+                 what, t[TSDF_T_UPLOAD], t[TSDF_T_INTEGRATE], t[TSDF_T_CHECK], t[TSDF_T_COUNT_TRI], t[TSDF_T_SCAN], t[TSDF_T_FLAGS], t[TSDF_T_EMIT],
+                 t[TSDF_T_VERTICES], t[TSDF_T_DOWNLOAD], (long long)g.nx * g.ny * g.nz, nv, nt);
 }
 }  // namespace
 
@@ -534,6 +583,51 @@ int sfmba_cloud_merge(int device, int64_t n, const float* xyz, const unsigned ch
                      c.t[MERGE_T_UPLOAD], c.t[MERGE_T_QUANTISE], c.t[MERGE_T_SORT], c.t[MERGE_T_RUNS], c.t[MERGE_T_REDUCE], c.t[MERGE_T_COMPACT],
                      c.t[MERGE_T_FINALISE], c.t[MERGE_T_DOWNLOAD], (long long)n, (long long)*total);
     return unit_result(rc, "cloud_merge");
+}
+// ---- a surface from the depth maps: TSDF fusion and marching tetrahedra (SfM::meshDenseCloud) -------------------------------------
+int sfmba_tsdf_integrate(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                         int channels, const float* K, const float* P, const float* const* depth, const float* origin, float voxel, int nx, int ny,
+                         int nz, float trunc, int32_t* sum, int32_t* weight, int32_t* csum, int32_t* cweight) {
+    if (!sum || !weight || (csum == nullptr) != (cweight == nullptr)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    const TsdfViews views{ n_images, img_ptr, pixels, width, height, channels, K, P, depth, trunc };
+    const TsdfGrid grid{ origin, voxel, nx, ny, nz };
+    if (const int rc = tsdf_check_views("tsdf_integrate", views)) return rc;
+    if (const int rc = tsdf_check_grid("tsdf_integrate", origin, voxel, nx, ny, nz)) return rc;
+    TimedCall<TSDF_T_COUNT> c("SFMBA_MESH_TIMING");          // (tools/mesh_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = tsdf_integrate(c.kit.stream, device, views, grid, sum, weight, csum, cweight, c.tm());
+    if (rc == 0 && c.on) tsdf_timing_line("tsdf_integrate", c.t, grid, 0, 0);
+    return tsdf_result(rc, "tsdf_integrate");
+}
+int sfmba_tsdf_extract(int device, const float* origin, float voxel, int nx, int ny, int nz, const int32_t* sum, const int32_t* weight,
+                       const int32_t* csum, const int32_t* cweight, int min_weight, float* xyz, unsigned char* bgr, int32_t* vkey, int64_t vcap,
+                       int32_t* tri, int64_t tcap, int64_t* n_vertices, int64_t* n_triangles) {
+    if (!sum || !weight || (csum == nullptr) != (cweight == nullptr)) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    const TsdfGrid grid{ origin, voxel, nx, ny, nz };
+    const TsdfMeshOut out{ xyz, bgr, vkey, vcap, tri, tcap, n_vertices, n_triangles };
+    if (const int rc = tsdf_check_out("tsdf_extract", min_weight, csum != nullptr, out)) return rc;
+    if (const int rc = tsdf_check_grid("tsdf_extract", origin, voxel, nx, ny, nz)) return rc;
+    TimedCall<TSDF_T_COUNT> c("SFMBA_MESH_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = tsdf_extract(c.kit.stream, device, grid, sum, weight, csum, cweight, min_weight, out, c.tm());
+    if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on) tsdf_timing_line("tsdf_extract", c.t, grid, (long long)*n_vertices, (long long)*n_triangles);
+    return tsdf_result(rc, "tsdf_extract");
+}
+int sfmba_tsdf_mesh(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                    int channels, const float* K, const float* P, const float* const* depth, const float* origin, float voxel, int nx, int ny, int nz,
+                    float trunc, int min_weight, float* xyz, unsigned char* bgr, int32_t* vkey, int64_t vcap, int32_t* tri, int64_t tcap,
+                    int64_t* n_vertices, int64_t* n_triangles) {
+    const TsdfViews views{ n_images, img_ptr, pixels, width, height, channels, K, P, depth, trunc };
+    const TsdfGrid grid{ origin, voxel, nx, ny, nz };
+    const TsdfMeshOut out{ xyz, bgr, vkey, vcap, tri, tcap, n_vertices, n_triangles };
+    if (const int rc = tsdf_check_out("tsdf_mesh", min_weight, pixels != nullptr, out)) return rc;
+    if (const int rc = tsdf_check_views("tsdf_mesh", views)) return rc;
+    if (const int rc = tsdf_check_grid("tsdf_mesh", origin, voxel, nx, ny, nz)) return rc;
+    TimedCall<TSDF_T_COUNT> c("SFMBA_MESH_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = tsdf_mesh(c.kit.stream, device, views, grid, min_weight, out, c.tm());
+    if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on) tsdf_timing_line("tsdf_mesh", c.t, grid, (long long)*n_vertices, (long long)*n_triangles);
+    return tsdf_result(rc, "tsdf_mesh");
 }
 // ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------
 int sfmba_pnp_ransac(int device, int n_prob, const int64_t* prob_ptr, const float* xyz, const float* uv, const float* K, int n_hyp,

@@ -210,6 +210,7 @@ void SfM::startRun(size_t n_views) {
     mDepthMaps.clear();
     mDenseCloud = DenseCloud();
     mMergedCloud = MergedCloud();
+    mMesh = Mesh();
     mDenseJobs.clear();
     mRunOkay = false;
     mTiming = std::getenv("SFMBA_SFM_TIMING") != nullptr;
@@ -425,6 +426,7 @@ ErrorCode SfM::densify(const DenseParams& params) {
     mDepthMaps.clear();
     mDenseCloud = DenseCloud();
     mMergedCloud = MergedCloud();
+    mMesh = Mesh();
     mDenseJobs.clear();
     if (mFeaturesGiven || mImages.empty()) {
         std::cerr << "densify: there are no pixels: the run started from setFeatures, and depth maps need the images" << std::endl;
@@ -605,6 +607,104 @@ bool SfM::saveMergedDenseCloudToPLY(const std::string& prefix) {
         file << p.x << " " << p.y << " " << p.z << " " << n.x << " " << n.y << " " << n.z << " " << (int)bgr[2] << " " << (int)bgr[1] << " "
              << (int)bgr[0] << " " << std::endl;
     }
+    file.close();
+    return !file.fail();
+}
+
+ErrorCode SfM::meshDenseCloud(const MeshParams& params) {
+    mMesh = Mesh();
+    if (mDenseJobs.empty() || mDepthMaps.size() != mImages.size()) {
+        std::cerr << "meshDenseCloud: needs a densify on these images that returned OKAY" << std::endl;
+        return ERROR;
+    }
+    if (!std::isfinite(params.voxel) || params.voxel < 0.0f || params.resolution < 2 || !std::isfinite(params.truncVoxels) ||
+        !(params.truncVoxels > 0.0f) || params.minWeight < 1 || params.minWeight > 65535) {
+        std::cerr << "meshDenseCloud: voxel must be finite and >= 0 (0 = from resolution), resolution >= 2, truncVoxels finite and > 0, "
+                     "minWeight in 1..65535" << std::endl;
+        return ERROR;
+    }
+    // the box of the dense cloud without its outermost hundredths (the rule is at the top of SfM.h)
+    float lo[3], hi[3];
+    double side[3], longest = 0.0;
+    for (int a = 0; a < 3; a++) {
+        std::vector<float> c;
+        c.reserve(mDenseCloud.points.size());
+        for (const cv::Point3f& p : mDenseCloud.points) {
+            const float v = a == 0 ? p.x : a == 1 ? p.y : p.z;
+            if (std::isfinite(v)) c.push_back(v);
+        }
+        if (c.empty()) {
+            std::cerr << "meshDenseCloud: the dense cloud has no finite point" << std::endl;
+            return ERROR;
+        }
+        std::sort(c.begin(), c.end());
+        lo[a] = c[c.size() / 100];
+        hi[a] = c[(99 * c.size()) / 100];
+        side[a] = (double)hi[a] - (double)lo[a];
+        longest = std::max(longest, side[a]);
+    }
+    MeshGrid grid;
+    grid.voxel = params.voxel == 0.0f ? (float)(longest / (double)(params.resolution - 1)) : params.voxel;
+    if (!std::isfinite(grid.voxel) || !(grid.voxel > 0.0f)) {
+        std::cerr << "meshDenseCloud: the dense cloud's box is empty: give a voxel" << std::endl;
+        return ERROR;
+    }
+    grid.trunc = params.truncVoxels * grid.voxel;
+    const double pad = (double)grid.trunc + (double)grid.voxel;
+    int dims[3];
+    float origin[3];
+    for (int a = 0; a < 3; a++) {
+        origin[a] = (float)((double)lo[a] - pad);
+        const double cells = std::floor((side[a] + (pad + pad)) / (double)grid.voxel) + 2.0;
+        dims[a] = cells < 1024.0 ? (int)cells : 1024;
+    }
+    grid.origin = cv::Point3f(origin[0], origin[1], origin[2]);
+    grid.nx = dims[0]; grid.ny = dims[1]; grid.nz = dims[2];
+    const bool timing = std::getenv("SFMBA_SFM_TIMING") != nullptr;
+    double ms[1] = { 0.0 };
+    bool ok = true;
+    Mesh mesh;
+    {
+        StageClock clock(timing ? ms : nullptr, 0);
+        mesh = SfMDenseUtilities::meshDepthMaps(mImages, mIntrinsics, mCameraPoses, mDepthMaps, grid, params.minWeight, &ok);
+    }
+    if (!ok) return ERROR;
+    mMesh = mesh;
+    say(LOG_INFO, "mesh: " + std::to_string(mMesh.vertices.size()) + " vertices, " + std::to_string(mMesh.triangles.size() / 3) + " triangles on a " +
+                      std::to_string(grid.nx) + " x " + std::to_string(grid.ny) + " x " + std::to_string(grid.nz) + " grid at voxel " +
+                      std::to_string(grid.voxel));
+    if (timing)
+        std::fprintf(stderr, "[sfmba sfm mesh] voxel %.9g trunc %.9g grid %d %d %d mesh_ms %.3f vertices %lld triangles %lld\n", (double)grid.voxel,
+                     (double)grid.trunc, grid.nx, grid.ny, grid.nz, ms[0], (long long)mMesh.vertices.size(), (long long)(mMesh.triangles.size() / 3));
+    return OKAY;
+}
+
+const Mesh& SfM::getMesh() const { return mMesh; }
+
+bool SfM::saveMeshToPLY(const std::string& prefix) {
+    std::ofstream file(prefix + "_mesh.ply");
+    const bool haveBgr = mMesh.bgr.size() == 3 * mMesh.vertices.size();
+    // the header of the points file (SfMExport.cpp), padding included, then the faces
+    file << "ply                 " << std::endl
+         << "format ascii 1.0    " << std::endl
+         << "element vertex " << mMesh.vertices.size() << std::endl
+         << "property float x    " << std::endl
+         << "property float y    " << std::endl
+         << "property float z    " << std::endl
+         << "property uchar red  " << std::endl
+         << "property uchar green" << std::endl
+         << "property uchar blue " << std::endl
+         << "element face " << mMesh.triangles.size() / 3 << std::endl
+         << "property list uchar int vertex_indices" << std::endl
+         << "end_header          " << std::endl;
+    for (size_t i = 0; i < mMesh.vertices.size(); i++) {
+        const cv::Point3f& p = mMesh.vertices[i];
+        const unsigned char none[3] = { 0, 0, 0 };
+        const unsigned char* bgr = haveBgr ? &mMesh.bgr[3 * i] : none;
+        file << p.x << " " << p.y << " " << p.z << " " << (int)bgr[2] << " " << (int)bgr[1] << " " << (int)bgr[0] << " " << std::endl;
+    }
+    for (size_t t = 0; t + 2 < mMesh.triangles.size(); t += 3)
+        file << "3 " << mMesh.triangles[t] << " " << mMesh.triangles[t + 1] << " " << mMesh.triangles[t + 2] << std::endl;
     file.close();
     return !file.fail();
 }

@@ -61,6 +61,16 @@
 //                 footprint of a pixel at the typical depth: g_j = sqrt((double)zNear_j * (double)zFar_j) over the jobs of the
 //                 densify, sorted ascending, voxel = (float)(g[n / 2] / (double)fx) (integer division).  The dense cloud itself is
 //                 not changed.
+//   mesh          meshDenseCloud(params) after a densify that returned OKAY: ONE sfmba_tsdf_mesh call (include/sfmba.h) over the
+//                 images and the depth maps of the views that have one: the maps are averaged along the viewing rays in a truncated
+//                 signed distance grid, whose zero set leaves as a coloured triangle mesh.  THE GRID: per axis a the finite
+//                 coordinates of the dense cloud, sorted ascending, n of them: lo_a = c[n / 100], hi_a = c[(99 n) / 100] (integer
+//                 division: floor(0.01 n), floor(0.99 n)), side_a = (double)hi_a - (double)lo_a.  voxel == 0 means
+//                 (float)(max side / (double)(resolution - 1)), resolution default 256.  trunc = truncVoxels * voxel (float),
+//                 truncVoxels default 4.  The box is padded by pad = (double)trunc + (double)voxel on every side:
+//                 origin_a = (float)((double)lo_a - pad), n_a = floor((side_a + (pad + pad)) / (double)voxel) + 2, capped at 1024.
+//                 minWeight (the views a grid vertex needs) defaults to 1.  These defaults are first choices like the ones above:
+//                 nobody has tuned them.  The dense cloud and the depth maps are not changed.
 // There is no visual debugging.
 // An object holds all of a run's state (the stage times of SFMBA_SFM_TIMING included): different objects may run in different
 // threads; one object is not re-entrant.
@@ -176,6 +186,20 @@ public:
      */
     bool saveMergedDenseCloudToPLY(const std::string& prefix);
 
+    /**
+     * A triangle mesh of the scene from the depth maps (the contract is at the top of this file).  Valid after a densify that returned
+     * OKAY.  With SFMBA_SFM_TIMING set, one stderr line reports mesh_ms.
+     * @return ERROR (nothing kept) without such a densify, for voxel < 0 or not finite, resolution < 2, truncVoxels not finite or
+     *         <= 0, minWeight outside 1..65535, a dense cloud without a finite point, or when the device call fails or refuses.
+     */
+    ErrorCode meshDenseCloud(const MeshParams& params = MeshParams());
+
+    /**
+     * <prefix>_mesh.ply: the mesh, ASCII, in the style of the other writers: x y z red green blue per vertex, then element face with
+     * property list uchar int vertex_indices.
+     */
+    bool saveMeshToPLY(const std::string& prefix);
+
     void setConsoleDebugLevel(unsigned int consoleDebugLevel) { mConsoleDebugLevel = consoleDebugLevel < (unsigned int)LOG_ERROR ? consoleDebugLevel : (unsigned int)LOG_ERROR; }
 
     const std::vector<cv::Mat>&     getImages() const { return mImages; }
@@ -190,6 +214,7 @@ public:
     const DenseCloud&               getDenseCloud() const { return mDenseCloud; }
     const std::vector<DenseJob>&    getDenseJobs() const { return mDenseJobs; }       // the jobs of the last densify, ascending view
     const MergedCloud&              getMergedDenseCloud() const { return mMergedCloud; }
+    const Mesh&                     getMesh() const;                                  // of the last meshDenseCloud; empty without one
 
 private:
     enum { T_EXTRACT, T_MATCH, T_RANK, T_BASELINE_POSE, T_BASELINE_TRIANGULATE, T_ASSOCIATE, T_PNP, T_PAIR_POSES, T_TRIANGULATE, T_MERGE,
@@ -225,7 +250,8 @@ private:
     DenseCloud                mDenseCloud;
     std::vector<DenseJob>     mDenseJobs;
     MergedCloud               mMergedCloud;
-    bool                      mRunOkay;          // the last runSfM returned OKAY and nothing was set since
+    Mesh                      mMesh;
+    bool                      mRunOkay;         // the last runSfM returned OKAY and nothing was set since
     bool                      mTiming;           // SFMBA_SFM_TIMING was set when the run began
     double                    mStageMs[T_COUNT]; // wall time per stage of the current run (all zero unless mTiming)
 };

@@ -231,4 +231,120 @@ MergedCloud SfMDenseUtilities::mergeCloud(const DenseCloud& cloud, const Points3
     return merged;
 }
 
+namespace {
+
+// the depth map pointers of a scene, one per image (NULL for an empty Mat); false if a map does not fit its image
+bool mapPointers(const char* who, const std::vector<cv::Mat>& images, const std::vector<cv::Mat>& depthMaps, std::vector<const float*>& maps) {
+    maps.assign(images.size(), nullptr);
+    for (size_t i = 0; i < images.size(); ++i) {
+        const cv::Mat& m = depthMaps[i];
+        if (m.empty()) continue;
+        if (m.type() != CV_32F || m.rows != images[i].rows || m.cols != images[i].cols) {
+            std::fprintf(stderr, "%s: a depth map is not CV_32F of its image's size\n", who);
+            return false;
+        }
+        maps[i] = m.ptr<float>(0);
+    }
+    return true;
+}
+
+// runs call(xyz, bgr, vcap, tri, tcap, &nv, &nt), a second time with the sizes the first reports, and rebuilds the mesh
+template <typename Call>
+bool runMeshCall(const char* who, bool colour, const MeshGrid& grid, Call call, Mesh& mesh) {
+    std::vector<float> xyz;
+    std::vector<unsigned char> bgr;
+    std::vector<int32_t> tri;
+    int64_t nv = 0, nt = 0, vcap = 0, tcap = 0;            // the first call reports the sizes
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        xyz.resize((size_t)vcap * 3 + 1); bgr.resize((size_t)vcap * 3 + 1); tri.resize((size_t)tcap * 3 + 1);
+        const int rc = call(xyz.data(), bgr.data(), vcap, tri.data(), tcap, &nv, &nt);
+        if (rc == SFMBA_OK) break;
+        if (rc == SFMBA_ERR_CAPACITY && attempt == 0) { vcap = nv; tcap = nt; continue; }
+        std::fprintf(stderr, "%s failed (sfmba rc=%d: %s)\n", who, rc, sfmba_last_error());
+        return false;
+    }
+    mesh.grid = grid;
+    mesh.vertices.reserve((size_t)nv);
+    for (int64_t i = 0; i < nv; ++i) mesh.vertices.push_back(cv::Point3f(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]));
+    if (colour) mesh.bgr.assign(bgr.begin(), bgr.begin() + 3 * nv);
+    mesh.triangles.assign(tri.begin(), tri.begin() + 3 * nt);
+    return true;
+}
+
+}  // namespace
+
+bool SfMDenseUtilities::integrateTSDF(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
+                                      const std::vector<cv::Mat>& depthMaps, const MeshGrid& grid, bool colour, TsdfVolume& volume) {
+    volume = TsdfVolume();
+    FlatScene f;
+    std::vector<const float*> maps;
+    if (!flattenScene(images, intrinsics, poses, f) || depthMaps.size() != images.size()) {
+        std::fprintf(stderr, "integrateTSDF: one pose and one depth map (or an empty Mat) per image are needed\n");
+        return false;
+    }
+    if (!mapPointers("integrateTSDF", images, depthMaps, maps)) return false;
+    const int64_t cells = (int64_t)grid.nx * grid.ny * grid.nz;
+    const bool sized = grid.nx >= 1 && grid.nx <= 1024 && grid.ny >= 1 && grid.ny <= 1024 && grid.nz >= 1 && grid.nz <= 1024 && cells <= ((int64_t)1 << 26);
+    TsdfVolume v;
+    v.grid = grid;
+    if (sized) {
+        v.sum.resize((size_t)cells); v.weight.resize((size_t)cells);
+        if (colour) { v.csum.resize((size_t)cells * 3); v.cweight.resize((size_t)cells); }
+    }
+    const float origin[3] = { grid.origin.x, grid.origin.y, grid.origin.z };
+    // (an unsized grid is refused by the call before it touches the outputs)
+    const int rc = sfmba_tsdf_integrate(0, (int)images.size(), f.ptr.data(), f.px.data(), f.w.data(), f.h.data(), f.channels, f.K, f.P.data(), maps.data(),
+                                        origin, grid.voxel, grid.nx, grid.ny, grid.nz, grid.trunc, sized ? v.sum.data() : nullptr,
+                                        sized ? v.weight.data() : nullptr, colour && sized ? v.csum.data() : nullptr,
+                                        colour && sized ? v.cweight.data() : nullptr);
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "integrateTSDF failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return false;
+    }
+    volume = v;
+    return true;
+}
+
+Mesh SfMDenseUtilities::extractMesh(const TsdfVolume& volume, int minWeight, bool* ok) {
+    Mesh mesh;
+    if (ok) *ok = false;
+    const MeshGrid& g = volume.grid;
+    const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
+    const bool colour = !volume.csum.empty();
+    if (g.nx < 1 || g.ny < 1 || g.nz < 1 || cells > ((int64_t)1 << 26) || (int64_t)volume.sum.size() != cells || (int64_t)volume.weight.size() != cells ||
+        (colour && ((int64_t)volume.csum.size() != 3 * cells || (int64_t)volume.cweight.size() != cells))) {
+        std::fprintf(stderr, "extractMesh: the volume's arrays do not fit its grid\n");
+        return mesh;
+    }
+    const float origin[3] = { g.origin.x, g.origin.y, g.origin.z };
+    const bool done = runMeshCall("extractMesh", colour, g, [&](float* xyz, unsigned char* bgr, int64_t vcap, int32_t* tri, int64_t tcap, int64_t* nv, int64_t* nt) {
+        return sfmba_tsdf_extract(0, origin, g.voxel, g.nx, g.ny, g.nz, volume.sum.data(), volume.weight.data(), colour ? volume.csum.data() : nullptr,
+                                  colour ? volume.cweight.data() : nullptr, minWeight, xyz, bgr, nullptr, vcap, tri, tcap, nv, nt);
+    }, mesh);
+    if (!done) return Mesh();
+    if (ok) *ok = true;
+    return mesh;
+}
+
+Mesh SfMDenseUtilities::meshDepthMaps(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
+                                      const std::vector<cv::Mat>& depthMaps, const MeshGrid& grid, int minWeight, bool* ok) {
+    Mesh mesh;
+    if (ok) *ok = false;
+    FlatScene f;
+    std::vector<const float*> maps;
+    if (!flattenScene(images, intrinsics, poses, f) || depthMaps.size() != images.size()) {
+        std::fprintf(stderr, "meshDepthMaps: one pose and one depth map (or an empty Mat) per image are needed\n");
+        return mesh;
+    }
+    if (!mapPointers("meshDepthMaps", images, depthMaps, maps)) return mesh;
+    const float origin[3] = { grid.origin.x, grid.origin.y, grid.origin.z };
+    const bool done = runMeshCall("meshDepthMaps", true, grid, [&](float* xyz, unsigned char* bgr, int64_t vcap, int32_t* tri, int64_t tcap, int64_t* nv, int64_t* nt) {
+        return sfmba_tsdf_mesh(0, (int)images.size(), f.ptr.data(), f.px.data(), f.w.data(), f.h.data(), f.channels, f.K, f.P.data(), maps.data(), origin,
+                               grid.voxel, grid.nx, grid.ny, grid.nz, grid.trunc, minWeight, xyz, bgr, nullptr, vcap, tri, tcap, nv, nt);
+    }, mesh);
+    if (!done) return Mesh();
+    if (ok) *ok = true;
+    return mesh;
+}
+
 }  // namespace sfmtoylib

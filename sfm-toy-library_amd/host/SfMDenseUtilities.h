@@ -3,7 +3,8 @@
 // of a set of views into coloured points in ONE device call.  The reference stops at the sparse cloud; this is the stage between
 // "camera poses" and "a model" (SfM::densify drives it).  Both functions are thin: they flatten, call and rebuild.  So are the two
 // that follow them, over sfmba_depth_normals / sfmba_cloud_merge: a normal per depth pixel, and one oriented point per occupied voxel
-// of the fused cloud (SfM::mergeDenseCloud drives them).
+// of the fused cloud (SfM::mergeDenseCloud drives them).  The last three, over sfmba_tsdf_integrate / sfmba_tsdf_extract /
+// sfmba_tsdf_mesh, turn the depth maps into a surface: a truncated signed distance grid and its triangle mesh (SfM::meshDenseCloud).
 #pragma once
 #include <vector>
 
@@ -52,6 +53,40 @@ struct MergedCloud {
     MergedCloud() : voxel(0.0f), skipped(0) {}
 };
 
+// The grid of a truncated signed distance field (include/sfmba.h, "the grid"): vertex (i, j, k) lies at origin + (i, j, k) voxel.
+struct MeshGrid {
+    cv::Point3f origin;
+    float       voxel;       // > 0
+    int         nx, ny, nz;  // each 1..1024, nx ny nz <= 2^26
+    float       trunc;       // the distance is clamped to [-trunc, trunc]; a view behind -trunc does not count
+    MeshGrid() : origin(0.0f, 0.0f, 0.0f), voxel(0.0f), nx(0), ny(0), nz(0), trunc(0.0f) {}
+};
+
+// What sfmba_tsdf_integrate leaves per grid vertex, in (z, y, x) order: integers only.
+struct TsdfVolume {
+    MeshGrid         grid;
+    std::vector<int> sum, weight;        // the summed distance quanta (1024 per trunc) and the number of views that count
+    std::vector<int> csum, cweight;      // 3 colour sums per vertex and their number of views; both empty without colour
+};
+
+// A triangle mesh: the vertices in ascending key order, the triangles in (cell, tetrahedron) order (include/sfmba.h, sfmba_tsdf_extract).
+// Normals face the outside, towards the cameras.
+struct Mesh {
+    Points3f                   vertices;
+    std::vector<unsigned char> bgr;        // 3 per vertex; empty if the grid had no colour
+    std::vector<int>           triangles;  // 3 vertex indices per triangle
+    MeshGrid                   grid;       // the grid it was taken from
+};
+
+// SfM::meshDenseCloud: how the grid is laid over the dense cloud (the rule is at the top of SfM.h).  First choices; nobody has tuned them.
+struct MeshParams {
+    float voxel;            // the grid's edge length, 0 = from resolution
+    int   resolution;       // grid vertices along the longest side of the cloud's box, >= 2
+    float truncVoxels;      // trunc in voxels, > 0
+    int   minWeight;        // views a grid vertex needs to count, 1..65535
+    MeshParams() : voxel(0.0f), resolution(256), truncVoxels(4.0f), minWeight(1) {}
+};
+
 class SfMDenseUtilities {
 public:
     /**
@@ -86,6 +121,28 @@ public:
      * @param ok  if not null, receives false when the device call fails or refuses an argument (the result is then empty).
      */
     static MergedCloud mergeCloud(const DenseCloud& cloud, const Points3f& normals, float voxel, int minCount, bool* ok = nullptr);
+
+    /**
+     * The depth maps averaged along the viewing rays into the grid: ONE sfmba_tsdf_integrate call.  images, poses and depthMaps as
+     * fuseDepthMaps takes them; colour: sum the pixels' colours too.
+     * @return false (volume empty) when the device call fails or refuses an argument; the reason goes to stderr.
+     */
+    static bool integrateTSDF(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
+                              const std::vector<cv::Mat>& depthMaps, const MeshGrid& grid, bool colour, TsdfVolume& volume);
+
+    /**
+     * The zero set of the volume over the cells whose eight corners were seen by at least minWeight views, by marching tetrahedra:
+     * ONE sfmba_tsdf_extract call (two when the first reports the sizes).
+     * @param ok  if not null, receives false when the device call fails or refuses an argument (the mesh is then empty).
+     */
+    static Mesh extractMesh(const TsdfVolume& volume, int minWeight, bool* ok = nullptr);
+
+    /**
+     * integrateTSDF with colour, then extractMesh, the grid never leaving the device: ONE sfmba_tsdf_mesh call (two when the first
+     * reports the sizes).  The result equals the two calls' byte for byte.
+     */
+    static Mesh meshDepthMaps(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
+                              const std::vector<cv::Mat>& depthMaps, const MeshGrid& grid, int minWeight, bool* ok = nullptr);
 };
 
 }  // namespace sfmtoylib

@@ -1,6 +1,7 @@
 // sfmtoy.cpp -- the command-line program of the reference (main.cpp) over sfmtoylib::SfM of this directory: read the images of a
 // directory, run the pipeline on the MI355X (-M flow: with the optical-flow matcher), write <prefix>_points.ply and <prefix>_cameras.ply -- and, with -D, densify and write
-// <prefix>_dense.ply; with --voxel on top of -D, merge that cloud and write <prefix>_dense_merged.ply.  The arguments are parsed here
+// <prefix>_dense.ply; with --voxel on top of -D, merge that cloud and write <prefix>_dense_merged.ply; with --mesh on top of -D, mesh
+// the depth maps and write <prefix>_mesh.ply.  The arguments are parsed here
 // (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
 #include <cstdlib>
 #include <cstring>
@@ -29,6 +30,8 @@ void usage(std::ostream& os, const char* program) {
        << "  -D, --dense                  also densify (plane-sweep depth maps of the registered views, fused) and write PREFIX_dense.ply\n"
        << "      --voxel SIZE             with -D: also merge the dense cloud into one oriented point per voxel of edge SIZE (0 = the\n"
        << "                               footprint of a pixel at the typical depth) and write PREFIX_dense_merged.ply\n"
+       << "      --mesh RES               with -D: also mesh the depth maps (TSDF fusion and marching tetrahedra on a grid of RES vertices\n"
+       << "                               along the longest side of the dense cloud's box, 2..1024) and write PREFIX_mesh.ply\n"
        << "  -v, --visual-debug N         accepted and ignored: there is no visual debugging\n";
 }
 
@@ -53,10 +56,10 @@ bool number(const std::string& text, double& value) {
 
 int main(int argc, char** argv) {
     std::string directory, prefix = "output", text;
-    double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0, voxel = 0.0;
+    double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0, voxel = 0.0, resolution = 256.0;
     FeatureType features = FEATURES_ORB;
     MatcherType matcher = MATCHER_DESCRIPTORS;
-    bool have_directory = false, dense = false, merged = false;
+    bool have_directory = false, dense = false, merged = false, meshed = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
         const std::string arg = argv[i];
@@ -81,6 +84,10 @@ int main(int argc, char** argv) {
             bad = !missing && (!number(text, voxel) || !(voxel >= 0.0) || !(voxel <= 3.0e38));
             merged = true;
         }
+        else if (option(argc, argv, i, "--mesh", "--mesh", text, missing)) {
+            bad = !missing && (!number(text, resolution) || !(resolution >= 2.0) || !(resolution <= 1024.0) || resolution != (double)(int)resolution);
+            meshed = true;
+        }
         else if (option(argc, argv, i, "-v", "--visual-debug", text, missing)) bad = !missing && !number(text, ignored);
         else if (arg.size() > 1 && arg[0] == '-') { std::cerr << argv[0] << ": unknown option " << arg << "\n"; usage(std::cerr, argv[0]); return 2; }
         else if (!have_directory) { directory = arg; have_directory = true; }
@@ -88,6 +95,7 @@ int main(int argc, char** argv) {
         if (missing || bad) { std::cerr << argv[0] << ": " << arg << (missing ? " needs a value\n" : " has a value that cannot be used\n"); usage(std::cerr, argv[0]); return 2; }
     }
     if (merged && !dense) { std::cerr << argv[0] << ": --voxel needs -D\n"; usage(std::cerr, argv[0]); return 2; }
+    if (meshed && !dense) { std::cerr << argv[0] << ": --mesh needs -D\n"; usage(std::cerr, argv[0]); return 2; }
     if (!have_directory || directory.empty()) { std::cerr << argv[0] << ": no input directory\n"; usage(std::cerr, argv[0]); return 2; }
 
     SfM sfm((float)downscale);
@@ -102,7 +110,15 @@ int main(int argc, char** argv) {
     if (!dense) return 0;
     if (sfm.densify() != OKAY) return 1;
     if (!sfm.saveDenseCloudToPLY(prefix)) return 1;
-    if (!merged) return 0;
-    if (sfm.mergeDenseCloud((float)voxel) != OKAY) return 1;
-    return sfm.saveMergedDenseCloudToPLY(prefix) ? 0 : 1;
+    if (merged) {
+        if (sfm.mergeDenseCloud((float)voxel) != OKAY) return 1;
+        if (!sfm.saveMergedDenseCloudToPLY(prefix)) return 1;
+    }
+    if (meshed) {
+        MeshParams params;
+        params.resolution = (int)resolution;
+        if (sfm.meshDenseCloud(params) != OKAY) return 1;
+        if (!sfm.saveMeshToPLY(prefix)) return 1;
+    }
+    return 0;
 }

@@ -798,6 +798,80 @@ int sfmba_shim_run_sfm_merged(int n_views, int channels, const int64_t* img_ptr,
     return 0;
 }
 
+// setImages, runSfM, densify() and meshDenseCloud({voxel, resolution, trunc_voxels, min_weight}) in one call
+// (tests/test_gpu_mesh_pipeline.py).  Back come the poses [n_views][12], K [9], has_map [n_views], the depth maps of ALL views in view
+// order (depth [sum of w h]; zeros where a view has none) and the dense cloud's points (cap_dense rows of dense_xyz), both as they
+// stand AFTER the mesh call with *unchanged = 1 iff the dense cloud and every depth map equal, byte for byte, the copies taken before
+// it; the grid the class chose (grid [8] floats: origin x y z, voxel, trunc, then nx ny nz as floats) and the mesh (cap_vertices rows of
+// mesh_xyz / mesh_bgr, cap_triangles rows of mesh_tri).  ply_prefix != NULL: saveMeshToPLY.  what == 1: no run at all, only
+// meshDenseCloud on a fresh object with images (it has to refuse; no device involved).  Returns runSfM's code, 10 + densify's code, 20 + meshDenseCloud's code (120 + it if a refusing call left a mesh behind),
+// -2 if a capacity is too small, -3 if the PLY file could not be written.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_mesh(int what, int n_views, int channels, const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h,
+                            int debug_level, float voxel, int resolution, float trunc_voxels, int min_weight, const char* ply_prefix, float* poses,
+                            float* K, unsigned char* has_map, float* depth, int64_t cap_dense, int64_t* n_dense, float* dense_xyz, int* unchanged,
+                            float* grid, int64_t cap_vertices, int64_t cap_triangles, int64_t* n_vertices, int64_t* n_triangles, float* mesh_xyz,
+                            unsigned char* mesh_bgr, int32_t* mesh_tri) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    sfm.setImages(images);
+    *n_dense = 0; *unchanged = 0; *n_vertices = 0; *n_triangles = 0;
+    MeshParams params;
+    params.voxel = voxel; params.resolution = resolution; params.truncVoxels = trunc_voxels; params.minWeight = min_weight;
+    ErrorCode code;
+    if (what == 1) {
+        code = sfm.meshDenseCloud(params);
+        return (code == OKAY || !sfm.getMesh().vertices.empty() ? 120 : 20) + (int)code;
+    }
+    if ((code = sfm.runSfM()) != OKAY) return (int)code;
+    for (int v = 0; v < n_views; ++v)
+        for (int e = 0; e < 12; ++e) poses[12 * v + e] = sfm.getCameraPoses()[v].val[e];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) K[3 * r + c] = sfm.getIntrinsics().K.at<float>(r, c);
+    if ((code = sfm.densify()) != OKAY) return 10 + (int)code;
+    const DenseCloud before = sfm.getDenseCloud();
+    std::vector<std::vector<float> > mapsBefore;             // a view without a map: empty
+    for (const cv::Mat& m : sfm.getDepthMaps())
+        mapsBefore.push_back(m.empty() ? std::vector<float>() : std::vector<float>(m.ptr<float>(0), m.ptr<float>(0) + (size_t)m.rows * m.cols));
+    code = sfm.meshDenseCloud(params);
+    if (code != OKAY) return (!sfm.getMesh().vertices.empty() || !sfm.getMesh().triangles.empty() ? 120 : 20) + (int)code;
+    const DenseCloud& cloud = sfm.getDenseCloud();
+    bool same = cloud.points.size() == before.points.size() && cloud.bgr == before.bgr && cloud.views == before.views && cloud.pixels == before.pixels &&
+                sfm.getDepthMaps().size() == mapsBefore.size();
+    size_t at = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const size_t n = (size_t)w[v] * h[v];
+        const cv::Mat& m = sfm.getDepthMaps()[(size_t)v];
+        has_map[v] = m.empty() ? 0 : 1;
+        if (m.empty()) std::memset(depth + at, 0, n * sizeof(float));
+        else std::memcpy(depth + at, m.ptr<float>(0), n * sizeof(float));
+        same = same && (m.empty() ? mapsBefore[(size_t)v].empty()
+                                  : mapsBefore[(size_t)v].size() == n && std::memcmp(m.ptr<float>(0), mapsBefore[(size_t)v].data(), n * sizeof(float)) == 0);
+        at += n;
+    }
+    const Mesh& mesh = sfm.getMesh();
+    *n_dense = (int64_t)cloud.points.size();
+    *n_vertices = (int64_t)mesh.vertices.size();
+    *n_triangles = (int64_t)(mesh.triangles.size() / 3);
+    if (*n_dense > cap_dense || *n_vertices > cap_vertices || *n_triangles > cap_triangles) return -2;
+    for (size_t i = 0; i < cloud.points.size(); ++i) {
+        dense_xyz[3 * i] = cloud.points[i].x; dense_xyz[3 * i + 1] = cloud.points[i].y; dense_xyz[3 * i + 2] = cloud.points[i].z;
+        same = same && std::memcmp(&cloud.points[i], &before.points[i], sizeof(cv::Point3f)) == 0;
+    }
+    *unchanged = same ? 1 : 0;
+    grid[0] = mesh.grid.origin.x; grid[1] = mesh.grid.origin.y; grid[2] = mesh.grid.origin.z; grid[3] = mesh.grid.voxel; grid[4] = mesh.grid.trunc;
+    grid[5] = (float)mesh.grid.nx; grid[6] = (float)mesh.grid.ny; grid[7] = (float)mesh.grid.nz;
+    for (size_t i = 0; i < mesh.vertices.size(); ++i) {
+        mesh_xyz[3 * i] = mesh.vertices[i].x; mesh_xyz[3 * i + 1] = mesh.vertices[i].y; mesh_xyz[3 * i + 2] = mesh.vertices[i].z;
+        for (int k = 0; k < 3; ++k) mesh_bgr[3 * i + k] = mesh.bgr[3 * i + k];
+    }
+    for (size_t i = 0; i < mesh.triangles.size(); ++i) mesh_tri[i] = mesh.triangles[i];
+    if (ply_prefix && !sfm.saveMeshToPLY(ply_prefix)) return -3;
+    return 0;
+}
+
 // SfM::densify() where it has to refuse (tests/test_depth_oracle_cpu.py; no device involved): what = 0 after setFeatures (there are
 // no pixels), 1 on images without a run, 2 on a fresh object.  Returns densify's code.
 extern "C" __attribute__((visibility("default")))
