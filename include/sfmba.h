@@ -1137,6 +1137,89 @@ SFMBA_API int sfmba_tsdf_mesh(int device, int n_images, const int64_t* img_ptr /
                 float* xyz /*[vcap][3]*/, unsigned char* bgr /*[vcap][3]*/, int32_t* vkey /*[vcap] or NULL*/, int64_t vcap,
                 int32_t* tri /*[tcap][3]*/, int64_t tcap, int64_t* n_vertices, int64_t* n_triangles);
 
+/* ---- cleaning a mesh: components, small-island removal, Taubin smoothing, vertex normals (SfM::cleanMesh) ------------------------
+ * The mesh of the calls above is a set of open sheets with islands: a depth outlier that survives the fuse is a floating shell of a
+ * few dozen triangles, and the surface carries the plane-step noise of the sweep.  These four calls label the connected components,
+ * drop the small ones, smooth without shrinking (Taubin's lambda | mu) and give every vertex a normal.  THE CONTRACT IS OUR OWN AND
+ * EQUALS NOBODY'S, stated so that the device is held BIT FOR BIT to a CPU restatement (tests/mesh_clean_oracle.py): positions are
+ * quantised to integers once, a pass is integer arithmetic with one floor division per axis, the few fp64 operations are EVERY ONE
+ * ROUNDED ON ITS OWN (csrc/mesh_clean_math.h switches the compiler's contraction off), and NOTHING BUT INTEGERS IS SUMMED ACROSS
+ * TRIANGLES, so the result depends neither on the order in which atomics arrive nor on how the work is cut.  Below, a sum written
+ * a + b + c is ((a + b) + c).
+ *
+ * the mesh        n_vertices >= 0 and n_triangles >= 0, both < 2^31; xyz float [n_vertices][3]; bgr uint8 [n_vertices][3] or NULL;
+ *                 tri int32 [n_triangles][3], indices into 0 .. n_vertices-1.
+ *
+ * sfmba_mesh_components
+ *   rule          two vertices are connected when some triangle names both; a triangle with a repeated index still connects the
+ *                 indices it names.  A triangle BELONGS to the component of its first index.
+ *   outputs       label int32 [n_vertices]: the lowest vertex index of the vertex's component (a vertex that no triangle names is
+ *                 its own label); comp_triangles int32 [n_vertices] (may be NULL): the number of triangles of the vertex's
+ *                 component, 0 for an unused vertex; *n_components: the labels that own at least one triangle; *largest: the label
+ *                 with the most triangles, ties to the LOWER label, -1 if there is no triangle.
+ *
+ * sfmba_mesh_filter
+ *   inputs        the mesh, min_triangles >= 1, keep_largest in {0, 1}.
+ *   rule          a component is KEPT iff its triangle count >= min_triangles and, with keep_largest, it also is `largest` (so
+ *                 nothing is kept when min_triangles exceeds the largest count).  A triangle is kept iff its component is; a vertex
+ *                 is kept iff a kept triangle names it.  Kept vertices and kept triangles KEEP THEIR RELATIVE ORDER; triangle indices
+ *                 are rewritten to the new numbering.  min_triangles = 1, keep_largest = 0 removes exactly the unused vertices.
+ *   outputs       xyz_out float [vcap][3]; bgr_out uint8 [vcap][3] (not written, and may be NULL, where bgr is NULL); tri_out int32
+ *                 [tcap][3]; vertex_of int32 [n_vertices] (may be NULL): the new index of a vertex or -1; *n_vertices_out,
+ *                 *n_triangles_out.  SFMBA_ERR_CAPACITY if vcap < *n_vertices_out or tcap < *n_triangles_out: both totals are valid,
+ *                 nothing else is written.
+ *
+ * sfmba_mesh_smooth
+ *   inputs        xyz, tri; origin float [3] (finite) and quantum > 0 (a finite float); iterations in 0..100; lambda, mu (floats).
+ *   quantisation  L = (int)floor((double)lambda 65536 + 0.5) in 1..65536 and M likewise from mu in -131072..-1.
+ *                 P_a = (int64)floor(((double)x_a - (double)origin_a) / (double)quantum + 0.5); every coordinate must be finite with
+ *                 |P_a| < 2^25.
+ *   a pass with factor F   for every triangle (a, b, c) whose three indices are DISTINCT: S_a += P_b + P_c, D_a += 2, and the same
+ *                 for b and c (integers only; an interior edge of a manifold mesh counts twice and a boundary edge once: on a closed
+ *                 manifold this is the uniform umbrella).  A vertex with D = 0 or D > 2^17 does not move.  Otherwise per axis
+ *                 n = F (S - D P), den = D 65536, P' = P + floor_div(2 n + den, 2 den): round half up, floor semantics for
+ *                 negatives; with |P| < 2^25 and D <= 2^17, |2 n + den| < 2^62.  If |P'_a| >= 2^25 on some axis the vertex does not
+ *                 move in this pass either (only a mu near -2 on a spike at the rim of the range gets there; every pass then starts
+ *                 from |P| < 2^25 and the bounds above hold throughout).  Every vertex reads the positions from before the pass.
+ *   an iteration  a pass with L, then a pass with M.
+ *   positions     xyz_out_a = (float)((double)origin_a + ((double)P_a (double)quantum)); with iterations == 0, xyz_out is xyz BIT FOR
+ *                 BIT (the range check still applies).
+ *   normals       normal float [n_vertices][3], may be NULL; from the final integer positions (with iterations == 0 the quantised
+ *                 input).  Per triangle with distinct indices N = (P_b - P_a) x (P_c - P_a) in int64 (differences < 2^26, products
+ *                 < 2^52, components < 2^53, so (double)N is exact); len = sqrt((Nx Nx + Ny Ny) + Nz Nz); a triangle with len == 0
+ *                 adds nothing; otherwise u_a = (int64)floor((N_a / len) 1048576.0 + 0.5) is added to each of its three vertices.
+ *                 The vertex normal is (float)(U_a / sqrt((Ux Ux + Uy Uy) + Uz Uz)) with U as doubles, (0, 0, 0) for a zero sum.
+ *                 EVERY TRIANGLE HAS EQUAL WEIGHT: THE NORMALS ARE NOT AREA WEIGHTED.
+ *
+ * sfmba_mesh_clean
+ *   the inputs of filter and of smooth, the outputs of filter and normal float [vcap][3] (may be NULL), the mesh never leaving the
+ *   device, colours carried through.  EQUALS sfmba_mesh_filter FOLLOWED BY sfmba_mesh_smooth BYTE FOR BYTE; the range check sees the
+ *   kept vertices only, and comes after the capacity protocol.
+ *
+ *   SFMBA_ERR_INVALID_ARG (nothing written): a negative or >= 2^31 count; a triangle index outside the vertex list (found on the
+ *                 device, before anything is written); min_triangles < 1; keep_largest outside {0, 1}; iterations outside 0..100;
+ *                 L or M outside its range (a NaN included); an origin that is not finite; quantum not finite or <= 0; a coordinate
+ *                 that is not finite or has |P_a| >= 2^25 (found on the device, before anything is written); a negative capacity;
+ *                 a NULL tri with n_triangles > 0, xyz, label or the smooth's xyz_out with n_vertices > 0, origin, n_components,
+ *                 largest, n_vertices_out, n_triangles_out, xyz_out (or bgr_out, where bgr is given) with vcap > 0, tri_out with
+ *                 tcap > 0.
+ *   All four: host pointers in and out, synchronous, deterministic.  SFMBA_ABI_VERSION stays 6: adding symbols is backward compatible.
+ */
+SFMBA_API int sfmba_mesh_components(int device, int64_t n_vertices, int64_t n_triangles, const int32_t* tri /*[n_triangles][3]*/,
+                int32_t* label /*[n_vertices]*/, int32_t* comp_triangles /*[n_vertices] or NULL*/, int64_t* n_components, int64_t* largest);
+SFMBA_API int sfmba_mesh_filter(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, const unsigned char* bgr /*or NULL*/,
+                int64_t n_triangles, const int32_t* tri /*[n_triangles][3]*/, int min_triangles /*>= 1*/, int keep_largest /*0, 1*/,
+                float* xyz_out /*[vcap][3]*/, unsigned char* bgr_out /*[vcap][3]*/, int64_t vcap, int32_t* tri_out /*[tcap][3]*/, int64_t tcap,
+                int32_t* vertex_of /*[n_vertices] or NULL*/, int64_t* n_vertices_out, int64_t* n_triangles_out);
+SFMBA_API int sfmba_mesh_smooth(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, int64_t n_triangles,
+                const int32_t* tri /*[n_triangles][3]*/, const float* origin /*[3]*/, float quantum, int iterations /*0..100*/, float lambda,
+                float mu, float* xyz_out /*[n_vertices][3]*/, float* normal /*[n_vertices][3] or NULL*/);
+SFMBA_API int sfmba_mesh_clean(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, const unsigned char* bgr /*or NULL*/,
+                int64_t n_triangles, const int32_t* tri /*[n_triangles][3]*/, int min_triangles /*>= 1*/, int keep_largest /*0, 1*/,
+                const float* origin /*[3]*/, float quantum, int iterations /*0..100*/, float lambda, float mu, float* xyz_out /*[vcap][3]*/,
+                unsigned char* bgr_out /*[vcap][3]*/, float* normal /*[vcap][3] or NULL*/, int64_t vcap, int32_t* tri_out /*[tcap][3]*/,
+                int64_t tcap, int32_t* vertex_of /*[n_vertices] or NULL*/, int64_t* n_vertices_out, int64_t* n_triangles_out);
+
 /* ---- matching by optical flow: pyramidal Lucas-Kanade and the snap to key points (SfMFeatureMatching::createFlowMatchMatrix) -----
  * The reference's legacy tree matched video-like input without descriptors (legacy/SfMToyLib_Old/OFFeatureMatcher.cpp): it tracked
  * the key points of image i into image j with gpu::PyrLKOpticalFlow::sparse, snapped every flow end point to a key point of j

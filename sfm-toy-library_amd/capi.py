@@ -40,6 +40,7 @@ SYMBOLS = [
     "sfmba_png_info", "sfmba_png_decode", "sfmba_match_features_l2", "sfmba_surf_extract",
     "sfmba_depth_sweep", "sfmba_depth_fuse", "sfmba_flow_track", "sfmba_flow_match",
     "sfmba_depth_normals", "sfmba_cloud_merge", "sfmba_tsdf_integrate", "sfmba_tsdf_extract", "sfmba_tsdf_mesh",
+    "sfmba_mesh_components", "sfmba_mesh_filter", "sfmba_mesh_smooth", "sfmba_mesh_clean",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -716,6 +717,103 @@ def tsdf_mesh(images, K, P, depth_maps, origin, voxel, dims, trunc, min_weight=1
     def call(*out):
         return lib().sfmba_tsdf_mesh(C.c_int(device), *views, *grid, C.c_float(trunc), C.c_int(min_weight), *out)
     return _tsdf_mesh_call(call, images is not None, want_vkey, vcap, tcap)
+
+
+def _clean_mesh(xyz, bgr, tri):
+    """The mesh arguments of the mesh-cleaning calls: xyz float32 [n, 3] (or a vertex count), bgr uint8 [n, 3] or None, tri int32 [m, 3]."""
+    tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+    if isinstance(xyz, (int, np.integer)):
+        return int(xyz), None, None, tri
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    if bgr is not None:
+        bgr = np.ascontiguousarray(bgr, dtype=np.uint8).reshape(-1, 3)
+        if len(bgr) != len(xyz):
+            raise ValueError("one colour per vertex")
+    return len(xyz), xyz, bgr, tri
+
+
+def _opt(a, t):
+    return None if a is None or a.size == 0 else _p(a, t)
+
+
+def mesh_components(n_vertices, tri, want_comp_triangles=True, device=0):
+    """sfmba_mesh_components: the connected components of a triangle list (the contract is in include/sfmba.h).
+
+    Returns a dict: label int32 [n_vertices], comp_triangles int32 [n_vertices] or None (NULL is passed), n_components, largest."""
+    nv, _, _, tri = _clean_mesh(int(n_vertices), None, tri)
+    label, comp = np.zeros(max(nv, 1), np.int32), np.zeros(max(nv, 1), np.int32)
+    nc, largest = C.c_int64(0), C.c_int64(0)
+    _check(lib().sfmba_mesh_components(C.c_int(device), C.c_int64(nv), C.c_int64(len(tri)), _opt(tri, _ip), _p(label, _ip),
+                                       _p(comp, _ip) if want_comp_triangles else None, C.byref(nc), C.byref(largest)))
+    return {"label": label[:nv].copy(), "comp_triangles": comp[:nv].copy() if want_comp_triangles else None, "n_components": int(nc.value),
+            "largest": int(largest.value)}
+
+
+def _mesh_clean_call(call, nv, colour, want_normal, want_vertex_of, vcap, tcap):
+    """Runs call(xyz_out, bgr_out, normal, vcap, tri_out, tcap, vertex_of, n_vertices_out, n_triangles_out) with the size-first
+    protocol of tsdf_extract."""
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+    n_v, n_t = C.c_int64(0), C.c_int64(0)
+    vcap, tcap = 0 if vcap is None else int(vcap), 0 if tcap is None else int(tcap)
+    vertex_of = np.zeros(max(nv, 1), np.int32)
+    for _ in range(2):
+        xyz, bgr, nrm = np.zeros((max(vcap, 1), 3), np.float32), np.zeros((max(vcap, 1), 3), np.uint8), np.zeros((max(vcap, 1), 3), np.float32)
+        tri = np.zeros((max(tcap, 1), 3), np.int32)
+        rc = call(_p(xyz, fp), _p(bgr, bp) if colour else None, _p(nrm, fp) if want_normal else None, C.c_int64(vcap), _p(tri, _ip),
+                  C.c_int64(tcap), _p(vertex_of, _ip) if want_vertex_of else None, C.byref(n_v), C.byref(n_t))
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        vcap, tcap = int(n_v.value), int(n_t.value)
+    _check(rc)
+    v, t = int(n_v.value), int(n_t.value)
+    return {"xyz": xyz[:v].copy(), "bgr": bgr[:v].copy() if colour else None, "normal": nrm[:v].copy() if want_normal else None,
+            "tri": tri[:t].copy(), "vertex_of": vertex_of[:nv].copy() if want_vertex_of else None}
+
+
+def mesh_filter(xyz, bgr, tri, min_triangles=1, keep_largest=False, want_vertex_of=True, vcap=None, tcap=None, device=0):
+    """sfmba_mesh_filter: drop the components with fewer than min_triangles triangles (or all but the largest) and compact (the
+    contract is in include/sfmba.h).
+
+    Returns a dict: xyz float32 [n, 3], bgr uint8 [n, 3] or None, tri int32 [m, 3], vertex_of int32 [n_vertices] or None.  vcap / tcap
+    None asks for the sizes first (capacity 0); short capacities are retried once with the sizes the library reports."""
+    nv, xyz, bgr, tri = _clean_mesh(xyz, bgr, tri)
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+
+    def call(oxyz, obgr, onrm, vcap, otri, tcap, vof, n_v, n_t):
+        return lib().sfmba_mesh_filter(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), _opt(bgr, bp), C.c_int64(len(tri)), _opt(tri, _ip),
+                                       C.c_int(min_triangles), C.c_int(int(keep_largest)), oxyz, obgr, vcap, otri, tcap, vof, n_v, n_t)
+    out = _mesh_clean_call(call, nv, bgr is not None, False, want_vertex_of, vcap, tcap)
+    del out["normal"]
+    return out
+
+
+def mesh_smooth(xyz, tri, origin, quantum, iterations=10, lam=0.5, mu=-0.53, want_normal=True, device=0):
+    """sfmba_mesh_smooth: Taubin's lambda | mu smoothing in integers and a normal per vertex (the contract is in include/sfmba.h).
+
+    Returns a dict: xyz float32 [n, 3], normal float32 [n, 3] or None (NULL is passed)."""
+    nv, xyz, _, tri = _clean_mesh(xyz, None, tri)
+    fp = C.POINTER(C.c_float)
+    origin = np.ascontiguousarray(origin, dtype=np.float32).reshape(3)
+    out, nrm = np.zeros((max(nv, 1), 3), np.float32), np.zeros((max(nv, 1), 3), np.float32)
+    _check(lib().sfmba_mesh_smooth(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), C.c_int64(len(tri)), _opt(tri, _ip), _p(origin, fp),
+                                   C.c_float(quantum), C.c_int(iterations), C.c_float(lam), C.c_float(mu), _p(out, fp),
+                                   _p(nrm, fp) if want_normal else None))
+    return {"xyz": out[:nv].copy(), "normal": nrm[:nv].copy() if want_normal else None}
+
+
+def mesh_clean(xyz, bgr, tri, origin, quantum, min_triangles=1, keep_largest=False, iterations=10, lam=0.5, mu=-0.53, want_normal=True,
+               want_vertex_of=True, vcap=None, tcap=None, device=0):
+    """sfmba_mesh_clean: mesh_filter followed by mesh_smooth with the mesh staying on the device; equals the two calls byte for byte
+    (the contract is in include/sfmba.h).  Returns a dict: xyz, bgr (or None), normal (or None), tri, vertex_of (or None)."""
+    nv, xyz, bgr, tri = _clean_mesh(xyz, bgr, tri)
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+    origin = np.ascontiguousarray(origin, dtype=np.float32).reshape(3)
+
+    def call(oxyz, obgr, onrm, vcap, otri, tcap, vof, n_v, n_t):
+        return lib().sfmba_mesh_clean(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), _opt(bgr, bp), C.c_int64(len(tri)), _opt(tri, _ip),
+                                      C.c_int(min_triangles), C.c_int(int(keep_largest)), _p(origin, fp), C.c_float(quantum), C.c_int(iterations),
+                                      C.c_float(lam), C.c_float(mu), oxyz, obgr, onrm, vcap, otri, tcap, vof, n_v, n_t)
+    return _mesh_clean_call(call, nv, bgr is not None, want_normal, want_vertex_of, vcap, tcap)
 
 
 class _ImageInfo(C.Structure):

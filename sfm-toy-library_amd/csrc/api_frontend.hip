@@ -1,5 +1,5 @@
 // api_frontend.hip -- C ABI of include/sfmba.h, the front-end entry points (everything in front of bundle adjustment: image files,
-// features, matches, RANSAC, triangulation, association, dense depth, flow, cloud merge, mesh): argument checks and dispatch.  The work
+// features, matches, RANSAC, triangulation, association, dense depth, flow, cloud merge, mesh, mesh cleaning): argument checks and dispatch.  The work
 // is in the unit each wrapper names; the error state, the device checks and the problem / solver entry points are in sfmba_api.hip.
 //
 // Every wrapper reads: checks, open, call, timing line, mapped result.  Every check comes before the first write: a refused call
@@ -15,6 +15,8 @@
 #include "jpeg_decode.h"
 #include "jpeg_math.h"
 #include "match_l2.h"
+#include "mesh_clean.h"
+#include "mesh_clean_math.h"
 #include "mesh_math.h"
 #include "orb_extract.h"
 #include "png_decode.h"
@@ -234,6 +236,52 @@ void tsdf_timing_line(const char* what, const double* t, const TsdfGrid& g, long
                  "download_ms %.6f voxels %lld vertices %lld triangles %lld\n",
                  what, t[TSDF_T_UPLOAD], t[TSDF_T_INTEGRATE], t[TSDF_T_CHECK], t[TSDF_T_COUNT_TRI], t[TSDF_T_SCAN], t[TSDF_T_FLAGS], t[TSDF_T_EMIT],
                  t[TSDF_T_VERTICES], t[TSDF_T_DOWNLOAD], (long long)g.nx * g.ny * g.nz, nv, nt);
+}
+// what the four mesh-cleaning calls refuse about the mesh, the filter's rule, the smoothing's parameters and the capacities; their
+// failure text and their timing line
+int clean_check_mesh(const char* who, int64_t n_vertices, const float* xyz, bool want_xyz, int64_t n_triangles, const int32_t* tri) {
+    const std::string w(who);
+    if (n_vertices < 0 || n_vertices > (int64_t)INT_MAX || n_triangles < 0 || n_triangles > (int64_t)INT_MAX)
+        return fail(SFMBA_ERR_INVALID_ARG, w + ": n_vertices and n_triangles must lie in 0 .. 2^31 - 1");
+    if ((n_triangles > 0 && !tri) || (want_xyz && n_vertices > 0 && !xyz)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    return 0;
+}
+int clean_check_filter(const char* who, int min_triangles, int keep_largest) {
+    if (min_triangles < 1) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": min_triangles must be >= 1");
+    if (keep_largest != 0 && keep_largest != 1) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": keep_largest must be 0 or 1");
+    return 0;
+}
+int clean_check_smooth(const char* who, const float* origin, float quantum, int iterations, float lambda, float mu, CleanSmoothParams& p) {
+    const std::string w(who);
+    if (!origin) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(origin[a])) return fail(SFMBA_ERR_INVALID_ARG, w + ": origin must be finite");
+        p.origin[a] = (double)origin[a];
+    }
+    if (!std::isfinite(quantum) || !(quantum > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, w + ": quantum must be finite and > 0");
+    p.quantum = (double)quantum;
+    if (iterations < 0 || iterations > CLEAN_MAX_ITERATIONS) return fail(SFMBA_ERR_INVALID_ARG, w + ": iterations must be in 0..100");
+    p.iterations = iterations;
+    if (!clean_factor(lambda, 1, 65536, p.L)) return fail(SFMBA_ERR_INVALID_ARG, w + ": lambda must quantise to 1..65536 / 65536");
+    if (!clean_factor(mu, -131072, -1, p.M)) return fail(SFMBA_ERR_INVALID_ARG, w + ": mu must quantise to -131072..-1 / 65536");
+    return 0;
+}
+int clean_check_out(const CleanFilterOut& o, bool colour) {
+    if (o.vcap < 0 || o.tcap < 0 || !o.n_vertices || !o.n_triangles || (o.vcap > 0 && (!o.xyz || (colour && !o.bgr))) || (o.tcap > 0 && !o.tri))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    return 0;
+}
+int clean_result(int rc, const char* who) {
+    if (rc == CLEAN_ERR_INDEX) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": a triangle index lies outside the vertex list");
+    if (rc == CLEAN_ERR_COORD) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": a coordinate is not finite or lies 2^25 quanta or more from the origin");
+    return unit_result(rc, who);
+}
+void clean_timing_line(const char* what, const double* t, long long nv, long long nt, long long nv_out, long long nt_out) {
+    std::fprintf(stderr,
+                 "[sfmba %s] upload_ms %.6f check_ms %.6f components_ms %.6f filter_ms %.6f quantise_ms %.6f smooth_ms %.6f normals_ms %.6f "
+                 "download_ms %.6f vertices %lld triangles %lld vertices_out %lld triangles_out %lld\n",
+                 what, t[CLEAN_T_UPLOAD], t[CLEAN_T_CHECK], t[CLEAN_T_COMPONENTS], t[CLEAN_T_FILTER], t[CLEAN_T_QUANTISE], t[CLEAN_T_SMOOTH],
+                 t[CLEAN_T_NORMALS], t[CLEAN_T_DOWNLOAD], nv, nt, nv_out, nt_out);
 }
 }  // namespace
 
@@ -628,6 +676,66 @@ int sfmba_tsdf_mesh(int device, int n_images, const int64_t* img_ptr, const unsi
     const int rc = tsdf_mesh(c.kit.stream, device, views, grid, min_weight, out, c.tm());
     if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on) tsdf_timing_line("tsdf_mesh", c.t, grid, (long long)*n_vertices, (long long)*n_triangles);
     return tsdf_result(rc, "tsdf_mesh");
+}
+// ---- cleaning a mesh: components, small-island removal, Taubin smoothing, vertex normals (SfM::cleanMesh) -------------------------
+int sfmba_mesh_components(int device, int64_t n_vertices, int64_t n_triangles, const int32_t* tri, int32_t* label, int32_t* comp_triangles,
+                          int64_t* n_components, int64_t* largest) {
+    if (const int rc = clean_check_mesh("mesh_components", n_vertices, nullptr, false, n_triangles, tri)) return rc;
+    if (!n_components || !largest || (n_vertices > 0 && !label)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    const CleanMesh m{ (int)n_vertices, (int)n_triangles, nullptr, nullptr, tri };
+    TimedCall<CLEAN_T_COUNT> c("SFMBA_MESH_CLEAN_TIMING");       // (tools/mesh_clean_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_components(c.kit.stream, device, m, label, comp_triangles, n_components, largest, c.tm());
+    if (rc == 0 && c.on) clean_timing_line("mesh_components", c.t, n_vertices, n_triangles, n_vertices, n_triangles);
+    return clean_result(rc, "mesh_components");
+}
+int sfmba_mesh_filter(int device, int64_t n_vertices, const float* xyz, const unsigned char* bgr, int64_t n_triangles, const int32_t* tri,
+                      int min_triangles, int keep_largest, float* xyz_out, unsigned char* bgr_out, int64_t vcap, int32_t* tri_out, int64_t tcap,
+                      int32_t* vertex_of, int64_t* n_vertices_out, int64_t* n_triangles_out) {
+    if (const int rc = clean_check_mesh("mesh_filter", n_vertices, xyz, true, n_triangles, tri)) return rc;
+    const CleanFilterOut out{ xyz_out, bgr_out, nullptr, vcap, tri_out, tcap, vertex_of, n_vertices_out, n_triangles_out };
+    if (const int rc = clean_check_out(out, bgr != nullptr)) return rc;
+    if (const int rc = clean_check_filter("mesh_filter", min_triangles, keep_largest)) return rc;
+    const CleanMesh m{ (int)n_vertices, (int)n_triangles, xyz, bgr, tri };
+    const CleanFilterParams f{ min_triangles, keep_largest };
+    TimedCall<CLEAN_T_COUNT> c("SFMBA_MESH_CLEAN_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_filter(c.kit.stream, device, m, f, out, c.tm());
+    if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on)
+        clean_timing_line("mesh_filter", c.t, n_vertices, n_triangles, (long long)*n_vertices_out, (long long)*n_triangles_out);
+    return clean_result(rc, "mesh_filter");
+}
+int sfmba_mesh_smooth(int device, int64_t n_vertices, const float* xyz, int64_t n_triangles, const int32_t* tri, const float* origin, float quantum,
+                      int iterations, float lambda, float mu, float* xyz_out, float* normal) {
+    if (const int rc = clean_check_mesh("mesh_smooth", n_vertices, xyz, true, n_triangles, tri)) return rc;
+    if (n_vertices > 0 && !xyz_out) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    CleanSmoothParams p;
+    if (const int rc = clean_check_smooth("mesh_smooth", origin, quantum, iterations, lambda, mu, p)) return rc;
+    const CleanMesh m{ (int)n_vertices, (int)n_triangles, xyz, nullptr, tri };
+    TimedCall<CLEAN_T_COUNT> c("SFMBA_MESH_CLEAN_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_smooth(c.kit.stream, device, m, p, xyz_out, normal, c.tm());
+    if (rc == 0 && c.on) clean_timing_line("mesh_smooth", c.t, n_vertices, n_triangles, n_vertices, n_triangles);
+    return clean_result(rc, "mesh_smooth");
+}
+int sfmba_mesh_clean(int device, int64_t n_vertices, const float* xyz, const unsigned char* bgr, int64_t n_triangles, const int32_t* tri,
+                     int min_triangles, int keep_largest, const float* origin, float quantum, int iterations, float lambda, float mu, float* xyz_out,
+                     unsigned char* bgr_out, float* normal, int64_t vcap, int32_t* tri_out, int64_t tcap, int32_t* vertex_of, int64_t* n_vertices_out,
+                     int64_t* n_triangles_out) {
+    if (const int rc = clean_check_mesh("mesh_clean", n_vertices, xyz, true, n_triangles, tri)) return rc;
+    const CleanFilterOut out{ xyz_out, bgr_out, normal, vcap, tri_out, tcap, vertex_of, n_vertices_out, n_triangles_out };
+    if (const int rc = clean_check_out(out, bgr != nullptr)) return rc;
+    if (const int rc = clean_check_filter("mesh_clean", min_triangles, keep_largest)) return rc;
+    CleanSmoothParams p;
+    if (const int rc = clean_check_smooth("mesh_clean", origin, quantum, iterations, lambda, mu, p)) return rc;
+    const CleanMesh m{ (int)n_vertices, (int)n_triangles, xyz, bgr, tri };
+    const CleanFilterParams f{ min_triangles, keep_largest };
+    TimedCall<CLEAN_T_COUNT> c("SFMBA_MESH_CLEAN_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_clean(c.kit.stream, device, m, f, p, out, c.tm());
+    if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on)
+        clean_timing_line("mesh_clean", c.t, n_vertices, n_triangles, (long long)*n_vertices_out, (long long)*n_triangles_out);
+    return clean_result(rc, "mesh_clean");
 }
 // ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------
 int sfmba_pnp_ransac(int device, int n_prob, const int64_t* prob_ptr, const float* xyz, const float* uv, const float* K, int n_hyp,

@@ -94,6 +94,7 @@ SfM::SfM(const float downscale) :
         mFeaturesGiven(false),
         mDownscaleApplied(false),
         mCols(0), mRows(0),
+        mMeshOkay(false),
         mRunOkay(false),
         mTiming(false) {
     for (double& ms : mStageMs) ms = 0.0;
@@ -211,6 +212,8 @@ void SfM::startRun(size_t n_views) {
     mDenseCloud = DenseCloud();
     mMergedCloud = MergedCloud();
     mMesh = Mesh();
+    mCleanMesh = Mesh();
+    mMeshOkay = false;
     mDenseJobs.clear();
     mRunOkay = false;
     mTiming = std::getenv("SFMBA_SFM_TIMING") != nullptr;
@@ -427,6 +430,8 @@ ErrorCode SfM::densify(const DenseParams& params) {
     mDenseCloud = DenseCloud();
     mMergedCloud = MergedCloud();
     mMesh = Mesh();
+    mCleanMesh = Mesh();
+    mMeshOkay = false;
     mDenseJobs.clear();
     if (mFeaturesGiven || mImages.empty()) {
         std::cerr << "densify: there are no pixels: the run started from setFeatures, and depth maps need the images" << std::endl;
@@ -613,6 +618,8 @@ bool SfM::saveMergedDenseCloudToPLY(const std::string& prefix) {
 
 ErrorCode SfM::meshDenseCloud(const MeshParams& params) {
     mMesh = Mesh();
+    mCleanMesh = Mesh();
+    mMeshOkay = false;
     if (mDenseJobs.empty() || mDepthMaps.size() != mImages.size()) {
         std::cerr << "meshDenseCloud: needs a densify on these images that returned OKAY" << std::endl;
         return ERROR;
@@ -670,6 +677,7 @@ ErrorCode SfM::meshDenseCloud(const MeshParams& params) {
     }
     if (!ok) return ERROR;
     mMesh = mesh;
+    mMeshOkay = true;
     say(LOG_INFO, "mesh: " + std::to_string(mMesh.vertices.size()) + " vertices, " + std::to_string(mMesh.triangles.size() / 3) + " triangles on a " +
                       std::to_string(grid.nx) + " x " + std::to_string(grid.ny) + " x " + std::to_string(grid.nz) + " grid at voxel " +
                       std::to_string(grid.voxel));
@@ -705,6 +713,67 @@ bool SfM::saveMeshToPLY(const std::string& prefix) {
     }
     for (size_t t = 0; t + 2 < mMesh.triangles.size(); t += 3)
         file << "3 " << mMesh.triangles[t] << " " << mMesh.triangles[t + 1] << " " << mMesh.triangles[t + 2] << std::endl;
+    file.close();
+    return !file.fail();
+}
+
+ErrorCode SfM::cleanMesh(const MeshCleanParams& params) {
+    mCleanMesh = Mesh();
+    if (!mMeshOkay) {
+        std::cerr << "cleanMesh: needs a meshDenseCloud that returned OKAY" << std::endl;
+        return ERROR;
+    }
+    const bool timing = std::getenv("SFMBA_SFM_TIMING") != nullptr;
+    double ms[1] = { 0.0 };
+    bool ok = true;
+    Mesh mesh;
+    {
+        StageClock clock(timing ? ms : nullptr, 0);
+        mesh = SfMDenseUtilities::cleanMesh(mMesh, params, &ok);
+    }
+    if (!ok) return ERROR;
+    mCleanMesh = mesh;
+    say(LOG_INFO, "clean mesh: " + std::to_string(mCleanMesh.vertices.size()) + " of " + std::to_string(mMesh.vertices.size()) + " vertices, " +
+                      std::to_string(mCleanMesh.triangles.size() / 3) + " of " + std::to_string(mMesh.triangles.size() / 3) + " triangles");
+    if (timing)
+        std::fprintf(stderr, "[sfmba sfm mesh_clean] clean_ms %.3f vertices %lld triangles %lld\n", ms[0], (long long)mCleanMesh.vertices.size(),
+                     (long long)(mCleanMesh.triangles.size() / 3));
+    return OKAY;
+}
+
+const Mesh& SfM::getCleanMesh() const { return mCleanMesh; }
+
+bool SfM::saveCleanMeshToPLY(const std::string& prefix) {
+    std::ofstream file(prefix + "_mesh_clean.ply");
+    const Mesh& m = mCleanMesh;
+    const bool haveBgr = m.bgr.size() == 3 * m.vertices.size(), haveNormals = m.normals.size() == 3 * m.vertices.size();
+    // the header of the mesh file with the normals of the merged cloud's file between the position and the colour
+    file << "ply                 " << std::endl
+         << "format ascii 1.0    " << std::endl
+         << "element vertex " << m.vertices.size() << std::endl
+         << "property float x    " << std::endl
+         << "property float y    " << std::endl
+         << "property float z    " << std::endl
+         << "property float nx   " << std::endl
+         << "property float ny   " << std::endl
+         << "property float nz   " << std::endl
+         << "property uchar red  " << std::endl
+         << "property uchar green" << std::endl
+         << "property uchar blue " << std::endl
+         << "element face " << m.triangles.size() / 3 << std::endl
+         << "property list uchar int vertex_indices" << std::endl
+         << "end_header          " << std::endl;
+    for (size_t i = 0; i < m.vertices.size(); i++) {
+        const cv::Point3f& p = m.vertices[i];
+        const unsigned char none[3] = { 0, 0, 0 };
+        const float flat[3] = { 0.0f, 0.0f, 0.0f };
+        const unsigned char* bgr = haveBgr ? &m.bgr[3 * i] : none;
+        const float* n = haveNormals ? &m.normals[3 * i] : flat;
+        file << p.x << " " << p.y << " " << p.z << " " << n[0] << " " << n[1] << " " << n[2] << " " << (int)bgr[2] << " " << (int)bgr[1] << " "
+             << (int)bgr[0] << " " << std::endl;
+    }
+    for (size_t t = 0; t + 2 < m.triangles.size(); t += 3)
+        file << "3 " << m.triangles[t] << " " << m.triangles[t + 1] << " " << m.triangles[t + 2] << std::endl;
     file.close();
     return !file.fail();
 }

@@ -71,6 +71,14 @@
 //                 origin_a = (float)((double)lo_a - pad), n_a = floor((side_a + (pad + pad)) / (double)voxel) + 2, capped at 1024.
 //                 minWeight (the views a grid vertex needs) defaults to 1.  These defaults are first choices like the ones above:
 //                 nobody has tuned them.  The dense cloud and the depth maps are not changed.
+//   clean mesh    cleanMesh(params) after a meshDenseCloud that returned OKAY: ONE sfmba_mesh_clean call (include/sfmba.h) over the
+//                 mesh: the connected components with fewer than minComponentTriangles triangles go (or, with keepLargest, all but
+//                 the largest), the rest is smoothed by smoothIterations iterations of Taubin's lambda | mu in integers, and every
+//                 vertex gets a normal (every triangle of a vertex has equal weight: NOT area weighted).  THE HOST RULES:
+//                 origin = the mesh grid's origin; quantum = voxel / 1024 (float), the unit the TSDF already uses;
+//                 minComponentTriangles == 0 means max(1, triangles / 1000) (integer division).  These defaults, and lambda 0.5 /
+//                 mu -0.53 (Taubin's usual pair) at 10 iterations, are first choices like the ones above: nobody has tuned them.
+//                 The mesh of meshDenseCloud, the dense cloud and the depth maps are not changed.
 // There is no visual debugging.
 // An object holds all of a run's state (the stage times of SFMBA_SFM_TIMING included): different objects may run in different
 // threads; one object is not re-entrant.
@@ -200,6 +208,21 @@ public:
      */
     bool saveMeshToPLY(const std::string& prefix);
 
+    /**
+     * The mesh without its small components, smoothed, with a normal per vertex (the contract is at the top of this file).  Valid after
+     * a meshDenseCloud that returned OKAY; cleared wherever that mesh is cleared.  With SFMBA_SFM_TIMING set, one stderr line reports
+     * clean_ms.
+     * @return ERROR (no clean mesh kept) without such a meshDenseCloud, or when the device call fails or refuses (minComponentTriangles
+     *         < 0, smoothIterations outside 0..100, lambda or mu outside their ranges).
+     */
+    ErrorCode cleanMesh(const MeshCleanParams& params = MeshCleanParams());
+
+    /**
+     * <prefix>_mesh_clean.ply: the clean mesh, ASCII, in the style of the other writers: x y z, nx ny nz, red green blue per vertex,
+     * then element face with property list uchar int vertex_indices.
+     */
+    bool saveCleanMeshToPLY(const std::string& prefix);
+
     void setConsoleDebugLevel(unsigned int consoleDebugLevel) { mConsoleDebugLevel = consoleDebugLevel < (unsigned int)LOG_ERROR ? consoleDebugLevel : (unsigned int)LOG_ERROR; }
 
     const std::vector<cv::Mat>&     getImages() const { return mImages; }
@@ -215,6 +238,7 @@ public:
     const std::vector<DenseJob>&    getDenseJobs() const { return mDenseJobs; }       // the jobs of the last densify, ascending view
     const MergedCloud&              getMergedDenseCloud() const { return mMergedCloud; }
     const Mesh&                     getMesh() const;                                  // of the last meshDenseCloud; empty without one
+    const Mesh&                     getCleanMesh() const;                             // of the last cleanMesh; empty without one
 
 private:
     enum { T_EXTRACT, T_MATCH, T_RANK, T_BASELINE_POSE, T_BASELINE_TRIANGULATE, T_ASSOCIATE, T_PNP, T_PAIR_POSES, T_TRIANGULATE, T_MERGE,
@@ -251,6 +275,8 @@ private:
     std::vector<DenseJob>     mDenseJobs;
     MergedCloud               mMergedCloud;
     Mesh                      mMesh;
+    Mesh                      mCleanMesh;
+    bool                      mMeshOkay;        // the last meshDenseCloud returned OKAY and nothing was set since
     bool                      mRunOkay;         // the last runSfM returned OKAY and nothing was set since
     bool                      mTiming;           // SFMBA_SFM_TIMING was set when the run began
     double                    mStageMs[T_COUNT]; // wall time per stage of the current run (all zero unless mTiming)

@@ -2,6 +2,7 @@
 // results.  See SfMDenseUtilities.h.
 #include "SfMDenseUtilities.h"
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -345,6 +346,61 @@ Mesh SfMDenseUtilities::meshDepthMaps(const std::vector<cv::Mat>& images, const 
     if (!done) return Mesh();
     if (ok) *ok = true;
     return mesh;
+}
+
+namespace {
+// the vertices as the C ABI takes them; false if the mesh's arrays do not fit together
+bool flattenMesh(const char* who, const Mesh& mesh, std::vector<float>& xyz) {
+    if (mesh.triangles.size() % 3 != 0 || (!mesh.bgr.empty() && mesh.bgr.size() != 3 * mesh.vertices.size())) {
+        std::fprintf(stderr, "%s: the mesh's arrays do not fit together\n", who);
+        return false;
+    }
+    xyz.resize(3 * mesh.vertices.size() + 1);
+    for (size_t i = 0; i < mesh.vertices.size(); ++i) {
+        xyz[3 * i] = mesh.vertices[i].x; xyz[3 * i + 1] = mesh.vertices[i].y; xyz[3 * i + 2] = mesh.vertices[i].z;
+    }
+    return true;
+}
+}  // namespace
+
+std::vector<int> SfMDenseUtilities::meshComponents(const Mesh& mesh, bool* ok) {
+    if (ok) *ok = false;
+    std::vector<float> xyz;
+    if (!flattenMesh("meshComponents", mesh, xyz)) return std::vector<int>();
+    std::vector<int32_t> label(mesh.vertices.size() + 1);
+    int64_t components = 0, largest = 0;
+    const int rc = sfmba_mesh_components(0, (int64_t)mesh.vertices.size(), (int64_t)(mesh.triangles.size() / 3), mesh.triangles.data(), label.data(),
+                                         nullptr, &components, &largest);
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "meshComponents failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return std::vector<int>();
+    }
+    if (ok) *ok = true;
+    return std::vector<int>(label.begin(), label.begin() + mesh.vertices.size());
+}
+
+Mesh SfMDenseUtilities::cleanMesh(const Mesh& mesh, const MeshCleanParams& params, bool* ok) {
+    if (ok) *ok = false;
+    std::vector<float> xyz;
+    if (!flattenMesh("cleanMesh", mesh, xyz)) return Mesh();
+    const bool colour = !mesh.bgr.empty();
+    const int64_t nv = (int64_t)mesh.vertices.size(), nt = (int64_t)(mesh.triangles.size() / 3);
+    // the host rules (SfM.h): the quantum is the unit the TSDF already uses, and 0 stands for a thousandth of the triangles
+    const float origin[3] = { mesh.grid.origin.x, mesh.grid.origin.y, mesh.grid.origin.z };
+    const float quantum = mesh.grid.voxel / 1024.0f;
+    const int minTriangles = params.minComponentTriangles == 0 ? (int)std::max<int64_t>(1, nt / 1000) : params.minComponentTriangles;
+    std::vector<float> normal;
+    Mesh out;
+    const bool done = runMeshCall("cleanMesh", colour, mesh.grid, [&](float* oxyz, unsigned char* obgr, int64_t vcap, int32_t* otri, int64_t tcap, int64_t* onv, int64_t* ont) {
+        normal.assign((size_t)vcap * 3 + 1, 0.0f);
+        return sfmba_mesh_clean(0, nv, xyz.data(), colour ? mesh.bgr.data() : nullptr, nt, mesh.triangles.data(), minTriangles, params.keepLargest ? 1 : 0,
+                                origin, quantum, params.smoothIterations, params.lambda, params.mu, oxyz, obgr, normal.data(), vcap, otri, tcap, nullptr,
+                                onv, ont);
+    }, out);
+    if (!done) return Mesh();
+    out.normals.assign(normal.begin(), normal.begin() + 3 * out.vertices.size());
+    if (ok) *ok = true;
+    return out;
 }
 
 }  // namespace sfmtoylib

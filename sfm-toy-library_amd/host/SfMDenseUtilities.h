@@ -76,6 +76,7 @@ struct Mesh {
     std::vector<unsigned char> bgr;        // 3 per vertex; empty if the grid had no colour
     std::vector<int>           triangles;  // 3 vertex indices per triangle
     MeshGrid                   grid;       // the grid it was taken from
+    std::vector<float>         normals;    // 3 per vertex, unit length or (0, 0, 0); empty on a raw mesh (cleanMesh fills them)
 };
 
 // SfM::meshDenseCloud: how the grid is laid over the dense cloud (the rule is at the top of SfM.h).  First choices; nobody has tuned them.
@@ -85,6 +86,17 @@ struct MeshParams {
     float truncVoxels;      // trunc in voxels, > 0
     int   minWeight;        // views a grid vertex needs to count, 1..65535
     MeshParams() : voxel(0.0f), resolution(256), truncVoxels(4.0f), minWeight(1) {}
+};
+
+// SfMDenseUtilities::cleanMesh / SfM::cleanMesh: which components go and how the rest is smoothed (include/sfmba.h, sfmba_mesh_clean; the
+// host rules are at the top of SfM.h).  lambda 0.5 / mu -0.53 is Taubin's usual pair; with 10 iterations and the island rule below they
+// are first choices; nobody has tuned them.
+struct MeshCleanParams {
+    int   minComponentTriangles;  // a component with fewer triangles goes; 0 = max(1, triangles / 1000)
+    bool  keepLargest;            // keep only the component with the most triangles
+    int   smoothIterations;       // 0..100, each a lambda pass and a mu pass
+    float lambda, mu;
+    MeshCleanParams() : minComponentTriangles(0), keepLargest(false), smoothIterations(10), lambda(0.5f), mu(-0.53f) {}
 };
 
 class SfMDenseUtilities {
@@ -143,6 +155,21 @@ public:
      */
     static Mesh meshDepthMaps(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
                               const std::vector<cv::Mat>& depthMaps, const MeshGrid& grid, int minWeight, bool* ok = nullptr);
+
+    /**
+     * Per vertex the lowest vertex index of its connected component (a vertex no triangle names is its own): ONE sfmba_mesh_components
+     * call.
+     * @param ok  if not null, receives false when the device call fails or refuses an argument (the result is then empty).
+     */
+    static std::vector<int> meshComponents(const Mesh& mesh, bool* ok = nullptr);
+
+    /**
+     * The mesh without its small components (or with its largest only), smoothed by Taubin's lambda | mu passes in integers of
+     * mesh.grid.voxel / 1024 about mesh.grid.origin, with a normal per vertex (every triangle of a vertex has equal weight: NOT area
+     * weighted): ONE sfmba_mesh_clean call (two when the first reports the sizes).  The grid is carried over.
+     * @param ok  if not null, receives false when the device call fails or refuses an argument (the mesh is then empty).
+     */
+    static Mesh cleanMesh(const Mesh& mesh, const MeshCleanParams& params, bool* ok = nullptr);
 };
 
 }  // namespace sfmtoylib

@@ -1,7 +1,8 @@
 // sfmtoy.cpp -- the command-line program of the reference (main.cpp) over sfmtoylib::SfM of this directory: read the images of a
 // directory, run the pipeline on the MI355X (-M flow: with the optical-flow matcher), write <prefix>_points.ply and <prefix>_cameras.ply -- and, with -D, densify and write
 // <prefix>_dense.ply; with --voxel on top of -D, merge that cloud and write <prefix>_dense_merged.ply; with --mesh on top of -D, mesh
-// the depth maps and write <prefix>_mesh.ply.  The arguments are parsed here
+// the depth maps and write <prefix>_mesh.ply; with --mesh-clean on top of --mesh, drop the mesh's small components, smooth it and write
+// <prefix>_mesh_clean.ply.  The arguments are parsed here
 // (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
 #include <cstdlib>
 #include <cstring>
@@ -32,6 +33,12 @@ void usage(std::ostream& os, const char* program) {
        << "                               footprint of a pixel at the typical depth) and write PREFIX_dense_merged.ply\n"
        << "      --mesh RES               with -D: also mesh the depth maps (TSDF fusion and marching tetrahedra on a grid of RES vertices\n"
        << "                               along the longest side of the dense cloud's box, 2..1024) and write PREFIX_mesh.ply\n"
+       << "      --mesh-clean             with --mesh: also drop the mesh's small components, smooth the rest (Taubin, 10 iterations) and\n"
+       << "                               write PREFIX_mesh_clean.ply with a normal per vertex; the other files are as without it\n"
+       << "      --mesh-min-component N   with --mesh-clean: a component with fewer than N triangles goes (default 0: a thousandth of the\n"
+       << "                               mesh's triangles, at least 1)\n"
+       << "      --mesh-keep-largest      with --mesh-clean: keep only the component with the most triangles\n"
+       << "      --mesh-smooth ITERS      with --mesh-clean: smoothing iterations, 0..100 (default 10)\n"
        << "  -v, --visual-debug N         accepted and ignored: there is no visual debugging\n";
 }
 
@@ -56,15 +63,18 @@ bool number(const std::string& text, double& value) {
 
 int main(int argc, char** argv) {
     std::string directory, prefix = "output", text;
-    double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0, voxel = 0.0, resolution = 256.0;
+    double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0, voxel = 0.0, resolution = 256.0,
+           min_component = 0.0, smooth = 10.0;
     FeatureType features = FEATURES_ORB;
     MatcherType matcher = MATCHER_DESCRIPTORS;
-    bool have_directory = false, dense = false, merged = false, meshed = false;
+    bool have_directory = false, dense = false, merged = false, meshed = false, cleaned = false, clean_option = false, keep_largest = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
         const std::string arg = argv[i];
         if (arg == "-h" || arg == "--help") { usage(std::cout, argv[0]); return 0; }
         if (arg == "-D" || arg == "--dense") { dense = true; continue; }
+        if (arg == "--mesh-clean") { cleaned = true; continue; }
+        if (arg == "--mesh-keep-largest") { keep_largest = clean_option = true; continue; }
         if (option(argc, argv, i, "-p", "--input-directory", text, missing)) { directory = text; have_directory = !missing; }
         else if (option(argc, argv, i, "-o", "--output-prefix", text, missing)) prefix = text;
         else if (option(argc, argv, i, "-s", "--downscale", text, missing)) bad = !missing && (!number(text, downscale) || !(downscale > 0.0));
@@ -88,6 +98,14 @@ int main(int argc, char** argv) {
             bad = !missing && (!number(text, resolution) || !(resolution >= 2.0) || !(resolution <= 1024.0) || resolution != (double)(int)resolution);
             meshed = true;
         }
+        else if (option(argc, argv, i, "--mesh-min-component", "--mesh-min-component", text, missing)) {
+            bad = !missing && (!number(text, min_component) || !(min_component >= 0.0) || !(min_component <= 2147483647.0) || min_component != (double)(int)min_component);
+            clean_option = true;
+        }
+        else if (option(argc, argv, i, "--mesh-smooth", "--mesh-smooth", text, missing)) {
+            bad = !missing && (!number(text, smooth) || !(smooth >= 0.0) || !(smooth <= 100.0) || smooth != (double)(int)smooth);
+            clean_option = true;
+        }
         else if (option(argc, argv, i, "-v", "--visual-debug", text, missing)) bad = !missing && !number(text, ignored);
         else if (arg.size() > 1 && arg[0] == '-') { std::cerr << argv[0] << ": unknown option " << arg << "\n"; usage(std::cerr, argv[0]); return 2; }
         else if (!have_directory) { directory = arg; have_directory = true; }
@@ -96,6 +114,8 @@ int main(int argc, char** argv) {
     }
     if (merged && !dense) { std::cerr << argv[0] << ": --voxel needs -D\n"; usage(std::cerr, argv[0]); return 2; }
     if (meshed && !dense) { std::cerr << argv[0] << ": --mesh needs -D\n"; usage(std::cerr, argv[0]); return 2; }
+    if (cleaned && !meshed) { std::cerr << argv[0] << ": --mesh-clean needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
+    if (clean_option && !cleaned) { std::cerr << argv[0] << ": --mesh-min-component, --mesh-keep-largest and --mesh-smooth need --mesh-clean\n"; usage(std::cerr, argv[0]); return 2; }
     if (!have_directory || directory.empty()) { std::cerr << argv[0] << ": no input directory\n"; usage(std::cerr, argv[0]); return 2; }
 
     SfM sfm((float)downscale);
@@ -119,6 +139,14 @@ int main(int argc, char** argv) {
         params.resolution = (int)resolution;
         if (sfm.meshDenseCloud(params) != OKAY) return 1;
         if (!sfm.saveMeshToPLY(prefix)) return 1;
+        if (cleaned) {
+            MeshCleanParams clean;
+            clean.minComponentTriangles = (int)min_component;
+            clean.keepLargest = keep_largest;
+            clean.smoothIterations = (int)smooth;
+            if (sfm.cleanMesh(clean) != OKAY) return 1;
+            if (!sfm.saveCleanMeshToPLY(prefix)) return 1;
+        }
     }
     return 0;
 }

@@ -872,6 +872,82 @@ int sfmba_shim_run_sfm_mesh(int what, int n_views, int channels, const int64_t* 
     return 0;
 }
 
+// setImages, runSfM, densify(), meshDenseCloud() with its defaults and cleanMesh({min_component, keep_largest, iterations, lambda, mu})
+// in one call (tests/test_gpu_mesh_clean_pipeline.py).  Back come the grid the class chose (grid [8], as above), the mesh of
+// meshDenseCloud as it stands AFTER cleanMesh (cap_vertices rows of mesh_xyz / mesh_bgr, cap_triangles rows of mesh_tri) and the clean
+// mesh (clean_xyz / clean_bgr / clean_normal, clean_tri, under the same capacities), with *unchanged = 1 iff the mesh, the dense cloud
+// and every depth map equal, byte for byte, the copies taken before cleanMesh.  ply_prefix != NULL: saveMeshToPLY and
+// saveCleanMeshToPLY.  what == 1: no run at all, only cleanMesh on a fresh object with images (it has to refuse; no device involved).
+// Returns runSfM's code, 10 + densify's code, 20 + meshDenseCloud's code, 30 + cleanMesh's code (130 + it if a refusing call left a
+// clean mesh behind), -2 if a capacity is too small, -3 if a PLY file could not be written.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_mesh_clean(int what, int n_views, int channels, const int64_t* img_ptr, const unsigned char* px, const int32_t* w,
+                                  const int32_t* h, int debug_level, int min_component, int keep_largest, int iterations, float lambda, float mu,
+                                  const char* ply_prefix, int* unchanged, float* grid, int64_t cap_vertices, int64_t cap_triangles,
+                                  int64_t* n_vertices, int64_t* n_triangles, float* mesh_xyz, unsigned char* mesh_bgr, int32_t* mesh_tri,
+                                  int64_t* n_clean_vertices, int64_t* n_clean_triangles, float* clean_xyz, unsigned char* clean_bgr,
+                                  float* clean_normal, int32_t* clean_tri) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    sfm.setImages(images);
+    *unchanged = 0; *n_vertices = 0; *n_triangles = 0; *n_clean_vertices = 0; *n_clean_triangles = 0;
+    MeshCleanParams params;
+    params.minComponentTriangles = min_component; params.keepLargest = keep_largest != 0; params.smoothIterations = iterations;
+    params.lambda = lambda; params.mu = mu;
+    const auto left_behind = [&]() { return !sfm.getCleanMesh().vertices.empty() || !sfm.getCleanMesh().triangles.empty(); };
+    ErrorCode code;
+    if (what == 1) {
+        code = sfm.cleanMesh(params);
+        return (code == OKAY || left_behind() ? 130 : 30) + (int)code;
+    }
+    if ((code = sfm.runSfM()) != OKAY) return (int)code;
+    if ((code = sfm.densify()) != OKAY) return 10 + (int)code;
+    if ((code = sfm.meshDenseCloud()) != OKAY) return 20 + (int)code;
+    const Mesh before = sfm.getMesh();
+    const DenseCloud cloudBefore = sfm.getDenseCloud();
+    std::vector<std::vector<float> > mapsBefore;             // a view without a map: empty
+    for (const cv::Mat& m : sfm.getDepthMaps())
+        mapsBefore.push_back(m.empty() ? std::vector<float>() : std::vector<float>(m.ptr<float>(0), m.ptr<float>(0) + (size_t)m.rows * m.cols));
+    code = sfm.cleanMesh(params);
+    if (code != OKAY) return (left_behind() ? 130 : 30) + (int)code;
+    const Mesh& mesh = sfm.getMesh();
+    const Mesh& clean = sfm.getCleanMesh();
+    const DenseCloud& cloud = sfm.getDenseCloud();
+    bool same = mesh.vertices.size() == before.vertices.size() && mesh.bgr == before.bgr && mesh.triangles == before.triangles && mesh.normals.empty() &&
+                cloud.points.size() == cloudBefore.points.size() && cloud.bgr == cloudBefore.bgr && sfm.getDepthMaps().size() == mapsBefore.size();
+    for (size_t i = 0; same && i < mesh.vertices.size(); ++i) same = std::memcmp(&mesh.vertices[i], &before.vertices[i], sizeof(cv::Point3f)) == 0;
+    for (size_t i = 0; same && i < cloud.points.size(); ++i) same = std::memcmp(&cloud.points[i], &cloudBefore.points[i], sizeof(cv::Point3f)) == 0;
+    for (size_t v = 0; same && v < mapsBefore.size(); ++v) {
+        const cv::Mat& m = sfm.getDepthMaps()[v];
+        const size_t n = m.empty() ? 0 : (size_t)m.rows * m.cols;
+        same = mapsBefore[v].size() == n && (n == 0 || std::memcmp(m.ptr<float>(0), mapsBefore[v].data(), n * sizeof(float)) == 0);
+    }
+    *unchanged = same ? 1 : 0;
+    *n_vertices = (int64_t)mesh.vertices.size();
+    *n_triangles = (int64_t)(mesh.triangles.size() / 3);
+    *n_clean_vertices = (int64_t)clean.vertices.size();
+    *n_clean_triangles = (int64_t)(clean.triangles.size() / 3);
+    if (*n_vertices > cap_vertices || *n_triangles > cap_triangles) return -2;
+    if (clean.bgr.size() != 3 * clean.vertices.size() || clean.normals.size() != 3 * clean.vertices.size()) return -4;
+    grid[0] = mesh.grid.origin.x; grid[1] = mesh.grid.origin.y; grid[2] = mesh.grid.origin.z; grid[3] = mesh.grid.voxel; grid[4] = mesh.grid.trunc;
+    grid[5] = (float)mesh.grid.nx; grid[6] = (float)mesh.grid.ny; grid[7] = (float)mesh.grid.nz;
+    for (size_t i = 0; i < mesh.vertices.size(); ++i) {
+        mesh_xyz[3 * i] = mesh.vertices[i].x; mesh_xyz[3 * i + 1] = mesh.vertices[i].y; mesh_xyz[3 * i + 2] = mesh.vertices[i].z;
+        for (int k = 0; k < 3; ++k) mesh_bgr[3 * i + k] = mesh.bgr[3 * i + k];
+    }
+    for (size_t i = 0; i < mesh.triangles.size(); ++i) mesh_tri[i] = mesh.triangles[i];
+    for (size_t i = 0; i < clean.vertices.size(); ++i) {
+        clean_xyz[3 * i] = clean.vertices[i].x; clean_xyz[3 * i + 1] = clean.vertices[i].y; clean_xyz[3 * i + 2] = clean.vertices[i].z;
+        for (int k = 0; k < 3; ++k) { clean_bgr[3 * i + k] = clean.bgr[3 * i + k]; clean_normal[3 * i + k] = clean.normals[3 * i + k]; }
+    }
+    for (size_t i = 0; i < clean.triangles.size(); ++i) clean_tri[i] = clean.triangles[i];
+    if (ply_prefix && (!sfm.saveMeshToPLY(ply_prefix) || !sfm.saveCleanMeshToPLY(ply_prefix))) return -3;
+    return 0;
+}
+
 // SfM::densify() where it has to refuse (tests/test_depth_oracle_cpu.py; no device involved): what = 0 after setFeatures (there are
 // no pixels), 1 on images without a run, 2 on a fresh object.  Returns densify's code.
 extern "C" __attribute__((visibility("default")))
