@@ -1137,6 +1137,63 @@ SFMBA_API int sfmba_tsdf_mesh(int device, int n_images, const int64_t* img_ptr /
                 float* xyz /*[vcap][3]*/, unsigned char* bgr /*[vcap][3]*/, int32_t* vkey /*[vcap] or NULL*/, int64_t vcap,
                 int32_t* tri /*[tcap][3]*/, int64_t tcap, int64_t* n_vertices, int64_t* n_triangles);
 
+/* ---- filling the holes of the surface: volumetric diffusion of the TSDF grid (MeshParams::fillIterations) -------------------------
+ * A cell of the extraction is active only if all eight corners are defined, so the zero set stops one cell short of every undefined
+ * vertex: behind every seen surface, at grazing angles and wherever a depth map has a hole, and the mesh of the calls above is OPEN.
+ * These two calls diffuse the signed distance into the undefined vertices (Davis et al., "Filling holes in complex surfaces using
+ * volumetric diffusion") and leave sfmba_tsdf_extract exactly as it is.  The integration marks seen free space (sdf > T contributes
+ * e = 1024), so the unknown region is bounded by "outside" wherever a camera looked.  THE CONTRACT IS OUR OWN AND EQUALS NOBODY'S,
+ * stated so that the device is held BIT FOR BIT to a CPU restatement (tests/tsdf_fill_oracle.py): NOTHING BUT INTEGERS
+ * (csrc/tsdf_fill_math.h).  Below, floor_div rounds towards minus infinity.  UNSEEN GEOMETRY CANNOT BE INVENTED: AT AN OPEN BORDER
+ * THE FILL CONTINUES THE SURFACE AS A SKIRT UP TO `iterations` VOXELS WIDE, so the feature is OFF BY DEFAULT, has two knobs (NOT
+ * TUNED) and says per vertex what it made up.
+ *
+ * sfmba_tsdf_fill
+ *   inputs        a grid as sfmba_tsdf_extract takes it (nx, ny, nz, sum, weight, and csum / cweight both or neither; the origin and
+ *                 the voxel are not needed), min_weight in 1..65535, iterations in 0..254, min_neighbours in 1..6.
+ *   definitions   a vertex is OBSERVED iff W >= min_weight.  Its value is V = floor_div(128 S + W, 2 W): 64 S / W rounded half up, in
+ *                 -65536..65536.  Its colour is c = (2 Sc + Wc) / (2 Wc) per channel, with hasC = (Wc > 0).  Every other vertex
+ *                 starts UNKNOWN, one with 0 < W < min_weight included.  KNOWN means observed, or filled in an earlier pass.
+ *   a pass        every vertex reads the state from BEFORE the pass (Jacobi; no atomic).  For a vertex that is not observed: n6 = the
+ *                 number of its KNOWN face neighbours, at most 6 (neighbours outside the grid do not exist).  An unknown vertex
+ *                 becomes known in this pass iff n6 >= min_neighbours.  A vertex that is already known and filled is updated in
+ *                 every pass (its n6 can no longer drop to 0).  The new value is V' = floor_div(2 sum V + n, 2 n), the sum over its
+ *                 known face neighbours and over itself if it was known, n the number of terms, at most 7.  Colour: among those
+ *                 same terms take the m with hasC; if m > 0 then c' = (2 sum c + m) / (2 m) per channel and hasC' = 1, otherwise
+ *                 hasC' = 0.  Observed vertices never change.  BOUNDS: |sum V| <= 7 * 65536; everything fits int32.
+ *   outputs       sum_out, weight_out, and csum_out / cweight_out where the input has them.  An observed or still-unknown vertex is
+ *                 copied BIT FOR BIT (with iterations == 0 the output is the input).  A filled vertex gets W = FW = 64 ceil(min_weight
+ *                 / 64), in 64..65536, so it is defined for the extraction at the same min_weight; S = V (FW / 64), so S / W = V / 64
+ *                 exactly and |S| <= 1024 W; csum = c and cweight = 1 if hasC, else zeros.  state uint8 [nz][ny][nx] (may be NULL):
+ *                 0 for observed, p in 1..254 for the pass in which the vertex became known, 255 for still unknown.  *n_filled.
+ *   DERIVABLE     a vertex with state == p lies within L1 distance p of an observed vertex.  So no mesh vertex made by the fill lies
+ *                 farther than iterations + 1 voxels (L1) from an observed grid vertex: the width of the skirt at an open border.
+ *
+ * sfmba_tsdf_mesh_fill
+ *   the arguments of sfmba_tsdf_mesh, plus fill_iterations and min_neighbours, plus vfilled uint8 [vcap] (may be NULL): 1 iff either
+ *   end of the mesh vertex's edge is a filled grid vertex.  Integrates, fills and extracts, the grid never leaving the device.
+ *   EQUALS sfmba_tsdf_integrate, sfmba_tsdf_fill, sfmba_tsdf_extract BYTE FOR BYTE.  With fill_iterations == 0 it equals
+ *   sfmba_tsdf_mesh byte for byte and vfilled is all 0.  The capacity protocol is the extraction's (vfilled is not written either).
+ *
+ *   SFMBA_ERR_INVALID_ARG (nothing written): whatever sfmba_tsdf_extract (for the combined call: sfmba_tsdf_mesh) refuses about the
+ *                 dimensions, min_weight and the grid's contents (found on the device, before anything is written); iterations
+ *                 outside 0..254; min_neighbours outside 1..6; a NULL sum, weight, sum_out, weight_out or n_filled; csum without
+ *                 cweight or the reverse; colour outputs missing where colour inputs are given.
+ *   IN-PLACE IS NOT SUPPORTED.  Both: host pointers in and out, synchronous, deterministic.  SFMBA_ABI_VERSION stays 6: adding
+ *   symbols is backward compatible.
+ */
+SFMBA_API int sfmba_tsdf_fill(int device, int nx, int ny, int nz, const int32_t* sum /*[nz][ny][nx]*/, const int32_t* weight /*[nz][ny][nx]*/,
+                const int32_t* csum /*[nz][ny][nx][3] or NULL*/, const int32_t* cweight /*[nz][ny][nx] or NULL*/, int min_weight /*1..65535*/,
+                int iterations /*0..254*/, int min_neighbours /*1..6*/, int32_t* sum_out, int32_t* weight_out, int32_t* csum_out /*or NULL*/,
+                int32_t* cweight_out /*or NULL*/, unsigned char* state /*[nz][ny][nx] or NULL*/, int64_t* n_filled);
+SFMBA_API int sfmba_tsdf_mesh_fill(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* pixels /*or NULL*/, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/,
+                const float* K /*[9]*/, const float* P /*[n_images][12]*/, const float* const* depth /*[n_images], each NULL or [h][w]*/,
+                const float* origin /*[3]*/, float voxel, int nx, int ny, int nz, float trunc, int min_weight /*1..65535*/,
+                int fill_iterations /*0..254*/, int min_neighbours /*1..6*/, float* xyz /*[vcap][3]*/, unsigned char* bgr /*[vcap][3]*/,
+                int32_t* vkey /*[vcap] or NULL*/, unsigned char* vfilled /*[vcap] or NULL*/, int64_t vcap, int32_t* tri /*[tcap][3]*/,
+                int64_t tcap, int64_t* n_vertices, int64_t* n_triangles);
+
 /* ---- cleaning a mesh: components, small-island removal, Taubin smoothing, vertex normals (SfM::cleanMesh) ------------------------
  * The mesh of the calls above is a set of open sheets with islands: a depth outlier that survives the fuse is a floating shell of a
  * few dozen triangles, and the surface carries the plane-step noise of the sweep.  These four calls label the connected components,

@@ -40,6 +40,7 @@ SYMBOLS = [
     "sfmba_png_info", "sfmba_png_decode", "sfmba_match_features_l2", "sfmba_surf_extract",
     "sfmba_depth_sweep", "sfmba_depth_fuse", "sfmba_flow_track", "sfmba_flow_match",
     "sfmba_depth_normals", "sfmba_cloud_merge", "sfmba_tsdf_integrate", "sfmba_tsdf_extract", "sfmba_tsdf_mesh",
+    "sfmba_tsdf_fill", "sfmba_tsdf_mesh_fill",
     "sfmba_mesh_components", "sfmba_mesh_filter", "sfmba_mesh_smooth", "sfmba_mesh_clean",
 ]
 
@@ -717,6 +718,55 @@ def tsdf_mesh(images, K, P, depth_maps, origin, voxel, dims, trunc, min_weight=1
     def call(*out):
         return lib().sfmba_tsdf_mesh(C.c_int(device), *views, *grid, C.c_float(trunc), C.c_int(min_weight), *out)
     return _tsdf_mesh_call(call, images is not None, want_vkey, vcap, tcap)
+
+
+def tsdf_fill(grid_sum, grid_weight, csum=None, cweight=None, min_weight=1, iterations=3, min_neighbours=2, want_state=True, device=0):
+    """sfmba_tsdf_fill: volumetric diffusion of the signed distance into the undefined vertices of a grid, so that the extraction closes
+    the holes (the contract is in include/sfmba.h; THE FILL CONTINUES THE SURFACE PAST AN OPEN BORDER AS A SKIRT UP TO `iterations`
+    VOXELS WIDE).
+
+    grid_sum, grid_weight int32 [nz, ny, nx]; csum int32 [nz, ny, nx, 3] and cweight int32 [nz, ny, nx] or both None.  Returns a dict:
+    sum, weight, csum, cweight (None without colour) of the filled grid; state uint8 [nz, ny, nx] (0 observed, p the pass in which the
+    vertex became known, 255 still unknown) or None; n_filled."""
+    S, W = np.ascontiguousarray(grid_sum, dtype=np.int32), np.ascontiguousarray(grid_weight, dtype=np.int32)
+    if S.ndim != 3 or W.shape != S.shape or (csum is None) != (cweight is None):
+        raise ValueError("sum and weight are [nz, ny, nx]; csum and cweight come together")
+    nz, ny, nx = S.shape
+    colour = csum is not None
+    if colour:
+        csum, cweight = np.ascontiguousarray(csum, dtype=np.int32), np.ascontiguousarray(cweight, dtype=np.int32)
+        if csum.shape != S.shape + (3,) or cweight.shape != S.shape:
+            raise ValueError("csum is [nz, ny, nx, 3] and cweight [nz, ny, nx]")
+    So, Wo = np.zeros_like(S), np.zeros_like(W)
+    CSo, CWo = (np.zeros_like(csum), np.zeros_like(cweight)) if colour else (None, None)
+    state = np.zeros(S.shape, np.uint8) if want_state else None
+    n_filled = C.c_int64(0)
+    bp = C.POINTER(C.c_ubyte)
+    _check(lib().sfmba_tsdf_fill(C.c_int(device), C.c_int(nx), C.c_int(ny), C.c_int(nz), _p(S, _ip), _p(W, _ip), _p(csum, _ip) if colour else None,
+                                 _p(cweight, _ip) if colour else None, C.c_int(min_weight), C.c_int(iterations), C.c_int(min_neighbours),
+                                 _p(So, _ip), _p(Wo, _ip), _p(CSo, _ip) if colour else None, _p(CWo, _ip) if colour else None,
+                                 _p(state, bp) if want_state else None, C.byref(n_filled)))
+    return {"sum": So, "weight": Wo, "csum": CSo, "cweight": CWo, "state": state, "n_filled": int(n_filled.value)}
+
+
+def tsdf_mesh_fill(images, K, P, depth_maps, origin, voxel, dims, trunc, min_weight=1, fill_iterations=3, min_neighbours=2, want_vkey=True,
+                   want_vfilled=True, vcap=None, tcap=None, device=0):
+    """sfmba_tsdf_mesh_fill: depth maps -> a triangle mesh with its holes filled, the grid never leaving the device; equals
+    tsdf_integrate, tsdf_fill and tsdf_extract byte for byte, and tsdf_mesh with fill_iterations 0 (the contract is in include/sfmba.h).
+    Arguments as tsdf_mesh takes them; the result has vfilled uint8 [n] (1 iff either end of the vertex's edge is a filled grid vertex)
+    or None beside what tsdf_mesh gives."""
+    views, keep = _tsdf_views(images, K, P, depth_maps)
+    grid, origin, _ = _tsdf_grid(origin, voxel, dims)
+    bp = C.POINTER(C.c_ubyte)
+    box = {}
+
+    def call(xyz, bgr, vkey, cap, *rest):
+        box["vfilled"] = np.zeros(max(int(cap.value), 1), np.uint8)
+        return lib().sfmba_tsdf_mesh_fill(C.c_int(device), *views, *grid, C.c_float(trunc), C.c_int(min_weight), C.c_int(fill_iterations),
+                                          C.c_int(min_neighbours), xyz, bgr, vkey, _p(box["vfilled"], bp) if want_vfilled else None, cap, *rest)
+    out = _tsdf_mesh_call(call, images is not None, want_vkey, vcap, tcap)
+    out["vfilled"] = box["vfilled"][:len(out["xyz"])].copy() if want_vfilled else None
+    return out
 
 
 def _clean_mesh(xyz, bgr, tri):

@@ -23,6 +23,8 @@
 #include "pnp_ransac.h"
 #include "problem.h"
 #include "surf_extract.h"
+#include "tsdf_fill.h"
+#include "tsdf_fill_math.h"
 #include "tsdf_mesh.h"
 #include <climits>
 #include <cmath>
@@ -191,16 +193,31 @@ void image_timing_line(const char* what, const double* tm) {
                  tm[JPEG_T_ENTROPY], tm[JPEG_T_UPLOAD], tm[JPEG_T_IDCT], tm[JPEG_T_COLOUR], tm[JPEG_T_RESIZE], tm[JPEG_T_DOWNLOAD], (int)tm[JPEG_T_GROUPS]);
 }
 // what the three mesh calls refuse about the grid, the views and the outputs; their failure text and their timing line
+int tsdf_check_dims(const char* who, int nx, int ny, int nz) {
+    const std::string w(who);
+    if (nx < 1 || nx > MESH_MAX_DIM || ny < 1 || ny > MESH_MAX_DIM || nz < 1 || nz > MESH_MAX_DIM)
+        return fail(SFMBA_ERR_INVALID_ARG, w + ": a grid dimension lies outside 1..1024");
+    if ((int64_t)nx * ny * nz > (int64_t)MESH_MAX_VOXELS) return fail(SFMBA_ERR_INVALID_ARG, w + ": more than 2^26 voxels");
+    return 0;
+}
+int tsdf_check_min_weight(const char* who, int min_weight) {
+    if (min_weight < 1 || min_weight > MESH_MAX_WEIGHT) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": min_weight must be in 1..65535");
+    return 0;
+}
+// what the two hole-filling calls refuse about the passes and the rule
+int tsdf_check_fill(const char* who, int iterations, int min_neighbours) {
+    const std::string w(who);
+    if (iterations < 0 || iterations > FILL_MAX_ITERATIONS) return fail(SFMBA_ERR_INVALID_ARG, w + ": iterations must be in 0..254");
+    if (min_neighbours < 1 || min_neighbours > 6) return fail(SFMBA_ERR_INVALID_ARG, w + ": min_neighbours must be in 1..6");
+    return 0;
+}
 int tsdf_check_grid(const char* who, const float* origin, float voxel, int nx, int ny, int nz) {
     const std::string w(who);
     if (!origin) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
     for (int a = 0; a < 3; ++a)
         if (!std::isfinite(origin[a])) return fail(SFMBA_ERR_INVALID_ARG, w + ": origin must be finite");
     if (!std::isfinite(voxel) || !(voxel > 0.0f)) return fail(SFMBA_ERR_INVALID_ARG, w + ": voxel must be finite and > 0");
-    if (nx < 1 || nx > MESH_MAX_DIM || ny < 1 || ny > MESH_MAX_DIM || nz < 1 || nz > MESH_MAX_DIM)
-        return fail(SFMBA_ERR_INVALID_ARG, w + ": a grid dimension lies outside 1..1024");
-    if ((int64_t)nx * ny * nz > (int64_t)MESH_MAX_VOXELS) return fail(SFMBA_ERR_INVALID_ARG, w + ": more than 2^26 voxels");
-    return 0;
+    return tsdf_check_dims(who, nx, ny, nz);
 }
 // what the fuse refuses about images, sizes, K and P (the pixels may be missing here), and trunc
 int tsdf_check_views(const char* who, const TsdfViews& v) {
@@ -222,13 +239,19 @@ int tsdf_check_views(const char* who, const TsdfViews& v) {
 int tsdf_check_out(const char* who, int min_weight, bool colour, const TsdfMeshOut& o) {
     if (o.vcap < 0 || o.tcap < 0 || !o.n_vertices || !o.n_triangles || (o.vcap > 0 && (!o.xyz || (colour && !o.bgr))) || (o.tcap > 0 && !o.tri))
         return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (min_weight < 1 || min_weight > MESH_MAX_WEIGHT) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": min_weight must be in 1..65535");
-    return 0;
+    return tsdf_check_min_weight(who, min_weight);
 }
 int tsdf_result(int rc, const char* who) {
     if (rc == TSDF_ERR_GRID)
         return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": the grid breaks 0 <= W, |S| <= 1024 W, 0 <= Wc or 0 <= colour sum <= 255 Wc");
     return unit_result(rc, who);
+}
+void tsdf_fill_timing_line(const char* what, const double* t, const TsdfGrid& g, int iterations, long long filled, long long nv, long long nt) {
+    std::fprintf(stderr,
+                 "[sfmba %s] upload_ms %.6f integrate_ms %.6f check_ms %.6f fill_ms %.6f count_ms %.6f scan_ms %.6f flags_ms %.6f emit_ms %.6f "
+                 "vertices_ms %.6f download_ms %.6f voxels %lld passes %d filled %lld vertices %lld triangles %lld\n",
+                 what, t[TSDF_T_UPLOAD], t[TSDF_T_INTEGRATE], t[TSDF_T_CHECK], t[TSDF_T_FILL], t[TSDF_T_COUNT_TRI], t[TSDF_T_SCAN], t[TSDF_T_FLAGS],
+                 t[TSDF_T_EMIT], t[TSDF_T_VERTICES], t[TSDF_T_DOWNLOAD], (long long)g.nx * g.ny * g.nz, iterations, filled, nv, nt);
 }
 void tsdf_timing_line(const char* what, const double* t, const TsdfGrid& g, long long nv, long long nt) {
     std::fprintf(stderr,
@@ -676,6 +699,43 @@ int sfmba_tsdf_mesh(int device, int n_images, const int64_t* img_ptr, const unsi
     const int rc = tsdf_mesh(c.kit.stream, device, views, grid, min_weight, out, c.tm());
     if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on) tsdf_timing_line("tsdf_mesh", c.t, grid, (long long)*n_vertices, (long long)*n_triangles);
     return tsdf_result(rc, "tsdf_mesh");
+}
+// ---- filling the holes of the surface: volumetric diffusion of the TSDF grid (MeshParams::fillIterations) -------------------------
+int sfmba_tsdf_fill(int device, int nx, int ny, int nz, const int32_t* sum, const int32_t* weight, const int32_t* csum, const int32_t* cweight,
+                    int min_weight, int iterations, int min_neighbours, int32_t* sum_out, int32_t* weight_out, int32_t* csum_out, int32_t* cweight_out,
+                    unsigned char* state, int64_t* n_filled) {
+    if (!sum || !weight || !sum_out || !weight_out || !n_filled || (csum == nullptr) != (cweight == nullptr) || (csum && (!csum_out || !cweight_out)))
+        return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = tsdf_check_min_weight("tsdf_fill", min_weight)) return rc;
+    if (const int rc = tsdf_check_fill("tsdf_fill", iterations, min_neighbours)) return rc;
+    if (const int rc = tsdf_check_dims("tsdf_fill", nx, ny, nz)) return rc;
+    const TsdfFillParams prm{ min_weight, iterations, min_neighbours };
+    const TsdfGrid grid{ nullptr, 0.0f, nx, ny, nz };
+    TimedCall<TSDF_T_COUNT> c("SFMBA_MESH_TIMING");          // (tools/tsdf_fill_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = tsdf_fill(c.kit.stream, device, nx, ny, nz, sum, weight, csum, cweight, prm, sum_out, weight_out, csum_out, cweight_out, state,
+                             n_filled, c.tm());
+    if (rc == 0 && c.on) tsdf_fill_timing_line("tsdf_fill", c.t, grid, iterations, (long long)*n_filled, 0, 0);
+    return tsdf_result(rc, "tsdf_fill");
+}
+int sfmba_tsdf_mesh_fill(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                         int channels, const float* K, const float* P, const float* const* depth, const float* origin, float voxel, int nx, int ny,
+                         int nz, float trunc, int min_weight, int fill_iterations, int min_neighbours, float* xyz, unsigned char* bgr, int32_t* vkey,
+                         unsigned char* vfilled, int64_t vcap, int32_t* tri, int64_t tcap, int64_t* n_vertices, int64_t* n_triangles) {
+    const TsdfViews views{ n_images, img_ptr, pixels, width, height, channels, K, P, depth, trunc };
+    const TsdfGrid grid{ origin, voxel, nx, ny, nz };
+    const TsdfMeshOut out{ xyz, bgr, vkey, vcap, tri, tcap, n_vertices, n_triangles, vfilled };
+    if (const int rc = tsdf_check_out("tsdf_mesh_fill", min_weight, pixels != nullptr, out)) return rc;
+    if (const int rc = tsdf_check_fill("tsdf_mesh_fill", fill_iterations, min_neighbours)) return rc;
+    if (const int rc = tsdf_check_views("tsdf_mesh_fill", views)) return rc;
+    if (const int rc = tsdf_check_grid("tsdf_mesh_fill", origin, voxel, nx, ny, nz)) return rc;
+    const TsdfFillParams prm{ min_weight, fill_iterations, min_neighbours };
+    TimedCall<TSDF_T_COUNT> c("SFMBA_MESH_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = tsdf_mesh_fill(c.kit.stream, device, views, grid, prm, out, c.tm());
+    if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on)
+        tsdf_fill_timing_line("tsdf_mesh_fill", c.t, grid, fill_iterations, -1, (long long)*n_vertices, (long long)*n_triangles);
+    return tsdf_result(rc, "tsdf_mesh_fill");
 }
 // ---- cleaning a mesh: components, small-island removal, Taubin smoothing, vertex normals (SfM::cleanMesh) -------------------------
 int sfmba_mesh_components(int device, int64_t n_vertices, int64_t n_triangles, const int32_t* tri, int32_t* label, int32_t* comp_triangles,

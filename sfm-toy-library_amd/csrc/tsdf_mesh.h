@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_arena.h"
 #include "unit_common.h"
 
 #include "../../include/sfmba.h"
@@ -18,6 +19,7 @@ constexpr int TSDF_TABLE_CHUNK = 64;
 
 // phases of the timing array
 enum { TSDF_T_UPLOAD = 0, TSDF_T_INTEGRATE, TSDF_T_CHECK, TSDF_T_COUNT_TRI, TSDF_T_SCAN, TSDF_T_FLAGS, TSDF_T_EMIT, TSDF_T_VERTICES, TSDF_T_DOWNLOAD,
+       TSDF_T_FILL,          // the hole filling of tsdf_fill.hip (0 in the three calls of tsdf_mesh.hip)
        TSDF_T_COUNT };
 
 struct TsdfGrid {
@@ -45,6 +47,7 @@ struct TsdfMeshOut {
     int32_t* tri;
     int64_t tcap;
     int64_t *n_vertices, *n_triangles;
+    unsigned char* vfilled = nullptr;    // [vcap] or NULL: sfmba_tsdf_mesh_fill only
 };
 
 // Host pointers in and out; arguments already validated (see include/sfmba.h for the contract).  timing (may be NULL):
@@ -56,5 +59,26 @@ int tsdf_extract(hipStream_t s, int device, const TsdfGrid& grid, const int32_t*
                  const int32_t* cweight, int min_weight, const TsdfMeshOut& out, double* timing);
 // integrate, then extract, the grid never leaving the device; colour iff views.pixels is given
 int tsdf_mesh(hipStream_t s, int device, const TsdfViews& views, const TsdfGrid& grid, int min_weight, const TsdfMeshOut& out, double* timing);
+
+
+// ---- the pieces on a DEVICE-RESIDENT grid, for tsdf_fill.hip: one copy of the validation, the integration and the extraction ----------
+struct TsdfGridDev {
+    double origin[3];
+    double voxel;
+    int nx, ny, nz, nvox;
+};
+struct TsdfGridArrays { int *sum, *weight, *csum, *cweight; };       // device pointers; csum and cweight NULL without colour
+
+TsdfGridDev tsdf_grid_dev(const TsdfGrid& grid);
+int tsdf_alloc_grid(DeviceArena& scratch, const TsdfGridDev& g, bool colour, TsdfGridArrays& a);
+void tsdf_zero_timing(double* timing);
+// *d_bad (zeroed by the caller) becomes 1 iff the grid breaks the bounds an integration guarantees; enqueued on s
+int tsdf_check_device(hipStream_t s, const TsdfGridDev& g, const TsdfGridArrays& a, int* d_bad);
+int tsdf_integrate_device(hipStream_t s, DeviceArena& scratch, PhaseTimer& tm, const TsdfViews& v, const TsdfGridDev& g, bool colour,
+                          const TsdfGridArrays& a);
+// check: hold the grid to its bounds first.  fill_state (device, [nvox], or NULL): the state bytes of a hole filling, from which
+// out.vfilled is made; with out.vfilled given and fill_state NULL it is zeroed.
+int tsdf_extract_device(hipStream_t s, DeviceArena& scratch, PhaseTimer& tm, const TsdfGridDev& g, const TsdfGridArrays& a, int min_weight, bool check,
+                        const TsdfMeshOut& out, const unsigned char* fill_state);
 
 }  // namespace sfmba

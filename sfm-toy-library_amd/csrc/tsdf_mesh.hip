@@ -24,6 +24,9 @@
 //                 (mesh_rank, the step a separate key -> rank pass would take), so the keys of the triangles never exist in memory.
 //   vertices      k_mesh_vertices: a lane per grid vertex with a flag writes its 1..7 vertices (position, colour, key), always from
 //                 the lower end A.
+//   vfilled       k_mesh_vfilled (sfmba_tsdf_mesh_fill only): a lane per mesh vertex reads the hole filling's state bytes of the two
+//                 ends of its edge.  The pieces that work on a device-resident grid (tsdf_alloc_grid, tsdf_check_device,
+//                 tsdf_integrate_device, tsdf_extract_device; tsdf_mesh.h) are what tsdf_fill.hip calls: one copy of each.
 //
 // SCRATCH, for V = nx ny nz voxels (V <= 2^26), T triangles and N vertices: the grid 8 V bytes (24 V with colour), cell bits 2 V,
 // triangle counts and offsets 8 V, vertex flags V, vertex counts and offsets 8 V, the scan's temporary (a few KB), 12 T for the
@@ -54,15 +57,9 @@ struct TsdfImage {
 };
 static_assert(sizeof(TsdfImage) == 128, "TsdfImage is copied to LDS as 16 words");
 
-struct GridDev {
-    double origin[3];
-    double voxel;
-    int nx, ny, nz, nvox;
-};
-
 struct IntegrateParams { double k4[4]; double trunc; int n_tab, channels; };
 
-__global__ __launch_bounds__(LANES) void k_tsdf_integrate(GridDev g, IntegrateParams prm, const TsdfImage* __restrict__ tab,
+__global__ __launch_bounds__(LANES) void k_tsdf_integrate(TsdfGridDev g, IntegrateParams prm, const TsdfImage* __restrict__ tab,
                                                           const float* __restrict__ maps, const unsigned char* __restrict__ raw,
                                                           int* __restrict__ sum, int* __restrict__ weight, int* __restrict__ csum,
                                                           int* __restrict__ cweight) {
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(LANES) void k_mesh_check(int nvox, const int* __res
 
 constexpr int CELL_ACTIVE = 0x100;         // cell bits: the inside bits of the eight corners, and this
 
-__global__ __launch_bounds__(LANES) void k_mesh_count(GridDev g, const int* __restrict__ sum, const int* __restrict__ weight, int min_weight,
+__global__ __launch_bounds__(LANES) void k_mesh_count(TsdfGridDev g, const int* __restrict__ sum, const int* __restrict__ weight, int min_weight,
                                                       unsigned short* __restrict__ cell_bits, int* __restrict__ tcount) {
     const int lin = blockIdx.x * LANES + threadIdx.x;
     if (lin >= g.nvox) return;
@@ -150,7 +147,7 @@ __global__ __launch_bounds__(LANES) void k_mesh_count(GridDev g, const int* __re
     tcount[lin] = n;
 }
 
-__global__ __launch_bounds__(LANES) void k_mesh_flags(GridDev g, const int* __restrict__ sum, const unsigned short* __restrict__ cell_bits,
+__global__ __launch_bounds__(LANES) void k_mesh_flags(TsdfGridDev g, const int* __restrict__ sum, const unsigned short* __restrict__ cell_bits,
                                                       unsigned char* __restrict__ vmask, int* __restrict__ vcount) {
     const int lin = blockIdx.x * LANES + threadIdx.x;
     if (lin >= g.nvox) return;
@@ -192,7 +189,7 @@ __device__ __forceinline__ int mesh_rank(const int* __restrict__ voff, const uns
     return voff[linA] + __popc((unsigned)vmask[linA] & ((1u << code) - 1u));
 }
 
-__global__ __launch_bounds__(LANES) void k_mesh_emit(GridDev g, const unsigned short* __restrict__ cell_bits, const int* __restrict__ tcount,
+__global__ __launch_bounds__(LANES) void k_mesh_emit(TsdfGridDev g, const unsigned short* __restrict__ cell_bits, const int* __restrict__ tcount,
                                                      const int* __restrict__ toff, const int* __restrict__ voff,
                                                      const unsigned char* __restrict__ vmask, int* __restrict__ tri) {
     const int lin = blockIdx.x * LANES + threadIdx.x;
@@ -209,7 +206,7 @@ __global__ __launch_bounds__(LANES) void k_mesh_emit(GridDev g, const unsigned s
     }
 }
 
-__global__ __launch_bounds__(LANES) void k_mesh_vertices(GridDev g, const int* __restrict__ sum, const int* __restrict__ weight,
+__global__ __launch_bounds__(LANES) void k_mesh_vertices(TsdfGridDev g, const int* __restrict__ sum, const int* __restrict__ weight,
                                                          const int* __restrict__ csum, const int* __restrict__ cweight,
                                                          const unsigned char* __restrict__ vmask, const int* __restrict__ voff,
                                                          float* __restrict__ xyz, unsigned char* __restrict__ bgr, int* __restrict__ vkey) {
@@ -234,10 +231,29 @@ __global__ __launch_bounds__(LANES) void k_mesh_vertices(GridDev g, const int* _
     }
 }
 
+// vfilled of a mesh vertex: 1 iff either end of its edge is a grid vertex the hole filling made (state 1..254; tsdf_fill.hip)
+__global__ __launch_bounds__(LANES) void k_mesh_vfilled(TsdfGridDev g, int nv, const int* __restrict__ vkey, const unsigned char* __restrict__ state,
+                                                        unsigned char* __restrict__ vfilled) {
+    const int r = blockIdx.x * LANES + threadIdx.x;
+    if (r >= nv) return;
+    const int lin = vkey[r] >> 3, d = (vkey[r] & 7) + 1;
+    const int at = lin + (d & 1) + ((d >> 1) & 1) * g.nx + ((d >> 2) & 1) * g.nx * g.ny;
+    const int sa = state[lin], sb = state[at];
+    vfilled[r] = (unsigned char)(((sa >= 1 && sa <= 254) || (sb >= 1 && sb <= 254)) ? 1 : 0);
+}
+
 unsigned blocks_for(long long n) { return (unsigned)((n + LANES - 1) / LANES); }
 
-GridDev grid_dev(const TsdfGrid& grid) {
-    GridDev g;
+}  // namespace
+
+int tsdf_check_device(hipStream_t s, const TsdfGridDev& g, const TsdfGridArrays& a, int* d_bad) {
+    hipLaunchKernelGGL(k_mesh_check, dim3(blocks_for(g.nvox)), dim3(LANES), 0, s, g.nvox, a.sum, a.weight, a.csum, a.cweight, d_bad);
+    UNIT_TRY(hipGetLastError());
+    return 0;
+}
+
+TsdfGridDev tsdf_grid_dev(const TsdfGrid& grid) {
+    TsdfGridDev g;
     for (int a = 0; a < 3; ++a) g.origin[a] = (double)grid.origin[a];
     g.voxel = (double)grid.voxel;
     g.nx = grid.nx; g.ny = grid.ny; g.nz = grid.nz;
@@ -245,9 +261,7 @@ GridDev grid_dev(const TsdfGrid& grid) {
     return g;
 }
 
-struct GridArrays { int *sum, *weight, *csum, *cweight; };
-
-int alloc_grid(DeviceArena& scratch, const GridDev& g, bool colour, GridArrays& a) {
+int tsdf_alloc_grid(DeviceArena& scratch, const TsdfGridDev& g, bool colour, TsdfGridArrays& a) {
     const size_t V = (size_t)g.nvox;
     a.csum = a.cweight = nullptr;
     UNIT_ALLOC(scratch, a.sum, int, V);
@@ -260,7 +274,7 @@ int alloc_grid(DeviceArena& scratch, const GridDev& g, bool colour, GridArrays& 
 }
 
 // uploads the maps (and, with colour, the pixels) of the images that have a map and fills the device grid
-int integrate_device(hipStream_t s, DeviceArena& scratch, PhaseTimer& tm, const TsdfViews& v, const GridDev& g, bool colour, const GridArrays& a) {
+int tsdf_integrate_device(hipStream_t s, DeviceArena& scratch, PhaseTimer& tm, const TsdfViews& v, const TsdfGridDev& g, bool colour, const TsdfGridArrays& a) {
     std::vector<TsdfImage> tab;
     long long n_map = 0, n_raw = 0;
     std::vector<int> image_of;
@@ -308,8 +322,8 @@ int integrate_device(hipStream_t s, DeviceArena& scratch, PhaseTimer& tm, const 
 }
 
 // the mesh of a device grid; check: hold the grid to its bounds first
-int extract_device(hipStream_t s, DeviceArena& scratch, PhaseTimer& tm, const GridDev& g, const GridArrays& a, int min_weight, bool check,
-                   const TsdfMeshOut& out) {
+int tsdf_extract_device(hipStream_t s, DeviceArena& scratch, PhaseTimer& tm, const TsdfGridDev& g, const TsdfGridArrays& a, int min_weight, bool check,
+                        const TsdfMeshOut& out, const unsigned char* fill_state) {
     const size_t V = (size_t)g.nvox;
     const unsigned blocks = blocks_for(g.nvox);
     unsigned short* d_cell;
@@ -329,8 +343,7 @@ int extract_device(hipStream_t s, DeviceArena& scratch, PhaseTimer& tm, const Gr
 
     if (check) {
         tm.begin(TSDF_T_CHECK);
-        hipLaunchKernelGGL(k_mesh_check, dim3(blocks), dim3(LANES), 0, s, g.nvox, a.sum, a.weight, a.csum, a.cweight, d_bad);
-        UNIT_TRY(hipGetLastError());
+        if (int rc = tsdf_check_device(s, g, a, d_bad)) return rc;
         tm.end();
     }
     tm.begin(TSDF_T_COUNT_TRI);
@@ -386,26 +399,36 @@ int extract_device(hipStream_t s, DeviceArena& scratch, PhaseTimer& tm, const Gr
     if (out.vkey) UNIT_TRY(hipMemcpyAsync(out.vkey, d_vkey, sizeof(int) * NV, hipMemcpyDeviceToHost, s));
     UNIT_TRY(hipMemcpyAsync(out.tri, d_tri, sizeof(int) * NT * 3, hipMemcpyDeviceToHost, s));
     tm.end();
+    if (out.vfilled && fill_state) {
+        unsigned char* d_vfilled;
+        UNIT_ALLOC(scratch, d_vfilled, unsigned char, NV);
+        tm.begin(TSDF_T_VERTICES);
+        hipLaunchKernelGGL(k_mesh_vfilled, dim3(blocks_for(nv)), dim3(LANES), 0, s, g, nv, d_vkey, fill_state, d_vfilled);
+        UNIT_TRY(hipGetLastError());
+        tm.next(TSDF_T_DOWNLOAD);
+        UNIT_TRY(hipMemcpyAsync(out.vfilled, d_vfilled, NV, hipMemcpyDeviceToHost, s));
+        tm.end();
+    } else if (out.vfilled) {
+        std::memset(out.vfilled, 0, NV);                         // no pass ran: nothing was made up
+    }
     UNIT_TRY(hipStreamSynchronize(s));
     return 0;
 }
 
-void zero_timing(double* timing) {
+void tsdf_zero_timing(double* timing) {
     if (timing) for (int i = 0; i < TSDF_T_COUNT; ++i) timing[i] = 0.0;
 }
 
-}  // namespace
-
 int tsdf_integrate(hipStream_t s, int device, const TsdfViews& views, const TsdfGrid& grid, int32_t* sum, int32_t* weight, int32_t* csum,
                    int32_t* cweight, double* timing) {
-    zero_timing(timing);
-    const GridDev g = grid_dev(grid);
+    tsdf_zero_timing(timing);
+    const TsdfGridDev g = tsdf_grid_dev(grid);
     const bool colour = views.pixels && csum && cweight;
     PhaseTimer tm{ s, timing != nullptr, {}, {} };
     DeviceArena scratch(device);
-    GridArrays a;
-    if (int rc = alloc_grid(scratch, g, colour, a)) return rc;
-    if (int rc = integrate_device(s, scratch, tm, views, g, colour, a)) return rc;
+    TsdfGridArrays a;
+    if (int rc = tsdf_alloc_grid(scratch, g, colour, a)) return rc;
+    if (int rc = tsdf_integrate_device(s, scratch, tm, views, g, colour, a)) return rc;
     const size_t V = (size_t)g.nvox;
     tm.begin(TSDF_T_DOWNLOAD);
     UNIT_TRY(hipMemcpyAsync(sum, a.sum, sizeof(int) * V, hipMemcpyDeviceToHost, s));
@@ -422,13 +445,13 @@ int tsdf_integrate(hipStream_t s, int device, const TsdfViews& views, const Tsdf
 
 int tsdf_extract(hipStream_t s, int device, const TsdfGrid& grid, const int32_t* sum, const int32_t* weight, const int32_t* csum,
                  const int32_t* cweight, int min_weight, const TsdfMeshOut& out, double* timing) {
-    zero_timing(timing);
-    const GridDev g = grid_dev(grid);
+    tsdf_zero_timing(timing);
+    const TsdfGridDev g = tsdf_grid_dev(grid);
     const bool colour = csum && cweight;
     PhaseTimer tm{ s, timing != nullptr, {}, {} };
     DeviceArena scratch(device);
-    GridArrays a;
-    if (int rc = alloc_grid(scratch, g, colour, a)) return rc;
+    TsdfGridArrays a;
+    if (int rc = tsdf_alloc_grid(scratch, g, colour, a)) return rc;
     const size_t V = (size_t)g.nvox;
     tm.begin(TSDF_T_UPLOAD);
     UNIT_TRY(hipMemcpyAsync(a.sum, sum, sizeof(int) * V, hipMemcpyHostToDevice, s));
@@ -438,21 +461,21 @@ int tsdf_extract(hipStream_t s, int device, const TsdfGrid& grid, const int32_t*
         UNIT_TRY(hipMemcpyAsync(a.cweight, cweight, sizeof(int) * V, hipMemcpyHostToDevice, s));
     }
     tm.end();
-    const int rc = extract_device(s, scratch, tm, g, a, min_weight, true, out);
+    const int rc = tsdf_extract_device(s, scratch, tm, g, a, min_weight, true, out, nullptr);
     if (timing) tm.collect(timing);
     return rc;
 }
 
 int tsdf_mesh(hipStream_t s, int device, const TsdfViews& views, const TsdfGrid& grid, int min_weight, const TsdfMeshOut& out, double* timing) {
-    zero_timing(timing);
-    const GridDev g = grid_dev(grid);
+    tsdf_zero_timing(timing);
+    const TsdfGridDev g = tsdf_grid_dev(grid);
     const bool colour = views.pixels != nullptr;
     PhaseTimer tm{ s, timing != nullptr, {}, {} };
     DeviceArena scratch(device);
-    GridArrays a;
-    if (int rc = alloc_grid(scratch, g, colour, a)) return rc;
-    if (int rc = integrate_device(s, scratch, tm, views, g, colour, a)) return rc;
-    const int rc = extract_device(s, scratch, tm, g, a, min_weight, false, out);
+    TsdfGridArrays a;
+    if (int rc = tsdf_alloc_grid(scratch, g, colour, a)) return rc;
+    if (int rc = tsdf_integrate_device(s, scratch, tm, views, g, colour, a)) return rc;
+    const int rc = tsdf_extract_device(s, scratch, tm, g, a, min_weight, false, out, nullptr);
     if (timing) tm.collect(timing);
     return rc;
 }

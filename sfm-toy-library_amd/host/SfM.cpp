@@ -630,6 +630,10 @@ ErrorCode SfM::meshDenseCloud(const MeshParams& params) {
                      "minWeight in 1..65535" << std::endl;
         return ERROR;
     }
+    if (params.fillIterations < 0 || params.fillIterations > 254 || params.fillMinNeighbours < 1 || params.fillMinNeighbours > 6) {
+        std::cerr << "meshDenseCloud: fillIterations must be in 0..254 (0 = no hole filling) and fillMinNeighbours in 1..6" << std::endl;
+        return ERROR;
+    }
     // the box of the dense cloud without its outermost hundredths (the rule is at the top of SfM.h)
     float lo[3], hi[3];
     double side[3], longest = 0.0;
@@ -673,7 +677,11 @@ ErrorCode SfM::meshDenseCloud(const MeshParams& params) {
     Mesh mesh;
     {
         StageClock clock(timing ? ms : nullptr, 0);
-        mesh = SfMDenseUtilities::meshDepthMaps(mImages, mIntrinsics, mCameraPoses, mDepthMaps, grid, params.minWeight, &ok);
+        if (params.fillIterations == 0)
+            mesh = SfMDenseUtilities::meshDepthMaps(mImages, mIntrinsics, mCameraPoses, mDepthMaps, grid, params.minWeight, &ok);
+        else                                                     // ONE sfmba_tsdf_mesh_fill call; mesh.filled is set
+            mesh = SfMDenseUtilities::meshDepthMaps(mImages, mIntrinsics, mCameraPoses, mDepthMaps, grid, params.minWeight, params.fillIterations,
+                                                    params.fillMinNeighbours, &ok);
     }
     if (!ok) return ERROR;
     mMesh = mesh;
@@ -681,6 +689,9 @@ ErrorCode SfM::meshDenseCloud(const MeshParams& params) {
     say(LOG_INFO, "mesh: " + std::to_string(mMesh.vertices.size()) + " vertices, " + std::to_string(mMesh.triangles.size() / 3) + " triangles on a " +
                       std::to_string(grid.nx) + " x " + std::to_string(grid.ny) + " x " + std::to_string(grid.nz) + " grid at voxel " +
                       std::to_string(grid.voxel));
+    if (!mMesh.filled.empty())
+        say(LOG_INFO, "mesh: " + std::to_string(std::count(mMesh.filled.begin(), mMesh.filled.end(), (unsigned char)1)) +
+                          " vertices made by the hole filling (" + std::to_string(params.fillIterations) + " passes)");
     if (timing)
         std::fprintf(stderr, "[sfmba sfm mesh] voxel %.9g trunc %.9g grid %d %d %d mesh_ms %.3f vertices %lld triangles %lld\n", (double)grid.voxel,
                      (double)grid.trunc, grid.nx, grid.ny, grid.nz, ms[0], (long long)mMesh.vertices.size(), (long long)(mMesh.triangles.size() / 3));

@@ -71,7 +71,12 @@
 //                 origin_a = (float)((double)lo_a - pad), n_a = floor((side_a + (pad + pad)) / (double)voxel) + 2, capped at 1024.
 //                 minWeight (the views a grid vertex needs) defaults to 1.  These defaults are first choices like the ones above:
 //                 nobody has tuned them.  The dense cloud and the depth maps are not changed.
-//   clean mesh    cleanMesh(params) after a meshDenseCloud that returned OKAY: ONE sfmba_mesh_clean call (include/sfmba.h) over the
+//   hole filling  params.fillIterations > 0 (default 0: OFF, the call above exactly): ONE sfmba_tsdf_mesh_fill call instead, which
+//                 diffuses the signed distance into the undefined grid vertices for that many passes between the integration and
+//                 the extraction (an unknown vertex is filled once fillMinNeighbours, default 2, of its face neighbours are
+//                 known); getMesh().filled then says per vertex what the fill made up.  AT AN OPEN BORDER THE SURFACE CONTINUES AS
+//                 A SKIRT UP TO fillIterations VOXELS WIDE; neither parameter has been tuned.  The grid rule does not change.
+//   clean mesh   cleanMesh(params) after a meshDenseCloud that returned OKAY: ONE sfmba_mesh_clean call (include/sfmba.h) over the
 //                 mesh: the connected components with fewer than minComponentTriangles triangles go (or, with keepLargest, all but
 //                 the largest), the rest is smoothed by smoothIterations iterations of Taubin's lambda | mu in integers, and every
 //                 vertex gets a normal (every triangle of a vertex has equal weight: NOT area weighted).  THE HOST RULES:

@@ -348,6 +348,64 @@ Mesh SfMDenseUtilities::meshDepthMaps(const std::vector<cv::Mat>& images, const 
     return mesh;
 }
 
+Mesh SfMDenseUtilities::meshDepthMaps(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
+                                      const std::vector<cv::Mat>& depthMaps, const MeshGrid& grid, int minWeight, int fillIterations,
+                                      int fillMinNeighbours, bool* ok) {
+    if (fillIterations == 0) return meshDepthMaps(images, intrinsics, poses, depthMaps, grid, minWeight, ok);      // the call made without the fill
+    Mesh mesh;
+    if (ok) *ok = false;
+    FlatScene f;
+    std::vector<const float*> maps;
+    if (!flattenScene(images, intrinsics, poses, f) || depthMaps.size() != images.size()) {
+        std::fprintf(stderr, "meshDepthMaps: one pose and one depth map (or an empty Mat) per image are needed\n");
+        return mesh;
+    }
+    if (!mapPointers("meshDepthMaps", images, depthMaps, maps)) return mesh;
+    const float origin[3] = { grid.origin.x, grid.origin.y, grid.origin.z };
+    std::vector<unsigned char> filled;
+    const bool done = runMeshCall("meshDepthMaps", true, grid, [&](float* xyz, unsigned char* bgr, int64_t vcap, int32_t* tri, int64_t tcap, int64_t* nv, int64_t* nt) {
+        filled.assign((size_t)vcap + 1, 0);
+        return sfmba_tsdf_mesh_fill(0, (int)images.size(), f.ptr.data(), f.px.data(), f.w.data(), f.h.data(), f.channels, f.K, f.P.data(), maps.data(),
+                                    origin, grid.voxel, grid.nx, grid.ny, grid.nz, grid.trunc, minWeight, fillIterations, fillMinNeighbours, xyz, bgr,
+                                    nullptr, filled.data(), vcap, tri, tcap, nv, nt);
+    }, mesh);
+    if (!done) return Mesh();
+    filled.resize(mesh.vertices.size());
+    mesh.filled.swap(filled);
+    if (ok) *ok = true;
+    return mesh;
+}
+
+bool SfMDenseUtilities::fillTSDF(const TsdfVolume& volume, int minWeight, int iterations, int minNeighbours, TsdfVolume& out,
+                                 std::vector<unsigned char>* state) {
+    out = TsdfVolume();
+    if (state) state->clear();
+    const MeshGrid& g = volume.grid;
+    const int64_t cells = (int64_t)g.nx * g.ny * g.nz;
+    const bool colour = !volume.csum.empty();
+    if (g.nx < 1 || g.ny < 1 || g.nz < 1 || cells > ((int64_t)1 << 26) || (int64_t)volume.sum.size() != cells || (int64_t)volume.weight.size() != cells ||
+        (colour && ((int64_t)volume.csum.size() != 3 * cells || (int64_t)volume.cweight.size() != cells))) {
+        std::fprintf(stderr, "fillTSDF: the volume's arrays do not fit its grid\n");
+        return false;
+    }
+    TsdfVolume v;
+    v.grid = g;
+    v.sum.resize((size_t)cells); v.weight.resize((size_t)cells);
+    if (colour) { v.csum.resize((size_t)cells * 3); v.cweight.resize((size_t)cells); }
+    std::vector<unsigned char> st(state ? (size_t)cells : 0);
+    int64_t filled = 0;
+    const int rc = sfmba_tsdf_fill(0, g.nx, g.ny, g.nz, volume.sum.data(), volume.weight.data(), colour ? volume.csum.data() : nullptr,
+                                   colour ? volume.cweight.data() : nullptr, minWeight, iterations, minNeighbours, v.sum.data(), v.weight.data(),
+                                   colour ? v.csum.data() : nullptr, colour ? v.cweight.data() : nullptr, state ? st.data() : nullptr, &filled);
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "fillTSDF failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return false;
+    }
+    out = v;
+    if (state) state->swap(st);
+    return true;
+}
+
 namespace {
 // the vertices as the C ABI takes them; false if the mesh's arrays do not fit together
 bool flattenMesh(const char* who, const Mesh& mesh, std::vector<float>& xyz) {

@@ -4,7 +4,8 @@
 // "camera poses" and "a model" (SfM::densify drives it).  Both functions are thin: they flatten, call and rebuild.  So are the two
 // that follow them, over sfmba_depth_normals / sfmba_cloud_merge: a normal per depth pixel, and one oriented point per occupied voxel
 // of the fused cloud (SfM::mergeDenseCloud drives them).  The last three, over sfmba_tsdf_integrate / sfmba_tsdf_extract /
-// sfmba_tsdf_mesh, turn the depth maps into a surface: a truncated signed distance grid and its triangle mesh (SfM::meshDenseCloud).
+// sfmba_tsdf_mesh, turn the depth maps into a surface: a truncated signed distance grid and its triangle mesh (SfM::meshDenseCloud);
+// sfmba_tsdf_fill / sfmba_tsdf_mesh_fill fill the grid's holes in between (MeshParams::fillIterations, off by default).
 #pragma once
 #include <vector>
 
@@ -77,6 +78,7 @@ struct Mesh {
     std::vector<int>           triangles;  // 3 vertex indices per triangle
     MeshGrid                   grid;       // the grid it was taken from
     std::vector<float>         normals;    // 3 per vertex, unit length or (0, 0, 0); empty on a raw mesh (cleanMesh fills them)
+    std::vector<unsigned char> filled;     // 1 per vertex that lies on an edge with an end the hole filling made; EMPTY when nothing was filled
 };
 
 // SfM::meshDenseCloud: how the grid is laid over the dense cloud (the rule is at the top of SfM.h).  First choices; nobody has tuned them.
@@ -85,7 +87,10 @@ struct MeshParams {
     int   resolution;       // grid vertices along the longest side of the cloud's box, >= 2
     float truncVoxels;      // trunc in voxels, > 0
     int   minWeight;        // views a grid vertex needs to count, 1..65535
-    MeshParams() : voxel(0.0f), resolution(256), truncVoxels(4.0f), minWeight(1) {}
+    int   fillIterations;   // hole filling (include/sfmba.h, sfmba_tsdf_fill): passes, 0..254; 0 = OFF, THE DEFAULT.  AT AN OPEN BORDER THE FILL
+                            // CONTINUES THE SURFACE AS A SKIRT UP TO THIS MANY VOXELS WIDE
+    int   fillMinNeighbours;  // known face neighbours an unknown grid vertex needs to be filled, 1..6; NOT TUNED
+    MeshParams() : voxel(0.0f), resolution(256), truncVoxels(4.0f), minWeight(1), fillIterations(0), fillMinNeighbours(2) {}
 };
 
 // SfMDenseUtilities::cleanMesh / SfM::cleanMesh: which components go and how the rest is smoothed (include/sfmba.h, sfmba_mesh_clean; the
@@ -155,6 +160,24 @@ public:
      */
     static Mesh meshDepthMaps(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
                               const std::vector<cv::Mat>& depthMaps, const MeshGrid& grid, int minWeight, bool* ok = nullptr);
+
+    /**
+     * meshDepthMaps with the holes of the grid filled between the integration and the extraction: ONE sfmba_tsdf_mesh_fill call (two
+     * when the first reports the sizes); mesh.filled says per vertex what the fill made up.  With fillIterations == 0 it is the call
+     * above and mesh.filled stays empty.
+     */
+    static Mesh meshDepthMaps(const std::vector<cv::Mat>& images, const Intrinsics& intrinsics, const std::vector<cv::Matx34f>& poses,
+                              const std::vector<cv::Mat>& depthMaps, const MeshGrid& grid, int minWeight, int fillIterations, int fillMinNeighbours,
+                              bool* ok = nullptr);
+
+    /**
+     * The volume with the signed distance diffused into its undefined vertices (volumetric diffusion; the rule is in include/sfmba.h):
+     * ONE sfmba_tsdf_fill call.  state (may be null): per vertex 0 observed, p the pass in which it became known, 255 still unknown.
+     * A filled vertex lies within `iterations` voxels (L1) of an observed one: THE SKIRT AT AN OPEN BORDER IS THAT WIDE.
+     * @return false (out empty) when the device call fails or refuses an argument; the reason goes to stderr.
+     */
+    static bool fillTSDF(const TsdfVolume& volume, int minWeight, int iterations, int minNeighbours, TsdfVolume& out,
+                         std::vector<unsigned char>* state = nullptr);
 
     /**
      * Per vertex the lowest vertex index of its connected component (a vertex no triangle names is its own): ONE sfmba_mesh_components

@@ -1,7 +1,7 @@
 // sfmtoy.cpp -- the command-line program of the reference (main.cpp) over sfmtoylib::SfM of this directory: read the images of a
 // directory, run the pipeline on the MI355X (-M flow: with the optical-flow matcher), write <prefix>_points.ply and <prefix>_cameras.ply -- and, with -D, densify and write
 // <prefix>_dense.ply; with --voxel on top of -D, merge that cloud and write <prefix>_dense_merged.ply; with --mesh on top of -D, mesh
-// the depth maps and write <prefix>_mesh.ply; with --mesh-clean on top of --mesh, drop the mesh's small components, smooth it and write
+// the depth maps and write <prefix>_mesh.ply (--mesh-fill N: with the grid's holes filled by N passes first); with --mesh-clean on top of --mesh, drop the mesh's small components, smooth it and write
 // <prefix>_mesh_clean.ply.  The arguments are parsed here
 // (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
 #include <cstdlib>
@@ -33,6 +33,9 @@ void usage(std::ostream& os, const char* program) {
        << "                               footprint of a pixel at the typical depth) and write PREFIX_dense_merged.ply\n"
        << "      --mesh RES               with -D: also mesh the depth maps (TSDF fusion and marching tetrahedra on a grid of RES vertices\n"
        << "                               along the longest side of the dense cloud's box, 2..1024) and write PREFIX_mesh.ply\n"
+       << "      --mesh-fill N            with --mesh: fill the holes of the grid by N passes of volumetric diffusion, 0..254 (default 0: off);\n"
+       << "                               PAST AN OPEN BORDER THE SURFACE CONTINUES AS A SKIRT UP TO N VOXELS WIDE\n"
+       << "      --mesh-fill-neighbours K with --mesh-fill: known face neighbours a grid vertex needs to be filled, 1..6 (default 2)\n"
        << "      --mesh-clean             with --mesh: also drop the mesh's small components, smooth the rest (Taubin, 10 iterations) and\n"
        << "                               write PREFIX_mesh_clean.ply with a normal per vertex; the other files are as without it\n"
        << "      --mesh-min-component N   with --mesh-clean: a component with fewer than N triangles goes (default 0: a thousandth of the\n"
@@ -64,10 +67,11 @@ bool number(const std::string& text, double& value) {
 int main(int argc, char** argv) {
     std::string directory, prefix = "output", text;
     double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0, voxel = 0.0, resolution = 256.0,
-           min_component = 0.0, smooth = 10.0;
+           min_component = 0.0, smooth = 10.0, fill = 0.0, fill_neighbours = 2.0;
     FeatureType features = FEATURES_ORB;
     MatcherType matcher = MATCHER_DESCRIPTORS;
-    bool have_directory = false, dense = false, merged = false, meshed = false, cleaned = false, clean_option = false, keep_largest = false;
+    bool have_directory = false, dense = false, merged = false, meshed = false, cleaned = false, clean_option = false, keep_largest = false,
+         filled = false, fill_option = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
         const std::string arg = argv[i];
@@ -98,6 +102,14 @@ int main(int argc, char** argv) {
             bad = !missing && (!number(text, resolution) || !(resolution >= 2.0) || !(resolution <= 1024.0) || resolution != (double)(int)resolution);
             meshed = true;
         }
+        else if (option(argc, argv, i, "--mesh-fill", "--mesh-fill", text, missing)) {
+            bad = !missing && (!number(text, fill) || !(fill >= 0.0) || !(fill <= 254.0) || fill != (double)(int)fill);
+            filled = true;
+        }
+        else if (option(argc, argv, i, "--mesh-fill-neighbours", "--mesh-fill-neighbours", text, missing)) {
+            bad = !missing && (!number(text, fill_neighbours) || !(fill_neighbours >= 1.0) || !(fill_neighbours <= 6.0) || fill_neighbours != (double)(int)fill_neighbours);
+            fill_option = true;
+        }
         else if (option(argc, argv, i, "--mesh-min-component", "--mesh-min-component", text, missing)) {
             bad = !missing && (!number(text, min_component) || !(min_component >= 0.0) || !(min_component <= 2147483647.0) || min_component != (double)(int)min_component);
             clean_option = true;
@@ -114,6 +126,8 @@ int main(int argc, char** argv) {
     }
     if (merged && !dense) { std::cerr << argv[0] << ": --voxel needs -D\n"; usage(std::cerr, argv[0]); return 2; }
     if (meshed && !dense) { std::cerr << argv[0] << ": --mesh needs -D\n"; usage(std::cerr, argv[0]); return 2; }
+    if (filled && !meshed) { std::cerr << argv[0] << ": --mesh-fill needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
+    if (fill_option && !filled) { std::cerr << argv[0] << ": --mesh-fill-neighbours needs --mesh-fill\n"; usage(std::cerr, argv[0]); return 2; }
     if (cleaned && !meshed) { std::cerr << argv[0] << ": --mesh-clean needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
     if (clean_option && !cleaned) { std::cerr << argv[0] << ": --mesh-min-component, --mesh-keep-largest and --mesh-smooth need --mesh-clean\n"; usage(std::cerr, argv[0]); return 2; }
     if (!have_directory || directory.empty()) { std::cerr << argv[0] << ": no input directory\n"; usage(std::cerr, argv[0]); return 2; }
@@ -137,6 +151,8 @@ int main(int argc, char** argv) {
     if (meshed) {
         MeshParams params;
         params.resolution = (int)resolution;
+        params.fillIterations = (int)fill;
+        params.fillMinNeighbours = (int)fill_neighbours;
         if (sfm.meshDenseCloud(params) != OKAY) return 1;
         if (!sfm.saveMeshToPLY(prefix)) return 1;
         if (cleaned) {

@@ -872,6 +872,96 @@ int sfmba_shim_run_sfm_mesh(int what, int n_views, int channels, const int64_t* 
     return 0;
 }
 
+// setImages, runSfM, densify(), then meshDenseCloud twice -- with fillIterations 0 and with {fill_iterations, fill_min_neighbours} -- and
+// cleanMesh() with its defaults on the filled mesh, in one call (tests/test_gpu_tsdf_fill_pipeline.py).  Back come the poses, K, has_map,
+// the depth maps and the dense cloud as in sfmba_shim_run_sfm_mesh, with *unchanged = 1 iff the dense cloud and every depth map equal,
+// byte for byte, the copies taken before the first mesh call; the grid of the first and of the second call (grid [16]: twice origin x y z,
+// voxel, trunc, nx ny nz as floats); the mesh without the fill (mesh0_*, *filled0_size = its filled.size()) and the mesh with it (mesh_*,
+// mesh_filled, *filled_size) under the same capacities; *clean_code = cleanMesh's code.  ply_prefix != NULL: saveMeshToPLY of the filled
+// mesh.  what == 1: no run at all, only meshDenseCloud with these fill parameters on a fresh object (it has to refuse).  Returns runSfM's
+// code, 10 + densify's code, 20 + the first meshDenseCloud's code, 40 + the second's, -2 if a capacity is too small, -3 if the PLY file
+// could not be written.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_mesh_fill(int what, int n_views, int channels, const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h,
+                                 int debug_level, int resolution, int min_weight, int fill_iterations, int fill_min_neighbours, const char* ply_prefix,
+                                 float* poses, float* K, unsigned char* has_map, float* depth, int64_t cap_dense, int64_t* n_dense, float* dense_xyz,
+                                 int* unchanged, float* grid, int64_t cap_vertices, int64_t cap_triangles, int64_t* n_vertices0, int64_t* n_triangles0,
+                                 float* mesh0_xyz, unsigned char* mesh0_bgr, int32_t* mesh0_tri, int64_t* filled0_size, int64_t* n_vertices,
+                                 int64_t* n_triangles, float* mesh_xyz, unsigned char* mesh_bgr, int32_t* mesh_tri, unsigned char* mesh_filled,
+                                 int64_t* filled_size, int* clean_code) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    sfm.setImages(images);
+    *n_dense = 0; *unchanged = 0; *n_vertices0 = 0; *n_triangles0 = 0; *n_vertices = 0; *n_triangles = 0; *filled0_size = -1; *filled_size = -1;
+    *clean_code = -1;
+    MeshParams params;
+    params.resolution = resolution; params.minWeight = min_weight;
+    MeshParams fill = params;
+    fill.fillIterations = fill_iterations; fill.fillMinNeighbours = fill_min_neighbours;
+    ErrorCode code;
+    if (what == 1) {
+        code = sfm.meshDenseCloud(fill);
+        return (code == OKAY || !sfm.getMesh().vertices.empty() ? 140 : 40) + (int)code;
+    }
+    if ((code = sfm.runSfM()) != OKAY) return (int)code;
+    for (int v = 0; v < n_views; ++v)
+        for (int e = 0; e < 12; ++e) poses[12 * v + e] = sfm.getCameraPoses()[v].val[e];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) K[3 * r + c] = sfm.getIntrinsics().K.at<float>(r, c);
+    if ((code = sfm.densify()) != OKAY) return 10 + (int)code;
+    const DenseCloud before = sfm.getDenseCloud();
+    std::vector<std::vector<float> > mapsBefore;             // a view without a map: empty
+    for (const cv::Mat& m : sfm.getDepthMaps())
+        mapsBefore.push_back(m.empty() ? std::vector<float>() : std::vector<float>(m.ptr<float>(0), m.ptr<float>(0) + (size_t)m.rows * m.cols));
+    auto put = [&](const Mesh& mesh, float* g, int64_t* nv, int64_t* nt, float* xyz, unsigned char* bgr, int32_t* tri) {
+        *nv = (int64_t)mesh.vertices.size();
+        *nt = (int64_t)(mesh.triangles.size() / 3);
+        if (*nv > cap_vertices || *nt > cap_triangles) return false;
+        g[0] = mesh.grid.origin.x; g[1] = mesh.grid.origin.y; g[2] = mesh.grid.origin.z; g[3] = mesh.grid.voxel; g[4] = mesh.grid.trunc;
+        g[5] = (float)mesh.grid.nx; g[6] = (float)mesh.grid.ny; g[7] = (float)mesh.grid.nz;
+        for (size_t i = 0; i < mesh.vertices.size(); ++i) {
+            xyz[3 * i] = mesh.vertices[i].x; xyz[3 * i + 1] = mesh.vertices[i].y; xyz[3 * i + 2] = mesh.vertices[i].z;
+            for (int k = 0; k < 3; ++k) bgr[3 * i + k] = mesh.bgr[3 * i + k];
+        }
+        for (size_t i = 0; i < mesh.triangles.size(); ++i) tri[i] = mesh.triangles[i];
+        return true;
+    };
+    if ((code = sfm.meshDenseCloud(params)) != OKAY) return 20 + (int)code;
+    *filled0_size = (int64_t)sfm.getMesh().filled.size();
+    if (!put(sfm.getMesh(), grid, n_vertices0, n_triangles0, mesh0_xyz, mesh0_bgr, mesh0_tri)) return -2;
+    if ((code = sfm.meshDenseCloud(fill)) != OKAY) return 40 + (int)code;
+    const Mesh& mesh = sfm.getMesh();
+    *filled_size = (int64_t)mesh.filled.size();
+    if (!put(mesh, grid + 8, n_vertices, n_triangles, mesh_xyz, mesh_bgr, mesh_tri)) return -2;
+    for (size_t i = 0; i < mesh.filled.size() && i < mesh.vertices.size(); ++i) mesh_filled[i] = mesh.filled[i];
+    const DenseCloud& cloud = sfm.getDenseCloud();
+    bool same = cloud.points.size() == before.points.size() && cloud.bgr == before.bgr && cloud.views == before.views && cloud.pixels == before.pixels &&
+                sfm.getDepthMaps().size() == mapsBefore.size();
+    size_t at = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const size_t n = (size_t)w[v] * h[v];
+        const cv::Mat& m = sfm.getDepthMaps()[(size_t)v];
+        has_map[v] = m.empty() ? 0 : 1;
+        if (m.empty()) std::memset(depth + at, 0, n * sizeof(float));
+        else std::memcpy(depth + at, m.ptr<float>(0), n * sizeof(float));
+        same = same && (m.empty() ? mapsBefore[(size_t)v].empty()
+                                  : mapsBefore[(size_t)v].size() == n && std::memcmp(m.ptr<float>(0), mapsBefore[(size_t)v].data(), n * sizeof(float)) == 0);
+        at += n;
+    }
+    *n_dense = (int64_t)cloud.points.size();
+    if (*n_dense > cap_dense) return -2;
+    for (size_t i = 0; i < cloud.points.size(); ++i) {
+        dense_xyz[3 * i] = cloud.points[i].x; dense_xyz[3 * i + 1] = cloud.points[i].y; dense_xyz[3 * i + 2] = cloud.points[i].z;
+        same = same && std::memcmp(&cloud.points[i], &before.points[i], sizeof(cv::Point3f)) == 0;
+    }
+    *unchanged = same ? 1 : 0;
+    if (ply_prefix && !sfm.saveMeshToPLY(ply_prefix)) return -3;
+    *clean_code = (int)sfm.cleanMesh();
+    return 0;
+}
+
 // setImages, runSfM, densify(), meshDenseCloud() with its defaults and cleanMesh({min_component, keep_largest, iterations, lambda, mu})
 // in one call (tests/test_gpu_mesh_clean_pipeline.py).  Back come the grid the class chose (grid [8], as above), the mesh of
 // meshDenseCloud as it stands AFTER cleanMesh (cap_vertices rows of mesh_xyz / mesh_bgr, cap_triangles rows of mesh_tri) and the clean
