@@ -227,18 +227,21 @@ typedef struct sfmba_summary {
     int    cholesky_fallbacks;        /* ABI v4: LM iterations of an AUTO solve whose CG did not reach 1e-12 and were factorised instead */
 } sfmba_summary;
 
-/* One row per LM iteration (row 0 = the initial evaluation), mirrors ceres::IterationSummary. */
+/* One row per LM iteration (row 0 = the initial evaluation), mirrors ceres::IterationSummary.  With x the point the iteration linearised at
+ * and x_trial = x + step the point it tried (tests/test_gpu_trace_columns.py holds every column to a long-double restatement, row by row).
+ * A row that ends the solve on a tolerance holds what Ceres had computed by then: the later columns are 0. */
 typedef struct sfmba_iteration {
     int    iteration;
-    int    step_is_valid;
-    int    step_is_successful;
-    int    linear_iters;
-    double cost;
-    double cost_change;
-    double gradient_max_norm;
-    double step_norm;
-    double relative_decrease;
-    double trust_region_radius;
+    int    step_is_valid;             /* the linear solve succeeded and the model cost change is positive; 0: the columns below it are 0, cost / gradient those of x */
+    int    step_is_successful;        /* relative_decrease > min_relative_decrease: x_trial is the next x */
+    int    linear_iters;              /* CG iterations of this row's linear solve (0: factorised) */
+    double cost;                      /* at x_trial after a successful or a rejected step (Ceres reports the candidate's cost on a rejected row), else at x */
+    double cost_change;               /* cost(x) - cost(x_trial) */
+    double gradient_max_norm;         /* max |J^T r| over ALL parameters, unscaled, at the point the row leaves the solve at: x_trial after a successful
+                                         step -- also when the iteration or time limit ends the solve with this row -- else the previous row's */
+    double step_norm;                 /* |x_trial - x|_2 over cameras, points and the focal, unscaled: the difference of the stored parameters */
+    double relative_decrease;         /* rho = cost_change / model cost change, the model's being -(J step)^T (r + J step / 2) with J, r at x */
+    double trust_region_radius;       /* AFTER this row's update: radius / max(1/3, 1 - (2 rho - 1)^3) on success, radius / 2, 4, 8 ... on consecutive rejections */
 } sfmba_iteration;
 
 typedef struct sfmba_problem sfmba_problem;   /* opaque, device-resident problem */

@@ -53,10 +53,11 @@ void launch_linearise_setup(sfmba_problem* p, int jacobi, bool begun = false) {
 }
 
 // The partial linearisation: per-point table, camera diagonal, duplicate pairs inside diagonal blocks, off-diagonal blocks of S (unpreconditioned).
-// ps_mode: launch_point_build (0: point scales from db.pscale; 1 / 2: form them here).
+// ps_mode: launch_point_build (0: point scales from db.pscale; 1 / 2: form them here).  point_pass_done: the early linearisation kernel
+// behind the last control kernel (launch_point_build, mode 4) has run the point pass at this very point already.
 template <typename T>
-void launch_partial_linearisation(sfmba_problem* p, int ps_mode) {
-    launch_point_build<T>(p->stream, p->ds, p->db, ps_mode);
+void launch_partial_linearisation(sfmba_problem* p, int ps_mode, bool point_pass_done = false) {
+    if (!point_pass_done) launch_point_build<T>(p->stream, p->ds, p->db, ps_mode);
     launch_cam_diag<T>(p->stream, p->ds, p->db);
     launch_schur_pairs<T>(p->stream, p->ds, p->db, 2);
     launch_schur_pairs<T>(p->stream, p->ds, p->db, 0);

@@ -433,6 +433,22 @@ int run_solve(sfmba_problem* p, const sfmba_options& o, sfmba_summary* summary, 
                          p->h_state->gmax, p->h_state->radius, p->h_state->termination);
         }
     }
+    // The run ends on a LIMIT behind an accepted step: the row of that step reports the gradient AT the accepted point, as Ceres' does
+    // (HandleSuccessfulStep evaluates there before FinalizeIterationAndCheckIfMinimizerCanContinue looks at the limits), and that evaluation
+    // counts among the jacobian_evals.  Inside the loop it is the next iteration's linearisation that writes it (post_linearisation); here
+    // there is none, so the point is linearised once more -- one linearisation per limit exit, nothing on a run that a tolerance ends.  The
+    // limit keeps its precedence over the gradient tolerance (the termination stays NO_CONVERGENCE); an evaluation that fails is FAILURE.
+    if (host_iter > 0 && term == SFMBA_NO_CONVERGENCE && (msg == MSG_MAX_ITERS || msg == MSG_MAX_TIME) && state_mirrored &&
+        p->h_state->termination == -1 && p->h_state->x_is_new) {
+        // (as the max_iters = 0 branch above; build_enqueued can be set on the time limit only: the iteration limit is known when the
+        // early kernel would be enqueued)
+        launch_partial_linearisation<T>(p, 0, /*point_pass_done=*/build_enqueued);
+        launch_finalize(p->stream, p->ds, p->db, 0);
+        if ((rc = launches_ok())) return rc;
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        if ((rc = download_state(p))) return rc;
+        if (p->h_state->termination == SFMBA_FAILURE) { term = p->h_state->termination; msg = p->h_state->message; }
+    }
     // k_lm_control mirrored the LM state into the pinned block before its last mailbox post, and it is the last kernel of
     // an iteration: unless that post was missed (or events have to be collected) there is nothing to wait for or to copy
     if (!state_mirrored || p->prof.on) {

@@ -228,6 +228,7 @@ static int solve_sharded_impl(sfmba_problem* p, const sfmba_options* opt, sfmba_
         }
         ImplicitProduct ip;
         int first_build = o.jacobi_scaling ? 1 : 2;          // the first point pass also forms the point scales
+        bool limit_exit = false;         // the loop ended on the iteration or time limit, not by the device's verdict
         for (;;) {
             if (dense_pcg_ensure_workspace(&p->solver)) return fail(SFMBA_ERR_ALLOC, "PCG workspace allocation failed");
             p->db.pcg_F = p->solver.Sfull;
@@ -367,12 +368,33 @@ static int solve_sharded_impl(sfmba_problem* p, const sfmba_options* opt, sfmba_
             p->shard_sum.linear_iters += mb[4];
             if (o.verbose) std::fprintf(stderr, "[sfmba shard %d/%d] LM iteration %d: %d CG iterations (%d launched), termination %d\n", p->shard_rank, p->shard_world, mb[3], mb[4], dist_cg ? dcg_launched : 0, mb[1]);
             p->shard_host_iter = mb[3];
-            if (shard_terminated(p, mb[1], mb[2])) break;
+            if (shard_terminated(p, mb[1], mb[2])) { limit_exit = mb[1] == -1; break; }
             // one rank (the matrix-free solve of an unsharded handle): the wall-clock limit of the reference (BA.cpp:176) applies; between
             // ranks it cannot (they would disagree on it)
             if (p->shard_world == 1 && o.max_seconds > 0.0 && now_seconds() - t_shard0 >= o.max_seconds) {
                 set_termination(p->shard_sum, SFMBA_NO_CONVERGENCE, MSG_MAX_TIME);
+                limit_exit = true;
                 break;
+            }
+        }
+        if (limit_exit && p->no_pairs && !p->sharded) {
+            // The matrix-free solve of an unsharded handle (solve_matrix_free) returns a trace; the sharded entry point returns none and
+            // keeps its count, whatever the number of ranks: a run that a LIMIT ends behind an accepted step reports the gradient AT the accepted
+            // point in that step's row, and counts the evaluation, as run_solve does (lm_solve.hip) -- the point is linearised once more, up to the
+            // kernel that does the post-linearisation bookkeeping (k_pcg_glue).  The limit keeps its precedence over the gradient tolerance.
+            if ((rc = download_state(p))) return rc;
+            if (p->h_state->termination == -1 && p->h_state->x_is_new) {
+                if (!build_enqueued) with_precision(p, [&](auto t) { launch_point_build<decltype(t)>(p->stream, dsp, p->db, 0); });
+                with_precision(p, [&](auto t) { launch_cam_diag<decltype(t)>(p->stream, dsc, p->db); });
+                launch_cd_fold(p->stream, p->ds, p->db);
+                launch_shard_diag(p->stream, p->ds, p->db, p->d_red, /*unpack=*/false, p->shard_rank, p->shard_world);
+                if ((rc = reduce(p->d_red, shard_diag_len(p->ds)))) return rc;
+                launch_shard_diag(p->stream, p->ds, p->db, p->d_red, /*unpack=*/true, p->shard_rank, p->shard_world);
+                { DeviceBuffers dbf = p->db; dbf.cd_part = nullptr; launch_finalize(p->stream, p->ds, dbf, 1); }
+                launch_pcg_glue(p->stream, p->ds, p->db);
+                if ((rc = launches_ok())) return rc;
+                if ((rc = download_state(p))) return rc;
+                if (p->h_state->termination == SFMBA_FAILURE) set_termination(p->shard_sum, p->h_state->termination, p->h_state->message);
             }
         }
         if (row_cg) {
