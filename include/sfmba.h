@@ -1280,6 +1280,75 @@ SFMBA_API int sfmba_mesh_clean(int device, int64_t n_vertices, const float* xyz 
                 unsigned char* bgr_out /*[vcap][3]*/, float* normal /*[vcap][3] or NULL*/, int64_t vcap, int32_t* tri_out /*[tcap][3]*/,
                 int64_t tcap, int32_t* vertex_of /*[n_vertices] or NULL*/, int64_t* n_vertices_out, int64_t* n_triangles_out);
 
+/* ---- texturing a mesh: a view per triangle and a texture atlas of fixed-size patches (SfM::textureMesh) ---------------------------
+ * A vertex of the meshes above has one colour: the mean over all views of the pixels that fell into the two grid vertices of its
+ * edge, blurred by the voxel and by views that disagree by the depth error, and no finer than the grid.  This call puts the
+ * photographs themselves on the surface: every triangle chooses ONE view, the one that sees it largest among those that see it at
+ * all, and gets a right-angled patch of S x S texels in an atlas, filled from that view by a perspective-correct bilinear fetch.  The
+ * triangles of a grid mesh are all about the same size, so a FIXED-SIZE PATCH PER TRIANGLE is the atlas and nothing is packed.  THE
+ * CONTRACT IS OUR OWN AND EQUALS NOBODY'S, stated so that the device is held BIT FOR BIT to a CPU restatement
+ * (tests/texture_oracle.py): fp64 per element, EVERY OPERATION ROUNDED ON ITS OWN (csrc/texture_math.h switches the compiler's
+ * contraction off), and everything from the fixed-point image coordinate to the texel is integer arithmetic.  Nothing is summed
+ * across triangles or texels and there is NO ATOMIC ANYWHERE.  Below, a sum written a + b + c is ((a + b) + c).
+ *
+ * sfmba_mesh_texture
+ *   the mesh      as the mesh-cleaning calls take it: xyz, bgr (or NULL), tri.
+ *   the views     images, K, P and the depth maps exactly as sfmba_depth_fuse / sfmba_tsdf_integrate take them (the pixels are
+ *                 required; depth[i] may be NULL: such a view has no visibility test).  n_images = 0 is legal.
+ *   parameters    occl_tol >= 0 (a finite float, world units); min_area >= 0 in (1/16 px)^2, DOUBLED; the patch S in 3..64; the
+ *                 blocks per atlas row B >= 1.
+ *   layout        triangle t lives in block b = t >> 1, half t & 1.  n_blocks = ceil(n_triangles / 2); W = B (S + 1),
+ *                 H = ceil(n_blocks / B) S; both must lie in 1..16384.  With n_triangles = 0 the atlas is ONE EMPTY BLOCK, S + 1 by
+ *                 S, whatever B, and all zero.  Block b has its origin at ((b mod B)(S + 1), (b / B) S).  Half 0 owns the local
+ *                 texels (i, j), 0 <= i, j < S, i + j <= S - 1.  Half 1 is the block turned by 180 degrees: its local texel (x, y) is
+ *                 its own frame's (i, j) = (S - x, S - 1 - y).  Both halves have S (S + 1) / 2 texels and every texel of a block
+ *                 belongs to exactly one half.  The corners A, B, C of a triangle sit on the texel CENTRES (0, 0), (S - 2, 0),
+ *                 (0, S - 2) of the half's own frame; the owned texels beyond the hypotenuse and the legs are extrapolated, so a
+ *                 bilinear fetch inside the uv triangle never reads a texel of the other half (the gutter).  uv float
+ *                 [n_triangles][3][2] holds the three corners in atlas pixel units, exact values integer + 0.5, origin top-left; the
+ *                 caller normalises.  Texels that no triangle owns (the second half of the last block of an odd n_triangles, the
+ *                 blocks past n_blocks in the last row) are 0.
+ *   view choice   per triangle, views in ascending index.  A vertex X = (double) of its floats PASSES in a view iff q = R X + t (the
+ *                 fuse's rule, q_i = ((R_i0 X_0 + R_i1 X_1) + R_i2 X_2) + t_i) has q_2 > 0; u = (fx q_0) / q_2 + cx and
+ *                 v = (fy q_1) / q_2 + cy lie in [0, w - 1] and [0, h - 1] (a NaN fails); and, where the view has a map, at the pixel
+ *                 (floor(u + 0.5), floor(v + 0.5)) zs = (double)map[py][px] > 0 and (q_2 - zs) <= (double)occl_tol.  The view is a
+ *                 CANDIDATE iff all three vertices pass.  With su = floor(16 u + 0.5), sv likewise (the sweep's fixed point), the
+ *                 doubled signed image area in int64 is a2 = (suB - suA)(svC - svA) - (svB - svA)(suC - suA); for fx, fy > 0 a
+ *                 triangle whose normal (B - A) x (C - A) points towards the camera has a2 < 0 (image y runs down).  score = -a2.
+ *                 The view is ELIGIBLE iff it is a candidate, score > 0 and score >= min_area.  view[t] is the eligible view of
+ *                 largest score, the LOWEST INDEX ON A TIE, or -1; score[t] (may be NULL) is that score, or 0.  A triangle with a
+ *                 non-finite coordinate or a repeated index gets -1.  *n_textured is the number of triangles with view >= 0.
+ *   texels        per owned texel (i, j) of the half's frame: wB = i, wC = j, wA = S - 2 - i - j (the least is -1);
+ *                 X_a = (((double)wA A_a + (double)wB B_a) + (double)wC C_a) / (double)(S - 2): interpolating in 3-D makes the
+ *                 mapping perspective-correct.  With view >= 0: q, u, v as above; if q_2 > 0 and neither u nor v is a NaN, both are
+ *                 clamped into the image, su and sv are taken as above, and channel c of the texel is (s12 + 8) >> 4 with s12 the
+ *                 sweep's bilinear sample (0..4080) of that channel at (su, sv) / 16; a gray image gives g, g, g.  Otherwise, and
+ *                 for a triangle with view = -1, the texel takes the FALLBACK: per channel
+ *                 floor((2 (wA cA + wB cB + wC cC) + (S - 2)) / (2 (S - 2))) in integers, clamped to 0..255, with cA, cB, cC the
+ *                 corners' bgr -- a FLOOR division, not a truncation -- and (0, 0, 0) where bgr is NULL.
+ *   outputs       atlas uint8 [H][W][3], BGR; uv; view int32 [n_triangles]; score int64 [n_triangles] or NULL; *n_textured.
+ *   NO COLOUR ADJUSTMENT ACROSS VIEWS: SEAMS WHERE EXPOSURES DIFFER STAY VISIBLE.  NO SMOOTHING OF THE VIEW LABELS.  NO CHART
+ *   MERGING: THE ATLAS SPENDS (S + 1) S / 2 TEXELS ON EVERY TRIANGLE, HOWEVER SMALL.
+ *
+ * sfmba_mesh_texture_size
+ *   *width = W and *height = H of the layout above; SFMBA_ERR_INVALID_ARG for what the call refuses about n_triangles, S, B, W and H.
+ *
+ *   SFMBA_ERR_INVALID_ARG (nothing written): whatever the fuse refuses about images, sizes, K and P; a negative or >= 2^31 count;
+ *                 a triangle index outside 0 .. n_vertices-1 (found on the device, before anything is written); S outside 3..64;
+ *                 B < 1; W or H above 16384; occl_tol not finite or < 0; min_area < 0; a NULL atlas, uv, view or n_textured (width
+ *                 or height for the size); a NULL xyz with n_vertices > 0, tri with n_triangles > 0, depth with n_images > 0.
+ *   Host pointers in and out, synchronous, deterministic.  SFMBA_ABI_VERSION stays 6: adding symbols is backward compatible.
+ */
+SFMBA_API int sfmba_mesh_texture_size(int64_t n_triangles, int patch /*S, 3..64*/, int blocks_per_row /*B >= 1*/, int32_t* width,
+                int32_t* height);
+SFMBA_API int sfmba_mesh_texture(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, const unsigned char* bgr /*or NULL*/,
+                int64_t n_triangles, const int32_t* tri /*[n_triangles][3]*/, int n_images, const int64_t* img_ptr,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels, const float* K /*[9]*/,
+                const float* P /*[n_images][12]*/, const float* const* depth /*[n_images], each NULL or [h][w]*/, float occl_tol,
+                int64_t min_area /*in (1/16 px)^2, doubled; >= 0*/, int patch /*S, 3..64*/, int blocks_per_row /*B >= 1*/,
+                unsigned char* atlas /*[H][W][3] BGR*/, float* uv /*[n_triangles][3][2]*/, int32_t* view /*[n_triangles]*/,
+                int64_t* score /*[n_triangles] or NULL*/, int64_t* n_textured);
+
 /* ---- matching by optical flow: pyramidal Lucas-Kanade and the snap to key points (SfMFeatureMatching::createFlowMatchMatrix) -----
  * The reference's legacy tree matched video-like input without descriptors (legacy/SfMToyLib_Old/OFFeatureMatcher.cpp): it tracked
  * the key points of image i into image j with gpu::PyrLKOpticalFlow::sparse, snapped every flow end point to a key point of j

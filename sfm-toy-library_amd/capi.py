@@ -42,6 +42,7 @@ SYMBOLS = [
     "sfmba_depth_normals", "sfmba_cloud_merge", "sfmba_tsdf_integrate", "sfmba_tsdf_extract", "sfmba_tsdf_mesh",
     "sfmba_tsdf_fill", "sfmba_tsdf_mesh_fill",
     "sfmba_mesh_components", "sfmba_mesh_filter", "sfmba_mesh_smooth", "sfmba_mesh_clean",
+    "sfmba_mesh_texture_size", "sfmba_mesh_texture",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -864,6 +865,39 @@ def mesh_clean(xyz, bgr, tri, origin, quantum, min_triangles=1, keep_largest=Fal
                                       C.c_int(min_triangles), C.c_int(int(keep_largest)), _p(origin, fp), C.c_float(quantum), C.c_int(iterations),
                                       C.c_float(lam), C.c_float(mu), oxyz, obgr, onrm, vcap, otri, tcap, vof, n_v, n_t)
     return _mesh_clean_call(call, nv, bgr is not None, want_normal, want_vertex_of, vcap, tcap)
+
+
+def mesh_texture_size(n_triangles, patch=6, blocks_per_row=1):
+    """sfmba_mesh_texture_size: (W, H) of the atlas of sfmba_mesh_texture (the contract is in include/sfmba.h)."""
+    w, h = C.c_int32(0), C.c_int32(0)
+    _check(lib().sfmba_mesh_texture_size(C.c_int64(n_triangles), C.c_int(patch), C.c_int(blocks_per_row), C.byref(w), C.byref(h)))
+    return int(w.value), int(h.value)
+
+
+def mesh_texture(xyz, bgr, tri, images, K, P, depth_maps, occl_tol, min_area=0, patch=6, blocks_per_row=None, want_score=True, device=0):
+    """sfmba_mesh_texture: a view per triangle and a texture atlas with one fixed-size patch per triangle (the contract is in
+    include/sfmba.h; NO COLOUR ADJUSTMENT ACROSS VIEWS, NO SMOOTHING OF THE VIEW LABELS, NO CHART MERGING).
+
+    The mesh as mesh_clean takes it; images, K, P, depth_maps as tsdf_integrate takes them (images are required; a map may be None).
+    blocks_per_row None: ceil(sqrt(n_blocks)), at least 1.  Returns a dict: atlas uint8 [H, W, 3] (BGR), uv float32 [m, 3, 2] in atlas
+    pixels, view int32 [m], score int64 [m] or None (NULL is passed), n_textured."""
+    nv, xyz, bgr, tri = _clean_mesh(xyz, bgr, tri)
+    nt = len(tri)
+    if blocks_per_row is None:
+        blocks_per_row = max(1, int(np.ceil(np.sqrt((nt + 1) // 2))))
+        while blocks_per_row * blocks_per_row < (nt + 1) // 2:
+            blocks_per_row += 1
+    views, keep = _tsdf_views(images, K, P, depth_maps)
+    W, H = mesh_texture_size(nt, patch, blocks_per_row)
+    fp, bp, lp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte), C.POINTER(C.c_int64)
+    atlas, uv = np.zeros((H, W, 3), np.uint8), np.zeros((max(nt, 1), 3, 2), np.float32)
+    view, score = np.zeros(max(nt, 1), np.int32), np.zeros(max(nt, 1), np.int64)
+    n_textured = C.c_int64(0)
+    _check(lib().sfmba_mesh_texture(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), _opt(bgr, bp), C.c_int64(nt), _opt(tri, _ip), *views,
+                                    C.c_float(occl_tol), C.c_int64(min_area), C.c_int(patch), C.c_int(blocks_per_row), _p(atlas, bp), _p(uv, fp),
+                                    _p(view, _ip), _p(score, lp) if want_score else None, C.byref(n_textured)))
+    return {"atlas": atlas, "uv": uv[:nt].copy(), "view": view[:nt].copy(), "score": score[:nt].copy() if want_score else None,
+            "n_textured": int(n_textured.value)}
 
 
 class _ImageInfo(C.Structure):

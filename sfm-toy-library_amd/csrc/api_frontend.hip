@@ -1,5 +1,5 @@
 // api_frontend.hip -- C ABI of include/sfmba.h, the front-end entry points (everything in front of bundle adjustment: image files,
-// features, matches, RANSAC, triangulation, association, dense depth, flow, cloud merge, mesh, mesh cleaning): argument checks and dispatch.  The work
+// features, matches, RANSAC, triangulation, association, dense depth, flow, cloud merge, mesh, mesh cleaning, texturing): argument checks and dispatch.  The work
 // is in the unit each wrapper names; the error state, the device checks and the problem / solver entry points are in sfmba_api.hip.
 //
 // Every wrapper reads: checks, open, call, timing line, mapped result.  Every check comes before the first write: a refused call
@@ -18,6 +18,8 @@
 #include "mesh_clean.h"
 #include "mesh_clean_math.h"
 #include "mesh_math.h"
+#include "mesh_texture.h"
+#include "texture_math.h"
 #include "orb_extract.h"
 #include "png_decode.h"
 #include "pnp_ransac.h"
@@ -305,6 +307,16 @@ void clean_timing_line(const char* what, const double* t, long long nv, long lon
                  "download_ms %.6f vertices %lld triangles %lld vertices_out %lld triangles_out %lld\n",
                  what, t[CLEAN_T_UPLOAD], t[CLEAN_T_CHECK], t[CLEAN_T_COMPONENTS], t[CLEAN_T_FILTER], t[CLEAN_T_QUANTISE], t[CLEAN_T_SMOOTH],
                  t[CLEAN_T_NORMALS], t[CLEAN_T_DOWNLOAD], nv, nt, nv_out, nt_out);
+}
+// what the two texturing calls refuse about the layout; W and H of the atlas
+int texture_check_layout(const char* who, int64_t n_triangles, int patch, int blocks_per_row, long long& W, long long& H) {
+    const std::string w(who);
+    if (n_triangles < 0 || n_triangles > (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, w + ": n_triangles must lie in 0 .. 2^31 - 1");
+    if (patch < TEX_MIN_PATCH || patch > TEX_MAX_PATCH) return fail(SFMBA_ERR_INVALID_ARG, w + ": patch must be in 3..64");
+    if (blocks_per_row < 1) return fail(SFMBA_ERR_INVALID_ARG, w + ": blocks_per_row must be >= 1");
+    if (!tex_atlas_size((long long)n_triangles, patch, blocks_per_row, W, H))
+        return fail(SFMBA_ERR_INVALID_ARG, w + ": the atlas has a side above 16384");
+    return 0;
 }
 }  // namespace
 
@@ -796,6 +808,41 @@ int sfmba_mesh_clean(int device, int64_t n_vertices, const float* xyz, const uns
     if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on)
         clean_timing_line("mesh_clean", c.t, n_vertices, n_triangles, (long long)*n_vertices_out, (long long)*n_triangles_out);
     return clean_result(rc, "mesh_clean");
+}
+// ---- texturing a mesh: a view per triangle and a texture atlas (SfM::textureMesh) -------------------------------------------------
+int sfmba_mesh_texture_size(int64_t n_triangles, int patch, int blocks_per_row, int32_t* width, int32_t* height) {
+    if (!width || !height) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    long long W, H;
+    if (const int rc = texture_check_layout("mesh_texture_size", n_triangles, patch, blocks_per_row, W, H)) return rc;
+    *width = (int32_t)W;
+    *height = (int32_t)H;
+    return SFMBA_OK;
+}
+int sfmba_mesh_texture(int device, int64_t n_vertices, const float* xyz, const unsigned char* bgr, int64_t n_triangles, const int32_t* tri,
+                       int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels,
+                       const float* K, const float* P, const float* const* depth, float occl_tol, int64_t min_area, int patch, int blocks_per_row,
+                       unsigned char* atlas, float* uv, int32_t* view, int64_t* score, int64_t* n_textured) {
+    if (const int rc = clean_check_mesh("mesh_texture", n_vertices, xyz, true, n_triangles, tri)) return rc;
+    if (!atlas || !uv || !view || !n_textured || (n_images > 0 && !depth)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (const int rc = depth_check_images("mesh_texture", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    if (!std::isfinite(occl_tol) || occl_tol < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "mesh_texture: occl_tol must be finite and >= 0");
+    if (min_area < 0) return fail(SFMBA_ERR_INVALID_ARG, "mesh_texture: min_area must be >= 0");
+    long long W, H;
+    if (const int rc = texture_check_layout("mesh_texture", n_triangles, patch, blocks_per_row, W, H)) return rc;
+    const TexMesh m{ (int)n_vertices, (int)n_triangles, xyz, bgr, tri };
+    const TexViews views{ n_images, img_ptr, pixels, width, height, channels, K, P, depth };
+    const TexParams prm{ occl_tol, min_area, patch, blocks_per_row, (int)W, (int)H };
+    const TexOut out{ atlas, uv, view, score, n_textured };
+    TimedCall<TEX_T_COUNT> c("SFMBA_MESH_TEXTURE_TIMING");       // (tools/texture_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_texture(c.kit.stream, device, m, views, prm, out, c.tm());
+    if (rc == 0 && c.on)
+        std::fprintf(stderr, "[sfmba mesh_texture] upload_ms %.6f check_ms %.6f views_ms %.6f raster_ms %.6f download_ms %.6f vertices %lld "
+                             "triangles %lld images %d width %lld height %lld textured %lld\n",
+                     c.t[TEX_T_UPLOAD], c.t[TEX_T_CHECK], c.t[TEX_T_VIEWS], c.t[TEX_T_RASTER], c.t[TEX_T_DOWNLOAD], (long long)n_vertices,
+                     (long long)n_triangles, n_images, W, H, (long long)*n_textured);
+    if (rc == TEX_ERR_INDEX) return fail(SFMBA_ERR_INVALID_ARG, "mesh_texture: a triangle index lies outside the vertex list");
+    return unit_result(rc, "mesh_texture");
 }
 // ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------
 int sfmba_pnp_ransac(int device, int n_prob, const int64_t* prob_ptr, const float* xyz, const float* uv, const float* K, int n_hyp,

@@ -98,12 +98,15 @@ DEPTH_HD int depth_fix(double c) {
     return (int)floor(c16 + 0.5);
 }
 // the bilinear sample at (su, sv) / 16 of a gray image, a 12-bit integer 0..4080
-DEPTH_HD int depth_sample(const unsigned char* img, int ws, int hs, int su, int sv) {
+// (`img` is the first byte of one channel of an image whose pixels lie `channels` bytes apart)
+DEPTH_HD int depth_sample_channel(const unsigned char* img, int ws, int hs, int su, int sv, int channels) {
     const int x0 = su >> 4, fx = su & 15, y0 = sv >> 4, fy = sv & 15;
     const int x1 = x0 + 1 < ws - 1 ? x0 + 1 : ws - 1, y1 = y0 + 1 < hs - 1 ? y0 + 1 : hs - 1;
-    const unsigned char *r0 = img + (size_t)y0 * (size_t)ws, *r1 = img + (size_t)y1 * (size_t)ws;
-    return ((16 - fx) * (16 - fy) * (int)r0[x0] + fx * (16 - fy) * (int)r0[x1] + (16 - fx) * fy * (int)r1[x0] + fx * fy * (int)r1[x1] + 8) >> 4;
+    const size_t c = (size_t)channels;
+    const unsigned char *r0 = img + (size_t)y0 * (size_t)ws * c, *r1 = img + (size_t)y1 * (size_t)ws * c;
+    return ((16 - fx) * (16 - fy) * (int)r0[x0 * c] + fx * (16 - fy) * (int)r0[x1 * c] + (16 - fx) * fy * (int)r1[x0 * c] + fx * fy * (int)r1[x1 * c] + 8) >> 4;
 }
+DEPTH_HD int depth_sample(const unsigned char* img, int ws, int hs, int su, int sv) { return depth_sample_channel(img, ws, hs, su, sv, 1); }
 // DEPTH_NO_SAMPLE or the sample of source pixels `img` for reference pixel (u, v) on the plane of inverse depth w
 DEPTH_HD int depth_warped_sample(const double* A, const double* b, int u, int v, double w, const unsigned char* img, int ws, int hs) {
     double up, vp;
@@ -154,21 +157,32 @@ DEPTH_HD void depth_unproject(const double* k4, const double* p, int u, int v, d
         X[j] = s;
     }
 }
-// q = R X + t as (((R_i0 X_0) + R_i1 X_1) + R_i2 X_2) + t_i; false unless q_z > 0 and the pixel (floor((fx q_x / q_z + cx) + 0.5),
-// floor((fy q_y / q_z + cy) + 0.5)) lies inside the ws x hs image
-DEPTH_HD bool depth_reproject(const double* k4, const double* p, const double* X, int ws, int hs, int& px, int& py, double& qz) {
+// q = R X + t as (((R_i0 X_0) + R_i1 X_1) + R_i2 X_2) + t_i
+DEPTH_HD void depth_camera_point(const double* p, const double* X, double* q) {
 #pragma clang fp contract(off)
-    double q[3];
     for (int i = 0; i < 3; ++i) {
         double s = p[4 * i] * X[0];
         s = s + p[4 * i + 1] * X[1];
         s = s + p[4 * i + 2] * X[2];
         q[i] = s + p[4 * i + 3];
     }
+}
+// u = (fx q_x) / q_z + cx, v = (fy q_y) / q_z + cy
+DEPTH_HD void depth_image_point(const double* k4, const double* q, double& u, double& v) {
+#pragma clang fp contract(off)
+    const double fu = k4[0] * q[0], fv = k4[1] * q[1];
+    u = fu / q[2] + k4[2];
+    v = fv / q[2] + k4[3];
+}
+// false unless q_z > 0 and the pixel (floor(u + 0.5), floor(v + 0.5)) of the two functions above lies inside the ws x hs image
+DEPTH_HD bool depth_reproject(const double* k4, const double* p, const double* X, int ws, int hs, int& px, int& py, double& qz) {
+#pragma clang fp contract(off)
+    double q[3], u, v;
+    depth_camera_point(p, X, q);
     qz = q[2];
     if (!(q[2] > 0.0)) return false;
-    const double fu = k4[0] * q[0], fv = k4[1] * q[1];
-    const double x = floor((fu / q[2] + k4[2]) + 0.5), y = floor((fv / q[2] + k4[3]) + 0.5);
+    depth_image_point(k4, q, u, v);
+    const double x = floor(u + 0.5), y = floor(v + 0.5);
     if (!(x >= 0.0 && x <= (double)(ws - 1) && y >= 0.0 && y <= (double)(hs - 1))) return false;
     px = (int)x;
     py = (int)y;

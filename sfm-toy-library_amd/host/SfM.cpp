@@ -19,6 +19,7 @@
 #include "SfMExport.h"
 #include "SfMImageUtilities.h"
 #include "SfMStereoUtilities.h"
+#include "../csrc/png_inflate.h"        // the CRC-32 and the Adler-32 of the PNG reader, for the atlas writer
 
 namespace sfmtoylib {
 
@@ -95,6 +96,7 @@ SfM::SfM(const float downscale) :
         mDownscaleApplied(false),
         mCols(0), mRows(0),
         mMeshOkay(false),
+        mCleanOkay(false),
         mRunOkay(false),
         mTiming(false) {
     for (double& ms : mStageMs) ms = 0.0;
@@ -213,6 +215,8 @@ void SfM::startRun(size_t n_views) {
     mMergedCloud = MergedCloud();
     mMesh = Mesh();
     mCleanMesh = Mesh();
+    mTexturedMesh = TexturedMesh();
+    mCleanOkay = false;
     mMeshOkay = false;
     mDenseJobs.clear();
     mRunOkay = false;
@@ -431,6 +435,8 @@ ErrorCode SfM::densify(const DenseParams& params) {
     mMergedCloud = MergedCloud();
     mMesh = Mesh();
     mCleanMesh = Mesh();
+    mTexturedMesh = TexturedMesh();
+    mCleanOkay = false;
     mMeshOkay = false;
     mDenseJobs.clear();
     if (mFeaturesGiven || mImages.empty()) {
@@ -619,6 +625,8 @@ bool SfM::saveMergedDenseCloudToPLY(const std::string& prefix) {
 ErrorCode SfM::meshDenseCloud(const MeshParams& params) {
     mMesh = Mesh();
     mCleanMesh = Mesh();
+    mTexturedMesh = TexturedMesh();
+    mCleanOkay = false;
     mMeshOkay = false;
     if (mDenseJobs.empty() || mDepthMaps.size() != mImages.size()) {
         std::cerr << "meshDenseCloud: needs a densify on these images that returned OKAY" << std::endl;
@@ -730,6 +738,8 @@ bool SfM::saveMeshToPLY(const std::string& prefix) {
 
 ErrorCode SfM::cleanMesh(const MeshCleanParams& params) {
     mCleanMesh = Mesh();
+    mTexturedMesh = TexturedMesh();
+    mCleanOkay = false;
     if (!mMeshOkay) {
         std::cerr << "cleanMesh: needs a meshDenseCloud that returned OKAY" << std::endl;
         return ERROR;
@@ -744,6 +754,7 @@ ErrorCode SfM::cleanMesh(const MeshCleanParams& params) {
     }
     if (!ok) return ERROR;
     mCleanMesh = mesh;
+    mCleanOkay = true;
     say(LOG_INFO, "clean mesh: " + std::to_string(mCleanMesh.vertices.size()) + " of " + std::to_string(mMesh.vertices.size()) + " vertices, " +
                       std::to_string(mCleanMesh.triangles.size() / 3) + " of " + std::to_string(mMesh.triangles.size() / 3) + " triangles");
     if (timing)
@@ -787,6 +798,109 @@ bool SfM::saveCleanMeshToPLY(const std::string& prefix) {
         file << "3 " << m.triangles[t] << " " << m.triangles[t + 1] << " " << m.triangles[t + 2] << std::endl;
     file.close();
     return !file.fail();
+}
+
+ErrorCode SfM::textureMesh(const TextureParams& params) {
+    mTexturedMesh = TexturedMesh();
+    if (!mMeshOkay) {
+        std::cerr << "textureMesh: needs a meshDenseCloud that returned OKAY" << std::endl;
+        return ERROR;
+    }
+    if (!std::isfinite(params.occlTolVoxels) || params.occlTolVoxels < 0.0f) {
+        std::cerr << "textureMesh: occlTolVoxels must be finite and >= 0" << std::endl;
+        return ERROR;
+    }
+    const Mesh& source = mCleanOkay ? mCleanMesh : mMesh;
+    const bool timing = std::getenv("SFMBA_SFM_TIMING") != nullptr;
+    double ms[1] = { 0.0 };
+    bool ok = true;
+    TexturedMesh textured;
+    {
+        StageClock clock(timing ? ms : nullptr, 0);
+        textured = SfMDenseUtilities::textureMesh(source, mImages, mIntrinsics, mCameraPoses, mDepthMaps, params, &ok);
+    }
+    if (!ok) return ERROR;
+    mTexturedMesh = textured;
+    say(LOG_INFO, "textured mesh: " + std::to_string(mTexturedMesh.textured) + " of " + std::to_string(mTexturedMesh.triangles.size() / 3) +
+                      " triangles have a view (" + (mCleanOkay ? "the clean mesh" : "the mesh") + "), atlas " + std::to_string(mTexturedMesh.atlas.cols) +
+                      " x " + std::to_string(mTexturedMesh.atlas.rows));
+    if (timing)
+        std::fprintf(stderr, "[sfmba sfm mesh_texture] texture_ms %.3f triangles %lld textured %lld width %d height %d\n", ms[0],
+                     (long long)(mTexturedMesh.triangles.size() / 3), mTexturedMesh.textured, mTexturedMesh.atlas.cols, mTexturedMesh.atlas.rows);
+    return OKAY;
+}
+
+const TexturedMesh& SfM::getTexturedMesh() const { return mTexturedMesh; }
+
+namespace {
+void be32(std::vector<unsigned char>& out, uint32_t v) {
+    for (int s = 24; s >= 0; s -= 8) out.push_back((unsigned char)(v >> s));
+}
+void pngChunk(std::vector<unsigned char>& file, const char* type, const std::vector<unsigned char>& data) {
+    be32(file, (uint32_t)data.size());
+    const size_t at = file.size();
+    file.insert(file.end(), type, type + 4);
+    file.insert(file.end(), data.begin(), data.end());
+    be32(file, sfmba::png_crc32(file.data() + at, data.size() + 4));
+}
+// a BGR image as an 8-bit RGB PNG: filter 0 on every row, the zlib stream made of STORED blocks (no compression), one IDAT chunk
+bool writeStoredPNG(const std::string& path, const cv::Mat& bgr) {
+    const size_t w = (size_t)bgr.cols, h = (size_t)bgr.rows;
+    std::vector<unsigned char> raw;
+    raw.reserve(h * (1 + 3 * w));
+    for (size_t y = 0; y < h; ++y) {
+        const unsigned char* row = bgr.ptr<unsigned char>((int)y);
+        raw.push_back(0);
+        for (size_t x = 0; x < w; ++x)
+            for (int c = 2; c >= 0; --c) raw.push_back(row[3 * x + c]);
+    }
+    std::vector<unsigned char> z;
+    z.reserve(raw.size() + 5 * (raw.size() / 65535 + 1) + 6);
+    z.push_back(0x78);
+    z.push_back(0x01);
+    for (size_t at = 0; at < raw.size(); at += 65535) {               // (an atlas has at least one row, so there is at least one block)
+        const size_t n = std::min<size_t>(65535, raw.size() - at);
+        z.push_back(at + n >= raw.size() ? 1 : 0);
+        z.push_back((unsigned char)(n & 255)); z.push_back((unsigned char)(n >> 8));
+        z.push_back((unsigned char)(~n & 255)); z.push_back((unsigned char)((~n >> 8) & 255));
+        z.insert(z.end(), raw.begin() + (std::ptrdiff_t)at, raw.begin() + (std::ptrdiff_t)(at + n));
+    }
+    be32(z, sfmba::png_adler32(raw.data(), raw.size()));
+    std::vector<unsigned char> file = { 0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n' }, ihdr;
+    be32(ihdr, (uint32_t)w);
+    be32(ihdr, (uint32_t)h);
+    const unsigned char kind[5] = { 8, 2, 0, 0, 0 };             // 8 bits, RGB, deflate, adaptive filters, no interlace
+    ihdr.insert(ihdr.end(), kind, kind + 5);
+    pngChunk(file, "IHDR", ihdr);
+    pngChunk(file, "IDAT", z);
+    pngChunk(file, "IEND", std::vector<unsigned char>());
+    std::ofstream out(path, std::ios::binary);
+    out.write(reinterpret_cast<const char*>(file.data()), (std::streamsize)file.size());
+    out.close();
+    return !out.fail();
+}
+}  // namespace
+
+bool SfM::saveTexturedMeshToOBJ(const std::string& prefix) {
+    const TexturedMesh& m = mTexturedMesh;
+    if (m.atlas.empty() || m.uv.size() != 2 * m.triangles.size()) return false;
+    const std::string base = prefix.substr(prefix.find_last_of('/') == std::string::npos ? 0 : prefix.find_last_of('/') + 1);
+    if (!writeStoredPNG(prefix + "_textured.png", m.atlas)) return false;
+    std::ofstream mtl(prefix + "_textured.mtl");
+    mtl << "newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd " << base << "_textured.png\n";
+    mtl.close();
+    if (mtl.fail()) return false;
+    FILE* obj = std::fopen((prefix + "_textured.obj").c_str(), "w");
+    if (!obj) return false;
+    std::fprintf(obj, "mtllib %s_textured.mtl\nusemtl atlas\n", base.c_str());
+    for (const cv::Point3f& p : m.vertices) std::fprintf(obj, "v %.9g %.9g %.9g\n", (double)p.x, (double)p.y, (double)p.z);
+    const double W = (double)m.atlas.cols, H = (double)m.atlas.rows;
+    for (size_t q = 0; q + 1 < m.uv.size(); q += 2) std::fprintf(obj, "vt %.9g %.9g\n", (double)m.uv[q] / W, 1.0 - (double)m.uv[q + 1] / H);
+    for (size_t t = 0; t + 2 < m.triangles.size(); t += 3)
+        std::fprintf(obj, "f %d/%lld %d/%lld %d/%lld\n", m.triangles[t] + 1, (long long)t + 1, m.triangles[t + 1] + 1, (long long)t + 2, m.triangles[t + 2] + 1,
+                     (long long)t + 3);
+    const bool bad = std::ferror(obj) != 0;
+    return std::fclose(obj) == 0 && !bad;
 }
 
 bool SfM::saveCloudAndCamerasToPLY(const std::string& prefix) {

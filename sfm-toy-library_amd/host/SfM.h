@@ -84,6 +84,16 @@
 //                 minComponentTriangles == 0 means max(1, triangles / 1000) (integer division).  These defaults, and lambda 0.5 /
 //                 mu -0.53 (Taubin's usual pair) at 10 iterations, are first choices like the ones above: nobody has tuned them.
 //                 The mesh of meshDenseCloud, the dense cloud and the depth maps are not changed.
+//   texture       textureMesh(params) after a meshDenseCloud that returned OKAY: ONE sfmba_mesh_texture call (include/sfmba.h) over
+//                 the clean mesh when cleanMesh has returned OKAY since, otherwise over the mesh, with all images, the poses and the
+//                 depth maps: every triangle takes the view that sees it largest among those that see all three vertices
+//                 unoccluded, and a patch of S (S + 1) / 2 texels in an atlas, filled from that view perspective-correctly; a
+//                 triangle no view sees keeps its blended vertex colours.  THE HOST RULES: patch S = 6; blocksPerRow 0 means
+//                 B = ceil(sqrt(ceil(triangles / 2))), at least 1 (a square atlas); occl_tol = occlTolVoxels * the grid's voxel
+//                 (float), occlTolVoxels default 2; min_area = round(2 * 256 * minAreaPx), minAreaPx default 0.5.  These are first
+//                 choices that NOBODY HAS TUNED.  NO COLOUR ADJUSTMENT ACROSS VIEWS (seams where exposures differ stay visible), NO
+//                 SMOOTHING OF THE VIEW LABELS, NO CHART MERGING (every triangle costs (S + 1) S / 2 texels, however small).  The
+//                 mesh, the clean mesh, the dense cloud and the depth maps are not changed.
 // There is no visual debugging.
 // An object holds all of a run's state (the stage times of SFMBA_SFM_TIMING included): different objects may run in different
 // threads; one object is not re-entrant.
@@ -228,6 +238,22 @@ public:
      */
     bool saveCleanMeshToPLY(const std::string& prefix);
 
+    /**
+     * The photographs on the mesh: a view per triangle and a texture atlas (the contract is at the top of this file).  Valid after a
+     * meshDenseCloud that returned OKAY; works on the clean mesh when cleanMesh has returned OKAY since, otherwise on the mesh; cleared
+     * wherever those are cleared.  ONE C-ABI call.  With SFMBA_SFM_TIMING set, one stderr line reports texture_ms.
+     * @return ERROR (no textured mesh kept) without such a meshDenseCloud, or when the device call fails or refuses (patch outside
+     *         3..64, an atlas side above 16384, occlTolVoxels or minAreaPx negative or not finite).
+     */
+    ErrorCode textureMesh(const TextureParams& params = TextureParams());
+
+    /**
+     * <prefix>_textured.obj (v, then three vt per triangle: u / W and 1 - v / H, printed with %.9g, then f a/1 b/2 c/3 ...),
+     * <prefix>_textured.mtl (one material whose map_Kd names the PNG) and <prefix>_textured.png (the atlas, 8-bit RGB, filter 0 on
+     * every row, STORED deflate blocks: NO COMPRESSION).
+     */
+    bool saveTexturedMeshToOBJ(const std::string& prefix);
+
     void setConsoleDebugLevel(unsigned int consoleDebugLevel) { mConsoleDebugLevel = consoleDebugLevel < (unsigned int)LOG_ERROR ? consoleDebugLevel : (unsigned int)LOG_ERROR; }
 
     const std::vector<cv::Mat>&     getImages() const { return mImages; }
@@ -244,6 +270,7 @@ public:
     const MergedCloud&              getMergedDenseCloud() const { return mMergedCloud; }
     const Mesh&                     getMesh() const;                                  // of the last meshDenseCloud; empty without one
     const Mesh&                     getCleanMesh() const;                             // of the last cleanMesh; empty without one
+    const TexturedMesh&             getTexturedMesh() const;                          // of the last textureMesh; empty without one
 
 private:
     enum { T_EXTRACT, T_MATCH, T_RANK, T_BASELINE_POSE, T_BASELINE_TRIANGULATE, T_ASSOCIATE, T_PNP, T_PAIR_POSES, T_TRIANGULATE, T_MERGE,
@@ -281,7 +308,9 @@ private:
     MergedCloud               mMergedCloud;
     Mesh                      mMesh;
     Mesh                      mCleanMesh;
+    TexturedMesh              mTexturedMesh;
     bool                      mMeshOkay;        // the last meshDenseCloud returned OKAY and nothing was set since
+    bool                      mCleanOkay;       // a cleanMesh returned OKAY since that meshDenseCloud
     bool                      mRunOkay;         // the last runSfM returned OKAY and nothing was set since
     bool                      mTiming;           // SFMBA_SFM_TIMING was set when the run began
     double                    mStageMs[T_COUNT]; // wall time per stage of the current run (all zero unless mTiming)

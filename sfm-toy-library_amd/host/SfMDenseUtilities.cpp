@@ -3,6 +3,7 @@
 #include "SfMDenseUtilities.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -457,6 +458,56 @@ Mesh SfMDenseUtilities::cleanMesh(const Mesh& mesh, const MeshCleanParams& param
     }, out);
     if (!done) return Mesh();
     out.normals.assign(normal.begin(), normal.begin() + 3 * out.vertices.size());
+    if (ok) *ok = true;
+    return out;
+}
+
+TexturedMesh SfMDenseUtilities::textureMesh(const Mesh& mesh, const std::vector<cv::Mat>& images, const Intrinsics& intrinsics,
+                                            const std::vector<cv::Matx34f>& poses, const std::vector<cv::Mat>& depthMaps, const TextureParams& params,
+                                            bool* ok) {
+    if (ok) *ok = false;
+    std::vector<float> xyz;
+    FlatScene f;
+    std::vector<const float*> maps;
+    if (!flattenMesh("textureMesh", mesh, xyz)) return TexturedMesh();
+    if (!flattenScene(images, intrinsics, poses, f) || depthMaps.size() != images.size()) {
+        std::fprintf(stderr, "textureMesh: one pose and one depth map (or an empty Mat) per image are needed\n");
+        return TexturedMesh();
+    }
+    if (!mapPointers("textureMesh", images, depthMaps, maps)) return TexturedMesh();
+    if (!std::isfinite(params.minAreaPx) || params.minAreaPx < 0.0f || params.minAreaPx > 1.0e9f || params.blocksPerRow < 0) {
+        std::fprintf(stderr, "textureMesh: minAreaPx must be finite and in 0..1e9, blocksPerRow >= 0 (0 = a square atlas)\n");
+        return TexturedMesh();
+    }
+    const int64_t nv = (int64_t)mesh.vertices.size(), nt = (int64_t)(mesh.triangles.size() / 3);
+    // the host rules (SfM.h)
+    int B = params.blocksPerRow;
+    if (B == 0)
+        for (B = 1; (int64_t)B * B < (nt + 1) / 2; ++B) {}
+    const float occlTol = params.occlTolVoxels * mesh.grid.voxel;
+    const int64_t minArea = (int64_t)std::llround(2.0 * 256.0 * (double)params.minAreaPx);
+    // the atlas of include/sfmba.h's layout (an empty mesh has one empty block); a layout the call refuses gets no atlas: the call
+    // refuses before it writes
+    const int64_t S = params.patch, blocks = (nt + 1) / 2;
+    const int64_t W = blocks ? B * (S + 1) : S + 1, H = blocks ? ((blocks + B - 1) / B) * S : S;
+    const bool sized = S >= 3 && S <= 64 && W <= 16384 && H <= 16384;
+    TexturedMesh out;
+    out.atlas = sized ? cv::Mat((int)H, (int)W, CV_8UC3) : cv::Mat(1, 1, CV_8UC3);
+    out.uv.resize((size_t)nt * 6 + 1);
+    std::vector<int32_t> view((size_t)nt + 1);
+    int64_t textured = 0;
+    const int rc = sfmba_mesh_texture(0, nv, xyz.data(), mesh.bgr.empty() ? nullptr : mesh.bgr.data(), nt, mesh.triangles.data(), (int)images.size(), f.ptr.data(),
+                            f.px.data(), f.w.data(), f.h.data(), f.channels, f.K, f.P.data(), maps.data(), occlTol, minArea, params.patch, B,
+                                      out.atlas.ptr<unsigned char>(0), out.uv.data(), view.data(), nullptr, &textured);
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "textureMesh failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return TexturedMesh();
+    }
+    out.vertices = mesh.vertices;
+    out.triangles = mesh.triangles;
+    out.uv.resize((size_t)nt * 6);
+    out.view.assign(view.begin(), view.begin() + nt);
+    out.textured = (long long)textured;
     if (ok) *ok = true;
     return out;
 }

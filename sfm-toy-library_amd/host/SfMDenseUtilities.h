@@ -104,6 +104,29 @@ struct MeshCleanParams {
     MeshCleanParams() : minComponentTriangles(0), keepLargest(false), smoothIterations(10), lambda(0.5f), mu(-0.53f) {}
 };
 
+// SfMDenseUtilities::textureMesh / SfM::textureMesh: the size of a triangle's patch and which views count (include/sfmba.h,
+// sfmba_mesh_texture; the host rules are at the top of SfM.h).  First choices; NOBODY HAS TUNED THEM.
+struct TextureParams {
+    int   patch;            // S: a triangle gets S (S + 1) / 2 texels, 3..64
+    int   blocksPerRow;     // B: blocks (pairs of triangles) per atlas row; 0 = ceil(sqrt(blocks)), at least 1
+    float occlTolVoxels;    // a vertex may lie this many voxels of the mesh's grid behind a view's depth map
+    float minAreaPx;        // a view counts for a triangle from this image area, in square pixels
+    TextureParams() : patch(6), blocksPerRow(0), occlTolVoxels(2.0f), minAreaPx(0.5f) {}
+};
+
+// A mesh that carries the photographs: triangle t has the corners uv[6 t .. 6 t + 5] (u, v per corner, in atlas pixels, origin top-left)
+// in the atlas and took its texels from view[t] (-1: none saw it; its patch holds the blended vertex colours).  NO COLOUR ADJUSTMENT
+// ACROSS VIEWS, NO SMOOTHING OF THE VIEW LABELS, NO CHART MERGING (include/sfmba.h).
+struct TexturedMesh {
+    Points3f           vertices;
+    std::vector<int>   triangles;  // 3 vertex indices per triangle
+    std::vector<float> uv;         // 6 per triangle
+    std::vector<int>   view;       // 1 per triangle
+    cv::Mat            atlas;      // CV_8UC3, BGR
+    long long          textured;   // triangles with a view
+    TexturedMesh() : textured(0) {}
+};
+
 class SfMDenseUtilities {
 public:
     /**
@@ -193,6 +216,17 @@ public:
      * @param ok  if not null, receives false when the device call fails or refuses an argument (the mesh is then empty).
      */
     static Mesh cleanMesh(const Mesh& mesh, const MeshCleanParams& params, bool* ok = nullptr);
+
+    /**
+     * A view per triangle and a texture atlas with one patch per triangle: ONE sfmba_mesh_texture call.  images, poses and depthMaps as
+     * fuseDepthMaps takes them (a view without a map has no visibility test).  THE HOST RULES: B = params.blocksPerRow, or
+     * ceil(sqrt(ceil(triangles / 2))) (at least 1) when that is 0; occl_tol = params.occlTolVoxels * mesh.grid.voxel (float);
+     * min_area = round(2 * 256 * params.minAreaPx).
+     * @param ok  if not null, receives false when the device call fails or refuses an argument (the result is then empty).
+     */
+    static TexturedMesh textureMesh(const Mesh& mesh, const std::vector<cv::Mat>& images, const Intrinsics& intrinsics,
+                                    const std::vector<cv::Matx34f>& poses, const std::vector<cv::Mat>& depthMaps, const TextureParams& params,
+                                    bool* ok = nullptr);
 };
 
 }  // namespace sfmtoylib

@@ -2,7 +2,8 @@
 // directory, run the pipeline on the MI355X (-M flow: with the optical-flow matcher), write <prefix>_points.ply and <prefix>_cameras.ply -- and, with -D, densify and write
 // <prefix>_dense.ply; with --voxel on top of -D, merge that cloud and write <prefix>_dense_merged.ply; with --mesh on top of -D, mesh
 // the depth maps and write <prefix>_mesh.ply (--mesh-fill N: with the grid's holes filled by N passes first); with --mesh-clean on top of --mesh, drop the mesh's small components, smooth it and write
-// <prefix>_mesh_clean.ply.  The arguments are parsed here
+// <prefix>_mesh_clean.ply; with --texture on top of --mesh, put the photographs on the mesh (the clean one with --mesh-clean) and write
+// <prefix>_textured.obj, .mtl and .png.  The arguments are parsed here
 // (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +43,9 @@ void usage(std::ostream& os, const char* program) {
        << "                               mesh's triangles, at least 1)\n"
        << "      --mesh-keep-largest      with --mesh-clean: keep only the component with the most triangles\n"
        << "      --mesh-smooth ITERS      with --mesh-clean: smoothing iterations, 0..100 (default 10)\n"
+       << "      --texture [S]            with --mesh: also choose a view per triangle, fill a texture atlas with a patch of S (S + 1) / 2 texels\n"
+       << "                               per triangle (S in 3..64, default 6) and write PREFIX_textured.obj, .mtl and .png (the clean mesh\n"
+       << "                               with --mesh-clean); NO COLOUR ADJUSTMENT ACROSS VIEWS; the other files are as without it\n"
        << "  -v, --visual-debug N         accepted and ignored: there is no visual debugging\n";
 }
 
@@ -67,11 +71,11 @@ bool number(const std::string& text, double& value) {
 int main(int argc, char** argv) {
     std::string directory, prefix = "output", text;
     double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0, voxel = 0.0, resolution = 256.0,
-           min_component = 0.0, smooth = 10.0, fill = 0.0, fill_neighbours = 2.0;
+           min_component = 0.0, smooth = 10.0, fill = 0.0, fill_neighbours = 2.0, patch = 6.0;
     FeatureType features = FEATURES_ORB;
     MatcherType matcher = MATCHER_DESCRIPTORS;
     bool have_directory = false, dense = false, merged = false, meshed = false, cleaned = false, clean_option = false, keep_largest = false,
-         filled = false, fill_option = false;
+         filled = false, fill_option = false, textured = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
         const std::string arg = argv[i];
@@ -79,6 +83,19 @@ int main(int argc, char** argv) {
         if (arg == "-D" || arg == "--dense") { dense = true; continue; }
         if (arg == "--mesh-clean") { cleaned = true; continue; }
         if (arg == "--mesh-keep-largest") { keep_largest = clean_option = true; continue; }
+        if (arg == "--texture" || arg.compare(0, 10, "--texture=") == 0) {
+            // the value is optional: "--texture=S", or a next argument made of digits only
+            textured = true;
+            text = arg.size() > 10 ? arg.substr(10) : "";
+            if (arg == "--texture" && i + 1 < argc && argv[i + 1][0] != '\0' && std::string(argv[i + 1]).find_first_not_of("0123456789") == std::string::npos)
+                text = argv[++i];
+            else if (arg == "--texture")
+                continue;
+            if (!number(text, patch) || !(patch >= 3.0) || !(patch <= 64.0) || patch != (double)(int)patch) {
+                std::cerr << argv[0] << ": --texture has a value that cannot be used\n"; usage(std::cerr, argv[0]); return 2;
+            }
+            continue;
+        }
         if (option(argc, argv, i, "-p", "--input-directory", text, missing)) { directory = text; have_directory = !missing; }
         else if (option(argc, argv, i, "-o", "--output-prefix", text, missing)) prefix = text;
         else if (option(argc, argv, i, "-s", "--downscale", text, missing)) bad = !missing && (!number(text, downscale) || !(downscale > 0.0));
@@ -130,6 +147,7 @@ int main(int argc, char** argv) {
     if (fill_option && !filled) { std::cerr << argv[0] << ": --mesh-fill-neighbours needs --mesh-fill\n"; usage(std::cerr, argv[0]); return 2; }
     if (cleaned && !meshed) { std::cerr << argv[0] << ": --mesh-clean needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
     if (clean_option && !cleaned) { std::cerr << argv[0] << ": --mesh-min-component, --mesh-keep-largest and --mesh-smooth need --mesh-clean\n"; usage(std::cerr, argv[0]); return 2; }
+    if (textured && !meshed) { std::cerr << argv[0] << ": --texture needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
     if (!have_directory || directory.empty()) { std::cerr << argv[0] << ": no input directory\n"; usage(std::cerr, argv[0]); return 2; }
 
     SfM sfm((float)downscale);
@@ -162,6 +180,12 @@ int main(int argc, char** argv) {
             clean.smoothIterations = (int)smooth;
             if (sfm.cleanMesh(clean) != OKAY) return 1;
             if (!sfm.saveCleanMeshToPLY(prefix)) return 1;
+        }
+        if (textured) {
+            TextureParams texture;
+            texture.patch = (int)patch;
+            if (sfm.textureMesh(texture) != OKAY) return 1;
+            if (!sfm.saveTexturedMeshToOBJ(prefix)) return 1;
         }
     }
     return 0;

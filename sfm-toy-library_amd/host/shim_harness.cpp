@@ -1038,6 +1038,118 @@ int sfmba_shim_run_sfm_mesh_clean(int what, int n_views, int channels, const int
     return 0;
 }
 
+// setImages, runSfM, densify(), meshDenseCloud() with its defaults, textureMesh({patch}) on the mesh, cleanMesh() with its defaults and
+// textureMesh({patch}) again, now on the clean mesh, in one call (tests/test_gpu_texture_pipeline.py).  Back come the poses
+// [n_views][12], K [9], has_map [n_views], the depth maps of ALL views in view order (zeros where a view has none), the grid's voxel, the
+// mesh and the clean mesh (cap_vertices rows of *_xyz / *_bgr, cap_triangles rows of *_tri) and the two textured meshes, k = 0 on the
+// mesh and k = 1 on the clean mesh: atlas_wh [2 k .. 2 k + 1], cap_atlas bytes of atlas at k cap_atlas, cap_triangles rows of uv
+// [.][6] and of view at k cap_triangles, textured [k], and same_source [k] = 1 iff its vertices and triangles are those of the mesh it
+// was made from.  *unchanged = 1 iff the mesh, the clean mesh, the dense cloud and every depth map equal, byte for byte, the copies
+// taken before the texturing calls.  obj_prefix != NULL: saveTexturedMeshToOBJ after the first call, and under obj_prefix + "_clean"
+// after the second.  what == 1: no run at all, only textureMesh on a fresh object with images (it has to refuse; no device involved).
+// Returns runSfM's code, 10 + densify's code, 20 + meshDenseCloud's code, 30 + cleanMesh's code, 50 + textureMesh's code (150 + it if a
+// refusing call left a textured mesh behind), -2 if a capacity is too small, -3 if a file could not be written.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_texture(int what, int n_views, int channels, const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h,
+                               int debug_level, int patch, const char* obj_prefix, float* poses, float* K, unsigned char* has_map, float* depth,
+                               float* voxel, int* unchanged, int64_t cap_vertices, int64_t cap_triangles, int64_t* n_vertices, int64_t* n_triangles,
+                               float* mesh_xyz, unsigned char* mesh_bgr, int32_t* mesh_tri, int64_t* n_clean_vertices, int64_t* n_clean_triangles,
+                               float* clean_xyz, unsigned char* clean_bgr, int32_t* clean_tri, int64_t cap_atlas, int32_t* atlas_wh, unsigned char* atlas,
+                               float* uv, int32_t* view, int64_t* textured, int* same_source) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    sfm.setImages(images);
+    *unchanged = 0; *n_vertices = 0; *n_triangles = 0; *n_clean_vertices = 0; *n_clean_triangles = 0;
+    TextureParams params;
+    params.patch = patch;
+    const auto left_behind = [&]() { return !sfm.getTexturedMesh().atlas.empty() || !sfm.getTexturedMesh().triangles.empty(); };
+    ErrorCode code;
+    if (what == 1) {
+        code = sfm.textureMesh(params);
+        return (code == OKAY || left_behind() ? 150 : 50) + (int)code;
+    }
+    if ((code = sfm.runSfM()) != OKAY) return (int)code;
+    for (int v = 0; v < n_views; ++v)
+        for (int e = 0; e < 12; ++e) poses[12 * v + e] = sfm.getCameraPoses()[v].val[e];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) K[3 * r + c] = sfm.getIntrinsics().K.at<float>(r, c);
+    if ((code = sfm.densify()) != OKAY) return 10 + (int)code;
+    if ((code = sfm.meshDenseCloud()) != OKAY) return 20 + (int)code;
+    const auto same_mesh = [](const Mesh& a, const Mesh& b) {
+        bool same = a.vertices.size() == b.vertices.size() && a.bgr == b.bgr && a.triangles == b.triangles && a.normals.size() == b.normals.size();
+        for (size_t i = 0; same && i < a.vertices.size(); ++i) same = std::memcmp(&a.vertices[i], &b.vertices[i], sizeof(cv::Point3f)) == 0;
+        return same && (a.normals.empty() || std::memcmp(a.normals.data(), b.normals.data(), a.normals.size() * sizeof(float)) == 0);
+    };
+    const auto put_textured = [&](int k, const Mesh& source) {
+        const TexturedMesh& t = sfm.getTexturedMesh();
+        const int64_t bytes = (int64_t)t.atlas.rows * t.atlas.cols * 3, nt = (int64_t)(t.triangles.size() / 3);
+        if (bytes > cap_atlas || nt > cap_triangles || (int64_t)t.uv.size() != 6 * nt || (int64_t)t.view.size() != nt) return false;
+        atlas_wh[2 * k] = t.atlas.cols; atlas_wh[2 * k + 1] = t.atlas.rows;
+        std::memcpy(atlas + (size_t)k * (size_t)cap_atlas, t.atlas.ptr<unsigned char>(0), (size_t)bytes);
+        std::memcpy(uv + (size_t)k * (size_t)cap_triangles * 6, t.uv.data(), t.uv.size() * sizeof(float));
+        std::memcpy(view + (size_t)k * (size_t)cap_triangles, t.view.data(), t.view.size() * sizeof(int32_t));
+        textured[k] = (int64_t)t.textured;
+        bool same = t.triangles == source.triangles && t.vertices.size() == source.vertices.size();
+        for (size_t i = 0; same && i < t.vertices.size(); ++i) same = std::memcmp(&t.vertices[i], &source.vertices[i], sizeof(cv::Point3f)) == 0;
+        same_source[k] = same ? 1 : 0;
+        return true;
+    };
+    const auto put_mesh = [](const Mesh& m, float* xyz, unsigned char* bgr, int32_t* tri) {
+        for (size_t i = 0; i < m.vertices.size(); ++i) {
+            xyz[3 * i] = m.vertices[i].x; xyz[3 * i + 1] = m.vertices[i].y; xyz[3 * i + 2] = m.vertices[i].z;
+            for (int k = 0; k < 3; ++k) bgr[3 * i + k] = m.bgr[3 * i + k];
+        }
+        for (size_t i = 0; i < m.triangles.size(); ++i) tri[i] = m.triangles[i];
+    };
+    const Mesh meshBefore = sfm.getMesh();
+    const DenseCloud cloudBefore = sfm.getDenseCloud();
+    std::vector<std::vector<float> > mapsBefore;             // a view without a map: empty
+    for (const cv::Mat& m : sfm.getDepthMaps())
+        mapsBefore.push_back(m.empty() ? std::vector<float>() : std::vector<float>(m.ptr<float>(0), m.ptr<float>(0) + (size_t)m.rows * m.cols));
+    *voxel = meshBefore.grid.voxel;
+    *n_vertices = (int64_t)meshBefore.vertices.size();
+    *n_triangles = (int64_t)(meshBefore.triangles.size() / 3);
+    if (*n_vertices > cap_vertices || *n_triangles > cap_triangles || meshBefore.bgr.size() != 3 * meshBefore.vertices.size()) return -2;
+    // on the mesh
+    code = sfm.textureMesh(params);
+    if (code != OKAY) return (left_behind() ? 150 : 50) + (int)code;
+    if (!put_textured(0, sfm.getMesh())) return -2;
+    if (obj_prefix && !sfm.saveTexturedMeshToOBJ(obj_prefix)) return -3;
+    // on the clean mesh
+    if ((code = sfm.cleanMesh()) != OKAY) return 30 + (int)code;
+    if (left_behind()) return 150;                           // cleanMesh clears what was made from the mesh before it
+    const Mesh cleanBefore = sfm.getCleanMesh();
+    *n_clean_vertices = (int64_t)cleanBefore.vertices.size();
+    *n_clean_triangles = (int64_t)(cleanBefore.triangles.size() / 3);
+    if (cleanBefore.bgr.size() != 3 * cleanBefore.vertices.size()) return -2;
+    code = sfm.textureMesh(params);
+    if (code != OKAY) return (left_behind() ? 150 : 50) + (int)code;
+    if (!put_textured(1, sfm.getCleanMesh())) return -2;
+    if (obj_prefix && !sfm.saveTexturedMeshToOBJ(std::string(obj_prefix) + "_clean")) return -3;
+    // nothing else moved
+    const DenseCloud& cloud = sfm.getDenseCloud();
+    bool same = same_mesh(sfm.getMesh(), meshBefore) && same_mesh(sfm.getCleanMesh(), cleanBefore) && cloud.points.size() == cloudBefore.points.size() &&
+                cloud.bgr == cloudBefore.bgr && sfm.getDepthMaps().size() == mapsBefore.size();
+    for (size_t i = 0; same && i < cloud.points.size(); ++i) same = std::memcmp(&cloud.points[i], &cloudBefore.points[i], sizeof(cv::Point3f)) == 0;
+    size_t at = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const size_t n = (size_t)w[v] * h[v];
+        const cv::Mat& m = sfm.getDepthMaps()[(size_t)v];
+        has_map[v] = m.empty() ? 0 : 1;
+        if (m.empty()) std::memset(depth + at, 0, n * sizeof(float));
+        else std::memcpy(depth + at, m.ptr<float>(0), n * sizeof(float));
+        same = same && (m.empty() ? mapsBefore[(size_t)v].empty()
+                                  : mapsBefore[(size_t)v].size() == n && std::memcmp(m.ptr<float>(0), mapsBefore[(size_t)v].data(), n * sizeof(float)) == 0);
+        at += n;
+    }
+    *unchanged = same ? 1 : 0;
+    put_mesh(meshBefore, mesh_xyz, mesh_bgr, mesh_tri);
+    put_mesh(cleanBefore, clean_xyz, clean_bgr, clean_tri);
+    return 0;
+}
+
 // SfM::densify() where it has to refuse (tests/test_depth_oracle_cpu.py; no device involved): what = 0 after setFeatures (there are
 // no pixels), 1 on images without a run, 2 on a fresh object.  Returns densify's code.
 extern "C" __attribute__((visibility("default")))
