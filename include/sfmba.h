@@ -1009,6 +1009,81 @@ SFMBA_API int sfmba_depth_fuse(int device, int n_images, const int64_t* img_ptr 
                 int64_t* pt_ptr /*[n_images+1]*/, float* xyz /*[cap][3]*/, unsigned char* bgr /*[cap][3]*/, int32_t* src_image /*[cap]*/,
                 int32_t* src_pixel /*[cap]*/, int64_t cap, int64_t* total);
 
+/* ---- regularised depth maps: semi-global matching over the sweep's cost volume (DenseParams::sgm) -------------------------------
+ * sfmba_depth_sweep is winner-take-all per pixel: no pixel hears from its neighbour, and a pixel whose window has no texture gets no
+ * depth at all.  These three calls keep the costs of ALL planes, quantised to a byte, and aggregate them along 4 or 8 path directions
+ * with a small penalty p1 for a change of one plane and a larger p2 for any other change (semi-global matching, Hirschmueller 2008);
+ * a pixel without a cost of its own then takes the plane its neighbours agree on.  THE CONTRACT IS OUR OWN AND EQUALS NOBODY'S, stated
+ * so that the device is held BIT FOR BIT to a CPU restatement (tests/sgm_oracle.py): the cost is the very fp64 value of
+ * sfmba_depth_sweep, everything from the quantised cost to the selection is INTEGER arithmetic, and the three fp64 expressions below
+ * have every operation rounded on its own (csrc/sgm_math.h switches the compiler's contraction off).
+ *
+ * sfmba_depth_cost_volume
+ *   inputs        images, K, P, jobs, n_planes D, radius, min_std and min_sources exactly as sfmba_depth_sweep takes and refuses them
+ *                 (there is no min_score); invalid_cost in 0..254 (checked here; the volume itself does not depend on it).
+ *   output        per job, concatenated in job order: cost uint8 [h][w][D], THE PLANE INDEX FASTEST.  Where the pixel takes part and
+ *                 plane k is VALID (both as defined under sfmba_depth_sweep) the entry is q = (int)floor((1.0 - C_k) * 127.0 + 0.5),
+ *                 0 (C_k = 1) .. 254 (C_k = -1); everywhere else -- an invalid plane, a pixel that does not take part -- it is the
+ *                 SENTINEL 255.
+ *
+ * sfmba_sgm_aggregate
+ *   inputs        n_jobs volumes as above: cost[j] uint8 [height[j]][width[j]][D] (host pointers; 1 <= width, height <= 16384;
+ *                 one D in 2..256 for all); 0 <= p1 <= p2 <= 1023; n_paths 4 or 8; invalid_cost in 0..254.
+ *   cost          c(p, d) = the entry, a sentinel read as invalid_cost: 0..254.
+ *   paths         direction r in the order (+1,0), (-1,0), (0,+1), (0,-1) and, with 8 paths, (+1,+1), (-1,-1), (+1,-1), (-1,+1)
+ *                 ((dx, dy), y down).  With q = p - r: L_r(p, d) = c(p, d) where q lies outside the image; otherwise
+ *                 L_r(p, d) = c(p, d) + min(L_r(q, d), L_r(q, d-1) + p1, L_r(q, d+1) + p1, m + p2) - m with m = min_i L_r(q, i); the
+ *                 terms with d-1 < 0 or d+1 > D-1 are left out.  Every term is >= m and m + p2 is always there, so
+ *                 0 <= L_r <= 254 + p2 <= 1277.
+ *   sums          S(p, d) = sum_r L_r(p, d) <= 8 * 1277 = 10216: a uint16.
+ *   selection     k* = the lowest d with the smallest S; best = S(p, k*); second = the smallest S over the d with |d - k*| > 1, or
+ *                 0xffff where there is no such d (D = 2, 3 with k* = 1).
+ *   outputs       per job (arrays of n_jobs host pointers): plane[j] int16 [h][w] = k*, best[j] and second[j] uint16 [h][w], and
+ *                 sums[j] uint16 [h][w][D], the whole S (sums, or any sums[j], may be NULL).
+ *   SFMBA_ERR_INVALID_ARG (nothing written): p1, p2, n_paths or invalid_cost outside the ranges above; D outside 2..256; a width or
+ *                 height outside 1..16384; n_jobs < 0; a NULL among cost, width, height, plane, best, second or their entries.
+ *
+ * sfmba_depth_sweep_sgm
+ *   inputs        those of sfmba_depth_cost_volume plus p1, p2, n_paths, and uniqueness in 0..100.  The volume and the sums never
+ *                 leave the device.
+ *   outputs       the three maps of sfmba_depth_sweep in the same layout.  plane = k* for EVERY pixel of the reference image, those
+ *                 that do not take part included.  The pixel is ACCEPTED iff second == 0xffff or
+ *                 100 (second - best) >= uniqueness second (integers; where all sums are 0 -- a constant cost 0 everywhere -- this holds
+ *                 for every uniqueness, and at uniqueness 0 every pixel is accepted).  If 0 < k* < D-1 and den = (S- - 2 S0) + S+ > 0 (integers; S-,
+ *                 S0, S+ the sums at k*-1, k*, k*+1) then delta = (0.5 * (double)(S- - S+)) / (double)den, otherwise delta = 0;
+ *                 depth = (float)(1 / (w_k* + (delta step))) as in sfmba_depth_sweep, 0 where the pixel is not accepted.
+ *                 score = (float)(1.0 - (double)q / 127.0) with q the pixel's OWN volume entry at k*, and 0 where that entry is the
+ *                 sentinel: the depth there came from the neighbours alone, and a caller can tell.
+ *   equals        sfmba_depth_cost_volume -> sfmba_sgm_aggregate -> the rules above, byte for byte.  Jobs go to the device in
+ *                 consecutive groups under sfmba_depth_sweep's scratch bound, which here also counts the volume (1 byte per entry)
+ *                 and the sums (2 bytes); a job that exceeds it alone forms a group of its own.  A batch equals the concatenation of
+ *                 single-job calls, whatever the grouping.
+ *   SFMBA_ERR_INVALID_ARG (nothing written): what sfmba_depth_cost_volume refuses; p1, p2 or n_paths outside the ranges of
+ *                 sfmba_sgm_aggregate; uniqueness outside 0..100.
+ *   WHAT THIS DOES NOT DO: NO LEFT-RIGHT CHECK -- sfmba_depth_fuse's reprojection filter is the cross-check.  NO ADAPTIVE p2: the
+ *                 penalty does not look at the image.  DEPTH IN REGIONS THAT NO SOURCE SEES IS MADE UP FROM THE NEIGHBOURS; only
+ *                 `uniqueness` and the fuse stand against it.  The defaults of the host layer (p1 8, p2 64, 8 paths, invalid_cost
+ *                 127, uniqueness 5) are FIRST CHOICES THAT NOBODY HAS TUNED.
+ *   Host pointers in and out, synchronous, deterministic.  SFMBA_ABI_VERSION stays 6: adding symbols is backward compatible.
+ */
+SFMBA_API int sfmba_depth_cost_volume(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/,
+                const float* K /*[9]*/, const float* P /*[n_images][12]*/, int n_jobs, const int32_t* job_ref /*[n_jobs]*/,
+                const int64_t* job_src_ptr /*[n_jobs+1]*/, const int32_t* job_src, const float* z_near /*[n_jobs]*/,
+                const float* z_far /*[n_jobs]*/, int n_planes /*2..256*/, int radius /*1..4*/, int min_std /*0..127*/,
+                int min_sources /*1..4*/, int invalid_cost /*0..254*/, unsigned char* cost);
+SFMBA_API int sfmba_sgm_aggregate(int device, int n_jobs, const unsigned char* const* cost /*[n_jobs], each [h][w][D]*/,
+                const int32_t* width /*[n_jobs]*/, const int32_t* height /*[n_jobs]*/, int n_planes /*2..256*/, int p1, int p2 /*0 <= p1 <= p2 <= 1023*/,
+                int n_paths /*4 or 8*/, int invalid_cost /*0..254*/, int16_t* const* plane /*[n_jobs], each [h][w]*/,
+                uint16_t* const* best, uint16_t* const* second, uint16_t* const* sums /*or NULL; [n_jobs], each NULL or [h][w][D]*/);
+SFMBA_API int sfmba_depth_sweep_sgm(int device, int n_images, const int64_t* img_ptr /*[n_images+1], byte offsets*/,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels /*1 gray, 3 BGR*/,
+                const float* K /*[9]*/, const float* P /*[n_images][12]*/, int n_jobs, const int32_t* job_ref /*[n_jobs]*/,
+                const int64_t* job_src_ptr /*[n_jobs+1]*/, const int32_t* job_src, const float* z_near /*[n_jobs]*/,
+                const float* z_far /*[n_jobs]*/, int n_planes /*2..256*/, int radius /*1..4*/, int min_std /*0..127*/,
+                int min_sources /*1..4*/, int p1, int p2, int n_paths, int invalid_cost, int uniqueness /*0..100*/, float* depth,
+                float* score, int16_t* plane /*or NULL*/);
+
 /* ---- one oriented point per surface element: a normal per depth pixel and the voxel merge (SfM::mergeDenseCloud) ---------------
  * sfmba_depth_fuse leaves a surface point once per view that saw it, and without a normal.  These two calls close the chain from
  * images to a model: a normal per depth pixel, and one point per occupied voxel.  THE CONTRACT IS OUR OWN, stated so that the device

@@ -43,6 +43,7 @@ SYMBOLS = [
     "sfmba_tsdf_fill", "sfmba_tsdf_mesh_fill",
     "sfmba_mesh_components", "sfmba_mesh_filter", "sfmba_mesh_smooth", "sfmba_mesh_clean",
     "sfmba_mesh_texture_size", "sfmba_mesh_texture",
+    "sfmba_depth_cost_volume", "sfmba_sgm_aggregate", "sfmba_depth_sweep_sgm",
 ]
 
 # reduced-system solver families of the step probe (SFMBA_FAMILY_* in include/sfmba.h), by value
@@ -416,6 +417,87 @@ def depth_sweep(images, K, P, jobs, n_planes=64, radius=3, min_std=2, min_score=
                                    _p(src_ptr, lp), _p(src, _ip), zn.ctypes.data_as(fp), zf.ctypes.data_as(fp), C.c_int(n_planes),
                                    C.c_int(radius), C.c_int(min_std), C.c_float(min_score), C.c_int(min_sources), depth.ctypes.data_as(fp),
                                    score.ctypes.data_as(fp), plane.ctypes.data_as(C.POINTER(C.c_int16)) if want_plane else None))
+    out, at = [], 0
+    for h, w in sizes:
+        n = h * w
+        out.append((depth[at:at + n].reshape(h, w).copy(), score[at:at + n].reshape(h, w).copy(),
+                    plane[at:at + n].reshape(h, w).copy() if want_plane else None))
+        at += n
+    return out
+
+
+def _sweep_inputs(images, K, P, jobs, device):
+    """The arguments sfmba_depth_sweep and the calls that store its cost volume share, up to z_far; and the (h, w) of every job."""
+    imgs, channels, img_ptr, flat, wd, ht = _flat_images(images)
+    K = np.ascontiguousarray(K, dtype=np.float32).reshape(9)
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1)
+    if len(P) != 12 * len(imgs):
+        raise ValueError("P must hold one 3 x 4 matrix per image")
+    ref = np.asarray([j[0] for j in jobs] or [0], dtype=np.int32)
+    src_ptr, src = _csr([list(j[1]) for j in jobs])
+    zn = np.asarray([j[2] for j in jobs] or [0], dtype=np.float32)
+    zf = np.asarray([j[3] for j in jobs] or [0], dtype=np.float32)
+    sizes = [(int(ht[r]), int(wd[r])) if 0 <= r < len(imgs) else (0, 0) for r in ref[:len(jobs)]]
+    lp, bp, fp = C.POINTER(C.c_int64), C.POINTER(C.c_ubyte), C.POINTER(C.c_float)
+    keep = (img_ptr, flat, wd, ht, K, P, ref, src_ptr, src, zn, zf)
+    args = [C.c_int(device), C.c_int(len(imgs)), _p(img_ptr, lp), flat.ctypes.data_as(bp), _p(wd, _ip), _p(ht, _ip), C.c_int(channels),
+            K.ctypes.data_as(fp), P.ctypes.data_as(fp), C.c_int(len(jobs)), _p(ref, _ip), _p(src_ptr, lp), _p(src, _ip), zn.ctypes.data_as(fp),
+            zf.ctypes.data_as(fp)]
+    return args, sizes, keep
+
+
+def depth_cost_volume(images, K, P, jobs, n_planes=64, radius=3, min_std=2, min_sources=1, invalid_cost=127, device=0):
+    """sfmba_depth_cost_volume: the quantised cost of every (pixel, plane) of a list of sweep jobs (the contract is in include/sfmba.h).
+    Inputs as depth_sweep.  Returns one uint8 [h, w, n_planes] array per job (255 = no cost)."""
+    args, sizes, keep = _sweep_inputs(images, K, P, jobs, device)
+    cost = np.zeros(max(sum(h * w for h, w in sizes) * max(n_planes, 0), 1), np.uint8)
+    _check(lib().sfmba_depth_cost_volume(*args, C.c_int(n_planes), C.c_int(radius), C.c_int(min_std), C.c_int(min_sources), C.c_int(invalid_cost),
+                                         cost.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    out, at = [], 0
+    for h, w in sizes:
+        out.append(cost[at:at + h * w * n_planes].reshape(h, w, n_planes).copy())
+        at += h * w * n_planes
+    return out
+
+
+def sgm_aggregate(volumes, p1=8, p2=64, n_paths=8, invalid_cost=127, want_sums=True, n_planes=None, device=0):
+    """sfmba_sgm_aggregate: semi-global aggregation and selection over cost volumes (the contract is in include/sfmba.h).
+
+    volumes: uint8 [h, w, D] arrays with one D (n_planes overrides the D that is passed).  Returns one dict per volume: plane int16
+    [h, w], best and second uint16 [h, w], sums uint16 [h, w, D] (None with want_sums=False: NULL is passed; want_sums may also be a
+    list of one flag per volume: an entry of the pointer array is then NULL)."""
+    vols = [np.ascontiguousarray(v, dtype=np.uint8) for v in volumes]
+    if any(v.ndim != 3 for v in vols) or len({v.shape[2] for v in vols}) > 1:
+        raise ValueError("volumes must be h x w x D uint8 arrays with one D")
+    D = (vols[0].shape[2] if vols else 2) if n_planes is None else n_planes
+    wd = np.asarray([v.shape[1] for v in vols] or [0], dtype=np.int32)
+    ht = np.asarray([v.shape[0] for v in vols] or [0], dtype=np.int32)
+    n = len(vols)
+    plane = [np.zeros(v.shape[:2], np.int16) for v in vols]
+    best = [np.zeros(v.shape[:2], np.uint16) for v in vols]
+    second = [np.zeros(v.shape[:2], np.uint16) for v in vols]
+    each = list(want_sums) if isinstance(want_sums, (list, tuple)) else [bool(want_sums)] * len(vols)
+    want_sums = bool(want_sums) and any(each)
+    sums = [np.zeros(v.shape, np.uint16) if e else None for v, e in zip(vols, each)] if want_sums else None
+    bp, sp, up = C.POINTER(C.c_ubyte), C.POINTER(C.c_int16), C.POINTER(C.c_uint16)
+    arr = lambda t, xs: (t * max(n, 1))(*[None if x is None else x.ctypes.data_as(t) for x in xs])
+    _check(lib().sfmba_sgm_aggregate(C.c_int(device), C.c_int(n), arr(bp, vols), _p(wd, _ip), _p(ht, _ip), C.c_int(D), C.c_int(p1), C.c_int(p2),
+                                     C.c_int(n_paths), C.c_int(invalid_cost), arr(sp, plane), arr(up, best), arr(up, second),
+                                     arr(up, sums) if want_sums else None))
+    return [dict(plane=plane[j], best=best[j], second=second[j], sums=sums[j] if want_sums else None) for j in range(n)]
+
+
+def depth_sweep_sgm(images, K, P, jobs, n_planes=64, radius=3, min_std=2, min_sources=1, p1=8, p2=64, n_paths=8, invalid_cost=127,
+                    uniqueness=5, want_plane=True, device=0):
+    """sfmba_depth_sweep_sgm: plane sweep, semi-global aggregation and selection in one call (the contract is in include/sfmba.h).
+    Inputs as depth_sweep (there is no min_score); returns what depth_sweep returns."""
+    args, sizes, keep = _sweep_inputs(images, K, P, jobs, device)
+    n_px = max(sum(h * w for h, w in sizes), 1)
+    depth, score, plane = np.zeros(n_px, np.float32), np.zeros(n_px, np.float32), np.zeros(n_px, np.int16)
+    fp = C.POINTER(C.c_float)
+    _check(lib().sfmba_depth_sweep_sgm(*args, C.c_int(n_planes), C.c_int(radius), C.c_int(min_std), C.c_int(min_sources), C.c_int(p1), C.c_int(p2),
+                                       C.c_int(n_paths), C.c_int(invalid_cost), C.c_int(uniqueness), depth.ctypes.data_as(fp),
+                                       score.ctypes.data_as(fp), plane.ctypes.data_as(C.POINTER(C.c_int16)) if want_plane else None))
     out, at = [], 0
     for h, w in sizes:
         n = h * w

@@ -6,6 +6,7 @@
 // leaves the outputs as they were.  What several entry points refuse in the same words is one check_* function below.
 #include "association.h"
 #include "cloud_merge.h"
+#include "depth_sgm.h"
 #include "depth_sweep.h"
 #include "essential_ransac.h"
 #include "feature_match.h"
@@ -24,6 +25,7 @@
 #include "png_decode.h"
 #include "pnp_ransac.h"
 #include "problem.h"
+#include "sgm_math.h"
 #include "surf_extract.h"
 #include "tsdf_fill.h"
 #include "tsdf_fill_math.h"
@@ -501,36 +503,127 @@ int sfmba_surf_extract(int device, int n_images, const int64_t* img_ptr, const u
     return unit_result(rc, "surf_extract");
 }
 // ---- dense depth maps and a dense cloud: plane-sweep stereo and the consistency filter (SfM::densify) ---------------------------
+namespace {
+// what sfmba_depth_sweep and the two calls that store its cost volume refuse about the images, the cameras, the jobs and the shared
+// parameters; *out_px receives the pixels of all reference images
+int depth_check_sweep(const char* who, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                      int channels, const float* K, const float* P, int n_jobs, const int32_t* job_ref, const int64_t* job_src_ptr,
+                      const int32_t* job_src, const float* z_near, const float* z_far, int n_planes, int radius, int min_std,
+                      const float* min_score /*NULL: the call has none*/, int min_sources, int64_t* out_px) {
+    const std::string w(who);
+    if (n_jobs < 0 || (n_jobs > 0 && (!job_ref || !job_src_ptr || !job_src || !z_near || !z_far))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (const int rc = depth_check_images(who, n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    if (n_planes < 2 || n_planes > 256) return fail(SFMBA_ERR_INVALID_ARG, w + ": n_planes must be in 2..256");
+    if (radius < 1 || radius > 4) return fail(SFMBA_ERR_INVALID_ARG, w + ": radius must be in 1..4");
+    if (min_std < 0 || min_std > 127) return fail(SFMBA_ERR_INVALID_ARG, w + ": min_std must be in 0..127");
+    if (min_score && (!(*min_score >= -1.0f) || !(*min_score <= 1.0f))) return fail(SFMBA_ERR_INVALID_ARG, w + ": min_score must be in [-1, 1]");
+    if (min_sources < 1 || min_sources > 4) return fail(SFMBA_ERR_INVALID_ARG, w + ": min_sources must be in 1..4");
+    *out_px = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (job_ref[j] < 0 || job_ref[j] >= n_images) return fail(SFMBA_ERR_INVALID_ARG, w + ": reference image index out of range");
+        if (!std::isfinite(z_near[j]) || !std::isfinite(z_far[j]) || !(z_near[j] > 0.0f) || !(z_near[j] < z_far[j]))
+            return fail(SFMBA_ERR_INVALID_ARG, w + ": a job needs 0 < z_near < z_far, both finite");
+        *out_px += (int64_t)width[job_ref[j]] * height[job_ref[j]];
+    }
+    if (n_jobs > 0)
+        if (const int rc = depth_check_lists(who, "source", n_images, n_jobs, job_ref, job_src_ptr, job_src, 1)) return rc;
+    return 0;
+}
+int sgm_check_params(const char* who, int p1, int p2, int n_paths, int invalid_cost) {
+    const std::string w(who);
+    if (p1 < 0 || p2 < p1 || p2 > SGM_MAX_PENALTY) return fail(SFMBA_ERR_INVALID_ARG, w + ": the penalties must satisfy 0 <= p1 <= p2 <= 1023");
+    if (n_paths != 4 && n_paths != 8) return fail(SFMBA_ERR_INVALID_ARG, w + ": n_paths must be 4 or 8");
+    if (invalid_cost < 0 || invalid_cost > SGM_MAX_COST) return fail(SFMBA_ERR_INVALID_ARG, w + ": invalid_cost must be in 0..254");
+    return 0;
+}
+void sweep_timing_line(const char* what, const double* t) {
+    std::fprintf(stderr, "[sfmba %s] upload_ms %.6f gray_ms %.6f sweep_ms %.6f download_ms %.6f groups %d\n", what, t[DEPTH_T_UPLOAD], t[DEPTH_T_GRAY],
+                 t[DEPTH_T_SWEEP], t[DEPTH_T_DOWNLOAD], (int)t[DEPTH_T_GROUPS]);
+}
+void sgm_timing_line(const char* what, const double* t) {
+    std::fprintf(stderr, "[sfmba %s] aggregate_ms %.6f select_ms %.6f finish_ms %.6f path_ms", what, t[SGM_T_AGGREGATE], t[SGM_T_SELECT], t[SGM_T_FINISH]);
+    for (int i = 0; i < 8; ++i) std::fprintf(stderr, " %.6f", t[SGM_T_PATH0 + i]);
+    std::fprintf(stderr, "\n");
+}
+}  // namespace
 int sfmba_depth_sweep(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
                       int channels, const float* K, const float* P, int n_jobs, const int32_t* job_ref, const int64_t* job_src_ptr,
                       const int32_t* job_src, const float* z_near, const float* z_far, int n_planes, int radius, int min_std, float min_score,
                       int min_sources, float* depth, float* score, int16_t* plane) {
-    if (n_jobs < 0 || (n_jobs > 0 && (!job_ref || !job_src_ptr || !job_src || !z_near || !z_far))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
-    if (const int rc = depth_check_images("depth_sweep", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
-    if (n_planes < 2 || n_planes > 256) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: n_planes must be in 2..256");
-    if (radius < 1 || radius > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: radius must be in 1..4");
-    if (min_std < 0 || min_std > 127) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_std must be in 0..127");
-    if (!(min_score >= -1.0f) || !(min_score <= 1.0f)) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_score must be in [-1, 1]");
-    if (min_sources < 1 || min_sources > 4) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: min_sources must be in 1..4");
     int64_t out_px = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        if (job_ref[j] < 0 || job_ref[j] >= n_images) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: reference image index out of range");
-        if (!std::isfinite(z_near[j]) || !std::isfinite(z_far[j]) || !(z_near[j] > 0.0f) || !(z_near[j] < z_far[j]))
-            return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep: a job needs 0 < z_near < z_far, both finite");
-        out_px += (int64_t)width[job_ref[j]] * height[job_ref[j]];
-    }
-    if (n_jobs > 0)
-        if (const int rc = depth_check_lists("depth_sweep", "source", n_images, n_jobs, job_ref, job_src_ptr, job_src, 1)) return rc;
+    if (const int rc = depth_check_sweep("depth_sweep", n_images, img_ptr, pixels, width, height, channels, K, P, n_jobs, job_ref, job_src_ptr, job_src,
+                                         z_near, z_far, n_planes, radius, min_std, &min_score, min_sources, &out_px))
+        return rc;
     if (out_px > 0 && (!depth || !score)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
     if (n_jobs == 0) return check_device(device);
     TimedCall<DEPTH_T_COUNT> c("SFMBA_DEPTH_TIMING");          // (tools/dense_bench.py)
     if (const int rc = c.open(device)) return rc;
     const int rc = depth_sweep(c.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, K, P, n_jobs, job_ref, job_src_ptr, job_src,
                                z_near, z_far, n_planes, radius, min_std, min_score, min_sources, depth, score, plane, c.tm());
-    if (rc == 0 && c.on)
-        std::fprintf(stderr, "[sfmba depth_sweep] upload_ms %.6f gray_ms %.6f sweep_ms %.6f download_ms %.6f groups %d\n", c.t[DEPTH_T_UPLOAD],
-                     c.t[DEPTH_T_GRAY], c.t[DEPTH_T_SWEEP], c.t[DEPTH_T_DOWNLOAD], (int)c.t[DEPTH_T_GROUPS]);
+    if (rc == 0 && c.on) sweep_timing_line("depth_sweep", c.t);
     return unit_result(rc, "depth_sweep");
+}
+// ---- semi-global matching over the sweep's cost volume (DenseParams::sgm) -----------------------------------------------------------
+int sfmba_depth_cost_volume(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width,
+                            const int32_t* height, int channels, const float* K, const float* P, int n_jobs, const int32_t* job_ref,
+                            const int64_t* job_src_ptr, const int32_t* job_src, const float* z_near, const float* z_far, int n_planes, int radius,
+                            int min_std, int min_sources, int invalid_cost, unsigned char* cost) {
+    int64_t out_px = 0;
+    if (const int rc = depth_check_sweep("depth_cost_volume", n_images, img_ptr, pixels, width, height, channels, K, P, n_jobs, job_ref, job_src_ptr,
+                                         job_src, z_near, z_far, n_planes, radius, min_std, nullptr, min_sources, &out_px))
+        return rc;
+    if (invalid_cost < 0 || invalid_cost > SGM_MAX_COST) return fail(SFMBA_ERR_INVALID_ARG, "depth_cost_volume: invalid_cost must be in 0..254");
+    if (out_px > 0 && !cost) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (n_jobs == 0) return check_device(device);
+    TimedCall<DEPTH_T_COUNT> c("SFMBA_DEPTH_TIMING");          // (tools/sgm_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = depth_cost_volume(c.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, K, P, n_jobs, job_ref, job_src_ptr,
+                                     job_src, z_near, z_far, n_planes, radius, min_std, min_sources, cost, c.tm());
+    if (rc == 0 && c.on) sweep_timing_line("depth_cost_volume", c.t);
+    return unit_result(rc, "depth_cost_volume");
+}
+int sfmba_sgm_aggregate(int device, int n_jobs, const unsigned char* const* cost, const int32_t* width, const int32_t* height, int n_planes, int p1,
+                        int p2, int n_paths, int invalid_cost, int16_t* const* plane, uint16_t* const* best, uint16_t* const* second,
+                        uint16_t* const* sums) {
+    if (n_jobs < 0 || (n_jobs > 0 && (!cost || !width || !height || !plane || !best || !second))) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (n_planes < 2 || n_planes > 256) return fail(SFMBA_ERR_INVALID_ARG, "sgm_aggregate: n_planes must be in 2..256");
+    if (const int rc = sgm_check_params("sgm_aggregate", p1, p2, n_paths, invalid_cost)) return rc;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (width[j] < 1 || width[j] > 16384 || height[j] < 1 || height[j] > 16384)
+            return fail(SFMBA_ERR_INVALID_ARG, "sgm_aggregate: a volume's width or height lies outside 1..16384");
+        if (!cost[j] || !plane[j] || !best[j] || !second[j]) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    }
+    if (n_jobs == 0) return check_device(device);
+    TimedCall<SGM_T_COUNT> c("SFMBA_DEPTH_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = sgm_aggregate(c.kit.stream, device, n_jobs, cost, width, height, n_planes, p1, p2, n_paths, invalid_cost, plane, best, second, sums,
+                                 c.tm());
+    if (rc == 0 && c.on) sgm_timing_line("sgm_aggregate", c.t);
+    return unit_result(rc, "sgm_aggregate");
+}
+int sfmba_depth_sweep_sgm(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                          int channels, const float* K, const float* P, int n_jobs, const int32_t* job_ref, const int64_t* job_src_ptr,
+                          const int32_t* job_src, const float* z_near, const float* z_far, int n_planes, int radius, int min_std, int min_sources,
+                          int p1, int p2, int n_paths, int invalid_cost, int uniqueness, float* depth, float* score, int16_t* plane) {
+    int64_t out_px = 0;
+    if (const int rc = depth_check_sweep("depth_sweep_sgm", n_images, img_ptr, pixels, width, height, channels, K, P, n_jobs, job_ref, job_src_ptr,
+                                         job_src, z_near, z_far, n_planes, radius, min_std, nullptr, min_sources, &out_px))
+        return rc;
+    if (const int rc = sgm_check_params("depth_sweep_sgm", p1, p2, n_paths, invalid_cost)) return rc;
+    if (uniqueness < 0 || uniqueness > 100) return fail(SFMBA_ERR_INVALID_ARG, "depth_sweep_sgm: uniqueness must be in 0..100");
+    if (out_px > 0 && (!depth || !score)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (n_jobs == 0) return check_device(device);
+    TimedCall<DEPTH_T_COUNT> c("SFMBA_DEPTH_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    double sgm_t[SGM_T_COUNT];
+    const int rc = depth_sweep_sgm(c.kit.stream, device, n_images, img_ptr, pixels, width, height, channels, K, P, n_jobs, job_ref, job_src_ptr, job_src,
+                                   z_near, z_far, n_planes, radius, min_std, min_sources, p1, p2, n_paths, invalid_cost, uniqueness, depth, score, plane,
+                                   c.tm(), c.on ? sgm_t : nullptr);
+    if (rc == 0 && c.on) {
+        sweep_timing_line("depth_sweep_sgm", c.t);
+        sgm_timing_line("depth_sweep_sgm", sgm_t);
+    }
+    return unit_result(rc, "depth_sweep_sgm");
 }
 int sfmba_depth_fuse(int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
                      int channels, const float* K, const float* P, const float* const* depth, const int64_t* chk_ptr, const int32_t* chk,

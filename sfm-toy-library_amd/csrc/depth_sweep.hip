@@ -12,12 +12,14 @@
 //                 valid), ONE barrier (the sample buffers alternate between two planes), and every lane sums its own window per
 //                 source: SJ, SJJ, SIJ in int32, the score in fp64.  A lane keeps the best cost, the cost before it, the previous
 //                 cost and a "take the next one" flag, so the refinement needs no cost volume: nothing but the three maps goes to
-//                 HBM.
+//                 HBM.  k_depth_sweep<R, true> is the same code with the other ending: it keeps no winner and stores the quantised
+//                 cost of every (pixel, plane) instead -- the volume that depth_sgm.hip aggregates.
 //   fuse          k_fuse_flag: one lane per pixel with a depth, the agreement count over the check images -> a 0 / 1 flag;
 //                 a hipCUB exclusive sum over the flags in (image, row, column) order gives every kept pixel its output row;
 //                 k_fuse_emit writes the rows.  The compaction is stable by construction.
 #include "depth_sweep.h"
 #include "depth_math.h"
+#include "sgm_math.h"
 #include "device_arena.h"
 
 #include <hipcub/hipcub.hpp>
@@ -53,10 +55,10 @@ __global__ __launch_bounds__(LANES) void k_depth_gray(const GrayJob* __restrict_
     }
 }
 
-template <int R>
+template <int R, bool COST>
 __global__ __launch_bounds__(LANES) void k_depth_sweep(const DepthJob* __restrict__ jobs, const unsigned char* __restrict__ gray, int D, int min_std,
                                                        double min_score, int min_sources, float* __restrict__ depth, float* __restrict__ score,
-                                                       int16_t* __restrict__ plane) {
+                                                       int16_t* __restrict__ plane, unsigned char* __restrict__ cost) {
     constexpr int SIDE = DEPTH_TILE + 2 * R, CELLS = SIDE * SIDE, N = (2 * R + 1) * (2 * R + 1);
     __shared__ unsigned short s_ref[CELLS];
     __shared__ unsigned short s_smp[2][DEPTH_MAX_SOURCES][CELLS];
@@ -95,6 +97,12 @@ __global__ __launch_bounds__(LANES) void k_depth_sweep(const DepthJob* __restric
     bool have = false, take_next = false, pred_ok = false, succ_ok = false, prev_ok = false;
     double best = 0.0, pred = 0.0, succ = 0.0, prev = 0.0;
     int best_k = -1;
+    // the cost store: a lane owns the D bytes of its pixel and writes them four planes at a time where the run is aligned (D % 4 == 0)
+    const bool inside = x < w && y < h;
+    unsigned char* run = nullptr;
+    unsigned pack = 0u;
+    if constexpr (COST)
+        if (inside) run = cost + ((size_t)J.out_off + (size_t)y * (size_t)w + x) * (size_t)D;
     for (int k = 0; k < D; ++k) {
         const double wk = depth_plane_w(J.wf, J.step, k);
         const int buf = k & 1;
@@ -108,6 +116,7 @@ __global__ __launch_bounds__(LANES) void k_depth_sweep(const DepthJob* __restric
             }
         }
         __syncthreads();                                       // the other buffer is written next: one barrier per plane
+        int q = SGM_SENTINEL;
         if (part) {
             double acc = 0.0;
             int count = 0;
@@ -133,15 +142,28 @@ __global__ __launch_bounds__(LANES) void k_depth_sweep(const DepthJob* __restric
             }
             const bool valid = count >= min_sources;          // min_sources >= 1
             const double C = valid ? acc / (double)count : 0.0;
-            if (take_next) { succ = C; succ_ok = valid; take_next = false; }
-            if (valid && (!have || C > best)) {
-                have = true; best = C; best_k = k;
-                pred = prev; pred_ok = prev_ok;
-                take_next = true; succ_ok = false;
+            if constexpr (COST) {
+                if (valid) q = sgm_quantise(C);
+            } else {
+                if (take_next) { succ = C; succ_ok = valid; take_next = false; }
+                if (valid && (!have || C > best)) {
+                    have = true; best = C; best_k = k;
+                    pred = prev; pred_ok = prev_ok;
+                    take_next = true; succ_ok = false;
+                }
+                prev = C; prev_ok = valid;
             }
-            prev = C; prev_ok = valid;
+        }
+        if constexpr (COST) if (inside) {
+            if ((D & 3) == 0) {
+                pack |= (unsigned)q << (8 * (k & 3));
+                if ((k & 3) == 3) { *reinterpret_cast<unsigned*>(run + k - 3) = pack; pack = 0u; }
+            } else {
+                run[k] = (unsigned char)q;
+            }
         }
     }
+    if constexpr (COST) return;
 
     if (x < w && y < h) {
         float z = 0.0f, sc = 0.0f;
@@ -225,8 +247,13 @@ long long align64(long long n) { return (n + 63) & ~63ll; }
 
 template <int R>
 void launch_sweep(hipStream_t s, unsigned tiles, unsigned n_jobs, const DepthJob* jobs, const unsigned char* gray, int D, int min_std, double min_score,
-                  int min_sources, float* depth, float* score, int16_t* plane) {
-    hipLaunchKernelGGL(k_depth_sweep<R>, dim3(tiles, n_jobs), dim3(LANES), 0, s, jobs, gray, D, min_std, min_score, min_sources, depth, score, plane);
+                  int min_sources, float* depth, float* score, int16_t* plane, unsigned char* cost) {
+    if (cost)
+        hipLaunchKernelGGL((k_depth_sweep<R, true>), dim3(tiles, n_jobs), dim3(LANES), 0, s, jobs, gray, D, min_std, min_score, min_sources, depth, score,
+                           plane, cost);
+    else
+        hipLaunchKernelGGL((k_depth_sweep<R, false>), dim3(tiles, n_jobs), dim3(LANES), 0, s, jobs, gray, D, min_std, min_score, min_sources, depth, score,
+                           plane, cost);
 }
 
 }  // namespace
@@ -234,7 +261,7 @@ void launch_sweep(hipStream_t s, unsigned tiles, unsigned n_jobs, const DepthJob
 int depth_sweep(hipStream_t s, int device, int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width,
                 const int32_t* height, int channels, const float* K, const float* P, int n_jobs, const int32_t* job_ref,
                 const int64_t* job_src_ptr, const int32_t* job_src, const float* z_near, const float* z_far, int n_planes, int radius,
-                int min_std, float min_score, int min_sources, float* depth, float* score, int16_t* plane, double* timing) {
+                int min_std, float min_score, int min_sources, float* depth, float* score, int16_t* plane, double* timing, DepthCostSink* sink) {
     if (timing) for (int i = 0; i < DEPTH_T_COUNT; ++i) timing[i] = 0.0;
     if (n_jobs == 0) return 0;
     const double k4[4] = { (double)K[0], (double)K[4], (double)K[2], (double)K[5] };
@@ -262,7 +289,8 @@ int depth_sweep(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
             want(job_ref[j1]);
             for (int64_t e = job_src_ptr[j1]; e < job_src_ptr[j1 + 1]; ++e) want(job_src[e]);
             const long long px = out_off[(size_t)j1 + 1] - out_off[(size_t)j1];
-            const long long bytes = raw_bytes + gray_bytes + add_raw + add_gray + 10 * (out_px + px);
+            long long bytes = raw_bytes + gray_bytes + add_raw + add_gray + 10 * (out_px + px);
+            if (sink) bytes += (long long)(1 + sink->extra_bytes_per_entry) * n_planes * (out_px + px);   // the volume and what the sink adds
             if (j1 > j0 && bytes > (long long)DEPTH_SCRATCH_BYTES) break;
             for (int i : fresh) {
                 slot[(size_t)i] = gray_bytes;
@@ -312,6 +340,8 @@ int depth_sweep(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
         UNIT_ALLOC(scratch, d_depth, float, (size_t)out_px);
         UNIT_ALLOC(scratch, d_score, float, (size_t)out_px);
         UNIT_ALLOC(scratch, d_plane, int16_t, (size_t)out_px);
+        unsigned char* d_cost = nullptr;
+        if (sink) UNIT_ALLOC(scratch, d_cost, unsigned char, (size_t)out_px * (size_t)n_planes);
 
         tm.begin(DEPTH_T_UPLOAD);
         UNIT_TRY(hipMemcpyAsync(d_tab, tab.data(), sizeof(DepthJob) * tab.size(), hipMemcpyHostToDevice, s));
@@ -342,18 +372,26 @@ int depth_sweep(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
         const unsigned tiles = (unsigned)max_tiles;
         const double ms = (double)min_score;
         switch (radius) {
-        case 1: launch_sweep<1>(s, tiles, (unsigned)nj, d_tab, d_gray, n_planes, min_std, ms, min_sources, d_depth, d_score, d_plane); break;
-        case 2: launch_sweep<2>(s, tiles, (unsigned)nj, d_tab, d_gray, n_planes, min_std, ms, min_sources, d_depth, d_score, d_plane); break;
-        case 3: launch_sweep<3>(s, tiles, (unsigned)nj, d_tab, d_gray, n_planes, min_std, ms, min_sources, d_depth, d_score, d_plane); break;
-        default: launch_sweep<4>(s, tiles, (unsigned)nj, d_tab, d_gray, n_planes, min_std, ms, min_sources, d_depth, d_score, d_plane); break;
+        case 1: launch_sweep<1>(s, tiles, (unsigned)nj, d_tab, d_gray, n_planes, min_std, ms, min_sources, d_depth, d_score, d_plane, d_cost); break;
+        case 2: launch_sweep<2>(s, tiles, (unsigned)nj, d_tab, d_gray, n_planes, min_std, ms, min_sources, d_depth, d_score, d_plane, d_cost); break;
+        case 3: launch_sweep<3>(s, tiles, (unsigned)nj, d_tab, d_gray, n_planes, min_std, ms, min_sources, d_depth, d_score, d_plane, d_cost); break;
+        default: launch_sweep<4>(s, tiles, (unsigned)nj, d_tab, d_gray, n_planes, min_std, ms, min_sources, d_depth, d_score, d_plane, d_cost); break;
         }
         UNIT_TRY(hipGetLastError());
         tm.end();
-        tm.begin(DEPTH_T_DOWNLOAD);
         const size_t at = (size_t)out_off[(size_t)j0];
-        UNIT_TRY(hipMemcpyAsync(depth + at, d_depth, sizeof(float) * (size_t)out_px, hipMemcpyDeviceToHost, s));
-        UNIT_TRY(hipMemcpyAsync(score + at, d_score, sizeof(float) * (size_t)out_px, hipMemcpyDeviceToHost, s));
-        if (plane) UNIT_TRY(hipMemcpyAsync(plane + at, d_plane, sizeof(int16_t) * (size_t)out_px, hipMemcpyDeviceToHost, s));
+        if (sink) {
+            std::vector<DepthCostJob> cj((size_t)nj);
+            for (int j = 0; j < nj; ++j) cj[(size_t)j] = DepthCostJob{ tab[(size_t)j].w, tab[(size_t)j].h, tab[(size_t)j].out_off, tab[(size_t)j].wf, tab[(size_t)j].step };
+            const DepthCostGroup g{ j0, nj, n_planes, cj.data(), (long long)at, out_px, d_cost, d_depth, d_score, d_plane };
+            if (const int rc = sink->group(s, scratch, g)) { (void)hipStreamSynchronize(s); return rc; }
+        }
+        tm.begin(DEPTH_T_DOWNLOAD);
+        if (!sink || sink->maps) {
+            UNIT_TRY(hipMemcpyAsync(depth + at, d_depth, sizeof(float) * (size_t)out_px, hipMemcpyDeviceToHost, s));
+            UNIT_TRY(hipMemcpyAsync(score + at, d_score, sizeof(float) * (size_t)out_px, hipMemcpyDeviceToHost, s));
+            if (plane) UNIT_TRY(hipMemcpyAsync(plane + at, d_plane, sizeof(int16_t) * (size_t)out_px, hipMemcpyDeviceToHost, s));
+        }
         tm.end();
         UNIT_TRY(hipStreamSynchronize(s));                    // the group's arena goes back to the cache below
         j0 = j1;

@@ -55,6 +55,9 @@
 //                 views of the fuse are the job's sources.  The defaults of DenseParams (64 planes, radius 3, min_std 2,
 //                 min_score 0.6, min_sources 1, rel_tol 0.01, min_consistent 1) are first choices like the merge distance above:
 //                 nobody has tuned them.  Nothing is de-duplicated: a surface point seen by three views appears three times.
+//                 With DenseParams::sgm set (OFF by default) the ONE sweep call is sfmba_depth_sweep_sgm with sgmP1, sgmP2, sgmPaths,
+//                 sgmInvalidCost and sgmUniqueness (8, 64, 8, 127, 5: untuned too): semi-global matching over the cost volume, a
+//                 plane for every pixel, min_score not read; the jobs, the fuse and everything after it are the same.
 //   merged        mergeDenseCloud(voxel, minCount, maxRelStep) after a densify that returned OKAY: ONE sfmba_depth_normals call over
 //                 the depth maps, every dense point takes the normal of its own pixel (through views / pixels of the dense cloud),
 //                 then ONE sfmba_cloud_merge (include/sfmba.h): one oriented point per occupied voxel.  voxel == 0 means AUTO, the

@@ -77,9 +77,14 @@ bool SfMDenseUtilities::computeDepthMaps(const std::vector<cv::Mat>& images, con
     if (jobs.empty()) return true;
     src.push_back(0);                                      // never read: keeps data() non-null
     std::vector<float> depth((size_t)pixels), score((size_t)pixels);
-    const int rc = sfmba_depth_sweep(0, (int)images.size(), f.ptr.data(), f.px.data(), f.w.data(), f.h.data(), f.channels, f.K, f.P.data(),
-                                     (int)jobs.size(), ref.data(), srcPtr.data(), src.data(), zNear.data(), zFar.data(), params.planes, params.radius,
-                                     params.minStd, params.minScore, params.minSources, depth.data(), score.data(), nullptr);
+    const int rc = params.sgm
+        ? sfmba_depth_sweep_sgm(0, (int)images.size(), f.ptr.data(), f.px.data(), f.w.data(), f.h.data(), f.channels, f.K, f.P.data(),
+                                (int)jobs.size(), ref.data(), srcPtr.data(), src.data(), zNear.data(), zFar.data(), params.planes, params.radius,
+                                params.minStd, params.minSources, params.sgmP1, params.sgmP2, params.sgmPaths, params.sgmInvalidCost,
+                                params.sgmUniqueness, depth.data(), score.data(), nullptr)
+        : sfmba_depth_sweep(0, (int)images.size(), f.ptr.data(), f.px.data(), f.w.data(), f.h.data(), f.channels, f.K, f.P.data(),
+                            (int)jobs.size(), ref.data(), srcPtr.data(), src.data(), zNear.data(), zFar.data(), params.planes, params.radius,
+                            params.minStd, params.minScore, params.minSources, depth.data(), score.data(), nullptr);
     if (rc != SFMBA_OK) {
         std::fprintf(stderr, "computeDepthMaps failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
         return false;

@@ -30,7 +30,17 @@ struct DenseParams {
     float relTol;           // fuse: relative depth difference that still agrees, >= 0
     int   minConsistent;    // fuse: agreeing check views a pixel needs, 0..4
     int   maxSources;       // SfM::densify: the nearest other good views swept against, 1..4
-    DenseParams() : planes(64), radius(3), minStd(2), minScore(0.6f), minSources(1), relTol(0.01f), minConsistent(1), maxSources(2) {}
+    // Semi-global matching over the sweep's cost volume (include/sfmba.h, sfmba_depth_sweep_sgm), OFF by default: with `sgm` unset
+    // computeDepthMaps makes the sfmba_depth_sweep call it always made and none of the fields below is read.  With it set every pixel
+    // of a reference view gets a plane -- one without texture takes what its neighbours agree on -- minScore is not read, and the
+    // score map holds 0 where the depth came from the neighbours alone.
+    bool  sgm;
+    int   sgmP1, sgmP2;     // the penalty for a change of one plane and for any other change, 0 <= sgmP1 <= sgmP2 <= 1023
+    int   sgmPaths;         // path directions, 4 or 8
+    int   sgmInvalidCost;   // what a plane without a cost reads as, 0..254
+    int   sgmUniqueness;    // accepted iff 100 (second - best) >= sgmUniqueness * second, 0..100
+    DenseParams() : planes(64), radius(3), minStd(2), minScore(0.6f), minSources(1), relTol(0.01f), minConsistent(1), maxSources(2), sgm(false),
+                    sgmP1(8), sgmP2(64), sgmPaths(8), sgmInvalidCost(127), sgmUniqueness(5) {}
 };
 
 // The fused points in (view, row, column) order.  A surface point seen by three views appears three times: nothing is de-duplicated

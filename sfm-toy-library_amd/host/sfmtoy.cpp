@@ -5,6 +5,7 @@
 // <prefix>_mesh_clean.ply; with --texture on top of --mesh, put the photographs on the mesh (the clean one with --mesh-clean) and write
 // <prefix>_textured.obj, .mtl and .png.  The arguments are parsed here
 // (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
+#include <cctype>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -30,6 +31,11 @@ void usage(std::ostream& os, const char* program) {
        << "                               the images and a snap to key points, for frame sequences; a match's distance is <= 2 px)\n"
        << "  -w, --flow-window N          with -M flow: match view i with views i+1 .. i+N only (default 0: all pairs)\n"
        << "  -D, --dense                  also densify (plane-sweep depth maps of the registered views, fused) and write PREFIX_dense.ply\n"
+       << "      --sgm [P1,P2]            with -D: regularise the depth maps by semi-global matching over the sweep's cost volume, with the\n"
+       << "                               penalties P1 <= P2 in 0..1023 (default 8,64); every pixel then gets a plane, one without texture\n"
+       << "                               from its neighbours; NO LEFT-RIGHT CHECK, the fuse is the cross-check\n"
+       << "      --sgm-paths 4|8          with --sgm: path directions (default 8)\n"
+       << "      --sgm-uniqueness U       with --sgm: a pixel needs 100 (second - best) >= U * second, 0..100 (default 5)\n"
        << "      --voxel SIZE             with -D: also merge the dense cloud into one oriented point per voxel of edge SIZE (0 = the\n"
        << "                               footprint of a pixel at the typical depth) and write PREFIX_dense_merged.ply\n"
        << "      --mesh RES               with -D: also mesh the depth maps (TSDF fusion and marching tetrahedra on a grid of RES vertices\n"
@@ -71,11 +77,12 @@ bool number(const std::string& text, double& value) {
 int main(int argc, char** argv) {
     std::string directory, prefix = "output", text;
     double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0, voxel = 0.0, resolution = 256.0,
-           min_component = 0.0, smooth = 10.0, fill = 0.0, fill_neighbours = 2.0, patch = 6.0;
+           min_component = 0.0, smooth = 10.0, fill = 0.0, fill_neighbours = 2.0, patch = 6.0, sgm_p1 = 8.0, sgm_p2 = 64.0, sgm_paths = 8.0,
+           sgm_uniqueness = 5.0;
     FeatureType features = FEATURES_ORB;
     MatcherType matcher = MATCHER_DESCRIPTORS;
     bool have_directory = false, dense = false, merged = false, meshed = false, cleaned = false, clean_option = false, keep_largest = false,
-         filled = false, fill_option = false, textured = false;
+         filled = false, fill_option = false, textured = false, sgm = false, sgm_option = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
         const std::string arg = argv[i];
@@ -96,6 +103,22 @@ int main(int argc, char** argv) {
             }
             continue;
         }
+        if (arg == "--sgm" || arg.compare(0, 6, "--sgm=") == 0) {
+            // the value is optional: "--sgm=P1,P2", or a next argument made of digits around a comma (a directory named 2024 is none)
+            sgm = true;
+            text = arg.size() > 6 ? arg.substr(6) : "";
+            if (arg == "--sgm" && i + 1 < argc && std::isdigit((unsigned char)argv[i + 1][0]) &&
+                std::string(argv[i + 1]).find(',') != std::string::npos && std::string(argv[i + 1]).find_first_not_of("0123456789,") == std::string::npos)
+                text = argv[++i];
+            else if (arg == "--sgm")
+                continue;
+            const size_t comma = text.find(',');
+            if (comma == std::string::npos || !number(text.substr(0, comma), sgm_p1) || !number(text.substr(comma + 1), sgm_p2) || !(sgm_p1 >= 0.0) ||
+                !(sgm_p1 <= sgm_p2) || !(sgm_p2 <= 1023.0) || sgm_p1 != (double)(int)sgm_p1 || sgm_p2 != (double)(int)sgm_p2) {
+                std::cerr << argv[0] << ": --sgm has a value that cannot be used\n"; usage(std::cerr, argv[0]); return 2;
+            }
+            continue;
+        }
         if (option(argc, argv, i, "-p", "--input-directory", text, missing)) { directory = text; have_directory = !missing; }
         else if (option(argc, argv, i, "-o", "--output-prefix", text, missing)) prefix = text;
         else if (option(argc, argv, i, "-s", "--downscale", text, missing)) bad = !missing && (!number(text, downscale) || !(downscale > 0.0));
@@ -111,6 +134,14 @@ int main(int argc, char** argv) {
         else if (option(argc, argv, i, "-w", "--flow-window", text, missing))
             bad = !missing && (!number(text, window) || !(window >= 0.0) || !(window <= 1.0e6) || window != (double)(int)window);
         else if (option(argc, argv, i, "-m", "--merge-distance", text, missing)) bad = !missing && (!number(text, merge) || !(merge >= 0.0) || !(merge <= 3.0e38));
+        else if (option(argc, argv, i, "--sgm-paths", "--sgm-paths", text, missing)) {
+            bad = !missing && (!number(text, sgm_paths) || (sgm_paths != 4.0 && sgm_paths != 8.0));
+            sgm_option = true;
+        }
+        else if (option(argc, argv, i, "--sgm-uniqueness", "--sgm-uniqueness", text, missing)) {
+            bad = !missing && (!number(text, sgm_uniqueness) || !(sgm_uniqueness >= 0.0) || !(sgm_uniqueness <= 100.0) || sgm_uniqueness != (double)(int)sgm_uniqueness);
+            sgm_option = true;
+        }
         else if (option(argc, argv, i, "--voxel", "--voxel", text, missing)) {
             bad = !missing && (!number(text, voxel) || !(voxel >= 0.0) || !(voxel <= 3.0e38));
             merged = true;
@@ -141,6 +172,8 @@ int main(int argc, char** argv) {
         else { std::cerr << argv[0] << ": more than one input directory\n"; usage(std::cerr, argv[0]); return 2; }
         if (missing || bad) { std::cerr << argv[0] << ": " << arg << (missing ? " needs a value\n" : " has a value that cannot be used\n"); usage(std::cerr, argv[0]); return 2; }
     }
+    if (sgm && !dense) { std::cerr << argv[0] << ": --sgm needs -D\n"; usage(std::cerr, argv[0]); return 2; }
+    if (sgm_option && !sgm) { std::cerr << argv[0] << ": --sgm-paths and --sgm-uniqueness need --sgm\n"; usage(std::cerr, argv[0]); return 2; }
     if (merged && !dense) { std::cerr << argv[0] << ": --voxel needs -D\n"; usage(std::cerr, argv[0]); return 2; }
     if (meshed && !dense) { std::cerr << argv[0] << ": --mesh needs -D\n"; usage(std::cerr, argv[0]); return 2; }
     if (filled && !meshed) { std::cerr << argv[0] << ": --mesh-fill needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
@@ -160,7 +193,13 @@ int main(int argc, char** argv) {
     if (sfm.runSfM() != OKAY) return 1;
     if (!sfm.saveCloudAndCamerasToPLY(prefix)) return 1;
     if (!dense) return 0;
-    if (sfm.densify() != OKAY) return 1;
+    DenseParams dense_params;
+    dense_params.sgm = sgm;
+    dense_params.sgmP1 = (int)sgm_p1;
+    dense_params.sgmP2 = (int)sgm_p2;
+    dense_params.sgmPaths = (int)sgm_paths;
+    dense_params.sgmUniqueness = (int)sgm_uniqueness;
+    if (sfm.densify(dense_params) != OKAY) return 1;
     if (!sfm.saveDenseCloudToPLY(prefix)) return 1;
     if (merged) {
         if (sfm.mergeDenseCloud((float)voxel) != OKAY) return 1;

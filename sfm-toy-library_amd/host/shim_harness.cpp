@@ -676,13 +676,15 @@ int sfmba_shim_run_sfm_typed(int feature_type, float merge_distance, int n_views
 // where a view has none) and the dense cloud (cap_dense rows: dense_xyz [..][3], dense_bgr [..][3], dense_view, dense_pixel).
 // ply_prefix != NULL: saveCloudAndCamerasToPLY and saveDenseCloudToPLY.  Returns as sfmba_shim_run_sfm; 10 + densify's code when the
 // run was OKAY and densify was not.
-extern "C" __attribute__((visibility("default")))
-int sfmba_shim_run_sfm_dense(int feature_type, float merge_distance, int n_views, int channels, const int64_t* img_ptr, const unsigned char* px,
-                             const int32_t* w, const int32_t* h, int debug_level, float* poses, float* K, unsigned char* done, unsigned char* good,
-                             int* n_added, int32_t* added_view, unsigned char* added_posed, int64_t* added_cloud, int64_t cap_pts, int64_t cap_views,
-                             int64_t* n_pts, float* xyz, int64_t* view_ptr, int32_t* view_idx, int32_t* feat_idx, const char* ply_prefix, int* n_jobs,
-                             int32_t* job_ref, int64_t* job_src_ptr, int32_t* job_src, float* z_near, float* z_far, unsigned char* has_map, float* depth,
-                             int64_t cap_dense, int64_t* n_dense, float* dense_xyz, unsigned char* dense_bgr, int32_t* dense_view, int32_t* dense_pixel) {
+// the body of sfmba_shim_run_sfm_dense and sfmba_shim_run_sfm_dense_sgm: `dense` goes to densify; mesh_resolution > 0 also runs
+// meshDenseCloud at that resolution and *n_triangles receives its triangle count
+static int runDense(const sfmtoylib::DenseParams& dense, int mesh_resolution, int64_t* n_triangles, int feature_type, float merge_distance, int n_views,
+                    int channels, const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h, int debug_level, float* poses,
+                    float* K, unsigned char* done, unsigned char* good, int* n_added, int32_t* added_view, unsigned char* added_posed,
+                    int64_t* added_cloud, int64_t cap_pts, int64_t cap_views, int64_t* n_pts, float* xyz, int64_t* view_ptr, int32_t* view_idx,
+                    int32_t* feat_idx, const char* ply_prefix, int* n_jobs, int32_t* job_ref, int64_t* job_src_ptr, int32_t* job_src, float* z_near,
+                    float* z_far, unsigned char* has_map, float* depth, int64_t cap_dense, int64_t* n_dense, float* dense_xyz, unsigned char* dense_bgr,
+                    int32_t* dense_view, int32_t* dense_pixel) {
     using namespace sfmtoylib;
     SfM sfm(1.0f);
     sfm.setConsoleDebugLevel((unsigned)debug_level);
@@ -696,7 +698,7 @@ int sfmba_shim_run_sfm_dense(int feature_type, float merge_distance, int n_views
     const int rc = flattenRun(sfm, sfm.runSfM(), n_views, poses, K, done, good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts,
                               xyz, view_ptr, view_idx, feat_idx, ply_prefix);
     if (rc != 0) return rc;
-    const ErrorCode code = sfm.densify();
+    const ErrorCode code = sfm.densify(dense);
     if (code != OKAY) return 10 + (int)code;
     job_src_ptr[0] = 0;
     for (const DenseJob& j : sfm.getDenseJobs()) {
@@ -723,7 +725,47 @@ int sfmba_shim_run_sfm_dense(int feature_type, float merge_distance, int n_views
         dense_view[i] = cloud.views[i]; dense_pixel[i] = cloud.pixels[i];
     }
     if (ply_prefix && !sfm.saveDenseCloudToPLY(ply_prefix)) return -3;
+    if (mesh_resolution > 0) {
+        MeshParams mesh;
+        mesh.resolution = mesh_resolution;
+        const ErrorCode meshed = sfm.meshDenseCloud(mesh);
+        if (meshed != OKAY) return 20 + (int)meshed;
+        *n_triangles = (int64_t)sfm.getMesh().triangles.size() / 3;
+    }
     return 0;
+}
+
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_dense(int feature_type, float merge_distance, int n_views, int channels, const int64_t* img_ptr, const unsigned char* px,
+                             const int32_t* w, const int32_t* h, int debug_level, float* poses, float* K, unsigned char* done, unsigned char* good,
+                             int* n_added, int32_t* added_view, unsigned char* added_posed, int64_t* added_cloud, int64_t cap_pts, int64_t cap_views,
+                             int64_t* n_pts, float* xyz, int64_t* view_ptr, int32_t* view_idx, int32_t* feat_idx, const char* ply_prefix, int* n_jobs,
+                             int32_t* job_ref, int64_t* job_src_ptr, int32_t* job_src, float* z_near, float* z_far, unsigned char* has_map, float* depth,
+                             int64_t cap_dense, int64_t* n_dense, float* dense_xyz, unsigned char* dense_bgr, int32_t* dense_view, int32_t* dense_pixel) {
+    return runDense(sfmtoylib::DenseParams(), 0, nullptr, feature_type, merge_distance, n_views, channels, img_ptr, px, w, h, debug_level, poses, K, done,
+                    good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts, xyz, view_ptr, view_idx, feat_idx, ply_prefix, n_jobs,
+                    job_ref, job_src_ptr, job_src, z_near, z_far, has_map, depth, cap_dense, n_dense, dense_xyz, dense_bgr, dense_view, dense_pixel);
+}
+
+// sfmba_shim_run_sfm_dense with the semi-global matching fields of DenseParams set from sgm [6] = sgm (0 / 1), sgmP1, sgmP2, sgmPaths,
+// sgmInvalidCost, sgmUniqueness (tests/test_gpu_sgm_pipeline.py); mesh_resolution > 0 also runs meshDenseCloud on the depth maps
+// (*n_triangles: the mesh's triangles; 20 + its code when it fails).
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_dense_sgm(const int32_t* sgm, int mesh_resolution, int64_t* n_triangles, int feature_type, float merge_distance, int n_views,
+                                 int channels, const int64_t* img_ptr, const unsigned char* px, const int32_t* w, const int32_t* h, int debug_level,
+                                 float* poses, float* K, unsigned char* done, unsigned char* good, int* n_added, int32_t* added_view,
+                                 unsigned char* added_posed, int64_t* added_cloud, int64_t cap_pts, int64_t cap_views, int64_t* n_pts, float* xyz,
+                                 int64_t* view_ptr, int32_t* view_idx, int32_t* feat_idx, const char* ply_prefix, int* n_jobs, int32_t* job_ref,
+                                 int64_t* job_src_ptr, int32_t* job_src, float* z_near, float* z_far, unsigned char* has_map, float* depth,
+                                 int64_t cap_dense, int64_t* n_dense, float* dense_xyz, unsigned char* dense_bgr, int32_t* dense_view,
+                                 int32_t* dense_pixel) {
+    sfmtoylib::DenseParams dense;
+    dense.sgm = sgm[0] != 0;
+    dense.sgmP1 = sgm[1]; dense.sgmP2 = sgm[2]; dense.sgmPaths = sgm[3]; dense.sgmInvalidCost = sgm[4]; dense.sgmUniqueness = sgm[5];
+    *n_triangles = 0;
+    return runDense(dense, mesh_resolution, n_triangles, feature_type, merge_distance, n_views, channels, img_ptr, px, w, h, debug_level, poses, K, done,
+                    good, n_added, added_view, added_posed, added_cloud, cap_pts, cap_views, n_pts, xyz, view_ptr, view_idx, feat_idx, ply_prefix, n_jobs,
+                    job_ref, job_src_ptr, job_src, z_near, z_far, has_map, depth, cap_dense, n_dense, dense_xyz, dense_bgr, dense_view, dense_pixel);
 }
 
 // setImages, runSfM, densify() and mergeDenseCloud(voxel, min_count, max_rel_step) in one call (tests/test_gpu_cloud_pipeline.py).
