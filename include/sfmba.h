@@ -150,7 +150,8 @@ typedef struct sfmba_options {
        thread-safely).  0 = library default, 1 = on, -1 = off.  ABI v4 let the environment variable named beside each switch
        override the field; since ABI v5 NOTHING below sfmba_problem_create* reads the environment: the fields are the only way
        (what is still read from the environment, when a problem is BUILT: SFMBA_DETERMINISTIC, SFMBA_PAIR_LPB, SFMBA_PAIR_LOADS, SFMBA_PAIR_LIMIT,
-       SFMBA_BUILD_TIMING). ---- */
+       SFMBA_BUILD_TIMING; and per call of a front-end unit that works in groups the test hooks SFMBA_GROUP_BYTES and SFMBA_GROUP_ITEMS, which
+       can only lower the scratch budget and the item cap of a group and never change an output). ---- */
     int    pcg_coarse_space;          /* SFMBA_PCG_COARSE         default on : two-level CG preconditioner (8 gauge vectors).  Where the reduced
                                          matrix is sparsely filled (< 1/2 of its blocks) with >= 90 % of the blocks within a quarter of the cyclic camera
                                          order -- views registered along a path -- and >= 32 cameras, the seven similarity vectors are used restricted to

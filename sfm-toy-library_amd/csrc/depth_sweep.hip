@@ -269,6 +269,8 @@ int depth_sweep(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
     for (int j = 0; j < n_jobs; ++j) out_off[(size_t)j + 1] = out_off[(size_t)j] + (long long)width[job_ref[j]] * height[job_ref[j]];
 
     PhaseTimer tm{ s, timing != nullptr, {}, {} };
+    const long long group_bytes = group_bytes_limit(DEPTH_SCRATCH_BYTES);
+    const int group_jobs = group_items_limit(DEPTH_MAX_GROUP_JOBS);
     int n_groups = 0;
     std::vector<long long> slot((size_t)n_images, -1);       // first gray byte of an image in the group, -1: not in it
     for (int j0 = 0; j0 < n_jobs;) {
@@ -277,7 +279,7 @@ int depth_sweep(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
         std::vector<int> used;
         long long raw_bytes = 0, gray_bytes = 0, out_px = 0, max_tiles = 0;
         int j1 = j0;
-        while (j1 < n_jobs && j1 - j0 < DEPTH_MAX_GROUP_JOBS) {
+        while (j1 < n_jobs && j1 - j0 < group_jobs) {
             long long add_raw = 0, add_gray = 0;
             std::vector<int> fresh;
             auto want = [&](int i) {
@@ -291,7 +293,7 @@ int depth_sweep(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
             const long long px = out_off[(size_t)j1 + 1] - out_off[(size_t)j1];
             long long bytes = raw_bytes + gray_bytes + add_raw + add_gray + 10 * (out_px + px);
             if (sink) bytes += (long long)(1 + sink->extra_bytes_per_entry) * n_planes * (out_px + px);   // the volume and what the sink adds
-            if (j1 > j0 && bytes > (long long)DEPTH_SCRATCH_BYTES) break;
+            if (j1 > j0 && bytes > group_bytes) break;
             for (int i : fresh) {
                 slot[(size_t)i] = gray_bytes;
                 gray_bytes += align64((long long)width[i] * height[i]);

@@ -13,7 +13,8 @@ namespace sfmba {
 // return values besides 0 (ok) and positive hipError_t codes: UNIT_ERR_* of unit_common.h
 
 // Pairs go to the device in consecutive groups.  A group's arrays (the pixels of the images its pairs name, their pyramids, the
-// points and what is written per point) stay within this bound; a pair that exceeds it alone forms a group of its own.
+// points and what is written per point) stay within this bound; a pair that exceeds it alone forms a group of its own.  The unit
+// caps the images of a group (65535, grid.y), not its pairs; the test hook SFMBA_GROUP_ITEMS (unit_common.h) counts pairs here.
 constexpr size_t FLOW_SCRATCH_BYTES = (size_t)512 << 20;
 constexpr int FLOW_MATCH_TILE = 256;           // key points of an LDS stage of the matcher
 constexpr int FLOW_MATCH_QUERIES = 64;         // queries of a workgroup: one lane each

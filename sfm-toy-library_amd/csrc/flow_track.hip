@@ -295,6 +295,8 @@ int flow_track(hipStream_t s, int device, int n_images, const int64_t* img_ptr, 
     const long long per_point = 8 + 8 + 1 + 4 + (dbg_G ? 24ll * L : 0) + (dbg_state ? 16ll * L : 0);
 
     PhaseTimer tm{ s, timing != nullptr, {}, {} };
+    const long long group_bytes = group_bytes_limit(FLOW_SCRATCH_BYTES);
+    const int group_pairs = group_items_limit(INT_MAX);      // the unit itself caps the images of a group, not its pairs: the hook counts pairs
     int n_groups = 0;
     std::vector<int> slot((size_t)n_images, -1);              // an image's row in the group's table, -1: not in it
     for (int p0 = 0; p0 < n_pairs;) {
@@ -304,7 +306,7 @@ int flow_track(hipStream_t s, int device, int n_images, const int64_t* img_ptr, 
         std::vector<FlowImage> tab;
         long long raw_bytes = 0, pyr_bytes = 0, n_pts = 0;
         int p1 = p0;
-        while (p1 < n_pairs) {
+        while (p1 < n_pairs && p1 - p0 < group_pairs) {
             long long add_raw = 0, add_pyr = 0;
             int fresh[2], n_fresh = 0;
             for (int i : { pair_src[p1], pair_dst[p1] }) {
@@ -316,7 +318,7 @@ int flow_track(hipStream_t s, int device, int n_images, const int64_t* img_ptr, 
             }
             const long long np = pt_ptr[p1 + 1] - pt_ptr[p1];
             const long long bytes = raw_bytes + pyr_bytes + add_raw + add_pyr + per_point * (n_pts + np);
-            if (p1 > p0 && (bytes > (long long)FLOW_SCRATCH_BYTES || n_pts + np >= (long long)INT_MAX || used.size() + n_fresh > 65535)) break;   // grid.y
+            if (p1 > p0 && (bytes > group_bytes || n_pts + np >= (long long)INT_MAX || used.size() + n_fresh > 65535)) break;   // grid.y
             for (int q = 0; q < n_fresh; ++q) {
                 const int i = fresh[q];
                 FlowImage T;

@@ -395,11 +395,13 @@ int orb_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr,
     UNIT_TRY(hipMemcpyAsync(d_stage_cur, stage_base.data(), sizeof(long long) * (size_t)n_images, hipMemcpyHostToDevice, s));
     tm.end();
 
+    const long long group_bytes = group_bytes_limit(ORB_SCRATCH_BYTES);
+    const int group_items = group_items_limit(ORB_MAX_GROUP_IMAGES);
     int n_groups = 0;
     for (int i0 = 0; i0 < n_images;) {
         int i1 = i0 + 1;
         long long bytes = plan[(size_t)i0].scratch;
-        while (i1 < n_images && i1 - i0 < ORB_MAX_GROUP_IMAGES && bytes + plan[(size_t)i1].scratch <= (long long)ORB_SCRATCH_BYTES)
+        while (i1 < n_images && i1 - i0 < group_items && bytes + plan[(size_t)i1].scratch <= group_bytes)
             bytes += plan[(size_t)i1++].scratch;
         const int ng = i1 - i0;
         ++n_groups;

@@ -243,6 +243,8 @@ int png_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr,
     if (*total > cap) return UNIT_ERR_CAPACITY;
 
     PhaseTimer tm{ s, timing != nullptr, {}, {} };
+    const long long group_bytes = group_bytes_limit(JPEG_SCRATCH_BYTES);
+    const int group_items = group_items_limit(JPEG_MAX_GROUP_IMAGES);
     int n_groups = 0;
     auto scratch_of = [&](int i) -> long long {
         const PngHeader& H = hdr[(size_t)i];
@@ -253,7 +255,7 @@ int png_decode(hipStream_t s, int device, int n_images, const int64_t* file_ptr,
     for (int i0 = 0; i0 < n_images;) {
         int i1 = i0 + 1;
         long long budget = scratch_of(i0);
-        while (i1 < n_images && i1 - i0 < JPEG_MAX_GROUP_IMAGES && budget + scratch_of(i1) <= (long long)JPEG_SCRATCH_BYTES) budget += scratch_of(i1++);
+        while (i1 < n_images && i1 - i0 < group_items && budget + scratch_of(i1) <= group_bytes) budget += scratch_of(i1++);
         std::vector<int> member;                                 // the decodable images of the group
         for (int i = i0; i < i1; ++i) if (hdr[(size_t)i].status == PNG_OK) member.push_back(i);
         i0 = i1;

@@ -269,11 +269,13 @@ int surf_extract(hipStream_t s, int device, int n_images, const int64_t* img_ptr
     std::vector<long long> h_mom, h_sums;
     double response_bytes = 0.0;
 
+    const long long group_bytes = group_bytes_limit(SURF_SCRATCH_BYTES);
+    const int group_items = group_items_limit(SURF_MAX_GROUP_IMAGES);
     int n_groups = 0;
     for (int i0 = 0; i0 < n_images;) {
         int i1 = i0 + 1;
         long long bytes = plan[(size_t)i0].scratch;
-        while (i1 < n_images && i1 - i0 < SURF_MAX_GROUP_IMAGES && bytes + plan[(size_t)i1].scratch <= (long long)SURF_SCRATCH_BYTES)
+        while (i1 < n_images && i1 - i0 < group_items && bytes + plan[(size_t)i1].scratch <= group_bytes)
             bytes += plan[(size_t)i1++].scratch;
         const int ng = i1 - i0;
         ++n_groups;

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cerrno>
+#include <cstdlib>
 #include <vector>
 
 namespace sfmba {
@@ -23,6 +25,22 @@ enum {
 #define UNIT_DRAIN_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipStreamSynchronize(s); return (int)e_; } } while (0)
 #define UNIT_DRAIN_ALLOC(arena, ptr, T, n) \
     do { ptr = (arena).alloc_n<T>(n); if (!ptr) { (void)hipStreamSynchronize(s); return (int)hipErrorOutOfMemory; } } while (0)
+
+// The limits of a group of the units that take their images, jobs or pairs in consecutive groups (orb_extract.hip ... flow_track.hip).
+// SFMBA_GROUP_BYTES and SFMBA_GROUP_ITEMS are test hooks that lower the unit's scratch budget and its cap on the items of a group, so
+// that the multi-group path runs at test size; read once per call.  Only a positive decimal integer below the unit's constant
+// counts: anything else (absent, empty, zero, negative, not a number, trailing text) leaves the constant, so a limit is never
+// raised.  The first item of a group enters it whatever the limits say.
+inline long long group_limit_from(const char* text, long long unit_limit) {
+    if (!text || !*text) return unit_limit;
+    char* end = nullptr;
+    errno = 0;
+    const long long v = std::strtoll(text, &end, 10);
+    if (errno != 0 || end == text || *end != '\0' || v <= 0) return unit_limit;
+    return v < unit_limit ? v : unit_limit;
+}
+inline long long group_bytes_limit(size_t unit_bytes) { return group_limit_from(std::getenv("SFMBA_GROUP_BYTES"), (long long)unit_bytes); }
+inline int group_items_limit(int unit_items) { return (int)group_limit_from(std::getenv("SFMBA_GROUP_ITEMS"), unit_items); }
 
 // HIP-event time per phase, summed; inert without a timing array.  begin / end bracket one phase; next ends the open phase and
 // begins another on the same event, so consecutive phases leave no gap.

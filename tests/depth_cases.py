@@ -122,10 +122,16 @@ def oracle(name):
     return do.sweep_integral(c["images"], c["K"], c["P"], c["jobs"][0], **c["params"])
 
 
-def batch():
-    """Five mixed jobs over one image list: different references, source counts, ranges and sizes."""
-    images, K, P = scene((33, 20), 3, src_size=(28, 25), seed=3)
+def batch(extended=False):
+    """Five mixed jobs over one image list: different references, source counts, ranges and sizes.
+
+    extended: two more images and two more jobs behind the same five (tests/group_cases.py).  With two jobs to a group image 1 is the
+    reference of job 1 and a source of job 2 in the next group, image 0 is named by jobs of all four groups, and job 5, the second
+    of its group, names two images (4 and 5) that no job before it names."""
+    images, K, P = scene((33, 20), 5 if extended else 3, src_size=(28, 25), seed=3)
     jobs = [(0, [1], Z_NEAR, Z_FAR), (1, [0, 2], 7.5, 13.0), (2, [0, 1, 3], Z_NEAR, Z_FAR), (3, [0], 9.0, 11.0), (0, [3, 2, 1], 8.5, 12.0)]
+    if extended:
+        jobs += [(4, [5], 8.25, 12.25), (5, [4, 0], 7.75, 12.75)]
     return dict(images=images, K=K, P=P, jobs=jobs, params=dict(n_planes=16, radius=2, min_std=2, min_score=0.6, min_sources=1))
 
 
