@@ -387,6 +387,27 @@ SFMBA_API int sfmba_problem_build_reduced(sfmba_problem* p, const sfmba_options*
  * *info = k > 0 if the leading minor of order k is not positive definite. */
 SFMBA_API int sfmba_dense_spd_solve(int device, int n, const double* A, const double* b, double* x,
                           int method, double pcg_tol, int pcg_max_iters, int* info, int* iters);
+/* The reduced-system CG in isolation (a kernel-level hook for parity tests, like the one above): A [n*n] row-major symmetric positive
+ * definite (the upper triangle is read), nrhs right-hand sides B [nrhs][n] solved one after another on ONE workspace -> X [nrhs][n] (the
+ * solution in the unknowns of A, after the block-Jacobi back-transform).  The call sets what a handle sets per solve and then goes
+ * through the library's own transform, path choice and family launches:
+ *   Wt        [8][n] coarse vectors in the TRANSFORMED unknowns (x~ = Lb^T x, Lb = the Cholesky factors of the 6 x 6 diagonal blocks and
+ *             the square root of a trailing scalar), fp32-representable values; NULL: no coarse space
+ *             (with SFMBA_PCG_PROBE_SEGMENTS vectors 0 .. 6 must be zero at the trailing unknown, as the gauge vectors of a problem are)
+ *   flags     SFMBA_PCG_PROBE_SYMMETRIC   the one-triangle streaming family where it applies (a non-deterministic handle's default)
+ *             SFMBA_PCG_PROBE_F32_MATRIX  the transformed matrix is kept in fp32 where the family reads it so (n > 1280)
+ *             SFMBA_PCG_PROBE_SEGMENTS    the segmented coarse space where it applies (needs Wt)
+ *             SFMBA_PCG_PROBE_POISON      after the transform, NaN goes into everything the kernels promise not to multiply: columns >= n of
+ *                                         the padded matrix and of the coarse vectors, the allocation slack behind both, and -- where the
+ *                                         symmetric family runs -- the strict lower triangle
+ *   tol       plain relative residual |r~| <= tol |b~| (not anchored)
+ *   max_iters [nrhs], each in 1 .. 1000: solve i stops after max_iters[i] iterations at the latest and X[i] is the iterate it reached
+ *   info      as sfmba_dense_spd_solve; iters [nrhs] or NULL: iterations per solve; path or NULL: family, f32_matrix, coarse_vectors of the
+ *             last solve (cg_iters = its iterations).
+ * A launch the runtime refuses is SFMBA_ERR_HIP at once; a size no family can launch is SFMBA_ERR_INVALID_ARG. */
+enum { SFMBA_PCG_PROBE_SYMMETRIC = 1, SFMBA_PCG_PROBE_F32_MATRIX = 2, SFMBA_PCG_PROBE_SEGMENTS = 4, SFMBA_PCG_PROBE_POISON = 8 };
+SFMBA_API int sfmba_dense_pcg_probe(int device, int n, const double* A, int nrhs, const double* B, const double* Wt, int flags, double tol,
+                                    const int* max_iters, double* X, int* info, int* iters, sfmba_step_probe* path);
 
 /*
  * Sharded API (multi-GPU): every rank holds the observations of a disjoint set of points

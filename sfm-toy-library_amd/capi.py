@@ -25,7 +25,7 @@ SYMBOLS = [
     "sfmba_problem_create", "sfmba_problem_reset", "sfmba_problem_set_params", "sfmba_problem_solve",
     "sfmba_problem_get_params", "sfmba_problem_destroy", "sfmba_problem_stream", "sfmba_problem_reduced_dim",
     "sfmba_problem_eval_residuals", "sfmba_problem_eval_jacobian", "sfmba_problem_build_reduced",
-    "sfmba_dense_spd_solve", "sfmba_shard_begin", "sfmba_shard_reduce_len", "sfmba_shard_reduce_buf",
+    "sfmba_dense_spd_solve", "sfmba_dense_pcg_probe", "sfmba_shard_begin", "sfmba_shard_reduce_len", "sfmba_shard_reduce_buf",
     "sfmba_shard_scalars_buf", "sfmba_shard_partial_build", "sfmba_shard_solve_update", "sfmba_shard_finish",
     "sfmba_shard_end", "sfmba_problem_set_profiling", "sfmba_problem_get_profile",
     "sfmba_problem_create_sharded", "sfmba_shard_setup_finish", "sfmba_shard_setup_len", "sfmba_shard_setup_buf", "sfmba_release_cache", "sfmba_triangulate",
@@ -1400,6 +1400,29 @@ def dense_spd_solve(A, b, method=0, tol=1e-12, max_iters=0, device=0):
     _check(lib().sfmba_dense_spd_solve(C.c_int(device), C.c_int(n), _p(A, _dp), _p(b, _dp), _p(x, _dp), C.c_int(method),
                                        C.c_double(tol), C.c_int(max_iters), C.byref(info), C.byref(iters)))
     return x, info.value, iters.value
+
+
+PCG_PROBE_SYMMETRIC, PCG_PROBE_F32_MATRIX, PCG_PROBE_SEGMENTS, PCG_PROBE_POISON = 1, 2, 4, 8
+
+
+def dense_pcg_probe(A, B, Wt=None, flags=0, tol=1e-10, max_iters=200, device=0):
+    """sfmba_dense_pcg_probe: the reduced-system CG on A [n, n] for the right-hand sides B [nrhs, n] (or [n]), one after another on one workspace.
+    Wt: None or [8, n] coarse vectors in the transformed unknowns; flags: PCG_PROBE_*; max_iters: one int or one per right-hand side.
+    Returns (X [nrhs, n], info, iters [nrhs], path dict: family, family_name, f32_matrix, coarse_vectors, cg_iters)."""
+    A = _d(A)
+    B = np.ascontiguousarray(np.atleast_2d(np.asarray(B, dtype=np.float64)))
+    nrhs, n = B.shape
+    if A.shape != (n, n) or (Wt is not None and np.shape(Wt) != (8, n)):
+        raise ValueError("A, B and Wt do not fit together")
+    W = None if Wt is None else np.ascontiguousarray(Wt, dtype=np.float64)
+    mi = _i(np.broadcast_to(np.asarray(max_iters, dtype=np.int32), (nrhs,)))
+    X = np.zeros((nrhs, n))
+    info, iters, path = C.c_int(0), np.zeros(nrhs, dtype=np.int32), _StepProbe()
+    _check(lib().sfmba_dense_pcg_probe(C.c_int(device), C.c_int(n), _p(A, _dp), C.c_int(nrhs), _p(B, _dp), None if W is None else _p(W, _dp),
+                                       C.c_int(flags), C.c_double(tol), _p(mi, _ip), _p(X, _dp), C.byref(info), _p(iters, _ip), C.byref(path)))
+    out = {k: int(getattr(path, k)) for k, _ in _StepProbe._fields_}
+    out["family_name"] = FAMILIES[out["family"]] if 0 <= out["family"] < len(FAMILIES) else str(out["family"])
+    return X, info.value, iters.copy(), out
 
 
 class Problem:

@@ -59,6 +59,7 @@ struct DenseSolver {
     double *sgV = nullptr, *sgE = nullptr, *sgEinv = nullptr, *sgT = nullptr, *sgRR = nullptr, *sgState = nullptr;
     const unsigned* blk_mask = nullptr;   // [ncam][(ncam + 31) / 32] per camera: cameras with a non-empty block in common (set by the caller; null: dense product)
     double blk_fill = 1.0;    // non-empty off-diagonal blocks / all (set by the caller)
+    size_t lds_limit = 0;     // LDS one workgroup may take on this device (hipDeviceAttributeMaxSharedMemoryPerBlock, asked once by dense_solver_create)
     int last_iters = 0;       // CG iterations of the previous solve
     int family = 0;           // SFMBA_FAMILY_* of the last dense_pcg_solve (a copy of run.path.family) / dense_cholesky_solve (the step probe, include/sfmba.h)
     int coarse_vectors = 0;   // ... and the coarse vectors of that CG (a copy of run.path.coarse_vectors)
@@ -86,7 +87,15 @@ inline int dense_padded_dim(int d) { return ((d + 1 + CHOL_NB - 1) / CHOL_NB) * 
 // *info_dev (device int) is set to k>0 if the leading minor k is not positive definite.
 void dense_cholesky_solve(hipStream_t s, DenseSolver* ws, double* S, double* rhs, int* info_dev, Profiler* prof = nullptr);
 
-// Block-Jacobi PCG on the same storage.  Returns the number of iterations (host sync inside).
+// Block-Jacobi PCG on the same storage.  Returns the number of iterations (host sync inside); below zero nothing was launched: PCG_ERR_ALLOC (the
+// workspace) or PCG_ERR_TOO_LARGE (the family this handle has to take keeps the search direction in LDS and d is beyond what a workgroup can hold:
+// the both-triangles streaming family -- deterministic handles, pcg_symmetric = -1 -- ends at d = 20 095 on gfx950).
+// PCG_ERR_LAUNCH: the runtime refused a launch of a waiting solve (no_wait = false); the HIP error is left for the caller to report.
+enum { PCG_ERR_ALLOC = -1, PCG_ERR_TOO_LARGE = -2, PCG_ERR_LAUNCH = -3 };
+inline const char* dense_pcg_error(int rc) {
+    return rc == PCG_ERR_TOO_LARGE ? "the reduced system is too large for the streaming CG family (its search direction has to fit the LDS of one workgroup)"
+         : rc == PCG_ERR_LAUNCH ? "a CG kernel launch failed" : "PCG workspace allocation failed";
+}
 struct PcgSolveOptions {
     bool finish = true;           // false leaves the solution in transformed form (x~, see pcg_common.h) for k_cam_update
     int hist_key = -1;            // >= 0 selects the history slot used to size the first batch of launches
@@ -112,6 +121,11 @@ int dense_pcg_transform(hipStream_t s, DenseSolver* ws, double* S, double* rhs, 
 // iteration count is then unknown to the host: consumers gate on ws->flags[0] on the device); dense_pcg_more enqueues up to
 // n further iterations of the same solve (returns how many; 0 = max_iters reached); dense_pcg_note records the final count.
 int dense_pcg_more(hipStream_t s, DenseSolver* ws, int n, Profiler* prof = nullptr);
+// The path dense_pcg_solve would take now (family 0: none can run this size); the one place that picks it.
+CgPath dense_pcg_path(const DenseSolver* ws, bool coarse, bool segments);
+// Test hook (sfmba_dense_pcg_probe): NaN into what the CG kernels promise never to multiply -- columns >= d of the transformed matrix and of W~ and the
+// tile slack behind both (pcg_common.h, pcg_tile_slack); with `lower` the strict lower triangle too (the symmetric family reads one triangle).
+void dense_pcg_poison(hipStream_t s, DenseSolver* ws, bool lower);
 void dense_pcg_note(DenseSolver* ws, int hist_key, int iters);
 int dense_pcg_ensure_workspace(DenseSolver* ws);
 // true where ws->symmetric selects the symmetric streaming path (d > 1280): the caller's pair pass may then write the upper triangle of S~ only

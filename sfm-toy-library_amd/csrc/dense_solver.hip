@@ -161,7 +161,7 @@ static bool pcg_reads_f32(const DenseSolver* ws) { return !pcg_fast_fits(ws->d) 
 // The path a solve takes: a pure function of the dimension, of what the caller set per solve (use_f32, symmetric, blk_mask / blk_fill), of the buffers
 // that exist, and of the two requests coarse (ws->W holds the gauge vectors) and segments (the segmented coarse space where it applies).  Everything
 // else -- the set-up, the launches, the batch sizing, the step probe -- reads the result.
-static CgPath dense_pcg_path(const DenseSolver* ws, bool coarse, bool segments) {
+CgPath dense_pcg_path(const DenseSolver* ws, bool coarse, bool segments) {
     const int d = ws->d, nc = (d - 1) / 6;
     const bool fast = pcg_fast_fits(d);
     // segmented coarse space (7 x 8 hat-restricted gauge vectors + 1), workgroup = camera; its streaming form (d > 1280): classical PCG, three launches
@@ -180,6 +180,8 @@ static CgPath dense_pcg_path(const DenseSolver* ws, bool coarse, bool segments) 
     p.nwg = (d + p.rows_per_wg - 1) / p.rows_per_wg;
     p.lds = sizeof(double) * (size_t)(ws->ld + (ml ? ML_LDS_TAIL : sg ? 0 : PCG_RED));
     p.f32 = pcg_reads_f32(ws);
+    // every family but the symmetric one keeps the search direction in dynamic LDS: a size the device cannot give is no family at all (dense_pcg_solve refuses it)
+    if (p.family != SFMBA_FAMILY_PCG_SYMMETRIC && p.lds > (ws->lds_limit ? ws->lds_limit : PCG_LDS_DEFAULT)) p.family = 0;
     // coarse space: the caller's linearisation wrote W~ (ws->W); AW, E^-1 and c_0 are formed by the family's set-up
     p.coarse = coarse && ws->W && ws->AW && p.rows_per_wg <= 4 * CO_MAXROWS;
     p.coarse_vectors = ml ? ML_NC : sg ? 7 * sg_hats(nc) + 1 : p.coarse ? PCG_NW : 0;
@@ -250,13 +252,16 @@ int dense_pcg_transform(hipStream_t s, DenseSolver* ws, double* S, double* rhs, 
 
 int dense_pcg_solve(hipStream_t s, DenseSolver* ws, double* S, double* rhs, double tol, int max_iters, int* info_dev, Profiler* prof, const PcgSolveOptions& o) {
     const int ld = ws->ld, d = ws->d;
-    if (dense_pcg_ensure_workspace(ws)) return -1;
+    if (dense_pcg_ensure_workspace(ws)) return PCG_ERR_ALLOC;
     if (max_iters <= 0) max_iters = 4 * d;
+    const CgPath path = dense_pcg_path(ws, o.coarse, o.segments);
+    if (path.family == 0) return PCG_ERR_TOO_LARGE;          // before anything is enqueued
     if (!o.pretransformed) dense_pcg_transform(s, ws, S, rhs, info_dev, prof);
     DenseSolver::CgRun& run = ws->run;
-    run.path = dense_pcg_path(ws, o.coarse, o.segments);
+    run.path = path;
     run.tol2 = tol * tol; run.in = 1; run.launched = 0; run.max_iters = max_iters; run.info = info_dev;
     ws->family = run.path.family; ws->coarse_vectors = run.path.coarse_vectors;        // (the step probe)
+    const bool clean = hipPeekAtLastError() == hipSuccess;      // (the launch check of the waiting loop below can only speak for this solve's launches)
     launch_cg_setup(s, ws, prof);
     volatile int* mb = ws->h_mailbox;
     if (mb) { mb[0] = -1; mb[1] = 0; }
@@ -271,9 +276,12 @@ int dense_pcg_solve(hipStream_t s, DenseSolver* ws, double* S, double* rhs, doub
     // launch short costs a host round trip of ~50 us, a surplus launch ~2: one more in reserve there)
     if (o.hist_key >= 0 && o.hist_key < (int)ws->hist.size() && ws->hist[o.hist_key] > 0) batch = ws->hist[o.hist_key] + batch_extra + (tol < 1e-10 ? 1 : 0) - first;
     if (o.no_wait) return dense_pcg_more(s, ws, batch, prof);
-    bool done = false;
+    bool done = false, waited = false;
     while (!done) {
-        if (dense_pcg_more(s, ws, batch, prof) == 0) break;
+        // (nothing left to launch BEFORE the first wait -- max_iters spent by a first launch that is an iteration --: what is in the queue is still waited for)
+        const int more = dense_pcg_more(s, ws, batch, prof);
+        if (more == 0 && waited) break;
+        if (clean && hipPeekAtLastError() != hipSuccess) return PCG_ERR_LAUNCH;      // a refused launch posts nothing: no wait (the error stays for the caller's launches_ok())
         const int it = run.launched;
         if (mb) {
             // poll the mailbox until the last launch of the batch has reported (or convergence was posted)
@@ -282,13 +290,16 @@ int dense_pcg_solve(hipStream_t s, DenseSolver* ws, double* S, double* rhs, doub
                 if (now_s() > t_end) { (void)hipStreamSynchronize(s); break; }
             }
             __sync_synchronize();
-            done = mb[1] != 0;
-            ws->h_flags[PF_DONE] = done; ws->h_flags[PF_ITERS] = mb[0] >= 0 ? mb[0] : it;
+            const int dn = mb[1];                    // 0, or the iterations of the finished solve + 1 (pcg_post): the count comes with the verdict
+            done = dn != 0;
+            ws->h_flags[PF_DONE] = done; ws->h_flags[PF_ITERS] = done ? dn - 1 : mb[0] >= 0 ? mb[0] : it;
         } else {
             (void)hipMemcpyAsync(ws->h_flags, ws->flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s);
             (void)hipStreamSynchronize(s);
             done = ws->h_flags[PF_DONE] != 0;
         }
+        waited = true;
+        if (more == 0) break;
         batch = 8;
     }
     if (o.finish) { ProfScope ps(prof, KID_PCG_FINISH, s);
@@ -307,16 +318,16 @@ template <typename T> static int ws_alloc(DenseSolver* ws, T** p, size_t bytes) 
 
 float* dense_pcg_want_f32(DenseSolver* ws) {
     if (pcg_fast_fits(ws->d)) return nullptr;                    // the fast path is latency-bound: fp64 there
-    if (!ws->Sfull32 && ws_alloc(ws, &ws->Sfull32, sizeof(float) * (size_t)ws->d * ws->ld)) return nullptr;
+    if (!ws->Sfull32 && ws_alloc(ws, &ws->Sfull32, sizeof(float) * ((size_t)ws->d * ws->ld + pcg_tile_slack(ws->d, ws->ld)))) return nullptr;
     return ws->Sfull32;
 }
 
 int dense_pcg_ensure_workspace(DenseSolver* ws) {
     if (!ws->Sfull) {
-        if (ws_alloc(ws, &ws->Sfull, sizeof(double) * (size_t)ws->d * ws->ld)) return -1;
+        if (ws_alloc(ws, &ws->Sfull, sizeof(double) * ((size_t)ws->d * ws->ld + pcg_tile_slack(ws->d, ws->ld)))) return -1;
     }
     if (!ws->W) {
-        if (ws_alloc(ws, &ws->W, sizeof(double) * (size_t)PCG_NW * ws->ld)) return -1;
+        if (ws_alloc(ws, &ws->W, sizeof(double) * ((size_t)PCG_NW * ws->ld + pcg_tile_slack(ws->d, ws->ld)))) return -1;
         if (ws_alloc(ws, &ws->AW, sizeof(double) * (size_t)PCG_NW * ws->ld)) return -1;
         if (ws_alloc(ws, &ws->epart, sizeof(double) * (size_t)(PCG_NW * PCG_NW + 2 * PCG_NW) * PCG_PART)) return -1;
         if (ws_alloc(ws, &ws->coarse, sizeof(double) * (size_t)(2 * PCG_NW * PCG_NW + PCG_NW))) return -1;
@@ -341,7 +352,7 @@ int dense_pcg_ensure_workspace(DenseSolver* ws) {
             ws->sym_nctiles = (int)ctiles.size();
             // what the coarse set-up ADDS into with atomics (the caller's linearisation zeroes it: DeviceBuffers::pcg_zero = sym_zero / sym_zero_n)
             ws->sym_zero_n = (size_t)PCG_NW * ws->ld;
-            if (ws_alloc(ws, &ws->sym_zero, sizeof(double) * ws->sym_zero_n)) return -1;
+            if (ws_alloc(ws, &ws->sym_zero, sizeof(double) * (ws->sym_zero_n + pcg_tile_slack(ws->d, ws->ld)))) return -1;
             if (hipMemset(ws->sym_zero, 0, sizeof(double) * ws->sym_zero_n) != hipSuccess) return -1;
             ws->AWt = ws->sym_zero;
             if (ws_alloc(ws, &ws->sym_tiles, sizeof(int4) * tiles.size())) return -1;
@@ -373,10 +384,15 @@ int dense_pcg_ensure_workspace(DenseSolver* ws) {
 
 int dense_solver_create(DenseSolver* ws, int d, int ld, DeviceArena* arena, char* pinned) {
     ws->d = d; ws->ld = ld; ws->arena = arena;
+    {   // what one workgroup may take of the LDS (a query; 160 KiB on gfx950): dense_pcg_path holds the families' requests against it
+        int dev = 0, lds = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || lds <= 0) { (void)hipGetLastError(); lds = (int)PCG_LDS_DEFAULT; }
+        ws->lds_limit = std::min((size_t)lds, PCG_LDS_GFX950);
+    }
     const int nblk = ld / NB;
     if (ws_alloc(ws, &ws->minv, sizeof(double) * (size_t)nblk * NB * NB)) return -1;
     if (ws_alloc(ws, &ws->y, sizeof(double) * ld)) return -1;
-    if (ws_alloc(ws, &ws->vec, sizeof(double) * 9 * (size_t)ld)) return -1;
+    if (ws_alloc(ws, &ws->vec, sizeof(double) * (9 * (size_t)ld + pcg_tile_slack(d, ld)))) return -1;
     if (ws_alloc(ws, &ws->part, sizeof(double) * 2 * PCG_NPART * PCG_PART)) return -1;
     if (ws_alloc(ws, &ws->binv, sizeof(double) * 36 * (size_t)(ld / 6 + 2))) return -1;
     if (ws_alloc(ws, &ws->scal, sizeof(double) * (PS_STATE + 2 * PS_STATE_LEN))) return -1;
@@ -394,6 +410,25 @@ int dense_solver_create(DenseSolver* ws, int d, int ld, DeviceArena* arena, char
     if (hipHostGetDevicePointer(reinterpret_cast<void**>(&ws->d_mailbox), const_cast<int*>(ws->h_mailbox), 0) != hipSuccess) return -1;
     ws->Sfull = nullptr;
     return 0;
+}
+
+// dense_pcg_poison: rows of ld entries, `rows` of them, then `slack` entries; NaN at columns >= d, behind the rows, and (lower) below the diagonal
+template <typename FT>
+__global__ __launch_bounds__(256) void k_pcg_poison(int d, int ld, int rows, size_t slack, int lower, FT* __restrict__ F) {
+    const size_t body = (size_t)rows * ld, n = body + slack;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t r = i / (size_t)ld, c = i - r * (size_t)ld;
+        if (i >= body || c >= (size_t)d || (lower && c < r)) F[i] = (FT)__builtin_nan("");
+    }
+}
+
+void dense_pcg_poison(hipStream_t s, DenseSolver* ws, bool lower) {
+    const int d = ws->d, ld = ws->ld;
+    const size_t slack = pcg_tile_slack(d, ld);
+    const int nwg = (int)std::min<size_t>(4096, ((size_t)d * ld + slack + 255) / 256);
+    if (pcg_reads_f32(ws)) hipLaunchKernelGGL(k_pcg_poison<float>, dim3(nwg), dim3(256), 0, s, d, ld, d, slack, lower ? 1 : 0, ws->Sfull32);
+    else if (ws->Sfull) hipLaunchKernelGGL(k_pcg_poison<double>, dim3(nwg), dim3(256), 0, s, d, ld, d, slack, lower ? 1 : 0, ws->Sfull);
+    if (ws->W) hipLaunchKernelGGL(k_pcg_poison<double>, dim3((PCG_NW * ld + (int)slack + 255) / 256), dim3(256), 0, s, d, ld, PCG_NW, slack, 0, ws->W);
 }
 
 void dense_solver_destroy(DenseSolver* ws) {

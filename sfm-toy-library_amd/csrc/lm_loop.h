@@ -80,6 +80,11 @@ inline void keep_both_triangles(sfmba_problem* p) { p->solver.symmetric = false;
 
 // Every launch of an LM iteration is in the queue: a failed launch must not leave the host waiting for a post
 int launches_ok();
+// dense_pcg_solve returned it < 0 (nothing is running): the error code and message of the call
+inline int pcg_refused(int it) {
+    if (it == PCG_ERR_LAUNCH) { const int rc = launches_ok(); if (rc) return rc; }
+    return fail(it == PCG_ERR_TOO_LARGE ? SFMBA_ERR_INVALID_ARG : it == PCG_ERR_LAUNCH ? SFMBA_ERR_HIP : SFMBA_ERR_ALLOC, dense_pcg_error(it));
+}
 // Waits for k_lm_control's mailbox post number `want`; a stream that drained without it is SFMBA_ERR_HIP: `what` + the HIP error, or + `lost`
 int await_control(sfmba_problem* p, int want, const char* what, const char* lost);
 void set_termination(sfmba_summary& sum, int termination, int message_id);

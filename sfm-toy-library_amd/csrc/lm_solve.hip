@@ -362,7 +362,7 @@ int run_solve(sfmba_problem* p, const sfmba_options& o, sfmba_summary* summary, 
                                            { .finish = false, .hist_key = host_iter, .pretransformed = true, .anchor = plan.anchor(first_linear_solve), .no_wait = true,
                                              .coarse = coarse_cg, .segments = segments_cg });
             first_linear_solve = false;
-            if (it < 0) return fail(SFMBA_ERR_ALLOC, "PCG workspace allocation failed");
+            if (it < 0) return pcg_refused(it);
             dbu.pcg_vec = p->solver.vec; dbu.pcg_linv = p->solver.binv; dbu.pcg_flags = p->solver.flags;
             dbu.cg_gate = pcg_gated ? p->solver.flags : nullptr;
             dbu.cg_force = 0;

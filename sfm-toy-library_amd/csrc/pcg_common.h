@@ -65,9 +65,11 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double* red) {
 }
 
 // Host mailbox (pinned, host-mapped): {iterations, done}.  The host polls it instead of issuing a D2H copy + stream
-// synchronise per batch; written by one lane with system-scope stores.
+// synchronise per batch; written by one lane with system-scope stores.  done: 0 while the solve runs, iterations + 1 once it has ended -- ONE word
+// carries the verdict and the count: a host that is polling when the post arrives sees `done` before the iterations word written behind it
+// (it used to read the count of the launch before: one iteration short, or the batch length for a zero right-hand side).
 __device__ __forceinline__ void pcg_post(int* mailbox, int iters, int done) {
-    __hip_atomic_store(mailbox + 1, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(mailbox + 1, done ? iters + 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(mailbox, iters, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -197,6 +199,32 @@ constexpr int SY_SLOT_STRIDE = 16;    // doubles between two accumulators
 #define SFMBA_SY_CR 128
 #endif
 constexpr int SY_CR = SFMBA_SY_CR;
+
+// Read extent of the symmetric kernels.  k_sy_prod and k_sy_coarse load every tile whole: lane l of a tile at column c0 (a multiple of SY_C, c0 < d)
+// reads the four entries c0 + 4 l .. c0 + 4 l + 3 of a matrix row, of p and of the eight rows of W~ WITHOUT a test against d or ld (the values of the
+// columns >= d are selected away afterwards).  The last column tile starts at c0 = SY_C floor((d - 1) / SY_C), so the highest column touched is
+// SY_C ceil(d / SY_C) - 1, in rows up to d - 1 of S~ (d rows of ld), in row 7 of W~ (8 rows of ld) and in p = vec + 4 ld or 5 ld (9 rows of ld).
+// With ld = 64 ceil((d + 1) / 64) that is up to
+//      pcg_tile_slack(d, ld) = max(0, SY_C ceil(d / SY_C) - ld)  <=  SY_C - 64 = 192
+// entries behind d ld entries of Sfull / Sfull32 and behind the 8 ld of W~ (0 where ld % SY_C == 0; 192, 128, 64 for ld % SY_C = 64, 128, 192); the
+// workspace allocates every array these kernels index by tile -- Sfull, Sfull32, W, AWt, vec -- with that many entries more (dense_solver.hip), so the
+// read stays inside the array's own allocation whatever the allocator's granularity.  (AWt is only indexed below d and p's overrun lands in the
+// following vectors of vec: they take the slack for uniformity, not from need.)
+// The other families, read for the same property at ld % 256 != 0 and d within four of ld: k_pcg_iter and k_sg_q read double2 columns 2 c, 2 c + 1 with
+// c < d >> 1 and float4 columns 4 c .. 4 c + 3 with c < d >> 2 (the fp32 prefetch of k_pcg_iter: lane + 64 m <= lane + 192 < d >> 2, else column 0),
+// the remainder entry by entry below d; k_pcg_coarse loads a quad only where its first column is below d, so its last column is below
+// 4 ceil(d / 4) <= ld, and its W~ loads are clamped to column 0; rows are clamped to the workgroup's first row, which exists.  None leaves d rows of ld.
+__host__ __device__ inline size_t pcg_tile_slack(int d, int ld) {
+    const int full = (d + SY_C - 1) / SY_C * SY_C;
+    return full > ld ? (size_t)(full - ld) : 0;
+}
+
+// Dynamic LDS of the iteration kernels that keep the search direction in LDS (k_pcg_iter, k_sg_q, k_pcg_iter_fast, k_pcg_iter_ml): CgPath::lds.  A
+// workgroup of gfx950 may take the whole 160 KiB of its CU (hipDeviceAttributeMaxSharedMemoryPerBlock = 163 840; DenseSolver::lds_limit holds the
+// device's answer); above the 64 KiB of the earlier parts the launch functions raise hipFuncAttributeMaxDynamicSharedMemorySize once per kernel.
+// dense_pcg_path refuses a size whose request exceeds the limit (family 0): the solve returns an error and launches nothing.
+constexpr size_t PCG_LDS_DEFAULT = (size_t)64 << 10;
+constexpr size_t PCG_LDS_GFX950 = (size_t)160 << 10;
 
 // segmented coarse space (pcg_segments.hip)
 constexpr int ML_G = 8;                    // hat functions along the (cyclic) camera order

@@ -347,8 +347,12 @@ void pcg_streaming_setup(hipStream_t s, const DenseSolver* ws, Profiler* prof) {
 void pcg_streaming_iterate(hipStream_t s, const DenseSolver* ws, bool init, int in, int anchor, double cap) {
     const DenseSolver::CgRun& run = ws->run;
     const CgPath& r = run.path;
-#define SFMBA_IT(INIT, FT, C, Fptr) hipLaunchKernelGGL((k_pcg_iter<INIT, FT, C>), dim3(r.nwg), dim3(256), r.lds, s, ws->d, ws->ld, Fptr, ws->vec, pcg_btilde(ws), ws->part, ws->scal, \
-        ws->flags, r.rows_per_wg, run.tol2, in, run.info, ws->d_mailbox, anchor, cap, ws->W, ws->AW, ws->coarse)
+    // (above 64 KiB of dynamic LDS -- ld > 7 840 -- the instantiation's limit is raised once, to what dense_pcg_path admits at the most)
+#define SFMBA_IT(INIT, FT, C, Fptr) do { \
+        static bool attr_set = false; \
+        if (r.lds > PCG_LDS_DEFAULT && !attr_set) { (void)hipFuncSetAttribute((const void*)k_pcg_iter<INIT, FT, C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCG_LDS_GFX950); attr_set = true; } \
+        hipLaunchKernelGGL((k_pcg_iter<INIT, FT, C>), dim3(r.nwg), dim3(256), r.lds, s, ws->d, ws->ld, Fptr, ws->vec, pcg_btilde(ws), ws->part, ws->scal, \
+        ws->flags, r.rows_per_wg, run.tol2, in, run.info, ws->d_mailbox, anchor, cap, ws->W, ws->AW, ws->coarse); } while (0)
     if (r.f32) {
         if (r.coarse) { if (init) SFMBA_IT(true, float, true, ws->Sfull32); else SFMBA_IT(false, float, true, ws->Sfull32); }
         else { if (init) SFMBA_IT(true, float, false, ws->Sfull32); else SFMBA_IT(false, float, false, ws->Sfull32); }

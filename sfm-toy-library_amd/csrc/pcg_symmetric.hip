@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void k_sy_prod(int d, int ld, const FT* __rest
     for (int u = 0; u < 8; ++u) { const int row = rw0 + u; f[u].load(F + (size_t)(row < rend ? row : r0) * ld + j0); }
     double pj[4];
     {
-        const double2 a = reinterpret_cast<const double2*>(p + j0)[0], b = reinterpret_cast<const double2*>(p + j0)[1];      // (j0 + 3 < ld: the padding is selected away)
+        const double2 a = reinterpret_cast<const double2*>(p + j0)[0], b = reinterpret_cast<const double2*>(p + j0)[1];      // (j0 + 3 < ld + pcg_tile_slack(d, ld), inside vec: what lies at columns >= d is selected away)
         pj[0] = j0 + 0 < d ? a.x : 0.0; pj[1] = j0 + 1 < d ? a.y : 0.0; pj[2] = j0 + 2 < d ? b.x : 0.0; pj[3] = j0 + 3 < d ? b.y : 0.0;
     }
     const int myrow = rw0 + (lane >> 3);              // the row whose total this lane group publishes

@@ -4,6 +4,7 @@
 //
 // There is NO CPU fallback in this library: without a HIP device every entry point returns SFMBA_ERR_NO_DEVICE.
 #include "lm_loop.h"
+#include "pcg_common.h"
 
 using namespace sfmba;
 
@@ -395,12 +396,70 @@ int sfmba_dense_spd_solve(int device, int n, const double* A, const double* b, d
     int it = 0;
     if (method == SFMBA_LINEAR_PCG) it = dense_pcg_solve(s, &ws, dA, db_, pcg_tol > 0 ? pcg_tol : 1e-10, pcg_max_iters, dinfo);
     else dense_cholesky_solve(s, &ws, dA, db_, dinfo);
+    
+    if (it < 0) return pcg_refused(it);
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipMemcpy(x, db_, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
     int hinfo = 0;
     HIP_TRY(hipMemcpy(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost));
     if (info) *info = hinfo;
     if (iters) *iters = it;
+    return SFMBA_OK;
+}
+
+int sfmba_dense_pcg_probe(int device, int n, const double* A, int nrhs, const double* B, const double* Wt, int flags, double tol,
+                          const int* max_iters, double* X, int* info, int* iters, sfmba_step_probe* path) {
+    constexpr int known = SFMBA_PCG_PROBE_SYMMETRIC | SFMBA_PCG_PROBE_F32_MATRIX | SFMBA_PCG_PROBE_SEGMENTS | SFMBA_PCG_PROBE_POISON;
+    if (n <= 0 || nrhs <= 0 || !A || !B || !X || !max_iters || !(tol > 0.0) || (flags & ~known)) return fail(SFMBA_ERR_INVALID_ARG, "bad arguments");
+    for (int i = 0; i < nrhs; ++i)
+        if (max_iters[i] <= 0 || max_iters[i] > 1000) return fail(SFMBA_ERR_INVALID_ARG, "max_iters must lie in 1 .. 1000");
+    if ((flags & SFMBA_PCG_PROBE_SEGMENTS) && !Wt) return fail(SFMBA_ERR_INVALID_ARG, "the segmented coarse space needs Wt");
+    int rc = check_device(device);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const int ld = dense_padded_dim(n);
+    double *dA = nullptr, *db_ = nullptr;
+    int* dinfo = nullptr;
+    DeviceTemps tmp(&dA, &db_, &dinfo);
+    HIP_TRY(dev_alloc(&dA, (size_t)n * ld));
+    HIP_TRY(hipMemset(dA, 0, sizeof(double) * (size_t)n * ld));
+    HIP_TRY(hipMemcpy2D(dA, sizeof(double) * (size_t)ld, A, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n, (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(dev_alloc(&db_, (size_t)ld));
+    HIP_TRY(dev_alloc(&dinfo, 1));
+    HIP_TRY(hipMemset(dinfo, 0, sizeof(int)));
+    DenseSolver ws;
+    if (dense_solver_create(&ws, n, ld)) return fail(SFMBA_ERR_ALLOC, "dense solver workspace allocation failed");
+    hipStream_t s = nullptr;
+    struct Guard { DenseSolver* ws; hipStream_t* s; ~Guard() { dense_solver_destroy(ws); if (*s) (void)hipStreamDestroy(*s); } } guard{ &ws, &s };
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    // what a handle sets per solve (lm_solve.hip): the triangle the product reads, the matrix precision, the coarse vectors
+    ws.symmetric = (flags & SFMBA_PCG_PROBE_SYMMETRIC) != 0;
+    ws.use_f32 = (flags & SFMBA_PCG_PROBE_F32_MATRIX) != 0 && dense_pcg_want_f32(&ws) != nullptr;
+    if (dense_pcg_ensure_workspace(&ws)) return fail(SFMBA_ERR_ALLOC, dense_pcg_error(PCG_ERR_ALLOC));
+    const size_t wn = (size_t)PCG_NW * ld + pcg_tile_slack(n, ld);
+    PcgSolveOptions o;
+    o.pretransformed = true; o.coarse = Wt != nullptr; o.segments = (flags & SFMBA_PCG_PROBE_SEGMENTS) != 0;
+    const CgPath plan = dense_pcg_path(&ws, o.coarse, o.segments);
+    for (int i = 0; i < nrhs; ++i) {
+        HIP_TRY(hipMemsetAsync(db_, 0, sizeof(double) * (size_t)ld, s));
+        HIP_TRY(hipMemcpyAsync(db_, B + (size_t)i * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(ws.W, 0, sizeof(double) * wn, s));
+        if (Wt) HIP_TRY(hipMemcpy2DAsync(ws.W, sizeof(double) * (size_t)ld, Wt, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n, PCG_NW, hipMemcpyHostToDevice, s));
+        if (dense_pcg_transform(s, &ws, dA, db_, dinfo)) return fail(SFMBA_ERR_ALLOC, dense_pcg_error(PCG_ERR_ALLOC));
+        if (flags & SFMBA_PCG_PROBE_POISON) dense_pcg_poison(s, &ws, plan.family == SFMBA_FAMILY_PCG_SYMMETRIC);
+        if (ws.sym_zero) HIP_TRY(hipMemsetAsync(ws.sym_zero, 0, sizeof(double) * ws.sym_zero_n, s));       // (the linearisation's part: DeviceBuffers::pcg_zero)
+        if ((rc = launches_ok())) return rc;
+        const int it = dense_pcg_solve(s, &ws, dA, db_, tol, max_iters[i], dinfo, nullptr, o);
+        if ((rc = launches_ok())) return rc;
+        if (it < 0) return pcg_refused(it);
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpy(X + (size_t)i * n, db_, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        if (iters) iters[i] = it;
+        if (path) *path = sfmba_step_probe{ ws.family, ws.run.path.f32 ? 1 : 0, ws.coarse_vectors, it, 0 };
+    }
+    int hinfo = 0;
+    HIP_TRY(hipMemcpy(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost));
+    if (info) *info = hinfo;
     return SFMBA_OK;
 }
 }  // extern "C"

@@ -102,7 +102,7 @@ int sfmba_shard_solve_update(sfmba_problem* p) {
         if (coarse_cg) { p->db.pcg_W = p->solver.W; launch_gauge(p->stream, p->ds, p->db); }
         const int it = dense_pcg_solve(p->stream, &p->solver, p->db.S, p->db.rhs, plan.tol, plan.max_iters, p->d_info, nullptr,
                                        { .finish = false, .hist_key = p->shard_host_iter, .pretransformed = true, .anchor = plan.anchor(p->shard_host_iter == 0), .coarse = coarse_cg });
-        if (it < 0) return fail(SFMBA_ERR_ALLOC, "PCG workspace allocation failed");
+        if (it < 0) return pcg_refused(it);
         p->shard_sum.linear_iters += it;
         dbu.pcg_vec = p->solver.vec; dbu.pcg_linv = p->solver.binv; dbu.pcg_flags = p->solver.flags;
         probe_note_solver(p, true, 0);
@@ -324,7 +324,7 @@ static int solve_sharded_impl(sfmba_problem* p, const sfmba_options* opt, sfmba_
                                             { .finish = false, .hist_key = p->shard_host_iter, .pretransformed = true, .anchor = plan.anchor(first_linear_solve), .no_wait = true,
                                               .coarse = coarse_cg });
             first_linear_solve = false;
-            if (it0 < 0) return fail(SFMBA_ERR_ALLOC, "PCG workspace allocation failed");
+            if (it0 < 0) return pcg_refused(it0);
             }
             DeviceBuffers dbu = p->db;
             if (f32) dbu.pu32 = p->d_pu32;

@@ -66,6 +66,26 @@ def test_no_cpu_fallback_without_device(capi, sfm):
         capi.dense_spd_solve(np.eye(3), np.ones(3))
     with pytest.raises(capi.SfmbaError, match="no HIP device"):
         capi.device_warmup(0, 1000)
+    with pytest.raises(capi.SfmbaError, match="no HIP device"):
+        capi.dense_pcg_probe(np.eye(7), np.ones(7), max_iters=5)
+
+
+def test_dense_pcg_probe_refuses_bad_arguments(capi):
+    """Refused before the device is looked at: an iteration cap outside 1 .. 1000 (no call may spin through 4 d batches), a tolerance that is
+    not positive, unknown flags, the segmented coarse space without vectors."""
+    A, b = np.eye(7), np.ones(7)
+    for bad in (0, -1, 1001):
+        with pytest.raises(capi.SfmbaError, match="max_iters must lie in 1 .. 1000"):
+            capi.dense_pcg_probe(A, b, max_iters=bad)
+    with pytest.raises(capi.SfmbaError, match="max_iters must lie in 1 .. 1000"):
+        capi.dense_pcg_probe(A, np.ones((3, 7)), max_iters=[5, 0, 5])
+    for kw in (dict(tol=0.0), dict(tol=float("nan")), dict(flags=16), dict(flags=-1)):
+        with pytest.raises(capi.SfmbaError, match="bad arguments"):
+            capi.dense_pcg_probe(A, b, max_iters=5, **kw)
+    with pytest.raises(capi.SfmbaError, match="needs Wt"):
+        capi.dense_pcg_probe(A, b, flags=capi.PCG_PROBE_SEGMENTS, max_iters=5)
+    with pytest.raises(ValueError):
+        capi.dense_pcg_probe(A, np.ones(6), max_iters=5)
 
 
 def test_product_never_imports_the_oracle():
