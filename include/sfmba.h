@@ -1424,8 +1424,9 @@ SFMBA_API int sfmba_mesh_clean(int device, int64_t n_vertices, const float* xyz 
  *                 floor((2 (wA cA + wB cB + wC cC) + (S - 2)) / (2 (S - 2))) in integers, clamped to 0..255, with cA, cB, cC the
  *                 corners' bgr -- a FLOOR division, not a truncation -- and (0, 0, 0) where bgr is NULL.
  *   outputs       atlas uint8 [H][W][3], BGR; uv; view int32 [n_triangles]; score int64 [n_triangles] or NULL; *n_textured.
- *   NO COLOUR ADJUSTMENT ACROSS VIEWS: SEAMS WHERE EXPOSURES DIFFER STAY VISIBLE.  NO SMOOTHING OF THE VIEW LABELS.  NO CHART
- *   MERGING: THE ATLAS SPENDS (S + 1) S / 2 TEXELS ON EVERY TRIANGLE, HOWEVER SMALL.
+ *   NO COLOUR ADJUSTMENT ACROSS VIEWS: SEAMS WHERE EXPOSURES DIFFER STAY VISIBLE.  NO SMOOTHING OF THE VIEW LABELS in this call (off by
+ *   default: see sfmba_mesh_texture_smooth in the next section).  NO CHART MERGING: THE ATLAS SPENDS (S + 1) S / 2 TEXELS ON EVERY
+ *   TRIANGLE, HOWEVER SMALL.
  *
  * sfmba_mesh_texture_size
  *   *width = W and *height = H of the layout above; SFMBA_ERR_INVALID_ARG for what the call refuses about n_triangles, S, B, W and H.
@@ -1445,6 +1446,101 @@ SFMBA_API int sfmba_mesh_texture(int device, int64_t n_vertices, const float* xy
                 int64_t min_area /*in (1/16 px)^2, doubled; >= 0*/, int patch /*S, 3..64*/, int blocks_per_row /*B >= 1*/,
                 unsigned char* atlas /*[H][W][3] BGR*/, float* uv /*[n_triangles][3][2]*/, int32_t* view /*[n_triangles]*/,
                 int64_t* score /*[n_triangles] or NULL*/, int64_t* n_textured);
+
+/* ---- smoothing the view labels: the K best views, the adjacency, score diffusion and a Potts relaxation (SfM::textureMesh) --------
+ * sfmba_mesh_texture chooses a view per triangle with no regard for its neighbours: where two views see a surface about equally large,
+ * the largest-area rule flips between them on noise, and every flip is a seam in the atlas.  The calls of this section choose the labels
+ * TOGETHER.  OFF BY DEFAULT: nothing above changes.  Like the texture call THE CONTRACT IS OUR OWN AND EQUALS NOBODY'S, and it is stated
+ * so that the device is held BIT FOR BIT to a CPU restatement (tests/label_oracle.py).  The projection arithmetic is exactly the texture
+ * call's (a view's candidate flag, score and eligibility as "view choice" above states them) and is not restated; EVERYTHING ELSE IS
+ * INTEGER ARITHMETIC (csrc/label_math.h).  The only atomics are integer adds on the statistics, whose result does not depend on order.
+ * T = n_triangles, K = n_candidates.  Every call that sorts edges needs 3 T < 2^31.
+ *
+ * sfmba_mesh_view_candidates
+ *   the mesh (xyz, tri), the views and occl_tol, min_area of sfmba_mesh_texture, and K in 1..8.  Per triangle the K ELIGIBLE views of
+ *   largest score, in descending score, TIES TO THE LOWER VIEW INDEX: cand_view int32 [T][K], cand_score int64 [T][K]; unused entries
+ *   are -1 and 0 and follow the used ones.  Rank 0 equals view[t] / score[t] of sfmba_mesh_texture bit for bit.  A triangle with a
+ *   repeated index or a non-finite coordinate gets no candidate.  Every score lies in 1 .. 2^37 - 1 (|su|, |sv| < 2^18).
+ *
+ * sfmba_mesh_adjacency
+ *   adj int32 [T][3].  Edge q of triangle t joins tri[t][q] and tri[t][(q + 1) % 3]; its key is (min << 32) | max of the two indices
+ *   (which must be >= 0; no vertex is read, so there is no upper limit).  A triangle with a repeated index contributes no edge, and its
+ *   three adj entries are -1.  An edge whose key occurs EXACTLY TWICE links its two triangles: adj[t][q] of either is the other.  A key
+ *   that occurs once is OPEN; a key that occurs three or more times is NON-MANIFOLD; every adj entry on such an edge is -1.  Two
+ *   triangles on the same three vertices are linked three times.  *n_pairs, *n_open_edges, *n_nonmanifold_edges count the keys of each
+ *   kind.  (Implementation: the keys, one stable radix sort with the value 3 t + q, one lane per sorted entry.)
+ *
+ * sfmba_mesh_view_smooth
+ *   cand_view, cand_score [T][K] as the candidates call writes them (each row: scores in 1 .. 2^37 - 1 in descending order with views in
+ *   0 .. n_images-1, then -1 and 0; anything else is refused), adj [T][3] with entries in -1 .. T-1, rings r in 0..8, penalty p in
+ *   0..65535, max_passes in 0..10000.  Writes view int32 [T] and stats int64 [8].  "n in adj(t)" runs over the three ENTRIES of adj[t]
+ *   that are >= 0: a triangle linked twice to the same neighbour counts it twice.
+ *   1 diffusion   s^0 = cand_score.  For i = 0 .. r-1 and every entry with cand_view[t][k] >= 0:
+ *                 s^{i+1}[t][k] = s^i[t][k] + sum over n in adj(t) of look(n, cand_view[t][k]), where look is s^i[n][j] for the FIRST j
+ *                 with cand_view[n][j] equal to that view, and 0 if n does not list it.  Entries with cand_view = -1 stay 0.  Every ring
+ *                 reads only the ring before (a Jacobi update).  A sum has at most four terms, so s^r < 4^8 2^37 = 2^53: int64 holds it.
+ *   2 start       rank[t] = the k of the largest s^r[t][k] among the entries with cand_view[t][k] >= 0, THE LOWEST k ON A TIE;
+ *                 view[t] = cand_view[t][rank[t]]; a triangle without a candidate has view -1 for good, never moves and pulls on nobody.
+ *                 With r = 0 the start is rank 0, the texture call's label.
+ *   3 data term   from the ORIGINAL scores: D[t][k] = floor(1024 (cand_score[t][0] - cand_score[t][k]) / cand_score[t][0]), 0..1023.
+ *   4 a pass      for a triangle with a candidate and every k with cand_view[t][k] >= 0:
+ *                 e[t][k] = D[t][k] + p #{n in adj(t): view[n] >= 0 and view[n] != cand_view[t][k]}; k* = the lowest k of least e;
+ *                 gain[t] = e[t][rank[t]] - e[t][k*] (>= 0; 0 for a triangle without a candidate).  t MOVES (rank[t] = k*, view[t] =
+ *                 cand_view[t][k*]) iff gain[t] > 0 and, for every n in adj(t), gain[t] > gain[n] or (gain[t] == gain[n] and t < n).
+ *                 ALL GAINS COME FROM THE LABELS BEFORE THE PASS.  With a symmetric adj (the adjacency call's) the movers of a pass are
+ *                 pairwise non-adjacent and the energy E = sum_t D[t][rank[t]] + p #{pairs with both views >= 0 and different} falls
+ *                 by exactly the sum of the movers' gains.  Passes run until one moves nothing or max_passes have run.
+ *   5 stats       a PAIR is an entry n = adj[t][q] with t < n.  stats[0] = E after the start, [1] = E at the end; the pairs with both
+ *                 views >= 0 and different [2] under rank 0, [3] after the start, [4] at the end; [5] the pairs with exactly one view
+ *                 -1 (a frontier between textured and untextured, which no pass can move: not a seam between two photographs);
+ *                 [6] the moves of all passes; [7] the passes in which something moved.
+ *   A triangle never gets a view that is not one of its own eligible candidates.
+ *
+ * sfmba_mesh_texture_from_views
+ *   sfmba_mesh_texture with view [T] as an INPUT: each entry is -1 or in 0 .. n_images-1 (anything else is refused, found on the device
+ *   before anything is written).  The same layout, texels, uv and atlas; no depth map, occl_tol or min_area, since nothing is tested.
+ *   *n_textured is the number of entries >= 0.
+ *
+ * sfmba_mesh_texture_smooth
+ *   candidates, adjacency, smoothing and the texture call's raster in ONE call, everything staying on the device.  It equals the
+ *   composition of the four calls above byte for byte: view and stats of the smoothing, score[t] = cand_score[t][rank[t]] (0 without a
+ *   candidate; may be NULL), atlas, uv and *n_textured of from_views.  With rings = 0 and max_passes = 0 it equals sfmba_mesh_texture
+ *   byte for byte in atlas, uv, view, score and n_textured.
+ *
+ *   OUT OF SCOPE: colour adjustment across views; chart merging; letting a triangle below the area floor borrow a neighbour's view; any
+ *   optimiser stronger than this local one (no graph cut, no message passing).
+ *   SFMBA_ERR_INVALID_ARG (nothing written): what sfmba_mesh_texture refuses about the arguments a call shares with it; K outside 1..8;
+ *                 rings outside 0..8; penalty outside 0..65535; max_passes outside 0..10000; 3 T >= 2^31; a negative index
+ *                 (adjacency); an adj entry outside -1 .. T-1; a cand_view outside -1 .. n_images-1 or a row that is no candidate
+ *                 list; a view outside -1 .. n_images-1 (from_views, found on the device); a NULL output, or a NULL input array with
+ *                 T > 0.
+ *   Host pointers in and out, synchronous, deterministic.  SFMBA_ABI_VERSION stays 6: adding symbols is backward compatible.
+ */
+SFMBA_API int sfmba_mesh_view_candidates(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, int64_t n_triangles,
+                const int32_t* tri /*[n_triangles][3]*/, int n_images, const int64_t* img_ptr, const unsigned char* pixels,
+                const int32_t* width, const int32_t* height, int channels, const float* K /*[9]*/, const float* P /*[n_images][12]*/,
+                const float* const* depth /*[n_images], each NULL or [h][w]*/, float occl_tol, int64_t min_area, int n_candidates /*1..8*/,
+                int32_t* cand_view /*[n_triangles][n_candidates]*/, int64_t* cand_score /*[n_triangles][n_candidates]*/);
+SFMBA_API int sfmba_mesh_adjacency(int device, int64_t n_triangles, const int32_t* tri /*[n_triangles][3]*/, int32_t* adj /*[n_triangles][3]*/,
+                int64_t* n_pairs, int64_t* n_open_edges, int64_t* n_nonmanifold_edges);
+SFMBA_API int sfmba_mesh_view_smooth(int device, int64_t n_triangles, int n_images, int n_candidates /*1..8*/,
+                const int32_t* cand_view /*[n_triangles][n_candidates]*/, const int64_t* cand_score /*[n_triangles][n_candidates]*/,
+                const int32_t* adj /*[n_triangles][3]*/, int rings /*0..8*/, int penalty /*0..65535*/, int max_passes /*0..10000*/,
+                int32_t* view /*[n_triangles]*/, int64_t* stats /*[8]*/);
+SFMBA_API int sfmba_mesh_texture_from_views(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, const unsigned char* bgr /*or NULL*/,
+                int64_t n_triangles, const int32_t* tri /*[n_triangles][3]*/, int n_images, const int64_t* img_ptr,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels, const float* K /*[9]*/,
+                const float* P /*[n_images][12]*/, int patch /*S, 3..64*/, int blocks_per_row /*B >= 1*/,
+                const int32_t* view /*[n_triangles], each -1 or an image*/, unsigned char* atlas /*[H][W][3] BGR*/,
+                float* uv /*[n_triangles][3][2]*/, int64_t* n_textured);
+SFMBA_API int sfmba_mesh_texture_smooth(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, const unsigned char* bgr /*or NULL*/,
+                int64_t n_triangles, const int32_t* tri /*[n_triangles][3]*/, int n_images, const int64_t* img_ptr,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels, const float* K /*[9]*/,
+                const float* P /*[n_images][12]*/, const float* const* depth /*[n_images], each NULL or [h][w]*/, float occl_tol,
+                int64_t min_area, int patch /*S, 3..64*/, int blocks_per_row /*B >= 1*/, int n_candidates /*1..8*/, int rings /*0..8*/,
+                int penalty /*0..65535*/, int max_passes /*0..10000*/, unsigned char* atlas /*[H][W][3] BGR*/,
+                float* uv /*[n_triangles][3][2]*/, int32_t* view /*[n_triangles]*/, int64_t* score /*[n_triangles] or NULL*/,
+                int64_t* n_textured, int64_t* stats /*[8]*/);
 
 /* ---- matching by optical flow: pyramidal Lucas-Kanade and the snap to key points (SfMFeatureMatching::createFlowMatchMatrix) -----
  * The reference's legacy tree matched video-like input without descriptors (legacy/SfMToyLib_Old/OFFeatureMatcher.cpp): it tracked

@@ -43,6 +43,7 @@ SYMBOLS = [
     "sfmba_tsdf_fill", "sfmba_tsdf_mesh_fill",
     "sfmba_mesh_components", "sfmba_mesh_filter", "sfmba_mesh_smooth", "sfmba_mesh_clean",
     "sfmba_mesh_texture_size", "sfmba_mesh_texture",
+    "sfmba_mesh_view_candidates", "sfmba_mesh_adjacency", "sfmba_mesh_view_smooth", "sfmba_mesh_texture_from_views", "sfmba_mesh_texture_smooth",
     "sfmba_depth_cost_volume", "sfmba_sgm_aggregate", "sfmba_depth_sweep_sgm",
 ]
 
@@ -980,6 +981,100 @@ def mesh_texture(xyz, bgr, tri, images, K, P, depth_maps, occl_tol, min_area=0, 
                                     _p(view, _ip), _p(score, lp) if want_score else None, C.byref(n_textured)))
     return {"atlas": atlas, "uv": uv[:nt].copy(), "view": view[:nt].copy(), "score": score[:nt].copy() if want_score else None,
             "n_textured": int(n_textured.value)}
+
+
+LABEL_STATS = ("energy_start", "energy_end", "diff_rank0", "diff_start", "diff_end", "frontier", "moves", "n_passes")    # stats[0..7]
+
+
+def _default_blocks_per_row(nt):
+    b = max(1, int(np.ceil(np.sqrt((nt + 1) // 2))))
+    while b * b < (nt + 1) // 2:
+        b += 1
+    return b
+
+
+def mesh_view_candidates(xyz, tri, images, K, P, depth_maps, occl_tol, min_area=0, n_candidates=4, device=0):
+    """sfmba_mesh_view_candidates: the n_candidates eligible views of largest score per triangle (the contract is in include/sfmba.h).
+    Returns (cand_view int32 [m, k], cand_score int64 [m, k]); unused entries are -1 and 0."""
+    nv, xyz, _, tri = _clean_mesh(xyz, None, tri)
+    nt, k = len(tri), int(n_candidates)
+    views, keep = _tsdf_views(images, K, P, depth_maps)
+    fp, lp = C.POINTER(C.c_float), C.POINTER(C.c_int64)
+    cv, cs = np.zeros((max(nt, 1), max(k, 1)), np.int32), np.zeros((max(nt, 1), max(k, 1)), np.int64)
+    _check(lib().sfmba_mesh_view_candidates(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), C.c_int64(nt), _opt(tri, _ip), *views, C.c_float(occl_tol),
+                                            C.c_int64(min_area), C.c_int(k), _p(cv, _ip), _p(cs, lp)))
+    return cv[:nt].copy(), cs[:nt].copy()
+
+
+def mesh_adjacency(tri, device=0):
+    """sfmba_mesh_adjacency: the triangle across each edge (the contract is in include/sfmba.h).  Returns a dict: adj int32 [m, 3],
+    n_pairs, n_open_edges, n_nonmanifold_edges."""
+    tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+    nt = len(tri)
+    adj = np.zeros((max(nt, 1), 3), np.int32)
+    n = [C.c_int64(0) for _ in range(3)]
+    _check(lib().sfmba_mesh_adjacency(C.c_int(device), C.c_int64(nt), _opt(tri, _ip), _p(adj, _ip), *[C.byref(c) for c in n]))
+    return {"adj": adj[:nt].copy(), "n_pairs": int(n[0].value), "n_open_edges": int(n[1].value), "n_nonmanifold_edges": int(n[2].value)}
+
+
+def mesh_view_smooth(cand_view, cand_score, adj, n_images, rings=0, penalty=256, max_passes=0, device=0):
+    """sfmba_mesh_view_smooth: score diffusion over `rings` rings and a parallel Potts relaxation of at most max_passes passes (the
+    contract is in include/sfmba.h).  Returns (view int32 [m], stats int64 [8], named by LABEL_STATS)."""
+    cv = np.ascontiguousarray(cand_view, dtype=np.int32)
+    cs = np.ascontiguousarray(cand_score, dtype=np.int64)
+    adj = np.ascontiguousarray(adj, dtype=np.int32).reshape(-1, 3)
+    if cv.ndim != 2 or cv.shape != cs.shape or len(adj) != len(cv):
+        raise ValueError("cand_view and cand_score [m, k] and adj [m, 3]")
+    nt, k = cv.shape
+    view, stats = np.zeros(max(nt, 1), np.int32), np.zeros(8, np.int64)
+    lp = C.POINTER(C.c_int64)
+    _check(lib().sfmba_mesh_view_smooth(C.c_int(device), C.c_int64(nt), C.c_int(n_images), C.c_int(k), _opt(cv, _ip), _opt(cs, lp), _opt(adj, _ip),
+                                        C.c_int(rings), C.c_int(penalty), C.c_int(max_passes), _p(view, _ip), _p(stats, lp)))
+    return view[:nt].copy(), stats
+
+
+def mesh_texture_from_views(xyz, bgr, tri, images, K, P, view, patch=6, blocks_per_row=None, device=0):
+    """sfmba_mesh_texture_from_views: the atlas of mesh_texture for GIVEN labels (each -1 or an image index; the contract is in
+    include/sfmba.h).  Returns a dict: atlas, uv, n_textured."""
+    nv, xyz, bgr, tri = _clean_mesh(xyz, bgr, tri)
+    nt = len(tri)
+    if blocks_per_row is None:
+        blocks_per_row = _default_blocks_per_row(nt)
+    view = np.ascontiguousarray(view, dtype=np.int32).reshape(-1)
+    if len(view) != nt:
+        raise ValueError("one view per triangle")
+    views, keep = _tsdf_views(images, K, P, [None] * len(images))
+    W, H = mesh_texture_size(nt, patch, blocks_per_row)
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+    atlas, uv = np.zeros((H, W, 3), np.uint8), np.zeros((max(nt, 1), 3, 2), np.float32)
+    n_textured = C.c_int64(0)
+    _check(lib().sfmba_mesh_texture_from_views(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), _opt(bgr, bp), C.c_int64(nt), _opt(tri, _ip), *views[:8],
+                                               C.c_int(patch), C.c_int(blocks_per_row), _opt(view, _ip), _p(atlas, bp), _p(uv, fp),
+                                               C.byref(n_textured)))
+    return {"atlas": atlas, "uv": uv[:nt].copy(), "n_textured": int(n_textured.value)}
+
+
+def mesh_texture_smooth(xyz, bgr, tri, images, K, P, depth_maps, occl_tol, min_area=0, patch=6, blocks_per_row=None, n_candidates=4, rings=4,
+                        penalty=256, max_passes=100, want_score=True, device=0):
+    """sfmba_mesh_texture_smooth: mesh_texture with smoothed view labels -- candidates, adjacency, diffusion, relaxation and the raster
+    in one call, everything staying on the device (the contract is in include/sfmba.h).  Returns mesh_texture's dict and stats int64 [8]
+    (named by LABEL_STATS)."""
+    nv, xyz, bgr, tri = _clean_mesh(xyz, bgr, tri)
+    nt = len(tri)
+    if blocks_per_row is None:
+        blocks_per_row = _default_blocks_per_row(nt)
+    views, keep = _tsdf_views(images, K, P, depth_maps)
+    W, H = mesh_texture_size(nt, patch, blocks_per_row)
+    fp, bp, lp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte), C.POINTER(C.c_int64)
+    atlas, uv = np.zeros((H, W, 3), np.uint8), np.zeros((max(nt, 1), 3, 2), np.float32)
+    view, score, stats = np.zeros(max(nt, 1), np.int32), np.zeros(max(nt, 1), np.int64), np.zeros(8, np.int64)
+    n_textured = C.c_int64(0)
+    _check(lib().sfmba_mesh_texture_smooth(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), _opt(bgr, bp), C.c_int64(nt), _opt(tri, _ip), *views,
+                                           C.c_float(occl_tol), C.c_int64(min_area), C.c_int(patch), C.c_int(blocks_per_row), C.c_int(n_candidates),
+                                           C.c_int(rings), C.c_int(penalty), C.c_int(max_passes), _p(atlas, bp), _p(uv, fp), _p(view, _ip),
+                                           _p(score, lp) if want_score else None, C.byref(n_textured), _p(stats, lp)))
+    return {"atlas": atlas, "uv": uv[:nt].copy(), "view": view[:nt].copy(), "score": score[:nt].copy() if want_score else None,
+            "n_textured": int(n_textured.value), "stats": stats}
 
 
 class _ImageInfo(C.Structure):

@@ -1,5 +1,5 @@
 // api_frontend.hip -- C ABI of include/sfmba.h, the front-end entry points (everything in front of bundle adjustment: image files,
-// features, matches, RANSAC, triangulation, association, dense depth, flow, cloud merge, mesh, mesh cleaning, texturing): argument checks and dispatch.  The work
+// features, matches, RANSAC, triangulation, association, dense depth, flow, cloud merge, mesh, mesh cleaning, texturing, label smoothing): argument checks and dispatch.  The work
 // is in the unit each wrapper names; the error state, the device checks and the problem / solver entry points are in sfmba_api.hip.
 //
 // Every wrapper reads: checks, open, call, timing line, mapped result.  Every check comes before the first write: a refused call
@@ -19,6 +19,7 @@
 #include "mesh_clean.h"
 #include "mesh_clean_math.h"
 #include "mesh_math.h"
+#include "mesh_labels.h"
 #include "mesh_texture.h"
 #include "texture_math.h"
 #include "orb_extract.h"
@@ -319,6 +320,57 @@ int texture_check_layout(const char* who, int64_t n_triangles, int patch, int bl
     if (!tex_atlas_size((long long)n_triangles, patch, blocks_per_row, W, H))
         return fail(SFMBA_ERR_INVALID_ARG, w + ": the atlas has a side above 16384");
     return 0;
+}
+// what the texturing calls refuse about the view rule
+int texture_check_rule(const char* who, float occl_tol, int64_t min_area) {
+    const std::string w(who);
+    if (!std::isfinite(occl_tol) || occl_tol < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, w + ": occl_tol must be finite and >= 0");
+    if (min_area < 0) return fail(SFMBA_ERR_INVALID_ARG, w + ": min_area must be >= 0");
+    return 0;
+}
+// ---- what the label calls refuse ------------------------------------------------------------------------------------------------
+int label_check_count(const char* who, int64_t n_triangles) {
+    if (n_triangles < 0 || n_triangles > (int64_t)(INT_MAX / 3))
+        return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": 3 n_triangles must lie in 0 .. 2^31 - 1");
+    return 0;
+}
+int label_check_k(const char* who, int n_candidates) {
+    if (n_candidates < 1 || n_candidates > LABEL_MAX_K) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": n_candidates must be in 1..8");
+    return 0;
+}
+int label_check_params(const char* who, int rings, int penalty, int max_passes) {
+    const std::string w(who);
+    if (rings < 0 || rings > LABEL_MAX_RINGS) return fail(SFMBA_ERR_INVALID_ARG, w + ": rings must be in 0..8");
+    if (penalty < 0 || penalty > LABEL_MAX_PENALTY) return fail(SFMBA_ERR_INVALID_ARG, w + ": penalty must be in 0..65535");
+    if (max_passes < 0 || max_passes > LABEL_MAX_PASSES) return fail(SFMBA_ERR_INVALID_ARG, w + ": max_passes must be in 0..10000");
+    return 0;
+}
+// the lists as sfmba_mesh_view_candidates writes them and an adjacency within the mesh
+int label_check_lists(const char* who, int64_t nt, int n_images, int K, const int32_t* cand_view, const int64_t* cand_score, const int32_t* adj) {
+    const std::string w(who);
+    for (int64_t t = 0; t < nt; ++t) {
+        for (int q = 0; q < 3; ++q)
+            if (adj[3 * t + q] < -1 || adj[3 * t + q] >= nt) return fail(SFMBA_ERR_INVALID_ARG, w + ": an adj entry lies outside -1 .. n_triangles-1");
+        for (int k = 0; k < K; ++k) {
+            const int32_t v = cand_view[t * K + k];
+            const int64_t s = cand_score[t * K + k];
+            if (v < -1 || v >= n_images) return fail(SFMBA_ERR_INVALID_ARG, w + ": a cand_view lies outside -1 .. n_images-1");
+            const bool ordered = v < 0 ? s == 0 : (s > 0 && s < LABEL_SCORE_LIMIT && (k == 0 || (cand_view[t * K + k - 1] >= 0 && cand_score[t * K + k - 1] >= s)));
+            if (!ordered) return fail(SFMBA_ERR_INVALID_ARG, w + ": a row is not a list of sfmba_mesh_view_candidates (scores in 1 .. 2^37-1, descending, then -1 and 0)");
+        }
+    }
+    return 0;
+}
+int texture_result(int rc, const char* who) {
+    if (rc == TEX_ERR_INDEX) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": a triangle index lies outside the vertex list");
+    if (rc == TEX_ERR_VIEW) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": a view lies outside -1 .. n_images-1");
+    return unit_result(rc, who);
+}
+void label_timing_line(const char* what, const double* t, long long nt) {
+    std::fprintf(stderr, "[sfmba %s] upload_ms %.6f candidates_ms %.6f keys_ms %.6f sort_ms %.6f link_ms %.6f rings_ms %.6f start_ms %.6f gain_ms %.6f "
+                         "move_ms %.6f stats_ms %.6f download_ms %.6f triangles %lld\n",
+                 what, t[LAB_T_UPLOAD], t[LAB_T_CANDIDATES], t[LAB_T_KEYS], t[LAB_T_SORT], t[LAB_T_LINK], t[LAB_T_RINGS], t[LAB_T_START], t[LAB_T_GAIN],
+                 t[LAB_T_MOVE], t[LAB_T_STATS], t[LAB_T_DOWNLOAD], nt);
 }
 }  // namespace
 
@@ -918,8 +970,7 @@ int sfmba_mesh_texture(int device, int64_t n_vertices, const float* xyz, const u
     if (const int rc = clean_check_mesh("mesh_texture", n_vertices, xyz, true, n_triangles, tri)) return rc;
     if (!atlas || !uv || !view || !n_textured || (n_images > 0 && !depth)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
     if (const int rc = depth_check_images("mesh_texture", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
-    if (!std::isfinite(occl_tol) || occl_tol < 0.0f) return fail(SFMBA_ERR_INVALID_ARG, "mesh_texture: occl_tol must be finite and >= 0");
-    if (min_area < 0) return fail(SFMBA_ERR_INVALID_ARG, "mesh_texture: min_area must be >= 0");
+    if (const int rc = texture_check_rule("mesh_texture", occl_tol, min_area)) return rc;
     long long W, H;
     if (const int rc = texture_check_layout("mesh_texture", n_triangles, patch, blocks_per_row, W, H)) return rc;
     const TexMesh m{ (int)n_vertices, (int)n_triangles, xyz, bgr, tri };
@@ -934,8 +985,105 @@ int sfmba_mesh_texture(int device, int64_t n_vertices, const float* xyz, const u
                              "triangles %lld images %d width %lld height %lld textured %lld\n",
                      c.t[TEX_T_UPLOAD], c.t[TEX_T_CHECK], c.t[TEX_T_VIEWS], c.t[TEX_T_RASTER], c.t[TEX_T_DOWNLOAD], (long long)n_vertices,
                      (long long)n_triangles, n_images, W, H, (long long)*n_textured);
-    if (rc == TEX_ERR_INDEX) return fail(SFMBA_ERR_INVALID_ARG, "mesh_texture: a triangle index lies outside the vertex list");
-    return unit_result(rc, "mesh_texture");
+    return texture_result(rc, "mesh_texture");
+}
+// ---- smoothing the view labels (SfM::textureMesh with TextureParams::smoothRings / smoothPasses) ------------------------------------
+int sfmba_mesh_view_candidates(int device, int64_t n_vertices, const float* xyz, int64_t n_triangles, const int32_t* tri, int n_images,
+                               const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels,
+                               const float* K, const float* P, const float* const* depth, float occl_tol, int64_t min_area, int n_candidates,
+                               int32_t* cand_view, int64_t* cand_score) {
+    if (const int rc = clean_check_mesh("mesh_view_candidates", n_vertices, xyz, true, n_triangles, tri)) return rc;
+    if ((n_triangles > 0 && (!cand_view || !cand_score)) || (n_images > 0 && !depth)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (const int rc = depth_check_images("mesh_view_candidates", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    if (const int rc = texture_check_rule("mesh_view_candidates", occl_tol, min_area)) return rc;
+    if (const int rc = label_check_k("mesh_view_candidates", n_candidates)) return rc;
+    const TexMesh m{ (int)n_vertices, (int)n_triangles, xyz, nullptr, tri };
+    const TexViews views{ n_images, img_ptr, pixels, width, height, channels, K, P, depth };
+    TimedCall<LAB_T_COUNT> c("SFMBA_MESH_LABELS_TIMING");        // (tools/texture_smooth_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_view_candidates(c.kit.stream, device, m, views, occl_tol, min_area, n_candidates, cand_view, cand_score, c.tm());
+    if (rc == 0 && c.on) label_timing_line("mesh_view_candidates", c.t, (long long)n_triangles);
+    return texture_result(rc, "mesh_view_candidates");
+}
+int sfmba_mesh_adjacency(int device, int64_t n_triangles, const int32_t* tri, int32_t* adj, int64_t* n_pairs, int64_t* n_open_edges,
+                         int64_t* n_nonmanifold_edges) {
+    if (const int rc = label_check_count("mesh_adjacency", n_triangles)) return rc;
+    if (!n_pairs || !n_open_edges || !n_nonmanifold_edges || (n_triangles > 0 && (!tri || !adj))) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    for (int64_t i = 0; i < 3 * n_triangles; ++i)
+        if (tri[i] < 0) return fail(SFMBA_ERR_INVALID_ARG, "mesh_adjacency: a triangle index is negative");
+    TimedCall<LAB_T_COUNT> c("SFMBA_MESH_LABELS_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    int64_t counts[3] = { 0, 0, 0 };
+    const int rc = mesh_adjacency(c.kit.stream, device, (int)n_triangles, tri, adj, counts, c.tm());
+    if (rc == 0) { *n_pairs = counts[0]; *n_open_edges = counts[1]; *n_nonmanifold_edges = counts[2]; }
+    if (rc == 0 && c.on) label_timing_line("mesh_adjacency", c.t, (long long)n_triangles);
+    return unit_result(rc, "mesh_adjacency");
+}
+int sfmba_mesh_view_smooth(int device, int64_t n_triangles, int n_images, int n_candidates, const int32_t* cand_view, const int64_t* cand_score,
+                           const int32_t* adj, int rings, int penalty, int max_passes, int32_t* view, int64_t* stats) {
+    if (const int rc = label_check_count("mesh_view_smooth", n_triangles)) return rc;
+    if (n_images < 0) return fail(SFMBA_ERR_INVALID_ARG, "bad argument");
+    if (!stats || (n_triangles > 0 && (!cand_view || !cand_score || !adj || !view))) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (const int rc = label_check_k("mesh_view_smooth", n_candidates)) return rc;
+    if (const int rc = label_check_params("mesh_view_smooth", rings, penalty, max_passes)) return rc;
+    if (const int rc = label_check_lists("mesh_view_smooth", n_triangles, n_images, n_candidates, cand_view, cand_score, adj)) return rc;
+    const LabelParams p{ n_candidates, rings, penalty, max_passes };
+    TimedCall<LAB_T_COUNT> c("SFMBA_MESH_LABELS_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_view_smooth(c.kit.stream, device, (int)n_triangles, p, cand_view, cand_score, adj, view, stats, c.tm());
+    if (rc == 0 && c.on) label_timing_line("mesh_view_smooth", c.t, (long long)n_triangles);
+    return unit_result(rc, "mesh_view_smooth");
+}
+int sfmba_mesh_texture_from_views(int device, int64_t n_vertices, const float* xyz, const unsigned char* bgr, int64_t n_triangles, const int32_t* tri,
+                                  int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                                  int channels, const float* K, const float* P, int patch, int blocks_per_row, const int32_t* view, unsigned char* atlas,
+                                  float* uv, int64_t* n_textured) {
+    if (const int rc = clean_check_mesh("mesh_texture_from_views", n_vertices, xyz, true, n_triangles, tri)) return rc;
+    if (!atlas || !uv || !n_textured || (n_triangles > 0 && !view)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (const int rc = depth_check_images("mesh_texture_from_views", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    long long W, H;
+    if (const int rc = texture_check_layout("mesh_texture_from_views", n_triangles, patch, blocks_per_row, W, H)) return rc;
+    const std::vector<const float*> no_maps((size_t)std::max(n_images, 1), nullptr);       // the labels are given: nothing is tested
+    const TexMesh m{ (int)n_vertices, (int)n_triangles, xyz, bgr, tri };
+    const TexViews views{ n_images, img_ptr, pixels, width, height, channels, K, P, no_maps.data() };
+    const TexParams prm{ 0.0f, 0, patch, blocks_per_row, (int)W, (int)H };
+    const TexOut out{ atlas, uv, nullptr, nullptr, n_textured };
+    const int32_t none = -1;
+    const TexLabels labels{ n_triangles > 0 ? view : &none, 0, 0, 0, 0, nullptr, nullptr };
+    TimedCall<TEX_T_COUNT> c("SFMBA_MESH_TEXTURE_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_texture(c.kit.stream, device, m, views, prm, out, c.tm(), &labels);
+    return texture_result(rc, "mesh_texture_from_views");
+}
+int sfmba_mesh_texture_smooth(int device, int64_t n_vertices, const float* xyz, const unsigned char* bgr, int64_t n_triangles, const int32_t* tri,
+                              int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                              int channels, const float* K, const float* P, const float* const* depth, float occl_tol, int64_t min_area, int patch,
+                              int blocks_per_row, int n_candidates, int rings, int penalty, int max_passes, unsigned char* atlas, float* uv,
+                              int32_t* view, int64_t* score, int64_t* n_textured, int64_t* stats) {
+    if (const int rc = clean_check_mesh("mesh_texture_smooth", n_vertices, xyz, true, n_triangles, tri)) return rc;
+    if (!atlas || !uv || !view || !n_textured || !stats || (n_images > 0 && !depth)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (const int rc = depth_check_images("mesh_texture_smooth", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    if (const int rc = texture_check_rule("mesh_texture_smooth", occl_tol, min_area)) return rc;
+    long long W, H;
+    if (const int rc = texture_check_layout("mesh_texture_smooth", n_triangles, patch, blocks_per_row, W, H)) return rc;
+    if (const int rc = label_check_count("mesh_texture_smooth", n_triangles)) return rc;
+    if (const int rc = label_check_k("mesh_texture_smooth", n_candidates)) return rc;
+    if (const int rc = label_check_params("mesh_texture_smooth", rings, penalty, max_passes)) return rc;
+    const TexMesh m{ (int)n_vertices, (int)n_triangles, xyz, bgr, tri };
+    const TexViews views{ n_images, img_ptr, pixels, width, height, channels, K, P, depth };
+    const TexParams prm{ occl_tol, min_area, patch, blocks_per_row, (int)W, (int)H };
+    const TexOut out{ atlas, uv, view, score, n_textured };
+    TimedCall<TEX_T_COUNT> c("SFMBA_MESH_TEXTURE_TIMING");
+    double lt[LAB_T_COUNT];
+    const TexLabels labels{ nullptr, n_candidates, rings, penalty, max_passes, stats, c.on ? lt : nullptr };
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_texture(c.kit.stream, device, m, views, prm, out, c.tm(), &labels);
+    if (rc == 0 && c.on) {
+        std::fprintf(stderr, "[sfmba mesh_texture_smooth] upload_ms %.6f check_ms %.6f views_ms %.6f raster_ms %.6f download_ms %.6f triangles %lld\n",
+                     c.t[TEX_T_UPLOAD], c.t[TEX_T_CHECK], c.t[TEX_T_VIEWS], c.t[TEX_T_RASTER], c.t[TEX_T_DOWNLOAD], (long long)n_triangles);
+        label_timing_line("mesh_texture_smooth", lt, (long long)n_triangles);
+    }
+    return texture_result(rc, "mesh_texture_smooth");
 }
 // ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------
 int sfmba_pnp_ransac(int device, int n_prob, const int64_t* prob_ptr, const float* xyz, const float* uv, const float* K, int n_hyp,

@@ -16,9 +16,15 @@
 //                 the 256 lanes walk the group's texels: one 3-vector blend, one projection with two fp64 divisions, four byte loads
 //                 per channel, three byte stores.  A texel nobody owns is written as 0, so the atlas needs no clear.
 //
+//   labels        (TexLabels, off unless a caller asks) GIVEN: k_tex_given holds the caller's labels to -1 .. n_images-1 (its own flag
+//                 word) and writes the corner uv in place of k_tex_views.  SMOOTHED: the same kernel writes uv alone, then the
+//                 candidates, the adjacency and the smoothing of mesh_labels.hip write the labels and the scores on the device, so
+//                 the views are projected once.  The raster is the same.
+//
 // SCRATCH, for V vertices, T triangles, an atlas of A texels, n images with p pixels and m depth-map pixels: the mesh 15 V + 12 T, the
 // outputs 3 A + 36 T, the views 128 n + channels p + 4 m.
 #include "mesh_texture.h"
+#include "mesh_labels.h"
 #include "texture_math.h"
 #include "device_arena.h"
 
@@ -35,28 +41,6 @@ constexpr int LANES = 256;
 constexpr int TEX_GROUP_TEXELS = 1024;         // a workgroup takes about this many texels ...
 constexpr int TEX_GROUP_MAX_BLOCKS = 32;       // ... in at most this many blocks (64 triangles in LDS)
 
-struct TexImage {
-    double P[12];
-    long long map_off;       // first float of its depth map among the maps on the device, -1 without a map
-    long long raw_off;       // first byte of its pixels among the pixels on the device
-    int w, h;
-    long long pad;           // 128 bytes
-};
-static_assert(sizeof(TexImage) == 128, "TexImage is 16 words");
-
-struct TexKernelParams {
-    double k4[4];
-    double occl_tol;
-    long long min_area;
-    int nv, nt, n_images, channels;
-    int S, B, W, H;          // B: blocks per row of the atlas as laid out (1 for an empty mesh)
-    int slots, group;        // block slots of the atlas (rows x B), blocks per workgroup of the raster
-};
-
-__device__ __forceinline__ TexView view_of(const TexImage& T, const float* __restrict__ maps, const unsigned char* __restrict__ raw) {
-    return TexView{ T.P, T.map_off >= 0 ? maps + T.map_off : nullptr, raw + T.raw_off, T.w, T.h };
-}
-
 __global__ __launch_bounds__(LANES) void k_tex_check(int nt, int nv, const int* __restrict__ tri, int* __restrict__ flag) {
     const long long t = (long long)blockIdx.x * LANES + threadIdx.x;
     if (t >= nt) return;
@@ -66,10 +50,6 @@ __global__ __launch_bounds__(LANES) void k_tex_check(int nt, int nv, const int* 
         b = b || v < 0 || v >= nv;
     }
     if (b) flag[0] = 1;
-}
-
-__device__ __forceinline__ void load_vertex(const float* __restrict__ xyz, int v, double* X) {
-    for (int a = 0; a < 3; ++a) X[a] = (double)xyz[3 * (size_t)v + a];
 }
 
 __global__ __launch_bounds__(LANES) void k_tex_views(TexKernelParams prm, const int* __restrict__ flag, const float* __restrict__ xyz,
@@ -95,6 +75,21 @@ __global__ __launch_bounds__(LANES) void k_tex_views(TexKernelParams prm, const 
     }
     view[t] = best_view;
     score[t] = best;
+    float corner[6];
+    tex_corner_uv(t, prm.S, prm.B, corner);
+    for (int q = 0; q < 6; ++q) uv[6 * (size_t)t + q] = corner[q];
+}
+
+// Labels that k_tex_views does not choose: a lane per triangle writes the corner uv, which k_tex_views writes otherwise.  GIVEN labels
+// (sfmba_mesh_texture_from_views; view != NULL) are held to -1 .. n_images-1, raising flag[0], which stops the raster, and flag[1],
+// which names the reason.  SMOOTHED labels (view == NULL) come later, from mesh_labels.hip, and need no check.
+__global__ __launch_bounds__(LANES) void k_tex_given(TexKernelParams prm, const int* __restrict__ view, int* __restrict__ flag, float* __restrict__ uv) {
+    const long long t = (long long)blockIdx.x * LANES + threadIdx.x;
+    if (t >= prm.nt) return;
+    if (view) {
+        const int v = view[t];
+        if (v < -1 || v >= prm.n_images) { flag[0] = 1; flag[1] = 1; }
+    }
     float corner[6];
     tex_corner_uv(t, prm.S, prm.B, corner);
     for (int q = 0; q < 6; ++q) uv[6 * (size_t)t + q] = corner[q];
@@ -185,15 +180,9 @@ unsigned blocks_for(long long n) { return (unsigned)((n + LANES - 1) / LANES); }
 
 }  // namespace
 
-int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v, const TexParams& p, const TexOut& out, double* timing) {
-    if (timing) for (int i = 0; i < TEX_T_COUNT; ++i) timing[i] = 0.0;
-    DeviceArena scratch(device);
-    PhaseTimer tm{ s, timing != nullptr, {}, {} };
-    const size_t NV = (size_t)m.nv, NT = (size_t)m.nt, texels = (size_t)p.W * (size_t)p.H;
-
-    // the view table
-    std::vector<TexImage> tab((size_t)v.n_images);
-    long long n_map = 0, n_raw = 0;
+void tex_view_table(const TexViews& v, std::vector<TexImage>& tab, long long& n_map, long long& n_raw) {
+    tab.assign((size_t)v.n_images, TexImage{});
+    n_map = n_raw = 0;
     for (int i = 0; i < v.n_images; ++i) {
         TexImage& T = tab[(size_t)i];
         std::memset(&T, 0, sizeof(T));
@@ -205,13 +194,43 @@ int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v,
         T.raw_off = n_raw;
         n_raw += px * v.channels;
     }
+}
+void tex_camera_params(const TexViews& v, float occl_tol, int64_t min_area, TexKernelParams& prm) {
+    prm.k4[0] = (double)v.K[0]; prm.k4[1] = (double)v.K[4]; prm.k4[2] = (double)v.K[2]; prm.k4[3] = (double)v.K[5];
+    prm.occl_tol = (double)occl_tol;
+    prm.min_area = (long long)min_area;
+    prm.n_images = v.n_images; prm.channels = v.channels;
+}
+int tex_check_indices(hipStream_t s, int nt, int nv, const int* d_tri, int* d_flag) {
+    if (nt > 0) {
+        hipLaunchKernelGGL(k_tex_check, dim3(blocks_for(nt)), dim3(LANES), 0, s, nt, nv, d_tri, d_flag);
+        UNIT_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v, const TexParams& p, const TexOut& out, double* timing,
+                 const TexLabels* labels) {
+    if (timing) for (int i = 0; i < TEX_T_COUNT; ++i) timing[i] = 0.0;
+    DeviceArena scratch(device), raw(device);                    // raw: the label stage's temporaries, not zeroed (mesh_labels.h)
+    PhaseTimer tm{ s, timing != nullptr, {}, {} };
+    const size_t NV = (size_t)m.nv, NT = (size_t)m.nt, texels = (size_t)p.W * (size_t)p.H;
+    const bool given = labels && labels->view_in, smooth = labels && !labels->view_in;
+    int64_t st[LABEL_STATS] = { 0 };
+    PhaseTimer ltm{ s, smooth && labels->timing != nullptr, {}, {} };
+    if (ltm.on) for (int i = 0; i < LAB_T_COUNT; ++i) labels->timing[i] = 0.0;
+
+    // the view table
+    std::vector<TexImage> tab;
+    long long n_map = 0, n_raw = 0;
+    tex_view_table(v, tab, n_map, n_raw);
 
     int *d_flag, *d_tri, *d_view;
     float *d_xyz, *d_maps, *d_uv;
     unsigned char *d_bgr = nullptr, *d_raw, *d_atlas;
     long long* d_score;
     TexImage* d_tab;
-    UNIT_ALLOC(scratch, d_flag, int, 1);                         // zeroed
+    UNIT_ALLOC(scratch, d_flag, int, 2);                         // zeroed
     UNIT_ALLOC(scratch, d_tri, int, NT * 3);
     UNIT_ALLOC(scratch, d_xyz, float, NV * 3);
     if (m.bgr) UNIT_ALLOC(scratch, d_bgr, unsigned char, NV * 3);
@@ -227,6 +246,7 @@ int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v,
     TEX_COPY(d_tri, m.tri, sizeof(int) * NT * 3, hipMemcpyHostToDevice);
     TEX_COPY(d_xyz, m.xyz, sizeof(float) * NV * 3, hipMemcpyHostToDevice);
     if (d_bgr) TEX_COPY(d_bgr, m.bgr, NV * 3, hipMemcpyHostToDevice);
+    if (given) TEX_COPY(d_view, labels->view_in, sizeof(int) * NT, hipMemcpyHostToDevice);
     TEX_COPY(d_tab, tab.data(), sizeof(TexImage) * tab.size(), hipMemcpyHostToDevice);
     for (int i = 0; i < v.n_images; ++i) {
         const TexImage& T = tab[(size_t)i];
@@ -237,10 +257,8 @@ int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v,
     tm.end();
 
     TexKernelParams prm;
-    prm.k4[0] = (double)v.K[0]; prm.k4[1] = (double)v.K[4]; prm.k4[2] = (double)v.K[2]; prm.k4[3] = (double)v.K[5];
-    prm.occl_tol = (double)p.occl_tol;
-    prm.min_area = (long long)p.min_area;
-    prm.nv = m.nv; prm.nt = m.nt; prm.n_images = v.n_images; prm.channels = v.channels;
+    tex_camera_params(v, p.occl_tol, p.min_area, prm);
+    prm.nv = m.nv; prm.nt = m.nt;
     prm.S = p.patch; prm.W = p.W; prm.H = p.H;
     prm.B = p.W / (p.patch + 1);
     prm.slots = prm.B * (p.H / p.patch);
@@ -248,14 +266,36 @@ int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v,
     prm.group = std::max(1, std::min(TEX_GROUP_MAX_BLOCKS, TEX_GROUP_TEXELS / per));
 
     tm.begin(TEX_T_CHECK);
-    if (m.nt > 0) {
-        hipLaunchKernelGGL(k_tex_check, dim3(blocks_for(m.nt)), dim3(LANES), 0, s, m.nt, m.nv, d_tri, d_flag);
-        UNIT_TRY(hipGetLastError());
-    }
+    if (int rc = tex_check_indices(s, m.nt, m.nv, d_tri, d_flag)) return rc;
     tm.next(TEX_T_VIEWS);
-    if (m.nt > 0) {
+    if (m.nt > 0 && (given || smooth)) {
+        hipLaunchKernelGGL(k_tex_given, dim3(blocks_for(m.nt)), dim3(LANES), 0, s, prm, given ? d_view : (const int*)nullptr, d_flag, d_uv);
+        UNIT_TRY(hipGetLastError());
+    } else if (m.nt > 0) {
         hipLaunchKernelGGL(k_tex_views, dim3(blocks_for(m.nt)), dim3(LANES), 0, s, prm, d_flag, d_xyz, d_tri, d_tab, d_maps, d_raw, d_view, d_score, d_uv);
         UNIT_TRY(hipGetLastError());
+    }
+    if (smooth) {
+        // the K best views, the adjacency, the smoothing: they write d_view and d_score.  The smoothing waits for the stream,
+        // so the index flag is read first: a list with a bad index goes no further.
+        int bad = 0;
+        UNIT_TRY(hipMemcpyAsync(&bad, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+        UNIT_TRY(hipStreamSynchronize(s));
+        if (bad) return TEX_ERR_INDEX;
+        const LabelParams lp{ labels->K, labels->rings, labels->penalty, labels->max_passes };
+        raw.set_zeroing(false);                                  // what the label stage takes is written in full before it is read
+        int *d_cv = nullptr, *d_adj = nullptr;
+        long long* d_cs = nullptr;
+        unsigned long long* d_counts = nullptr;
+        UNIT_ALLOC(raw, d_cv, int, NT * (size_t)lp.K);
+        UNIT_ALLOC(raw, d_cs, long long, NT * (size_t)lp.K);
+        UNIT_ALLOC(raw, d_adj, int, NT * 3);
+        UNIT_ALLOC(scratch, d_counts, unsigned long long, 3);
+        ltm.begin(LAB_T_CANDIDATES);
+        if (int rc = labels_candidates_dev(s, prm, d_flag, d_xyz, d_tri, d_tab, d_maps, d_raw, lp.K, d_cv, d_cs)) return rc;
+        ltm.end();
+        if (int rc = labels_adjacency_dev(s, raw, m.nt, d_tri, d_adj, d_counts, &ltm)) return rc;
+        if (int rc = labels_smooth_dev(s, scratch, raw, m.nt, lp, d_cv, d_cs, d_adj, d_view, d_score, st, &ltm)) return rc;
     }
     tm.next(TEX_T_RASTER);
     hipLaunchKernelGGL(k_tex_raster, dim3((unsigned)((prm.slots + prm.group - 1) / prm.group)), dim3(LANES), 0, s, prm, d_flag, d_xyz, d_bgr, d_tri, d_tab,
@@ -263,23 +303,26 @@ int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v,
     UNIT_TRY(hipGetLastError());
     tm.end();
 
-    int flag = 0;
-    UNIT_TRY(hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    int flag[2] = { 0, 0 };
+    UNIT_TRY(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s));
     UNIT_TRY(hipStreamSynchronize(s));                           // also: `tab` is spent
-    if (flag) return TEX_ERR_INDEX;
+    if (flag[1]) return TEX_ERR_VIEW;
+    if (flag[0]) return TEX_ERR_INDEX;
 
     tm.begin(TEX_T_DOWNLOAD);
     TEX_COPY(out.atlas, d_atlas, texels * 3, hipMemcpyDeviceToHost);
     TEX_COPY(out.uv, d_uv, sizeof(float) * NT * 6, hipMemcpyDeviceToHost);
-    TEX_COPY(out.view, d_view, sizeof(int) * NT, hipMemcpyDeviceToHost);
+    if (out.view) TEX_COPY(out.view, d_view, sizeof(int) * NT, hipMemcpyDeviceToHost);
     if (out.score) TEX_COPY(out.score, d_score, sizeof(long long) * NT, hipMemcpyDeviceToHost);
     tm.end();
     UNIT_TRY(hipStreamSynchronize(s));
+    const int32_t* final_view = given ? labels->view_in : out.view;
     int64_t textured = 0;
-    for (size_t t = 0; t < NT; ++t) textured += out.view[t] >= 0;
+    for (size_t t = 0; t < NT; ++t) textured += final_view[t] >= 0;
     *out.n_textured = textured;
+    if (smooth) for (int i = 0; i < LABEL_STATS; ++i) labels->stats[i] = st[i];
     if (timing) tm.collect(timing);
+    if (ltm.on) ltm.collect(labels->timing);
     return 0;
 }
-
 }  // namespace sfmba

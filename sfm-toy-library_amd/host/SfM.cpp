@@ -824,6 +824,13 @@ ErrorCode SfM::textureMesh(const TextureParams& params) {
     say(LOG_INFO, "textured mesh: " + std::to_string(mTexturedMesh.textured) + " of " + std::to_string(mTexturedMesh.triangles.size() / 3) +
                       " triangles have a view (" + (mCleanOkay ? "the clean mesh" : "the mesh") + "), atlas " + std::to_string(mTexturedMesh.atlas.cols) +
                       " x " + std::to_string(mTexturedMesh.atlas.rows));
+    if (mTexturedMesh.smoothed) {
+        const long long* st = mTexturedMesh.smoothStats;
+        say(LOG_INFO, "smoothed view labels: pairs of neighbours with different views " + std::to_string(st[2]) + " plain, " + std::to_string(st[3]) +
+                          " after the diffusion, " + std::to_string(st[4]) + " at the end (" + std::to_string(st[5]) +
+                          " more pairs have one side without a view); energy " + std::to_string(st[0]) + " -> " + std::to_string(st[1]) + "; " +
+                          std::to_string(st[6]) + " moves in " + std::to_string(st[7]) + " passes");
+    }
     if (timing)
         std::fprintf(stderr, "[sfmba sfm mesh_texture] texture_ms %.3f triangles %lld textured %lld width %d height %d\n", ms[0],
                      (long long)(mTexturedMesh.triangles.size() / 3), mTexturedMesh.textured, mTexturedMesh.atlas.cols, mTexturedMesh.atlas.rows);

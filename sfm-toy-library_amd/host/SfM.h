@@ -95,8 +95,14 @@
 //                 B = ceil(sqrt(ceil(triangles / 2))), at least 1 (a square atlas); occl_tol = occlTolVoxels * the grid's voxel
 //                 (float), occlTolVoxels default 2; min_area = round(2 * 256 * minAreaPx), minAreaPx default 0.5.  These are first
 //                 choices that NOBODY HAS TUNED.  NO COLOUR ADJUSTMENT ACROSS VIEWS (seams where exposures differ stay visible), NO
-//                 SMOOTHING OF THE VIEW LABELS, NO CHART MERGING (every triangle costs (S + 1) S / 2 texels, however small).  The
-//                 mesh, the clean mesh, the dense cloud and the depth maps are not changed.
+//                 SMOOTHING OF THE VIEW LABELS BY DEFAULT, NO CHART MERGING (every triangle costs (S + 1) S / 2 texels, however small).
+//                 The mesh, the clean mesh, the dense cloud and the depth maps are not changed.
+//                 With params.smoothRings or params.smoothPasses not 0 the labels are chosen TOGETHER, by ONE
+//                 sfmba_mesh_texture_smooth call in place of the plain one (include/sfmba.h, "smoothing the view labels"): the
+//                 params.candidates best views per triangle, their scores summed over smoothRings rings of neighbours, then at most
+//                 smoothPasses passes of a Potts relaxation with the penalty smoothPenalty; the textured mesh then carries the call's
+//                 eight statistics, and an INFO line reports them.  The defaults (off; 256; 4 candidates) and sfmtoy's 4 rings, 256
+//                 and 100 passes are first choices that nobody has tuned.
 // There is no visual debugging.
 // An object holds all of a run's state (the stage times of SFMBA_SFM_TIMING included): different objects may run in different
 // threads; one object is not re-entrant.

@@ -116,17 +116,29 @@ struct MeshCleanParams {
 
 // SfMDenseUtilities::textureMesh / SfM::textureMesh: the size of a triangle's patch and which views count (include/sfmba.h,
 // sfmba_mesh_texture; the host rules are at the top of SfM.h).  First choices; NOBODY HAS TUNED THEM.
+// SMOOTHING THE VIEW LABELS IS OFF BY DEFAULT: with smoothRings = 0 and smoothPasses = 0 the call is the plain sfmba_mesh_texture call and
+// the other three smoothing fields are not read.  Otherwise ONE sfmba_mesh_texture_smooth call chooses the labels together (the K =
+// candidates best views per triangle, their scores summed over smoothRings rings of neighbours, then at most smoothPasses passes of a
+// Potts relaxation with the penalty smoothPenalty, in 1/1024 of the best view's area).  sfmtoy's --texture-smooth switches 4, 256 and
+// 100 passes on; those too are first choices that nobody has tuned.
 struct TextureParams {
     int   patch;            // S: a triangle gets S (S + 1) / 2 texels, 3..64
     int   blocksPerRow;     // B: blocks (pairs of triangles) per atlas row; 0 = ceil(sqrt(blocks)), at least 1
     float occlTolVoxels;    // a vertex may lie this many voxels of the mesh's grid behind a view's depth map
     float minAreaPx;        // a view counts for a triangle from this image area, in square pixels
-    TextureParams() : patch(6), blocksPerRow(0), occlTolVoxels(2.0f), minAreaPx(0.5f) {}
+    int   smoothRings;      // r, 0..8: rings of neighbours whose scores a triangle hears before it chooses
+    int   smoothPenalty;    // p, 0..65535: what a pair of neighbours with different views costs
+    int   smoothPasses;     // 0..10000: the most relaxation passes
+    int   candidates;       // K, 1..8: views a triangle may choose among
+    TextureParams() : patch(6), blocksPerRow(0), occlTolVoxels(2.0f), minAreaPx(0.5f), smoothRings(0), smoothPenalty(256), smoothPasses(0), candidates(4) {}
 };
 
 // A mesh that carries the photographs: triangle t has the corners uv[6 t .. 6 t + 5] (u, v per corner, in atlas pixels, origin top-left)
 // in the atlas and took its texels from view[t] (-1: none saw it; its patch holds the blended vertex colours).  NO COLOUR ADJUSTMENT
-// ACROSS VIEWS, NO SMOOTHING OF THE VIEW LABELS, NO CHART MERGING (include/sfmba.h).
+// ACROSS VIEWS, NO SMOOTHING OF THE VIEW LABELS unless TextureParams asks for it (off by default), NO CHART MERGING (include/sfmba.h).
+// smoothed: the labels came from sfmba_mesh_texture_smooth, and smoothStats holds its eight statistics (include/sfmba.h: the energy after
+// the start and at the end; the pairs of neighbours with different views under the plain rule, after the start and at the end; the pairs
+// with one side without a view; the moves; the passes that moved something); all zero otherwise.
 struct TexturedMesh {
     Points3f           vertices;
     std::vector<int>   triangles;  // 3 vertex indices per triangle
@@ -134,7 +146,9 @@ struct TexturedMesh {
     std::vector<int>   view;       // 1 per triangle
     cv::Mat            atlas;      // CV_8UC3, BGR
     long long          textured;   // triangles with a view
-    TexturedMesh() : textured(0) {}
+    bool               smoothed;
+    long long          smoothStats[8];
+    TexturedMesh() : textured(0), smoothed(false), smoothStats{ 0, 0, 0, 0, 0, 0, 0, 0 } {}
 };
 
 class SfMDenseUtilities {
@@ -228,7 +242,8 @@ public:
     static Mesh cleanMesh(const Mesh& mesh, const MeshCleanParams& params, bool* ok = nullptr);
 
     /**
-     * A view per triangle and a texture atlas with one patch per triangle: ONE sfmba_mesh_texture call.  images, poses and depthMaps as
+     * A view per triangle and a texture atlas with one patch per triangle: ONE sfmba_mesh_texture call, or, when params.smoothRings or
+     * params.smoothPasses is not 0, ONE sfmba_mesh_texture_smooth call.  images, poses and depthMaps as
      * fuseDepthMaps takes them (a view without a map has no visibility test).  THE HOST RULES: B = params.blocksPerRow, or
      * ceil(sqrt(ceil(triangles / 2))) (at least 1) when that is 0; occl_tol = params.occlTolVoxels * mesh.grid.voxel (float);
      * min_area = round(2 * 256 * params.minAreaPx).

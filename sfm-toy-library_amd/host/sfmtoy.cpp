@@ -3,7 +3,7 @@
 // <prefix>_dense.ply; with --voxel on top of -D, merge that cloud and write <prefix>_dense_merged.ply; with --mesh on top of -D, mesh
 // the depth maps and write <prefix>_mesh.ply (--mesh-fill N: with the grid's holes filled by N passes first); with --mesh-clean on top of --mesh, drop the mesh's small components, smooth it and write
 // <prefix>_mesh_clean.ply; with --texture on top of --mesh, put the photographs on the mesh (the clean one with --mesh-clean) and write
-// <prefix>_textured.obj, .mtl and .png.  The arguments are parsed here
+// <prefix>_textured.obj, .mtl and .png (--texture-smooth: with the views of neighbouring triangles chosen together).  The arguments are parsed here
 // (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
 #include <cctype>
 #include <cstdlib>
@@ -52,6 +52,11 @@ void usage(std::ostream& os, const char* program) {
        << "      --texture [S]            with --mesh: also choose a view per triangle, fill a texture atlas with a patch of S (S + 1) / 2 texels\n"
        << "                               per triangle (S in 3..64, default 6) and write PREFIX_textured.obj, .mtl and .png (the clean mesh\n"
        << "                               with --mesh-clean); NO COLOUR ADJUSTMENT ACROSS VIEWS; the other files are as without it\n"
+       << "      --texture-smooth [R,P]   with --texture: choose the views of neighbouring triangles together: every view's score summed over R\n"
+       << "                               rings of neighbours (0..8) before the choice, then a Potts relaxation in which a pair of neighbours\n"
+       << "                               with different views costs P (0..65535, in 1/1024 of the best view's area); default 4,256, first\n"
+       << "                               choices that nobody has tuned; the other files are as without it\n"
+       << "      --texture-smooth-passes N  with --texture-smooth: the most relaxation passes, 0..10000 (default 100)\n"
        << "  -v, --visual-debug N         accepted and ignored: there is no visual debugging\n";
 }
 
@@ -78,11 +83,11 @@ int main(int argc, char** argv) {
     std::string directory, prefix = "output", text;
     double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0, voxel = 0.0, resolution = 256.0,
            min_component = 0.0, smooth = 10.0, fill = 0.0, fill_neighbours = 2.0, patch = 6.0, sgm_p1 = 8.0, sgm_p2 = 64.0, sgm_paths = 8.0,
-           sgm_uniqueness = 5.0;
+           sgm_uniqueness = 5.0, smooth_rings = 4.0, smooth_penalty = 256.0, smooth_passes = 100.0;
     FeatureType features = FEATURES_ORB;
     MatcherType matcher = MATCHER_DESCRIPTORS;
     bool have_directory = false, dense = false, merged = false, meshed = false, cleaned = false, clean_option = false, keep_largest = false,
-         filled = false, fill_option = false, textured = false, sgm = false, sgm_option = false;
+         filled = false, fill_option = false, textured = false, sgm = false, sgm_option = false, texture_smooth = false, smooth_option = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
         const std::string arg = argv[i];
@@ -100,6 +105,23 @@ int main(int argc, char** argv) {
                 continue;
             if (!number(text, patch) || !(patch >= 3.0) || !(patch <= 64.0) || patch != (double)(int)patch) {
                 std::cerr << argv[0] << ": --texture has a value that cannot be used\n"; usage(std::cerr, argv[0]); return 2;
+            }
+            continue;
+        }
+        if (arg == "--texture-smooth" || arg.compare(0, 17, "--texture-smooth=") == 0) {
+            // the value is optional: "--texture-smooth=R,P", or a next argument made of digits around a comma
+            texture_smooth = true;
+            text = arg.size() > 17 ? arg.substr(17) : "";
+            if (arg == "--texture-smooth" && i + 1 < argc && std::isdigit((unsigned char)argv[i + 1][0]) &&
+                std::string(argv[i + 1]).find(',') != std::string::npos && std::string(argv[i + 1]).find_first_not_of("0123456789,") == std::string::npos)
+                text = argv[++i];
+            else if (arg == "--texture-smooth")
+                continue;
+            const size_t comma = text.find(',');
+            if (comma == std::string::npos || !number(text.substr(0, comma), smooth_rings) || !number(text.substr(comma + 1), smooth_penalty) ||
+                !(smooth_rings >= 0.0) || !(smooth_rings <= 8.0) || !(smooth_penalty >= 0.0) || !(smooth_penalty <= 65535.0) ||
+                smooth_rings != (double)(int)smooth_rings || smooth_penalty != (double)(int)smooth_penalty) {
+                std::cerr << argv[0] << ": --texture-smooth has a value that cannot be used\n"; usage(std::cerr, argv[0]); return 2;
             }
             continue;
         }
@@ -166,6 +188,10 @@ int main(int argc, char** argv) {
             bad = !missing && (!number(text, smooth) || !(smooth >= 0.0) || !(smooth <= 100.0) || smooth != (double)(int)smooth);
             clean_option = true;
         }
+        else if (option(argc, argv, i, "--texture-smooth-passes", "--texture-smooth-passes", text, missing)) {
+            bad = !missing && (!number(text, smooth_passes) || !(smooth_passes >= 0.0) || !(smooth_passes <= 10000.0) || smooth_passes != (double)(int)smooth_passes);
+            smooth_option = true;
+        }
         else if (option(argc, argv, i, "-v", "--visual-debug", text, missing)) bad = !missing && !number(text, ignored);
         else if (arg.size() > 1 && arg[0] == '-') { std::cerr << argv[0] << ": unknown option " << arg << "\n"; usage(std::cerr, argv[0]); return 2; }
         else if (!have_directory) { directory = arg; have_directory = true; }
@@ -181,6 +207,8 @@ int main(int argc, char** argv) {
     if (cleaned && !meshed) { std::cerr << argv[0] << ": --mesh-clean needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
     if (clean_option && !cleaned) { std::cerr << argv[0] << ": --mesh-min-component, --mesh-keep-largest and --mesh-smooth need --mesh-clean\n"; usage(std::cerr, argv[0]); return 2; }
     if (textured && !meshed) { std::cerr << argv[0] << ": --texture needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
+    if (texture_smooth && !textured) { std::cerr << argv[0] << ": --texture-smooth needs --texture\n"; usage(std::cerr, argv[0]); return 2; }
+    if (smooth_option && !texture_smooth) { std::cerr << argv[0] << ": --texture-smooth-passes needs --texture-smooth\n"; usage(std::cerr, argv[0]); return 2; }
     if (!have_directory || directory.empty()) { std::cerr << argv[0] << ": no input directory\n"; usage(std::cerr, argv[0]); return 2; }
 
     SfM sfm((float)downscale);
@@ -223,6 +251,11 @@ int main(int argc, char** argv) {
         if (textured) {
             TextureParams texture;
             texture.patch = (int)patch;
+            if (texture_smooth) {
+                texture.smoothRings = (int)smooth_rings;
+                texture.smoothPenalty = (int)smooth_penalty;
+                texture.smoothPasses = (int)smooth_passes;
+            }
             if (sfm.textureMesh(texture) != OKAY) return 1;
             if (!sfm.saveTexturedMeshToOBJ(prefix)) return 1;
         }
