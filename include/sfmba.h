@@ -1424,7 +1424,8 @@ SFMBA_API int sfmba_mesh_clean(int device, int64_t n_vertices, const float* xyz 
  *                 floor((2 (wA cA + wB cB + wC cC) + (S - 2)) / (2 (S - 2))) in integers, clamped to 0..255, with cA, cB, cC the
  *                 corners' bgr -- a FLOOR division, not a truncation -- and (0, 0, 0) where bgr is NULL.
  *   outputs       atlas uint8 [H][W][3], BGR; uv; view int32 [n_triangles]; score int64 [n_triangles] or NULL; *n_textured.
- *   NO COLOUR ADJUSTMENT ACROSS VIEWS: SEAMS WHERE EXPOSURES DIFFER STAY VISIBLE.  NO SMOOTHING OF THE VIEW LABELS in this call (off by
+ *   NO COLOUR ADJUSTMENT ACROSS VIEWS unless asked for (off by default), see "levelling the colours across seams" below: SEAMS WHERE
+ *   EXPOSURES DIFFER STAY VISIBLE.  NO SMOOTHING OF THE VIEW LABELS in this call (off by
  *   default: see sfmba_mesh_texture_smooth in the next section).  NO CHART MERGING: THE ATLAS SPENDS (S + 1) S / 2 TEXELS ON EVERY
  *   TRIANGLE, HOWEVER SMALL.
  *
@@ -1507,7 +1508,7 @@ SFMBA_API int sfmba_mesh_texture(int device, int64_t n_vertices, const float* xy
  *   candidate; may be NULL), atlas, uv and *n_textured of from_views.  With rings = 0 and max_passes = 0 it equals sfmba_mesh_texture
  *   byte for byte in atlas, uv, view, score and n_textured.
  *
- *   OUT OF SCOPE: colour adjustment across views; chart merging; letting a triangle below the area floor borrow a neighbour's view; any
+ *   OUT OF SCOPE: chart merging; letting a triangle below the area floor borrow a neighbour's view; any
  *   optimiser stronger than this local one (no graph cut, no message passing).
  *   SFMBA_ERR_INVALID_ARG (nothing written): what sfmba_mesh_texture refuses about the arguments a call shares with it; K outside 1..8;
  *                 rings outside 0..8; penalty outside 0..65535; max_passes outside 0..10000; 3 T >= 2^31; a negative index
@@ -1541,6 +1542,93 @@ SFMBA_API int sfmba_mesh_texture_smooth(int device, int64_t n_vertices, const fl
                 int penalty /*0..65535*/, int max_passes /*0..10000*/, unsigned char* atlas /*[H][W][3] BGR*/,
                 float* uv /*[n_triangles][3][2]*/, int32_t* view /*[n_triangles]*/, int64_t* score /*[n_triangles] or NULL*/,
                 int64_t* n_textured, int64_t* stats /*[8]*/);
+
+/* ---- levelling the colours across seams: a node per (vertex, view), additive offsets by integer diffusion (SfM::textureMesh) --------
+ * Where two triangles take their texels from different photographs, the difference in exposure and vignetting shows as a step at the
+ * shared edge.  The calls of this section give every (vertex, view) pair an additive colour offset: the offsets of one vertex in two
+ * views close the gap between the two photographs, the offsets within one view vary smoothly over the mesh, and the raster interpolates
+ * the offset across each triangle's patch (global seam levelling after Lempitsky & Ivanov and Waechter et al., by Jacobi passes).
+ * OFF BY DEFAULT: nothing above changes.  THE CONTRACT IS OUR OWN AND EQUALS NOBODY'S, and it is stated so that the device is held BIT
+ * FOR BIT to a CPU restatement (tests/colour_oracle.py).  Past the fixed-point image coordinate of the texture call EVERYTHING IS
+ * INTEGER ARITHMETIC (csrc/colour_math.h) and every division is a FLOOR division.  The only atomic is an integer add on the count of
+ * clamped texels.  T = n_triangles; a sum written a + b + c is ((a + b) + c).  Every call of this section needs 3 T < 2^31.
+ *
+ * sfmba_mesh_colour_nodes
+ *   the mesh (xyz, tri), the views exactly as sfmba_mesh_texture_from_views takes them, view [T] GIVEN (each entry -1 or an image
+ *   index) and a sample radius r in 0..2.  A triangle CONTRIBUTES iff view[t] >= 0, it has no repeated index and its three vertices are
+ *   finite; it names the three keys (tri[t][q] << 32) | view[t].  A NODE is a distinct key; nodes are numbered in ascending key order.
+ *   Outputs: *n_nodes; node_vertex, node_view int32 [3 T] and seen uint8 [3 T], F int32 [3 T][3], of which the first n_nodes entries
+ *   are written (the caller provides 3 T); node_of int32 [T][3], -1 -1 -1 for a triangle that does not contribute.
+ *   The colour of a node (v, l): X = the doubles of the vertex's floats; the texture call's texel rule gives (su, sv) in view l; where it
+ *   gives none (q_2 <= 0 or a NaN) the node is BLIND: seen = 0, F = 0.  Otherwise seen = 1 and, with n = (2 r + 1)^2, per channel c
+ *   SUM = the sum of the 12-bit samples at (clamp(su + 16 dx, 0, 16 (w - 1)), clamp(sv + 16 dy, 0, 16 (h - 1))) over dx, dy in -r..r
+ *   and F_c = floor((32 SUM + n) / (2 n)): the mean sample in 1/256 grey level, 0..65280.  A gray image gives three equal channels.
+ *   (Implementation: the keys, one stable radix sort with the value 3 t + q, head flags and an exclusive sum.)
+ *
+ * sfmba_mesh_colour_level
+ *   PURE INTEGER: it reads no pixel and no coordinate.  Inputs: n_nodes, node_vertex [n_nodes] NON-DECREASING, seen [n_nodes] (not 0:
+ *   seeing), F [n_nodes][3] each in 0..65280, node_of [T][3] with every row all -1 or all in 0 .. n_nodes-1, a seam weight w in 1..256
+ *   and passes N in 0..1024.  Outputs: g int32 [n_nodes][3] in 1/256 grey level and stats int64 [8].
+ *   g^0 = 0.  A blind node keeps g = 0, belongs to no sibling set and is nobody's link.  sib(n) is the seeing nodes with n's
+ *   node_vertex, n INCLUDED; k = |sib(n)|.  The LINKS of n are, for every entry node_of[t][q] = n, the two other entries of that row
+ *   that are seeing nodes: an interior edge of one view counts twice and a border edge once, which is intended.
+ *   One pass, for every seeing node n and channel c: A = sum over m in sib(n) of ((F_m + g^i_m) - F_n) and a = k if k >= 2, else
+ *   A = a = 0; B = the sum of g^i_u over the links of n and b their number; den = w a + b, num = w A + B.  If den = 0,
+ *   g^{i+1}_n = g^i_n; otherwise g^{i+1}_n = clamp(floor((2 num + den) / (2 den)), -65280, 65280).  Every pass reads only the pass
+ *   before (Jacobi, two buffers); exactly N passes run: no convergence test.  k <= n_images, |F + g| < 2^18, w <= 2^8: int64 holds
+ *   every sum with room to spare.  With the node in its own sibling set the spread at a seam falls monotonically with the passes.
+ *   stats: [0] nodes, [1] blind nodes, [2] SEAM VERTICES (vertices with k >= 2), [3] the sum over seam vertices and channels of
+ *   (max - min of F over the siblings), [4] the same of F + g^N, [5] the largest |g^N|, [6] 0 (see the adjust call), [7] N.
+ *
+ * sfmba_mesh_texture_levelled
+ *   sfmba_mesh_texture_from_views plus node_of [T][3], g [n_nodes][3] (each in -65280..65280) and n_nodes: the same layout, uv and
+ *   fallback.  A texel that is SAMPLED takes per channel G = (wA g_A + wB g_B) + wC g_C with the texel's own integer weights (the
+ *   least is -1) and the offsets of the nodes node_of[t][0..2] (a row of -1: G = 0), and
+ *   texel = clamp(floor((16 (S - 2) s12 + G + 128 (S - 2)) / (256 (S - 2))), 0, 255).  With G = 0 this is (s12 + 8) >> 4, the texture
+ *   call's texel.  FALLBACK TEXELS ARE NEVER ADJUSTED.  Extra outputs: *n_textured, and *n_clamped = the texels for which the clamp
+ *   changed at least one channel.
+ *
+ * sfmba_mesh_texture_adjust
+ *   the arguments of sfmba_mesh_texture_smooth, then sample_radius, seam_weight, level_passes and level_stats int64 [8]: the labels
+ *   first (with rings = 0 and max_passes = 0 they are the plain rule's), then nodes, offsets and the levelled raster, everything staying
+ *   on the device.  It equals the composition of the separate calls byte for byte; level_stats holds the level call's statistics
+ *   with [6] = n_clamped.  With level_passes = 0 it equals sfmba_mesh_texture_smooth byte for byte in atlas, uv, view, score, n_textured
+ *   and stats.
+ *
+ *   OUT OF SCOPE: per-view gain or gamma estimation (the offsets are additive and local); Poisson blending of patch interiors; colour
+ *   statistics sampled along edges rather than at vertices; chart merging.
+ *   SFMBA_ERR_INVALID_ARG (nothing written): everything the calls of the shared arguments refuse; r outside 0..2; w outside 1..256;
+ *                 passes outside 0..1024; 3 T >= 2^31; a node_of entry outside -1 .. n_nodes-1 or a row that is partly -1; a
+ *                 decreasing node_vertex; an F outside 0..65280; a g outside -65280..65280 (levelled); a view outside
+ *                 -1 .. n_images-1 (found on the device, before anything is written); a NULL output, or a NULL input array with a
+ *                 positive count.
+ *   Host pointers in and out, synchronous, deterministic.  SFMBA_ABI_VERSION stays 6: adding symbols is backward compatible.
+ */
+SFMBA_API int sfmba_mesh_colour_nodes(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, int64_t n_triangles,
+                const int32_t* tri /*[n_triangles][3]*/, int n_images, const int64_t* img_ptr, const unsigned char* pixels,
+                const int32_t* width, const int32_t* height, int channels, const float* K /*[9]*/, const float* P /*[n_images][12]*/,
+                const int32_t* view /*[n_triangles], each -1 or an image*/, int sample_radius /*0..2*/, int64_t* n_nodes,
+                int32_t* node_vertex /*[3 n_triangles]*/, int32_t* node_view /*[3 n_triangles]*/, int32_t* node_of /*[n_triangles][3]*/,
+                unsigned char* seen /*[3 n_triangles]*/, int32_t* F /*[3 n_triangles][3]*/);
+SFMBA_API int sfmba_mesh_colour_level(int device, int64_t n_nodes, const int32_t* node_vertex /*[n_nodes]*/, const unsigned char* seen /*[n_nodes]*/,
+                const int32_t* F /*[n_nodes][3]*/, int64_t n_triangles, const int32_t* node_of /*[n_triangles][3]*/,
+                int seam_weight /*1..256*/, int passes /*0..1024*/, int32_t* g /*[n_nodes][3]*/, int64_t* stats /*[8]*/);
+SFMBA_API int sfmba_mesh_texture_levelled(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, const unsigned char* bgr /*or NULL*/,
+                int64_t n_triangles, const int32_t* tri /*[n_triangles][3]*/, int n_images, const int64_t* img_ptr,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels, const float* K /*[9]*/,
+                const float* P /*[n_images][12]*/, int patch /*S, 3..64*/, int blocks_per_row /*B >= 1*/,
+                const int32_t* view /*[n_triangles], each -1 or an image*/, const int32_t* node_of /*[n_triangles][3]*/,
+                const int32_t* g /*[n_nodes][3]*/, int64_t n_nodes, unsigned char* atlas /*[H][W][3] BGR*/,
+                float* uv /*[n_triangles][3][2]*/, int64_t* n_textured, int64_t* n_clamped);
+SFMBA_API int sfmba_mesh_texture_adjust(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, const unsigned char* bgr /*or NULL*/,
+                int64_t n_triangles, const int32_t* tri /*[n_triangles][3]*/, int n_images, const int64_t* img_ptr,
+                const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels, const float* K /*[9]*/,
+                const float* P /*[n_images][12]*/, const float* const* depth /*[n_images], each NULL or [h][w]*/, float occl_tol,
+                int64_t min_area, int patch /*S, 3..64*/, int blocks_per_row /*B >= 1*/, int n_candidates /*1..8*/, int rings /*0..8*/,
+                int penalty /*0..65535*/, int max_passes /*0..10000*/, unsigned char* atlas /*[H][W][3] BGR*/,
+                float* uv /*[n_triangles][3][2]*/, int32_t* view /*[n_triangles]*/, int64_t* score /*[n_triangles] or NULL*/,
+                int64_t* n_textured, int64_t* stats /*[8]*/, int sample_radius /*0..2*/, int seam_weight /*1..256*/,
+                int level_passes /*0..1024*/, int64_t* level_stats /*[8]*/);
 
 /* ---- matching by optical flow: pyramidal Lucas-Kanade and the snap to key points (SfMFeatureMatching::createFlowMatchMatrix) -----
  * The reference's legacy tree matched video-like input without descriptors (legacy/SfMToyLib_Old/OFFeatureMatcher.cpp): it tracked

@@ -44,6 +44,7 @@ SYMBOLS = [
     "sfmba_mesh_components", "sfmba_mesh_filter", "sfmba_mesh_smooth", "sfmba_mesh_clean",
     "sfmba_mesh_texture_size", "sfmba_mesh_texture",
     "sfmba_mesh_view_candidates", "sfmba_mesh_adjacency", "sfmba_mesh_view_smooth", "sfmba_mesh_texture_from_views", "sfmba_mesh_texture_smooth",
+    "sfmba_mesh_colour_nodes", "sfmba_mesh_colour_level", "sfmba_mesh_texture_levelled", "sfmba_mesh_texture_adjust",
     "sfmba_depth_cost_volume", "sfmba_sgm_aggregate", "sfmba_depth_sweep_sgm",
 ]
 
@@ -959,7 +960,8 @@ def mesh_texture_size(n_triangles, patch=6, blocks_per_row=1):
 
 def mesh_texture(xyz, bgr, tri, images, K, P, depth_maps, occl_tol, min_area=0, patch=6, blocks_per_row=None, want_score=True, device=0):
     """sfmba_mesh_texture: a view per triangle and a texture atlas with one fixed-size patch per triangle (the contract is in
-    include/sfmba.h; NO COLOUR ADJUSTMENT ACROSS VIEWS, NO SMOOTHING OF THE VIEW LABELS, NO CHART MERGING).
+    include/sfmba.h; NO COLOUR ADJUSTMENT ACROSS VIEWS unless asked for (off by default), see mesh_texture_adjust, NO SMOOTHING OF THE VIEW
+    LABELS, NO CHART MERGING).
 
     The mesh as mesh_clean takes it; images, K, P, depth_maps as tsdf_integrate takes them (images are required; a map may be None).
     blocks_per_row None: ceil(sqrt(n_blocks)), at least 1.  Returns a dict: atlas uint8 [H, W, 3] (BGR), uv float32 [m, 3, 2] in atlas
@@ -1075,6 +1077,96 @@ def mesh_texture_smooth(xyz, bgr, tri, images, K, P, depth_maps, occl_tol, min_a
                                            _p(score, lp) if want_score else None, C.byref(n_textured), _p(stats, lp)))
     return {"atlas": atlas, "uv": uv[:nt].copy(), "view": view[:nt].copy(), "score": score[:nt].copy() if want_score else None,
             "n_textured": int(n_textured.value), "stats": stats}
+
+
+COLOUR_STATS = ("nodes", "blind", "seam_vertices", "spread_before", "spread_after", "max_offset", "n_clamped", "n_passes")    # stats[0..7]
+
+
+def mesh_colour_nodes(xyz, tri, images, K, P, view, sample_radius=1, device=0):
+    """sfmba_mesh_colour_nodes: a node per distinct (vertex, view) of the contributing triangles and its colour in 1/256 grey level (the
+    contract is in include/sfmba.h, "levelling the colours across seams").  Returns a dict: n_nodes, node_vertex int32 [n], node_view
+    int32 [n], node_of int32 [m, 3], seen uint8 [n], F int32 [n, 3]."""
+    nv, xyz, _, tri = _clean_mesh(xyz, None, tri)
+    nt = len(tri)
+    view = np.ascontiguousarray(view, dtype=np.int32).reshape(-1)
+    if len(view) != nt:
+        raise ValueError("one view per triangle")
+    views, keep = _tsdf_views(images, K, P, [None] * len(images))
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+    cap = max(3 * nt, 1)
+    node_vertex, node_view, node_of = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros((max(nt, 1), 3), np.int32)
+    seen, F = np.zeros(cap, np.uint8), np.zeros((cap, 3), np.int32)
+    n = C.c_int64(0)
+    _check(lib().sfmba_mesh_colour_nodes(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), C.c_int64(nt), _opt(tri, _ip), *views[:8], _opt(view, _ip),
+                                         C.c_int(sample_radius), C.byref(n), _p(node_vertex, _ip), _p(node_view, _ip), _p(node_of, _ip), _p(seen, bp),
+                                         _p(F, _ip)))
+    n = int(n.value)
+    return {"n_nodes": n, "node_vertex": node_vertex[:n].copy(), "node_view": node_view[:n].copy(), "node_of": node_of[:nt].copy(),
+            "seen": seen[:n].copy(), "F": F[:n].copy()}
+
+
+def mesh_colour_level(node_vertex, seen, F, node_of, seam_weight=16, passes=16, device=0):
+    """sfmba_mesh_colour_level: the additive offset of every node after `passes` integer Jacobi passes (the contract is in
+    include/sfmba.h).  Returns (g int32 [n, 3] in 1/256 grey level, stats int64 [8], named by COLOUR_STATS)."""
+    node_vertex = np.ascontiguousarray(node_vertex, dtype=np.int32).reshape(-1)
+    seen = np.ascontiguousarray(seen, dtype=np.uint8).reshape(-1)
+    F = np.ascontiguousarray(F, dtype=np.int32).reshape(-1, 3)
+    node_of = np.ascontiguousarray(node_of, dtype=np.int32).reshape(-1, 3)
+    n = len(node_vertex)
+    if len(seen) != n or len(F) != n:
+        raise ValueError("node_vertex [n], seen [n] and F [n, 3]")
+    g, stats = np.zeros((max(n, 1), 3), np.int32), np.zeros(8, np.int64)
+    bp, lp = C.POINTER(C.c_ubyte), C.POINTER(C.c_int64)
+    _check(lib().sfmba_mesh_colour_level(C.c_int(device), C.c_int64(n), _opt(node_vertex, _ip), _opt(seen, bp), _opt(F, _ip), C.c_int64(len(node_of)),
+                                         _opt(node_of, _ip), C.c_int(seam_weight), C.c_int(passes), _p(g, _ip), _p(stats, lp)))
+    return g[:n].copy(), stats
+
+
+def mesh_texture_levelled(xyz, bgr, tri, images, K, P, view, node_of, g, patch=6, blocks_per_row=None, device=0):
+    """sfmba_mesh_texture_levelled: mesh_texture_from_views with the offsets g [n, 3] of the nodes node_of [m, 3] blended into every
+    sampled texel (the contract is in include/sfmba.h).  Returns a dict: atlas, uv, n_textured, n_clamped."""
+    nv, xyz, bgr, tri = _clean_mesh(xyz, bgr, tri)
+    nt = len(tri)
+    if blocks_per_row is None:
+        blocks_per_row = _default_blocks_per_row(nt)
+    view = np.ascontiguousarray(view, dtype=np.int32).reshape(-1)
+    node_of = np.ascontiguousarray(node_of, dtype=np.int32).reshape(-1, 3)
+    g = np.ascontiguousarray(g, dtype=np.int32).reshape(-1, 3)
+    if len(view) != nt or len(node_of) != nt:
+        raise ValueError("one view and one row of nodes per triangle")
+    views, keep = _tsdf_views(images, K, P, [None] * len(images))
+    W, H = mesh_texture_size(nt, patch, blocks_per_row)
+    fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+    atlas, uv = np.zeros((H, W, 3), np.uint8), np.zeros((max(nt, 1), 3, 2), np.float32)
+    n_textured, n_clamped = C.c_int64(0), C.c_int64(0)
+    _check(lib().sfmba_mesh_texture_levelled(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), _opt(bgr, bp), C.c_int64(nt), _opt(tri, _ip), *views[:8],
+                                             C.c_int(patch), C.c_int(blocks_per_row), _opt(view, _ip), _opt(node_of, _ip), _opt(g, _ip), C.c_int64(len(g)),
+                                             _p(atlas, bp), _p(uv, fp), C.byref(n_textured), C.byref(n_clamped)))
+    return {"atlas": atlas, "uv": uv[:nt].copy(), "n_textured": int(n_textured.value), "n_clamped": int(n_clamped.value)}
+
+
+def mesh_texture_adjust(xyz, bgr, tri, images, K, P, depth_maps, occl_tol, min_area=0, patch=6, blocks_per_row=None, n_candidates=4, rings=4,
+                        penalty=256, max_passes=100, sample_radius=1, seam_weight=16, level_passes=16, want_score=True, device=0):
+    """sfmba_mesh_texture_adjust: mesh_texture_smooth followed by the seam levelling -- nodes, offsets and the levelled raster in one call,
+    everything staying on the device (the contract is in include/sfmba.h).  The defaults 1 / 16 / 16 are first choices that nobody has
+    tuned.  Returns mesh_texture_smooth's dict and level_stats int64 [8] (named by COLOUR_STATS)."""
+    nv, xyz, bgr, tri = _clean_mesh(xyz, bgr, tri)
+    nt = len(tri)
+    if blocks_per_row is None:
+        blocks_per_row = _default_blocks_per_row(nt)
+    views, keep = _tsdf_views(images, K, P, depth_maps)
+    W, H = mesh_texture_size(nt, patch, blocks_per_row)
+    fp, bp, lp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte), C.POINTER(C.c_int64)
+    atlas, uv = np.zeros((H, W, 3), np.uint8), np.zeros((max(nt, 1), 3, 2), np.float32)
+    view, score, stats, level_stats = np.zeros(max(nt, 1), np.int32), np.zeros(max(nt, 1), np.int64), np.zeros(8, np.int64), np.zeros(8, np.int64)
+    n_textured = C.c_int64(0)
+    _check(lib().sfmba_mesh_texture_adjust(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), _opt(bgr, bp), C.c_int64(nt), _opt(tri, _ip), *views,
+                                           C.c_float(occl_tol), C.c_int64(min_area), C.c_int(patch), C.c_int(blocks_per_row), C.c_int(n_candidates),
+                                           C.c_int(rings), C.c_int(penalty), C.c_int(max_passes), _p(atlas, bp), _p(uv, fp), _p(view, _ip),
+                                           _p(score, lp) if want_score else None, C.byref(n_textured), _p(stats, lp), C.c_int(sample_radius),
+                                           C.c_int(seam_weight), C.c_int(level_passes), _p(level_stats, lp)))
+    return {"atlas": atlas, "uv": uv[:nt].copy(), "view": view[:nt].copy(), "score": score[:nt].copy() if want_score else None,
+            "n_textured": int(n_textured.value), "stats": stats, "level_stats": level_stats}
 
 
 class _ImageInfo(C.Structure):

@@ -19,6 +19,7 @@
 #include "mesh_clean.h"
 #include "mesh_clean_math.h"
 #include "mesh_math.h"
+#include "mesh_colour.h"
 #include "mesh_labels.h"
 #include "mesh_texture.h"
 #include "texture_math.h"
@@ -358,6 +359,28 @@ int label_check_lists(const char* who, int64_t nt, int n_images, int K, const in
             const bool ordered = v < 0 ? s == 0 : (s > 0 && s < LABEL_SCORE_LIMIT && (k == 0 || (cand_view[t * K + k - 1] >= 0 && cand_score[t * K + k - 1] >= s)));
             if (!ordered) return fail(SFMBA_ERR_INVALID_ARG, w + ": a row is not a list of sfmba_mesh_view_candidates (scores in 1 .. 2^37-1, descending, then -1 and 0)");
         }
+    }
+    return 0;
+}
+// ---- what the levelling calls refuse ---------------------------------------------------------------------------------------------
+int colour_check_params(const char* who, int sample_radius, int seam_weight, int passes) {
+    const std::string w(who);
+    if (sample_radius < 0 || sample_radius > COLOUR_MAX_RADIUS) return fail(SFMBA_ERR_INVALID_ARG, w + ": sample_radius must be in 0..2");
+    if (seam_weight < 1 || seam_weight > COLOUR_MAX_WEIGHT) return fail(SFMBA_ERR_INVALID_ARG, w + ": seam_weight must be in 1..256");
+    if (passes < 0 || passes > COLOUR_MAX_PASSES) return fail(SFMBA_ERR_INVALID_ARG, w + ": passes must be in 0..1024");
+    return 0;
+}
+// every row of node_of is -1 -1 -1 or three nodes in 0 .. n_nodes-1
+int colour_check_rows(const char* who, int64_t nt, const int32_t* node_of, int64_t n_nodes) {
+    const std::string w(who);
+    for (int64_t t = 0; t < nt; ++t) {
+        int none = 0;
+        for (int q = 0; q < 3; ++q) {
+            const int32_t n = node_of[3 * t + q];
+            if (n < -1 || n >= n_nodes) return fail(SFMBA_ERR_INVALID_ARG, w + ": a node_of entry lies outside -1 .. n_nodes-1");
+            none += n < 0;
+        }
+        if (none != 0 && none != 3) return fail(SFMBA_ERR_INVALID_ARG, w + ": a node_of row is partly -1");
     }
     return 0;
 }
@@ -1084,6 +1107,104 @@ int sfmba_mesh_texture_smooth(int device, int64_t n_vertices, const float* xyz, 
         label_timing_line("mesh_texture_smooth", lt, (long long)n_triangles);
     }
     return texture_result(rc, "mesh_texture_smooth");
+}
+// ---- levelling the colours across seams (SfM::textureMesh with TextureParams::levelPasses) ----------------------------------------------
+int sfmba_mesh_colour_nodes(int device, int64_t n_vertices, const float* xyz, int64_t n_triangles, const int32_t* tri, int n_images,
+                            const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height, int channels,
+                            const float* K, const float* P, const int32_t* view, int sample_radius, int64_t* n_nodes, int32_t* node_vertex,
+                            int32_t* node_view, int32_t* node_of, unsigned char* seen, int32_t* F) {
+    if (const int rc = clean_check_mesh("mesh_colour_nodes", n_vertices, xyz, true, n_triangles, tri)) return rc;
+    if (!n_nodes || (n_triangles > 0 && (!view || !node_vertex || !node_view || !node_of || !seen || !F))) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (const int rc = depth_check_images("mesh_colour_nodes", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    if (const int rc = label_check_count("mesh_colour_nodes", n_triangles)) return rc;
+    if (const int rc = colour_check_params("mesh_colour_nodes", sample_radius, 1, 0)) return rc;
+    const TexMesh m{ (int)n_vertices, (int)n_triangles, xyz, nullptr, tri };
+    const TexViews views{ n_images, img_ptr, pixels, width, height, channels, K, P, nullptr };
+    CallKit ck;
+    if (const int rc = ck.open(device)) return rc;
+    const int rc = mesh_colour_nodes(ck.kit.stream, device, m, views, view, sample_radius, n_nodes, node_vertex, node_view, node_of, seen, F);
+    return texture_result(rc, "mesh_colour_nodes");
+}
+int sfmba_mesh_colour_level(int device, int64_t n_nodes, const int32_t* node_vertex, const unsigned char* seen, const int32_t* F, int64_t n_triangles,
+                            const int32_t* node_of, int seam_weight, int passes, int32_t* g, int64_t* stats) {
+    if (const int rc = label_check_count("mesh_colour_level", n_triangles)) return rc;
+    if (n_nodes < 0 || n_nodes > (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "mesh_colour_level: n_nodes must lie in 0 .. 2^31 - 1");
+    if (!stats || (n_nodes > 0 && (!node_vertex || !seen || !F || !g)) || (n_triangles > 0 && !node_of)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (const int rc = colour_check_params("mesh_colour_level", 0, seam_weight, passes)) return rc;
+    if (const int rc = colour_check_rows("mesh_colour_level", n_triangles, node_of, n_nodes)) return rc;
+    for (int64_t n = 0; n < n_nodes; ++n) {
+        if (n > 0 && node_vertex[n] < node_vertex[n - 1]) return fail(SFMBA_ERR_INVALID_ARG, "mesh_colour_level: node_vertex decreases");
+        for (int c = 0; c < 3; ++c)
+            if (F[3 * n + c] < 0 || F[3 * n + c] > COLOUR_F_MAX) return fail(SFMBA_ERR_INVALID_ARG, "mesh_colour_level: an F lies outside 0..65280");
+    }
+    CallKit ck;
+    if (const int rc = ck.open(device)) return rc;
+    const int rc = mesh_colour_level(ck.kit.stream, device, (int)n_nodes, node_vertex, seen, F, (int)n_triangles, node_of, seam_weight, passes, g, stats);
+    return unit_result(rc, "mesh_colour_level");
+}
+int sfmba_mesh_texture_levelled(int device, int64_t n_vertices, const float* xyz, const unsigned char* bgr, int64_t n_triangles, const int32_t* tri,
+                                int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                                int channels, const float* K, const float* P, int patch, int blocks_per_row, const int32_t* view, const int32_t* node_of,
+                                const int32_t* g, int64_t n_nodes, unsigned char* atlas, float* uv, int64_t* n_textured, int64_t* n_clamped) {
+    if (const int rc = clean_check_mesh("mesh_texture_levelled", n_vertices, xyz, true, n_triangles, tri)) return rc;
+    if (n_nodes < 0 || n_nodes > (int64_t)INT_MAX) return fail(SFMBA_ERR_INVALID_ARG, "mesh_texture_levelled: n_nodes must lie in 0 .. 2^31 - 1");
+    if (!atlas || !uv || !n_textured || !n_clamped || (n_triangles > 0 && (!view || !node_of)) || (n_nodes > 0 && !g)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (const int rc = depth_check_images("mesh_texture_levelled", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    long long W, H;
+    if (const int rc = texture_check_layout("mesh_texture_levelled", n_triangles, patch, blocks_per_row, W, H)) return rc;
+    if (const int rc = label_check_count("mesh_texture_levelled", n_triangles)) return rc;
+    if (const int rc = colour_check_rows("mesh_texture_levelled", n_triangles, node_of, n_nodes)) return rc;
+    for (int64_t i = 0; i < 3 * n_nodes; ++i)
+        if (g[i] < -COLOUR_F_MAX || g[i] > COLOUR_F_MAX) return fail(SFMBA_ERR_INVALID_ARG, "mesh_texture_levelled: a g lies outside -65280..65280");
+    const std::vector<const float*> no_maps((size_t)std::max(n_images, 1), nullptr);       // the labels are given: nothing is tested
+    const TexMesh m{ (int)n_vertices, (int)n_triangles, xyz, bgr, tri };
+    const TexViews views{ n_images, img_ptr, pixels, width, height, channels, K, P, no_maps.data() };
+    const TexParams prm{ 0.0f, 0, patch, blocks_per_row, (int)W, (int)H };
+    const TexOut out{ atlas, uv, nullptr, nullptr, n_textured };
+    const int32_t none = -1;
+    const TexLabels labels{ n_triangles > 0 ? view : &none, 0, 0, 0, 0, nullptr, nullptr };
+    const int32_t no_row[3] = { -1, -1, -1 };
+    const TexLevel level{ n_triangles > 0 ? node_of : no_row, g, (int)n_nodes, 0, 0, 0, nullptr, n_clamped, nullptr };
+    TimedCall<TEX_T_COUNT> c("SFMBA_MESH_TEXTURE_TIMING");
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_texture(c.kit.stream, device, m, views, prm, out, c.tm(), &labels, &level);
+    return texture_result(rc, "mesh_texture_levelled");
+}
+int sfmba_mesh_texture_adjust(int device, int64_t n_vertices, const float* xyz, const unsigned char* bgr, int64_t n_triangles, const int32_t* tri,
+                              int n_images, const int64_t* img_ptr, const unsigned char* pixels, const int32_t* width, const int32_t* height,
+                              int channels, const float* K, const float* P, const float* const* depth, float occl_tol, int64_t min_area, int patch,
+                              int blocks_per_row, int n_candidates, int rings, int penalty, int max_passes, unsigned char* atlas, float* uv,
+                              int32_t* view, int64_t* score, int64_t* n_textured, int64_t* stats, int sample_radius, int seam_weight, int level_passes,
+                              int64_t* level_stats) {
+    if (const int rc = clean_check_mesh("mesh_texture_adjust", n_vertices, xyz, true, n_triangles, tri)) return rc;
+    if (!atlas || !uv || !view || !n_textured || !stats || !level_stats || (n_images > 0 && !depth)) return fail(SFMBA_ERR_INVALID_ARG, "NULL array");
+    if (const int rc = depth_check_images("mesh_texture_adjust", n_images, img_ptr, pixels, width, height, channels, K, P)) return rc;
+    if (const int rc = texture_check_rule("mesh_texture_adjust", occl_tol, min_area)) return rc;
+    long long W, H;
+    if (const int rc = texture_check_layout("mesh_texture_adjust", n_triangles, patch, blocks_per_row, W, H)) return rc;
+    if (const int rc = label_check_count("mesh_texture_adjust", n_triangles)) return rc;
+    if (const int rc = label_check_k("mesh_texture_adjust", n_candidates)) return rc;
+    if (const int rc = label_check_params("mesh_texture_adjust", rings, penalty, max_passes)) return rc;
+    if (const int rc = colour_check_params("mesh_texture_adjust", sample_radius, seam_weight, level_passes)) return rc;
+    const TexMesh m{ (int)n_vertices, (int)n_triangles, xyz, bgr, tri };
+    const TexViews views{ n_images, img_ptr, pixels, width, height, channels, K, P, depth };
+    const TexParams prm{ occl_tol, min_area, patch, blocks_per_row, (int)W, (int)H };
+    const TexOut out{ atlas, uv, view, score, n_textured };
+    TimedCall<TEX_T_COUNT> c("SFMBA_MESH_TEXTURE_TIMING");       // (tools/texture_level_bench.py)
+    double lt[LAB_T_COUNT], ct[COL_T_COUNT];
+    const TexLabels labels{ nullptr, n_candidates, rings, penalty, max_passes, stats, c.on ? lt : nullptr };
+    const TexLevel level{ nullptr, nullptr, 0, sample_radius, seam_weight, level_passes, level_stats, nullptr, c.on ? ct : nullptr };
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_texture(c.kit.stream, device, m, views, prm, out, c.tm(), &labels, &level);
+    if (rc == 0 && c.on) {
+        std::fprintf(stderr, "[sfmba mesh_texture_adjust] upload_ms %.6f check_ms %.6f views_ms %.6f raster_ms %.6f download_ms %.6f triangles %lld\n",
+                     c.t[TEX_T_UPLOAD], c.t[TEX_T_CHECK], c.t[TEX_T_VIEWS], c.t[TEX_T_RASTER], c.t[TEX_T_DOWNLOAD], (long long)n_triangles);
+        label_timing_line("mesh_texture_adjust", lt, (long long)n_triangles);
+        std::fprintf(stderr, "[sfmba mesh_texture_adjust level] keys_ms %.6f sort_ms %.6f nodes_ms %.6f colours_ms %.6f passes_ms %.6f stats_ms %.6f nodes %lld "
+                             "passes %d\n",
+                     ct[COL_T_KEYS], ct[COL_T_SORT], ct[COL_T_NODES], ct[COL_T_COLOURS], ct[COL_T_PASSES], ct[COL_T_STATS], (long long)level_stats[0], level_passes);
+    }
+    return texture_result(rc, "mesh_texture_adjust");
 }
 // ---- pose of a new view (SfMStereoUtilities::findCameraPoseFrom2D3DMatch) -------------------------------------------
 int sfmba_pnp_ransac(int device, int n_prob, const int64_t* prob_ptr, const float* xyz, const float* uv, const float* K, int n_hyp,

@@ -59,6 +59,18 @@ struct TexLabels {
     double* timing;               // [LAB_T_COUNT] of the smoothing's phases (mesh_labels.h), or NULL
 };
 
+// the levelling of the colours across seams (mesh_colour.h), off unless a caller asks: the offsets are GIVEN (node_of_in, g_in) or come
+// from nodes, colours and passes on the call's final labels, everything staying on the device
+struct TexLevel {
+    const int32_t* node_of_in;    // [nt][3], each row -1 -1 -1 or nodes in 0 .. n_nodes-1: the offsets are given
+    const int32_t* g_in;          // [n_nodes][3] in 1/256 grey level
+    int n_nodes;
+    int radius, weight, passes;   // node_of_in == NULL: the sample radius of the node colours, the seam weight, the Jacobi passes
+    int64_t* stats;               // [COLOUR_STATS] (colour_math.h), or NULL
+    int64_t* n_clamped;           // the texels whose clamp changed a channel, or NULL
+    double* timing;               // [COL_T_COUNT] of the levelling's phases (mesh_colour.h), or NULL
+};
+
 // one view and the parameters as the kernels of mesh_texture.hip and mesh_labels.hip take them
 struct TexImage {
     double P[12];
@@ -94,6 +106,6 @@ int tex_check_indices(hipStream_t s, int nt, int nv, const int* d_tri, int* d_fl
 // Host pointers in and out; arguments already validated (see include/sfmba.h for the contract).  timing (may be NULL):
 // [TEX_T_COUNT] = HIP-event milliseconds on `s` of the phases above.
 int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v, const TexParams& p, const TexOut& out, double* timing,
-                 const TexLabels* labels = nullptr);
+                 const TexLabels* labels = nullptr, const TexLevel* level = nullptr);
 
 }  // namespace sfmba

@@ -20,17 +20,25 @@
 //                 word) and writes the corner uv in place of k_tex_views.  SMOOTHED: the same kernel writes uv alone, then the
 //                 candidates, the adjacency and the smoothing of mesh_labels.hip write the labels and the scores on the device, so
 //                 the views are projected once.  The raster is the same.
+//   levelling     (TexLevel, off unless a caller asks; the contract is "levelling the colours across seams", the stages are in
+//                 mesh_colour.hip) k_tex_raster<true> keeps the offsets of the triangle's three nodes in its LDS record, blends them
+//                 with the texel's own integer weights and adds them to the sample before the texel is rounded (colour_texel); the
+//                 texels that the clamp changed are counted: one LDS add per texel that clamps, one global add per workgroup.  The
+//                 offsets are GIVEN (sfmba_mesh_texture_levelled) or come from the nodes, colours and passes of mesh_colour.hip on the
+//                 final labels, everything staying on the device (sfmba_mesh_texture_adjust).  k_tex_raster<false> is the raster above.
 //
 // SCRATCH, for V vertices, T triangles, an atlas of A texels, n images with p pixels and m depth-map pixels: the mesh 15 V + 12 T, the
 // outputs 3 A + 36 T, the views 128 n + channels p + 4 m.
 #include "mesh_texture.h"
 #include "mesh_labels.h"
+#include "mesh_colour.h"
 #include "texture_math.h"
 #include "device_arena.h"
 
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace sfmba {
@@ -103,21 +111,30 @@ struct TexTri {
     int w, h, view;
     int colour[3][3];            // [corner][channel]
 };
+// and with the offsets of its three nodes
+struct TexTriLevel : TexTri {
+    int offset[3][3];            // [corner][channel], 1/256 grey level
+};
 
+template <bool LEVEL>
 __global__ __launch_bounds__(LANES) void k_tex_raster(TexKernelParams prm, const int* __restrict__ flag, const float* __restrict__ xyz,
                                                       const unsigned char* __restrict__ bgr, const int* __restrict__ tri,
                                                       const TexImage* __restrict__ tab, const float* __restrict__ maps,
                                                       const unsigned char* __restrict__ raw, const int* __restrict__ view,
-                                                      unsigned char* __restrict__ atlas) {
-    __shared__ TexTri s_tri[2 * TEX_GROUP_MAX_BLOCKS];
+                                                      unsigned char* __restrict__ atlas, const int* __restrict__ node_of,
+                                                      const int4* __restrict__ offsets, unsigned long long* __restrict__ n_clamped) {
+    using Record = typename std::conditional<LEVEL, TexTriLevel, TexTri>::type;
+    __shared__ Record s_tri[2 * TEX_GROUP_MAX_BLOCKS];
+    __shared__ unsigned s_clamped;
     if (flag[0]) return;
+    if (LEVEL && threadIdx.x == 0) s_clamped = 0;
     const int S = prm.S, per = (S + 1) * S;
     const long long slot0 = (long long)blockIdx.x * prm.group;
     const int n_slots = (int)min((long long)prm.group, (long long)prm.slots - slot0);
     // ---- the group's triangles, once ----
     if ((int)threadIdx.x < 2 * n_slots) {
         const long long t = 2 * slot0 + threadIdx.x;
-        TexTri& R = s_tri[threadIdx.x];
+        Record& R = s_tri[threadIdx.x];
         R.view = -1;
         if (t < prm.nt) {
             const int idx[3] = { tri[3 * (size_t)t], tri[3 * (size_t)t + 1], tri[3 * (size_t)t + 2] };
@@ -135,6 +152,13 @@ __global__ __launch_bounds__(LANES) void k_tex_raster(TexKernelParams prm, const
                 R.w = T.w;
                 R.h = T.h;
             }
+            if constexpr (LEVEL) {
+                for (int c = 0; c < 3; ++c) {
+                    const int n = node_of[3 * (size_t)t + c];
+                    const int4 g = n >= 0 ? offsets[n] : make_int4(0, 0, 0, 0);
+                    R.offset[c][0] = g.x; R.offset[c][1] = g.y; R.offset[c][2] = g.z;
+                }
+            }
         }
     }
     __syncthreads();
@@ -148,7 +172,7 @@ __global__ __launch_bounds__(LANES) void k_tex_raster(TexKernelParams prm, const
         const int half = tex_half_of(S, x, y, i, j);
         unsigned char out[3] = { 0, 0, 0 };
         if (2 * slot + half < prm.nt) {
-            const TexTri& R = s_tri[2 * blk + half];
+            const Record& R = s_tri[2 * blk + half];
             bool sampled = false;
             if (R.view >= 0) {
                 const TexView V{ R.P, nullptr, R.pixels, R.w, R.h };
@@ -157,7 +181,14 @@ __global__ __launch_bounds__(LANES) void k_tex_raster(TexKernelParams prm, const
                 tex_point(S, i, j, R.A, R.B, R.C, P3);
                 if (tex_texel_coord(prm.k4, V, P3, q, u, v, su, sv)) {
                     sampled = true;
-                    if (prm.channels == 3) {
+                    if constexpr (LEVEL) {
+                        bool clamped = false;
+                        for (int ch = 0; ch < 3; ++ch) {
+                            const int s12 = tex_sample12(V, prm.channels, ch, su, sv);
+                            out[ch] = colour_texel(S, s12, colour_blend(S, i, j, R.offset[0][ch], R.offset[1][ch], R.offset[2][ch]), clamped);
+                        }
+                        if (clamped) atomicAdd(&s_clamped, 1u);
+                    } else if (prm.channels == 3) {
                         for (int ch = 0; ch < 3; ++ch) out[ch] = tex_texel(tex_sample12(V, 3, ch, su, sv));
                     } else {
                         out[0] = out[1] = out[2] = tex_texel(tex_sample12(V, 1, 0, su, sv));
@@ -171,6 +202,10 @@ __global__ __launch_bounds__(LANES) void k_tex_raster(TexKernelParams prm, const
         dst[0] = out[0];
         dst[1] = out[1];
         dst[2] = out[2];
+    }
+    if constexpr (LEVEL) {
+        __syncthreads();
+        if (threadIdx.x == 0 && s_clamped) atomicAdd(n_clamped, (unsigned long long)s_clamped);
     }
 }
 
@@ -210,7 +245,7 @@ int tex_check_indices(hipStream_t s, int nt, int nv, const int* d_tri, int* d_fl
 }
 
 int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v, const TexParams& p, const TexOut& out, double* timing,
-                 const TexLabels* labels) {
+                 const TexLabels* labels, const TexLevel* level) {
     if (timing) for (int i = 0; i < TEX_T_COUNT; ++i) timing[i] = 0.0;
     DeviceArena scratch(device), raw(device);                    // raw: the label stage's temporaries, not zeroed (mesh_labels.h)
     PhaseTimer tm{ s, timing != nullptr, {}, {} };
@@ -219,6 +254,10 @@ int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v,
     int64_t st[LABEL_STATS] = { 0 };
     PhaseTimer ltm{ s, smooth && labels->timing != nullptr, {}, {} };
     if (ltm.on) for (int i = 0; i < LAB_T_COUNT; ++i) labels->timing[i] = 0.0;
+    const bool offsets_given = level && level->node_of_in;
+    int64_t cst[COLOUR_STATS] = { 0 };
+    PhaseTimer ctm{ s, level && level->timing != nullptr, {}, {} };
+    if (ctm.on) for (int i = 0; i < COL_T_COUNT; ++i) level->timing[i] = 0.0;
 
     // the view table
     std::vector<TexImage> tab;
@@ -241,8 +280,28 @@ int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v,
     UNIT_ALLOC(scratch, d_score, long long, NT);
     UNIT_ALLOC(scratch, d_uv, float, NT * 6);
     UNIT_ALLOC(scratch, d_atlas, unsigned char, texels * 3);
+    // the levelling: the node of every corner, the offset of every node, the count of the texels that clamp
+    const int* d_node_of = nullptr;
+    const int4* d_g = nullptr;
+    unsigned long long* d_clamped = nullptr;
+    std::vector<int4> g_rec;
+    if (level) UNIT_ALLOC(scratch, d_clamped, unsigned long long, 1);       // zeroed
+    if (offsets_given) {
+        int* node_of;
+        int4* g;
+        UNIT_ALLOC(scratch, node_of, int, NT * 3);
+        UNIT_ALLOC(scratch, g, int4, (size_t)level->n_nodes);
+        g_rec.resize((size_t)level->n_nodes);
+        for (size_t n = 0; n < g_rec.size(); ++n) g_rec[n] = make_int4(level->g_in[3 * n], level->g_in[3 * n + 1], level->g_in[3 * n + 2], 1);
+        d_node_of = node_of;
+        d_g = g;
+    }
 
     tm.begin(TEX_T_UPLOAD);
+    if (offsets_given) {
+        TEX_COPY(const_cast<int*>(d_node_of), level->node_of_in, sizeof(int) * NT * 3, hipMemcpyHostToDevice);
+        TEX_COPY(const_cast<int4*>(d_g), g_rec.data(), sizeof(int4) * g_rec.size(), hipMemcpyHostToDevice);
+    }
     TEX_COPY(d_tri, m.tri, sizeof(int) * NT * 3, hipMemcpyHostToDevice);
     TEX_COPY(d_xyz, m.xyz, sizeof(float) * NV * 3, hipMemcpyHostToDevice);
     if (d_bgr) TEX_COPY(d_bgr, m.bgr, NV * 3, hipMemcpyHostToDevice);
@@ -297,15 +356,33 @@ int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v,
         if (int rc = labels_adjacency_dev(s, raw, m.nt, d_tri, d_adj, d_counts, &ltm)) return rc;
         if (int rc = labels_smooth_dev(s, scratch, raw, m.nt, lp, d_cv, d_cs, d_adj, d_view, d_score, st, &ltm)) return rc;
     }
+    if (level && !offsets_given) {
+        // nodes, colours and passes on the final labels (the smoothing has waited for the stream and the index flag has been read)
+        ColourNodes nodes;
+        int n_nodes = 0;
+        if (int rc = colour_nodes_dev(s, raw, prm, d_xyz, d_tri, d_tab, d_raw, d_view, level->radius, nodes, n_nodes, &ctm)) return rc;
+        if (int rc = colour_level_dev(s, raw, n_nodes, nodes.node_vertex, nodes.F, nodes.node_of, nodes.entry, nodes.run, level->weight, level->passes, &d_g, cst,
+                                      &ctm))
+            return rc;
+        d_node_of = nodes.node_of;
+    }
     tm.next(TEX_T_RASTER);
-    hipLaunchKernelGGL(k_tex_raster, dim3((unsigned)((prm.slots + prm.group - 1) / prm.group)), dim3(LANES), 0, s, prm, d_flag, d_xyz, d_bgr, d_tri, d_tab,
-                       d_maps, d_raw, d_view, d_atlas);
+    const dim3 raster_grid((unsigned)((prm.slots + prm.group - 1) / prm.group));
+    if (level && m.nt > 0) {
+        hipLaunchKernelGGL(k_tex_raster<true>, raster_grid, dim3(LANES), 0, s, prm, d_flag, d_xyz, d_bgr, d_tri, d_tab, d_maps, d_raw, d_view, d_atlas, d_node_of,
+                           d_g, d_clamped);
+    } else {
+        hipLaunchKernelGGL(k_tex_raster<false>, raster_grid, dim3(LANES), 0, s, prm, d_flag, d_xyz, d_bgr, d_tri, d_tab, d_maps, d_raw, d_view, d_atlas,
+                           (const int*)nullptr, (const int4*)nullptr, (unsigned long long*)nullptr);
+    }
     UNIT_TRY(hipGetLastError());
     tm.end();
 
     int flag[2] = { 0, 0 };
+    unsigned long long clamped = 0;
     UNIT_TRY(hipMemcpyAsync(flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s));
-    UNIT_TRY(hipStreamSynchronize(s));                           // also: `tab` is spent
+    if (level) UNIT_TRY(hipMemcpyAsync(&clamped, d_clamped, sizeof(clamped), hipMemcpyDeviceToHost, s));
+    UNIT_TRY(hipStreamSynchronize(s));                           // also: `tab` and `g_rec` are spent
     if (flag[1]) return TEX_ERR_VIEW;
     if (flag[0]) return TEX_ERR_INDEX;
 
@@ -321,6 +398,12 @@ int mesh_texture(hipStream_t s, int device, const TexMesh& m, const TexViews& v,
     for (size_t t = 0; t < NT; ++t) textured += final_view[t] >= 0;
     *out.n_textured = textured;
     if (smooth) for (int i = 0; i < LABEL_STATS; ++i) labels->stats[i] = st[i];
+    if (level) {
+        cst[COLOUR_S_CLAMPED] = (int64_t)clamped;
+        if (level->stats) for (int i = 0; i < COLOUR_STATS; ++i) level->stats[i] = cst[i];
+        if (level->n_clamped) *level->n_clamped = (int64_t)clamped;
+        if (ctm.on) ctm.collect(level->timing);
+    }
     if (timing) tm.collect(timing);
     if (ltm.on) ltm.collect(labels->timing);
     return 0;

@@ -831,6 +831,13 @@ ErrorCode SfM::textureMesh(const TextureParams& params) {
                           " more pairs have one side without a view); energy " + std::to_string(st[0]) + " -> " + std::to_string(st[1]) + "; " +
                           std::to_string(st[6]) + " moves in " + std::to_string(st[7]) + " passes");
     }
+    if (mTexturedMesh.levelled) {
+        const long long* st = mTexturedMesh.levelStats;
+        say(LOG_INFO, "levelled colours: " + std::to_string(st[0]) + " nodes (" + std::to_string(st[1]) + " blind), " + std::to_string(st[2]) +
+                          " seam vertices; summed spread at the seams " + std::to_string(st[3]) + " -> " + std::to_string(st[4]) +
+                          " (1/256 grey level) in " + std::to_string(st[7]) + " passes; largest offset " + std::to_string(st[5]) + "; " +
+                          std::to_string(st[6]) + " texels clamped");
+    }
     if (timing)
         std::fprintf(stderr, "[sfmba sfm mesh_texture] texture_ms %.3f triangles %lld textured %lld width %d height %d\n", ms[0],
                      (long long)(mTexturedMesh.triangles.size() / 3), mTexturedMesh.textured, mTexturedMesh.atlas.cols, mTexturedMesh.atlas.rows);

@@ -94,7 +94,8 @@
 //                 triangle no view sees keeps its blended vertex colours.  THE HOST RULES: patch S = 6; blocksPerRow 0 means
 //                 B = ceil(sqrt(ceil(triangles / 2))), at least 1 (a square atlas); occl_tol = occlTolVoxels * the grid's voxel
 //                 (float), occlTolVoxels default 2; min_area = round(2 * 256 * minAreaPx), minAreaPx default 0.5.  These are first
-//                 choices that NOBODY HAS TUNED.  NO COLOUR ADJUSTMENT ACROSS VIEWS (seams where exposures differ stay visible), NO
+//                 choices that NOBODY HAS TUNED.  NO COLOUR ADJUSTMENT ACROSS VIEWS unless asked for (off by default), see
+//                 params.levelPasses below (seams where exposures differ stay visible), NO
 //                 SMOOTHING OF THE VIEW LABELS BY DEFAULT, NO CHART MERGING (every triangle costs (S + 1) S / 2 texels, however small).
 //                 The mesh, the clean mesh, the dense cloud and the depth maps are not changed.
 //                 With params.smoothRings or params.smoothPasses not 0 the labels are chosen TOGETHER, by ONE
@@ -103,6 +104,12 @@
 //                 smoothPasses passes of a Potts relaxation with the penalty smoothPenalty; the textured mesh then carries the call's
 //                 eight statistics, and an INFO line reports them.  The defaults (off; 256; 4 candidates) and sfmtoy's 4 rings, 256
 //                 and 100 passes are first choices that nobody has tuned.
+//                 With params.levelPasses not 0 the colours are LEVELLED ACROSS SEAMS, by ONE sfmba_mesh_texture_adjust call in place
+//                 of the two above (include/sfmba.h, "levelling the colours across seams"): the labels as above, then an additive
+//                 colour offset per (vertex, view) by levelPasses integer Jacobi passes with the seam weight levelSeamWeight, from
+//                 colours sampled with the radius levelSampleRadius, blended into every sampled texel; the textured mesh then
+//                 carries the call's eight statistics, and an INFO line reports them.  The defaults (off; 16; 1) and sfmtoy's 16
+//                 passes are first choices that NOBODY HAS TUNED.
 // There is no visual debugging.
 // An object holds all of a run's state (the stage times of SFMBA_SFM_TIMING included): different objects may run in different
 // threads; one object is not re-entrant.

@@ -500,11 +500,17 @@ TexturedMesh SfMDenseUtilities::textureMesh(const Mesh& mesh, const std::vector<
     out.atlas = sized ? cv::Mat((int)H, (int)W, CV_8UC3) : cv::Mat(1, 1, CV_8UC3);
     out.uv.resize((size_t)nt * 6 + 1);
     std::vector<int32_t> view((size_t)nt + 1);
-    int64_t textured = 0, stats[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    // smoothing is off by default: the call is then exactly the plain one
+    int64_t textured = 0, stats[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, levelStats[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    // smoothing and levelling are off by default: the call is then exactly the plain one
     out.smoothed = params.smoothRings != 0 || params.smoothPasses != 0;
+    out.levelled = params.levelPasses != 0;
     const unsigned char* bgr = mesh.bgr.empty() ? nullptr : mesh.bgr.data();
-    const int rc = out.smoothed
+    const int rc = out.levelled
+        ? sfmba_mesh_texture_adjust(0, nv, xyz.data(), bgr, nt, mesh.triangles.data(), (int)images.size(), f.ptr.data(), f.px.data(), f.w.data(), f.h.data(),
+                                    f.channels, f.K, f.P.data(), maps.data(), occlTol, minArea, params.patch, B, params.candidates, params.smoothRings,
+                                    params.smoothPenalty, params.smoothPasses, out.atlas.ptr<unsigned char>(0), out.uv.data(), view.data(), nullptr,
+                                    &textured, stats, params.levelSampleRadius, params.levelSeamWeight, params.levelPasses, levelStats)
+        : out.smoothed
         ? sfmba_mesh_texture_smooth(0, nv, xyz.data(), bgr, nt, mesh.triangles.data(), (int)images.size(), f.ptr.data(), f.px.data(), f.w.data(), f.h.data(),
                                     f.channels, f.K, f.P.data(), maps.data(), occlTol, minArea, params.patch, B, params.candidates, params.smoothRings,
                                     params.smoothPenalty, params.smoothPasses, out.atlas.ptr<unsigned char>(0), out.uv.data(), view.data(), nullptr,
@@ -521,7 +527,8 @@ TexturedMesh SfMDenseUtilities::textureMesh(const Mesh& mesh, const std::vector<
     out.uv.resize((size_t)nt * 6);
     out.view.assign(view.begin(), view.begin() + nt);
     out.textured = (long long)textured;
-    for (int i = 0; i < 8; ++i) out.smoothStats[i] = (long long)stats[i];
+    for (int i = 0; i < 8; ++i) out.smoothStats[i] = out.smoothed ? (long long)stats[i] : 0;
+    for (int i = 0; i < 8; ++i) out.levelStats[i] = (long long)levelStats[i];
     if (ok) *ok = true;
     return out;
 }

@@ -121,6 +121,11 @@ struct MeshCleanParams {
 // candidates best views per triangle, their scores summed over smoothRings rings of neighbours, then at most smoothPasses passes of a
 // Potts relaxation with the penalty smoothPenalty, in 1/1024 of the best view's area).  sfmtoy's --texture-smooth switches 4, 256 and
 // 100 passes on; those too are first choices that nobody has tuned.
+// LEVELLING THE COLOURS ACROSS SEAMS IS OFF BY DEFAULT: with levelPasses = 0 the call is the one above and the other two levelling fields
+// are not read.  Otherwise ONE sfmba_mesh_texture_adjust call chooses the labels as above (the plain rule with smoothRings = 0 and
+// smoothPasses = 0), gives every (vertex, view) pair an additive colour offset by levelPasses integer Jacobi passes and blends the
+// offsets into the sampled texels (include/sfmba.h, "levelling the colours across seams").  The defaults 16 and 1, and the 16 passes
+// that sfmtoy's --texture-level switches on, are first choices that NOBODY HAS TUNED.
 struct TextureParams {
     int   patch;            // S: a triangle gets S (S + 1) / 2 texels, 3..64
     int   blocksPerRow;     // B: blocks (pairs of triangles) per atlas row; 0 = ceil(sqrt(blocks)), at least 1
@@ -130,15 +135,23 @@ struct TextureParams {
     int   smoothPenalty;    // p, 0..65535: what a pair of neighbours with different views costs
     int   smoothPasses;     // 0..10000: the most relaxation passes
     int   candidates;       // K, 1..8: views a triangle may choose among
-    TextureParams() : patch(6), blocksPerRow(0), occlTolVoxels(2.0f), minAreaPx(0.5f), smoothRings(0), smoothPenalty(256), smoothPasses(0), candidates(4) {}
+    int   levelPasses;      // N, 0..1024: Jacobi passes of the seam levelling; 0 = off
+    int   levelSeamWeight;  // w, 1..256: what closing the gap at a seam counts against smoothness within a view
+    int   levelSampleRadius;  // r, 0..2: a node's colour is the mean over (2 r + 1)^2 samples about its vertex
+    TextureParams() : patch(6), blocksPerRow(0), occlTolVoxels(2.0f), minAreaPx(0.5f), smoothRings(0), smoothPenalty(256), smoothPasses(0), candidates(4),
+                      levelPasses(0), levelSeamWeight(16), levelSampleRadius(1) {}
 };
 
 // A mesh that carries the photographs: triangle t has the corners uv[6 t .. 6 t + 5] (u, v per corner, in atlas pixels, origin top-left)
 // in the atlas and took its texels from view[t] (-1: none saw it; its patch holds the blended vertex colours).  NO COLOUR ADJUSTMENT
-// ACROSS VIEWS, NO SMOOTHING OF THE VIEW LABELS unless TextureParams asks for it (off by default), NO CHART MERGING (include/sfmba.h).
+// ACROSS VIEWS unless asked for (off by default), see TextureParams::levelPasses, NO SMOOTHING OF THE VIEW LABELS unless TextureParams asks
+// for it (off by default), NO CHART MERGING (include/sfmba.h).
 // smoothed: the labels came from sfmba_mesh_texture_smooth, and smoothStats holds its eight statistics (include/sfmba.h: the energy after
 // the start and at the end; the pairs of neighbours with different views under the plain rule, after the start and at the end; the pairs
 // with one side without a view; the moves; the passes that moved something); all zero otherwise.
+// levelled: the atlas came from sfmba_mesh_texture_adjust, and levelStats holds its eight statistics (nodes; blind nodes; seam vertices; the
+// summed spread of the colours at the seam vertices before and after, in 1/256 grey level; the largest offset; the texels that clamped; the
+// passes); all zero otherwise.
 struct TexturedMesh {
     Points3f           vertices;
     std::vector<int>   triangles;  // 3 vertex indices per triangle
@@ -148,7 +161,9 @@ struct TexturedMesh {
     long long          textured;   // triangles with a view
     bool               smoothed;
     long long          smoothStats[8];
-    TexturedMesh() : textured(0), smoothed(false), smoothStats{ 0, 0, 0, 0, 0, 0, 0, 0 } {}
+    bool               levelled;
+    long long          levelStats[8];
+    TexturedMesh() : textured(0), smoothed(false), smoothStats{ 0, 0, 0, 0, 0, 0, 0, 0 }, levelled(false), levelStats{ 0, 0, 0, 0, 0, 0, 0, 0 } {}
 };
 
 class SfMDenseUtilities {
@@ -243,7 +258,7 @@ public:
 
     /**
      * A view per triangle and a texture atlas with one patch per triangle: ONE sfmba_mesh_texture call, or, when params.smoothRings or
-     * params.smoothPasses is not 0, ONE sfmba_mesh_texture_smooth call.  images, poses and depthMaps as
+     * params.smoothPasses is not 0, ONE sfmba_mesh_texture_smooth call, or, when params.levelPasses is not 0, ONE sfmba_mesh_texture_adjust call.  images, poses and depthMaps as
      * fuseDepthMaps takes them (a view without a map has no visibility test).  THE HOST RULES: B = params.blocksPerRow, or
      * ceil(sqrt(ceil(triangles / 2))) (at least 1) when that is 0; occl_tol = params.occlTolVoxels * mesh.grid.voxel (float);
      * min_area = round(2 * 256 * params.minAreaPx).

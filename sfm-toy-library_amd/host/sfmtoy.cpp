@@ -3,7 +3,7 @@
 // <prefix>_dense.ply; with --voxel on top of -D, merge that cloud and write <prefix>_dense_merged.ply; with --mesh on top of -D, mesh
 // the depth maps and write <prefix>_mesh.ply (--mesh-fill N: with the grid's holes filled by N passes first); with --mesh-clean on top of --mesh, drop the mesh's small components, smooth it and write
 // <prefix>_mesh_clean.ply; with --texture on top of --mesh, put the photographs on the mesh (the clean one with --mesh-clean) and write
-// <prefix>_textured.obj, .mtl and .png (--texture-smooth: with the views of neighbouring triangles chosen together).  The arguments are parsed here
+// <prefix>_textured.obj, .mtl and .png (--texture-smooth: with the views of neighbouring triangles chosen together; --texture-level: with the colours levelled across the seams).  The arguments are parsed here
 // (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
 #include <cctype>
 #include <cstdlib>
@@ -51,12 +51,17 @@ void usage(std::ostream& os, const char* program) {
        << "      --mesh-smooth ITERS      with --mesh-clean: smoothing iterations, 0..100 (default 10)\n"
        << "      --texture [S]            with --mesh: also choose a view per triangle, fill a texture atlas with a patch of S (S + 1) / 2 texels\n"
        << "                               per triangle (S in 3..64, default 6) and write PREFIX_textured.obj, .mtl and .png (the clean mesh\n"
-       << "                               with --mesh-clean); NO COLOUR ADJUSTMENT ACROSS VIEWS; the other files are as without it\n"
+       << "                               with --mesh-clean); NO COLOUR ADJUSTMENT ACROSS VIEWS unless --texture-level asks for it; the other\n"
+       << "                               files are as without it\n"
        << "      --texture-smooth [R,P]   with --texture: choose the views of neighbouring triangles together: every view's score summed over R\n"
        << "                               rings of neighbours (0..8) before the choice, then a Potts relaxation in which a pair of neighbours\n"
        << "                               with different views costs P (0..65535, in 1/1024 of the best view's area); default 4,256, first\n"
        << "                               choices that nobody has tuned; the other files are as without it\n"
        << "      --texture-smooth-passes N  with --texture-smooth: the most relaxation passes, 0..10000 (default 100)\n"
+       << "      --texture-level [N[,W]]  with --texture: level the colours across the seams between photographs: an additive offset per vertex\n"
+       << "                               and view by N integer Jacobi passes (1..1024) with the seam weight W (1..256); default 16,16, first\n"
+       << "                               choices that nobody has tuned; only PREFIX_textured.png changes\n"
+       << "      --texture-level-radius R with --texture-level: a vertex's colour in a view is the mean over (2 R + 1)^2 samples, 0..2 (default 1)\n"
        << "  -v, --visual-debug N         accepted and ignored: there is no visual debugging\n";
 }
 
@@ -83,11 +88,13 @@ int main(int argc, char** argv) {
     std::string directory, prefix = "output", text;
     double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0, voxel = 0.0, resolution = 256.0,
            min_component = 0.0, smooth = 10.0, fill = 0.0, fill_neighbours = 2.0, patch = 6.0, sgm_p1 = 8.0, sgm_p2 = 64.0, sgm_paths = 8.0,
-           sgm_uniqueness = 5.0, smooth_rings = 4.0, smooth_penalty = 256.0, smooth_passes = 100.0;
+           sgm_uniqueness = 5.0, smooth_rings = 4.0, smooth_penalty = 256.0, smooth_passes = 100.0, level_passes = 16.0, level_weight = 16.0,
+           level_radius = 1.0;
     FeatureType features = FEATURES_ORB;
     MatcherType matcher = MATCHER_DESCRIPTORS;
     bool have_directory = false, dense = false, merged = false, meshed = false, cleaned = false, clean_option = false, keep_largest = false,
-         filled = false, fill_option = false, textured = false, sgm = false, sgm_option = false, texture_smooth = false, smooth_option = false;
+         filled = false, fill_option = false, textured = false, sgm = false, sgm_option = false, texture_smooth = false, smooth_option = false, texture_level = false,
+         level_option = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
         const std::string arg = argv[i];
@@ -122,6 +129,24 @@ int main(int argc, char** argv) {
                 !(smooth_rings >= 0.0) || !(smooth_rings <= 8.0) || !(smooth_penalty >= 0.0) || !(smooth_penalty <= 65535.0) ||
                 smooth_rings != (double)(int)smooth_rings || smooth_penalty != (double)(int)smooth_penalty) {
                 std::cerr << argv[0] << ": --texture-smooth has a value that cannot be used\n"; usage(std::cerr, argv[0]); return 2;
+            }
+            continue;
+        }
+        if (arg == "--texture-level" || arg.compare(0, 16, "--texture-level=") == 0) {
+            // the value is optional: "--texture-level=N[,W]", or a next argument made of digits with at most one comma among them
+            texture_level = true;
+            text = arg.size() > 16 ? arg.substr(16) : "";
+            if (arg == "--texture-level" && i + 1 < argc && std::isdigit((unsigned char)argv[i + 1][0]) &&
+                std::string(argv[i + 1]).find_first_not_of("0123456789,") == std::string::npos)
+                text = argv[++i];
+            else if (arg == "--texture-level")
+                continue;
+            const size_t comma = text.find(',');
+            const bool weighted = comma != std::string::npos;
+            if (!number(text.substr(0, comma), level_passes) || (weighted && !number(text.substr(comma + 1), level_weight)) || !(level_passes >= 1.0) ||
+                !(level_passes <= 1024.0) || !(level_weight >= 1.0) || !(level_weight <= 256.0) || level_passes != (double)(int)level_passes ||
+                level_weight != (double)(int)level_weight) {
+                std::cerr << argv[0] << ": --texture-level has a value that cannot be used\n"; usage(std::cerr, argv[0]); return 2;
             }
             continue;
         }
@@ -192,6 +217,10 @@ int main(int argc, char** argv) {
             bad = !missing && (!number(text, smooth_passes) || !(smooth_passes >= 0.0) || !(smooth_passes <= 10000.0) || smooth_passes != (double)(int)smooth_passes);
             smooth_option = true;
         }
+        else if (option(argc, argv, i, "--texture-level-radius", "--texture-level-radius", text, missing)) {
+            bad = !missing && (!number(text, level_radius) || !(level_radius >= 0.0) || !(level_radius <= 2.0) || level_radius != (double)(int)level_radius);
+            level_option = true;
+        }
         else if (option(argc, argv, i, "-v", "--visual-debug", text, missing)) bad = !missing && !number(text, ignored);
         else if (arg.size() > 1 && arg[0] == '-') { std::cerr << argv[0] << ": unknown option " << arg << "\n"; usage(std::cerr, argv[0]); return 2; }
         else if (!have_directory) { directory = arg; have_directory = true; }
@@ -209,6 +238,8 @@ int main(int argc, char** argv) {
     if (textured && !meshed) { std::cerr << argv[0] << ": --texture needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
     if (texture_smooth && !textured) { std::cerr << argv[0] << ": --texture-smooth needs --texture\n"; usage(std::cerr, argv[0]); return 2; }
     if (smooth_option && !texture_smooth) { std::cerr << argv[0] << ": --texture-smooth-passes needs --texture-smooth\n"; usage(std::cerr, argv[0]); return 2; }
+    if (texture_level && !textured) { std::cerr << argv[0] << ": --texture-level needs --texture\n"; usage(std::cerr, argv[0]); return 2; }
+    if (level_option && !texture_level) { std::cerr << argv[0] << ": --texture-level-radius needs --texture-level\n"; usage(std::cerr, argv[0]); return 2; }
     if (!have_directory || directory.empty()) { std::cerr << argv[0] << ": no input directory\n"; usage(std::cerr, argv[0]); return 2; }
 
     SfM sfm((float)downscale);
@@ -255,6 +286,11 @@ int main(int argc, char** argv) {
                 texture.smoothRings = (int)smooth_rings;
                 texture.smoothPenalty = (int)smooth_penalty;
                 texture.smoothPasses = (int)smooth_passes;
+            }
+            if (texture_level) {
+                texture.levelPasses = (int)level_passes;
+                texture.levelSeamWeight = (int)level_weight;
+                texture.levelSampleRadius = (int)level_radius;
             }
             if (sfm.textureMesh(texture) != OKAY) return 1;
             if (!sfm.saveTexturedMeshToOBJ(prefix)) return 1;
