@@ -1377,6 +1377,67 @@ SFMBA_API int sfmba_mesh_clean(int device, int64_t n_vertices, const float* xyz 
                 unsigned char* bgr_out /*[vcap][3]*/, float* normal /*[vcap][3] or NULL*/, int64_t vcap, int32_t* tri_out /*[tcap][3]*/,
                 int64_t tcap, int32_t* vertex_of /*[n_vertices] or NULL*/, int64_t* n_vertices_out, int64_t* n_triangles_out);
 
+/* ---- decimating a mesh: vertex clustering with quadric placement (SfM::decimateMesh) ----------------------------------------------
+ * Marching tetrahedra emits triangles far smaller than a pixel's footprint, and everything after the mesh (the view choice, the
+ * atlas, the label smoothing, the colour levelling) pays per triangle.  This call hands those stages fewer, larger triangles: every
+ * vertex falls into a cubic cell of `cell` quanta, a cell's vertices become ONE representative, and the triangles that survive are
+ * those whose three vertices lie in three different cells (out-of-core vertex clustering, Lindstrom 2000).  The representative is
+ * either the rounded mean of the members or the minimiser of the cell's quadric (the summed squared distances to the planes of the
+ * incident triangles), which keeps the edges and corners that a mean rounds off.  THE CONTRACT IS OUR OWN AND EQUALS NOBODY'S, stated
+ * so that the device is held BIT FOR BIT to a CPU restatement (tests/decimate_oracle.py): NOTHING BUT INTEGERS IS SUMMED ACROSS
+ * VERTICES OR TRIANGLES, the few fp64 operations are EVERY ONE ROUNDED ON ITS OWN (csrc/decimate_math.h switches the compiler's
+ * contraction off), and a sum written a + b + c is ((a + b) + c).
+ *
+ *   inputs        the mesh of the cleaning calls; origin float [3] (finite) and quantum > 0 (a finite float); cell in 32..2^20, in
+ *                 quanta; placement 0 (mean) or 1 (quadric); reg in 1..2^20, read only with placement 1.
+ *   quantisation  P_a exactly as sfmba_mesh_smooth computes it, with the same refusal of a coordinate that is not finite or has
+ *                 |P_a| >= 2^25.
+ *   cell and key  c_a = floor_div(P_a, cell), r_a = P_a - c_a cell in 0..cell-1; with cell >= 32, c_a lies in [-2^20, 2^20).
+ *                 key = ((c_z + 2^20) << 42) | ((c_y + 2^20) << 21) | (c_x + 2^20).  Every vertex is a member of its cell's cluster,
+ *                 whether or not a triangle names it.
+ *   mean          for a cluster of n members Sp_a = the sum of r_a over the members (< 2^51); R_a = floor_div(2 Sp_a + n, 2 n).  A
+ *                 colour channel is the same rounded mean over the members' bytes.
+ *   quadric       (placement 1) a triangle contributes when its three indices are DISTINCT and its normal is non-zero:
+ *                 N = (P_b - P_a) x (P_c - P_a) in int64 and len = sqrt((Nx Nx + Ny Ny) + Nz Nz) as in the smooth's normals;
+ *                 u_a = (int64)floor((N_a / len) 1024.0 + 0.5), |u_a| <= 1024.  EVERY TRIANGLE HAS EQUAL WEIGHT: THE QUADRICS ARE
+ *                 NOT AREA WEIGHTED.  For each of its three vertices v, into the cluster of v, with v's own r:
+ *                 e = (u_x r_x + u_y r_y) + u_z r_z (|e| < 2^32); A_ij += u_i u_j (six entries); b_i += u_i e; n_inc += 1.
+ *                 A cluster takes the mean's R when n_inc == 0 or n_inc > 2^16 (counted in stats).  Up to that cap |A_ij| <= 2^36
+ *                 and |b_i| < 2^58.
+ *   the solve     in doubles: rho = (double)reg (double)n_inc; m_a = (double)Sp_a / (double)n; s = (double)A + rho I;
+ *                 g_a = (double)b_a + rho m_a.  Cofactors c00 = s11 s22 - s12 s12, c01 = s02 s12 - s01 s22, c02 = s01 s12 - s02 s11,
+ *                 c11 = s00 s22 - s02 s02, c12 = s01 s02 - s00 s12, c22 = s00 s11 - s01 s01; det = (s00 c00 + s01 c01) + s02 c02;
+ *                 x_0 = ((c00 g0 + c01 g1) + c02 g2) / det, x_1 and x_2 likewise from the symmetric adjugate.  If !(det > 0) or an
+ *                 x_a is not finite the cluster takes the mean's R (counted in stats); otherwise
+ *                 R_a = clamp((int64)floor(x_a + 0.5), 0, cell - 1): A REPRESENTATIVE NEVER LEAVES ITS CELL.  The regulariser pulls
+ *                 towards the members' mean with weight reg / 2^20 relative to a unit normal.
+ *   position      xyz_out_a = (float)((double)origin_a + ((double)(c_a cell + R_a) (double)quantum)).
+ *   triangles     a triangle is COLLAPSED when two of its vertices share a cluster (a repeated index is one such case).  Among the
+ *                 others with the same UNORDERED triple of clusters the lowest input index survives, whatever the orientation.
+ *                 Survivors keep their relative order and their index order (so their orientation).  A cluster is emitted iff a
+ *                 surviving triangle names it; clusters are emitted in ASCENDING KEY ORDER.
+ *   outputs       xyz_out float [vcap][3]; bgr_out uint8 [vcap][3] (not written, and may be NULL, where bgr is NULL); members int32
+ *                 [vcap] (may be NULL): a cluster's member count; tri_out int32 [tcap][3]; triangle_of int32 [tcap] (may be NULL):
+ *                 the input index of an output triangle; vertex_of int32 [n_vertices] (may be NULL): the output index of a vertex's
+ *                 cluster or -1; *n_vertices_out, *n_triangles_out; stats int64 [4] (may be NULL) = { clusters before the emit rule,
+ *                 collapsed triangles, duplicates dropped, clusters with placement 1 that took the mean }.
+ *                 SFMBA_ERR_CAPACITY if vcap < *n_vertices_out or tcap < *n_triangles_out: both totals are valid, nothing else is
+ *                 written.
+ *   SFMBA_ERR_INVALID_ARG (nothing written): what sfmba_mesh_filter and sfmba_mesh_smooth refuse about the mesh, origin, quantum,
+ *                 the capacities and the pointers (the index and coordinate checks run on the device, before anything is written);
+ *                 cell outside 32..2^20; placement outside {0, 1}; reg outside 1..2^20 when placement is 1.
+ *   NOT DONE: no edge-collapse simplification, no topology guarantee (sheets closer than a cell fuse, a few non-manifold edges
+ *   appear on a clean solid and thousands on the noisy open sheets of a reconstruction: profiles/mesh_decimate.txt), no area
+ *   weighting, no boundary-preserving quadrics.
+ *   Host pointers in and out, synchronous, deterministic.  SFMBA_ABI_VERSION stays 6: adding a symbol is backward compatible.
+ */
+SFMBA_API int sfmba_mesh_decimate(int device, int64_t n_vertices, const float* xyz /*[n_vertices][3]*/, const unsigned char* bgr /*or NULL*/,
+                int64_t n_triangles, const int32_t* tri /*[n_triangles][3]*/, const float* origin /*[3]*/, float quantum,
+                int cell /*32..2^20, in quanta*/, int placement /*0 mean, 1 quadric*/, int reg /*1..2^20; read only with placement 1*/,
+                float* xyz_out /*[vcap][3]*/, unsigned char* bgr_out /*[vcap][3]*/, int32_t* members /*[vcap] or NULL*/, int64_t vcap,
+                int32_t* tri_out /*[tcap][3]*/, int32_t* triangle_of /*[tcap] or NULL: input index of an output triangle*/, int64_t tcap,
+                int32_t* vertex_of /*[n_vertices] or NULL*/, int64_t* n_vertices_out, int64_t* n_triangles_out, int64_t* stats /*[4] or NULL*/);
+
 /* ---- texturing a mesh: a view per triangle and a texture atlas of fixed-size patches (SfM::textureMesh) ---------------------------
  * A vertex of the meshes above has one colour: the mean over all views of the pixels that fell into the two grid vertices of its
  * edge, blurred by the voxel and by views that disagree by the depth error, and no finer than the grid.  This call puts the

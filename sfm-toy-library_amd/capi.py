@@ -41,7 +41,7 @@ SYMBOLS = [
     "sfmba_depth_sweep", "sfmba_depth_fuse", "sfmba_flow_track", "sfmba_flow_match",
     "sfmba_depth_normals", "sfmba_cloud_merge", "sfmba_tsdf_integrate", "sfmba_tsdf_extract", "sfmba_tsdf_mesh",
     "sfmba_tsdf_fill", "sfmba_tsdf_mesh_fill",
-    "sfmba_mesh_components", "sfmba_mesh_filter", "sfmba_mesh_smooth", "sfmba_mesh_clean",
+    "sfmba_mesh_components", "sfmba_mesh_filter", "sfmba_mesh_smooth", "sfmba_mesh_clean", "sfmba_mesh_decimate",
     "sfmba_mesh_texture_size", "sfmba_mesh_texture",
     "sfmba_mesh_view_candidates", "sfmba_mesh_adjacency", "sfmba_mesh_view_smooth", "sfmba_mesh_texture_from_views", "sfmba_mesh_texture_smooth",
     "sfmba_mesh_colour_nodes", "sfmba_mesh_colour_level", "sfmba_mesh_texture_levelled", "sfmba_mesh_texture_adjust",
@@ -949,6 +949,39 @@ def mesh_clean(xyz, bgr, tri, origin, quantum, min_triangles=1, keep_largest=Fal
                                       C.c_int(min_triangles), C.c_int(int(keep_largest)), _p(origin, fp), C.c_float(quantum), C.c_int(iterations),
                                       C.c_float(lam), C.c_float(mu), oxyz, obgr, onrm, vcap, otri, tcap, vof, n_v, n_t)
     return _mesh_clean_call(call, nv, bgr is not None, want_normal, want_vertex_of, vcap, tcap)
+
+
+def mesh_decimate(xyz, bgr, tri, origin, quantum, cell, placement=1, reg=1024, want_members=True, want_triangle_of=True, want_vertex_of=True,
+                  want_stats=True, vcap=None, tcap=None, device=0):
+    """sfmba_mesh_decimate: vertex clustering with the mean (placement 0) or the quadric (1) placement (the contract is in
+    include/sfmba.h).
+
+    Returns a dict: xyz float32 [n, 3], bgr uint8 [n, 3] or None, members int32 [n] or None, tri int32 [m, 3], triangle_of int32 [m] or
+    None, vertex_of int32 [n_vertices] or None, stats (a list of four) or None; None where NULL is passed.  vcap / tcap None asks for
+    the sizes first (capacity 0); short capacities are retried once with the sizes the library reports."""
+    nv, xyz, bgr, tri = _clean_mesh(xyz, bgr, tri)
+    fp, bp, lp = C.POINTER(C.c_float), C.POINTER(C.c_ubyte), C.POINTER(C.c_int64)
+    origin = np.ascontiguousarray(origin, dtype=np.float32).reshape(3)
+    colour = bgr is not None
+    n_v, n_t = C.c_int64(0), C.c_int64(0)
+    vcap, tcap = 0 if vcap is None else int(vcap), 0 if tcap is None else int(tcap)
+    vertex_of, stats = np.zeros(max(nv, 1), np.int32), np.zeros(4, np.int64)
+    for _ in range(2):
+        oxyz, obgr, mem = np.zeros((max(vcap, 1), 3), np.float32), np.zeros((max(vcap, 1), 3), np.uint8), np.zeros(max(vcap, 1), np.int32)
+        otri, tof = np.zeros((max(tcap, 1), 3), np.int32), np.zeros(max(tcap, 1), np.int32)
+        rc = lib().sfmba_mesh_decimate(C.c_int(device), C.c_int64(nv), _opt(xyz, fp), _opt(bgr, bp), C.c_int64(len(tri)), _opt(tri, _ip),
+                                       _p(origin, fp), C.c_float(quantum), C.c_int(cell), C.c_int(placement), C.c_int(reg), _p(oxyz, fp),
+                                       _p(obgr, bp) if colour else None, _p(mem, _ip) if want_members else None, C.c_int64(vcap), _p(otri, _ip),
+                                       _p(tof, _ip) if want_triangle_of else None, C.c_int64(tcap), _p(vertex_of, _ip) if want_vertex_of else None,
+                                       C.byref(n_v), C.byref(n_t), _p(stats, lp) if want_stats else None)
+        if rc != SFMBA_ERR_CAPACITY:
+            break
+        vcap, tcap = int(n_v.value), int(n_t.value)
+    _check(rc)
+    v, t = int(n_v.value), int(n_t.value)
+    return {"xyz": oxyz[:v].copy(), "bgr": obgr[:v].copy() if colour else None, "members": mem[:v].copy() if want_members else None,
+            "tri": otri[:t].copy(), "triangle_of": tof[:t].copy() if want_triangle_of else None,
+            "vertex_of": vertex_of[:nv].copy() if want_vertex_of else None, "stats": [int(x) for x in stats] if want_stats else None}
 
 
 def mesh_texture_size(n_triangles, patch=6, blocks_per_row=1):

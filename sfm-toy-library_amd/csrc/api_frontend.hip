@@ -18,6 +18,8 @@
 #include "match_l2.h"
 #include "mesh_clean.h"
 #include "mesh_clean_math.h"
+#include "mesh_decimate.h"
+#include "decimate_math.h"
 #include "mesh_math.h"
 #include "mesh_colour.h"
 #include "mesh_labels.h"
@@ -976,6 +978,36 @@ int sfmba_mesh_clean(int device, int64_t n_vertices, const float* xyz, const uns
     if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on)
         clean_timing_line("mesh_clean", c.t, n_vertices, n_triangles, (long long)*n_vertices_out, (long long)*n_triangles_out);
     return clean_result(rc, "mesh_clean");
+}
+// ---- decimating a mesh: vertex clustering with quadric placement (SfM::decimateMesh) ----------------------------------------------
+int sfmba_mesh_decimate(int device, int64_t n_vertices, const float* xyz, const unsigned char* bgr, int64_t n_triangles, const int32_t* tri,
+                        const float* origin, float quantum, int cell, int placement, int reg, float* xyz_out, unsigned char* bgr_out, int32_t* members,
+                        int64_t vcap, int32_t* tri_out, int32_t* triangle_of, int64_t tcap, int32_t* vertex_of, int64_t* n_vertices_out,
+                        int64_t* n_triangles_out, int64_t* stats) {
+    const char* who = "mesh_decimate";
+    if (const int rc = clean_check_mesh(who, n_vertices, xyz, true, n_triangles, tri)) return rc;
+    const CleanFilterOut shape{ xyz_out, bgr_out, nullptr, vcap, tri_out, tcap, vertex_of, n_vertices_out, n_triangles_out };
+    if (const int rc = clean_check_out(shape, bgr != nullptr)) return rc;
+    CleanSmoothParams q;                                          // the smooth's rules for origin and quantum
+    if (const int rc = clean_check_smooth(who, origin, quantum, 0, 0.5f, -0.5f, q)) return rc;
+    if (cell < DEC_MIN_CELL || cell > DEC_MAX_CELL) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": cell must be in 32..2^20 quanta");
+    if (placement != 0 && placement != 1) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": placement must be 0 (mean) or 1 (quadric)");
+    if (placement == 1 && (reg < 1 || reg > DEC_MAX_REG)) return fail(SFMBA_ERR_INVALID_ARG, std::string(who) + ": reg must be in 1..2^20");
+    const CleanMesh m{ (int)n_vertices, (int)n_triangles, xyz, bgr, tri };
+    const DecimateParams p{ { q.origin[0], q.origin[1], q.origin[2] }, q.quantum, cell, placement, placement == 1 ? reg : 1 };
+    const DecimateOut out{ xyz_out, bgr_out, members, vcap, tri_out, triangle_of, tcap, vertex_of, n_vertices_out, n_triangles_out, stats };
+    TimedCall<DEC_T_COUNT> c("SFMBA_MESH_DECIMATE_TIMING");      // (tools/mesh_decimate_bench.py)
+    if (const int rc = c.open(device)) return rc;
+    const int rc = mesh_decimate(c.kit.stream, device, m, p, out, c.tm());
+    if ((rc == 0 || rc == UNIT_ERR_CAPACITY) && c.on)
+        std::fprintf(stderr,
+                     "[sfmba mesh_decimate] upload_ms %.6f keys_ms %.6f sort_ms %.6f runs_ms %.6f members_ms %.6f quadrics_ms %.6f solve_ms %.6f "
+                     "map_ms %.6f dedup_ms %.6f compact_ms %.6f emit_ms %.6f download_ms %.6f vertices %lld triangles %lld vertices_out %lld "
+                     "triangles_out %lld\n",
+                     c.t[DEC_T_UPLOAD], c.t[DEC_T_KEYS], c.t[DEC_T_SORT], c.t[DEC_T_RUNS], c.t[DEC_T_MEMBERS], c.t[DEC_T_QUADRICS], c.t[DEC_T_SOLVE],
+                     c.t[DEC_T_MAP], c.t[DEC_T_DEDUP], c.t[DEC_T_COMPACT], c.t[DEC_T_EMIT], c.t[DEC_T_DOWNLOAD], (long long)n_vertices,
+                     (long long)n_triangles, (long long)*n_vertices_out, (long long)*n_triangles_out);
+    return clean_result(rc, who);
 }
 // ---- texturing a mesh: a view per triangle and a texture atlas (SfM::textureMesh) -------------------------------------------------
 int sfmba_mesh_texture_size(int64_t n_triangles, int patch, int blocks_per_row, int32_t* width, int32_t* height) {

@@ -97,6 +97,7 @@ SfM::SfM(const float downscale) :
         mCols(0), mRows(0),
         mMeshOkay(false),
         mCleanOkay(false),
+        mDecimateOkay(false),
         mRunOkay(false),
         mTiming(false) {
     for (double& ms : mStageMs) ms = 0.0;
@@ -215,8 +216,10 @@ void SfM::startRun(size_t n_views) {
     mMergedCloud = MergedCloud();
     mMesh = Mesh();
     mCleanMesh = Mesh();
+    mDecimatedMesh = Mesh();
     mTexturedMesh = TexturedMesh();
     mCleanOkay = false;
+    mDecimateOkay = false;
     mMeshOkay = false;
     mDenseJobs.clear();
     mRunOkay = false;
@@ -435,8 +438,10 @@ ErrorCode SfM::densify(const DenseParams& params) {
     mMergedCloud = MergedCloud();
     mMesh = Mesh();
     mCleanMesh = Mesh();
+    mDecimatedMesh = Mesh();
     mTexturedMesh = TexturedMesh();
     mCleanOkay = false;
+    mDecimateOkay = false;
     mMeshOkay = false;
     mDenseJobs.clear();
     if (mFeaturesGiven || mImages.empty()) {
@@ -625,8 +630,10 @@ bool SfM::saveMergedDenseCloudToPLY(const std::string& prefix) {
 ErrorCode SfM::meshDenseCloud(const MeshParams& params) {
     mMesh = Mesh();
     mCleanMesh = Mesh();
+    mDecimatedMesh = Mesh();
     mTexturedMesh = TexturedMesh();
     mCleanOkay = false;
+    mDecimateOkay = false;
     mMeshOkay = false;
     if (mDenseJobs.empty() || mDepthMaps.size() != mImages.size()) {
         std::cerr << "meshDenseCloud: needs a densify on these images that returned OKAY" << std::endl;
@@ -738,8 +745,10 @@ bool SfM::saveMeshToPLY(const std::string& prefix) {
 
 ErrorCode SfM::cleanMesh(const MeshCleanParams& params) {
     mCleanMesh = Mesh();
+    mDecimatedMesh = Mesh();
     mTexturedMesh = TexturedMesh();
     mCleanOkay = false;
+    mDecimateOkay = false;
     if (!mMeshOkay) {
         std::cerr << "cleanMesh: needs a meshDenseCloud that returned OKAY" << std::endl;
         return ERROR;
@@ -765,9 +774,9 @@ ErrorCode SfM::cleanMesh(const MeshCleanParams& params) {
 
 const Mesh& SfM::getCleanMesh() const { return mCleanMesh; }
 
-bool SfM::saveCleanMeshToPLY(const std::string& prefix) {
-    std::ofstream file(prefix + "_mesh_clean.ply");
-    const Mesh& m = mCleanMesh;
+// a mesh with normals, ASCII: x y z, nx ny nz, red green blue per vertex, then the faces
+static bool writeMeshWithNormalsToPLY(const std::string& path, const Mesh& m) {
+    std::ofstream file(path);
     const bool haveBgr = m.bgr.size() == 3 * m.vertices.size(), haveNormals = m.normals.size() == 3 * m.vertices.size();
     // the header of the mesh file with the normals of the merged cloud's file between the position and the colour
     file << "ply                 " << std::endl
@@ -800,6 +809,43 @@ bool SfM::saveCleanMeshToPLY(const std::string& prefix) {
     return !file.fail();
 }
 
+bool SfM::saveCleanMeshToPLY(const std::string& prefix) { return writeMeshWithNormalsToPLY(prefix + "_mesh_clean.ply", mCleanMesh); }
+
+ErrorCode SfM::decimateMesh(const MeshDecimateParams& params) {
+    mDecimatedMesh = Mesh();
+    mTexturedMesh = TexturedMesh();
+    mDecimateOkay = false;
+    if (!mMeshOkay) {
+        std::cerr << "decimateMesh: needs a meshDenseCloud that returned OKAY" << std::endl;
+        return ERROR;
+    }
+    const Mesh& source = mCleanOkay ? mCleanMesh : mMesh;
+    const bool timing = std::getenv("SFMBA_SFM_TIMING") != nullptr;
+    double ms[1] = { 0.0 };
+    long long stats[4] = { 0, 0, 0, 0 };
+    bool ok = true;
+    Mesh mesh;
+    {
+        StageClock clock(timing ? ms : nullptr, 0);
+        mesh = SfMDenseUtilities::decimateMesh(source, params, &ok, stats);
+    }
+    if (!ok) return ERROR;
+    mDecimatedMesh = mesh;
+    mDecimateOkay = true;
+    say(LOG_INFO, "decimated mesh: " + std::to_string(mDecimatedMesh.vertices.size()) + " of " + std::to_string(source.vertices.size()) + " vertices, " +
+                      std::to_string(mDecimatedMesh.triangles.size() / 3) + " of " + std::to_string(source.triangles.size() / 3) + " triangles (" +
+                      (mCleanOkay ? "the clean mesh" : "the mesh") + "); " + std::to_string(stats[0]) + " clusters, " + std::to_string(stats[1]) +
+                      " triangles collapsed, " + std::to_string(stats[2]) + " duplicates, " + std::to_string(stats[3]) + " clusters took the mean");
+    if (timing)
+        std::fprintf(stderr, "[sfmba sfm mesh_decimate] decimate_ms %.3f vertices %lld triangles %lld\n", ms[0], (long long)mDecimatedMesh.vertices.size(),
+                     (long long)(mDecimatedMesh.triangles.size() / 3));
+    return OKAY;
+}
+
+const Mesh& SfM::getDecimatedMesh() const { return mDecimatedMesh; }
+
+bool SfM::saveDecimatedMeshToPLY(const std::string& prefix) { return writeMeshWithNormalsToPLY(prefix + "_mesh_decimated.ply", mDecimatedMesh); }
+
 ErrorCode SfM::textureMesh(const TextureParams& params) {
     mTexturedMesh = TexturedMesh();
     if (!mMeshOkay) {
@@ -810,7 +856,7 @@ ErrorCode SfM::textureMesh(const TextureParams& params) {
         std::cerr << "textureMesh: occlTolVoxels must be finite and >= 0" << std::endl;
         return ERROR;
     }
-    const Mesh& source = mCleanOkay ? mCleanMesh : mMesh;
+    const Mesh& source = mDecimateOkay ? mDecimatedMesh : mCleanOkay ? mCleanMesh : mMesh;
     const bool timing = std::getenv("SFMBA_SFM_TIMING") != nullptr;
     double ms[1] = { 0.0 };
     bool ok = true;
@@ -822,7 +868,7 @@ ErrorCode SfM::textureMesh(const TextureParams& params) {
     if (!ok) return ERROR;
     mTexturedMesh = textured;
     say(LOG_INFO, "textured mesh: " + std::to_string(mTexturedMesh.textured) + " of " + std::to_string(mTexturedMesh.triangles.size() / 3) +
-                      " triangles have a view (" + (mCleanOkay ? "the clean mesh" : "the mesh") + "), atlas " + std::to_string(mTexturedMesh.atlas.cols) +
+                      " triangles have a view (" + (mDecimateOkay ? "the decimated mesh" : mCleanOkay ? "the clean mesh" : "the mesh") + "), atlas " + std::to_string(mTexturedMesh.atlas.cols) +
                       " x " + std::to_string(mTexturedMesh.atlas.rows));
     if (mTexturedMesh.smoothed) {
         const long long* st = mTexturedMesh.smoothStats;

@@ -87,7 +87,17 @@
 //                 minComponentTriangles == 0 means max(1, triangles / 1000) (integer division).  These defaults, and lambda 0.5 /
 //                 mu -0.53 (Taubin's usual pair) at 10 iterations, are first choices like the ones above: nobody has tuned them.
 //                 The mesh of meshDenseCloud, the dense cloud and the depth maps are not changed.
+//   decimate     decimateMesh(params) after a meshDenseCloud that returned OKAY: ONE sfmba_mesh_decimate call (include/sfmba.h) over the
+//                 clean mesh when cleanMesh has returned OKAY since, otherwise over the mesh: every cell of cellVoxels voxels becomes
+//                 one vertex (the minimiser of the cell's quadric, kept inside the cell, or the rounded mean), and the triangles that
+//                 still span three cells survive, once each; then ONE sfmba_mesh_smooth call with 0 iterations gives the normals.
+//                 THE HOST RULES: origin = the mesh grid's origin; quantum = voxel / 1024 (float); cell = round(cellVoxels * 1024),
+//                 refused outside 32..2^20.  cellVoxels 2, the quadric placement and reg 1024 are first choices that NOBODY HAS
+//                 TUNED.  NOT DONE: no edge-collapse simplification, no topology guarantee (sheets closer than a cell fuse, a few
+//                 non-manifold edges appear), no area weighting, no boundary-preserving quadrics.  The mesh, the clean mesh, the dense
+//                 cloud and the depth maps are not changed; a later meshDenseCloud or cleanMesh clears the decimated mesh.
 //   texture       textureMesh(params) after a meshDenseCloud that returned OKAY: ONE sfmba_mesh_texture call (include/sfmba.h) over
+//                 the decimated mesh when decimateMesh has returned OKAY since, otherwise over
 //                 the clean mesh when cleanMesh has returned OKAY since, otherwise over the mesh, with all images, the poses and the
 //                 depth maps: every triangle takes the view that sees it largest among those that see all three vertices
 //                 unoccluded, and a patch of S (S + 1) / 2 texels in an atlas, filled from that view perspective-correctly; a
@@ -255,8 +265,24 @@ public:
     bool saveCleanMeshToPLY(const std::string& prefix);
 
     /**
+     * Fewer, larger triangles: vertex clustering with the quadric (or the mean) placement and a normal per vertex (the contract is at the
+     * top of this file).  Valid after a meshDenseCloud that returned OKAY; works on the clean mesh when cleanMesh has returned OKAY since,
+     * otherwise on the mesh; cleared by a later meshDenseCloud or cleanMesh, and wherever the mesh is cleared.  With SFMBA_SFM_TIMING set,
+     * one stderr line reports decimate_ms.
+     * @return ERROR (no decimated mesh kept) without such a meshDenseCloud, when cellVoxels * 1024 rounds outside 32..2^20, or when a
+     *         device call fails or refuses (placement outside {0, 1}, reg outside 1..2^20 with the quadric placement).
+     */
+    ErrorCode decimateMesh(const MeshDecimateParams& params = MeshDecimateParams());
+
+    /**
+     * <prefix>_mesh_decimated.ply: the decimated mesh, in the clean mesh's layout.
+     */
+    bool saveDecimatedMeshToPLY(const std::string& prefix);
+
+    /**
      * The photographs on the mesh: a view per triangle and a texture atlas (the contract is at the top of this file).  Valid after a
-     * meshDenseCloud that returned OKAY; works on the clean mesh when cleanMesh has returned OKAY since, otherwise on the mesh; cleared
+     * meshDenseCloud that returned OKAY; works on the decimated mesh when decimateMesh has returned OKAY since, otherwise
+     * on the clean mesh when cleanMesh has returned OKAY since, otherwise on the mesh; cleared
      * wherever those are cleared.  ONE C-ABI call.  With SFMBA_SFM_TIMING set, one stderr line reports texture_ms.
      * @return ERROR (no textured mesh kept) without such a meshDenseCloud, or when the device call fails or refuses (patch outside
      *         3..64, an atlas side above 16384, occlTolVoxels or minAreaPx negative or not finite).
@@ -286,6 +312,7 @@ public:
     const MergedCloud&              getMergedDenseCloud() const { return mMergedCloud; }
     const Mesh&                     getMesh() const;                                  // of the last meshDenseCloud; empty without one
     const Mesh&                     getCleanMesh() const;                             // of the last cleanMesh; empty without one
+    const Mesh&                     getDecimatedMesh() const;                         // of the last decimateMesh; empty without one
     const TexturedMesh&             getTexturedMesh() const;                          // of the last textureMesh; empty without one
 
 private:
@@ -324,9 +351,11 @@ private:
     MergedCloud               mMergedCloud;
     Mesh                      mMesh;
     Mesh                      mCleanMesh;
+    Mesh                      mDecimatedMesh;
     TexturedMesh              mTexturedMesh;
     bool                      mMeshOkay;        // the last meshDenseCloud returned OKAY and nothing was set since
     bool                      mCleanOkay;       // a cleanMesh returned OKAY since that meshDenseCloud
+    bool                      mDecimateOkay;    // a decimateMesh returned OKAY since that meshDenseCloud and since the last cleanMesh
     bool                      mRunOkay;         // the last runSfM returned OKAY and nothing was set since
     bool                      mTiming;           // SFMBA_SFM_TIMING was set when the run began
     double                    mStageMs[T_COUNT]; // wall time per stage of the current run (all zero unless mTiming)

@@ -467,6 +467,45 @@ Mesh SfMDenseUtilities::cleanMesh(const Mesh& mesh, const MeshCleanParams& param
     return out;
 }
 
+Mesh SfMDenseUtilities::decimateMesh(const Mesh& mesh, const MeshDecimateParams& params, bool* ok, long long* stats) {
+    if (ok) *ok = false;
+    std::vector<float> xyz;
+    if (!flattenMesh("decimateMesh", mesh, xyz)) return Mesh();
+    const bool colour = !mesh.bgr.empty();
+    const int64_t nv = (int64_t)mesh.vertices.size(), nt = (int64_t)(mesh.triangles.size() / 3);
+    // the host rules (SfM.h): the quantum is the unit the TSDF already uses, and a cell is given in voxels
+    const float origin[3] = { mesh.grid.origin.x, mesh.grid.origin.y, mesh.grid.origin.z };
+    const float quantum = mesh.grid.voxel / 1024.0f;
+    const double cellQuanta = std::round((double)params.cellVoxels * 1024.0);
+    if (!(cellQuanta >= 32.0 && cellQuanta <= 1048576.0)) {
+        std::fprintf(stderr, "decimateMesh: cellVoxels * 1024 must round to 32..2^20 quanta\n");
+        return Mesh();
+    }
+    const int cell = (int)cellQuanta;
+    int64_t st[4] = { 0, 0, 0, 0 };
+    Mesh out;
+    const bool done = runMeshCall("decimateMesh", colour, mesh.grid, [&](float* oxyz, unsigned char* obgr, int64_t vcap, int32_t* otri, int64_t tcap, int64_t* onv, int64_t* ont) {
+        return sfmba_mesh_decimate(0, nv, xyz.data(), colour ? mesh.bgr.data() : nullptr, nt, mesh.triangles.data(), origin, quantum, cell, params.placement,
+                                   params.reg, oxyz, obgr, nullptr, vcap, otri, nullptr, tcap, nullptr, onv, ont, st);
+    }, out);
+    if (!done) return Mesh();
+    // the normals: the smooth's, with no iteration, on the decimated mesh
+    std::vector<float> oxyz, same, normal;
+    if (!flattenMesh("decimateMesh", out, oxyz)) return Mesh();
+    same.assign(oxyz.size() + 1, 0.0f);
+    normal.assign(oxyz.size() + 1, 0.0f);
+    const int rc = sfmba_mesh_smooth(0, (int64_t)out.vertices.size(), oxyz.data(), (int64_t)(out.triangles.size() / 3), out.triangles.data(), origin, quantum, 0,
+                                     0.5f, -0.53f, same.data(), normal.data());
+    if (rc != SFMBA_OK) {
+        std::fprintf(stderr, "decimateMesh: the normals failed (sfmba rc=%d: %s)\n", rc, sfmba_last_error());
+        return Mesh();
+    }
+    out.normals.assign(normal.begin(), normal.begin() + 3 * out.vertices.size());
+    if (stats) for (int i = 0; i < 4; ++i) stats[i] = (long long)st[i];
+    if (ok) *ok = true;
+    return out;
+}
+
 TexturedMesh SfMDenseUtilities::textureMesh(const Mesh& mesh, const std::vector<cv::Mat>& images, const Intrinsics& intrinsics,
                                             const std::vector<cv::Matx34f>& poses, const std::vector<cv::Mat>& depthMaps, const TextureParams& params,
                                             bool* ok) {

@@ -114,6 +114,17 @@ struct MeshCleanParams {
     MeshCleanParams() : minComponentTriangles(0), keepLargest(false), smoothIterations(10), lambda(0.5f), mu(-0.53f) {}
 };
 
+// SfMDenseUtilities::decimateMesh / SfM::decimateMesh: the size of a cell and where its representative goes (include/sfmba.h,
+// sfmba_mesh_decimate; the host rules are at the top of SfM.h).  Two voxels a cell, the quadric placement and reg 1024 are first choices;
+// NOBODY HAS TUNED THEM.
+struct MeshDecimateParams {
+    enum { MEAN = 0, QUADRIC = 1 };
+    float cellVoxels;       // the edge of a cell in voxels of the mesh's grid; cell = round(cellVoxels * 1024) quanta must lie in 32..2^20
+    int   placement;        // MEAN: the rounded mean of a cell's vertices; QUADRIC: the minimiser of the cell's quadric, kept inside the cell
+    int   reg;              // 1..2^20, read with QUADRIC only: pulls towards the mean with weight reg / 2^20 relative to a unit normal
+    MeshDecimateParams() : cellVoxels(2.0f), placement(QUADRIC), reg(1024) {}
+};
+
 // SfMDenseUtilities::textureMesh / SfM::textureMesh: the size of a triangle's patch and which views count (include/sfmba.h,
 // sfmba_mesh_texture; the host rules are at the top of SfM.h).  First choices; NOBODY HAS TUNED THEM.
 // SMOOTHING THE VIEW LABELS IS OFF BY DEFAULT: with smoothRings = 0 and smoothPasses = 0 the call is the plain sfmba_mesh_texture call and
@@ -255,6 +266,19 @@ public:
      * @param ok  if not null, receives false when the device call fails or refuses an argument (the mesh is then empty).
      */
     static Mesh cleanMesh(const Mesh& mesh, const MeshCleanParams& params, bool* ok = nullptr);
+
+    /**
+     * The mesh with every cell of params.cellVoxels voxels collapsed to one vertex (vertex clustering; the mean or the quadric
+     * placement) and the triangles that still span three cells, without duplicates: ONE sfmba_mesh_decimate call (two when the first
+     * reports the sizes) in integers of mesh.grid.voxel / 1024 about mesh.grid.origin, then ONE sfmba_mesh_smooth call with 0 iterations
+     * on the result for its normals (NOT area weighted).  The grid is carried over; `filled` is not.  NO TOPOLOGY GUARANTEE: sheets closer
+     * than a cell fuse and a few non-manifold edges appear.
+     * @param ok     if not null, receives false when cell = round(cellVoxels * 1024) lies outside 32..2^20 or a device call fails or
+     *               refuses an argument (the mesh is then empty).
+     * @param stats  if not null, receives the call's four statistics: clusters, collapsed triangles, duplicates dropped, clusters that
+     *               the quadric placement left to the mean.
+     */
+    static Mesh decimateMesh(const Mesh& mesh, const MeshDecimateParams& params, bool* ok = nullptr, long long* stats = nullptr);
 
     /**
      * A view per triangle and a texture atlas with one patch per triangle: ONE sfmba_mesh_texture call, or, when params.smoothRings or

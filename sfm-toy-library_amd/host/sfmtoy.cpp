@@ -2,7 +2,8 @@
 // directory, run the pipeline on the MI355X (-M flow: with the optical-flow matcher), write <prefix>_points.ply and <prefix>_cameras.ply -- and, with -D, densify and write
 // <prefix>_dense.ply; with --voxel on top of -D, merge that cloud and write <prefix>_dense_merged.ply; with --mesh on top of -D, mesh
 // the depth maps and write <prefix>_mesh.ply (--mesh-fill N: with the grid's holes filled by N passes first); with --mesh-clean on top of --mesh, drop the mesh's small components, smooth it and write
-// <prefix>_mesh_clean.ply; with --texture on top of --mesh, put the photographs on the mesh (the clean one with --mesh-clean) and write
+// <prefix>_mesh_clean.ply; with --mesh-decimate on top of --mesh, cluster the vertices of the mesh (the clean one with --mesh-clean) into cells and
+// write <prefix>_mesh_decimated.ply; with --texture on top of --mesh, put the photographs on the mesh (the decimated one with --mesh-decimate, else the clean one with --mesh-clean) and write
 // <prefix>_textured.obj, .mtl and .png (--texture-smooth: with the views of neighbouring triangles chosen together; --texture-level: with the colours levelled across the seams).  The arguments are parsed here
 // (no boost).  Exit status: 0 when runSfM returned OKAY and the files were written, 1 on ERROR, 2 on a usage error.
 #include <cctype>
@@ -49,6 +50,11 @@ void usage(std::ostream& os, const char* program) {
        << "                               mesh's triangles, at least 1)\n"
        << "      --mesh-keep-largest      with --mesh-clean: keep only the component with the most triangles\n"
        << "      --mesh-smooth ITERS      with --mesh-clean: smoothing iterations, 0..100 (default 10)\n"
+       << "      --mesh-decimate [C]      with --mesh: also collapse every cell of C voxels (default 2; C * 1024 must round to 32..1048576) of the\n"
+       << "                               mesh (the clean one with --mesh-clean) to one vertex, placed by the cell's quadric, and write\n"
+       << "                               PREFIX_mesh_decimated.ply with a normal per vertex; --texture then works on this mesh; first choices\n"
+       << "                               that nobody has tuned; NO TOPOLOGY GUARANTEE; the other files are as without it\n"
+       << "      --mesh-decimate-mean     with --mesh-decimate: place a cell's vertex at the rounded mean of its vertices instead\n"
        << "      --texture [S]            with --mesh: also choose a view per triangle, fill a texture atlas with a patch of S (S + 1) / 2 texels\n"
        << "                               per triangle (S in 3..64, default 6) and write PREFIX_textured.obj, .mtl and .png (the clean mesh\n"
        << "                               with --mesh-clean); NO COLOUR ADJUSTMENT ACROSS VIEWS unless --texture-level asks for it; the other\n"
@@ -89,12 +95,12 @@ int main(int argc, char** argv) {
     double downscale = 1.0, level = LOG_INFO, ignored = 0.0, merge = 20.0, window = 0.0, voxel = 0.0, resolution = 256.0,
            min_component = 0.0, smooth = 10.0, fill = 0.0, fill_neighbours = 2.0, patch = 6.0, sgm_p1 = 8.0, sgm_p2 = 64.0, sgm_paths = 8.0,
            sgm_uniqueness = 5.0, smooth_rings = 4.0, smooth_penalty = 256.0, smooth_passes = 100.0, level_passes = 16.0, level_weight = 16.0,
-           level_radius = 1.0;
+           level_radius = 1.0, decimate_cell = 2.0;
     FeatureType features = FEATURES_ORB;
     MatcherType matcher = MATCHER_DESCRIPTORS;
     bool have_directory = false, dense = false, merged = false, meshed = false, cleaned = false, clean_option = false, keep_largest = false,
          filled = false, fill_option = false, textured = false, sgm = false, sgm_option = false, texture_smooth = false, smooth_option = false, texture_level = false,
-         level_option = false;
+         level_option = false, decimated = false, decimate_mean = false;
     for (int i = 1; i < argc; ++i) {
         bool missing = false, bad = false;
         const std::string arg = argv[i];
@@ -102,6 +108,20 @@ int main(int argc, char** argv) {
         if (arg == "-D" || arg == "--dense") { dense = true; continue; }
         if (arg == "--mesh-clean") { cleaned = true; continue; }
         if (arg == "--mesh-keep-largest") { keep_largest = clean_option = true; continue; }
+        if (arg == "--mesh-decimate-mean") { decimate_mean = true; continue; }
+        if (arg == "--mesh-decimate" || arg.compare(0, 16, "--mesh-decimate=") == 0) {
+            // the value is optional: "--mesh-decimate=C", or a next argument made of digits and a point only
+            decimated = true;
+            text = arg.size() > 16 ? arg.substr(16) : "";
+            if (arg == "--mesh-decimate" && i + 1 < argc && argv[i + 1][0] != '\0' && std::string(argv[i + 1]).find_first_not_of("0123456789.") == std::string::npos)
+                text = argv[++i];
+            else if (arg == "--mesh-decimate")
+                continue;
+            if (!number(text, decimate_cell) || !(decimate_cell * 1024.0 >= 31.5) || !(decimate_cell * 1024.0 < 1048576.5)) {
+                std::cerr << argv[0] << ": --mesh-decimate has a value that cannot be used\n"; usage(std::cerr, argv[0]); return 2;
+            }
+            continue;
+        }
         if (arg == "--texture" || arg.compare(0, 10, "--texture=") == 0) {
             // the value is optional: "--texture=S", or a next argument made of digits only
             textured = true;
@@ -235,6 +255,8 @@ int main(int argc, char** argv) {
     if (fill_option && !filled) { std::cerr << argv[0] << ": --mesh-fill-neighbours needs --mesh-fill\n"; usage(std::cerr, argv[0]); return 2; }
     if (cleaned && !meshed) { std::cerr << argv[0] << ": --mesh-clean needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
     if (clean_option && !cleaned) { std::cerr << argv[0] << ": --mesh-min-component, --mesh-keep-largest and --mesh-smooth need --mesh-clean\n"; usage(std::cerr, argv[0]); return 2; }
+    if (decimated && !meshed) { std::cerr << argv[0] << ": --mesh-decimate needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
+    if (decimate_mean && !decimated) { std::cerr << argv[0] << ": --mesh-decimate-mean needs --mesh-decimate\n"; usage(std::cerr, argv[0]); return 2; }
     if (textured && !meshed) { std::cerr << argv[0] << ": --texture needs --mesh\n"; usage(std::cerr, argv[0]); return 2; }
     if (texture_smooth && !textured) { std::cerr << argv[0] << ": --texture-smooth needs --texture\n"; usage(std::cerr, argv[0]); return 2; }
     if (smooth_option && !texture_smooth) { std::cerr << argv[0] << ": --texture-smooth-passes needs --texture-smooth\n"; usage(std::cerr, argv[0]); return 2; }
@@ -278,6 +300,13 @@ int main(int argc, char** argv) {
             clean.smoothIterations = (int)smooth;
             if (sfm.cleanMesh(clean) != OKAY) return 1;
             if (!sfm.saveCleanMeshToPLY(prefix)) return 1;
+        }
+        if (decimated) {
+            MeshDecimateParams decimate;
+            decimate.cellVoxels = (float)decimate_cell;
+            if (decimate_mean) decimate.placement = MeshDecimateParams::MEAN;
+            if (sfm.decimateMesh(decimate) != OKAY) return 1;
+            if (!sfm.saveDecimatedMeshToPLY(prefix)) return 1;
         }
         if (textured) {
             TextureParams texture;

@@ -1192,6 +1192,134 @@ int sfmba_shim_run_sfm_texture(int what, int n_views, int channels, const int64_
     return 0;
 }
 
+// setImages, runSfM, densify(), meshDenseCloud() with its defaults, textureMesh({patch}) on the mesh, decimateMesh({cell_voxels, placement,
+// reg}) on the mesh, textureMesh({patch}) again, now on the decimated mesh, cleanMesh() with its defaults and decimateMesh again, now on
+// the clean mesh, in one call (tests/test_gpu_mesh_decimate_pipeline.py).  Back come the poses [n_views][12], K [9], has_map [n_views],
+// the depth maps of ALL views in view order (zeros where a view has none), the grid the class chose (grid [8]: origin, voxel, trunc,
+// dims), four meshes under the capacities cap_vertices and cap_triangles -- k = 0 the mesh, 1 the clean mesh, 2 the decimated mesh, 3 the
+// decimated clean mesh: counts [2 k .. 2 k + 1], xyz / bgr / normal at k cap_vertices rows, tri at k cap_triangles rows (the mesh has no
+// normals: zeros) -- and the two textured meshes as sfmba_shim_run_sfm_texture returns them, k = 0 on the mesh and k = 1 on the decimated
+// mesh.  *unchanged = 1 iff the mesh, the clean mesh, the dense cloud and every depth map equal, byte for byte, the copies taken when
+// they were made.  ply_prefix != NULL: saveDecimatedMeshToPLY after the first decimateMesh.  what == 1: no run at all, only decimateMesh
+// on a fresh object with images (it has to refuse; no device involved).  Returns runSfM's code, 10 + densify's code, 20 +
+// meshDenseCloud's code, 30 + cleanMesh's code, 50 + textureMesh's code, 60 + decimateMesh's code (160 + it if a refusing call left a
+// decimated mesh behind), 150 if decimateMesh left the textured mesh standing, 170 if cleanMesh left the decimated mesh standing, -2 if
+// a capacity is too small, -3 if a file could not be written.
+extern "C" __attribute__((visibility("default")))
+int sfmba_shim_run_sfm_mesh_decimate(int what, int n_views, int channels, const int64_t* img_ptr, const unsigned char* px, const int32_t* w,
+                                     const int32_t* h, int debug_level, float cell_voxels, int placement, int reg, int patch, const char* ply_prefix,
+                                     float* poses, float* K, unsigned char* has_map, float* depth, float* grid, int* unchanged, int64_t cap_vertices,
+                                     int64_t cap_triangles, int64_t* counts, float* xyz, unsigned char* bgr, float* normal, int32_t* tri,
+                                     int64_t cap_atlas, int32_t* atlas_wh, unsigned char* atlas, float* uv, int32_t* view, int64_t* textured,
+                                     int* same_source) {
+    using namespace sfmtoylib;
+    SfM sfm(1.0f);
+    sfm.setConsoleDebugLevel((unsigned)debug_level);
+    std::vector<cv::Mat> images;
+    for (int i = 0; i < n_views; ++i) images.push_back(buildImage(w[i], h[i], channels, px + img_ptr[i]));
+    sfm.setImages(images);
+    *unchanged = 0;
+    for (int k = 0; k < 8; ++k) counts[k] = 0;
+    MeshDecimateParams params;
+    params.cellVoxels = cell_voxels; params.placement = placement; params.reg = reg;
+    TextureParams texture;
+    texture.patch = patch;
+    const auto left_behind = [&]() { return !sfm.getDecimatedMesh().vertices.empty() || !sfm.getDecimatedMesh().triangles.empty(); };
+    const auto texture_left = [&]() { return !sfm.getTexturedMesh().atlas.empty() || !sfm.getTexturedMesh().triangles.empty(); };
+    ErrorCode code;
+    if (what == 1) {
+        code = sfm.decimateMesh(params);
+        return (code == OKAY || left_behind() ? 160 : 60) + (int)code;
+    }
+    if ((code = sfm.runSfM()) != OKAY) return (int)code;
+    for (int v = 0; v < n_views; ++v)
+        for (int e = 0; e < 12; ++e) poses[12 * v + e] = sfm.getCameraPoses()[v].val[e];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) K[3 * r + c] = sfm.getIntrinsics().K.at<float>(r, c);
+    if ((code = sfm.densify()) != OKAY) return 10 + (int)code;
+    if ((code = sfm.meshDenseCloud()) != OKAY) return 20 + (int)code;
+    const auto same_mesh = [](const Mesh& a, const Mesh& b) {
+        bool same = a.vertices.size() == b.vertices.size() && a.bgr == b.bgr && a.triangles == b.triangles && a.normals.size() == b.normals.size();
+        for (size_t i = 0; same && i < a.vertices.size(); ++i) same = std::memcmp(&a.vertices[i], &b.vertices[i], sizeof(cv::Point3f)) == 0;
+        return same && (a.normals.empty() || std::memcmp(a.normals.data(), b.normals.data(), a.normals.size() * sizeof(float)) == 0);
+    };
+    const auto put_mesh = [&](int k, const Mesh& m) {
+        const int64_t nv = (int64_t)m.vertices.size(), nt = (int64_t)(m.triangles.size() / 3);
+        counts[2 * k] = nv; counts[2 * k + 1] = nt;
+        if (nv > cap_vertices || nt > cap_triangles || m.bgr.size() != 3 * m.vertices.size() || (!m.normals.empty() && m.normals.size() != 3 * m.vertices.size()))
+            return false;
+        float* X = xyz + (size_t)k * (size_t)cap_vertices * 3;
+        float* N = normal + (size_t)k * (size_t)cap_vertices * 3;
+        unsigned char* C = bgr + (size_t)k * (size_t)cap_vertices * 3;
+        for (size_t i = 0; i < m.vertices.size(); ++i) {
+            X[3 * i] = m.vertices[i].x; X[3 * i + 1] = m.vertices[i].y; X[3 * i + 2] = m.vertices[i].z;
+            for (int q = 0; q < 3; ++q) { C[3 * i + q] = m.bgr[3 * i + q]; N[3 * i + q] = m.normals.empty() ? 0.0f : m.normals[3 * i + q]; }
+        }
+        std::memcpy(tri + (size_t)k * (size_t)cap_triangles * 3, m.triangles.data(), m.triangles.size() * sizeof(int32_t));
+        return true;
+    };
+    const auto put_textured = [&](int k, const Mesh& source) {
+        const TexturedMesh& t = sfm.getTexturedMesh();
+        const int64_t bytes = (int64_t)t.atlas.rows * t.atlas.cols * 3, nt = (int64_t)(t.triangles.size() / 3);
+        if (bytes > cap_atlas || nt > cap_triangles || (int64_t)t.uv.size() != 6 * nt || (int64_t)t.view.size() != nt) return false;
+        atlas_wh[2 * k] = t.atlas.cols; atlas_wh[2 * k + 1] = t.atlas.rows;
+        std::memcpy(atlas + (size_t)k * (size_t)cap_atlas, t.atlas.ptr<unsigned char>(0), (size_t)bytes);
+        std::memcpy(uv + (size_t)k * (size_t)cap_triangles * 6, t.uv.data(), t.uv.size() * sizeof(float));
+        std::memcpy(view + (size_t)k * (size_t)cap_triangles, t.view.data(), t.view.size() * sizeof(int32_t));
+        textured[k] = (int64_t)t.textured;
+        bool same = t.triangles == source.triangles && t.vertices.size() == source.vertices.size();
+        for (size_t i = 0; same && i < t.vertices.size(); ++i) same = std::memcmp(&t.vertices[i], &source.vertices[i], sizeof(cv::Point3f)) == 0;
+        same_source[k] = same ? 1 : 0;
+        return true;
+    };
+    const Mesh meshBefore = sfm.getMesh();
+    const DenseCloud cloudBefore = sfm.getDenseCloud();
+    std::vector<std::vector<float> > mapsBefore;             // a view without a map: empty
+    for (const cv::Mat& m : sfm.getDepthMaps())
+        mapsBefore.push_back(m.empty() ? std::vector<float>() : std::vector<float>(m.ptr<float>(0), m.ptr<float>(0) + (size_t)m.rows * m.cols));
+    const MeshGrid& g = meshBefore.grid;
+    grid[0] = g.origin.x; grid[1] = g.origin.y; grid[2] = g.origin.z; grid[3] = g.voxel; grid[4] = g.trunc;
+    grid[5] = (float)g.nx; grid[6] = (float)g.ny; grid[7] = (float)g.nz;
+    // without decimateMesh: the texture of the mesh
+    code = sfm.textureMesh(texture);
+    if (code != OKAY) return 50 + (int)code;
+    if (!put_textured(0, sfm.getMesh())) return -2;
+    // on the mesh
+    code = sfm.decimateMesh(params);
+    if (code != OKAY) return (left_behind() ? 160 : 60) + (int)code;
+    if (texture_left()) return 150;                          // decimateMesh clears what was made from the mesh before it
+    if (!put_mesh(2, sfm.getDecimatedMesh())) return -2;
+    if (ply_prefix && !sfm.saveDecimatedMeshToPLY(ply_prefix)) return -3;
+    code = sfm.textureMesh(texture);
+    if (code != OKAY) return 50 + (int)code;
+    if (!put_textured(1, sfm.getDecimatedMesh())) return -2;
+    // on the clean mesh
+    if ((code = sfm.cleanMesh()) != OKAY) return 30 + (int)code;
+    if (left_behind()) return 170;                           // cleanMesh clears the decimated mesh
+    const Mesh cleanBefore = sfm.getCleanMesh();
+    code = sfm.decimateMesh(params);
+    if (code != OKAY) return (left_behind() ? 160 : 60) + (int)code;
+    if (!put_mesh(3, sfm.getDecimatedMesh())) return -2;
+    // nothing else moved
+    const DenseCloud& cloud = sfm.getDenseCloud();
+    bool same = same_mesh(sfm.getMesh(), meshBefore) && same_mesh(sfm.getCleanMesh(), cleanBefore) && cloud.points.size() == cloudBefore.points.size() &&
+                cloud.bgr == cloudBefore.bgr && sfm.getDepthMaps().size() == mapsBefore.size();
+    for (size_t i = 0; same && i < cloud.points.size(); ++i) same = std::memcmp(&cloud.points[i], &cloudBefore.points[i], sizeof(cv::Point3f)) == 0;
+    size_t at = 0;
+    for (int v = 0; v < n_views; ++v) {
+        const size_t n = (size_t)w[v] * h[v];
+        const cv::Mat& m = sfm.getDepthMaps()[(size_t)v];
+        has_map[v] = m.empty() ? 0 : 1;
+        if (m.empty()) std::memset(depth + at, 0, n * sizeof(float));
+        else std::memcpy(depth + at, m.ptr<float>(0), n * sizeof(float));
+        same = same && (m.empty() ? mapsBefore[(size_t)v].empty()
+                                  : mapsBefore[(size_t)v].size() == n && std::memcmp(m.ptr<float>(0), mapsBefore[(size_t)v].data(), n * sizeof(float)) == 0);
+        at += n;
+    }
+    *unchanged = same ? 1 : 0;
+    if (!put_mesh(0, meshBefore) || !put_mesh(1, cleanBefore)) return -2;
+    return 0;
+}
+
 // SfM::densify() where it has to refuse (tests/test_depth_oracle_cpu.py; no device involved): what = 0 after setFeatures (there are
 // no pixels), 1 on images without a run, 2 on a fresh object.  Returns densify's code.
 extern "C" __attribute__((visibility("default")))
