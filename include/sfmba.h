@@ -408,6 +408,37 @@ SFMBA_API int sfmba_dense_spd_solve(int device, int n, const double* A, const do
 enum { SFMBA_PCG_PROBE_SYMMETRIC = 1, SFMBA_PCG_PROBE_F32_MATRIX = 2, SFMBA_PCG_PROBE_SEGMENTS = 4, SFMBA_PCG_PROBE_POISON = 8 };
 SFMBA_API int sfmba_dense_pcg_probe(int device, int n, const double* A, int nrhs, const double* B, const double* Wt, int flags, double tol,
                                     const int* max_iters, double* X, int* info, int* iters, sfmba_step_probe* path);
+/* The distributed CG of the sharded forms (SFMBA_FAMILY_DIST_BLOCKS / SFMBA_FAMILY_DIST_ROWS) in isolation, every rank of a world of `world`
+ * ranks simulated in THIS process on one device (a kernel-level hook for parity tests, like the one above; no communicator, no RCCL).
+ * A [n*n] as above with n = 6 ncam + 1, B [nrhs][n] solved one after another on the same workspaces, Wt [8][n] as above or NULL.  The call
+ * goes through the library's own transform, then gives every simulated rank k a workspace of its own (the library's partition of the block
+ * rows, its own x, flags and info word) and that rank's chunk of the reduce-scatter layout: the upper off-diagonal 6 x 6 blocks of the
+ * transformed matrix for the block rows rows[k] .. rows[k + 1].  Focal row, b~ and W~ are the buffers the sharded loop passes.  Every rank is
+ * driven by the library's own set-up and iteration entry points; the all-reduce they call is an in-place sum over the ranks' buffers, added in
+ * rank order, so every rank receives identical bits.
+ *   flags     SFMBA_DCG_PROBE_F32     blocks AND focal row in fp32, together, as the sharded loop pairs them; only where the reduced matrix
+ *                                     is stored in fp32 (n > 1280), SFMBA_ERR_INVALID_ARG elsewhere.  (The product kernels are also
+ *                                     instantiated for fp32 blocks with an fp64 focal row and the reverse: no caller pairs them so, the
+ *                                     mixed pairs are not reachable and not tested.)
+ *             SFMBA_DCG_PROBE_POISON  NaN in the padding of every rank's chunk behind its last block, in columns >= n of the transformed
+ *                                     matrix, of W~ and of b~: the kernels promise not to read these
+ *   tol       plain relative residual |r~| <= tol |b~| (not anchored)
+ *   max_iters [nrhs], each in 1 .. 1000: solve i is ended after max_iters[i] iteration launches at the latest (the done flag is then set
+ *             as a converging launch sets it) and Xt[i] is the iterate it reached
+ *   surplus   >= 0: that many further iteration launches per solve behind its end, each with its collective, as the fixed batches of the
+ *             sharded loop issue them; they must change nothing
+ *   Xt        [nrhs][n] rank 0's solution in the TRANSFORMED unknowns (x~ = Lb^T x)
+ *   info      as sfmba_dense_spd_solve (the transform's, else rank 0's breakdown word); iters [nrhs] or NULL: iterations per solve
+ *   rows      [world + 1] or NULL, chunk_blocks or NULL: the partition of the block rows and the blocks per chunk the library chose
+ *   replicas_differ   or NULL: before every collective and at the end of every solve each rank's x, p, r (both parities), scalar state,
+ *             thresholds, flags and info word are compared bit for bit with rank 0's on the device; 0, or the number of the first such
+ *             check (counted from 1 over the whole call) that found a difference.
+ * world outside 1 .. 16, n % 6 != 1, a max_iters entry outside 1 .. 1000 and unknown flags are SFMBA_ERR_INVALID_ARG before the device is
+ * looked at. */
+enum { SFMBA_DCG_PROBE_F32 = 1, SFMBA_DCG_PROBE_POISON = 2 };
+SFMBA_API int sfmba_dist_cg_probe(int device, int n, const double* A, int world, int nrhs, const double* B, const double* Wt, int flags, double tol,
+                                  const int* max_iters, int surplus, double* Xt, int* info, int* iters, int* rows, long long* chunk_blocks,
+                                  int* replicas_differ);
 
 /*
  * Sharded API (multi-GPU): every rank holds the observations of a disjoint set of points

@@ -25,7 +25,7 @@ SYMBOLS = [
     "sfmba_problem_create", "sfmba_problem_reset", "sfmba_problem_set_params", "sfmba_problem_solve",
     "sfmba_problem_get_params", "sfmba_problem_destroy", "sfmba_problem_stream", "sfmba_problem_reduced_dim",
     "sfmba_problem_eval_residuals", "sfmba_problem_eval_jacobian", "sfmba_problem_build_reduced",
-    "sfmba_dense_spd_solve", "sfmba_dense_pcg_probe", "sfmba_shard_begin", "sfmba_shard_reduce_len", "sfmba_shard_reduce_buf",
+    "sfmba_dense_spd_solve", "sfmba_dense_pcg_probe", "sfmba_dist_cg_probe", "sfmba_shard_begin", "sfmba_shard_reduce_len", "sfmba_shard_reduce_buf",
     "sfmba_shard_scalars_buf", "sfmba_shard_partial_build", "sfmba_shard_solve_update", "sfmba_shard_finish",
     "sfmba_shard_end", "sfmba_problem_set_profiling", "sfmba_problem_get_profile",
     "sfmba_problem_create_sharded", "sfmba_shard_setup_finish", "sfmba_shard_setup_len", "sfmba_shard_setup_buf", "sfmba_release_cache", "sfmba_triangulate",
@@ -1643,6 +1643,32 @@ def dense_pcg_probe(A, B, Wt=None, flags=0, tol=1e-10, max_iters=200, device=0):
     out = {k: int(getattr(path, k)) for k, _ in _StepProbe._fields_}
     out["family_name"] = FAMILIES[out["family"]] if 0 <= out["family"] < len(FAMILIES) else str(out["family"])
     return X, info.value, iters.copy(), out
+
+
+DCG_PROBE_F32, DCG_PROBE_POISON = 1, 2
+
+
+def dist_cg_probe(A, world, B, Wt=None, flags=0, tol=1e-10, max_iters=200, surplus=0, device=0):
+    """sfmba_dist_cg_probe: the distributed CG on A [n, n], n = 6 ncam + 1, with every rank of a world of `world` ranks simulated in this process,
+    for the right-hand sides B [nrhs, n] (or [n]) one after another.  Wt: None or [8, n] coarse vectors in the transformed unknowns; flags:
+    DCG_PROBE_*; max_iters: one int or one per right-hand side; surplus: further launches behind the end of every solve.
+    Returns a dict: Xt [nrhs, n] (rank 0's solution in the TRANSFORMED unknowns), info, iters [nrhs], rows [world + 1], chunk_blocks,
+    replicas_differ (0, or the number of the first check at which a rank's replicated state differed from rank 0's)."""
+    A = _d(A)
+    B = np.ascontiguousarray(np.atleast_2d(np.asarray(B, dtype=np.float64)))
+    nrhs, n = B.shape
+    if A.shape != (n, n) or (Wt is not None and np.shape(Wt) != (8, n)):
+        raise ValueError("A, B and Wt do not fit together")
+    W = None if Wt is None else np.ascontiguousarray(Wt, dtype=np.float64)
+    mi = _i(np.broadcast_to(np.asarray(max_iters, dtype=np.int32), (nrhs,)))
+    Xt = np.zeros((nrhs, n))
+    info, differ, chunk = C.c_int(0), C.c_int(0), C.c_longlong(0)
+    iters, rows = np.zeros(nrhs, dtype=np.int32), np.zeros(max(int(world), 0) + 1, dtype=np.int32)
+    _check(lib().sfmba_dist_cg_probe(C.c_int(device), C.c_int(n), _p(A, _dp), C.c_int(world), C.c_int(nrhs), _p(B, _dp), None if W is None else _p(W, _dp),
+                                     C.c_int(flags), C.c_double(tol), _p(mi, _ip), C.c_int(surplus), _p(Xt, _dp), C.byref(info), _p(iters, _ip),
+                                     _p(rows, _ip), C.byref(chunk), C.byref(differ)))
+    return {"Xt": Xt, "info": info.value, "iters": iters.copy(), "rows": [int(r) for r in rows], "chunk_blocks": int(chunk.value),
+            "replicas_differ": differ.value}
 
 
 class Problem:

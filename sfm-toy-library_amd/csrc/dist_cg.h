@@ -18,7 +18,6 @@ struct DistCg {
     long long chunk_blocks = 0;          // blocks per rank in the reduce-scatter layout (the largest range, the others padded)
     std::vector<int> rows;               // [world + 1] partition of the block rows
     int* d_row_shift = nullptr;          // [ncam] block offset to ADD to a block's upper-triangle list position (pair pass -> reduce-scatter layout)
-    double *qa = nullptr, *qb = nullptr; // [ld] row part / transposed part of the partial product
     double* qred = nullptr;              // [9 * ld] the all-reduce buffer: partial products (one per CG iteration; eight at the coarse setup)
     double *x = nullptr, *r = nullptr, *p = nullptr;   // [ld] each ([2][ld] for r: by launch parity), replicated (x: the caller's buffer -- DenseSolver::vec, where k_cam_update looks)
     double* AW = nullptr;                // [8][ld] S~ W~
@@ -54,5 +53,19 @@ int  dcg_begin(hipStream_t s, DistCg* g, const DcgSolveArgs& a, dcg_allreduce_fn
 // n iterations: product from the owned blocks, all-reduce of the partial vector, replicated update.  Iterations behind the converging one
 // return at once -- and still take part in their collective, so that every rank issues the same sequence.
 int  dcg_iterate(hipStream_t s, DistCg* g, const DcgSolveArgs& a, int n, dcg_allreduce_fn ar, void* ctx);
+
+// Test hook (sfmba_dist_cg_probe): every rank of a world as a DistCg of its own in ONE process, driven by dcg_begin / dcg_iterate above with a
+// callback that meets the other ranks and sums their buffers.
+constexpr int DCG_PROBE_MAX_WORLD = 16;
+// g's chunk of the reduce-scatter layout (36 chunk_blocks values, fp64 or fp32) from the transformed matrix F (d rows of ld, the same type);
+// the padding behind the rank's last block is zero, or NaN with `poison`
+void dcg_probe_fill_owned(hipStream_t s, const DistCg& g, const void* F, bool f32, void* owned, bool poison);
+// in place: every bufs[k][0 .. n) becomes the sum over k = 0 .. world - 1, added in that order
+void dcg_probe_allreduce(hipStream_t s, int world, double* const* bufs, long long n);
+// *first_diff (device, zero before the first call) becomes `tag` if it is still zero and any rank's x, p, r (both parities), scalar state,
+// scal, flags or info word differs in a bit from rank 0's
+void dcg_probe_compare(hipStream_t s, int world, const DistCg* ranks, int* const* flags, int* const* info, int tag, int* first_diff);
+// ends a solve that has not ended itself after `launched` launches (PF_DONE as k_dcg_upd leaves it): the launches behind are surplus launches
+void dcg_probe_stop(hipStream_t s, int* flags, int launched);
 
 }  // namespace sfmba

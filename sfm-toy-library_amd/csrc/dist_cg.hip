@@ -16,8 +16,6 @@ constexpr int STEP_T = 1024;
 
 __device__ __forceinline__ long long first_of_row(int I, int ncam) { return (long long)I * ncam - (long long)I * (I + 1) / 2; }   // off-diagonal upper blocks before row I
 
-template <typename FT> __device__ __forceinline__ double ld_val(const FT* p, size_t i) { return (double)p[i]; }
-
 // N block-wide sums (every thread returns all of them); sh: >= 16 * N doubles
 template <int N>
 __device__ __forceinline__ void block_sums_all(double (&v)[N], double* sh) {
@@ -32,87 +30,6 @@ __device__ __forceinline__ void block_sums_all(double (&v)[N], double* sh) {
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < N; ++k) { double s = 0.0; for (int i = 0; i < nw; ++i) s += sh[i * N + k]; v[k] = s; }
-}
-
-// Partial product from the OWNED blocks (rows [row0, row1) of the upper triangle, in list order behind `owned`):
-//   role A, one workgroup per owned row I:      qa[6 I + r]  = sum_{J > I} sum_c B_IJ[r][c] p[6 J + c]
-//   role B, one workgroup per column J > row0:  qb[6 J + c]  = sum_{I in [row0, min(row1, J))} sum_r B_IJ[r][c] p[6 I + r]
-template <typename FT>
-__global__ __launch_bounds__(256) void k_dcg_spmv(int ncam, int row0, int row1, const FT* __restrict__ owned, const double* __restrict__ p,
-                                                  double* __restrict__ qa, double* __restrict__ qb, const int* __restrict__ flags) {
-    if (flags && flags[PF_DONE]) return;
-    __shared__ double sh[4 * 6];
-    const int nA = row1 - row0;
-    const bool roleA = (int)blockIdx.x < nA;
-    const long long base = first_of_row(row0, ncam);
-    double acc[6] = { 0, 0, 0, 0, 0, 0 };
-    if (roleA) {
-        const int I = row0 + blockIdx.x;
-        const long long rowpos = first_of_row(I, ncam) - base;
-        for (int J = I + 1 + threadIdx.x; J < ncam; J += blockDim.x) {
-            const FT* B = owned + (size_t)(rowpos + (J - I - 1)) * 36;
-            double pj[6];
-#pragma unroll
-            for (int c = 0; c < 6; ++c) pj[c] = p[6 * J + c];
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = 0; c < 6; ++c) acc[r] = fma(ld_val(B, 6 * r + c), pj[c], acc[r]);
-        }
-    } else {
-        const int J = row0 + 1 + ((int)blockIdx.x - nA);
-        const int iend = row1 < J ? row1 : J;
-        for (int I = row0 + threadIdx.x; I < iend; I += blockDim.x) {
-            const FT* B = owned + (size_t)(first_of_row(I, ncam) - base + (J - I - 1)) * 36;
-            double pi[6];
-#pragma unroll
-            for (int r = 0; r < 6; ++r) pi[r] = p[6 * I + r];
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = 0; c < 6; ++c) acc[c] = fma(ld_val(B, 6 * r + c), pi[r], acc[c]);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) acc[k] = wave_allsum(acc[k]);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) sh[w * 6 + k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const double s = sh[threadIdx.x] + sh[6 + threadIdx.x] + sh[12 + threadIdx.x] + sh[18 + threadIdx.x];
-        if (roleA) qa[6 * (row0 + blockIdx.x) + threadIdx.x] = s;
-        else qb[6 * (row0 + 1 + ((int)blockIdx.x - nA)) + threadIdx.x] = s;
-    }
-}
-
-// the rank's partial product as it goes into the all-reduce: owned-block parts + (rank 0 only) what is known everywhere: the identity
-// diagonal blocks and the focal row / column of S~
-template <typename FF>
-__global__ __launch_bounds__(STEP_T) void k_dcg_comb(int d, int ncam, int row0, int row1, int rank, const double* __restrict__ qa, const double* __restrict__ qb,
-                                                      const double* __restrict__ p, const FF* __restrict__ focal_row, double* __restrict__ out,
-                                                      const int* __restrict__ flags) {
-    if (flags && flags[PF_DONE]) return;
-    __shared__ double sh[16];
-    const int fo = d - 1;
-    double fdot[1] = { 0.0 };
-    if (rank == 0) { for (int i = threadIdx.x; i < fo; i += blockDim.x) fdot[0] += (double)focal_row[i] * p[i]; }
-    block_sums_all<1>(fdot, sh);
-    const double pf = p[fo];
-    for (int i = threadIdx.x; i < d; i += blockDim.x) {
-        const int cam = i / 6;
-        double v = 0.0;
-        if (i < fo) {
-            if (cam >= row0 && cam < row1) v += qa[i];
-            if (cam > row0) v += qb[i];
-            if (rank == 0) v += p[i] + (double)focal_row[i] * pf;
-        } else if (rank == 0) {
-            v = pf + fdot[0];
-        }
-        out[i] = v;
-    }
 }
 
 // 8 x 8 symmetric E -> E^-1 by Gauss-Jordan with a pivot test (dependent gauge vectors -- fewer cameras than gauge freedoms -- drop out)
@@ -272,10 +189,11 @@ __global__ __launch_bounds__(STEP_T) void k_dcg_step(int d, int ld, const double
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The multi-workgroup form (round 5): TWO launches and ONE all-reduce per CG iteration, none of them a single
-// workgroup.  k_dcg_init / k_dcg_step / k_dcg_comb above -- one workgroup over the whole vector, two or three dependent block
-// reductions each: 120 / 19 / 8 us at d = 6001 -- are what sank the distributed forms of round 4; they stay for the implicit product.
+// workgroup.  k_dcg_init / k_dcg_step above -- one workgroup over the whole vector, two or three dependent block reductions each:
+// 120 / 19 us at d = 6001 (and a combine launch of 8 us between them, gone with the block product it served) -- are what sank the
+// distributed forms of round 4; they stay for the implicit product, which forms whole vectors in launches of its own.
 //   k_dcg_prod   a WAVE per camera c: row part (blocks (c, J), J > c, if the rank owns row c) and transposed part (blocks (I, c) of the
-//                owned rows I < c) of the rank's partial product, straight into the all-reduce buffer (no qa / qb, no combine launch);
+//                owned rows I < c) of the rank's partial product, straight into the all-reduce buffer (no staging vectors, no combine launch);
 //                per workgroup the partial dot products p . out and W~^T out -- LINEAR in the partial product, so they ride through
 //                the same all-reduce and arrive summed over the ranks
 //   all-reduce   q (ld doubles) | the partial dots (16 doubles per product workgroup)
@@ -714,7 +632,6 @@ int dcg_create(DistCg* g, int d, int ld, int ncam, int rank, int world, DeviceAr
     }
     // all or nothing: a workspace that fails half way leaves nothing behind in *g (the arena keeps the bytes until the problem goes)
     int* d_row_shift = arena->alloc_n<int>(shift.size());
-    double* qa = arena->alloc_n<double>((size_t)ld); double* qb = arena->alloc_n<double>((size_t)ld);
     // all-reduce buffer: [8][ld] S~ W~ (set-up) | [ld] the iteration's product | the partial dots of the product workgroups behind either
     g->np = (ncam + CPW - 1) / CPW + 1;
     const size_t qred_len = (size_t)9 * ld + (size_t)g->np * LIN8_STRIDE;
@@ -722,26 +639,15 @@ int dcg_create(DistCg* g, int d, int ld, int ncam, int rank, int world, DeviceAr
     double* r = arena->alloc_n<double>((size_t)2 * ld); double* pp = arena->alloc_n<double>((size_t)ld);
     double* scal = arena->alloc_n<double>(128);
     double* state = arena->alloc_n<double>((size_t)2 * ST_LEN);
-    if (!d_row_shift || !qa || !qb || !qred || !r || !pp || !scal || !state) return -1;
+    if (!d_row_shift || !qred || !r || !pp || !scal || !state) return -1;
     if (hipMemcpy(d_row_shift, shift.data(), sizeof(int) * shift.size(), hipMemcpyHostToDevice) != hipSuccess) return -1;
     // the collectives carry ld doubles per vector, the kernels write d of them: the padding is zero once and for all
     if (hipMemset(qred, 0, sizeof(double) * qred_len) != hipSuccess) return -1;
     if (hipMemset(state, 0, sizeof(double) * 2 * ST_LEN) != hipSuccess) return -1;
-    g->d_row_shift = d_row_shift; g->qa = qa; g->qb = qb; g->qred = qred; g->r = r; g->p = pp; g->scal = scal; g->state = state;
+    g->d_row_shift = d_row_shift; g->qred = qred; g->r = r; g->p = pp; g->scal = scal; g->state = state;
     g->AW = g->qred;                  // slots 0..7 of the all-reduce buffer ARE S~ W~ after the setup; slot 8 carries the iterations' products
     g->ready = true;
     return 0;
-}
-
-static void launch_product(hipStream_t s, const DistCg* g, const DcgSolveArgs& a, const double* p, double* out, const int* flags) {
-    if (a.implicit) { launch_implicit_product(s, *a.implicit, p, out, flags); return; }
-    const int nA = g->row1 - g->row0, nB = std::max(0, g->ncam - g->row0 - 1);
-    if (nA + nB > 0) {
-        if (a.owned_f32) hipLaunchKernelGGL(k_dcg_spmv<float>, dim3(nA + nB), dim3(256), 0, s, g->ncam, g->row0, g->row1, static_cast<const float*>(a.owned), p, g->qa, g->qb, flags);
-        else hipLaunchKernelGGL(k_dcg_spmv<double>, dim3(nA + nB), dim3(256), 0, s, g->ncam, g->row0, g->row1, static_cast<const double*>(a.owned), p, g->qa, g->qb, flags);
-    }
-    if (a.focal_row32) hipLaunchKernelGGL(k_dcg_comb<float>, dim3(1), dim3(STEP_T), 0, s, g->d, g->ncam, g->row0, g->row1, g->rank, g->qa, g->qb, p, a.focal_row32, out, flags);
-    else hipLaunchKernelGGL(k_dcg_comb<double>, dim3(1), dim3(STEP_T), 0, s, g->d, g->ncam, g->row0, g->row1, g->rank, g->qa, g->qb, p, a.focal_row, out, flags);
 }
 
 static int upd_grid(int d) { return std::max(1, std::min(UPD_MAXWG, (d + 255) / 256)); }
@@ -751,7 +657,7 @@ int dcg_begin(hipStream_t s, DistCg* g, const DcgSolveArgs& a, dcg_allreduce_fn 
     if (a.implicit) {
         // the implicit product forms whole vectors in launches of its own: the single-workgroup update kernels of round 4
         if (a.W) {
-            for (int k = 0; k < NW; ++k) launch_product(s, g, a, a.W + (size_t)k * g->ld, g->qred + (size_t)k * g->ld, nullptr);
+            for (int k = 0; k < NW; ++k) launch_implicit_product(s, *a.implicit, a.W + (size_t)k * g->ld, g->qred + (size_t)k * g->ld, nullptr);
             if (ar) { const int rc = ar(ctx, g->qred, (long long)NW * g->ld, s); if (rc) return rc; }
         }
         hipLaunchKernelGGL(k_dcg_init, dim3(1), dim3(STEP_T), 0, s, g->d, g->ld, a.bt, a.W, g->AW, g->x, g->r, g->p, g->scal, a.flags, a.anchor, a.cap);
@@ -775,7 +681,7 @@ int dcg_iterate(hipStream_t s, DistCg* g, const DcgSolveArgs& a, int n, dcg_allr
     double* q = g->qred + (size_t)NW * g->ld;
     if (a.implicit) {
         for (int it = 0; it < n; ++it) {
-            launch_product(s, g, a, g->p, q, a.flags);
+            launch_implicit_product(s, *a.implicit, g->p, q, a.flags);
             if (ar) { const int rc = ar(ctx, q, (long long)g->ld, s); if (rc) return rc; }
             hipLaunchKernelGGL(k_dcg_step, dim3(1), dim3(STEP_T), 0, s, g->d, g->ld, q, a.W, g->x, g->r, g->p, g->scal, a.flags, a.tol * a.tol, a.info);
         }
@@ -797,5 +703,91 @@ int dcg_iterate(hipStream_t s, DistCg* g, const DcgSolveArgs& a, int n, dcg_allr
     }
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Test hook (sfmba_dist_cg_probe, dist_cg.h): the pieces that let every rank of a world live in one process on one device.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct ProbeBufs { double* b[DCG_PROBE_MAX_WORLD]; };
+struct ProbeVecs { const unsigned long long* v[DCG_PROBE_MAX_WORLD][5]; const int* flags[DCG_PROBE_MAX_WORLD]; const int* info[DCG_PROBE_MAX_WORLD]; };
+
+// rank's chunk of the reduce-scatter layout from the transformed matrix F (d rows of ld): blockIdx.y < nrows: the blocks of row row0 + blockIdx.y;
+// blockIdx.y == nrows: the padding behind the rank's last block (zero, or NaN: the kernels promise not to read it)
+template <typename FT>
+__global__ __launch_bounds__(256) void k_dcg_probe_fill(int ld, int ncam, int row0, int row1, long long chunk_blocks, const FT* __restrict__ F,
+                                                         FT* __restrict__ owned, int poison) {
+    const int nrows = row1 - row0;
+    const long long base = first_of_row(row0, ncam), mine = first_of_row(row1, ncam) - base;
+    if ((int)blockIdx.y == nrows) {
+        const FT pad = poison ? (FT)__builtin_nan("") : (FT)0;
+        for (long long i = 36 * mine + (long long)blockIdx.x * 256 + threadIdx.x; i < 36 * chunk_blocks; i += (long long)gridDim.x * 256) owned[i] = pad;
+        return;
+    }
+    const int I = row0 + blockIdx.y;
+    const long long rowpos = first_of_row(I, ncam) - base;
+    const int n = 36 * (ncam - 1 - I);
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) {
+        const int blk = t / 36, e = t - 36 * blk, J = I + 1 + blk;
+        owned[(size_t)(rowpos + blk) * 36 + e] = F[(size_t)(6 * I + e / 6) * ld + 6 * J + e % 6];
+    }
+}
+
+// the all-reduce: every rank's buffer becomes the sum over the ranks, added in rank order (identical bits everywhere)
+__global__ __launch_bounds__(256) void k_dcg_probe_sum(ProbeBufs B, int world, long long n) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double s = B.b[0][i];
+    for (int k = 1; k < world; ++k) s += B.b[k][i];
+    for (int k = 0; k < world; ++k) B.b[k][i] = s;
+}
+
+// what is replicated, bit for bit against rank 0: x, p, both r buffers, the scalar state of both parities, scal, the flags, the info word
+__global__ __launch_bounds__(256) void k_dcg_probe_compare(ProbeVecs V, int world, int ld, int tag, int* __restrict__ first_diff) {
+    const int len[5] = { ld, ld, 2 * ld, 2 * ST_LEN, 128 };
+    bool differ = false;
+    for (int seg = 0; seg < 5; ++seg)
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < len[seg]; i += gridDim.x * 256) {
+            const unsigned long long ref = V.v[0][seg][i];
+            for (int k = 1; k < world; ++k) differ |= V.v[k][seg][i] != ref;
+        }
+    if (blockIdx.x == 0 && threadIdx.x < 5) {
+        for (int k = 1; k < world; ++k)
+            differ |= threadIdx.x < 4 ? V.flags[k][threadIdx.x] != V.flags[0][threadIdx.x] : V.info[k][0] != V.info[0][0];
+    }
+    if (differ) atomicCAS(first_diff, 0, tag);
+}
+
+// a solve stopped by its iteration cap: what k_dcg_upd writes when it ends one, so that the launches behind it are surplus launches
+__global__ void k_dcg_probe_stop(int* __restrict__ flags, int launched) { if (flags[PF_DONE] == 0) flags[PF_DONE] = launched + 1; }
+
+}  // namespace
+
+void dcg_probe_fill_owned(hipStream_t s, const DistCg& g, const void* F, bool f32, void* owned, bool poison) {
+    const dim3 grid((unsigned)std::max(1, std::min(64, (36 * std::max(g.ncam - 1, 1) + 255) / 256)), (unsigned)(g.row1 - g.row0 + 1));
+    if (f32) hipLaunchKernelGGL(k_dcg_probe_fill<float>, grid, dim3(256), 0, s, g.ld, g.ncam, g.row0, g.row1, g.chunk_blocks, static_cast<const float*>(F),
+                                static_cast<float*>(owned), poison ? 1 : 0);
+    else hipLaunchKernelGGL(k_dcg_probe_fill<double>, grid, dim3(256), 0, s, g.ld, g.ncam, g.row0, g.row1, g.chunk_blocks, static_cast<const double*>(F),
+                            static_cast<double*>(owned), poison ? 1 : 0);
+}
+
+void dcg_probe_allreduce(hipStream_t s, int world, double* const* bufs, long long n) {
+    ProbeBufs B;
+    for (int k = 0; k < DCG_PROBE_MAX_WORLD; ++k) B.b[k] = k < world ? bufs[k] : nullptr;
+    hipLaunchKernelGGL(k_dcg_probe_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, B, world, n);
+}
+
+void dcg_probe_compare(hipStream_t s, int world, const DistCg* ranks, int* const* flags, int* const* info, int tag, int* first_diff) {
+    ProbeVecs V;
+    for (int k = 0; k < DCG_PROBE_MAX_WORLD; ++k) {
+        const DistCg& g = ranks[k < world ? k : 0];
+        const double* v[5] = { g.x, g.p, g.r, g.state, g.scal };
+        for (int j = 0; j < 5; ++j) V.v[k][j] = reinterpret_cast<const unsigned long long*>(v[j]);
+        V.flags[k] = flags[k < world ? k : 0]; V.info[k] = info[k < world ? k : 0];
+    }
+    hipLaunchKernelGGL(k_dcg_probe_compare, dim3(16), dim3(256), 0, s, V, world, ranks[0].ld, tag, first_diff);
+}
+
+void dcg_probe_stop(hipStream_t s, int* flags, int launched) { hipLaunchKernelGGL(k_dcg_probe_stop, dim3(1), dim3(1), 0, s, flags, launched); }
 
 }  // namespace sfmba

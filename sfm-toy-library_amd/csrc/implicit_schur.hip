@@ -16,7 +16,7 @@ namespace sfmba {
 //                 s_i = sum_obs w (through the wave's LDS) -> spt[i]
 //   k_imp_cams    camera-major, one workgroup per chunk of a camera's observations (the chunks of k_cam_diag_f): e = C (s_i - w),
 //                 h = P^T e, sums of X_g x h and h over the camera's observations -> acc[j] (six values per camera)
-//   k_imp_out     per camera: q~_j = -Linv D [Q^T a; b] (+ on rank 0 the identity / focal part, as k_dcg_comb adds it)
+//   k_imp_out     per camera: q~_j = -Linv D [Q^T a; b] (+ on rank 0 the identity / focal part, as k_dcg_prod adds it, dist_cg.hip)
 // Every observation is evaluated twice per product, with the expressions of k_point_update; C = (P R) L~ in the precision of the
 // Jacobian blocks.  Pairs of observations of ONE camera on a point (duplicates) live in the diagonal blocks: a problem that has them
 // does not take this path (the caller checks ds.ndupwg).

@@ -5,6 +5,10 @@
 // There is NO CPU fallback in this library: without a HIP device every entry point returns SFMBA_ERR_NO_DEVICE.
 #include "lm_loop.h"
 #include "pcg_common.h"
+#include <condition_variable>
+#include <functional>
+#include <mutex>
+#include <thread>
 
 using namespace sfmba;
 
@@ -460,6 +464,168 @@ int sfmba_dense_pcg_probe(int device, int n, const double* A, int nrhs, const do
     int hinfo = 0;
     HIP_TRY(hipMemcpy(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost));
     if (info) *info = hinfo;
+    return SFMBA_OK;
+}
+
+int sfmba_dist_cg_probe(int device, int n, const double* A, int world, int nrhs, const double* B, const double* Wt, int flags, double tol,
+                        const int* max_iters, int surplus, double* Xt, int* info, int* iters, int* rows, long long* chunk_blocks, int* replicas_differ) {
+    constexpr int known = SFMBA_DCG_PROBE_F32 | SFMBA_DCG_PROBE_POISON;
+    if (n <= 0 || n % 6 != 1 || nrhs <= 0 || !A || !B || !Xt || !max_iters || !(tol > 0.0) || (flags & ~known) || surplus < 0 || surplus > 1000)
+        return fail(SFMBA_ERR_INVALID_ARG, "bad arguments");
+    if (world < 1 || world > DCG_PROBE_MAX_WORLD) return fail(SFMBA_ERR_INVALID_ARG, "world must lie in 1 .. 16");
+    for (int i = 0; i < nrhs; ++i)
+        if (max_iters[i] <= 0 || max_iters[i] > 1000) return fail(SFMBA_ERR_INVALID_ARG, "max_iters must lie in 1 .. 1000");
+    int rc = check_device(device);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const int ld = dense_padded_dim(n), ncam = (n - 1) / 6;
+    const bool poison = (flags & SFMBA_DCG_PROBE_POISON) != 0;
+    double *dA = nullptr, *db_ = nullptr, *dx = nullptr;
+    int *dinfo = nullptr, *dwords = nullptr, *dfirst = nullptr;
+    void* downed = nullptr;
+    DeviceTemps tmp(&dA, &db_, &dx, &dinfo, &dwords, &dfirst, &downed);
+    HIP_TRY(dev_alloc(&dA, (size_t)n * ld));
+    HIP_TRY(hipMemset(dA, 0, sizeof(double) * (size_t)n * ld));
+    HIP_TRY(hipMemcpy2D(dA, sizeof(double) * (size_t)ld, A, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n, (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(dev_alloc(&db_, (size_t)ld));
+    HIP_TRY(dev_alloc(&dinfo, 1));
+    HIP_TRY(hipMemset(dinfo, 0, sizeof(int)));
+    DenseSolver ws;
+    if (dense_solver_create(&ws, n, ld)) return fail(SFMBA_ERR_ALLOC, "dense solver workspace allocation failed");
+    hipStream_t s = nullptr;
+    DeviceArena arena(device);          // the ranks' workspaces (dcg_create); goes back to the cache with the call
+    struct Guard { DenseSolver* ws; hipStream_t* s; ~Guard() { if (*s) { (void)hipStreamSynchronize(*s); (void)hipStreamDestroy(*s); } dense_solver_destroy(ws); } } guard{ &ws, &s };
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    if (dense_pcg_ensure_workspace(&ws)) return fail(SFMBA_ERR_ALLOC, dense_pcg_error(PCG_ERR_ALLOC));
+    // blocks and focal row in fp32 together, as the sharded loop pairs them (sharded_solve.hip: da.owned_f32 / da.focal_row32) -- only where the size stores fp32
+    const bool f32 = (flags & SFMBA_DCG_PROBE_F32) != 0;
+    if (f32 && dense_pcg_want_f32(&ws) == nullptr) return fail(SFMBA_ERR_INVALID_ARG, "SFMBA_DCG_PROBE_F32: the reduced matrix is not stored in fp32 at this size");
+    ws.use_f32 = f32;
+
+    // every simulated rank: a DistCg, x, flags, an info word and its chunk of the reduce-scatter layout
+    std::vector<DistCg> ranks((size_t)world);
+    std::vector<int*> rflags((size_t)world), rinfo((size_t)world);
+    std::vector<char*> owned((size_t)world);
+    for (int k = 0; k < world; ++k)
+        if (dcg_create(&ranks[(size_t)k], n, ld, ncam, k, world, &arena)) return fail(SFMBA_ERR_ALLOC, "distributed CG workspace allocation failed");
+    const size_t chunk_bytes = (size_t)dcg_chunk_values(ranks[0]) * (f32 ? 4 : 8);
+    HIP_TRY(dev_alloc(&dx, (size_t)world * ld));
+    HIP_TRY(hipMemset(dx, 0, sizeof(double) * (size_t)world * ld));
+    HIP_TRY(dev_alloc(&dwords, (size_t)world * 8));
+    HIP_TRY(hipMemset(dwords, 0, sizeof(int) * (size_t)world * 8));
+    HIP_TRY(hipMalloc(&downed, chunk_bytes * (size_t)world));
+    for (int k = 0; k < world; ++k) {
+        ranks[(size_t)k].x = dx + (size_t)k * ld;
+        rflags[(size_t)k] = dwords + (size_t)k * 8; rinfo[(size_t)k] = dwords + (size_t)k * 8 + 4;
+        owned[(size_t)k] = static_cast<char*>(downed) + (size_t)k * chunk_bytes;
+    }
+    HIP_TRY(dev_alloc(&dfirst, 1));          // the number of the first check of the replicas that found a difference
+    HIP_TRY(hipMemset(dfirst, 0, sizeof(int)));
+    if (rows) for (int k = 0; k <= world; ++k) rows[k] = ranks[0].rows[(size_t)k];
+    if (chunk_blocks) *chunk_blocks = ranks[0].chunk_blocks;
+
+    // lockstep: one host thread per rank on ONE stream; the ranks meet inside the all-reduce callback, where the last to arrive enqueues the check of the
+    // replicas and the sum (every rank's launches in front of its collective are in the stream by then), and at the end of every batch
+    struct Lockstep {
+        std::mutex m; std::condition_variable cv; int world = 1, waiting = 0; long gen = 0;
+        void meet(const std::function<void()>& last) {
+            std::unique_lock<std::mutex> lk(m);
+            if (++waiting == world) { last(); waiting = 0; ++gen; cv.notify_all(); }
+            else { const long g = gen; cv.wait(lk, [&] { return gen != g; }); }
+        }
+    } step;
+    step.world = world;
+    struct Shared { Lockstep* step; int world; const DistCg* ranks; int* const* flags; int* const* info; int* first; int checks; double* bufs[DCG_PROBE_MAX_WORLD]; } sh{
+        &step, world, ranks.data(), rflags.data(), rinfo.data(), dfirst, 0, {} };
+    struct RankCtx { Shared* sh; int rank; };
+    auto ar = [](void* c, void* buf, long long len, hipStream_t st) -> int {
+        RankCtx* r = static_cast<RankCtx*>(c);
+        Shared* q = r->sh;
+        { std::lock_guard<std::mutex> lk(q->step->m); q->bufs[r->rank] = static_cast<double*>(buf); }
+        q->step->meet([&] {
+            dcg_probe_compare(st, q->world, q->ranks, q->flags, q->info, ++q->checks, q->first);
+            dcg_probe_allreduce(st, q->world, q->bufs, len);
+        });
+        return 0;
+    };
+
+    for (int i = 0; i < nrhs; ++i) {
+        HIP_TRY(hipMemsetAsync(db_, 0, sizeof(double) * (size_t)ld, s));
+        HIP_TRY(hipMemcpyAsync(db_, B + (size_t)i * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(ws.W, 0, sizeof(double) * ((size_t)PCG_NW * ld + pcg_tile_slack(n, ld)), s));
+        if (Wt) HIP_TRY(hipMemcpy2DAsync(ws.W, sizeof(double) * (size_t)ld, Wt, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n, PCG_NW, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(pcg_btilde(&ws), 0, sizeof(double) * (size_t)ld, s));
+        if (dense_pcg_transform(s, &ws, dA, db_, dinfo)) return fail(SFMBA_ERR_ALLOC, dense_pcg_error(PCG_ERR_ALLOC));
+        if (poison) {
+            dense_pcg_poison(s, &ws, false);
+            const std::vector<double> nan((size_t)(ld - n), __builtin_nan(""));
+            HIP_TRY(hipMemcpyAsync(pcg_btilde(&ws) + n, nan.data(), sizeof(double) * nan.size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));       // (the host vector goes out of scope)
+        }
+        const void* F = f32 ? static_cast<const void*>(ws.Sfull32) : static_cast<const void*>(ws.Sfull);
+        for (int k = 0; k < world; ++k) dcg_probe_fill_owned(s, ranks[(size_t)k], F, f32, owned[(size_t)k], poison);
+        if ((rc = launches_ok())) return rc;
+
+        // what the sharded loop passes (sharded_solve.hip): the rank's chunk, row d - 1 of the CG's matrix, b~, W~; plain relative stopping rule
+        std::vector<DcgSolveArgs> args((size_t)world);
+        std::vector<RankCtx> ctx((size_t)world);
+        for (int k = 0; k < world; ++k) {
+            DcgSolveArgs& da = args[(size_t)k];
+            da.owned = owned[(size_t)k]; da.owned_f32 = f32;
+            if (f32) da.focal_row32 = ws.Sfull32 + (size_t)(n - 1) * ld; else da.focal_row = ws.Sfull + (size_t)(n - 1) * ld;
+            da.bt = pcg_btilde(&ws); da.W = Wt ? ws.W : nullptr;
+            da.flags = rflags[(size_t)k]; da.info = rinfo[(size_t)k]; da.tol = tol; da.anchor = 0; da.cap = 1.0;
+            ctx[(size_t)k] = RankCtx{ &sh, k };
+        }
+        const int cap = max_iters[i];
+        int launched = 0, failed = 0;            // (written by the last rank to arrive, under the lock)
+        bool ended = false;
+        auto run_rank = [&](int k) {
+            (void)hipSetDevice(device);
+            DistCg* g = &ranks[(size_t)k];
+            // (the callback never fails, so neither do dcg_begin / dcg_iterate: every rank makes the same sequence of calls and meetings)
+            int lrc = dcg_begin(s, g, args[(size_t)k], ar, &ctx[(size_t)k]);
+            bool sync_failed = false;
+            for (;;) {
+                // a batch, then the verdict of rank 0's flags for everybody (the replicas are held to it by the check)
+                const int batch = std::min(24, cap - launched);
+                if (!lrc && batch > 0) lrc = dcg_iterate(s, g, args[(size_t)k], batch, ar, &ctx[(size_t)k]);
+                bool stop = false;
+                step.meet([&] {
+                    launched += batch;
+                    int h[4] = { 0, 0, 0, 0 };
+                    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(h, rflags[0], sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) failed = 1;
+                    ended = failed || h[PF_DONE] != 0 || launched >= cap;
+                    if (ended && !failed) for (int j = 0; j < world; ++j) dcg_probe_stop(s, rflags[(size_t)j], launched);
+                });
+                { std::lock_guard<std::mutex> lk(step.m); stop = ended; sync_failed = failed != 0; }      // (both as the meeting left them: the same on every rank)
+                if (stop) break;
+            }
+            // surplus launches: each issues its collective, as the fixed batch of the sharded loop does
+            if (!sync_failed && surplus > 0) lrc = dcg_iterate(s, g, args[(size_t)k], surplus, ar, &ctx[(size_t)k]);
+            if (lrc || hipGetLastError() != hipSuccess) { std::lock_guard<std::mutex> lk(step.m); failed = 1; }      // (a refused launch is this thread's error)
+        };
+        {
+            std::vector<std::thread> threads;
+            for (int k = 1; k < world; ++k) threads.emplace_back(run_rank, k);
+            run_rank(0);
+            for (std::thread& t : threads) t.join();
+        }
+        dcg_probe_compare(s, world, ranks.data(), rflags.data(), rinfo.data(), ++sh.checks, dfirst);
+        if ((rc = launches_ok())) return rc;
+        HIP_TRY(hipStreamSynchronize(s));
+        if (failed) return fail(SFMBA_ERR_HIP, "distributed CG probe: a rank's launches failed");
+        HIP_TRY(hipMemcpy(Xt + (size_t)i * n, ranks[0].x, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        int h[4] = { 0, 0, 0, 0 };
+        HIP_TRY(hipMemcpy(h, rflags[0], sizeof(h), hipMemcpyDeviceToHost));
+        if (iters) iters[i] = h[PF_ITERS];
+    }
+    int hinfo = 0, hrank = 0, hfirst = 0;
+    HIP_TRY(hipMemcpy(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&hrank, rinfo[0], sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&hfirst, dfirst, sizeof(int), hipMemcpyDeviceToHost));
+    if (info) *info = hinfo ? hinfo : hrank;
+    if (replicas_differ) *replicas_differ = hfirst;
     return SFMBA_OK;
 }
 }  // extern "C"

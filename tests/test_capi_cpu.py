@@ -88,6 +88,31 @@ def test_dense_pcg_probe_refuses_bad_arguments(capi):
         capi.dense_pcg_probe(A, np.ones(6), max_iters=5)
 
 
+def test_dist_cg_probe_refuses_bad_arguments(capi):
+    """Refused before the device is looked at: a world outside 1 .. 16, a dimension that is not 6 ncam + 1, an iteration cap outside 1 .. 1000,
+    unknown flags, a negative surplus, a tolerance that is not positive."""
+    A, b = np.eye(7), np.ones(7)
+    for bad in (0, -1, 17):
+        with pytest.raises(capi.SfmbaError, match="world must lie in 1 .. 16"):
+            capi.dist_cg_probe(A, bad, b, max_iters=5)
+    for n in (6, 8, 12):
+        with pytest.raises(capi.SfmbaError, match="bad arguments"):
+            capi.dist_cg_probe(np.eye(n), 2, np.ones(n), max_iters=5)
+    for bad in (0, -1, 1001):
+        with pytest.raises(capi.SfmbaError, match="max_iters must lie in 1 .. 1000"):
+            capi.dist_cg_probe(A, 2, b, max_iters=bad)
+    with pytest.raises(capi.SfmbaError, match="max_iters must lie in 1 .. 1000"):
+        capi.dist_cg_probe(A, 2, np.ones((3, 7)), max_iters=[5, 0, 5])
+    for kw in (dict(flags=4), dict(flags=-1), dict(surplus=-1), dict(tol=0.0), dict(tol=float("nan"))):
+        with pytest.raises(capi.SfmbaError, match="bad arguments"):
+            capi.dist_cg_probe(A, 2, b, max_iters=5, **kw)
+    with pytest.raises(ValueError):
+        capi.dist_cg_probe(A, 2, np.ones(6), max_iters=5)
+    if capi.device_count() == 0:
+        with pytest.raises(capi.SfmbaError, match="no HIP device"):
+            capi.dist_cg_probe(A, 2, b, max_iters=5)
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "sfm-toy-library_amd")
     for dirpath, _, files in os.walk(pkg):
